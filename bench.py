@@ -4,6 +4,12 @@
     python bench.py [--gpus N --steps K --warmup W]      (N > 1 from a plain shell: starts the N ranks itself)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
+    python bench.py --full                               (also the unsettled, sustained, one-stream and host-to-device
+                                                          figures, the roofline passes and the CPU baseline)
+    python bench.py --dump-outputs DIR                   (rank 0's last timed step as DIR/<name>.npy)
+
+A plain run sets up, settles and warms up, times K steps and prints the headline figure; everything else it can measure
+sits behind --full.
 
 One "step" = one pass of the whole hot path over one batch of synthetic frames resident in HBM:
 per GPU 32 frames (640x640x3 uint8) -> YOLOv8n-seg detect + NMS + mask logits -> for the 8 best detections
@@ -86,6 +92,44 @@ def group_launches(recs, nprof, precision):
     return res
 
 
+DUMP_LIMIT_BYTES = 64_000_000
+
+
+def dump_outputs(step_out, out_dir, limit=DUMP_LIMIT_BYTES):
+    """--dump-outputs: what one step hands a caller of Pipeline.run (ids, scores, n_det, boxes, crops, z and the detector's
+    tensors as det_<name>) written as out_dir/<name>.npy, floating point as float32 (float64 kept), integers as float64
+    (exact).  Every array gets an equal share of what the smaller ones leave of `limit`; one larger than its share keeps a
+    fixed, seeded sample of its rows (sorted), listed in out_dir/<name>_rows.npy.  Returns {name: shape written}."""
+    flat = {}
+    for k, v in step_out.items():
+        if isinstance(v, dict):
+            flat.update({f"{k}_{kk}": vv for kk, vv in v.items() if vv is not None})
+        elif v is not None:
+            flat[k] = v
+    host = {}
+    for k, t in flat.items():
+        x = t.detach().cpu().numpy() if isinstance(t, torch.Tensor) else np.asarray(t)
+        host[k] = x.astype(np.float64 if x.dtype == np.float64 or (x.dtype.kind in "iu" and x.dtype.itemsize > 2) else np.float32)
+    os.makedirs(out_dir, exist_ok=True)
+    left, written = limit - 2 * 128 * len(host), {}  # (an .npy header is 128 bytes)
+    order = sorted(host, key=lambda k: (host[k].nbytes, k))
+    for i, k in enumerate(order):
+        x = host[k]
+        share = left // (len(order) - i)
+        if x.nbytes > share:
+            # rows along the first axis; single elements where even one row would take half the share
+            rows = x.reshape(len(x), -1) if x.ndim > 1 and x[0].nbytes * 2 <= share else x.reshape(-1, 1)
+            n = min(len(rows), max(1, share // (rows[0].nbytes + 8)))
+            sel = np.sort(np.random.default_rng(0).choice(len(rows), n, replace=False))
+            x = x[sel] if len(rows) == len(x) else x.reshape(-1)[sel]
+            np.save(os.path.join(out_dir, f"{k}_rows.npy"), sel.astype(np.float64))
+            left -= sel.size * 8
+        np.save(os.path.join(out_dir, f"{k}.npy"), x)
+        left -= x.nbytes
+        written[k] = tuple(x.shape)
+    return written
+
+
 def parse():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -115,6 +159,12 @@ def parse():
     ap.add_argument("--sustained-seconds", type=float, default=2.0, help="config.sustained_value: the same step loop run for at least this "
                     "long after the timed region (0: skip)")
     ap.add_argument("--no-h2d", action="store_true", help="skip config.with_h2d_value (frames arriving in pinned host memory)")
+    ap.add_argument("--full", action="store_true", help="besides `value`: config.unsettled_value, the sustained, one-stream and "
+                    "host-to-device figures, the roofline passes and the CPU baseline (each still subject to its --no-* switch "
+                    "above); a plain run times the K steps of `value` only")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="after the timed steps, write what rank 0's last timed "
+                    "step returned (ids, scores, boxes, crops, embeddings, detector tensors) as DIR/<name>.npy, float32 / float64, "
+                    "at most 64 MB in all (larger arrays as a seeded sample of rows)")
     return ap.parse_args()
 
 
@@ -260,10 +310,12 @@ def main():
             d_ = float(tt.item())
         return d_, r_
 
-    # The contract's measurement exactly as written on the freshly leased GPU first - W warm-up steps, then K timed steps -
-    # reported as config.unsettled_value; `value` is the same measurement after the settle phase below
-    run_steps(a.warmup)
-    dt_cold, _ = timed(lambda: run_steps(a.steps))
+    # --full: the contract's measurement exactly as written, first thing in the process - W warm-up steps, then K timed
+    # steps - reported as config.unsettled_value; `value` is the same measurement after the settle phase below
+    dt_cold = None
+    if a.full:
+        run_steps(a.warmup)
+        dt_cold, _ = timed(lambda: run_steps(a.steps))
 
     # untimed: bring the freshly leased GPU to its sustained state, then the W warm-up steps the contract asks for
     t_settle = time.perf_counter()
@@ -275,6 +327,8 @@ def main():
     dt, out = timed(lambda: run_steps(a.steps))
     cards = world * F * K * a.steps
     value = cards / dt
+    if a.dump_outputs and rank == 0:
+        dump_outputs(out[-1], a.dump_outputs)
     import zlib
 
     # checksum of rank 0's top-1 ids over the timed steps: equal across bank layouts, stream counts and rank counts
@@ -315,29 +369,30 @@ def main():
                         "latter two at high priority; the detector's own fork-join off; MTGV_OVERLAP=on set by bench.py, the "
                         "library default is 1; switches MTGV_STREAM_PRIO, MTGV_CROP_STAGE, MTGV_MATCH_STREAM, MTGV_MATCH_PRIO, "
                         "MTGV_OVERLAP_DET_FORK in mtgv/pipeline.py)") if overlap else "1",
-            "settle": f"{a.settle_steps} untimed steps ({t_settle:.1f} s of steady load) before the {a.warmup} warm-up steps of `value`; "
-            "unsettled_value is the same W + K measurement taken BEFORE them, first thing on the freshly leased GPU",
-            "unsettled_value": round(cards / dt_cold, 1),
+            "settle": f"{a.settle_steps} untimed steps ({t_settle:.1f} s of steady load) before the {a.warmup} warm-up steps of `value`"
+            + ("; unsettled_value is the same W + K measurement taken BEFORE them, first thing in the process" if a.full else ""),
             "ids_crc32_rank0": ids_crc,
             "rccl_world": dist.get_world_size() if dist.is_initialized() else 1,
             "dist_backend": (dist.get_backend() if dist.is_initialized() else None),
         },
     }
-    if a.sustained_seconds > 0:
+    if dt_cold is not None:
+        res["config"]["unsettled_value"] = round(cards / dt_cold, 1)
+    if a.full and a.sustained_seconds > 0:
         # the same step loop for seconds instead of K steps (every rank the same step count: the sharded match is a collective)
         n_sus = max(a.steps, int(a.sustained_seconds / (dt / a.steps)) + 1)
         dts, _ = timed(lambda: [run_steps(min(64, n_sus - i0)) and None for i0 in range(0, n_sus, 64)])
         res["config"]["sustained_value"] = round(world * F * K * n_sus / dts, 1)
         res["config"]["sustained_steps"] = n_sus
         res["config"]["sustained_seconds"] = round(dts, 2)
-    if overlap and not a.no_one_stream:
+    if a.full and overlap and not a.no_one_stream:
         # the library default (one stream: MTGV_OVERLAP off) on the same K steps, timed the same way; `value` above is the
         # two-stream figure, which needs the opt-in
         pipe.run(batches[0])
         dt1, _ = timed(lambda: [pipe.run(batches[i % NB]) for i in range(a.steps)] and None)
         res["config"]["one_stream_value"] = round(cards / dt1, 1)
         res["config"]["one_stream_ms_per_step"] = round(dt1 / a.steps * 1e3, 3)
-    if not a.no_h2d:
+    if a.full and not a.no_h2d:
         # frames arriving from the host (the reference's do: server.py:272-280): the NB batches sit in pinned host memory
         # and are copied in on a third stream (copy engine) into a ring of three device buffers, one to two batches ahead
         from mtgv.pipeline import HostFrames
@@ -398,7 +453,7 @@ def main():
         barrier()
         return (ms.value / nprof, fl.value / nprof, int(nl.value // nprof), by.value / nprof, groups, fill_per_step)
 
-    if not a.no_roofline:
+    if a.full and not a.no_roofline:
         prof = profile_pass(precision)
         if precision == "f16x3" and not a.no_f32_roofline:
             # the same step with exact f32-input MFMAs (the library's other operand mode): one warm pass, then the same
@@ -481,7 +536,7 @@ def main():
                     "frac": round(tf32 / PEAK_MFMA_TFLOPS["f32"], 4), "gemm_ms_per_step": round(ms32, 3),
                     "launches_per_step": n32, "groups": groups32,
                 }
-        if world == 1 and not a.no_cpu_baseline:
+        if a.full and world == 1 and not a.no_cpu_baseline:
             # bounded CPU sample of the same workload on the host cores: the oracle pipeline
             from oracle import pipeline_ref
 

@@ -26,7 +26,7 @@ def test_two_ranks_sharded_bench_runs():
     cmd = [
         sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2", "--master-addr", "127.0.0.1",
         "--master-port", str(_free_port()), os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1",
-        "--frames", "4", "--bank", "20000", "--encoder", "cnvnxt2ae_nano",
+        "--frames", "4", "--bank", "20000", "--encoder", "cnvnxt2ae_nano", "--full",
     ]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
@@ -44,7 +44,7 @@ def test_bench_launches_its_own_ranks():
     for k in ("RANK", "LOCAL_RANK", "WORLD_SIZE", "MASTER_ADDR", "MASTER_PORT"):
         env.pop(k, None)
     cmd = [sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "2", "--warmup", "1", "--frames", "4",
-           "--bank", "20000", "--encoder", "cnvnxt2ae_nano", "--no-f32-roofline"]
+           "--bank", "20000", "--encoder", "cnvnxt2ae_nano", "--full", "--no-f32-roofline"]
     r = subprocess.run(cmd, env=env, capture_output=True, text=True, timeout=300)
     assert r.returncode == 0, r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -8,7 +8,7 @@ OUT=$ROOT/gpurun_out/pmc_traffic_$PREC
 mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
 for C in FETCH_SIZE WRITE_SIZE; do
-  rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/$C -- python3 $ROOT/bench.py --steps 2 --warmup 1 \
+  rocprofv3 --kernel-trace --pmc $C --output-format csv -d $OUT/$C -- python3 $ROOT/bench.py --full --steps 2 --warmup 1 \
     --no-cpu-baseline --no-roofline --no-overlap --no-h2d --sustained-seconds 0 --settle-steps 0 --precision $PREC > $OUT/$C.log 2>&1
 done
 # 6 steps: (1 warm-up + 2 timed) before the (empty) settle phase and again after it

@@ -9,7 +9,7 @@ ROOT=${GRAFT_REPO_ROOT:-$(cd "$(dirname "$0")/.." && pwd)}
 OUT=$ROOT/gpurun_out/prof_$TAG
 mkdir -p $OUT
 cd /tmp; export TMPDIR=/tmp
-COMMON="--steps 10 --warmup 2 --no-cpu-baseline --no-roofline --no-one-stream --no-h2d --sustained-seconds 0"
+COMMON="--full --steps 10 --warmup 2 --no-cpu-baseline --no-roofline --no-one-stream --no-h2d --sustained-seconds 0"
 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/two_streams -- python3 $ROOT/bench.py $COMMON > $OUT/two_streams.log 2>&1
 # (every kernel alone on the GPU: one pipeline stream AND the detector's internal fork-join off)
 MTGV_DET_FORK=0 rocprofv3 --kernel-trace --stats --output-format csv -d $OUT/no_overlap -- python3 $ROOT/bench.py $COMMON --no-overlap > $OUT/no_overlap.log 2>&1
@@ -32,7 +32,7 @@ rm -rf $ROOT/gpurun_out/pmc_$TAG/p1 $ROOT/gpurun_out/pmc_$TAG/p2 $ROOT/gpurun_ou
 cd /tmp
 for m in two_streams no_overlap; do
   X=""; [ $m = no_overlap ] && X="--no-overlap"
-  rocprofv3 --kernel-trace --output-format csv -d $OUT/kt_$m -- python3 $ROOT/bench.py --steps 20 --warmup 3 --settle-steps 16 --no-cpu-baseline --no-roofline --no-one-stream --no-h2d --sustained-seconds 0 $X > $OUT/kt_$m.log 2>&1
+  rocprofv3 --kernel-trace --output-format csv -d $OUT/kt_$m -- python3 $ROOT/bench.py --full --steps 20 --warmup 3 --settle-steps 16 --no-cpu-baseline --no-roofline --no-one-stream --no-h2d --sustained-seconds 0 $X > $OUT/kt_$m.log 2>&1
   python3 $ROOT/tools/trace_idle.py $(find $OUT/kt_$m -name "*kernel_trace.csv" | head -1) 0.10 > $OUT/${TAG}_idle_$m.txt 2>&1 || true
   rm -rf $OUT/kt_$m
 done
