@@ -797,11 +797,11 @@ void Detector::c2f(int idx, const View& in, const View& out, int n, hipStream_t 
   conv(cw_.at(P + ".cv2"), cat.slice(0, (2 + ci.n) * ch), out, 1, ACT_SILU, nullptr, n, s);
 }
 
-// model.0 (Conv 3 -> 16, k3 s2): on its own kernel straight from the uint8 frame, or (counting mode, f32 debugging
-// switch) through the float copy and the implicit GEMM
+// model.0 (Conv 3 -> 16, k3 s2): on its own kernel straight from the uint8 frame, or (counting mode) through the float
+// copy and the implicit GEMM
 void Detector::conv0(const uint8_t* frames, int n, int flip, hipStream_t s) {
   const int S = cfg_.imgsz;
-  if (fmt_ == 1 || (!count_flops_ && getenv("MTGV_CONV0_GEMM") == nullptr)) {
+  if (fmt_ == 1 || !count_flops_) {
     const ConvW& w0 = cw_.at("model.0");
     const View l0 = view("l0");
     const long total = (long)n * (S / 2) * (S / 8);

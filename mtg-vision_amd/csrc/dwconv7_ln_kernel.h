@@ -292,10 +292,8 @@ static void dwconv7_ln_launch_t(const float* in, const float* w49, const float* 
   // bit-identical): one block per image, so it needs a batch that fills the CUs; measured against the row-group form
   // (tools/micro/dwconv_stream_probe.hip, profiles/r04_dwconv_stream_probe.txt) it wins where rows are long in pixels -
   // 48 x 32 x 96: 121 vs 129 us, 24 x 16 x 192: 61 vs 66 - and ties or loses at 12 x 8 x 384 / 6 x 4 x 768.
-  // MTGV_DW_STREAM=0: off.
-  const char* const stream_env = getenv("MTGV_DW_STREAM");
   if constexpr (PK == 0)
-  if (rows_on && !(stream_env && atoi(stream_env) == 0) && N >= 128) {
+  if (rows_on && N >= 128) {
 #define DWSTREAM_GO(C_, G_)                                                                                                \
   (out_fmt == 1 ? dwconv7_ln_stream_launch<C_, G_, 4, 3, true>(in, w49, bias, ln_w, ln_b, out, N, H, 1, eps, s)            \
                 : dwconv7_ln_stream_launch<C_, G_, 4, 3, false>(in, w49, bias, ln_w, ln_b, out, N, H, 1, eps, s))

@@ -322,8 +322,6 @@ size_t gemm_grn_part_floats_max(int M, int N, int hw) {
 }
 
 bool gemm_ln_fusable(const GemmArgs& a, const GemmPlan& pl) {
-  static const bool on = [] { const char* e = getenv("MTGV_GEMM_LN"); return e == nullptr || atoi(e) != 0; }();
-  if (!on) return false;
   const bool conv = !(a.KH == 1 && a.KW == 1 && a.stride == 1 && a.stride_w <= 1 && a.pad == 0);
   const bool remap = !(a.os == 1 && a.oy == 0 && a.ox == 0 && a.OH2 == a.OH && a.OW2 == a.OW);
   // the instance that carries the epilogue: conv gather, 128 x 96 x 16 tile; one tile per row, whole tiles, plain f32 rows out

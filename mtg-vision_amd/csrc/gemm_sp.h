@@ -21,9 +21,8 @@ struct SpPlan {
   int tiles_m = 0, tiles_n = 0;
 };
 
-// f16x3 operand mode with the LDS-DMA kernel enabled (MTGV_GEMM_SP != 0): executors then keep activations in SP8
+// f16x3 operand mode: the LDS-DMA kernel runs, and executors keep activations in SP8
 bool gemm_sp_active();
-bool topk_sp_on();  // MTGV_SP_TOPK != 0: bank matches of >= 128 queries on the LDS-DMA kernel
 // Can (and should) this launch run on the SP kernel?  a.a_fmt says how A is stored.
 SpPlan gemm_sp_plan(const GemmArgs& a);
 // true when a dense [M][K] x [N][K]^T launch with these sizes would take SP8 activations (producer kernels ask before

@@ -2,7 +2,6 @@
 #include "gemm_sp.h"
 
 #include <stdlib.h>
-#include <string.h>
 #include <map>
 #include <mutex>
 #include <vector>
@@ -177,15 +176,6 @@ const SpCfg kCfg[] = {
 };
 constexpr int kNumCfg = sizeof(kCfg) / sizeof(kCfg[0]);
 
-bool sp_enabled() {
-  static int on = -1;
-  if (on < 0) {
-    const char* e = getenv("MTGV_GEMM_SP");
-    on = (e != nullptr && !strcmp(e, "0")) ? 0 : 1;
-  }
-  return on != 0;
-}
-
 bool is_conv(const GemmArgs& a) { return !(a.KH == 1 && a.KW == 1 && a.stride == 1 && a.stride_w <= 1 && a.pad == 0); }
 }  // namespace
 
@@ -209,12 +199,7 @@ bool window_conv_fits(const GemmArgs& a, const SpPlan& pl) {
   return window_bytes(k, a.Wd) + (size_t)2 * k.bn() * k.rb() <= 80 * 1024;
 }
 
-bool topk_sp_on() {
-  static const bool on = [] { const char* e = getenv("MTGV_SP_TOPK"); return e == nullptr || atoi(e) != 0; }();
-  return on;
-}
-
-bool gemm_sp_active() { return sp_enabled() && gemm_precision() == GEMM_PREC_F16X3; }
+bool gemm_sp_active() { return gemm_precision() == GEMM_PREC_F16X3; }
 
 bool gemm_sp_takes_sp8(const float* W, int M, int N, int K, int lda, int c_off) {
   if (!gemm_sp_active()) return false;
@@ -222,18 +207,18 @@ bool gemm_sp_takes_sp8(const float* W, int M, int N, int K, int lda, int c_off) 
   return sp8_lookup(W, K, nullptr, nullptr);
 }
 
-// chained 1x1: SP8 conv / dense input, SiLU between the layers, the whole output row in one tile of a one-wave-column
-// configuration (N = 32 / 64 / 96 -> configurations 4 / 3 / 2), plain epilogue otherwise
+// chained 1x1: SP8 conv input (A mode 2 / 5: the only ones with EPI 32 instances, gemm_sp_inst.h), SiLU between the
+// layers, the whole output row in one tile of a one-wave-column configuration (N = 32 / 64 / 96 -> configurations
+// 4 / 3 / 2), plain epilogue otherwise
 static int chain_cfg(const GemmArgs& a) {
-  static const bool on = [] { const char* e = getenv("MTGV_SP_CHAIN"); return e == nullptr || atoi(e) != 0; }();
-  if (!on || a.W2 == nullptr || a.Out2 == nullptr) return -1;
+  if (a.W2 == nullptr || a.Out2 == nullptr || !is_conv(a)) return -1;
   if (!(gemm_sp_active() && a.a_fmt == 1 && a.act == ACT_SILU && a.res == nullptr && a.grn_part == nullptr && a.topk == 0 && a.batch == 1 &&
         a.os == 1 && a.os_nq == 0 && a.OH2 == a.OH && a.OW2 == a.OW && a.a_scale == nullptr && a.ln_w == nullptr))
     return -1;
   if (!(a.N == 32 || a.N == 64 || a.N == 96) || a.N2 <= 0 || a.N2 % 32 != 0 || a.N2 > a.N) return -1;
   if (a.K % 8 != 0 || a.c_total % 8 != 0 || a.c_off % 8 != 0 || a.ldo2 % 4 != 0 || a.o_off2 % 4 != 0 || ((uintptr_t)a.Out2 & 15) != 0) return -1;
   if (a.out_fmt2 == 1 && (a.ldo2 % 8 != 0 || a.o_off2 % 8 != 0)) return -1;
-  if (is_conv(a) && (a.stride_w > 0 || a.Cin % 8 != 0)) return -1;
+  if (a.stride_w > 0 || a.Cin % 8 != 0) return -1;
   if (!sp8_lookup(a.W, a.K, nullptr, nullptr) || !sp8_lookup(a.W2, a.N, nullptr, nullptr)) return -1;
   return a.N == 32 ? 4 : (a.N == 64 ? 3 : 2);
 }
@@ -256,14 +241,13 @@ SpPlan gemm_sp_plan(const GemmArgs& a) {
                "gemm: SP8 tensors handed to a launch the SP kernel cannot run (M=%d N=%d K=%d)", a.M, a.N, a.K);
     return pl;
   };
-  if (!sp_enabled() || gemm_precision() != GEMM_PREC_F16X3) return none();
+  if (!gemm_sp_active()) return none();
   const bool conv = is_conv(a);
   const bool remap = !(a.os == 1 && a.oy == 0 && a.ox == 0 && a.OH2 == a.OH && a.OW2 == a.OW);
   if (a.batch != 1 || a.crop_boxes != nullptr || a.m_count != nullptr || a.ln_w != nullptr) return none();
   if (a.topk > 0) {  // match path: 128 x 192 tiles, f32 queries by DMA (A mode 4), fused top-k (gemm_sp_kernel.h, EPI 16)
     if (sp8_in || conv || a.K % 8 != 0 || a.c_total % 8 != 0 || a.c_off % 8 != 0 || ((uintptr_t)a.A & 15) != 0 || a.a_scale != nullptr ||
-        a.a_mul != 1.0f || a.res != nullptr || a.act != ACT_NONE || a.M < 128 || a.N < 192 || !sp8_lookup(a.W, a.K, nullptr, nullptr) ||
-        !topk_sp_on())
+        a.a_mul != 1.0f || a.res != nullptr || a.act != ACT_NONE || a.M < 128 || a.N < 192 || !sp8_lookup(a.W, a.K, nullptr, nullptr))
       return none();
     const SpCfg& k1 = kCfg[1];
     pl.cfg = 1;
@@ -289,8 +273,9 @@ SpPlan gemm_sp_plan(const GemmArgs& a) {
 
   int best = -1;
   double best_cost = 0;
-  if (const char* e = getenv("MTGV_SP_CFG")) {
-    const int c = atoi(e);
+  const char* const forced = getenv("MTGV_SP_CFG");  // tools/sp_cfg_sweep.py
+  if (forced != nullptr) {
+    const int c = atoi(forced);
     if (c >= 0 && c < kNumCfg && kCfg[c].ks == 2) best = c;
   }
   if (best < 0) {
@@ -308,20 +293,17 @@ SpPlan gemm_sp_plan(const GemmArgs& a) {
     }
   }
   // the whole-ConvTranspose launch (os_nq column groups of 64): one group per 128 x 64 tile measured 9 % faster than 128 x 128
-  if (a.os_nq == 64 && getenv("MTGV_SP_CFG") == nullptr) best = 3;
+  if (a.os_nq == 64 && forced == nullptr) best = 3;
   {  // 3x3 / stride-1 convs with 16-channel slices (Cin % 32 != 0): the window conv in 16-k stages instead of nine tap gathers
-    static const bool on6 = [] { const char* e = getenv("MTGV_SP_WIN16"); return e == nullptr || atoi(e) != 0; }();
     SpPlan p6;
     p6.cfg = 6;
-    if (on6 && getenv("MTGV_SP_CFG") == nullptr && conv && sp8_in && a.Cin % 32 != 0 && a.N <= 32 && window_conv_fits(a, p6)) best = 6;
+    if (forced == nullptr && conv && sp8_in && a.Cin % 32 != 0 && a.N <= 32 && window_conv_fits(a, p6)) best = 6;
   }
-  {  // eight-wave twin of the 128 x 192 tile (four waves per SIMD) for pwconv1-shaped launches: SP8 rows in, activation
-     // + GRN sums out; measured -3..-4 % on the stage 2-3 layers, nothing on the others (MTGV_SP_CFG8=0: off)
-    static const bool on8 = [] { const char* e = getenv("MTGV_SP_CFG8"); return e == nullptr || atoi(e) != 0; }();
-    // (not below 12288 rows: 6144 x 3072 x 768, the stage-3 pwconv1, is 8 % faster on the four-wave tile -
-    // tools/sp_cfg_sweep.py, profiles/r04_sp_cfg_sweep.txt)
-    if (on8 && best == 1 && !conv && sp8_in && a.grn_part != nullptr && a.topk == 0 && a.K >= 256 && a.M >= 12288) best = 5;
-  }
+  // eight-wave twin of the 128 x 192 tile (four waves per SIMD) for pwconv1-shaped launches: SP8 rows in, activation
+  // + GRN sums out; measured -3..-4 % on the stage 2-3 layers, nothing on the others (not below 12288 rows: 6144 x
+  // 3072 x 768, the stage-3 pwconv1, is 8 % faster on the four-wave tile - tools/sp_cfg_sweep.py,
+  // profiles/r04_sp_cfg_sweep.txt)
+  if (best == 1 && !conv && sp8_in && a.grn_part != nullptr && a.topk == 0 && a.K >= 256 && a.M >= 12288) best = 5;
   const SpCfg& k = kCfg[best];
   pl.cfg = best;
   pl.bm = k.bm(), pl.bn = k.bn();

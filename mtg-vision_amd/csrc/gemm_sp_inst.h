@@ -1,8 +1,6 @@
 // One tile configuration of the LDS-DMA split GEMM per translation unit (they compile in parallel): a file defines
 // SP_CFG_ID, SP_WM, SP_WN, SP_TM, SP_TN and includes this header.
 #pragma once
-#include <stdlib.h>
-
 #include "gemm_sp_kernel.h"
 
 namespace mtgv {
@@ -48,8 +46,7 @@ void sp_launch_one(const SpDev& g, hipStream_t s) {
     // (the deeper ring costs one: 204800 x 32 layers +12 %) and the two-deep ring stays
     constexpr int BM = 32 * SP_TM * SP_WM, BN = 32 * SP_TN * SP_WN, RB = 64 * SP_KS, RPP = 1024 / RB;
     const size_t win = (size_t)((BM + 2 * g.Wd + 2 + RPP - 1) / RPP * RPP) * RB;
-    static const bool deep_on = [] { const char* e = getenv("MTGV_SP_WINRING"); return e == nullptr || atoi(e) != 0; }();
-    if (deep_on && (long)g.tiles_m * g.tiles_n <= 512 && win + (size_t)4 * BN * RB <= 80 * 1024) {
+    if ((long)g.tiles_m * g.tiles_n <= 512 && win + (size_t)4 * BN * RB <= 80 * 1024) {
       sp_launch_nst<AMODE, ACT, EPI, 4>(g, s);
       return;
     }

@@ -51,52 +51,11 @@
 
 namespace mtgv {
 
-// Experiment switch (build-time, tools only): wave priority around the phases of a main-loop stage.
-//   MTGV_SP_PRIO == 1: s_setprio 1 while a wave issues its MFMAs; == 2: s_setprio 1 while it issues DMA and LDS reads.
-#ifndef MTGV_SP_PRIO
-#define MTGV_SP_PRIO 0
-#endif
-#define MTGV_SP_PRIO_MFMA(v) do { if (MTGV_SP_PRIO == 1) __builtin_amdgcn_s_setprio(v); } while (0)
-#define MTGV_SP_PRIO_LOAD(v) do { if (MTGV_SP_PRIO == 2) __builtin_amdgcn_s_setprio(v); } while (0)
-// Experiment switch: half-stage stagger of waves 4..7 of the eight-wave SP8 tile (MI355X_MICROARCH.md, "Two waves per SIMD",
-// item 9): those waves run their second k16 step's MFMAs right after the NEXT barrier, while waves 0..3 issue DMA and read.
-#ifndef MTGV_SP_STAGGER
-#define MTGV_SP_STAGGER 0
-#endif
-// TIMING EXPERIMENTS ONLY (results are wrong): what a dense main-loop stage pays for its operand traffic.
-//   MTGV_SP_EXP == 1: no DMA after the prologue (the loop computes on stale LDS): MFMA + LDS reads + conversion alone;
-//   MTGV_SP_EXP == 2: DMA issued as usual but never waited for (vmcnt left alone): issue cost without the latency;
-//   MTGV_SP_EXP == 3: DMA of every second stage only (half the issue cost and bytes), waits as usual;
-//   MTGV_SP_EXP == 4: (f32 A) the next stage's DMA issued behind this stage's LDS reads instead of ahead of them (results right);
-//   MTGV_SP_EXP == 5: every dense DMA piece with a quarter of its lanes (sp8.h): the instruction count without the bytes;
-//   MTGV_SP_EXP == 6: (f32 A) no LDS reads for the GRN multipliers; 7: (f32 A) a third of the weight-fragment LDS reads;
-//   MTGV_SP_EXP == 9: (f32 A) no scaling and no hi / lo split: the 48 vector instructions of a stage gone (operands are garbage).
-#ifndef MTGV_SP_EXP
-#define MTGV_SP_EXP 0
-#endif
-
 typedef float spf16 __attribute__((ext_vector_type(16)));
 
-// One MFMA of the main loop.  MTGV_SP_MFMA16 (build-time, TIMING EXPERIMENT ONLY - the results are not the product): the
-// same operand registers and the same FLOPs issued as two v_mfma_f32_16x16x32_f16 (MI355X_MICROARCH.md, DVFS item 7: the
-// clock the chip holds under matrix load depends on the MFMA shape), each k16 step on its own half of the accumulator.
-#ifndef MTGV_SP_MFMA16
-#define MTGV_SP_MFMA16 0
-#endif
-__device__ __forceinline__ spf16 sp_mfma(sp_h8 b, sp_h8 a, spf16 c, int ks) {
-#if MTGV_SP_MFMA16
-  typedef float f4 __attribute__((ext_vector_type(4)));
-  const int o = (ks & 1) * 8;
-  f4 c0 = {c[o + 0], c[o + 1], c[o + 2], c[o + 3]}, c1 = {c[o + 4], c[o + 5], c[o + 6], c[o + 7]};
-  c0 = __builtin_amdgcn_mfma_f32_16x16x32_f16(b, a, c0, 0, 0, 0);
-  c1 = __builtin_amdgcn_mfma_f32_16x16x32_f16(a, b, c1, 0, 0, 0);
-#pragma unroll
-  for (int e = 0; e < 4; ++e) c[o + e] = c0[e], c[o + 4 + e] = c1[e];
-  return c;
-#else
-  (void)ks;
+// One MFMA of the main loop.
+__device__ __forceinline__ spf16 sp_mfma(sp_h8 b, sp_h8 a, spf16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_f16(b, a, c, 0, 0, 0);
-#endif
 }
 
 struct SpDev {
@@ -440,9 +399,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
   const int slot = lane & 7, lrow = lane >> 3;
   sp_f4 wsc[TN], bsv[TN];
   bool col_ok[TN];
-  // (stagger experiment: waves 4..7 hold a k16 step's fragments across the barrier, so the column vectors are fetched
-  // after the main loop instead of under it - 8 TN registers)
-  constexpr bool COLVEC_LATE = MTGV_SP_STAGGER != 0 && WM * WN == 8 && AMODE == 0 && KS == 2;
+  // (a lambda called once, right here: written straight-line, the same loop compiles to a different register allocation
+  // of the whole kernel - other SGPR spill counts - than the one the tile configurations were measured with)
   auto load_colvecs = [&]() {
 #pragma unroll
   for (int j = 0; j < TN; ++j) {
@@ -464,8 +422,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
     bsv[j] = b0;
   }
   };
-  if constexpr (!COLVEC_LATE) load_colvecs();
-
+  load_colvecs();
 
   // a wave whose rows all lie beyond M (ragged last tile, tiny-M problems) skips its MFMAs
   const bool wave_active = m0 + wm * TM * 32 < g.M;
@@ -479,9 +436,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
   auto wait_stage = [&](bool tail) {
     // steady state: everything but the AHEAD youngest stages has landed; near the end fewer stages are outstanding
     // than that, so the tail waits for all of them
-    if (MTGV_SP_EXP == 2 && !tail) {
-      asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-    } else if (AHEAD == 0 || tail) {
+    if (AHEAD == 0 || tail) {
       asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     } else if (my_pieces == PPW) {
       asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(PPW * AHEAD) : "memory");
@@ -554,9 +509,9 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
             for (int j = 0; j < TN; ++j)
 #pragma unroll
               for (int i = 0; i < TM; ++i) {
-                acc[i][j] = sp_mfma(bl[j], ah[i], acc[i][j], ks);
-                acc[i][j] = sp_mfma(bh[j], al[i], acc[i][j], ks);
-                acc[i][j] = sp_mfma(bh[j], ah[i], acc[i][j], ks);
+                acc[i][j] = sp_mfma(bl[j], ah[i], acc[i][j]);
+                acc[i][j] = sp_mfma(bh[j], al[i], acc[i][j]);
+                acc[i][j] = sp_mfma(bh[j], ah[i], acc[i][j]);
               }
           }
         }
@@ -565,67 +520,18 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
       }
     }
   } else {
-  {
     storeA(0);
     int buf = 0;                      // ring slot of stage t
     int nbuf = NST - 1;               // ring slot of stage t + NST - 1
-    constexpr bool STGR = MTGV_SP_STAGGER != 0 && NW == 8 && AMODE == 0 && KS == 2;
-    const bool late = STGR && wave >= 4;
-    sp_h8 hah[TM], hal[TM], hbh[TN], hbl[TN];  // (stagger) the second k16 step's fragments, held across the barrier
-    auto frag_read = [&](const char* sb, int ks, sp_h8* fah, sp_h8* fal, sp_h8* fbh, sp_h8* fbl) {
-      const unsigned shi = (unsigned)(((ks * 4 + h * 2 + 0) ^ swr) << 4);
-      const unsigned slo = (unsigned)(((ks * 4 + h * 2 + 1) ^ swr) << 4);
-#pragma unroll
-      for (int i = 0; i < TM; ++i) {
-        fah[i] = *reinterpret_cast<const sp_h8*>(sb + a_off[i] + shi);
-        fal[i] = *reinterpret_cast<const sp_h8*>(sb + a_off[i] + slo);
-      }
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        fbh[j] = *reinterpret_cast<const sp_h8*>(sb + b_off[j] + shi);
-        fbl[j] = *reinterpret_cast<const sp_h8*>(sb + b_off[j] + slo);
-      }
-    };
-    auto frag_mfma = [&](const sp_h8* fah, const sp_h8* fal, const sp_h8* fbh, const sp_h8* fbl) {
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int i = 0; i < TM; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fbl[j], fah[i], acc[i][j], 0, 0, 0);
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int i = 0; i < TM; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fbh[j], fal[i], acc[i][j], 0, 0, 0);
-#pragma unroll
-      for (int j = 0; j < TN; ++j)
-#pragma unroll
-        for (int i = 0; i < TM; ++i) acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(fbh[j], fah[i], acc[i][j], 0, 0, 0);
-    };
     for (int t = 0; t < nk; ++t) {
       // stage t landed: this wave's DMA pieces (vmcnt) and REG-mode ds_writes (lgkmcnt), then everyone's (barrier).
       // The barrier also says every wave has finished reading the slot of stage t - 1, which is refilled next.
       wait_stage(t + NST - 1 > nk);
       __builtin_amdgcn_s_barrier();
       if (g.stamps != nullptr && t == 0) st1 = (long)__builtin_amdgcn_s_memtime();
-      MTGV_SP_PRIO_LOAD(1);
-      if constexpr (STGR) {
-        if (late && wave_active && t > 0) {  // the previous stage's second k16 step, out of registers
-          frag_mfma(hah, hal, hbh, hbl);
-          __builtin_amdgcn_sched_barrier(0);
-        }
-      }
       if (t + NST - 1 < nk) {
-        constexpr bool LATE_DMA = MTGV_SP_EXP == 4 && AF32 && KS == 2 && !HI16;  // (issued behind the stage's LDS reads, below)
-        if (MTGV_SP_EXP != 1 && (MTGV_SP_EXP != 3 || (t & 1)) && !(LATE_DMA && wave_active)) issue(t + NST - 1, nbuf);
+        issue(t + NST - 1, nbuf);
         loadA(t + 1);
-      }
-      if (STGR && late) {
-        if (wave_active) {
-          const char* const sb = ring + buf * STG;
-          sp_h8 ah[TM], al[TM], bh[TN], bl[TN];
-          frag_read(sb, 0, ah, al, bh, bl);
-          frag_mfma(ah, al, bh, bl);
-          frag_read(sb, 1, hah, hal, hbh, hbl);
-        }
       }
       if (wave_active && HI16) {  // four k16 steps per stage, one product each
         const char* const sb = ring + buf * STG;
@@ -640,7 +546,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
   #pragma unroll
           for (int j = 0; j < TN; ++j)
   #pragma unroll
-            for (int i = 0; i < TM; ++i) acc[i][j] = sp_mfma(bh[j], ah[i], acc[i][j], ks);
+            for (int i = 0; i < TM; ++i) acc[i][j] = sp_mfma(bh[j], ah[i], acc[i][j]);
         }
       }
       if constexpr (AF32 && KS == 2 && !HI16) {
@@ -661,64 +567,43 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
               xa[ks][i][0] = *reinterpret_cast<const sp_f4*>(sb + a_off[i] + shi);
               xa[ks][i][1] = *reinterpret_cast<const sp_f4*>(sb + a_off[i] + slo);
               if constexpr (AMODE == 3) {
-                if (MTGV_SP_EXP == 6) {  // experiment: no LDS reads for the multipliers
-                  xs[ks][i][0] = xs[ks][i][1] = sp_f4{1.f, 1.f, 1.f, 1.f};
-                } else {
-                  xs[ks][i][0] = *reinterpret_cast<const sp_f4*>(sb + sc_off[i] + ks * 64);
-                  xs[ks][i][1] = *reinterpret_cast<const sp_f4*>(sb + sc_off[i] + ks * 64 + 16);
-                }
+                xs[ks][i][0] = *reinterpret_cast<const sp_f4*>(sb + sc_off[i] + ks * 64);
+                xs[ks][i][1] = *reinterpret_cast<const sp_f4*>(sb + sc_off[i] + ks * 64 + 16);
               }
             }
   #pragma unroll
             for (int j = 0; j < TN; ++j) {
-              if (MTGV_SP_EXP == 7 && j > 0) {  // experiment: one column block's weight fragments for all (a third of the B reads)
-                bh[ks][j] = bh[ks][0], bl[ks][j] = bl[ks][0];
-              } else {
-                bh[ks][j] = *reinterpret_cast<const sp_h8*>(sb + b_off[j] + shi);
-                bl[ks][j] = *reinterpret_cast<const sp_h8*>(sb + b_off[j] + slo);
-              }
+              bh[ks][j] = *reinterpret_cast<const sp_h8*>(sb + b_off[j] + shi);
+              bl[ks][j] = *reinterpret_cast<const sp_h8*>(sb + b_off[j] + slo);
             }
           }
-          if constexpr (MTGV_SP_EXP == 4) {  // experiment: the stage's LDS latency runs under the next stage's DMA issue
-            __builtin_amdgcn_sched_barrier(0);
-            if (t + NST - 1 < nk) issue(t + NST - 1, nbuf);
-            __builtin_amdgcn_sched_barrier(0);
-          }
-          if constexpr (AMODE == 3 && MTGV_SP_EXP != 9) {
+          if constexpr (AMODE == 3) {
   #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
   #pragma unroll
               for (int i = 0; i < TM; ++i) xa[ks][i][0] = xa[ks][i][0] * xs[ks][i][0], xa[ks][i][1] = xa[ks][i][1] * xs[ks][i][1];
           }
-          MTGV_SP_PRIO_LOAD(0);
-          MTGV_SP_PRIO_MFMA(1);
           sp_h8 ah[2][TM], al[2][TM];
   #pragma unroll
-          for (int i = 0; i < TM; ++i) {
-            if (MTGV_SP_EXP == 9) ah[0][i] = __builtin_bit_cast(sp_h8, xa[0][i][0]), al[0][i] = __builtin_bit_cast(sp_h8, xa[0][i][1]);  // experiment: no conversion
-            else sp8_split8_mix(xa[0][i][0], xa[0][i][1], ah[0][i], al[0][i]);
-          }
+          for (int i = 0; i < TM; ++i) sp8_split8_mix(xa[0][i][0], xa[0][i][1], ah[0][i], al[0][i]);
   #pragma unroll
           for (int ks = 0; ks < 2; ++ks) {
             if (ks == 0) {
   #pragma unroll
-              for (int i = 0; i < TM; ++i) {
-                if (MTGV_SP_EXP == 9) ah[1][i] = __builtin_bit_cast(sp_h8, xa[1][i][0]), al[1][i] = __builtin_bit_cast(sp_h8, xa[1][i][1]);
-                else sp8_split8_mix(xa[1][i][0], xa[1][i][1], ah[1][i], al[1][i]);
-              }
+              for (int i = 0; i < TM; ++i) sp8_split8_mix(xa[1][i][0], xa[1][i][1], ah[1][i], al[1][i]);
             }
   #pragma unroll
             for (int j = 0; j < TN; ++j)
   #pragma unroll
-              for (int i = 0; i < TM; ++i) acc[i][j] = sp_mfma(bl[ks][j], ah[ks][i], acc[i][j], ks);
+              for (int i = 0; i < TM; ++i) acc[i][j] = sp_mfma(bl[ks][j], ah[ks][i], acc[i][j]);
   #pragma unroll
             for (int j = 0; j < TN; ++j)
   #pragma unroll
-              for (int i = 0; i < TM; ++i) acc[i][j] = sp_mfma(bh[ks][j], al[ks][i], acc[i][j], ks);
+              for (int i = 0; i < TM; ++i) acc[i][j] = sp_mfma(bh[ks][j], al[ks][i], acc[i][j]);
   #pragma unroll
             for (int j = 0; j < TN; ++j)
   #pragma unroll
-              for (int i = 0; i < TM; ++i) acc[i][j] = sp_mfma(bh[ks][j], ah[ks][i], acc[i][j], ks);
+              for (int i = 0; i < TM; ++i) acc[i][j] = sp_mfma(bh[ks][j], ah[ks][i], acc[i][j]);
           }
           // issue order: every LDS read, the first step's conversion, then the first step's MFMAs one by one, each
           // followed by a share of the second step's conversion
@@ -727,12 +612,11 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
           __builtin_amdgcn_sched_group_barrier(0x002, CV * TM, 0);                                     // VALU
   #pragma unroll
           for (int q = 0; q < 3 * TM * TN; ++q) {
-            __builtin_amdgcn_sched_group_barrier(0x008, 1 + MTGV_SP_MFMA16, 0);  // MFMA
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);  // MFMA
             __builtin_amdgcn_sched_group_barrier(0x002, (CV * TM + 3 * TM * TN - 1) / (3 * TM * TN), 0);  // VALU
           }
-          MTGV_SP_PRIO_MFMA(0);
         }
-      } else if (wave_active && !HI16 && !(STGR && late)) {
+      } else if (wave_active && !HI16) {
         const char* const sb = ring + buf * STG;
   #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
@@ -761,34 +645,24 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
           }
           // small cross terms first, the hi*hi product last (per accumulator); the three products of an accumulator are
           // issued TM * TN instructions apart, so no MFMA waits on the one just before it
-          if (ks == 0) { MTGV_SP_PRIO_LOAD(0); MTGV_SP_PRIO_MFMA(1); }
   #pragma unroll
           for (int j = 0; j < TN; ++j)
   #pragma unroll
-            for (int i = 0; i < TM; ++i) acc[i][j] = sp_mfma(bl[j], ah[i], acc[i][j], ks);
+            for (int i = 0; i < TM; ++i) acc[i][j] = sp_mfma(bl[j], ah[i], acc[i][j]);
   #pragma unroll
           for (int j = 0; j < TN; ++j)
   #pragma unroll
-            for (int i = 0; i < TM; ++i) acc[i][j] = sp_mfma(bh[j], al[i], acc[i][j], ks);
+            for (int i = 0; i < TM; ++i) acc[i][j] = sp_mfma(bh[j], al[i], acc[i][j]);
   #pragma unroll
           for (int j = 0; j < TN; ++j)
   #pragma unroll
-            for (int i = 0; i < TM; ++i) acc[i][j] = sp_mfma(bh[j], ah[i], acc[i][j], ks);
+            for (int i = 0; i < TM; ++i) acc[i][j] = sp_mfma(bh[j], ah[i], acc[i][j]);
         }
-        MTGV_SP_PRIO_MFMA(0);
       }
-      MTGV_SP_PRIO_LOAD(0);
       if (AMODE == 1 && t + 1 < nk) storeA(buf ^ 1);
       buf = buf + 1 == NST ? 0 : buf + 1;
       nbuf = nbuf + 1 == NST ? 0 : nbuf + 1;
     }
-    if constexpr (STGR) {
-      if (late && wave_active && nk > 0) {
-        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
-        frag_mfma(hah, hal, hbh, hbl);
-      }
-    }
-  }
   }
 
   // ---- epilogue ----
@@ -799,7 +673,6 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
     else if constexpr (ACT == ACT_SILU) return act_silu(x);
     else return apply_act(x, g.act);
   };
-  if constexpr (COLVEC_LATE) load_colvecs();
   __builtin_amdgcn_s_barrier();  // every wave is done with the ring: it becomes the store staging area
   const long st2 = g.stamps != nullptr ? (long)__builtin_amdgcn_s_memtime() : 0;
 

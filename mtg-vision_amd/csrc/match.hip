@@ -374,7 +374,7 @@ int64_t Bank::prepass_fallbacks() const {
 bool Bank::prepass_ok(int b, int k) const {
   const char* e = getenv("MTGV_MATCH_PREPASS");  // read per call: tests and tools compare the two paths in one process
   const bool on = e == nullptr || atoi(e) != 0;
-  return on && gemm_sp_active() && topk_sp_on() && b >= 128 && k <= 4 && dim_ % 64 == 0 && size_ >= 4096 && hi_.p != nullptr;
+  return on && gemm_sp_active() && b >= 128 && k <= 4 && dim_ % 64 == 0 && size_ >= 4096 && hi_.p != nullptr;
 }
 
 void Bank::topk_prepass(const float* q, int b, int k, int64_t id_base, float thr, int64_t* ids, float* scores, hipStream_t s) {

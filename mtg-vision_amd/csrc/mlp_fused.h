@@ -5,7 +5,7 @@
 
 namespace mtgv {
 
-// Can a Block with C channels and hw pixels per image run fused (f16x3 operand mode, MTGV_MLP_FUSED != 0)?
+// Can a Block with C channels and hw pixels per image run fused (f16x3 operand mode)?
 bool mlp_fused_supported(int C, int hw, int act);
 
 // bytes of the permuted SP8 copy of W2 [C][4C] (followed by nothing: the row scales are a separate [C] float array)

@@ -11,11 +11,6 @@
 namespace mtgv {
 
 namespace {
-bool fused_on() {
-  static const bool on = [] { const char* e = getenv("MTGV_MLP_FUSED"); return e == nullptr || atoi(e) != 0; }();
-  return on;
-}
-
 template <int C16, int ACT, int PASS>
 void launch_pass(const MlpDev& g, hipStream_t s) {
   constexpr int C = 16 * C16, KB = (C16 + 1) / 2;
@@ -45,7 +40,7 @@ void launch_any(const MlpDev& g, int C, int act, hipStream_t s) {
 }  // namespace
 
 bool mlp_fused_supported(int C, int hw, int act) {
-  return fused_on() && gemm_sp_active() && (C == 96 || C == 80) && (act == ACT_MISH || act == ACT_GELU) && hw >= 128 && hw % 32 == 0;
+  return gemm_sp_active() && (C == 96 || C == 80) && (act == ACT_MISH || act == ACT_GELU) && hw >= 128 && hw % 32 == 0;
 }
 
 void mlp_pack_w2p_launch(const float* W2, void* w2p, float* ws2, int C, hipStream_t s) {

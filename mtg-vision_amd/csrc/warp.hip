@@ -240,8 +240,7 @@ MTGV_API int mtgv_warp_quads(const uint8_t* frames_dev, int32_t nf, int32_t fh, 
     HIP_OK(hipGetLastError());
     const long total = (long)nq * out_h * out_w;
     // four pixels per thread need rows of whole groups and dword-aligned buffers (frame f starts at f * fh * fw * 3 bytes)
-    static const bool px1 = getenv("MTGV_WARP_PX1") != nullptr;  // debugging aid: one pixel per thread
-    if (!px1 && out_w % 4 == 0 && ((uintptr_t)out_dev & 3) == 0 && ((uintptr_t)frames_dev & 3) == 0 && ((long)fh * fw * 3) % 4 == 0)
+    if (out_w % 4 == 0 && ((uintptr_t)out_dev & 3) == 0 && ((uintptr_t)frames_dev & 3) == 0 && ((long)fh * fw * 3) % 4 == 0)
       hipLaunchKernelGGL(warp_kernel<4>, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, s, frames_dev, fh, fw, coef, frame_idx_dev,
                          nq, out_h, out_w, out_dev);
     else

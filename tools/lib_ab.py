@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """A/B of alternative library builds (mtg-vision_amd/build.py with MTGV_BUILD_TAG): per-launch GEMM times of one pipeline
 step per library, minimum over REPS profiled steps, summed by launch kind.
-    python tools/lib_ab.py base prio1 stg ...      ("base" = the product library)"""
+    python tools/lib_ab.py base TAG ...      ("base" = the product library)"""
 import csv, os, subprocess, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 OUT = os.path.join(ROOT, "gpurun_out", "lib_ab")

@@ -29,9 +29,9 @@ def timeit(fn, warm=8, it=40):
     e1.record(); torch.cuda.synchronize()
     return e0.elapsed_time(e1) / it
 
-sw = ["MTGV_DET_FORK", "MTGV_PROTO_UP1", "MTGV_SPPF_POOLS1", "MTGV_DW_STREAM"]
+sw = ["MTGV_DET_FORK", "MTGV_PROTO_UP1", "MTGV_SPPF_POOLS1"]
 cases = [("round-3 schedule (all off)", dict.fromkeys(sw, "0")), ("fork only", {**dict.fromkeys(sw, "0"), "MTGV_DET_FORK": "1"}),
-         ("fork + upsample/pools in one launch", {**dict.fromkeys(sw, "1"), "MTGV_DW_STREAM": "0"}), ("all on (default)", dict.fromkeys(sw, "1"))]
+         ("all on (default)", dict.fromkeys(sw, "1"))]
 for rep in range(2):
     for name, env in cases:
         os.environ.update(env)
