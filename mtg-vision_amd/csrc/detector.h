@@ -1,4 +1,5 @@
-// YOLOv8n-seg executor: conv stack on the f32-MFMA implicit GEMM, decode, NMS, mask GEMM.
+// YOLOv8n-seg / YOLO11n-seg executor: conv stack on the implicit GEMM of gemm_launch (split-precision f16x3 or f32),
+// decode, NMS, mask logits.
 #pragma once
 #include "common.h"
 #include "encoder.h"
@@ -22,6 +23,7 @@ struct View {
   float* p = nullptr;
   int H = 0, W = 0, ct = 0, co = 0, C = 0;
   int fmt = 0;  // 0: f32; 1: SP8 (sp8.h) - same bytes per element, channel offsets in multiples of 8
+  bool f32 = false;  // arena buffer kept f32 in every forward (view() gives the others the forward's format)
   View slice(int off, int c) const {
     View v = *this;
     v.co = co + off;
@@ -55,7 +57,7 @@ class Detector {
   void expect_conv_bn(const std::string& prefix, int cout, int cin, int k);
   ConvW fold(const std::string& prefix, int cin_pad = 0);           // Conv+BN
   ConvW plain(const std::string& prefix);                           // Conv2d with bias
-  ConvW concat_out(const std::vector<ConvW>& parts);                // stack along cout
+  ConvW concat_out(const std::vector<ConvW>& parts);                // stack along cout (same cin and k)
   float* upload(const std::vector<float>& v, int row_k = 0);  // row_k > 0: a GEMM B operand with rows of row_k floats
   void conv(const ConvW& w, const View& in, const View& out, int stride, int act, const View* res, int n, hipStream_t s);
   // Conv(w1, SiLU) followed by the 1x1 conv w2 (act2) with w1's output consumed on chip (gemm_sp_kernel.h, EPI 32): `mid` is
@@ -71,13 +73,18 @@ class Detector {
   void c3k2(int idx, const View& in, const View& out, int n, hipStream_t s);
   void c2psa(int idx, const View& in, const View& out, int n, hipStream_t s);
   void build_v11();
-  void arena_v11();
+  // activation arena: one entry per buffer of max_batch frames, carved in this order
+  struct ArenaBuf { const char* name; int h, w, c; bool f32 = false; };  // f32: View::f32
+  std::vector<ArenaBuf> arena_v8() const;
+  std::vector<ArenaBuf> arena_v11() const;
+  void plan_arena(const std::vector<ArenaBuf>& bufs);
   void forward_v11(const uint8_t* frames, int n, int flip, hipStream_t s);
   void forward_v8(const uint8_t* frames, int n, int flip, hipStream_t s);
   void head_tail(int n, int* n_det, float* boxes, float* conf, int* cls, int* keep_idx, float* mask_logits, int mask_rows,
                  hipStream_t s);
   void conv0(const uint8_t* frames, int n, int flip, hipStream_t s);
   void sppf(const std::string& prefix, const View& in, const View& spp, const View& out, int n, hipStream_t s);
+  void upsample2x(const View& in, const View& out, int n, hipStream_t s);
   void proto(const std::string& head, const View& p3, int n, hipStream_t s);
   void head_level_v8(int l, int n, hipStream_t s);
   void head_level_v11(int l, int n, hipStream_t s);
@@ -93,7 +100,6 @@ class Detector {
   hipStream_t fork_after(hipStream_t s, int i);
   void join_into(hipStream_t s, int i);
   bool v11() const { return cfg_.arch == 11; }
-  View take(int n, int h, int w, int c);
   View view(const std::string& k) const;
 
   mtgv_detector_cfg cfg_;
@@ -110,18 +116,17 @@ class Detector {
   std::map<int, C2fInfo> c2f_;
   struct C3k2Info { int cout, n, ch; bool c3k; };
   std::map<int, C3k2Info> c3k2_;
-  ConvW head_bc_[3];            // v11: box + coefficient first convs merged
   ConvW cls_dw1_[3], cls_pw1_[3], cls_dw2_[3], cls_pw2_[3];
   std::string head_ = "model.22";
+  // head_first_: the first 3x3 convs of the branches that read the level's features, stacked (v8: box, class and
+  // coefficient; v11: box and coefficient)
   ConvW head_first_[3], head_box2_[3], head_cls2_[3], head_coef2_[3], head_box3_[3], head_cls3_[3], head_coef3_[3];
   ConvW proto_up_[4];
   ConvW proto_up_all_;  // the four phase matrices stacked (kh, kw, cout): the ConvTranspose as one launch (GemmArgs::os_nq)
 
   // activations (arena)
   DevBuf arena_;
-  size_t arena_used_ = 0;
   std::map<std::string, View> v_;
-  float *rawhead_[3] = {nullptr, nullptr, nullptr}, *pred_ = nullptr, *coef_ = nullptr;
   int* nms_ws_ = nullptr;
   size_t nms_ws_bytes_ = 0;
   int last_n_ = 0;

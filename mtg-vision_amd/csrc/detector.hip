@@ -2,7 +2,7 @@
 // scale "n" (third-party to the reference; call site mtgvision/od_export.py:141-160, model
 // family od_train.py:46-70).  BatchNorm (eps 1e-3) is folded into the conv weights at
 // finalize(); Concat is free (producers write channel slices of the consumer's buffer);
-// every Conv+SiLU is one launch of the f32-MFMA implicit GEMM (gemm_f32.hip).
+// every Conv+SiLU is one launch of the implicit GEMM (gemm_launch, gemm_f32.hip).
 #include "detector.h"
 #include "nms.h"
 #include "rowops.h"
@@ -539,20 +539,72 @@ ConvW Detector::plain(const std::string& p) {
   return c;
 }
 
-View Detector::take(int n, int h, int w, int c) {
-  const size_t fl = ((size_t)n * h * w * c + 63) / 64 * 64;
-  MTGV_CHECK(arena_used_ + fl <= arena_.n, ERR_RUNTIME, "detector arena exhausted");
-  View v;
-  v.p = arena_.p + arena_used_;
-  v.H = h, v.W = w, v.ct = c, v.co = 0, v.C = c;
-  arena_used_ += fl;
-  return v;
+// ConvWs that read the same input stacked along cout, rows and biases in the order given: one launch for all of them
+ConvW Detector::concat_out(const std::vector<ConvW>& parts) {
+  const int cin = parts.at(0).cin, k = parts[0].k;
+  const size_t per = (size_t)k * k * cin;
+  std::vector<float> w, b;
+  for (const ConvW& q : parts) {
+    MTGV_CHECK(q.cin == cin && q.k == k, ERR_RUNTIME, "detector: concat_out of convs with different inputs");
+    const size_t wo = w.size(), bo = b.size();
+    w.resize(wo + (size_t)q.cout * per), b.resize(bo + q.cout);
+    HIP_OK(hipMemcpy(w.data() + wo, q.w, (size_t)q.cout * per * sizeof(float), hipMemcpyDeviceToHost));
+    HIP_OK(hipMemcpy(b.data() + bo, q.b, (size_t)q.cout * sizeof(float), hipMemcpyDeviceToHost));
+  }
+  ConvW c;
+  c.w = upload(w, (int)per), c.b = upload(b), c.cout = (int)b.size(), c.cin = cin, c.k = k;
+  return c;
 }
 
-// activation view by name, in the format of the current forward (fmt_)
+// Carve the activation arena for max_batch frames: each buffer 256-byte aligned, in table order.  Cleared once: the raw
+// head rows' class padding column (index 67) is never written by a conv.
+void Detector::plan_arena(const std::vector<ArenaBuf>& bufs) {
+  auto floats = [&](const ArenaBuf& b) { return ((size_t)cfg_.max_batch * b.h * b.w * b.c + 63) / 64 * 64; };
+  size_t total = 0;
+  for (const ArenaBuf& b : bufs) total += floats(b);
+  arena_.alloc(total);
+  v_.clear();
+  float* p = arena_.p;
+  for (const ArenaBuf& b : bufs) {
+    View v;
+    v.p = p, v.H = b.h, v.W = b.w, v.ct = b.c, v.C = b.c, v.f32 = b.f32;
+    MTGV_CHECK(v_.emplace(b.name, v).second, ERR_RUNTIME, "detector: arena buffer '%s' listed twice", b.name);
+    p += floats(b);
+  }
+  HIP_OK(hipMemset(arena_.p, 0, arena_.n * sizeof(float)));
+}
+
+std::vector<Detector::ArenaBuf> Detector::arena_v8() const {
+  const int S = cfg_.imgsz, s2 = S / 2, s4 = S / 4, s8 = S / 8, s16 = S / 16, s32 = S / 32;
+  const int c16 = chn(64), c32 = chn(128), c64 = chn(256), c128 = chn(512), c256 = chn(1024);
+  return {
+      {"l0", s2, s2, c16}, {"l1", s4, s4, c32},
+      {"cat2", s4, s4, 3 * c32 / 2}, {"tmp2", s4, s4, c32 / 2}, {"l2", s4, s4, c32},
+      {"l3", s8, s8, c64}, {"cat4", s8, s8, 4 * c64 / 2}, {"tmp4", s8, s8, c64 / 2},
+      {"cat14", s8, s8, c128 + c64},                                      // concat 14 = [up(12), 4]
+      {"l5", s16, s16, c128}, {"cat6", s16, s16, 4 * c128 / 2}, {"tmp6", s16, s16, c128 / 2},
+      {"cat11", s16, s16, c256 + c128},                                   // concat 11 = [up(9), 6]
+      {"l7", s32, s32, c256}, {"cat8", s32, s32, 3 * c256 / 2}, {"tmp8", s32, s32, c256 / 2}, {"l8", s32, s32, c256},
+      {"sppcat", s32, s32, 2 * c256},
+      {"cat20", s32, s32, c128 + c256},                                   // concat 20 = [19, 9]
+      {"cat12", s16, s16, 3 * c128 / 2}, {"tmp12", s16, s16, c128 / 2},
+      {"cat17", s16, s16, c64 + c128},                                    // concat 17 = [16, 12]
+      {"cat15", s8, s8, 3 * c64 / 2}, {"tmp15", s8, s8, c64 / 2}, {"p3", s8, s8, c64},
+      {"cat18", s16, s16, 3 * c128 / 2}, {"tmp18", s16, s16, c128 / 2}, {"p4", s16, s16, c128},
+      {"cat21", s32, s32, 3 * c256 / 2}, {"tmp21", s32, s32, c256 / 2}, {"p5", s32, s32, c256},
+      // head temporaries per level (the levels' branches run concurrently)
+      {"t1_0", s8, s8, 160}, {"t2_0", s8, s8, 160}, {"t1_1", s16, s16, 160}, {"t2_1", s16, s16, 160},
+      {"t1_2", s32, s32, 160}, {"t2_2", s32, s32, 160},
+      {"rawhead0", s8, s8, RAW_CT, true}, {"rawhead1", s16, s16, RAW_CT, true}, {"rawhead2", s32, s32, RAW_CT, true},
+      {"pr1", s8, s8, npr_}, {"pr2", s4, s4, npr_}, {"pr3", s4, s4, npr_}, {"protos", s4, s4, nm_, true},
+      {"pred", 1, na_, 4 + cfg_.nc + nm_, true}, {"coef", 1, cfg_.max_det, nm_, true},
+  };
+}
+
+// activation view by name, in the format of the current forward (fmt_) unless the buffer is kept f32
 View Detector::view(const std::string& k) const {
   View v = v_.at(k);
-  v.fmt = (k == "x0" || k == "protos") ? 0 : fmt_;
+  v.fmt = v.f32 ? 0 : fmt_;
   return v;
 }
 
@@ -581,48 +633,24 @@ void Detector::finalize() {
     }
   }
   const std::string H = head_;
-  for (int l = 0; l < 3 && !v11(); ++l) {
+  for (int l = 0; l < 3; ++l) {
     const std::string ls = std::to_string(l);
-    // the three branches' first 3x3 convs read the same input: one conv with 64+64+32 outputs
-    const ConvW &a = cw_.at(H + ".cv2." + ls + ".0"), &b = cw_.at(H + ".cv3." + ls + ".0"), &c = cw_.at(H + ".cv4." + ls + ".0");
-    const size_t per = (size_t)9 * a.cin;
-    std::vector<float> w((size_t)(a.cout + b.cout + c.cout) * per), bias(a.cout + b.cout + c.cout);
-    size_t wo = 0, bo = 0;
-    for (const ConvW* q : {&a, &b, &c}) {
-      HIP_OK(hipMemcpy(w.data() + wo, q->w, (size_t)q->cout * per * sizeof(float), hipMemcpyDeviceToHost));
-      HIP_OK(hipMemcpy(bias.data() + bo, q->b, (size_t)q->cout * sizeof(float), hipMemcpyDeviceToHost));
-      wo += (size_t)q->cout * per, bo += q->cout;
+    const std::string B = H + ".cv2." + ls, C = H + ".cv3." + ls, M = H + ".cv4." + ls;  // box, class, coefficient branches
+    if (v11()) {
+      // box and coefficient branches start with a 3x3 conv on the same input: one conv with 64+32 outputs
+      head_first_[l] = concat_out({cw_.at(B + ".0"), cw_.at(M + ".0")});
+      cls_dw1_[l] = cw_.at(C + ".0.0"), cls_pw1_[l] = cw_.at(C + ".0.1");
+      cls_dw2_[l] = cw_.at(C + ".1.0"), cls_pw2_[l] = cw_.at(C + ".1.1");
+    } else {
+      // the three branches' first 3x3 convs read the same input: one conv with 64+64+32 outputs
+      head_first_[l] = concat_out({cw_.at(B + ".0"), cw_.at(C + ".0"), cw_.at(M + ".0")});
+      head_cls2_[l] = cw_.at(C + ".1");
     }
-    head_first_[l].w = upload(w, (int)per), head_first_[l].b = upload(bias);
-    head_first_[l].cout = a.cout + b.cout + c.cout, head_first_[l].cin = a.cin, head_first_[l].k = 3;
-    head_box2_[l] = cw_.at(H + ".cv2." + ls + ".1");
-    head_cls2_[l] = cw_.at(H + ".cv3." + ls + ".1");
-    head_coef2_[l] = cw_.at(H + ".cv4." + ls + ".1");
-    head_box3_[l] = plain(H + ".cv2." + ls + ".2");
-    head_cls3_[l] = plain(H + ".cv3." + ls + ".2");
-    head_coef3_[l] = plain(H + ".cv4." + ls + ".2");
-  }
-  for (int l = 0; l < 3 && v11(); ++l) {
-    const std::string ls = std::to_string(l);
-    // box and coefficient branches start with a 3x3 conv on the same input: one conv with 64+32 outputs
-    const ConvW &a = cw_.at(H + ".cv2." + ls + ".0"), &c = cw_.at(H + ".cv4." + ls + ".0");
-    const size_t per = (size_t)9 * a.cin;
-    std::vector<float> w((size_t)(a.cout + c.cout) * per), bias(a.cout + c.cout);
-    size_t wo = 0, bo = 0;
-    for (const ConvW* q : {&a, &c}) {
-      HIP_OK(hipMemcpy(w.data() + wo, q->w, (size_t)q->cout * per * sizeof(float), hipMemcpyDeviceToHost));
-      HIP_OK(hipMemcpy(bias.data() + bo, q->b, (size_t)q->cout * sizeof(float), hipMemcpyDeviceToHost));
-      wo += (size_t)q->cout * per, bo += q->cout;
-    }
-    head_bc_[l].w = upload(w, (int)per), head_bc_[l].b = upload(bias);
-    head_bc_[l].cout = a.cout + c.cout, head_bc_[l].cin = a.cin, head_bc_[l].k = 3;
-    head_box2_[l] = cw_.at(H + ".cv2." + ls + ".1");
-    head_coef2_[l] = cw_.at(H + ".cv4." + ls + ".1");
-    cls_dw1_[l] = cw_.at(H + ".cv3." + ls + ".0.0"), cls_pw1_[l] = cw_.at(H + ".cv3." + ls + ".0.1");
-    cls_dw2_[l] = cw_.at(H + ".cv3." + ls + ".1.0"), cls_pw2_[l] = cw_.at(H + ".cv3." + ls + ".1.1");
-    head_box3_[l] = plain(H + ".cv2." + ls + ".2");
-    head_cls3_[l] = plain(H + ".cv3." + ls + ".2");
-    head_coef3_[l] = plain(H + ".cv4." + ls + ".2");
+    head_box2_[l] = cw_.at(B + ".1");
+    head_coef2_[l] = cw_.at(M + ".1");
+    head_box3_[l] = plain(B + ".2");
+    head_cls3_[l] = plain(C + ".2");
+    head_coef3_[l] = plain(M + ".2");
   }
   // DFL weights must be arange(16) (they are a fixed buffer upstream); the decode kernel hard-codes them
   {
@@ -644,80 +672,10 @@ void Detector::finalize() {
         proto_up_[kh * 2 + kw] = c;
       }
     // all four phases as one [4 co][ci] operand, rows (kh, kw, o): one launch reads the input once (proto())
-    std::vector<float> m4((size_t)4 * co * ci), b4((size_t)4 * co);
-    const auto& bsrc = raw_.at(H + ".proto.upsample.bias").data;
-    for (int q = 0; q < 4; ++q)
-      for (int o = 0; o < co; ++o) {
-        b4[(size_t)q * co + o] = bsrc[o];
-        for (int i = 0; i < ci; ++i) m4[((size_t)q * co + o) * ci + i] = w.data[(((size_t)i * co + o) * 2 + (q >> 1)) * 2 + (q & 1)];
-      }
-    proto_up_all_.w = upload(m4, ci), proto_up_all_.b = upload(b4), proto_up_all_.cout = 4 * co, proto_up_all_.cin = ci, proto_up_all_.k = 1;
+    proto_up_all_ = concat_out({proto_up_[0], proto_up_[1], proto_up_[2], proto_up_[3]});
   }
 
-  if (v11()) {
-    arena_v11();
-  } else {
-  // activation arena for max_batch
-  const int nb = cfg_.max_batch, S = cfg_.imgsz;
-  const int s2 = S / 2, s4 = S / 4, s8 = S / 8, s16 = S / 16, s32 = S / 32;
-  const int c16 = chn(64), c32 = chn(128), c64 = chn(256), c128 = chn(512), c256 = chn(1024);
-  size_t total = 0;
-  auto sz = [&](int h, int w, int c) { total += ((size_t)nb * h * w * c + 63) / 64 * 64; };
-  sz(S, S, 4), sz(s2, s2, c16), sz(s4, s4, c32);
-  sz(s4, s4, 3 * c32 / 2), sz(s4, s4, c32 / 2), sz(s4, s4, c32);       // node 2
-  sz(s8, s8, c64);                                                      // 3
-  sz(s8, s8, 4 * c64 / 2), sz(s8, s8, c64 / 2);                         // 4
-  sz(s8, s8, c128 + c64);                                               // cat14
-  sz(s16, s16, c128);                                                   // 5
-  sz(s16, s16, 4 * c128 / 2), sz(s16, s16, c128 / 2);                   // 6
-  sz(s16, s16, c256 + c128);                                            // cat11
-  sz(s32, s32, c256);                                                   // 7
-  sz(s32, s32, 3 * c256 / 2), sz(s32, s32, c256 / 2), sz(s32, s32, c256);  // 8
-  sz(s32, s32, 2 * c256);                                               // sppcat
-  sz(s32, s32, c128 + c256);                                            // cat20
-  sz(s16, s16, 3 * c128 / 2), sz(s16, s16, c128 / 2);                   // 12
-  sz(s16, s16, c64 + c128);                                             // cat17
-  sz(s8, s8, 3 * c64 / 2), sz(s8, s8, c64 / 2), sz(s8, s8, c64);        // 15, p3
-  sz(s16, s16, 3 * c128 / 2), sz(s16, s16, c128 / 2), sz(s16, s16, c128);  // 18, p4
-  sz(s32, s32, 3 * c256 / 2), sz(s32, s32, c256 / 2), sz(s32, s32, c256);  // 21, p5
-  sz(s8, s8, 160), sz(s8, s8, 160), sz(s16, s16, 160), sz(s16, s16, 160), sz(s32, s32, 160), sz(s32, s32, 160);  // head t1/t2 per level (the levels' branches run concurrently)
-  sz(s8, s8, RAW_CT), sz(s16, s16, RAW_CT), sz(s32, s32, RAW_CT);       // rawhead
-  sz(s8, s8, npr_), sz(s4, s4, npr_), sz(s4, s4, npr_), sz(s4, s4, nm_);  // proto
-  sz(1, na_, 4 + cfg_.nc + nm_);                                        // pred
-  sz(1, cfg_.max_det, nm_);                                             // coef
-  arena_.alloc(total + 1024);
-  arena_used_ = 0;
-  v_.clear();
-  v_["x0"] = take(nb, S, S, 4);
-  v_["l0"] = take(nb, s2, s2, c16);
-  v_["l1"] = take(nb, s4, s4, c32);
-  v_["cat2"] = take(nb, s4, s4, 3 * c32 / 2), v_["tmp2"] = take(nb, s4, s4, c32 / 2), v_["l2"] = take(nb, s4, s4, c32);
-  v_["l3"] = take(nb, s8, s8, c64);
-  v_["cat4"] = take(nb, s8, s8, 4 * c64 / 2), v_["tmp4"] = take(nb, s8, s8, c64 / 2);
-  v_["cat14"] = take(nb, s8, s8, c128 + c64);
-  v_["l5"] = take(nb, s16, s16, c128);
-  v_["cat6"] = take(nb, s16, s16, 4 * c128 / 2), v_["tmp6"] = take(nb, s16, s16, c128 / 2);
-  v_["cat11"] = take(nb, s16, s16, c256 + c128);
-  v_["l7"] = take(nb, s32, s32, c256);
-  v_["cat8"] = take(nb, s32, s32, 3 * c256 / 2), v_["tmp8"] = take(nb, s32, s32, c256 / 2), v_["l8"] = take(nb, s32, s32, c256);
-  v_["sppcat"] = take(nb, s32, s32, 2 * c256);
-  v_["cat20"] = take(nb, s32, s32, c128 + c256);
-  v_["cat12"] = take(nb, s16, s16, 3 * c128 / 2), v_["tmp12"] = take(nb, s16, s16, c128 / 2);
-  v_["cat17"] = take(nb, s16, s16, c64 + c128);
-  v_["cat15"] = take(nb, s8, s8, 3 * c64 / 2), v_["tmp15"] = take(nb, s8, s8, c64 / 2), v_["p3"] = take(nb, s8, s8, c64);
-  v_["cat18"] = take(nb, s16, s16, 3 * c128 / 2), v_["tmp18"] = take(nb, s16, s16, c128 / 2), v_["p4"] = take(nb, s16, s16, c128);
-  v_["cat21"] = take(nb, s32, s32, 3 * c256 / 2), v_["tmp21"] = take(nb, s32, s32, c256 / 2), v_["p5"] = take(nb, s32, s32, c256);
-  v_["t1_0"] = take(nb, s8, s8, 160), v_["t2_0"] = take(nb, s8, s8, 160);
-  v_["t1_1"] = take(nb, s16, s16, 160), v_["t2_1"] = take(nb, s16, s16, 160);
-  v_["t1_2"] = take(nb, s32, s32, 160), v_["t2_2"] = take(nb, s32, s32, 160);
-  rawhead_[0] = take(nb, s8, s8, RAW_CT).p, rawhead_[1] = take(nb, s16, s16, RAW_CT).p, rawhead_[2] = take(nb, s32, s32, RAW_CT).p;
-  v_["pr1"] = take(nb, s8, s8, npr_), v_["pr2"] = take(nb, s4, s4, npr_), v_["pr3"] = take(nb, s4, s4, npr_);
-  v_["protos"] = take(nb, s4, s4, nm_);
-  pred_ = take(nb, 1, na_, 4 + cfg_.nc + nm_).p;
-  coef_ = take(nb, 1, cfg_.max_det, nm_).p;
-  }
-  // rawhead class padding column (index 67) is never written by a conv; keep it defined
-  HIP_OK(hipMemset(arena_.p, 0, arena_.n * sizeof(float)));
+  plan_arena(v11() ? arena_v11() : arena_v8());
   if (nms_ws_) (void)hipFree(nms_ws_);
   nms_ws_bytes_ = nms_workspace_bytes(cfg_.max_batch, na_);
   HIP_OK(hipMalloc((void**)&nms_ws_, nms_ws_bytes_));
@@ -744,9 +702,7 @@ void Detector::conv(const ConvW& w, const View& in, const View& out, int stride,
   g.a_fmt = in.fmt, g.out_fmt = out.fmt;
   if (res) g.res = res->p + res->co, g.ldr = res->ct, g.res_fmt = res->fmt;
   if (count_flops_) {
-    // model.0 is stored with a zero 4th input channel; count the real 3
-    const double kk = (&w == &cw_.at("model.0")) ? 27.0 : (double)g.K;
-    flops_ += 2.0 * g.M * g.N * kk;
+    flops_ += 2.0 * g.M * g.N * g.K;
     return;
   }
   gemm_launch(g, gemm_plan(g.M, g.N, g.K, act != ACT_NONE), s);
@@ -797,25 +753,23 @@ void Detector::c2f(int idx, const View& in, const View& out, int n, hipStream_t 
   conv(cw_.at(P + ".cv2"), cat.slice(0, (2 + ci.n) * ch), out, 1, ACT_SILU, nullptr, n, s);
 }
 
-// model.0 (Conv 3 -> 16, k3 s2): on its own kernel straight from the uint8 frame, or (counting mode) through the float
-// copy and the implicit GEMM
+// model.0 (Conv 3 -> 16, k3 s2) on its own kernel straight from the uint8 frame
 void Detector::conv0(const uint8_t* frames, int n, int flip, hipStream_t s) {
   const int S = cfg_.imgsz;
-  if (fmt_ == 1 || !count_flops_) {
-    const ConvW& w0 = cw_.at("model.0");
-    const View l0 = view("l0");
-    const long total = (long)n * (S / 2) * (S / 8);
-    MTGV_CHECK((S / 2) % 4 == 0 && w0.cout == 16 && w0.cin == 4 && w0.k == 3, ERR_RUNTIME, "detector: unexpected model.0 geometry");
-    MTGV_CHECK(((uintptr_t)frames & 7) == 0, ERR_INVALID, "detector: the frame buffer must be 8-byte aligned");
-    if (fmt_ == 1)
-      hipLaunchKernelGGL((conv0_u8_kernel<true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, frames, w0.w, w0.b, l0.p, S, flip, total);
-    else
-      hipLaunchKernelGGL((conv0_u8_kernel<false>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, frames, w0.w, w0.b, l0.p, S, flip, total);
-    HIP_OK(hipGetLastError());
-  } else {
-    if (!count_flops_) u8_to_f32_launch(frames, view("x0").p, (long)n * S * S, 3, 4, 1.0f, 0.0f, flip, s);
-    conv(cw_.at("model.0"), view("x0"), view("l0"), 2, ACT_SILU, nullptr, n, s);
+  const ConvW& w0 = cw_.at("model.0");
+  const View l0 = view("l0");
+  MTGV_CHECK((S / 2) % 4 == 0 && w0.cout == 16 && w0.cin == 4 && w0.k == 3, ERR_RUNTIME, "detector: unexpected model.0 geometry");
+  if (count_flops_) {  // K = 27: the weights' zero 4th input channel is not counted
+    flops_ += 2.0 * n * l0.H * l0.W * w0.cout * 27.0;
+    return;
   }
+  MTGV_CHECK(((uintptr_t)frames & 7) == 0, ERR_INVALID, "detector: the frame buffer must be 8-byte aligned");
+  const long total = (long)n * (S / 2) * (S / 8);
+  if (fmt_ == 1)
+    hipLaunchKernelGGL((conv0_u8_kernel<true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, frames, w0.w, w0.b, l0.p, S, flip, total);
+  else
+    hipLaunchKernelGGL((conv0_u8_kernel<false>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, frames, w0.w, w0.b, l0.p, S, flip, total);
+  HIP_OK(hipGetLastError());
 }
 
 // Proto: Conv3 -> ConvTranspose2d(k2,s2) as four scattered 1x1 GEMMs -> Conv3 -> Conv1
@@ -902,10 +856,12 @@ void Detector::head_tail(int n, int* n_det, float* boxes, float* conf, int* cls,
                          hipStream_t s) {
   const int S = cfg_.imgsz;
   const long tot = (long)n * na_;
-  hipLaunchKernelGGL(decode_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, rawhead_[0], rawhead_[1], rawhead_[2],
-                     pred_, n, cfg_.nc, nm_, S, na_);
+  float* const pred = v_.at("pred").p;
+  float* const coef = v_.at("coef").p;
+  hipLaunchKernelGGL(decode_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, v_.at("rawhead0").p, v_.at("rawhead1").p,
+                     v_.at("rawhead2").p, pred, n, cfg_.nc, nm_, S, na_);
   HIP_OK(hipGetLastError());
-  nms_launch(pred_, n, cfg_.nc, nm_, na_, cfg_.conf, cfg_.iou, cfg_.max_det, 7680.0f, n_det, boxes, conf, cls, keep_idx, coef_,
+  nms_launch(pred, n, cfg_.nc, nm_, na_, cfg_.conf, cfg_.iou, cfg_.max_det, 7680.0f, n_det, boxes, conf, cls, keep_idx, coef,
              nms_ws_, nms_ws_bytes_, s);
   join_into(s, 0);  // the prototype branch ran beside the heads, decode and NMS (one workgroup per frame: 32 of 256 CUs)
   if (mask_logits != nullptr) {
@@ -913,14 +869,14 @@ void Detector::head_tail(int n, int* n_det, float* boxes, float* conf, int* cls,
     const View pr = view("protos");
     const int npx = pr.H * pr.W;
     if (nm_ == 32 && mask_rows <= 16 && !count_flops_) {  // a handful of masks per frame: one pass over the prototypes
-      hipLaunchKernelGGL(mask_logits_kernel, dim3((unsigned)((npx + 255) / 256), (unsigned)n), dim3(256), 0, s, coef_, pr.p, n_det, boxes,
+      hipLaunchKernelGGL(mask_logits_kernel, dim3((unsigned)((npx + 255) / 256), (unsigned)n), dim3(256), 0, s, coef, pr.p, n_det, boxes,
                          mask_logits, npx, pr.W, mask_rows, cfg_.max_det, (float)pr.W / (float)S);
       HIP_OK(hipGetLastError());
       return;
     }
     // the batched GEMM writes only the rows of kept detections: the rest is cleared first
     HIP_OK(hipMemsetAsync(mask_logits, 0, (size_t)n * mask_rows * npx * sizeof(float), s));
-    GemmArgs g = linear_args(coef_, nm_, pr.p, nullptr, mask_logits, npx, mask_rows, npx, nm_, ACT_NONE);
+    GemmArgs g = linear_args(coef, nm_, pr.p, nullptr, mask_logits, npx, mask_rows, npx, nm_, ACT_NONE);
     g.batch = n;
     g.strideA = (long)cfg_.max_det * nm_;
     g.strideW = (long)npx * nm_;
@@ -979,6 +935,12 @@ void Detector::sppf(const std::string& P, const View& in, const View& spp, const
   conv(cw_.at(P + ".cv2"), spp, out, 1, ACT_SILU, nullptr, n, s);
 }
 
+// nearest-neighbour 2x of `in` into the leading channels of `out` (whole elements move: either format)
+void Detector::upsample2x(const View& in, const View& out, int n, hipStream_t s) {
+  if (count_flops_) return;
+  upsample2x_launch(in.p, in.ct, in.co, out.p, out.ct, out.co, n, in.H, in.W, in.C, s);
+}
+
 void Detector::forward_v8(const uint8_t* frames, int n, int flip, hipStream_t s) {
   const int c64 = chn(256), c128 = chn(512), c256 = chn(1024);
   auto V = [&](const char* k) -> View { return view(k); };
@@ -998,10 +960,10 @@ void Detector::forward_v8(const uint8_t* frames, int n, int flip, hipStream_t s)
   sppf("model.9", V("l8"), V("sppcat"), n9, n, s);
   // top-down
   const View cat11 = V("cat11"), cat14 = V("cat14"), cat17 = V("cat17"), cat20 = V("cat20");
-  if (!count_flops_) upsample2x_launch(n9.p, n9.ct, n9.co, cat11.p, cat11.ct, 0, n, n9.H, n9.W, c256, s);
+  upsample2x(n9, cat11, n, s);
   const View n12 = cat17.slice(c64, c128);          // concat 17 = [16, 12]
   c2f(12, cat11, n12, n, s);
-  if (!count_flops_) upsample2x_launch(n12.p, n12.ct, n12.co, cat14.p, cat14.ct, 0, n, n12.H, n12.W, c128, s);
+  upsample2x(n12, cat14, n, s);
   c2f(15, cat14, V("p3"), n, s);
   // P3 exists: the prototype branch (0.5 ms of chip-filling launches) and the P3 head leave the caller's stream; the
   // rest of the neck - 100..400-tile launches that cannot fill 256 CUs on their own - runs beside them
@@ -1021,9 +983,8 @@ void Detector::head_level_v8(int l, int n, hipStream_t s) {
   const char* feats[3] = {"p3", "p4", "p5"};
   const std::string ls = std::to_string(l);
   const View f = view(feats[l]), t1 = view("t1_" + ls), t2 = view("t2_" + ls);
+  const View rh = view("rawhead" + ls);
   conv(head_first_[l], f, t1, 1, ACT_SILU, nullptr, n, s);
-  View rh;
-  rh.p = rawhead_[l], rh.H = f.H, rh.W = f.W, rh.ct = RAW_CT, rh.co = 0, rh.C = RAW_CT;
   // box and coefficient branches: the 3x3 and the final 1x1 as one launch each (the class branch's 3 outputs are no column quad)
   conv_pair(head_box2_[l], t1.slice(0, 64), t2.slice(0, 64), 1, head_box3_[l], rh.slice(0, 64), ACT_NONE, n, s);
   conv(head_cls2_[l], t1.slice(64, 64), t2.slice(64, 64), 1, ACT_SILU, nullptr, n, s);
@@ -1033,7 +994,7 @@ void Detector::head_level_v8(int l, int n, hipStream_t s) {
 
 void Detector::raw(int n, float* pred, float* protos, hipStream_t s) {
   MTGV_CHECK(n > 0 && n <= last_n_, ERR_INVALID, "raw: n=%d but the last forward had %d frames", n, last_n_);
-  if (pred) HIP_OK(hipMemcpyAsync(pred, pred_, (size_t)n * no() * na_ * sizeof(float), hipMemcpyDeviceToDevice, s));
+  if (pred) HIP_OK(hipMemcpyAsync(pred, v_.at("pred").p, (size_t)n * no() * na_ * sizeof(float), hipMemcpyDeviceToDevice, s));
   if (protos) {
     const View pr = v_.at("protos");
     const long hw = (long)pr.H * pr.W, total = (long)n * nm_ * hw;

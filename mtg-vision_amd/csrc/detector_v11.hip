@@ -290,13 +290,11 @@ void Detector::build_v11() {
 // ---------------------------------------------------------------------------
 // activation arena
 // ---------------------------------------------------------------------------
-void Detector::arena_v11() {
-  const int nb = cfg_.max_batch, S = cfg_.imgsz;
-  const int s2 = S / 2, s4 = S / 4, s8 = S / 8, s16 = S / 16, s32 = S / 32;
+std::vector<Detector::ArenaBuf> Detector::arena_v11() const {
+  const int S = cfg_.imgsz, s2 = S / 2, s4 = S / 4, s8 = S / 8, s16 = S / 16, s32 = S / 32;
   const int c16 = chn(64), c32 = chn(128), c64 = chn(256), c128 = chn(512), c256 = chn(1024);
-  struct B { const char* name; int h, w, c; };
-  std::vector<B> bufs = {
-      {"x0", S, S, 4}, {"l0", s2, s2, c16}, {"l1", s4, s4, c32},
+  return {
+      {"l0", s2, s2, c16}, {"l1", s4, s4, c32},
       {"cat2", s4, s4, 48}, {"tmp2", s4, s4, 8}, {"l2", s4, s4, c64},
       {"l3", s8, s8, c64}, {"cat4", s8, s8, 96}, {"tmp4", s8, s8, 16},
       {"cat15", s8, s8, c128 + c128},                                     // concat 15 = [up(13), 4]
@@ -304,7 +302,8 @@ void Detector::arena_v11() {
       {"cat12", s16, s16, c256 + c128},                                   // concat 12 = [up(10), 6]
       {"l7", s32, s32, c256}, {"cat8", s32, s32, 384}, {"kcat8", s32, s32, 128}, {"tmp8", s32, s32, 64}, {"l8", s32, s32, c256},
       {"sppcat", s32, s32, 2 * c256}, {"l9", s32, s32, c256},
-      {"psacat", s32, s32, c256}, {"qkv", s32, s32, c256}, {"att", s32, s32, c128}, {"atty", s32, s32, c128}, {"ffn", s32, s32, c256},
+      // (the attention core and the positional encoding read qkv and att in f32)
+      {"psacat", s32, s32, c256}, {"qkv", s32, s32, c256, true}, {"att", s32, s32, c128, true}, {"atty", s32, s32, c128}, {"ffn", s32, s32, c256},
       {"cat21", s32, s32, c128 + c256},                                   // concat 21 = [20, 10]
       {"cat13", s16, s16, 192}, {"tmp13", s16, s16, 32},
       {"cat18", s16, s16, c64 + c128},                                    // concat 18 = [17, 13]
@@ -315,20 +314,10 @@ void Detector::arena_v11() {
       {"t1_0", s8, s8, 96}, {"t2_0", s8, s8, 96}, {"dwa_0", s8, s8, c64}, {"dwb_0", s8, s8, 64}, {"dwc_0", s8, s8, 64}, {"dwd_0", s8, s8, 64},
       {"t1_1", s16, s16, 96}, {"t2_1", s16, s16, 96}, {"dwa_1", s16, s16, c128}, {"dwb_1", s16, s16, 64}, {"dwc_1", s16, s16, 64}, {"dwd_1", s16, s16, 64},
       {"t1_2", s32, s32, 96}, {"t2_2", s32, s32, 96}, {"dwa_2", s32, s32, c256}, {"dwb_2", s32, s32, 64}, {"dwc_2", s32, s32, 64}, {"dwd_2", s32, s32, 64},
-      {"pr1", s8, s8, npr_}, {"pr2", s4, s4, npr_}, {"pr3", s4, s4, npr_}, {"protos", s4, s4, nm_},
+      {"pr1", s8, s8, npr_}, {"pr2", s4, s4, npr_}, {"pr3", s4, s4, npr_}, {"protos", s4, s4, nm_, true},
+      {"rawhead0", s8, s8, RAW_CT, true}, {"rawhead1", s16, s16, RAW_CT, true}, {"rawhead2", s32, s32, RAW_CT, true},
+      {"pred", 1, na_, 4 + cfg_.nc + nm_, true}, {"coef", 1, cfg_.max_det, nm_, true},
   };
-  size_t total = 0;
-  auto sz = [&](size_t n, int h, int w, int c) { total += (n * h * w * c + 63) / 64 * 64; };
-  for (const B& b : bufs) sz(nb, b.h, b.w, b.c);
-  sz(nb, s8, s8, RAW_CT), sz(nb, s16, s16, RAW_CT), sz(nb, s32, s32, RAW_CT);
-  sz(nb, 1, na_, 4 + cfg_.nc + nm_), sz(nb, 1, cfg_.max_det, nm_);
-  arena_.alloc(total + 1024);
-  arena_used_ = 0;
-  v_.clear();
-  for (const B& b : bufs) v_[b.name] = take(nb, b.h, b.w, b.c);
-  rawhead_[0] = take(nb, s8, s8, RAW_CT).p, rawhead_[1] = take(nb, s16, s16, RAW_CT).p, rawhead_[2] = take(nb, s32, s32, RAW_CT).p;
-  pred_ = take(nb, 1, na_, 4 + cfg_.nc + nm_).p;
-  coef_ = take(nb, 1, cfg_.max_det, nm_).p;
 }
 
 // ---------------------------------------------------------------------------
@@ -375,8 +364,7 @@ void Detector::c2psa(int idx, const View& in, const View& out, int n, hipStream_
   conv(cw_.at(P + ".cv1"), in, cat, 1, ACT_SILU, nullptr, n, s);
   const View b = cat.slice(c, c);
   const std::string A = P + ".m.0.attn";
-  View qkv = view("qkv"), att = view("att"), y = view("atty");
-  qkv.fmt = 0, att.fmt = 0;  // the attention core and the positional encoding read f32
+  const View qkv = view("qkv"), att = view("att"), y = view("atty");
   conv(cw_.at(A + ".qkv"), b, qkv, 1, ACT_NONE, nullptr, n, s);
   const int N = cat.H * cat.W;
   if (count_flops_) {
@@ -416,10 +404,10 @@ void Detector::forward_v11(const uint8_t* frames, int n, int flip, hipStream_t s
   const View n10 = cat21.slice(c128, c256);         // concat 21 = [20, 10]
   c2psa(10, V("l9"), n10, n, s);
   // top-down
-  if (!count_flops_) upsample2x_launch(n10.p, n10.ct, n10.co, cat12.p, cat12.ct, 0, n, n10.H, n10.W, c256, s);
+  upsample2x(n10, cat12, n, s);
   const View n13 = cat18.slice(c64, c128);          // concat 18 = [17, 13]
   c3k2(13, cat12, n13, n, s);
-  if (!count_flops_) upsample2x_launch(n13.p, n13.ct, n13.co, cat15.p, cat15.ct, 0, n, n13.H, n13.W, c128, s);
+  upsample2x(n13, cat15, n, s);
   c3k2(16, cat15, V("p3"), n, s);
   // the same fork-join as forward_v8: prototype branch and P3 / P4 heads beside the rest of the neck
   proto(head_, V("p3"), n, fork_after(s, 0));
@@ -438,9 +426,8 @@ void Detector::head_level_v11(int l, int n, hipStream_t s) {
   const char* feats[3] = {"p3", "p4", "p5"};
   const std::string ls = std::to_string(l);
   const View f = view(feats[l]), t1 = view("t1_" + ls), t2 = view("t2_" + ls);
-  View rh;
-  rh.p = rawhead_[l], rh.H = f.H, rh.W = f.W, rh.ct = RAW_CT, rh.co = 0, rh.C = RAW_CT;
-  conv(head_bc_[l], f, t1, 1, ACT_SILU, nullptr, n, s);
+  const View rh = view("rawhead" + ls);
+  conv(head_first_[l], f, t1, 1, ACT_SILU, nullptr, n, s);
   conv_pair(head_box2_[l], t1.slice(0, 64), t2.slice(0, 64), 1, head_box3_[l], rh.slice(0, 64), ACT_NONE, n, s);
   conv_pair(head_coef2_[l], t1.slice(64, 32), t2.slice(64, 32), 1, head_coef3_[l], rh.slice(RAW_COEF, nm_), ACT_NONE, n, s);
   // class branch: (depthwise 3x3, 1x1) twice, then the plain 1x1

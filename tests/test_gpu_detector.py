@@ -91,6 +91,7 @@ def test_forward_pred_and_protos(det_setup):
     print(f"box {box_err:.2e}px cls {cls_err:.2e} coef {coef_err:.2e} protos {proto_err:.2e}")
     assert box_err < 640 * 1e-4 and cls_err < 1e-4 and coef_err < 1e-4 and proto_err < 1e-4
     assert abs(det.flops_per_frame() / 1e9 - 12.0) < 3.0  # same order as the published 12.6 GFLOP (80 classes)
+    assert det.flops_per_frame() == 11_342_592_000.0  # exact count of this graph (nc = 3, model.0 with K = 27)
 
 
 def test_detect_matches_oracle(det_setup):

@@ -45,6 +45,7 @@ def test_yolo11_forward_pred_and_protos(det11, mode):
     gf = det.flops_per_frame() / 1e9
     print(f"yolo11n-seg: {gf:.2f} GFLOP / frame (nc = {nc})")
     assert 7.0 < gf < 13.0  # published: 10.4 GFLOP (80 classes)
+    assert det.flops_per_frame() == 9_631_846_400.0  # exact count of this graph (nc = 3, model.0 with K = 27)
 
 
 def test_yolo11_detect_matches_oracle(det11):
