@@ -259,7 +259,7 @@ MTGV_API int mtgv_op_linear(const float* a_dev, const float* w_dev, const float*
     g.res = res_dev;
     g.ldr = n;
     range_guard(g, a_dev, (long)m * k, (hipStream_t)stream);
-    gemm_launch(g, gemm_plan(m, n, k, act != 0), (hipStream_t)stream);
+    gemm_launch(g, (hipStream_t)stream);
   });
 }
 MTGV_API int64_t mtgv_op_linear_ex_part_floats(int32_t m, int32_t n, int32_t k, int32_t act, int32_t hw) {
@@ -291,14 +291,11 @@ MTGV_API int mtgv_op_linear_ex(const float* a_dev, const float* w_dev, const flo
       fold_shift_into_bias_launch(w_dev, a_shift_dev, bias_dev, fold_tmp.p, n, k, (hipStream_t)stream);
       g.bias = fold_tmp.p;
     }
-    const GemmPlan pl = gemm_plan(m, n, k, act != 0, a_scale_dev != nullptr);
     if (grn_part_dev) {
       g.grn_part = grn_part_dev;  // before the layout: the kernel choice depends on it
-      t_last_grn = gemm_grn_layout(g, pl);
-      g.segmax = t_last_grn.segmax;
-      g.grn_unit_rows = t_last_grn.unit_rows;
+      t_last_grn = gemm_grn_layout(g);
     }
-    gemm_launch(g, pl, (hipStream_t)stream);
+    gemm_launch(g, (hipStream_t)stream);
   });
 }
 MTGV_API int mtgv_op_conv2d(const float* x_dev, const float* w_dev, const float* bias_dev, float* out_dev, int32_t n, int32_t h,
@@ -317,7 +314,7 @@ MTGV_API int mtgv_op_conv2d(const float* x_dev, const float* w_dev, const float*
     g.OH = oh, g.OW = ow, g.OH2 = oh, g.OW2 = ow;
     g.ldo = cout;
     g.act = act;
-    gemm_launch(g, gemm_plan(g.M, g.N, g.K, act != 0), (hipStream_t)stream);
+    gemm_launch(g, (hipStream_t)stream);
   });
 }
 MTGV_API int mtgv_op_layernorm(const float* x_dev, const float* w_dev, const float* b_dev, float* out_dev, int64_t rows,

@@ -705,7 +705,7 @@ void Detector::conv(const ConvW& w, const View& in, const View& out, int stride,
     flops_ += 2.0 * g.M * g.N * g.K;
     return;
   }
-  gemm_launch(g, gemm_plan(g.M, g.N, g.K, act != ACT_NONE), s);
+  gemm_launch(g, s);
 }
 
 void Detector::conv_pair(const ConvW& w1, const View& in, const View& mid, int stride, const ConvW& w2, const View& out2, int act2, int n,
@@ -725,7 +725,7 @@ void Detector::conv_pair(const ConvW& w1, const View& in, const View& mid, int s
     g.a_fmt = in.fmt, g.out_fmt = mid.fmt;
     g.W2 = w2.w, g.bias2 = w2.b, g.Out2 = out2.p, g.N2 = w2.cout, g.ldo2 = out2.ct, g.o_off2 = out2.co, g.out_fmt2 = out2.fmt, g.act2 = act2;
     if (gemm_sp_chain_ok(g)) {
-      gemm_launch(g, gemm_plan(g.M, g.N, g.K, true), s);
+      gemm_launch(g, s);
       return;
     }
   }
@@ -793,7 +793,7 @@ void Detector::proto(const std::string& H, const View& p3, int n, hipStream_t s)
       g.os = 2, g.oy = 0, g.ox = 0, g.os_nq = npr_, g.OH2 = out.H, g.OW2 = out.W;
       g.ldo = out.ct;
       g.a_fmt = in.fmt, g.out_fmt = out.fmt;
-      gemm_launch(g, gemm_plan(g.M, g.N, g.K), s);
+      gemm_launch(g, s);
     }
     for (int q = 0; q < 4 && !single; ++q) {
       const ConvW& w = proto_up_[q];
@@ -808,7 +808,7 @@ void Detector::proto(const std::string& H, const View& p3, int n, hipStream_t s)
       if (count_flops_)
         flops_ += 2.0 * g.M * g.N * g.K;
       else
-        gemm_launch(g, gemm_plan(g.M, g.N, g.K), s);
+        gemm_launch(g, s);
     }
   }
   conv_pair(cw_.at(H + ".proto.cv2"), view("pr2"), view("pr3"), 1, cw_.at(H + ".proto.cv3"), view("protos"), ACT_SILU, n, s);
@@ -886,7 +886,7 @@ void Detector::head_tail(int n, int* n_det, float* boxes, float* conf, int* cls,
     g.crop_rows = cfg_.max_det;
     g.crop_scale = (float)pr.W / (float)S;
     g.crop_w = pr.W;
-    gemm_launch(g, gemm_plan(g.M, g.N, g.K), s);
+    gemm_launch(g, s);
   }
 }
 

@@ -171,13 +171,10 @@ bool run_block(const float* x, float* out, int n, int h, int w, int c, int act, 
 
   GemmArgs g1 = linear_args(ws.t2, c, bw.w1, bw.b1, ws.hid, 4 * c, M, 4 * c, c, act);
   g1.a_fmt = fmt;
-  const GemmPlan p1 = gemm_plan(M, 4 * c, c, true);
   g1.hw = hw;
   g1.grn_part = ws.part;  // set before the layout is computed: which kernel takes the launch depends on it
-  const GrnLayout gl = gemm_grn_layout(g1, p1);
-  g1.segmax = gl.segmax;
-  g1.grn_unit_rows = gl.unit_rows;
-  gemm_launch(g1, p1, s);
+  const GrnLayout gl = gemm_grn_layout(g1);
+  gemm_launch(g1, s);
 
   grn_finalize_launch(ws.part, gl, n, hw, 4 * c, bw.gamma, ws.scale, s);
 
@@ -192,7 +189,7 @@ bool run_block(const float* x, float* out, int n, int h, int w, int c, int act, 
     fold_shift_into_bias_launch(bw.w2, bw.beta, bw.b2, ws.bfold, c, 4 * c, s);
     g2.bias = ws.bfold;
   }
-  gemm_launch(g2, gemm_plan(M, c, 4 * c, false, true), s);
+  gemm_launch(g2, s);
   return false;
 }
 
@@ -497,15 +494,10 @@ void Encoder::body(int n, float* z_out, hipStream_t s) {
     g.KH = 4, g.KW = 1, g.stride = 4, g.stride_w = 1, g.pad = 0;
     g.OH = sh_[0], g.OW = sw_[0], g.OH2 = sh_[0], g.OW2 = sw_[0];
     g.ldo = d[0];
-    const GemmPlan pl = gemm_plan(g.M, g.N, g.K);
-    if (gemm_ln_fusable(g, pl)) {  // the stem's LayerNorm in the conv's epilogue: its output is written once
-      g.Out = cur;
-      g.ln_w = stem_ln_w_, g.ln_b = stem_ln_b_, g.ln_eps = 1e-6f;
-      gemm_launch(g, pl, s);
-    } else {
-      gemm_launch(g, pl, s);
-      ln_rows_launch(alt, d[0], 0, cur, d[0], 0, stem_ln_w_, stem_ln_b_, g.M, d[0], 1e-6f, s);
-    }
+    const bool fuse_ln = gemm_ln_fusable(g);  // the stem's LayerNorm in the conv's epilogue: its output is written once
+    if (fuse_ln) g.Out = cur, g.ln_w = stem_ln_w_, g.ln_b = stem_ln_b_, g.ln_eps = 1e-6f;
+    gemm_launch(g, s);
+    if (!fuse_ln) ln_rows_launch(alt, d[0], 0, cur, d[0], 0, stem_ln_w_, stem_ln_b_, g.M, d[0], 1e-6f, s);
   }
 
   const char* const ln_env = getenv("MTGV_LN_FUSE");  // read per call: a test compares both forms in one process
@@ -537,7 +529,7 @@ void Encoder::body(int n, float* z_out, hipStream_t s) {
       g.KH = 2, g.KW = 2, g.stride = 2, g.pad = 0;
       g.OH = h, g.OW = w, g.OH2 = h, g.OW2 = w;
       g.ldo = c;
-      gemm_launch(g, gemm_plan(g.M, g.N, g.K), s);
+      gemm_launch(g, s);
     }
     const BlockWsSize z = block_ws_size(n, h, w, c);
     BlockWs ws;
@@ -576,7 +568,7 @@ void Encoder::body(int n, float* z_out, hipStream_t s) {
     const int zc = zs / P;
     GemmArgs g = linear_args(cur, c3, pool_w_, pool_b_, head_b2_.p, zc, n * P, zc, c3,
                              ht == MTGV_HEAD_CONV_ACT_MLP ? ACT_MISH : ACT_NONE);
-    gemm_launch(g, gemm_plan(g.M, g.N, g.K), s);
+    gemm_launch(g, s);
     ln_rows_launch(head_b2_.p, zc, 0, feat, zc, 0, pool_ln_w_, pool_ln_b_, (long)n * P, zc, 1e-6f, s);
     feat_dim = zs;
   } else {
@@ -587,12 +579,12 @@ void Encoder::body(int n, float* z_out, hipStream_t s) {
   }
   if (mlp) {
     GemmArgs g = linear_args(feat, feat_dim, head_w_, head_b_, head_b2_.p, zs, n, zs, feat_dim, ACT_MISH);
-    gemm_launch(g, gemm_plan(g.M, g.N, g.K), s);
+    gemm_launch(g, s);
     GemmArgs g2 = linear_args(head_b2_.p, zs, head2_w_, head2_b_, z_out, zs, n, zs, zs, ACT_NONE);
-    gemm_launch(g2, gemm_plan(g2.M, g2.N, g2.K), s);
+    gemm_launch(g2, s);
   } else {
     GemmArgs g = linear_args(feat, feat_dim, head_w_, head_b_, z_out, zs, n, zs, feat_dim, ACT_NONE);
-    gemm_launch(g, gemm_plan(g.M, g.N, g.K), s);
+    gemm_launch(g, s);
   }
 }
 

@@ -57,10 +57,11 @@ struct GemmArgs {
   int act = ACT_NONE;
 
   // GRN (convnextv2.py:171-174): per-(tile, image-segment, n) partial sums of out^2
-  float* grn_part = nullptr;    // [tiles_m][segmax][N]
+  float* grn_part = nullptr;    // [units][segmax][N], sized by gemm_grn_layout
   int hw = 0;                   // rows per image for GRN / prologue segmentation
+  // written by gemm_launch (GrnLayout::segmax / unit_rows of the launch) when grn_part is set; callers leave them alone
   int segmax = 0;
-  int grn_unit_rows = 0;        // rows per partial unit the caller planned for (GrnLayout::unit_rows); 0: not checked
+  int grn_unit_rows = 0;
   // GRN apply fused into the A load of pwconv2: a' = a * a_scale[img][k] + a_shift[k]
   const float* a_scale = nullptr;
   const float* a_shift = nullptr;
@@ -88,21 +89,19 @@ struct GemmArgs {
   float ln_eps = 0.f;
 };
 
-struct GemmPlan {
-  int tm, tn, bk;               // tile: BM = 128*tm, BN = 32*tn
-  int tiles_m, tiles_n;
-  int bm() const { return 128 * tm; }
-  int bn() const { return 32 * tn; }
-};
+// A is gathered through a window (anything but a dense 1x1 / linear)
+inline bool is_conv(const GemmArgs& a) { return !(a.KH == 1 && a.KW == 1 && a.stride == 1 && a.stride_w <= 1 && a.pad == 0); }
+// output row m is scattered to another grid (orow != m)
+inline bool is_remap(const GemmArgs& a) { return !(a.os == 1 && a.oy == 0 && a.ox == 0 && a.OH2 == a.OH && a.OW2 == a.OW); }
 
-// heavy_epilogue: the launch applies an activation (transcendentals per output element)
-// scaled_a: the launch applies the GRN multiplier to A (a_scale)
-GemmPlan gemm_plan(int M, int N, int K, bool heavy_epilogue = false, bool scaled_a = false);
-int gemm_grn_segmax(const GemmPlan& p, int hw);
-size_t gemm_grn_part_floats(const GemmPlan& p, int N, int hw);
-void gemm_launch(const GemmArgs& a, const GemmPlan& p, hipStream_t s);
+// Runs the launch `a` describes.  The kernel and its tile follow from the arguments alone: the LDS-DMA kernel
+// (gemm_sp.h) when it takes the launch, else the convert-on-load kernel (gemm_kernel.h) with the tile of its cost model
+// (MTGV_GEMM_TILE=tm,tn,bk forces one; top-k launches have a fixed tile).
+void gemm_launch(const GemmArgs& a, hipStream_t s);
 // can this launch (no activation, no residual, not routed to the LDS-DMA kernel) normalise its rows in the epilogue?
-bool gemm_ln_fusable(const GemmArgs& a, const GemmPlan& p);
+bool gemm_ln_fusable(const GemmArgs& a);
+// candidate groups of a top-k launch (a.topk > 0): per row, `slots` groups of `cols` columns each
+void gemm_topk_layout(const GemmArgs& a, int* slots, int* cols);
 
 // Operand precision of every GEMM launch of the process (see gemm_f32.hip): GEMM_PREC_F32 = f32 MFMA,
 // GEMM_PREC_F16X3 = fp16 hi+lo split, three fp16 MFMAs per product.  Initial value from MTGV_GEMM_PREC=f32|f16x3.
@@ -134,20 +133,18 @@ double gemm_profile_bytes();  // compulsory operand + result bytes of the launch
 void gemm_profile_begin(const GemmArgs& a, hipStream_t s, int sp, double fill, double bytes);
 void gemm_profile_end(hipStream_t s);
 
-// Layout of the GRN partial sums a launch with these arguments writes (grn_part itself need not be set yet):
-// [ceil(M / unit_rows)][segmax][N] floats.  Depends on which kernel gemm_launch will pick for the arguments.
+// Layout of the GRN partial sums a launch with these arguments writes: [ceil(M / unit_rows)][segmax][N] floats.
+// Depends on which kernel gemm_launch will pick, so grn_part must be set (to any non-null pointer) already.
 struct GrnLayout {
   int unit_rows = 0, segmax = 0;
   size_t floats = 0;
 };
-GrnLayout gemm_grn_layout(const GemmArgs& a, const GemmPlan& p);
+GrnLayout gemm_grn_layout(const GemmArgs& a);
 // upper bound of GrnLayout::floats over every kernel / tile that could be chosen
 size_t gemm_grn_part_floats_max(int M, int N, int hw);
 
 // sum the partials of one GEMM into the GRN apply table
 //   scale[img][n] = gamma[n] * Gx / (mean_n Gx + 1e-6) + 1,  Gx = sqrt(sum x^2)
-void grn_finalize_launch(const float* part, const GemmPlan& p, int n_img, int hw, int N, const float* gamma,
-                         float* scale, hipStream_t s);
 void grn_finalize_launch(const float* part, const GrnLayout& l, int n_img, int hw, int N, const float* gamma, float* scale,
                          hipStream_t s);
 

@@ -38,7 +38,7 @@ struct GemmProf {
   double flops = 0;
   double bytes = 0;  // compulsory HBM bytes: every operand element read once, every output written once
   long launches = 0;
-  struct Rec { int M, N, K, KH, stride, batch, act, apro, grn, topk, sp; double bytes, fill, xflops; };
+  struct Rec { int M, N, K, KH, stride, batch, act, apro, grn, topk, tm, tn, bk, sp; double bytes, fill, xflops; };
   std::vector<Rec> recs;
 } g_prof;
 }  // namespace
@@ -62,10 +62,9 @@ void gemm_profile_dump(const char* path) {
     float t = 0.f;
     HIP_OK(hipEventElapsedTime(&t, g_prof.ev[i], g_prof.ev[i + 1]));
     const auto& r = g_prof.recs[i / 2];
-    const GemmPlan pl = r.topk ? GemmPlan{1, 2, 16, 0, 0} : gemm_plan(r.M, r.N, r.K, r.act != 0, r.apro != 0);
     const double fl = 2.0 * r.M * r.N * r.K * r.batch + r.xflops;  // xflops: a second layer chained into the launch
     fprintf(f, "%zu,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%.4f,%.2f,%.0f,%d,%.0f,%.0f\n", i / 2, r.M, r.N, r.K, r.KH, r.stride, r.batch, r.act,
-            r.apro, r.grn, r.topk, pl.tm, pl.tn, pl.bk, t, fl / (t * 1e-3) / 1e12, r.bytes, r.sp, r.fill, r.xflops);
+            r.apro, r.grn, r.topk, r.tm, r.tn, r.bk, t, fl / (t * 1e-3) / 1e12, r.bytes, r.sp, r.fill, r.xflops);
   }
   fclose(f);
   gemm_sp_stamps_dump((std::string(path) + ".stamps").c_str());
@@ -87,8 +86,9 @@ void gemm_profile_read(double* ms, double* flops, long* launches) {
   if (launches) *launches = g_prof.launches;
 }
 
+// pl: the convert-on-load tile of the launch (recorded also for launches another kernel runs)
 // fill: bytes the launch's tiles pull into LDS (every tile its A and B panels; 4 bytes per element in either format)
-static void prof_begin(const GemmArgs& a, hipStream_t s, int sp, double fill, double bytes_override = -1.0) {
+static void prof_begin(const GemmArgs& a, const GemmPlan& pl, hipStream_t s, int sp, double fill, double bytes_override = -1.0) {
   if (!g_prof.on) return;
   while (g_prof.ev.size() < g_prof.used + 2) {
     hipEvent_t e;
@@ -99,8 +99,7 @@ static void prof_begin(const GemmArgs& a, hipStream_t s, int sp, double fill, do
   const double xfl = a.W2 != nullptr ? 2.0 * (double)a.M * a.N2 * a.N : 0.0;
   g_prof.flops += 2.0 * (double)a.M * a.N * a.K * a.batch + xfl;
   {
-    const bool conv = !(a.KH == 1 && a.KW == 1 && a.stride == 1 && a.stride_w <= 1 && a.pad == 0);
-    const double a_el = conv ? (double)(a.M / (a.OH * a.OW)) * a.H * a.Wd * a.Cin : (double)a.M * a.K;
+    const double a_el = is_conv(a) ? (double)(a.M / (a.OH * a.OW)) * a.H * a.Wd * a.Cin : (double)a.M * a.K;
     const double w_el = (double)a.N * a.K;
     // (a chained launch stores only its second layer's output and reads the second weight matrix besides)
     const double o_el = a.topk > 0 ? (double)a.M * ceil_div(a.N, 64) * a.topk * 2
@@ -110,7 +109,8 @@ static void prof_begin(const GemmArgs& a, hipStream_t s, int sp, double fill, do
                        a.batch * (o_el + r_el));
     if (bytes_override >= 0.0) by = bytes_override;
     g_prof.bytes += by;
-    g_prof.recs.push_back({a.M, a.N, a.K, a.KH, a.stride, a.batch, a.act, a.a_scale != nullptr, a.grn_part != nullptr, a.topk, sp, by, fill, xfl});
+    g_prof.recs.push_back({a.M, a.N, a.K, a.KH, a.stride, a.batch, a.act, a.a_scale != nullptr, a.grn_part != nullptr, a.topk,
+                           pl.tm, pl.tn, pl.bk, sp, by, fill, xfl});
   }
   g_prof.launches += 1;
 }
@@ -119,8 +119,6 @@ static void prof_end(hipStream_t s) {
   HIP_OK(hipEventRecord(g_prof.ev[g_prof.used + 1], s));
   g_prof.used += 2;
 }
-void gemm_profile_begin(const GemmArgs& a, hipStream_t s, int sp, double fill, double bytes) { prof_begin(a, s, sp, fill, bytes); }
-void gemm_profile_end(hipStream_t s) { prof_end(s); }
 
 // ---------------------------------------------------------------------------
 // pre-split weight registry (f16x3)
@@ -246,17 +244,20 @@ void gemm_set_precision(int prec) {
   g_prec = prec;
 }
 
-GemmPlan gemm_plan(int M, int N, int K, bool heavy_epilogue, bool scaled_a) {
-  GemmPlan pl;
-  if (const char* e = getenv("MTGV_GEMM_TILE")) {
+static GemmPlan tile(int tm, int tn, int bk, int M, int N) {
+  GemmPlan pl{tm, tn, bk, 0, 0};
+  pl.tiles_m = ceil_div(M, pl.bm());
+  pl.tiles_n = ceil_div(N, pl.bn());
+  return pl;
+}
+
+// heavy_epilogue: the launch applies an activation (transcendentals per output element)
+// scaled_a: the launch applies the GRN multiplier to A (a_scale)
+static GemmPlan gemm_plan(int M, int N, int K, bool heavy_epilogue, bool scaled_a) {
+  if (const char* e = getenv("MTGV_GEMM_TILE")) {  // read at every launch (tests switch it within one process)
     int tm = 0, tn = 0, bk = 0;
-    if (sscanf(e, "%d,%d,%d", &tm, &tn, &bk) == 3 && (tm == 1 || tm == 2) && tn >= 1 && tn <= 5 &&
-        (bk == 16 || bk == 32)) {
-      pl.tm = tm, pl.tn = tn, pl.bk = bk;
-      pl.tiles_m = ceil_div(M, pl.bm());
-      pl.tiles_n = ceil_div(N, pl.bn());
-      return pl;
-    }
+    if (sscanf(e, "%d,%d,%d", &tm, &tn, &bk) == 3 && (tm == 1 || tm == 2) && tn >= 1 && tn <= 5 && (bk == 16 || bk == 32))
+      return tile(tm, tn, bk, M, N);
   }
   // Cost model fitted to tile sweeps on MI355X (tools/gemm_sweep.py, profiles/r01_gemm_sweep.txt):
   // narrow tiles with BK = 16 win - more resident blocks per CU overlap one block's tile load and
@@ -283,33 +284,37 @@ GemmPlan gemm_plan(int M, int N, int K, bool heavy_epilogue, bool scaled_a) {
     const double cost = rounds * 128.0 * 32.0 * tn * ((double)K + ov) / eff[tn];
     if (best < 0 || cost < best) best = cost, best_tn = tn;
   }
-  pl.tm = 1;
-  pl.tn = best_tn;
-  pl.bk = (best_tn == 1 && K >= 256) ? 32 : 16;  // sweep: BK 32 pays only for the narrowest tile on long K
-  pl.tiles_m = ceil_div(M, pl.bm());
-  pl.tiles_n = ceil_div(N, pl.bn());
-  return pl;
+  return tile(1, best_tn, (best_tn == 1 && K >= 256) ? 32 : 16, M, N);  // sweep: BK 32 pays only for the narrowest tile on long K
 }
 
-int gemm_grn_segmax(const GemmPlan& p, int hw) { return (p.bm() - 1) / hw + 2; }
-
-size_t gemm_grn_part_floats(const GemmPlan& p, int N, int hw) {
-  return (size_t)p.tiles_m * gemm_grn_segmax(p, hw) * N;
+// the convert-on-load kernel's tile for a launch: the top-k epilogue has one instance (gemm_dispatch), every other
+// launch gets the cost model's choice
+static GemmPlan plan_for(const GemmArgs& a) {
+  if (a.topk > 0) return tile(1, 2, 16, a.M, a.N);
+  return gemm_plan(a.M, a.N, a.K, a.act != ACT_NONE, a.a_scale != nullptr);
 }
 
-GrnLayout gemm_grn_layout(const GemmArgs& a, const GemmPlan& p) {
+void gemm_profile_begin(const GemmArgs& a, hipStream_t s, int sp, double fill, double bytes) {
+  if (g_prof.on) prof_begin(a, plan_for(a), s, sp, fill, bytes);
+}
+void gemm_profile_end(hipStream_t s) { prof_end(s); }
+
+// partial sums in units of the LDS-DMA kernel's wave rows or of the convert-on-load kernel's block rows
+static GrnLayout grn_layout(const GemmArgs& a, const SpPlan& sp, const GemmPlan& pl) {
   GrnLayout l;
-  const SpPlan sp = gemm_sp_plan(a);
-  const int hw = a.hw > 0 ? a.hw : 1;
-  if (sp.cfg >= 0) {
-    l.unit_rows = sp.unit_rows;
-    l.segmax = (sp.unit_rows - 1) / hw + 2;
-  } else {
-    l.unit_rows = p.bm();
-    l.segmax = gemm_grn_segmax(p, hw);
-  }
+  l.unit_rows = sp.cfg >= 0 ? sp.unit_rows : pl.bm();
+  l.segmax = (l.unit_rows - 1) / (a.hw > 0 ? a.hw : 1) + 2;
   l.floats = (size_t)ceil_div(a.M, l.unit_rows) * l.segmax * a.N;
   return l;
+}
+
+GrnLayout gemm_grn_layout(const GemmArgs& a) { return grn_layout(a, gemm_sp_plan(a), plan_for(a)); }
+
+void gemm_topk_layout(const GemmArgs& a, int* slots, int* cols) {
+  if (gemm_sp_topk_layout(a, slots, cols)) return;
+  const GemmPlan pl = plan_for(a);  // one group per column tile
+  *slots = pl.tiles_n;
+  *cols = pl.bn();
 }
 
 size_t gemm_grn_part_floats_max(int M, int N, int hw) {
@@ -321,22 +326,24 @@ size_t gemm_grn_part_floats_max(int M, int N, int hw) {
   return mx;
 }
 
-bool gemm_ln_fusable(const GemmArgs& a, const GemmPlan& pl) {
-  const bool conv = !(a.KH == 1 && a.KW == 1 && a.stride == 1 && a.stride_w <= 1 && a.pad == 0);
-  const bool remap = !(a.os == 1 && a.oy == 0 && a.ox == 0 && a.OH2 == a.OH && a.OW2 == a.OW);
+static bool ln_fusable(const GemmArgs& a, const GemmPlan& pl) {
   // the instance that carries the epilogue: conv gather, 128 x 96 x 16 tile; one tile per row, whole tiles, plain f32 rows out
-  if (!(pl.tm == 1 && pl.tn == 3 && pl.bk == 16 && conv && a.N == pl.bn() && a.M % pl.bm() == 0)) return false;
+  if (!(pl.tm == 1 && pl.tn == 3 && pl.bk == 16 && is_conv(a) && a.N == pl.bn() && a.M % pl.bm() == 0)) return false;
   if (a.batch != 1 || a.act != ACT_NONE || a.res != nullptr || a.a_scale != nullptr || a.grn_part != nullptr || a.topk > 0 ||
-      a.crop_boxes != nullptr || a.m_count != nullptr || remap || a.out_fmt != 0 || a.a_fmt != 0)
+      a.crop_boxes != nullptr || a.m_count != nullptr || is_remap(a) || a.out_fmt != 0 || a.a_fmt != 0)
     return false;
   GemmArgs t = a;
   t.ln_w = nullptr;
   return gemm_sp_plan(t).cfg < 0;  // (the LDS-DMA kernel has no such epilogue)
 }
 
-void gemm_launch(const GemmArgs& a, const GemmPlan& pl, hipStream_t s) {
+bool gemm_ln_fusable(const GemmArgs& a) { return ln_fusable(a, plan_for(a)); }
+
+void gemm_launch(const GemmArgs& args, hipStream_t s) {
+  GemmArgs a = args;
+  const GemmPlan pl = plan_for(a);
   if (a.ln_w != nullptr)
-    MTGV_CHECK(a.ln_b != nullptr && gemm_ln_fusable(a, pl), ERR_INVALID, "gemm: this launch cannot normalise its rows in the epilogue");
+    MTGV_CHECK(a.ln_b != nullptr && ln_fusable(a, pl), ERR_INVALID, "gemm: this launch cannot normalise its rows in the epilogue");
   MTGV_CHECK(a.batch >= 1 && a.batch <= 65535, ERR_INVALID, "gemm: batch=%d", a.batch);
   MTGV_CHECK(a.M > 0 && a.N > 0 && a.K > 0, ERR_INVALID, "gemm: empty problem M=%d N=%d K=%d", a.M, a.N, a.K);
   MTGV_CHECK(a.K % 4 == 0 && a.Cin % 4 == 0 && a.c_total % 4 == 0 && a.c_off % 4 == 0, ERR_INVALID,
@@ -344,27 +351,24 @@ void gemm_launch(const GemmArgs& a, const GemmPlan& pl, hipStream_t s) {
   MTGV_CHECK(a.K == a.KH * a.KW * a.Cin, ERR_INVALID, "gemm: K=%d != %d*%d*%d", a.K, a.KH, a.KW, a.Cin);
   MTGV_CHECK(((uintptr_t)a.A % 16) == 0 && ((uintptr_t)a.W % 16) == 0, ERR_INVALID, "gemm: operands must be 16-byte aligned");
   MTGV_CHECK((long)a.M * (long)(a.OH * a.OW > a.hw ? a.OH * a.OW : a.hw) < (1l << 40), ERR_INVALID, "gemm: M too large for fastdiv");
-  const bool conv = !(a.KH == 1 && a.KW == 1 && a.stride == 1 && a.stride_w <= 1 && a.pad == 0);
+  const bool conv = is_conv(a);
   const bool apro = a.a_scale != nullptr;
   MTGV_CHECK(!(apro && conv), ERR_INVALID, "gemm: GRN prologue only on 1x1");
   MTGV_CHECK(!(apro && a.act != ACT_NONE), ERR_INVALID, "gemm: GRN prologue is only combined with a linear epilogue");
   MTGV_CHECK(a.a_shift == nullptr, ERR_INVALID, "gemm: fold the GRN shift into the bias (fold_shift_into_bias_launch)");
   if (!conv) MTGV_CHECK(a.OH == a.H && a.OW == a.Wd, ERR_INVALID, "gemm: 1x1 geometry mismatch");
   if (apro || a.grn_part) MTGV_CHECK(a.hw > 0 && a.M % a.hw == 0, ERR_INVALID, "gemm: hw=%d must divide M=%d", a.hw, a.M);
-  {
-    const SpPlan sp = gemm_sp_plan(a);  // the LDS-DMA split kernel takes every launch it can run
-    if (sp.cfg >= 0) {
-      if (a.grn_part) MTGV_CHECK(a.hw > 0 && a.M % a.hw == 0, ERR_INVALID, "gemm: hw=%d must divide M=%d", a.hw, a.M);
-      prof_begin(a, s, 1, g_prof.on ? gemm_sp_fill_bytes(a, sp) : 0.0);
-      gemm_sp_launch(a, sp, s);
-      prof_end(s);
-      return;
-    }
-  }
+  const SpPlan sp = gemm_sp_plan(a);  // the LDS-DMA split kernel takes every launch it can run
   if (a.grn_part) {
-    MTGV_CHECK(a.segmax >= gemm_grn_segmax(pl, a.hw), ERR_INVALID, "gemm: segmax too small");
-    MTGV_CHECK(a.grn_unit_rows == 0 || a.grn_unit_rows == pl.bm(), ERR_RUNTIME,
-               "gemm: GRN partials planned for %d-row units, this launch writes %d-row units", a.grn_unit_rows, pl.bm());
+    const GrnLayout l = grn_layout(a, sp, pl);
+    a.segmax = l.segmax;
+    a.grn_unit_rows = l.unit_rows;
+  }
+  if (sp.cfg >= 0) {
+    prof_begin(a, pl, s, 1, g_prof.on ? gemm_sp_fill_bytes(a, sp) : 0.0);
+    gemm_sp_launch(a, sp, s);
+    prof_end(s);
+    return;
   }
 
   MTGV_CHECK(a.os_nq == 0, ERR_INVALID, "gemm: the grouped scatter epilogue (os_nq) exists on the LDS-DMA kernel only");
@@ -389,14 +393,14 @@ void gemm_launch(const GemmArgs& a, const GemmPlan& pl, hipStream_t s) {
     const double s_bytes = a.a_scale != nullptr && a.hw > 0 ? (double)(a.M / a.hw) * a.K * 4.0 : 0.0;
     g.off32_ok = a_bytes < lim && w_bytes < lim && s_bytes < lim;
   }
-  g.remap = !(a.os == 1 && a.oy == 0 && a.ox == 0 && a.OH2 == a.OH && a.OW2 == a.OW);
+  g.remap = is_remap(a);
   const int grid = pl.tiles_m * pl.tiles_n;
 
   if (a.topk > 0) {
-    MTGV_CHECK(pl.tm == 1 && pl.tn == 2 && pl.bk == 16 && !conv && !apro, ERR_INVALID, "gemm: top-k epilogue needs the 128x64x16 tile");
+    MTGV_CHECK(!conv && !apro, ERR_INVALID, "gemm: top-k epilogue needs the 128x64x16 tile");
     MTGV_CHECK(a.cand_s != nullptr && a.cand_i != nullptr && a.topk <= 128, ERR_INVALID, "gemm: bad top-k arguments");
   }
-  prof_begin(a, s, 0, (double)grid * a.batch * (pl.bm() + pl.bn()) * a.K * 4.0);
+  prof_begin(a, pl, s, 0, (double)grid * a.batch * (pl.bm() + pl.bn()) * a.K * 4.0);
   const bool found = gemm_precision() == GEMM_PREC_F16X3 ? gemm_dispatch_f16x3(g, pl, conv, apro, grid, s)
                                                          : gemm_dispatch_f32(g, pl, conv, apro, grid, s);
   if (found) {
@@ -472,14 +476,6 @@ void grn_finalize_launch(const float* part, const GrnLayout& l, int n_img, int h
   hipLaunchKernelGGL(grn_finalize_kernel, dim3(n_img), dim3(256), lds, s, part, l.unit_rows, l.segmax, hw, N,
                      make_fastdiv((uint32_t)hw), make_fastdiv((uint32_t)l.unit_rows), gamma, scale);
   HIP_OK(hipGetLastError());
-}
-
-void grn_finalize_launch(const float* part, const GemmPlan& p, int n_img, int hw, int N, const float* gamma, float* scale,
-                         hipStream_t s) {
-  GrnLayout l;
-  l.unit_rows = p.bm();
-  l.segmax = gemm_grn_segmax(p, hw);
-  grn_finalize_launch(part, l, n_img, hw, N, gamma, scale, s);
 }
 
 }  // namespace mtgv

@@ -30,6 +30,14 @@ struct GemmDev {
   int off32_ok;  // every operand of the launch spans less than 4 GiB: 32-bit byte offsets are enough
 };
 
+// tile of one launch (chosen by gemm_launch, gemm_f32.hip)
+struct GemmPlan {
+  int tm, tn, bk;  // BM = 128*tm, BN = 32*tn
+  int tiles_m, tiles_n;
+  int bm() const { return 128 * tm; }
+  int bn() const { return 32 * tn; }
+};
+
 // x = hi + lo + O(2^-22 |x|) while lo is a normal fp16 (|x| >= 2^-3); below that lo is subnormal and the error floor is
 // 2^-25 ABSOLUTE (fp16 subnormals are kept by the matrix unit).  Registered weights therefore carry a power-of-two scale
 // per row (wscale, undone on the f32 accumulator) that puts the row maximum at 2^13..2^14; activations are O(1) per row

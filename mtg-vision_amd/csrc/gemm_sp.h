@@ -28,10 +28,11 @@ SpPlan gemm_sp_plan(const GemmArgs& a);
 // true when a dense [M][K] x [N][K]^T launch with these sizes would take SP8 activations (producer kernels ask before
 // choosing their output format)
 bool gemm_sp_takes_sp8(const float* W, int M, int N, int K, int lda, int c_off);
+// only through gemm_launch, which has checked the arguments and filled in a.segmax for GRN launches
 void gemm_sp_launch(const GemmArgs& a, const SpPlan& pl, hipStream_t s);
 // can the launch described by `a` (W2 / bias2 / Out2 / N2 ... set) run with its second layer chained into the epilogue?
 bool gemm_sp_chain_ok(const GemmArgs& a);
-bool gemm_sp_topk_layout(const GemmArgs& a, int* slots, int* cols);  // candidate groups of a top-k launch the SP kernel takes
+bool gemm_sp_topk_layout(const GemmArgs& a, int* slots, int* cols);  // gemm_topk_layout when the SP kernel takes the launch
 double gemm_sp_fill_bytes(const GemmArgs& a, const SpPlan& pl);  // LDS fill bytes of the launch (profiling aid)
 void gemm_sp_stamps_dump(const char* path);  // tuning aid, see gemm_sp.hip
 

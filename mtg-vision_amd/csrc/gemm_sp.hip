@@ -175,8 +175,6 @@ const SpCfg kCfg[] = {
     {4, 1, 1, 1, 0.00, 1},  // 128 x 32 in 16-k stages: window convs with 16-channel slices only (chosen below, not searched)
 };
 constexpr int kNumCfg = sizeof(kCfg) / sizeof(kCfg[0]);
-
-bool is_conv(const GemmArgs& a) { return !(a.KH == 1 && a.KW == 1 && a.stride == 1 && a.stride_w <= 1 && a.pad == 0); }
 }  // namespace
 
 bool window_conv_on() {
@@ -243,7 +241,7 @@ SpPlan gemm_sp_plan(const GemmArgs& a) {
   };
   if (!gemm_sp_active()) return none();
   const bool conv = is_conv(a);
-  const bool remap = !(a.os == 1 && a.oy == 0 && a.ox == 0 && a.OH2 == a.OH && a.OW2 == a.OW);
+  const bool remap = is_remap(a);
   if (a.batch != 1 || a.crop_boxes != nullptr || a.m_count != nullptr || a.ln_w != nullptr) return none();
   if (a.topk > 0) {  // match path: 128 x 192 tiles, f32 queries by DMA (A mode 4), fused top-k (gemm_sp_kernel.h, EPI 16)
     if (sp8_in || conv || a.K % 8 != 0 || a.c_total % 8 != 0 || a.c_off % 8 != 0 || ((uintptr_t)a.A & 15) != 0 || a.a_scale != nullptr ||
@@ -426,7 +424,7 @@ void gemm_sp_launch(const GemmArgs& a, const SpPlan& pl, hipStream_t s) {
   g.d_ow = make_fastdiv((uint32_t)a.OW);
   g.d_cin = make_fastdiv((uint32_t)(a.Cin > 0 ? a.Cin : 1));
   g.d_kw = make_fastdiv((uint32_t)a.KW);
-  g.remap = !(a.os == 1 && a.oy == 0 && a.ox == 0 && a.OH2 == a.OH && a.OW2 == a.OW);
+  g.remap = is_remap(a);
   g.os = a.os, g.oy = a.oy, g.ox = a.ox, g.OH2 = a.OH2, g.OW2 = a.OW2;
   if (a.W2 != nullptr) {
     const char* w28 = nullptr;
@@ -441,12 +439,6 @@ void gemm_sp_launch(const GemmArgs& a, const SpPlan& pl, hipStream_t s) {
     MTGV_CHECK(g.remap && a.os_nq % 8 == 0 && a.N == a.os * a.os * a.os_nq && a.oy == 0 && a.ox == 0 && a.res == nullptr &&
                    a.grn_part == nullptr,
                ERR_INVALID, "gemm_sp: os_nq=%d does not describe a %dx%d scatter of N=%d columns", a.os_nq, a.os, a.os, a.N);
-  if (a.grn_part != nullptr) {
-    MTGV_CHECK(a.segmax >= (pl.unit_rows - 1) / g.hw + 2, ERR_INVALID, "gemm_sp: segmax %d too small", a.segmax);
-    // the caller sized and will reduce the partial sums for the unit it planned with (gemm_grn_layout)
-    MTGV_CHECK(a.grn_unit_rows == 0 || a.grn_unit_rows == pl.unit_rows, ERR_RUNTIME,
-               "gemm_sp: GRN partials planned for %d-row units, this launch writes %d-row units", a.grn_unit_rows, pl.unit_rows);
-  }
   // f32 A: by DMA and split at the fragment read when the rows are 16-byte aligned, need no range multiplier and a
   // tile's rows span at most 8 images of the per-image multipliers; through registers otherwise
   int amode = a.a_fmt == 1 ? (is_conv(a) ? 2 : 0) : 1;

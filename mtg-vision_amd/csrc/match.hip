@@ -445,16 +445,12 @@ void Bank::topk(const float* q, int b, int k, int64_t id_base, float thr, int64_
     topk_prepass(q, b, k, id_base, thr, ids, scores, s);
     return;
   }
-  GemmPlan pl;
-  pl.tm = 1, pl.tn = 2, pl.bk = 16;
-  pl.tiles_m = ceil_div(b, pl.bm());
-  pl.tiles_n = ceil_div((int)size_, pl.bn());
   qn_.ensure((size_t)b * dim_);
   GemmArgs g = linear_args(qn_.p, dim_, vecs_.p, nullptr, nullptr, 0, b, (int)size_, dim_, ACT_NONE);
   // candidate groups: 64-column tiles of the convert-on-load kernel, or the per-wave column ranges of the LDS-DMA kernel
-  int slots = pl.tiles_n, cols = pl.bn();
+  int slots = 0, cols = 0;
   g.topk = 1;
-  (void)gemm_sp_topk_layout(g, &slots, &cols);
+  gemm_topk_layout(g, &slots, &cols);
   const int kt = k < cols ? k : cols;  // a group cannot contribute more candidates than it has columns
   const size_t ncand = (size_t)slots * kt;
   cand_s_.ensure((size_t)b * ncand);
@@ -463,7 +459,7 @@ void Bank::topk(const float* q, int b, int k, int64_t id_base, float thr, int64_
   g.cand_s = cand_s_.p;
   g.cand_i = reinterpret_cast<int*>(cand_i_.p);
   g.topk = kt;
-  gemm_launch(g, pl, s);
+  gemm_launch(g, s);
   hipLaunchKernelGGL((topk_merge_kernel<int>), dim3(b), dim3(256), 0, s, cand_s_.p, (const int*)cand_i_.p, (int)ncand, k,
                      (long)id_base, thr, (long*)ids, scores);
   HIP_OK(hipGetLastError());
