@@ -293,6 +293,38 @@ MTGV_API int mtgv_make_cropped(const uint8_t* images_dev, const int64_t* offsets
  * (mtgv.detector.letterbox_geometry: r = min(size / h, size / w), nh = round(h r), ...). */
 MTGV_API int mtgv_letterbox_u8(const uint8_t* src_dev, int32_t h, int32_t w, uint8_t* dst_dev, int32_t size, int32_t nh, int32_t nw,
                                int32_t top, int32_t left, int32_t pad_value, void* stream);
+/* fills the pad of n letterboxed (size, size, 3) uint8 frames with pad_value: every pixel outside the (nh, nw) rectangle
+ * at (top, left), which someone else writes (mtgv.jpeg.JpegDecoder.decode_frames decodes a frame that already fits
+ * straight into it) */
+MTGV_API int mtgv_letterbox_pad_u8(uint8_t* frames_dev, int32_t n, int32_t size, int32_t nh, int32_t nw, int32_t top, int32_t left,
+                                   int32_t pad_value, void* stream);
+
+/* ------------------------------------------------------------------------- */
+/* JPEG decode: the frames of mtgvision/server.py:272-280 (cv2.imdecode on the host) and the */
+/* card scans of qdrant_populate.py:70-90 go from compressed bytes to RGB on the GPU.                            */
+/* Baseline sequential Huffman 8-bit (SOF0 / SOF1); 1 component (returned as RGB, the channel replicated) or      */
+/* YCbCr with luma sampling 1x1, 2x1 or 2x2 and chroma 1x1; restart intervals; any size up to the handle's limits. */
+/* Output equals libjpeg-turbo's default decode (islow IDCT, fancy upsampling, fixed-point YCbCr -> RGB).          */
+/* ------------------------------------------------------------------------- */
+typedef struct mtgv_jpeg_decoder mtgv_jpeg_decoder;
+/* host only, no device needed: info[0..5] = h, w, components, sampling (444 / 422 / 420 / 400, 0 other), restart
+ * interval (MCUs, 0 none), supported (1 / 0).  Returns 1 (ERR_INVALID) with a message for malformed input; for a
+ * well-formed but unsupported file it returns 0 with info[5] = 0 and mtgv_last_error() naming the first unsupported
+ * feature (progressive, arithmetic coding, lossless, 12-bit, CMYK / 4 components, other sampling factors ...). */
+MTGV_API int mtgv_jpeg_info(const uint8_t* data, int64_t nbytes, int32_t* info);
+/* Limits of one batch: max_images files, max_bytes compressed bytes in all, max_pixels pixels in all once every image
+ * is padded to whole MCUs (8 or 16 pixels; a 640x480 frame needs 640 * 480).  The pinned staging buffer and every
+ * device workspace are allocated here, never inside a decode.  Bound to the device current at creation. */
+MTGV_API int mtgv_jpeg_decoder_create(int32_t max_images, int64_t max_bytes, int64_t max_pixels, mtgv_jpeg_decoder** out);
+MTGV_API void mtgv_jpeg_decoder_destroy(mtgv_jpeg_decoder* h);
+/* n JPEGs in host memory (file i at data_host + offsets[i], sizes[i] bytes) -> RGB uint8, image i written at
+ * dst_dev + dst_offset[i] with rows dst_pitch[i] bytes apart (>= 3 w).  Every file is parsed first: malformed or
+ * unsupported input returns 1 (ERR_INVALID) naming the image and the reason, before anything is launched.
+ * status_dev (n) int32: 0 decoded, 1 corrupt entropy-coded data (that image's slot is then left undefined; nothing is
+ * written outside it).  Asynchronous on `stream`: the host buffers may be reused when the call returns. */
+MTGV_API int mtgv_jpeg_decode(mtgv_jpeg_decoder* h, const uint8_t* data_host, const int64_t* offsets, const int64_t* sizes,
+                              int32_t n, uint8_t* dst_dev, const int64_t* dst_offset, const int64_t* dst_pitch,
+                              int32_t* status_dev, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Single ops (unit-test and composition surface; same kernels the handles use) */

@@ -1,0 +1,1233 @@
+// Baseline JPEG decode on the GPU (SOF0 / SOF1, Huffman, 8-bit; 1 component or YCbCr 4:4:4 / 4:2:2 / 4:2:0).
+//
+// Host: walk the markers of every image, build descriptors (geometry, quantisation tables, Huffman lookup tables,
+// restart interval, entropy-coded segment), pack them with the entropy-coded bytes into the handle's pinned staging
+// buffer and copy it in one transfer.  Anything outside the supported subset is refused before any launch.
+//
+// Device, one batch in eleven launches (all integer arithmetic):
+//   unstuff_count / unstuff_scan / unstuff_scatter  drop the 0x00 after each 0xFF and the RSTn markers (prefix-sum
+//                              compaction per 4 KiB tile) -> one bit stream per image + the start byte of every
+//                              restart segment
+//   sync / sync_fix            self-synchronising parallel Huffman decode (Weissenberger & Schmidt, ICPP 2018): the
+//                              stream is cut into 64-byte chunks, each decoded from a guessed state (chunk start, block
+//                              0 of the MCU, zig-zag 0) to the first symbol boundary past its end; the exit state
+//                              (bit position, block in MCU, zig-zag index) must equal the next chunk's start state.
+//                              Within a workgroup, chunks re-decode from their predecessor's exit until nothing
+//                              changes (at most 256 rounds); sync_fix then walks every image's workgroup seams in
+//                              order, re-decoding chunk after chunk until the states agree again.  Chunk 0 and every
+//                              restart segment start from a known state, so once start[c] == exit[c - 1] holds for
+//                              every chunk each start is proven; the worst case is a sequential walk.
+//   count / verify             blocks per chunk -> per-image exclusive scan; totals per image and per restart segment
+//                              checked against the frame geometry -> status word
+//   write                      decode again from the proven states, int16 coefficients into their block slots
+//   dc                         per-component prefix sum of the DC differences, reset at every restart segment
+//   idct                       dequantise + islow integer IDCT (the IJG / libjpeg-turbo jidctint algorithm) -> planes
+//   color                      fancy h2v1 / h2v2 upsampling (libjpeg-turbo jdsample rules) + fixed-point YCbCr -> RGB
+//                              (jdcolor tables) -> RGB uint8 at the caller's offset / pitch
+// Every decode loop is bounded by the stream length.  A stream that does not decode sets its image's status word; the
+// write, dc, idct and color launches then skip that image, so nothing is written outside its workspace and slot.
+#include <stdarg.h>
+#include <string.h>
+
+#include <algorithm>
+#include <map>
+#include <string>
+#include <vector>
+
+#include "common.h"
+#include "mtgv.h"
+
+using namespace mtgv;
+
+namespace {
+
+constexpr int CHUNK_BYTES = 64;    // self-synchronising decode: bytes of stream per thread
+constexpr int SYNC_WG = 256;       // chunks per workgroup of the in-workgroup synchronisation
+constexpr int TILE_BYTES = 4096;   // unstuffing: 256 threads x 16 bytes
+constexpr uint32_t POS_END = 0xFFFFFFFFu, POS_ERR = 0xFFFFFFFEu;
+
+struct HuffTab {
+  uint16_t lut[512];    // 9-bit lookahead: (length << 8) | symbol; 0: the code is longer than 9 bits
+  int32_t maxcode[17];  // largest code of each length, -1 if none
+  int32_t valoff[17];   // symbol index = code + valoff[length]
+  uint8_t val[256];
+};
+
+struct CompDesc {
+  uint16_t q[64];  // natural order
+  int32_t dc, ac;  // Huffman table index within the batch
+  int32_t h, v;    // sampling factors (1 x 1 for a single-component scan)
+  int32_t bw, bh;  // plane size in blocks
+  int64_t plane;   // byte offset of the plane in the plane workspace
+};
+
+struct ImgDesc {
+  int32_t h, w, ncomp, mode;  // mode: 0 grey, 1 4:4:4, 2 4:2:2, 3 4:2:0
+  int32_t mcux, mcuy, bpm, ri, nseg, nchunks, ntiles, pad_;
+  int8_t bcomp[8], bdx[8], bdy[8];  // MCU slot -> component, block offset inside the MCU
+  int64_t ecs;                      // byte offset of the entropy-coded data (staging) and of the bit stream (workspace)
+  int64_t ecs_len;
+  int64_t chunk0, seg0, tile0, blk0, pix0, nblocks;
+  int64_t dst_off, pitch;
+  CompDesc c[3];
+};
+
+struct Params {
+  const ImgDesc* d;
+  const HuffTab* tabs;
+  const int64_t* chunk_base;  // n + 1 prefix arrays for the ragged launches
+  const int64_t* blk_base;
+  const int64_t* seg_base;
+  const int64_t* tile_base;
+  const int64_t* pix_base;
+  const uint8_t* ecs;  // staged entropy-coded bytes
+  int n;
+  uint8_t* cs;          // compacted bit streams
+  int32_t* tile_cnt;    // per tile: kept bytes, markers, offset, marker offset
+  uint32_t* slen;       // stream bytes per image
+  int32_t* err;         // per image: 1 entropy decode error, 2 restart marker error
+  int32_t* ok;          // per image: decoded so far
+  uint32_t* seg_start;  // start byte of each restart segment in the bit stream
+  uint32_t* seg_cnt;    // blocks decoded in each segment
+  uint64_t* cstart;     // chunk start / exit states
+  uint64_t* cexit;
+  uint32_t* ccnt;       // blocks started in each chunk, then their exclusive scan
+  int16_t* coef;        // 64 per block, natural order
+  uint8_t* plane;
+  uint8_t* dst;
+  int32_t* status;
+};
+
+__constant__ uint8_t k_natural[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                                      41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                                      30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+const uint8_t h_natural[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
+                               41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
+                               30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
+
+__device__ inline int find_base(const int64_t* base, int n, int64_t x) {  // largest i < n with base[i] <= x
+  int lo = 0, hi = n - 1;
+  while (lo < hi) {
+    const int mid = (lo + hi + 1) >> 1;
+    if (base[mid] <= x) lo = mid;
+    else hi = mid - 1;
+  }
+  return lo;
+}
+
+__device__ inline int wave_incl(int v) {
+  const int lane = threadIdx.x & 63;
+#pragma unroll
+  for (int o = 1; o < 64; o <<= 1) {
+    const int t = __shfl_up(v, o, 64);
+    if (lane >= o) v += t;
+  }
+  return v;
+}
+
+// inclusive scan over a 256-thread workgroup; `total` gets the sum.  s: 4 ints of LDS.
+__device__ inline int block_incl(int v, int* s, int& total) {
+  const int wv = threadIdx.x >> 6;
+  v = wave_incl(v);
+  __syncthreads();
+  if ((threadIdx.x & 63) == 63) s[wv] = v;
+  __syncthreads();
+  int before = 0;
+  for (int i = 0; i < wv; ++i) before += s[i];
+  total = s[0] + s[1] + s[2] + s[3];
+  return v + before;
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// unstuffing
+
+// byte p of an entropy-coded segment d[0, len): kept in the bit stream?  *marker: an RSTn marker starts here
+__device__ inline bool keep_byte(const uint8_t* d, int64_t len, int64_t p, int* marker) {
+  const uint8_t b = d[p];
+  *marker = -1;
+  if (b == 0xFF) {
+    const uint8_t nx = p + 1 < len ? d[p + 1] : 0xFF;
+    if (nx >= 0xD0 && nx <= 0xD7) *marker = nx - 0xD0;
+    return nx == 0x00;  // stuffed 0xFF; otherwise a fill byte or the first byte of a marker
+  }
+  if (p > 0 && d[p - 1] == 0xFF && (b == 0x00 || (b >= 0xD0 && b <= 0xD7))) return false;
+  return true;
+}
+
+__global__ __launch_bounds__(256) void unstuff_count_kernel(Params P) {
+  __shared__ int s[8];
+  const int t = blockIdx.x;
+  const int i = find_base(P.tile_base, P.n, t);
+  const ImgDesc& D = P.d[i];
+  const uint8_t* d = P.ecs + D.ecs;
+  const int64_t p0 = (int64_t)(t - P.tile_base[i]) * TILE_BYTES + threadIdx.x * 16;
+  int kept = 0, mk = 0;
+  for (int k = 0; k < 16; ++k) {
+    const int64_t p = p0 + k;
+    if (p >= D.ecs_len) break;
+    int m;
+    kept += keep_byte(d, D.ecs_len, p, &m);
+    mk += m >= 0;
+  }
+  int tk, tm;
+  block_incl(kept, s, tk);
+  block_incl(mk, s + 4, tm);
+  if (threadIdx.x == 0) {
+    P.tile_cnt[t * 4 + 0] = tk;
+    P.tile_cnt[t * 4 + 1] = tm;
+  }
+}
+
+// one thread per image: tile offsets, stream length, marker count
+__global__ __launch_bounds__(64) void unstuff_scan_kernel(Params P) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= P.n) return;
+  const ImgDesc& D = P.d[i];
+  int off = 0, moff = 0;
+  for (int64_t t = P.tile_base[i]; t < P.tile_base[i + 1]; ++t) {
+    P.tile_cnt[t * 4 + 2] = off;
+    P.tile_cnt[t * 4 + 3] = moff;
+    off += P.tile_cnt[t * 4 + 0];
+    moff += P.tile_cnt[t * 4 + 1];
+  }
+  P.slen[i] = (uint32_t)off;
+  P.seg_start[D.seg0] = 0;
+  if (moff != D.nseg - 1) atomicOr(&P.err[i], 2);
+}
+
+__global__ __launch_bounds__(256) void unstuff_scatter_kernel(Params P) {
+  __shared__ int s[8];
+  const int t = blockIdx.x;
+  const int i = find_base(P.tile_base, P.n, t);
+  const ImgDesc& D = P.d[i];
+  const uint8_t* d = P.ecs + D.ecs;
+  const int64_t p0 = (int64_t)(t - P.tile_base[i]) * TILE_BYTES + threadIdx.x * 16;
+  uint32_t keepm = 0;
+  int kept = 0, mk = 0, mnum[16];
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    const int64_t p = p0 + k;
+    mnum[k] = -1;
+    if (p >= D.ecs_len) continue;
+    if (keep_byte(d, D.ecs_len, p, &mnum[k])) keepm |= 1u << k, ++kept;
+    mk += mnum[k] >= 0;
+  }
+  int tk, tm;
+  int ko = block_incl(kept, s, tk) - kept + P.tile_cnt[t * 4 + 2];
+  int mo = block_incl(mk, s + 4, tm) - mk + P.tile_cnt[t * 4 + 3];
+  uint8_t* out = P.cs + D.ecs;
+#pragma unroll
+  for (int k = 0; k < 16; ++k) {
+    if (mnum[k] >= 0) {
+      // marker number mo starts segment mo + 1 at the next kept byte
+      if (mo + 1 < D.nseg) P.seg_start[D.seg0 + mo + 1] = (uint32_t)ko;
+      if (mnum[k] != (mo & 7)) atomicOr(&P.err[i], 2);
+      ++mo;
+    }
+    if (keepm >> k & 1) out[ko++] = d[p0 + k];
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// Huffman decode from a state.  State word: bit position | block in MCU << 32 | zig-zag index << 40.
+
+__device__ inline uint64_t pack_st(uint32_t pos, int b, int z) { return (uint64_t)pos | (uint64_t)b << 32 | (uint64_t)z << 40; }
+
+__device__ inline uint32_t peek32(const uint8_t* s, uint32_t pos) {
+  const uint32_t* w = (const uint32_t*)s + (pos >> 5);
+  const uint64_t x = (uint64_t)__builtin_bswap32(w[0]) << 32 | __builtin_bswap32(w[1]);
+  return (uint32_t)(x >> (32 - (pos & 31)));
+}
+
+enum { RUN_SYNC = 0, RUN_COUNT = 1, RUN_WRITE = 2 };
+
+struct RunOut {
+  uint32_t blocks;
+  bool error;
+};
+
+// Decode image i's stream from state `st` until the first symbol boundary at or past bit `stop` (RUN_WRITE: the first
+// block boundary).  Returns the state there, POS_END past the last segment, POS_ERR on an invalid code or a segment
+// that does not end on an MCU boundary.  RUN_COUNT adds the blocks started before `stop` to seg_cnt; RUN_WRITE writes
+// them from block `blk` on (a block already started at `st` is decoded, not written).
+template <int MODE>
+__device__ uint64_t run(const Params& P, int i, uint64_t st, uint32_t stop, int64_t blk, RunOut& ro) {
+  ro.blocks = 0;
+  ro.error = false;
+  uint32_t pos = (uint32_t)st;
+  if (pos == POS_END) return st;
+  if (pos == POS_ERR) {
+    ro.error = true;
+    return st;
+  }
+  const ImgDesc& D = P.d[i];
+  const uint8_t* s = P.cs + D.ecs;
+  const uint32_t nbits = P.slen[i] * 8u;
+  const uint32_t* segst = P.seg_start + D.seg0;
+  int b = (int)(st >> 32) & 0xff, z = (int)(st >> 40) & 0xff;
+  if (b >= D.bpm || z > 63) {
+    ro.error = true;
+    return pack_st(POS_ERR, 0, 0);
+  }
+  int seg;
+  {  // segment of pos: largest s with segst[s] * 8 <= pos
+    int lo = 0, hi = D.nseg - 1;
+    while (lo < hi) {
+      const int mid = (lo + hi + 1) >> 1;
+      if ((uint64_t)segst[mid] * 8 <= pos) lo = mid;
+      else hi = mid - 1;
+    }
+    seg = lo;
+  }
+  // (segment starts the unstuffing did not write - fewer markers than restart intervals, an image already marked
+  // corrupt - are clamped to the stream so that no read leaves it)
+  auto seg_end_of = [&](int sg) { return sg + 1 < D.nseg ? (uint32_t)min((uint64_t)segst[sg + 1] * 8, (uint64_t)nbits) : nbits; };
+  uint32_t seg_end = seg_end_of(seg);
+  if (pos > nbits) pos = nbits;
+  uint32_t seg_blocks = 0;
+  const int64_t blk_end = D.blk0 + D.nblocks;
+  bool skip = MODE == RUN_WRITE && z != 0;
+  int16_t* out = nullptr;
+  int comp = D.bcomp[b];
+  const HuffTab* tdc = P.tabs + D.c[comp].dc;
+  const HuffTab* tac = P.tabs + D.c[comp].ac;
+  uint64_t res;
+  const uint32_t budget = nbits + (uint32_t)D.nseg + 2;
+  for (uint32_t it = 0;; ++it) {
+    if (it > budget) {
+      res = pack_st(POS_ERR, 0, 0);
+      ro.error = true;
+      break;
+    }
+    if (pos >= stop && (MODE != RUN_WRITE || z == 0)) {
+      res = pack_st(pos, b, z);
+      break;
+    }
+    bool past = pos >= seg_end;
+    int len = 0, sym = 0;
+    uint32_t w = 0;
+    if (!past) {
+      w = peek32(s, pos);
+      const HuffTab* t = z == 0 ? tdc : tac;
+      const uint32_t e = t->lut[w >> 23];
+      if (e) {
+        len = (int)(e >> 8);
+        sym = (int)(e & 0xff);
+      } else {
+        len = 10;
+        while (len <= 16 && (int32_t)(w >> (32 - len)) > t->maxcode[len]) ++len;
+        if (len > 16) {
+          // no code matches: corrupt data (or an unsynchronised guess) if all 16 bits lie inside the segment; otherwise
+          // these are the segment's 1-bit padding, which no code may consist of
+          if (pos + 16 <= seg_end) {
+            res = pack_st(POS_ERR, 0, 0);
+            ro.error = true;
+            break;
+          }
+          len = 17;  // past the end
+        } else {
+          sym = t->val[(w >> (32 - len)) + t->valoff[len]];
+        }
+      }
+      const int sb = z == 0 ? sym : (sym & 15);
+      past = pos + (uint32_t)len + (uint32_t)sb > seg_end;
+      if (!past) {
+        int v = 0;
+        if (sb) {
+          const uint32_t bits = (w << len) >> (32 - sb);
+          v = bits < (1u << (sb - 1)) ? (int)bits - (1 << sb) + 1 : (int)bits;
+        }
+        pos += (uint32_t)(len + sb);
+        if (z == 0) {  // DC difference: a block starts
+          ++ro.blocks;
+          ++seg_blocks;
+          if (MODE == RUN_WRITE && blk >= blk_end) skip = true;  // cannot happen once verified; kept as a bound
+          if (MODE == RUN_WRITE && !skip) {
+            out = P.coef + (blk++) * 64;
+            int4* o4 = (int4*)out;
+#pragma unroll
+            for (int k = 0; k < 8; ++k) o4[k] = make_int4(0, 0, 0, 0);
+            out[0] = (int16_t)v;
+          }
+          z = 1;
+        } else {
+          const int r = sym >> 4;
+          if (sb) {
+            z += r;
+            if (MODE == RUN_WRITE && !skip) out[k_natural[z > 63 ? 63 : z]] = (int16_t)v;
+            ++z;
+          } else if (r == 15) {
+            z += 16;  // ZRL
+          } else {
+            z = 64;  // EOB
+          }
+        }
+        if (z >= 64) {
+          z = 0;
+          if (++b == D.bpm) b = 0;
+          skip = false;
+          comp = D.bcomp[b];
+          tdc = P.tabs + D.c[comp].dc;
+          tac = P.tabs + D.c[comp].ac;
+        }
+        continue;
+      }
+    }
+    // the next symbol would run past the end of the restart segment: the segment is complete
+    if (b != 0 || z != 0) {
+      res = pack_st(POS_ERR, 0, 0);
+      ro.error = true;
+      break;
+    }
+    if (MODE == RUN_COUNT && seg_blocks) atomicAdd(&P.seg_cnt[D.seg0 + seg], seg_blocks);
+    seg_blocks = 0;
+    if (seg + 1 >= D.nseg) {
+      res = pack_st(POS_END, 0, 0);
+      break;
+    }
+    ++seg;
+    pos = seg_end;
+    seg_end = seg_end_of(seg);
+    if (pos > seg_end) pos = seg_end;
+  }
+  if (MODE == RUN_COUNT && seg_blocks) atomicAdd(&P.seg_cnt[D.seg0 + seg], seg_blocks);
+  return res;
+}
+
+__device__ inline uint64_t guess_state(const Params& P, int i, int64_t k) {
+  const uint64_t pos = (uint64_t)k * CHUNK_BYTES * 8;
+  return pos >= (uint64_t)P.slen[i] * 8 ? pack_st(k == 0 ? 0 : POS_END, 0, 0) : pack_st((uint32_t)pos, 0, 0);
+}
+
+__global__ __launch_bounds__(SYNC_WG) void sync_kernel(Params P, int64_t nchunks) {
+  __shared__ uint64_t s_exit[SYNC_WG];
+  __shared__ int s_changed[2];
+  const int64_t c = (int64_t)blockIdx.x * SYNC_WG + threadIdx.x;
+  const bool valid = c < nchunks;
+  const int i = valid ? find_base(P.chunk_base, P.n, c) : 0;
+  const int64_t k = valid ? c - P.chunk_base[i] : 0;
+  const bool linked = valid && k > 0 && threadIdx.x > 0;
+  const uint32_t stop = (uint32_t)((k + 1) * CHUNK_BYTES * 8);
+  RunOut ro;
+  uint64_t start = valid ? guess_state(P, i, k) : 0;
+  uint64_t ex = valid ? run<RUN_SYNC>(P, i, start, stop, 0, ro) : 0;
+  for (int round = 0; round < SYNC_WG; ++round) {
+    s_exit[threadIdx.x] = ex;
+    if (threadIdx.x == 0) s_changed[round & 1] = 0;
+    __syncthreads();
+    if (linked) {
+      const uint64_t ns = s_exit[threadIdx.x - 1];
+      if (ns != start) {
+        start = ns;
+        ex = run<RUN_SYNC>(P, i, start, stop, 0, ro);
+        s_changed[round & 1] = 1;
+      }
+    }
+    __syncthreads();
+    if (!s_changed[round & 1]) break;
+  }
+  if (valid) {
+    P.cstart[c] = start;
+    P.cexit[c] = ex;
+  }
+}
+
+// one thread per image: the workgroup seams, in stream order
+__global__ __launch_bounds__(64) void sync_fix_kernel(Params P) {
+  const int i = blockIdx.x * 64 + threadIdx.x;
+  if (i >= P.n) return;
+  const int64_t cb = P.chunk_base[i], ce = P.chunk_base[i + 1];
+  RunOut ro;
+  for (int64_t c = (cb / SYNC_WG + 1) * SYNC_WG; c < ce;) {
+    uint64_t e = P.cexit[c - 1];
+    int64_t j = c;
+    while (j < ce && P.cstart[j] != e) {
+      P.cstart[j] = e;
+      e = run<RUN_SYNC>(P, i, e, (uint32_t)((j - cb + 1) * CHUNK_BYTES * 8), 0, ro);
+      P.cexit[j] = e;
+      ++j;
+    }
+    c = (j / SYNC_WG + 1) * SYNC_WG;
+  }
+}
+
+__global__ __launch_bounds__(256) void count_kernel(Params P, int64_t nchunks) {
+  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= nchunks) return;
+  const int i = find_base(P.chunk_base, P.n, c);
+  const int64_t k = c - P.chunk_base[i];
+  RunOut ro;
+  run<RUN_COUNT>(P, i, P.cstart[c], (uint32_t)((k + 1) * CHUNK_BYTES * 8), 0, ro);
+  P.ccnt[c] = ro.blocks;
+  if (ro.error) atomicOr(&P.err[i], 1);
+}
+
+// one wave per image: exclusive scan of the chunk counts, totals checked against the geometry -> status
+__global__ __launch_bounds__(64) void verify_kernel(Params P) {
+  const int i = blockIdx.x;
+  const ImgDesc& D = P.d[i];
+  const int lane = threadIdx.x;
+  const int64_t cb = P.chunk_base[i], ce = P.chunk_base[i + 1];
+  int64_t run_total = 0;
+  for (int64_t c0 = cb; c0 < ce; c0 += 64) {
+    const int64_t c = c0 + lane;
+    const int v = c < ce ? (int)P.ccnt[c] : 0;
+    const int inc = wave_incl(v);
+    if (c < ce) P.ccnt[c] = (uint32_t)(run_total + inc - v);
+    run_total += __shfl(inc, 63, 64);
+  }
+  bool bad = run_total != D.nblocks;
+  const int64_t nmcu = (int64_t)D.mcux * D.mcuy;
+  for (int s = lane; s < D.nseg; s += 64) {
+    const int64_t left = nmcu - (int64_t)s * D.ri;
+    const int64_t want = (left < D.ri ? left : D.ri) * D.bpm;
+    bad |= P.seg_cnt[D.seg0 + s] != want;
+  }
+  bad = __any(bad);
+  if (lane == 0) {
+    const int ok = !bad && P.err[i] == 0;
+    P.ok[i] = ok;
+    P.status[i] = ok ? 0 : 1;
+  }
+}
+
+__global__ __launch_bounds__(256) void write_kernel(Params P, int64_t nchunks) {
+  const int64_t c = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (c >= nchunks) return;
+  const int i = find_base(P.chunk_base, P.n, c);
+  if (!P.ok[i]) return;
+  const int64_t k = c - P.chunk_base[i];
+  RunOut ro;
+  run<RUN_WRITE>(P, i, P.cstart[c], (uint32_t)((k + 1) * CHUNK_BYTES * 8), P.d[i].blk0 + P.ccnt[c], ro);
+}
+
+// one workgroup per restart segment: DC = running sum of the differences, per component
+__global__ __launch_bounds__(256) void dc_kernel(Params P) {
+  __shared__ int s[12];
+  const int64_t g = blockIdx.x;
+  const int i = find_base(P.seg_base, P.n, g);
+  if (!P.ok[i]) return;  // uniform over the workgroup
+  const ImgDesc& D = P.d[i];
+  const int64_t sg = g - P.seg_base[i];
+  const int64_t nmcu = (int64_t)D.mcux * D.mcuy;
+  const int64_t b0 = sg * D.ri * D.bpm, b1 = ((sg + 1) * D.ri < nmcu ? (sg + 1) * D.ri : nmcu) * D.bpm;
+  int carry[3] = {0, 0, 0};
+  for (int64_t t0 = b0; t0 < b1; t0 += 256) {
+    const int64_t bi = t0 + threadIdx.x;
+    const bool in = bi < b1;
+    int16_t* cf = P.coef + (D.blk0 + bi) * 64;
+    const int v = in ? cf[0] : 0;
+    const int comp = in ? D.bcomp[bi % D.bpm] : -1;
+    int mine = 0;
+    for (int q = 0; q < D.ncomp; ++q) {
+      int tot;
+      const int inc = block_incl(comp == q ? v : 0, s + 4 * q, tot);
+      if (comp == q) mine = carry[q] + inc;
+      carry[q] += tot;
+    }
+    if (in) cf[0] = (int16_t)mine;
+  }
+}
+
+__device__ inline uint8_t idct_limit(int x) {  // libjpeg's post-IDCT range-limit table, indexed with x & 1023
+  const int i = x & 1023;
+  return (uint8_t)(i < 128 ? i + 128 : i < 512 ? 255 : i < 896 ? 0 : i - 896);
+}
+
+// 8 threads per block: a column each in pass 1, a row each in pass 2
+__global__ __launch_bounds__(256) void idct_kernel(Params P, int64_t nblocks) {
+  __shared__ int ws[32][8][9];
+  const int lb = threadIdx.x >> 3, lane = threadIdx.x & 7;
+  const int64_t blk = (int64_t)blockIdx.x * 32 + lb;
+  const bool valid = blk < nblocks;
+  const int i = valid ? find_base(P.blk_base, P.n, blk) : 0;
+  const bool live = valid && P.ok[i];
+  const ImgDesc& D = P.d[i];
+  const int64_t L = blk - D.blk0;
+  const int slot = live ? (int)(L % D.bpm) : 0;
+  const CompDesc& C = D.c[live ? D.bcomp[slot] : 0];
+  constexpr int CB = 13, P1 = 2;
+  auto mul = [](int a, int f) { return a * f; };
+  if (live) {  // pass 1: column `lane`
+    const int16_t* in = P.coef + blk * 64 + lane;
+    const uint16_t* q = C.q + lane;
+    int z2 = in[16] * q[16], z3 = in[48] * q[48];
+    int z1 = mul(z2 + z3, 4433);
+    int tmp2 = z1 + mul(z3, -15137), tmp3 = z1 + mul(z2, 6270);
+    z2 = in[0] * q[0];
+    z3 = in[32] * q[32];
+    int tmp0 = (z2 + z3) << CB, tmp1 = (z2 - z3) << CB;
+    const int t10 = tmp0 + tmp3, t13 = tmp0 - tmp3, t11 = tmp1 + tmp2, t12 = tmp1 - tmp2;
+    tmp0 = in[56] * q[56];
+    tmp1 = in[40] * q[40];
+    tmp2 = in[24] * q[24];
+    tmp3 = in[8] * q[8];
+    z1 = tmp0 + tmp3;
+    z2 = tmp1 + tmp2;
+    z3 = tmp0 + tmp2;
+    int z4 = tmp1 + tmp3;
+    const int z5 = mul(z3 + z4, 9633);
+    tmp0 = mul(tmp0, 2446);
+    tmp1 = mul(tmp1, 16819);
+    tmp2 = mul(tmp2, 25172);
+    tmp3 = mul(tmp3, 12299);
+    z1 = mul(z1, -7373);
+    z2 = mul(z2, -20995);
+    z3 = mul(z3, -16069) + z5;
+    z4 = mul(z4, -3196) + z5;
+    tmp0 += z1 + z3;
+    tmp1 += z2 + z4;
+    tmp2 += z2 + z3;
+    tmp3 += z1 + z4;
+    constexpr int sh = CB - P1, rd = 1 << (sh - 1);
+    int(*w)[9] = ws[lb];
+    w[0][lane] = (t10 + tmp3 + rd) >> sh;
+    w[7][lane] = (t10 - tmp3 + rd) >> sh;
+    w[1][lane] = (t11 + tmp2 + rd) >> sh;
+    w[6][lane] = (t11 - tmp2 + rd) >> sh;
+    w[2][lane] = (t12 + tmp1 + rd) >> sh;
+    w[5][lane] = (t12 - tmp1 + rd) >> sh;
+    w[3][lane] = (t13 + tmp0 + rd) >> sh;
+    w[4][lane] = (t13 - tmp0 + rd) >> sh;
+  }
+  __syncthreads();
+  if (!live) return;
+  const int* r = ws[lb][lane];
+  int z2 = r[2], z3 = r[6];
+  int z1 = mul(z2 + z3, 4433);
+  int tmp2 = z1 + mul(z3, -15137), tmp3 = z1 + mul(z2, 6270);
+  int tmp0 = (r[0] + r[4]) << CB, tmp1 = (r[0] - r[4]) << CB;
+  const int t10 = tmp0 + tmp3, t13 = tmp0 - tmp3, t11 = tmp1 + tmp2, t12 = tmp1 - tmp2;
+  tmp0 = r[7];
+  tmp1 = r[5];
+  tmp2 = r[3];
+  tmp3 = r[1];
+  z1 = tmp0 + tmp3;
+  z2 = tmp1 + tmp2;
+  z3 = tmp0 + tmp2;
+  int z4 = tmp1 + tmp3;
+  const int z5 = mul(z3 + z4, 9633);
+  tmp0 = mul(tmp0, 2446);
+  tmp1 = mul(tmp1, 16819);
+  tmp2 = mul(tmp2, 25172);
+  tmp3 = mul(tmp3, 12299);
+  z1 = mul(z1, -7373);
+  z2 = mul(z2, -20995);
+  z3 = mul(z3, -16069) + z5;
+  z4 = mul(z4, -3196) + z5;
+  tmp0 += z1 + z3;
+  tmp1 += z2 + z4;
+  tmp2 += z2 + z3;
+  tmp3 += z1 + z4;
+  constexpr int sh = CB + P1 + 3, rd = 1 << (sh - 1);
+  uint8_t o[8];
+  o[0] = idct_limit((t10 + tmp3 + rd) >> sh);
+  o[7] = idct_limit((t10 - tmp3 + rd) >> sh);
+  o[1] = idct_limit((t11 + tmp2 + rd) >> sh);
+  o[6] = idct_limit((t11 - tmp2 + rd) >> sh);
+  o[2] = idct_limit((t12 + tmp1 + rd) >> sh);
+  o[5] = idct_limit((t12 - tmp1 + rd) >> sh);
+  o[3] = idct_limit((t13 + tmp0 + rd) >> sh);
+  o[4] = idct_limit((t13 - tmp0 + rd) >> sh);
+  int64_t by, bx;
+  if (D.ncomp == 1) {
+    by = L / C.bw;
+    bx = L % C.bw;
+  } else {
+    const int64_t m = L / D.bpm;
+    by = (m / D.mcux) * C.v + D.bdy[slot];
+    bx = (m % D.mcux) * C.h + D.bdx[slot];
+  }
+  uint8_t* dst = P.plane + C.plane + (by * 8 + lane) * (int64_t)(C.bw * 8) + bx * 8;
+  uint2 pk;
+  pk.x = o[0] | o[1] << 8 | o[2] << 16 | (uint32_t)o[3] << 24;
+  pk.y = o[4] | o[5] << 8 | o[6] << 16 | (uint32_t)o[7] << 24;
+  *(uint2*)dst = pk;
+}
+
+// libjpeg jdcolor.c tables, evaluated: FIX(x) = round(x * 2^16), ONE_HALF = 2^15
+__device__ inline void ycc_rgb(int y, int cb, int cr, uint8_t* o) {
+  cb -= 128;
+  cr -= 128;
+  const int r = y + ((91881 * cr + 32768) >> 16);
+  const int g = y + ((-22554 * cb + 32768 + -46802 * cr) >> 16);
+  const int b = y + ((116130 * cb + 32768) >> 16);
+  o[0] = (uint8_t)min(max(r, 0), 255);
+  o[1] = (uint8_t)min(max(g, 0), 255);
+  o[2] = (uint8_t)min(max(b, 0), 255);
+}
+
+// chroma sample of output pixel (y, x): libjpeg-turbo h2v1 / h2v2 fancy upsampling (box replication when the
+// downsampled width is 2 or less, as jinit_upsampler selects)
+__device__ inline int chroma(const uint8_t* p, int stride, int mode, int y, int x, int cw, int ch) {
+  if (mode == 1) return p[(int64_t)y * stride + x];
+  const int xi = x >> 1;
+  if (mode == 2) {
+    const uint8_t* r = p + (int64_t)y * stride;
+    if (cw <= 2) return r[xi];
+    if ((x & 1) == 0) return xi == 0 ? r[0] : (3 * r[xi] + r[xi - 1] + 1) >> 2;
+    return xi == cw - 1 ? r[xi] : (3 * r[xi] + r[xi + 1] + 2) >> 2;
+  }
+  const int yi = y >> 1;
+  if (cw <= 2) return p[(int64_t)yi * stride + xi];
+  const int yn = min(max((y & 1) ? yi + 1 : yi - 1, 0), ch - 1);
+  const uint8_t* r0 = p + (int64_t)yi * stride;
+  const uint8_t* r1 = p + (int64_t)yn * stride;
+  auto col = [&](int c) { return 3 * r0[c] + r1[c]; };
+  const int t = col(xi);
+  if ((x & 1) == 0) return xi == 0 ? (4 * t + 8) >> 4 : (3 * t + col(xi - 1) + 8) >> 4;
+  return xi == cw - 1 ? (4 * t + 7) >> 4 : (3 * t + col(xi + 1) + 7) >> 4;
+}
+
+__global__ __launch_bounds__(256) void color_kernel(Params P, int64_t npix) {
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= npix) return;
+  const int i = find_base(P.pix_base, P.n, g);
+  if (!P.ok[i]) return;
+  const ImgDesc& D = P.d[i];
+  const int64_t l = g - P.pix_base[i];
+  const int y = (int)(l / D.w), x = (int)(l % D.w);
+  const int ys = D.c[0].bw * 8;
+  const int Y = P.plane[D.c[0].plane + (int64_t)y * ys + x];
+  uint8_t* o = P.dst + D.dst_off + (int64_t)y * D.pitch + (int64_t)x * 3;
+  if (D.ncomp == 1) {
+    o[0] = o[1] = o[2] = (uint8_t)Y;
+    return;
+  }
+  const int cs = D.c[1].bw * 8, cw = (D.w + 1) >> 1, ch = (D.h + 1) >> 1;
+  const int cb = chroma(P.plane + D.c[1].plane, cs, D.mode, y, x, cw, ch);
+  const int cr = chroma(P.plane + D.c[2].plane, cs, D.mode, y, x, cw, ch);
+  uint8_t rgb[3];
+  ycc_rgb(Y, cb, cr, rgb);
+  o[0] = rgb[0];
+  o[1] = rgb[1];
+  o[2] = rgb[2];
+}
+
+// ---------------------------------------------------------------------------------------------------------------------
+// host: marker walk
+
+struct Parsed {
+  int h = 0, w = 0, ncomp = 0, sampling = 0, ri = 0, supported = 0;
+  std::string why;  // first unsupported feature
+  struct Comp {
+    int id, h, v, tq, td, ta;
+  } comp[4];
+  uint16_t qt[4][64];
+  bool qdef[4] = {false, false, false, false};
+  uint8_t hbits[2][4][17];
+  uint8_t hval[2][4][256];
+  bool hdef[2][4] = {{false, false, false, false}, {false, false, false, false}};
+  int64_t ecs = 0, ecs_len = 0;
+};
+
+[[noreturn]] void bad(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
+void bad(const char* fmt, ...) {
+  char b[256];
+  va_list ap;
+  va_start(ap, fmt);
+  vsnprintf(b, sizeof(b), fmt, ap);
+  va_end(ap);
+  throw Error(ERR_INVALID, std::string("jpeg: ") + b);
+}
+
+void unsupported(Parsed& p, const std::string& why) {
+  if (p.why.empty()) p.why = why;
+}
+
+inline int be16(const uint8_t* d) { return d[0] << 8 | d[1]; }
+
+// canonical codes of a DHT table; false if a code does not fit its length (libjpeg: no all-ones code)
+bool huff_codes(const uint8_t* bits, int* maxcode, int* valoff, uint16_t* lut, const uint8_t* val) {
+  int code = 0, k = 0;
+  if (lut) memset(lut, 0, 512 * sizeof(uint16_t));
+  for (int l = 1; l <= 16; ++l) {
+    const int first = code, firstk = k;
+    for (int j = 0; j < bits[l]; ++j, ++code, ++k) {
+      if (lut && l <= 9) {
+        const int sh = 9 - l;
+        for (int e = 0; e < (1 << sh); ++e) lut[(code << sh) | e] = (uint16_t)(l << 8 | val[k]);
+      }
+    }
+    if (code >= (1 << l)) return false;
+    if (maxcode) {
+      maxcode[l] = bits[l] ? code - 1 : -1;
+      valoff[l] = firstk - first;
+    }
+    code <<= 1;
+  }
+  return true;
+}
+
+// walks the markers of one file; throws ERR_INVALID on malformed input, sets p.why on unsupported input
+void parse(const uint8_t* d, int64_t n, Parsed& p) {
+  if (d == nullptr || n <= 0) bad("empty input (%lld bytes)", (long long)n);
+  if (n < 2 || d[0] != 0xFF || d[1] != 0xD8) bad("no SOI marker at the start");
+  int64_t q = 2;
+  bool sof = false, jfif = false, adobe = false;
+  int adobe_transform = -1;
+  for (;;) {
+    if (q >= n) bad("truncated before SOS (byte %lld)", (long long)q);
+    if (d[q] != 0xFF) bad("expected a marker at byte %lld, found 0x%02X", (long long)q, d[q]);
+    while (q < n && d[q] == 0xFF) ++q;
+    if (q >= n) bad("truncated before SOS");
+    const int m = d[q++];
+    if (m == 0xD8) bad("second SOI marker at byte %lld", (long long)q - 2);
+    if (m == 0xD9) bad("EOI before any SOS: no image data");
+    if ((m >= 0xD0 && m <= 0xD7) || m == 0x01) continue;
+    if (q + 2 > n) bad("truncated marker 0x%02X", m);
+    const int len = be16(d + q);
+    if (len < 2 || q + len > n) bad("truncated marker segment 0x%02X (length %d, %lld bytes left)", m, len, (long long)(n - q));
+    const uint8_t* s = d + q + 2;
+    const int sl = len - 2;
+    q += len;
+    if (m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
+      if (sof) bad("second SOF marker 0x%02X", m);
+      sof = true;
+      if (sl < 6) bad("SOF segment too short");
+      const int prec = s[0];
+      p.h = be16(s + 1);
+      p.w = be16(s + 3);
+      p.ncomp = s[5];
+      if (sl < 6 + 3 * p.ncomp) bad("SOF segment too short for %d components", p.ncomp);
+      if (p.w == 0) bad("image width 0");
+      for (int c = 0; c < std::min(p.ncomp, 4); ++c) {
+        p.comp[c].id = s[6 + 3 * c];
+        p.comp[c].h = s[7 + 3 * c] >> 4;
+        p.comp[c].v = s[7 + 3 * c] & 15;
+        p.comp[c].tq = s[8 + 3 * c];
+        if (p.comp[c].h < 1 || p.comp[c].h > 4 || p.comp[c].v < 1 || p.comp[c].v > 4) bad("invalid sampling factors of component %d", c);
+        if (p.comp[c].tq > 3) bad("invalid quantisation table index %d", p.comp[c].tq);
+      }
+      if (m == 0xC2 || m == 0xC6) unsupported(p, "progressive JPEG (SOF" + std::to_string(m - 0xC0) + ")");
+      else if (m == 0xC3 || m == 0xC7 || m == 0xCB || m == 0xCF) unsupported(p, "lossless JPEG (SOF" + std::to_string(m - 0xC0) + ")");
+      else if (m >= 0xC9) unsupported(p, "arithmetic coding (SOF" + std::to_string(m - 0xC0) + ")");
+      else if (m == 0xC5) unsupported(p, "hierarchical JPEG (SOF5)");
+      if (prec != 8) unsupported(p, std::to_string(prec) + "-bit samples");
+      if (p.h == 0) unsupported(p, "height given by a DNL marker");
+      if (p.ncomp == 4) unsupported(p, "4 components (CMYK / YCCK)");
+      else if (p.ncomp != 1 && p.ncomp != 3) unsupported(p, std::to_string(p.ncomp) + " components");
+      if (p.ncomp == 3) {
+        const auto& c = p.comp;
+        if (c[1].h != 1 || c[1].v != 1 || c[2].h != 1 || c[2].v != 1) unsupported(p, "chroma sampling factors other than 1x1");
+        else if (c[0].h == 1 && c[0].v == 1) p.sampling = 444;
+        else if (c[0].h == 2 && c[0].v == 1) p.sampling = 422;
+        else if (c[0].h == 2 && c[0].v == 2) p.sampling = 420;
+        else unsupported(p, "luma sampling " + std::to_string(c[0].h) + "x" + std::to_string(c[0].v));
+      } else if (p.ncomp == 1) {
+        p.sampling = 400;
+      }
+    } else if (m == 0xDB) {  // DQT
+      int o = 0;
+      while (o < sl) {
+        const int pq = s[o] >> 4, tq = s[o] & 15;
+        ++o;
+        if (pq > 1 || tq > 3) bad("invalid DQT table %d precision %d", tq, pq);
+        if (o + 64 * (pq + 1) > sl) bad("truncated DQT segment");
+        for (int k = 0; k < 64; ++k) p.qt[tq][h_natural[k]] = pq ? (uint16_t)be16(s + o + 2 * k) : s[o + k];
+        o += 64 * (pq + 1);
+        p.qdef[tq] = true;
+      }
+    } else if (m == 0xC4) {  // DHT
+      int o = 0;
+      while (o < sl) {
+        if (o + 17 > sl) bad("truncated DHT segment");
+        const int tc = s[o] >> 4, th = s[o] & 15;
+        if (tc > 1 || th > 3) bad("invalid DHT class %d / index %d", tc, th);
+        int total = 0;
+        uint8_t bits[17] = {0};
+        for (int l = 1; l <= 16; ++l) total += bits[l] = s[o + l];
+        if (total > 256) bad("DHT table with %d codes (more than 256)", total);
+        if (o + 17 + total > sl) bad("truncated DHT segment");
+        if (!huff_codes(bits, nullptr, nullptr, nullptr, nullptr)) bad("bad Huffman table (class %d, index %d): codes do not fit their lengths", tc, th);
+        memcpy(p.hbits[tc][th], bits, 17);
+        memset(p.hval[tc][th], 0, 256);
+        memcpy(p.hval[tc][th], s + o + 17, total);
+        if (tc == 0)
+          for (int k = 0; k < total; ++k)
+            if (p.hval[tc][th][k] > 15) bad("DC Huffman table %d has a symbol %d > 15", th, p.hval[tc][th][k]);
+        p.hdef[tc][th] = true;
+        o += 17 + total;
+      }
+    } else if (m == 0xDD) {  // DRI
+      if (sl != 2) bad("DRI segment of length %d", len);
+      p.ri = be16(s);
+    } else if (m == 0xE0) {
+      if (sl >= 5 && memcmp(s, "JFIF\0", 5) == 0) jfif = true;
+    } else if (m == 0xEE) {
+      if (sl >= 12 && memcmp(s, "Adobe", 5) == 0) adobe = true, adobe_transform = s[11];
+    } else if (m == 0xDC) {
+      unsupported(p, "DNL marker");
+    } else if (m == 0xDA) {  // SOS
+      if (!sof) bad("SOS before SOF");
+      if (sl < 1) bad("SOS segment too short");
+      const int ns = s[0];
+      if (sl != 4 + 2 * ns || ns < 1 || ns > 4) bad("malformed SOS segment");
+      if (ns != p.ncomp) unsupported(p, "non-interleaved scans (" + std::to_string(ns) + " of " + std::to_string(p.ncomp) + " components)");
+      for (int j = 0; j < ns && j < p.ncomp && p.ncomp <= 4; ++j) {
+        int c = 0;
+        while (c < p.ncomp && p.comp[c].id != s[1 + 2 * j]) ++c;
+        if (c == p.ncomp) bad("SOS names component %d, absent from SOF", s[1 + 2 * j]);
+        if (c != j) unsupported(p, "scan component order differs from the frame's");
+        p.comp[c].td = s[2 + 2 * j] >> 4;
+        p.comp[c].ta = s[2 + 2 * j] & 15;
+        if (p.comp[c].td > 3 || p.comp[c].ta > 3) bad("invalid Huffman table index in SOS");
+      }
+      const int ss = s[1 + 2 * ns], se = s[2 + 2 * ns], ah = s[3 + 2 * ns] >> 4, al = s[3 + 2 * ns] & 15;
+      if (ss != 0 || se != 63 || ah != 0 || al != 0) unsupported(p, "spectral selection / successive approximation in the scan");
+      p.ecs = q;
+      break;
+    }
+    // APPn, COM and every other segment: skipped
+  }
+  if (p.ncomp == 3 && !jfif && ((adobe && adobe_transform == 0) || (!adobe && p.comp[0].id == 'R' && p.comp[1].id == 'G' && p.comp[2].id == 'B')))
+    unsupported(p, "RGB colour space (no YCbCr transform)");
+  // end of the entropy-coded segment: the first marker other than RSTn
+  int64_t e = p.ecs;
+  for (;;) {
+    const void* f = memchr(d + e, 0xFF, (size_t)(n - e));
+    if (f == nullptr) bad("truncated entropy-coded data (no EOI marker)");
+    e = (const uint8_t*)f - d;
+    int64_t k = e + 1;
+    while (k < n && d[k] == 0xFF) ++k;
+    if (k >= n) bad("truncated entropy-coded data (no EOI marker)");
+    if (d[k] == 0x00 || (d[k] >= 0xD0 && d[k] <= 0xD7)) {
+      e = k + 1;
+      continue;
+    }
+    break;
+  }
+  p.ecs_len = e - p.ecs;
+  // what follows: EOI, or segments after which another scan would be unsupported
+  int64_t q2 = e;
+  for (;;) {
+    while (q2 < n && d[q2] == 0xFF) ++q2;
+    if (q2 >= n) bad("truncated after the scan (no EOI marker)");
+    const int m = d[q2++];
+    if (m == 0xD9) break;
+    if (m == 0xDA) {
+      unsupported(p, "more than one scan");
+      break;
+    }
+    if (m == 0xDC) unsupported(p, "DNL marker");
+    if (q2 + 2 > n) bad("truncated marker 0x%02X after the scan", m);
+    const int len = be16(d + q2);
+    if (len < 2 || q2 + len > n) bad("truncated marker segment 0x%02X after the scan", m);
+    q2 += len;
+    if (q2 < n && d[q2] != 0xFF) bad("expected a marker at byte %lld after the scan", (long long)q2);
+  }
+  if (p.why.empty()) {
+    for (int c = 0; c < p.ncomp; ++c) {
+      if (!p.qdef[p.comp[c].tq]) bad("component %d uses undefined quantisation table %d", c, p.comp[c].tq);
+      if (!p.hdef[0][p.comp[c].td]) bad("component %d uses undefined DC Huffman table %d", c, p.comp[c].td);
+      if (!p.hdef[1][p.comp[c].ta]) bad("component %d uses undefined AC Huffman table %d", c, p.comp[c].ta);
+    }
+    p.supported = 1;
+  }
+}
+
+}  // namespace
+
+struct mtgv_jpeg_decoder {
+  int max_images;
+  int64_t max_bytes, max_pixels;
+  int64_t cap_stage, cap_chunks, cap_tiles, cap_segs, cap_blocks, cap_plane;
+  uint8_t* h_stage = nullptr;
+  uint8_t* d_stage = nullptr;
+  uint8_t* d_cs = nullptr;
+  int32_t* d_tile = nullptr;
+  uint32_t* d_slen = nullptr;
+  int32_t* d_err = nullptr;
+  int32_t* d_ok = nullptr;
+  uint32_t* d_seg = nullptr;
+  uint32_t* d_segcnt = nullptr;
+  uint64_t* d_cstart = nullptr;
+  uint64_t* d_cexit = nullptr;
+  uint32_t* d_ccnt = nullptr;
+  int16_t* d_coef = nullptr;
+  uint8_t* d_plane = nullptr;
+  hipEvent_t staged = nullptr;  // the last upload from h_stage
+  bool pending = false;
+  int device = 0;
+};
+
+namespace {
+
+int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
+
+void destroy(mtgv_jpeg_decoder* h) {
+  if (!h) return;
+  if (h->pending) (void)hipEventSynchronize(h->staged);
+  if (h->staged) (void)hipEventDestroy(h->staged);
+  if (h->h_stage) (void)hipHostFree(h->h_stage);
+  void* dev[] = {h->d_stage, h->d_cs,     h->d_tile,   h->d_slen, h->d_err,  h->d_ok,   h->d_seg,
+                 h->d_segcnt, h->d_cstart, h->d_cexit, h->d_ccnt, h->d_coef, h->d_plane};
+  for (void* p : dev)
+    if (p) (void)hipFree(p);
+  delete h;
+}
+
+}  // namespace
+
+MTGV_API int mtgv_jpeg_info(const uint8_t* data, int64_t nbytes, int32_t* info) {
+  return guarded([&] {
+    MTGV_CHECK(info != nullptr, ERR_INVALID, "null info");
+    Parsed p;
+    parse(data, nbytes, p);
+    info[0] = p.h;
+    info[1] = p.w;
+    info[2] = p.ncomp;
+    info[3] = p.sampling;
+    info[4] = p.ri;
+    info[5] = p.supported;
+    set_last_error(p.supported ? std::string() : "jpeg: unsupported: " + p.why);
+  });
+}
+
+MTGV_API int mtgv_jpeg_decoder_create(int32_t max_images, int64_t max_bytes, int64_t max_pixels, mtgv_jpeg_decoder** out) {
+  return guarded([&] {
+    MTGV_CHECK(out != nullptr, ERR_INVALID, "null out");
+    *out = nullptr;
+    MTGV_CHECK(max_images >= 1 && max_bytes >= 1 && max_pixels >= 1, ERR_INVALID, "limits must be positive: %d images, %lld bytes, %lld pixels",
+               max_images, (long long)max_bytes, (long long)max_pixels);
+    MTGV_CHECK(max_bytes < (1ll << 31) && max_pixels < (1ll << 34), ERR_INVALID, "limits too large");
+    auto* h = new mtgv_jpeg_decoder();
+    h->max_images = max_images;
+    h->max_bytes = max_bytes;
+    h->max_pixels = max_pixels;
+    const int64_t n = max_images;
+    h->cap_chunks = max_bytes / CHUNK_BYTES + n;
+    h->cap_tiles = max_bytes / TILE_BYTES + n;
+    h->cap_segs = max_bytes / 2 + n;
+    h->cap_blocks = 3 * ceil_div64(max_pixels, 64);
+    h->cap_plane = 3 * max_pixels;
+    h->cap_stage = align_up(n * (int64_t)sizeof(ImgDesc), 256) + align_up(4 * n * (int64_t)sizeof(HuffTab), 256) +
+                   align_up(5 * (n + 1) * 8, 256) + max_bytes + 16 * n + 256;
+    try {
+      HIP_OK(hipGetDevice(&h->device));
+      HIP_OK(hipHostMalloc((void**)&h->h_stage, h->cap_stage, hipHostMallocDefault));
+      HIP_OK(hipMalloc((void**)&h->d_stage, h->cap_stage));
+      HIP_OK(hipMalloc((void**)&h->d_cs, max_bytes + 16 * n + 256));
+      HIP_OK(hipMalloc((void**)&h->d_tile, h->cap_tiles * 4 * sizeof(int32_t)));
+      HIP_OK(hipMalloc((void**)&h->d_slen, n * sizeof(uint32_t)));
+      HIP_OK(hipMalloc((void**)&h->d_err, n * sizeof(int32_t)));
+      HIP_OK(hipMalloc((void**)&h->d_ok, n * sizeof(int32_t)));
+      HIP_OK(hipMalloc((void**)&h->d_seg, h->cap_segs * sizeof(uint32_t)));
+      HIP_OK(hipMalloc((void**)&h->d_segcnt, h->cap_segs * sizeof(uint32_t)));
+      HIP_OK(hipMalloc((void**)&h->d_cstart, h->cap_chunks * sizeof(uint64_t)));
+      HIP_OK(hipMalloc((void**)&h->d_cexit, h->cap_chunks * sizeof(uint64_t)));
+      HIP_OK(hipMalloc((void**)&h->d_ccnt, h->cap_chunks * sizeof(uint32_t)));
+      HIP_OK(hipMalloc((void**)&h->d_coef, h->cap_blocks * 64 * sizeof(int16_t)));
+      HIP_OK(hipMalloc((void**)&h->d_plane, h->cap_plane));
+      HIP_OK(hipEventCreateWithFlags(&h->staged, hipEventDisableTiming));
+    } catch (...) {
+      destroy(h);
+      throw;
+    }
+    *out = h;
+  });
+}
+
+MTGV_API void mtgv_jpeg_decoder_destroy(mtgv_jpeg_decoder* h) { destroy(h); }
+
+MTGV_API int mtgv_jpeg_decode(mtgv_jpeg_decoder* h, const uint8_t* data_host, const int64_t* offsets, const int64_t* sizes, int32_t n,
+                              uint8_t* dst_dev, const int64_t* dst_offset, const int64_t* dst_pitch, int32_t* status_dev,
+                              void* stream) {
+  return guarded([&] {
+    MTGV_CHECK(h != nullptr, ERR_INVALID, "null decoder");
+    MTGV_CHECK(n >= 0 && n <= h->max_images, ERR_INVALID, "jpeg: %d images, the decoder holds at most %d", n, h->max_images);
+    if (n == 0) return;
+    MTGV_CHECK(data_host && offsets && sizes && dst_dev && dst_offset && dst_pitch && status_dev, ERR_INVALID, "null argument");
+    hipStream_t s = (hipStream_t)stream;
+    // ---- parse every image before touching the staging buffer or launching anything
+    std::vector<Parsed> ps(n);
+    int64_t in_bytes = 0, pix = 0;
+    for (int i = 0; i < n; ++i) {
+      MTGV_CHECK(sizes[i] >= 0 && offsets[i] >= 0, ERR_INVALID, "jpeg: image %d: negative offset or size", i);
+      try {
+        parse(data_host + offsets[i], sizes[i], ps[i]);
+      } catch (const Error& e) {
+        throw Error(e.code, std::string(e.what()) + " (image " + std::to_string(i) + ")");
+      }
+      MTGV_CHECK(ps[i].supported, ERR_INVALID, "jpeg: image %d unsupported: %s", i, ps[i].why.c_str());
+      in_bytes += sizes[i];
+      MTGV_CHECK(dst_pitch[i] >= 3ll * ps[i].w && dst_offset[i] >= 0, ERR_INVALID, "jpeg: image %d: pitch %lld < 3 * width %d", i,
+                 (long long)dst_pitch[i], ps[i].w);
+    }
+    MTGV_CHECK(in_bytes <= h->max_bytes, ERR_INVALID, "jpeg: batch of %lld bytes, the decoder holds at most %lld", (long long)in_bytes,
+               (long long)h->max_bytes);
+    // ---- descriptors, Huffman tables (deduplicated), ragged bases
+    std::vector<ImgDesc> ds(n);
+    std::vector<HuffTab> tabs;
+    std::map<std::string, int> tab_ix;
+    std::vector<int64_t> bases(5 * (size_t)(n + 1), 0);
+    int64_t* cb = bases.data();
+    int64_t* bb = cb + (n + 1);
+    int64_t* sb = bb + (n + 1);
+    int64_t* tb = sb + (n + 1);
+    int64_t* pb = tb + (n + 1);
+    int64_t ecs_off = 0, plane_off = 0;
+    auto table = [&](const uint8_t* bits, const uint8_t* val) {
+      std::string key((const char*)bits, 17);
+      key.append((const char*)val, 256);
+      auto it = tab_ix.find(key);
+      if (it != tab_ix.end()) return it->second;
+      HuffTab t;
+      memset(&t, 0, sizeof(t));
+      memcpy(t.val, val, 256);
+      huff_codes(bits, t.maxcode, t.valoff, t.lut, val);
+      t.maxcode[0] = -1;
+      tabs.push_back(t);
+      return tab_ix[key] = (int)tabs.size() - 1;
+    };
+    for (int i = 0; i < n; ++i) {
+      const Parsed& p = ps[i];
+      ImgDesc& D = ds[i];
+      memset(&D, 0, sizeof(D));
+      D.h = p.h;
+      D.w = p.w;
+      D.ncomp = p.ncomp;
+      D.mode = p.ncomp == 1 ? 0 : p.sampling == 444 ? 1 : p.sampling == 422 ? 2 : 3;
+      const int hm = p.ncomp == 1 ? 1 : p.comp[0].h, vm = p.ncomp == 1 ? 1 : p.comp[0].v;
+      D.mcux = ceil_div(p.w, 8 * hm);
+      D.mcuy = ceil_div(p.h, 8 * vm);
+      const int64_t nmcu = (int64_t)D.mcux * D.mcuy;
+      D.ri = p.ri ? p.ri : (int)std::min<int64_t>(nmcu, 1 << 30);
+      D.nseg = (int)ceil_div64(nmcu, D.ri);
+      MTGV_CHECK(2 * (int64_t)(D.nseg - 1) <= p.ecs_len, ERR_INVALID,
+                 "jpeg: image %d: %d restart intervals cannot fit in %lld bytes of entropy-coded data", i, D.nseg, (long long)p.ecs_len);
+      D.bpm = 0;
+      for (int c = 0; c < p.ncomp; ++c) {
+        const int ch = p.ncomp == 1 ? 1 : p.comp[c].h, cv = p.ncomp == 1 ? 1 : p.comp[c].v;
+        CompDesc& C = D.c[c];
+        memcpy(C.q, p.qt[p.comp[c].tq], sizeof(C.q));
+        C.dc = table(p.hbits[0][p.comp[c].td], p.hval[0][p.comp[c].td]);
+        C.ac = table(p.hbits[1][p.comp[c].ta], p.hval[1][p.comp[c].ta]);
+        C.h = ch;
+        C.v = cv;
+        C.bw = D.mcux * ch;
+        C.bh = D.mcuy * cv;
+        C.plane = plane_off;
+        plane_off += (int64_t)C.bw * 8 * C.bh * 8;
+        for (int y = 0; y < cv; ++y)
+          for (int x = 0; x < ch; ++x, ++D.bpm) {
+            D.bcomp[D.bpm] = (int8_t)c;
+            D.bdx[D.bpm] = (int8_t)x;
+            D.bdy[D.bpm] = (int8_t)y;
+          }
+      }
+      D.nblocks = nmcu * D.bpm;
+      D.ecs = ecs_off;
+      D.ecs_len = p.ecs_len;
+      ecs_off += align_up(p.ecs_len, 8) + 8;
+      D.nchunks = (int)std::max<int64_t>(1, ceil_div64(p.ecs_len, CHUNK_BYTES));
+      D.ntiles = (int)std::max<int64_t>(1, ceil_div64(p.ecs_len, TILE_BYTES));
+      D.chunk0 = cb[i];
+      D.seg0 = sb[i];
+      D.tile0 = tb[i];
+      D.blk0 = bb[i];
+      D.pix0 = pb[i];
+      D.dst_off = dst_offset[i];
+      D.pitch = dst_pitch[i];
+      cb[i + 1] = cb[i] + D.nchunks;
+      bb[i + 1] = bb[i] + D.nblocks;
+      sb[i + 1] = sb[i] + D.nseg;
+      tb[i + 1] = tb[i] + D.ntiles;
+      pb[i + 1] = pb[i] + (int64_t)p.h * p.w;
+      pix += (int64_t)D.mcux * 8 * hm * D.mcuy * 8 * vm;
+    }
+    MTGV_CHECK(pix <= h->max_pixels, ERR_INVALID, "jpeg: batch needs %lld pixels padded to whole MCUs, the decoder holds %lld",
+               (long long)pix, (long long)h->max_pixels);
+    MTGV_CHECK(bb[n] <= h->cap_blocks && plane_off <= h->cap_plane && cb[n] <= h->cap_chunks && tb[n] <= h->cap_tiles &&
+                   sb[n] <= h->cap_segs && ecs_off <= h->max_bytes + 16ll * h->max_images,
+               ERR_INVALID, "jpeg: batch exceeds the decoder's workspace");
+    // ---- staging layout: descriptors | tables | bases | entropy-coded bytes
+    const int64_t o_tab = align_up((int64_t)n * sizeof(ImgDesc), 256);
+    const int64_t o_base = o_tab + align_up((int64_t)tabs.size() * sizeof(HuffTab), 256);
+    const int64_t o_ecs = o_base + align_up((int64_t)bases.size() * 8, 256);
+    const int64_t total = o_ecs + ecs_off;
+    MTGV_CHECK(total <= h->cap_stage, ERR_RUNTIME, "jpeg: staging overflow (%lld > %lld)", (long long)total, (long long)h->cap_stage);
+    if (h->pending) HIP_OK(hipEventSynchronize(h->staged));  // the previous upload has left the pinned buffer
+    h->pending = false;
+    uint8_t* st = h->h_stage;
+    memcpy(st, ds.data(), n * sizeof(ImgDesc));
+    memcpy(st + o_tab, tabs.data(), tabs.size() * sizeof(HuffTab));
+    memcpy(st + o_base, bases.data(), bases.size() * 8);
+    for (int i = 0; i < n; ++i) {
+      memcpy(st + o_ecs + ds[i].ecs, data_host + offsets[i] + ps[i].ecs, ps[i].ecs_len);
+      memset(st + o_ecs + ds[i].ecs + ps[i].ecs_len, 0, align_up(ps[i].ecs_len, 8) + 8 - ps[i].ecs_len);
+    }
+    HIP_OK(hipMemcpyAsync(h->d_stage, st, total, hipMemcpyHostToDevice, s));
+    HIP_OK(hipEventRecord(h->staged, s));
+    h->pending = true;
+    HIP_OK(hipMemsetAsync(h->d_err, 0, n * sizeof(int32_t), s));
+    HIP_OK(hipMemsetAsync(h->d_segcnt, 0, sb[n] * sizeof(uint32_t), s));
+    Params P;
+    P.d = (const ImgDesc*)h->d_stage;
+    P.tabs = (const HuffTab*)(h->d_stage + o_tab);
+    const int64_t* db = (const int64_t*)(h->d_stage + o_base);
+    P.chunk_base = db;
+    P.blk_base = db + (n + 1);
+    P.seg_base = db + 2 * (n + 1);
+    P.tile_base = db + 3 * (n + 1);
+    P.pix_base = db + 4 * (n + 1);
+    P.ecs = h->d_stage + o_ecs;
+    P.n = n;
+    P.cs = h->d_cs;
+    P.tile_cnt = h->d_tile;
+    P.slen = h->d_slen;
+    P.err = h->d_err;
+    P.ok = h->d_ok;
+    P.seg_start = h->d_seg;
+    P.seg_cnt = h->d_segcnt;
+    P.cstart = h->d_cstart;
+    P.cexit = h->d_cexit;
+    P.ccnt = h->d_ccnt;
+    P.coef = h->d_coef;
+    P.plane = h->d_plane;
+    P.dst = dst_dev;
+    P.status = status_dev;
+    const int64_t nch = cb[n];
+    hipLaunchKernelGGL(unstuff_count_kernel, dim3((unsigned)tb[n]), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(unstuff_scan_kernel, dim3(ceil_div(n, 64)), dim3(64), 0, s, P);
+    hipLaunchKernelGGL(unstuff_scatter_kernel, dim3((unsigned)tb[n]), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(sync_kernel, dim3((unsigned)ceil_div64(nch, SYNC_WG)), dim3(SYNC_WG), 0, s, P, nch);
+    hipLaunchKernelGGL(sync_fix_kernel, dim3(ceil_div(n, 64)), dim3(64), 0, s, P);
+    hipLaunchKernelGGL(count_kernel, dim3((unsigned)ceil_div64(nch, 256)), dim3(256), 0, s, P, nch);
+    hipLaunchKernelGGL(verify_kernel, dim3(n), dim3(64), 0, s, P);
+    hipLaunchKernelGGL(write_kernel, dim3((unsigned)ceil_div64(nch, 256)), dim3(256), 0, s, P, nch);
+    hipLaunchKernelGGL(dc_kernel, dim3((unsigned)sb[n]), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(idct_kernel, dim3((unsigned)ceil_div64(bb[n], 32)), dim3(256), 0, s, P, bb[n]);
+    hipLaunchKernelGGL(color_kernel, dim3((unsigned)ceil_div64(pb[n], 256)), dim3(256), 0, s, P, pb[n]);
+    HIP_OK(hipGetLastError());
+  });
+}
+
+namespace {
+// pad of n letterboxed size x size x 3 frames whose (nh, nw) image at (top, left) is written by someone else
+__global__ __launch_bounds__(256) void letterbox_pad_kernel(uint8_t* __restrict__ f, int64_t npix, int size, int nh, int nw, int top,
+                                                            int left, uint8_t v) {
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= npix) return;
+  const int p = (int)(g % ((int64_t)size * size));
+  const int y = p / size - top, x = p % size - left;
+  if (y >= 0 && y < nh && x >= 0 && x < nw) return;
+  uint8_t* o = f + g * 3;
+  o[0] = o[1] = o[2] = v;
+}
+}  // namespace
+
+MTGV_API int mtgv_letterbox_pad_u8(uint8_t* frames_dev, int32_t n, int32_t size, int32_t nh, int32_t nw, int32_t top, int32_t left,
+                                   int32_t pad_value, void* stream) {
+  return guarded([&] {
+    MTGV_CHECK(frames_dev != nullptr || n == 0, ERR_INVALID, "null frames");
+    MTGV_CHECK(n >= 0 && size > 0 && nh >= 0 && nw >= 0 && top >= 0 && left >= 0 && top + nh <= size && left + nw <= size, ERR_INVALID,
+               "letterbox pad: image %dx%d at (%d, %d) outside a %d frame", nh, nw, top, left, size);
+    MTGV_CHECK(pad_value >= 0 && pad_value <= 255, ERR_INVALID, "pad value %d outside [0, 255]", pad_value);
+    const int64_t npix = (int64_t)n * size * size;
+    if (npix == 0) return;
+    hipLaunchKernelGGL(letterbox_pad_kernel, dim3((unsigned)ceil_div64(npix, 256)), dim3(256), 0, (hipStream_t)stream, frames_dev, npix,
+                       size, nh, nw, top, left, (uint8_t)pad_value);
+    HIP_OK(hipGetLastError());
+  });
+}

@@ -4,7 +4,8 @@ Reference dataflow (mtgvision/qdrant_populate.py:70-90, four worker processes, e
     retrieve existing ids -> for each missing card: download -> imread -> make_cropped(size_hw=encoder.input_hwc)
     -> encoder.predict -> QdrantPoint(id, vector) -> save_points.
 Here the same steps run per batch on the GPU: one ragged `make_cropped` launch, one batched encoder forward,
-one append to the device-resident bank.  Downloading / decoding stays with the caller (images arrive as arrays).
+one append to the device-resident bank.  Downloading stays with the caller; images arrive as arrays (`make_cropped`,
+`build_bank`) or as JPEG files decoded on the GPU (`make_cropped_jpeg`, `build_bank_jpeg`, mtgv.jpeg).
 """
 
 from __future__ import annotations
@@ -45,6 +46,62 @@ def make_cropped(images: Sequence[np.ndarray], size_hw=(192, 128), device=None) 
     with torch.cuda.device(dev):
         native.check(native.lib().mtgv_make_cropped(native.ptr(buf), native.ptr(offs_t), native.ptr(hw_t), n, oh, ow, native.ptr(out), native.stream()))
     return out
+
+
+def make_cropped_jpeg(datas: Sequence[bytes], size_hw=(192, 128), device=None, decoder=None) -> torch.Tensor:
+    """list of JPEG card scans -> (n, h, w, 3) float32 in [0,1] on the GPU: one batched GPU decode into the ragged layout,
+    then the same make_cropped launch.  Unsupported or corrupt files raise (mtgv.jpeg.JpegDecoder)."""
+    from .jpeg import JpegDecoder, _padded_pixels, jpeg_info
+
+    native.require_gpu()
+    dev = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    n = len(datas)
+    oh, ow = size_hw
+    out = torch.empty((n, oh, ow, 3), dtype=torch.float32, device=dev)
+    if n == 0:
+        return out
+    if decoder is None:
+        decoder = JpegDecoder(n, sum(len(d) for d in datas), sum(_padded_pixels(jpeg_info(d)) for d in datas), dev)
+    buf, offs_t, hw_t, _ = decoder.decode(datas)
+    with torch.cuda.device(dev):
+        native.check(native.lib().mtgv_make_cropped(native.ptr(buf), native.ptr(offs_t), native.ptr(hw_t), n, oh, ow, native.ptr(out), native.stream()))
+    return out
+
+
+def build_bank_jpeg(cards: Iterable[Tuple[str, bytes]], encoder: Encoder, store: VectorStoreQdrant, batch_size: int = 256) -> int:
+    """build_bank over (id, JPEG bytes) pairs: each batch is decoded on the GPU (make_cropped_jpeg).  Returns the number
+    of cards added."""
+    from .jpeg import JpegDecoder, _padded_pixels, jpeg_info
+
+    h, w, _ = encoder.input_hwc
+    added = 0
+    batch: List[Tuple[str, bytes]] = []
+    dec = None
+
+    def flush():
+        nonlocal added, batch, dec
+        if not batch:
+            return
+        existing = {p.id for p in store.retrieve((cid for cid, _ in batch), with_payload=False)}
+        todo = [(cid, d) for cid, d in batch if str(cid) not in existing]
+        batch = []
+        if not todo:
+            return
+        datas = [d for _, d in todo]
+        nb, pix = sum(len(d) for d in datas), sum(_padded_pixels(jpeg_info(d)) for d in datas)
+        if dec is None or dec.max_images < len(datas) or dec.max_bytes < nb or dec.max_pixels < pix:
+            dec = JpegDecoder(batch_size, max(nb, dec.max_bytes if dec else 0), max(pix, dec.max_pixels if dec else 0), encoder.device)
+        x = make_cropped_jpeg(datas, (h, w), encoder.device, dec)
+        z = encoder.encode(x).cpu().numpy()
+        store.save_points(QdrantPoint(id=str(cid), vector=zi, payload=None) for (cid, _), zi in zip(todo, z))
+        added += len(todo)
+
+    for item in cards:
+        batch.append(item)
+        if len(batch) >= batch_size:
+            flush()
+    flush()
+    return added
 
 
 def build_bank(cards: Iterable[Tuple[str, np.ndarray]], encoder: Encoder, store: VectorStoreQdrant, batch_size: int = 256) -> int:

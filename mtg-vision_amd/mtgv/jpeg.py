@@ -1,0 +1,275 @@
+"""Baseline JPEG decode on the GPU (csrc/jpeg.hip).
+
+The reference decodes every frame on the host (mtgvision/server.py:272-280: cv2.imdecode(..., IMREAD_COLOR_RGB)) and
+reads card scans from JPEG files for the bank build (qdrant_populate.py:70-90).  Here the compressed bytes go to the
+device in one copy per batch and are decoded there:
+
+    dec = JpegDecoder(max_images=32, max_bytes=4 << 20, max_pixels=32 * 640 * 480)
+    frames = dec.decode_frames(list_of_jpeg_bytes)          # (n, 640, 640, 3) uint8, letterboxed, on the GPU
+    buf, offsets, hw, status = dec.decode(list_of_jpeg_bytes)  # ragged RGB, the layout mtgv_make_cropped takes
+
+Supported: baseline / extended sequential Huffman 8-bit (SOF0 / SOF1), greyscale or YCbCr 4:4:4 / 4:2:2 / 4:2:0,
+restart intervals.  The output equals libjpeg-turbo's default decode (Pillow's `Image.open(f).convert("RGB")`).
+Anything else raises before a launch; there is no host fallback inside the library - a caller that wants one checks
+`jpeg_info(data).supported` itself.
+"""
+
+from __future__ import annotations
+
+import ctypes as C
+from typing import List, NamedTuple, Sequence
+
+import numpy as np
+import torch
+
+from . import native
+from .detector import letterbox_geometry
+
+
+class JpegInfo(NamedTuple):
+    h: int
+    w: int
+    components: int
+    sampling: int  # 444 / 422 / 420 / 400 (greyscale), 0 other
+    restart_interval: int  # MCUs per restart segment, 0 none
+    supported: bool
+    reason: str  # first unsupported feature ("" when supported)
+
+
+def jpeg_info(data: bytes) -> JpegInfo:
+    """Header probe on the host (no device needed).  Raises AssertionError for malformed input."""
+    L = native.lib()
+    info = (C.c_int32 * 6)()
+    buf = C.create_string_buffer(bytes(data), len(data)) if len(data) else None
+    native.check(L.mtgv_jpeg_info(buf, len(data), info))
+    sup = bool(info[5])
+    reason = "" if sup else (L.mtgv_last_error() or b"").decode("utf-8", "replace")
+    return JpegInfo(info[0], info[1], info[2], info[3], info[4], sup, reason)
+
+
+def _pack(datas: Sequence[bytes]):
+    datas = [bytes(d) for d in datas]
+    sizes = np.array([len(d) for d in datas], np.int64)
+    offs = np.zeros(len(datas), np.int64)
+    if len(datas) > 1:
+        offs[1:] = np.cumsum(sizes)[:-1]
+    blob = np.frombuffer(b"".join(datas), np.uint8) if sizes.sum() else np.zeros(1, np.uint8)
+    return np.ascontiguousarray(blob), offs, sizes
+
+
+def _p(a: np.ndarray):
+    return C.c_void_p(a.ctypes.data)
+
+
+class JpegDecoder:
+    """Batched GPU JPEG decoder.  Limits (fixed here, workspace allocated once): max_images per call, max_bytes of
+    compressed data per call, max_pixels per call counted after padding each image to whole MCUs (8 or 16 pixels).
+    Not thread-safe; calls run on the current stream of `device`."""
+
+    def __init__(self, max_images: int, max_bytes: int, max_pixels: int, device=None):
+        native.require_gpu()
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.max_images, self.max_bytes, self.max_pixels = int(max_images), int(max_bytes), int(max_pixels)
+        self._h = native.c_vp(0)
+        with torch.cuda.device(self.device):
+            native.check(native.lib().mtgv_jpeg_decoder_create(self.max_images, self.max_bytes, self.max_pixels, C.byref(self._h)))
+
+    def _infos(self, datas: Sequence[bytes]) -> List[JpegInfo]:
+        infos = [jpeg_info(d) for d in datas]
+        bad = [(i, f.reason) for i, f in enumerate(infos) if not f.supported]
+        if bad:
+            raise AssertionError(f"jpeg: unsupported input (no GPU decode; decode these on the host): {bad}")
+        return infos
+
+    def _launch(self, datas, dst: torch.Tensor, dst_off: np.ndarray, pitch: np.ndarray) -> torch.Tensor:
+        """decode into dst (uint8 device tensor), synchronise, raise on a non-zero status"""
+        n = len(datas)
+        blob, offs, sizes = _pack(datas)
+        status = torch.empty(n, dtype=torch.int32, device=self.device)
+        dst_off = np.ascontiguousarray(dst_off, np.int64)
+        pitch = np.ascontiguousarray(pitch, np.int64)
+        with torch.cuda.device(self.device):
+            native.check(native.lib().mtgv_jpeg_decode(self._h, _p(blob), _p(offs), _p(sizes), n, native.ptr(dst), _p(dst_off), _p(pitch),
+                                                       native.ptr(status), native.stream()))
+        return status
+
+    @staticmethod
+    def _raise_on_status(status: torch.Tensor) -> None:
+        st = status.cpu().numpy()  # synchronises
+        failed = np.nonzero(st)[0].tolist()
+        if failed:
+            raise RuntimeError(f"jpeg: corrupt entropy-coded data in image(s) {failed} of the batch")
+
+    def decode(self, datas: Sequence[bytes], check: bool = True):
+        """JPEG files -> (buf (sum h*w*3,) uint8, offsets (n,) int64, hw (n, 2) int32, status (n,) int32), all on the
+        device: images back to back in HWC RGB, the ragged layout mtgv_make_cropped takes.  With check (default) the
+        call synchronises and raises RuntimeError naming the images whose stream did not decode."""
+        infos = self._infos(datas)
+        n = len(datas)
+        hw = np.array([(f.h, f.w) for f in infos], np.int64).reshape(n, 2)
+        nbytes = hw[:, 0] * hw[:, 1] * 3
+        offs = np.zeros(n, np.int64)
+        if n > 1:
+            offs[1:] = np.cumsum(nbytes)[:-1]
+        buf = torch.empty(int(nbytes.sum()), dtype=torch.uint8, device=self.device)
+        if n == 0:
+            z = torch.zeros(0, dtype=torch.int64, device=self.device)
+            return buf, z, z.view(0, 2).int(), z.int()
+        status = self._launch(datas, buf, offs, hw[:, 1] * 3)
+        if check:
+            self._raise_on_status(status)
+        return buf, torch.from_numpy(offs).to(self.device), torch.from_numpy(hw.astype(np.int32)).to(self.device), status
+
+    @staticmethod
+    def images(buf: torch.Tensor, offsets, hw) -> List[torch.Tensor]:
+        """per-image (h, w, 3) views of decode()'s buffer"""
+        offsets = offsets.cpu().tolist() if torch.is_tensor(offsets) else list(offsets)
+        hw = hw.cpu().tolist() if torch.is_tensor(hw) else list(hw)
+        return [buf[o : o + h * w * 3].view(h, w, 3) for o, (h, w) in zip(offsets, hw)]
+
+    def decode_frames(self, datas: Sequence[bytes], size: int = 640, pad_value: int = 114, out: torch.Tensor = None, check: bool = True):
+        """JPEG frames -> (n, size, size, 3) uint8 letterboxed frames on the GPU (mtgv.detector.letterbox_geometry).  A frame
+        that already fits (640x480 webcam frames) is decoded straight into its padded frame through offset and pitch and only
+        the pad is filled; any other is decoded to scratch and resampled by mtgv_letterbox_u8."""
+        infos = self._infos(datas)
+        n = len(datas)
+        if out is None:
+            out = torch.empty((n, size, size, 3), dtype=torch.uint8, device=self.device)
+        assert out.shape == (n, size, size, 3) and out.dtype == torch.uint8 and out.is_contiguous()
+        if n == 0:
+            return out
+        L = native.lib()
+        fsz = size * size * 3
+        geo = [letterbox_geometry(f.h, f.w, size) for f in infos]
+        direct = [i for i, f in enumerate(infos) if (geo[i][1], geo[i][2]) == (f.h, f.w)]
+        other = [i for i in range(n) if (geo[i][1], geo[i][2]) != (infos[i].h, infos[i].w)]
+        dst_off = np.zeros(n, np.int64)
+        pitch = np.zeros(n, np.int64)
+        scratch = None
+        if other:
+            sz = np.array([infos[i].h * infos[i].w * 3 for i in other], np.int64)
+            soff = np.concatenate([[0], np.cumsum(sz)[:-1]]).astype(np.int64)
+            scratch = torch.empty(int(sz.sum()), dtype=torch.uint8, device=self.device)
+        # one decode writes into the frames and the scratch: two destinations, one base pointer -> offsets relative to
+        # the lower of the two allocations
+        base = out if scratch is None else (out if out.data_ptr() <= scratch.data_ptr() else scratch)
+        b0 = base.data_ptr()
+        for i in direct:
+            _, nh, nw, top, left = geo[i]
+            dst_off[i] = out.data_ptr() - b0 + i * fsz + (top * size + left) * 3
+            pitch[i] = size * 3
+        for j, i in enumerate(other):
+            dst_off[i] = scratch.data_ptr() - b0 + int(soff[j])
+            pitch[i] = infos[i].w * 3
+        status = self._launch(datas, base, dst_off, pitch)
+        with torch.cuda.device(self.device):
+            groups = {}
+            for i in direct:
+                groups.setdefault(geo[i][1:], []).append(i)
+            for (nh, nw, top, left), idx in groups.items():
+                runs = _runs(idx)
+                for a, b in runs:  # consecutive frames of one geometry: one launch
+                    native.check(L.mtgv_letterbox_pad_u8(C.c_void_p(out.data_ptr() + a * fsz), b - a, size, nh, nw, top, left, pad_value,
+                                                         native.stream()))
+            for j, i in enumerate(other):
+                f = infos[i]
+                _, nh, nw, top, left = geo[i]
+                native.check(L.mtgv_letterbox_u8(C.c_void_p(scratch.data_ptr() + int(soff[j])), f.h, f.w, C.c_void_p(out.data_ptr() + i * fsz),
+                                                 size, nh, nw, top, left, pad_value, native.stream()))
+        if scratch is not None:
+            scratch.record_stream(torch.cuda.current_stream(self.device))
+        if check:
+            self._raise_on_status(status)
+        self.last_status = status
+        return out
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) and self._h.value:
+                native.lib().mtgv_jpeg_decoder_destroy(self._h)
+                self._h = native.c_vp(0)
+        except Exception:
+            pass
+
+
+def _runs(idx: List[int]):
+    """[(start, end)) runs of consecutive integers"""
+    out, s = [], None
+    for k, i in enumerate(idx):
+        if s is None:
+            s = i
+        if k + 1 == len(idx) or idx[k + 1] != i + 1:
+            out.append((s, i + 1))
+            s = None
+    return out
+
+
+class JpegFrames:
+    """Frame batches that arrive as JPEG bytes (one file per websocket message, mtgvision/server.py:272-280), decoded on
+    the GPU into a small ring of letterboxed frame buffers on a stream of their own; the same lease interface as
+    mtgv.pipeline.HostFrames, so `Pipeline.run_many(src.leases(n))` consumes them unchanged.
+
+    A lease's `tensor()` makes the consuming stream wait for its decode; `done()` (called by the pipeline after the de-warp)
+    lets the buffer be overwritten by the decode `depth` batches later.  The host parse and the staging copy happen when a
+    lease is issued (unsupported input raises there); a lease's `status` is its batch's (n,) int32 device status word,
+    which the caller reads once the pipeline's outputs are synchronised (reading it earlier would stall the overlap)."""
+
+    def __init__(self, jpeg_batches: Sequence[Sequence[bytes]], device, size: int = 640, pad_value: int = 114, depth: int = 3,
+                 decoder: JpegDecoder = None):
+        assert depth >= 2 and len(jpeg_batches) > 0
+        self.batches = [list(b) for b in jpeg_batches]
+        self.device = torch.device(device)
+        self.size, self.pad_value, self.depth = size, pad_value, depth
+        n = max(len(b) for b in self.batches)
+        if decoder is None:
+            nbytes = max(sum(len(d) for d in b) for b in self.batches)
+            pix = max(sum(_padded_pixels(jpeg_info(d)) for d in b) for b in self.batches)
+            decoder = JpegDecoder(n, nbytes, pix, self.device)
+        self.dec = decoder
+        self.s_dec = torch.cuda.Stream(self.device)
+        self.bufs = [torch.empty((n, size, size, 3), dtype=torch.uint8, device=self.device) for _ in range(depth)]
+        self.decoded = [torch.cuda.Event() for _ in range(depth)]
+        self.released = [None] * depth
+        self._issued = 0
+
+    class _Lease:
+        def __init__(self, src, slot, n, status):
+            self.src, self.slot, self.n, self.status = src, slot, n, status
+
+        def tensor(self) -> torch.Tensor:
+            torch.cuda.current_stream(self.src.device).wait_event(self.src.decoded[self.slot])
+            return self.src.bufs[self.slot][: self.n]
+
+        def done(self) -> None:
+            ev = torch.cuda.Event()
+            ev.record(torch.cuda.current_stream(self.src.device))
+            self.src.released[self.slot] = ev
+
+    def _issue(self, batch_index: int):
+        j = self._issued % self.depth
+        datas = self.batches[batch_index % len(self.batches)]
+        self._issued += 1
+        with torch.cuda.stream(self.s_dec):
+            if self.released[j] is not None:
+                self.s_dec.wait_event(self.released[j])  # the batch that used this buffer has been de-warped
+            n = len(datas)
+            self.dec.decode_frames(datas, self.size, self.pad_value, out=self.bufs[j][:n], check=False)
+            status = self.dec.last_status
+            self.decoded[j].record(self.s_dec)
+        return JpegFrames._Lease(self, j, n, status)
+
+    def leases(self, n: int):
+        """n leases of batches 0, 1, ... (cyclically), decodes one to two batches ahead of their consumer (HostFrames.leases)"""
+        ahead = [self._issue(b) for b in range(min(n, self.depth - 1))]
+        issued = len(ahead)
+        for i in range(n):
+            if i > 0 and issued < n:
+                ahead.append(self._issue(issued))
+                issued += 1
+            yield ahead.pop(0)
+
+
+def _padded_pixels(f: JpegInfo) -> int:
+    m = 16 if f.sampling == 420 else 8
+    mx = 16 if f.sampling in (420, 422) else 8
+    return -(-f.h // m) * m * (-(-f.w // mx) * mx)

@@ -101,6 +101,11 @@ SIGNATURES = {
     "mtgv_mask_quads": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mtgv_mask_quads_logits": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mtgv_make_cropped": (C.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "mtgv_letterbox_pad_u8": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "mtgv_jpeg_info": (C.c_int, [c_vp, c_i64, C.POINTER(c_i32)]),
+    "mtgv_jpeg_decoder_create": (C.c_int, [c_i32, c_i64, c_i64, C.POINTER(c_vp)]),
+    "mtgv_jpeg_decoder_destroy": (None, [c_vp]),
+    "mtgv_jpeg_decode": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mtgv_op_linear": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "mtgv_op_linear_ex_part_floats": (c_i64, [c_i32, c_i32, c_i32, c_i32, c_i32]),
     "mtgv_op_last_grn_layout": (C.c_int, [c_vp, c_vp]),
