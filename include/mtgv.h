@@ -327,6 +327,32 @@ MTGV_API int mtgv_jpeg_decode(mtgv_jpeg_decoder* h, const uint8_t* data_host, co
                               int32_t* status_dev, void* stream);
 
 /* ------------------------------------------------------------------------- */
+/* JPEG encode: the card thumbnails of mtgvision/server.py:222-225 (encode_rgb_im:           */
+/* cv2.imencode(".jpg", ..., quality 50) on the host) are encoded on the GPU.  RGB uint8 in, baseline sequential   */
+/* Huffman JPEG (SOF0) out: JFIF header, YCbCr 4:2:0 or 4:4:4, the Annex K tables scaled to quality 1..100 (clamped */
+/* to 255), islow forward DCT, no restart markers.  The files are byte for byte libjpeg-turbo's with its defaults  */
+/* (Pillow's Image.save(f, "JPEG", quality=q, subsampling=2 / 0)).  Anything else is refused with status 1.         */
+/* ------------------------------------------------------------------------- */
+typedef struct mtgv_jpeg_encoder mtgv_jpeg_encoder;
+/* host only: worst-case file size of one h x w image (sampling 420 / 444), 0xFF stuffing included */
+MTGV_API int mtgv_jpeg_encode_bound(int32_t h, int32_t w, int32_t sampling, int64_t* nbytes);
+/* host only: the bytes from SOI through SOS exactly as the encoder writes them (623 bytes) */
+MTGV_API int mtgv_jpeg_encode_header(int32_t h, int32_t w, int32_t quality, int32_t sampling, uint8_t* out_host, int64_t capacity,
+                                     int64_t* nbytes);
+/* Limits of one call: max_images images, max_pixels pixels in all once every image is padded to whole MCUs (multiples
+ * of 16 for 4:2:0, of 8 for 4:4:4; a 192 x 128 crop needs 192 * 128).  Every device workspace is allocated (and the
+ * bit-stream workspace cleared) here, never inside an encode.  Bound to the device current at creation. */
+MTGV_API int mtgv_jpeg_encoder_create(int32_t max_images, int64_t max_pixels, mtgv_jpeg_encoder** out);
+MTGV_API void mtgv_jpeg_encoder_destroy(mtgv_jpeg_encoder* h);
+/* n contiguous height x width x 3 RGB uint8 images at src_dev -> n JPEG files back to back in out_dev; file i is
+ * out_dev[out_offsets_dev[i], out_offsets_dev[i + 1]) (n + 1 int64 on the device, out_offsets_dev[0] = 0).  Quality
+ * 1..100, sampling 420 / 444, sizes 1..65535, the handle's limits and out_capacity >= n * mtgv_jpeg_encode_bound are
+ * checked before any launch (status 1, a "jpeg:" message).  Asynchronous on `stream`, library kernels only; nothing is
+ * written past out_offsets_dev[n]. */
+MTGV_API int mtgv_jpeg_encode(mtgv_jpeg_encoder* h, const uint8_t* src_dev, int32_t n, int32_t height, int32_t width, int32_t quality,
+                              int32_t sampling, uint8_t* out_dev, int64_t out_capacity, int64_t* out_offsets_dev, void* stream);
+
+/* ------------------------------------------------------------------------- */
 /* Single ops (unit-test and composition surface; same kernels the handles use) */
 /* ------------------------------------------------------------------------- */
 /* out[M,N] = act(A[M,K] W[N,K]^T + bias) (+res);  act: 0 none 1 gelu 2 mish 3 silu 4 sigmoid */

@@ -273,3 +273,83 @@ def _padded_pixels(f: JpegInfo) -> int:
     m = 16 if f.sampling == 420 else 8
     mx = 16 if f.sampling in (420, 422) else 8
     return -(-f.h // m) * m * (-(-f.w // mx) * mx)
+
+
+# ---------------------------------------------------------------------------------------------------------------------
+# encode (csrc/jpeg_enc.hip)
+
+SAMPLINGS = (420, 444)
+
+
+def jpeg_encode_bound(h: int, w: int, sampling: int = 420) -> int:
+    """worst-case file size in bytes of one h x w image (host only, no device needed)"""
+    n = C.c_int64(0)
+    native.check(native.lib().mtgv_jpeg_encode_bound(int(h), int(w), int(sampling), C.byref(n)))
+    return n.value
+
+
+def jpeg_header(h: int, w: int, quality: int = 50, sampling: int = 420) -> bytes:
+    """the bytes from SOI through SOS exactly as the encoder writes them (host only)"""
+    buf = (C.c_uint8 * 1024)()
+    n = C.c_int64(0)
+    native.check(native.lib().mtgv_jpeg_encode_header(int(h), int(w), int(quality), int(sampling), buf, len(buf), C.byref(n)))
+    return bytes(buf[: n.value])
+
+
+class JpegEncoder:
+    """Batched GPU JPEG encoder: (N, H, W, 3) RGB uint8 -> N baseline JPEG files, byte for byte what Pillow (libjpeg-turbo)
+    writes with `Image.save(f, "JPEG", quality=q, subsampling=2 / 0)` for sampling 420 / 444.
+
+        enc = JpegEncoder(max_images=256, max_pixels=256 * 192 * 128)
+        buf, offsets = enc.encode_device(crops)       # packed files + (N + 1,) int64 offsets, on the device, no sync
+        files = enc.encode(crops)                     # list of bytes: one synchronisation, two copies
+
+    Limits (fixed here, workspace allocated once): max_images per call, max_pixels per call counted after padding each
+    image to whole MCUs (multiples of 16 for 4:2:0, 8 for 4:4:4).  Not thread-safe; calls run on the current stream of
+    `device` and launch library kernels only."""
+
+    def __init__(self, max_images: int, max_pixels: int, device=None):
+        native.require_gpu()
+        self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+        self.max_images, self.max_pixels = int(max_images), int(max_pixels)
+        self._h = native.c_vp(0)
+        with torch.cuda.device(self.device):
+            native.check(native.lib().mtgv_jpeg_encoder_create(self.max_images, self.max_pixels, C.byref(self._h)))
+
+    def encode_device(self, images: torch.Tensor, quality: int = 50, sampling: int = 420, out: torch.Tensor = None):
+        """(N, H, W, 3) uint8 device tensor -> (buf, offsets): file i is buf[offsets[i]:offsets[i + 1]].  buf holds
+        N * jpeg_encode_bound(H, W, sampling) bytes (or is `out`, at least that large); both stay on the device and
+        the call does not synchronise."""
+        assert images.dim() == 4 and images.shape[-1] == 3 and images.dtype == torch.uint8, (tuple(images.shape), images.dtype)
+        assert images.device == self.device, (images.device, self.device)
+        images = images.contiguous()
+        n, h, w = int(images.shape[0]), int(images.shape[1]), int(images.shape[2])
+        cap = n * jpeg_encode_bound(h, w, sampling) if n else 0
+        if out is None:
+            out = torch.empty(max(cap, 1), dtype=torch.uint8, device=self.device)
+        assert out.dtype == torch.uint8 and out.device == self.device and out.is_contiguous()
+        offsets = torch.empty(n + 1, dtype=torch.int64, device=self.device)
+        with torch.cuda.device(self.device):
+            native.check(native.lib().mtgv_jpeg_encode(self._h, native.ptr(images), n, h, w, int(quality), int(sampling), native.ptr(out),
+                                                       out.numel(), native.ptr(offsets), native.stream()))
+        return out, offsets
+
+    def encode(self, images: torch.Tensor, quality: int = 50, sampling: int = 420) -> List[bytes]:
+        """(N, H, W, 3) uint8 device tensor -> N JPEG files on the host"""
+        buf, offsets = self.encode_device(images, quality, sampling)
+        return split_files(buf, offsets)
+
+    def __del__(self):
+        try:
+            if getattr(self, "_h", None) and self._h.value:
+                native.lib().mtgv_jpeg_encoder_destroy(self._h)
+                self._h = native.c_vp(0)
+        except Exception:
+            pass
+
+
+def split_files(buf: torch.Tensor, offsets: torch.Tensor) -> List[bytes]:
+    """encode_device's (buf, offsets) -> list of bytes: the offsets first (this synchronises), then the used part of buf"""
+    off = offsets.cpu().numpy()
+    data = buf[: int(off[-1])].cpu().numpy().tobytes()
+    return [data[int(off[i]) : int(off[i + 1])] for i in range(len(off) - 1)]

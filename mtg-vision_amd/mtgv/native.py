@@ -106,6 +106,11 @@ SIGNATURES = {
     "mtgv_jpeg_decoder_create": (C.c_int, [c_i32, c_i64, c_i64, C.POINTER(c_vp)]),
     "mtgv_jpeg_decoder_destroy": (None, [c_vp]),
     "mtgv_jpeg_decode": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mtgv_jpeg_encode_bound": (C.c_int, [c_i32, c_i32, c_i32, C.POINTER(c_i64)]),
+    "mtgv_jpeg_encode_header": (C.c_int, [c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, C.POINTER(c_i64)]),
+    "mtgv_jpeg_encoder_create": (C.c_int, [c_i32, c_i64, C.POINTER(c_vp)]),
+    "mtgv_jpeg_encoder_destroy": (None, [c_vp]),
+    "mtgv_jpeg_encode": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_i64, c_vp, c_vp]),
     "mtgv_op_linear": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "mtgv_op_linear_ex_part_floats": (c_i64, [c_i32, c_i32, c_i32, c_i32, c_i32]),
     "mtgv_op_last_grn_layout": (C.c_int, [c_vp, c_vp]),

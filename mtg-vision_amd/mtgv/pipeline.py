@@ -92,12 +92,25 @@ def _frames_of(item):
 
 class Pipeline:
     def __init__(self, detector: Detector, encoder: Encoder, matcher, cards_per_frame: int = 8, top_k: int = 1,
-                 match_fn: Optional[Callable] = None, quad_source: str = "box"):
+                 match_fn: Optional[Callable] = None, quad_source: str = "box", thumbnail_quality: Optional[int] = None):
         """quad_source: "box" crops the detection boxes (the synthetic bench workload, SURVEY.md section 8d config 4);
         "mask" crops the oriented quad fitted to each detection's mask, as the reference does
-        (od_export.py:52-111: InstanceSeg._orient + extract_dewarped)."""
+        (od_export.py:52-111: InstanceSeg._orient + extract_dewarped).
+        thumbnail_quality: when set, every step's crops are also encoded as 4:2:0 JPEG files at that quality on the GPU
+        right after the de-warp, on the stream that made them (the thumbnails of mtgvision/server.py:222-225); the
+        output gains `thumbs` (packed files, device) and `thumb_offsets` ((F * K + 1,) int64, device), file j being
+        thumbs[thumb_offsets[j]:thumb_offsets[j + 1]].  None (default): no encode, no extra launch."""
         assert quad_source in ("box", "mask"), quad_source
         self.quad_source = quad_source
+        self.thumbnail_quality = None if thumbnail_quality is None else int(thumbnail_quality)
+        self._jpeg = None
+        if self.thumbnail_quality is not None:
+            from .jpeg import JpegEncoder
+
+            assert 1 <= self.thumbnail_quality <= 100, thumbnail_quality
+            h, w = encoder.cfg.image_hw
+            # the encoder takes at most encoder.max_batch crops per step
+            self._jpeg = JpegEncoder(encoder.max_batch, encoder.max_batch * (-(-h // 16) * 16) * (-(-w // 16) * 16), detector.device)
         self.detector, self.encoder, self.matcher = detector, encoder, matcher
         self.K = int(cards_per_frame)
         self.top_k = int(top_k)
@@ -110,7 +123,14 @@ class Pipeline:
         self._warp_ws = None
 
     def _embed_match(self, frames_u8: torch.Tensor, det, lease=None):
-        return self._embed(det, *self._crop(frames_u8, det, lease))
+        boxes, crops = self._crop(frames_u8, det, lease)
+        return self._embed(det, boxes, crops, *self._thumbnails(crops))
+
+    def _thumbnails(self, crops):
+        """(thumbs, thumb_offsets): the crops as JPEG files, encoded on the current stream; (None, None) when off"""
+        if self._jpeg is None:
+            return None, None
+        return self._jpeg.encode_device(crops, self.thumbnail_quality, 420)
 
     def _crop(self, frames_u8: torch.Tensor, det, lease=None):
         """detections -> (boxes (F, K, 4), crops (F * K, h, w, 3) uint8): the K best boxes or mask quadrilaterals, de-warped"""
@@ -134,7 +154,7 @@ class Pipeline:
             lease.done()  # the de-warp is the last reader of the frames
         return boxes, crops
 
-    def _embed(self, det, boxes, crops, match_stream=None):
+    def _embed(self, det, boxes, crops, thumbs=None, thumb_offsets=None, match_stream=None):
         F, K = boxes.shape[0], self.K
         z = self.encoder.encode(crops)
         if match_stream is None:
@@ -146,7 +166,7 @@ class Pipeline:
                 match_stream.wait_event(ev)
                 z.record_stream(match_stream)
                 ids, scores = self.match_fn(z, self.top_k)
-        return {
+        out = {
             "ids": ids.view(F, K, self.top_k),
             "scores": scores.view(F, K, self.top_k),
             "n_det": det["n_det"],
@@ -155,6 +175,9 @@ class Pipeline:
             "z": z,
             "det": det,
         }
+        if thumbs is not None:
+            out["thumbs"], out["thumb_offsets"] = thumbs, thumb_offsets
+        return out
 
     @staticmethod
     def overlap_enabled() -> bool:
@@ -237,6 +260,8 @@ class Pipeline:
                     cropped = self._crop(frames, det, lease) if crop_on_det else None
                     ev = torch.cuda.Event()
                     ev.record(self._s_det)
+                    if cropped is not None:  # behind the event: this batch's embed does not wait for its thumbnails
+                        cropped = (*cropped, *self._thumbnails(cropped[1]))
                 nxt = (frames, det, ev, lease, cropped)
             if pending is not None:
                 pf, pdet, pev, please, pcrop = pending
@@ -253,8 +278,9 @@ class Pipeline:
         if s_match is not None:
             cur.wait_stream(s_match)
         for o in outs:
-            for t in (o["ids"], o["scores"], o["z"], o["crops"], o["boxes"]):
-                t.record_stream(cur)
+            for t in (o["ids"], o["scores"], o["z"], o["crops"], o["boxes"], o.get("thumbs"), o.get("thumb_offsets")):
+                if t is not None:
+                    t.record_stream(cur)
         return outs
 
     def run(self, frames_u8: torch.Tensor, flip_rgb: bool = True):

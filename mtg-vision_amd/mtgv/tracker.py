@@ -12,7 +12,8 @@ cards and join their payloads.  Differences, all on the host side:
   published algorithm - per-coordinate constant-velocity Kalman filter with norfair's default parameters, detections
   matched greedily against the predicted positions, hit counters (-1 per frame, +2 per hit, capped), ids handed out after
   the initialisation delay: PARITY UNPINNED.  `MeanEuclideanTracker` is the same policy without the filter.
-* JPEG thumbnails (`encode_rgb_im`, server.py:223-226) use Pillow instead of cv2.
+* JPEG thumbnails (`encode_rgb_im`, server.py:223-226) use Pillow instead of cv2, or, with `jpeg_encoder`, one GPU
+  call per frame (`mtgv.jpeg.JpegEncoder`, byte for byte Pillow's files).
 """
 
 from __future__ import annotations
@@ -31,6 +32,27 @@ def get_color(seed) -> str:
     """stable '#rrggbb' per track id (server.py:215-221)"""
     h = int(hashlib.sha256(str(seed).encode()).hexdigest(), 16)
     return f"#{(h >> 16) & 0xFF:02x}{(h >> 8) & 0xFF:02x}{h & 0xFF:02x}"
+
+
+def encode_rgb_images_gpu(encoder, ims: list) -> list:
+    """base64 JPEG (quality 50, 4:2:0) of RGB uint8 images with a `mtgv.jpeg.JpegEncoder`: one encode per run of
+    same-sized images that fits the encoder's limits; the strings equal `encode_rgb_im`'s"""
+    import torch
+
+    from .jpeg import split_files
+
+    out = [None] * len(ims)
+    groups: dict = {}
+    for j, im in enumerate(ims):
+        groups.setdefault(np.asarray(im).shape, []).append(j)
+    for (h, w, _), idx in groups.items():
+        per = max(1, min(encoder.max_images, encoder.max_pixels // max(1, (-(-h // 16) * 16) * (-(-w // 16) * 16))))
+        for a in range(0, len(idx), per):
+            part = idx[a : a + per]
+            batch = torch.from_numpy(np.ascontiguousarray(np.stack([ims[j] for j in part]))).to(encoder.device)
+            for j, f in zip(part, split_files(*encoder.encode_device(batch, 50, 420))):
+                out[j] = base64.b64encode(f).decode("utf-8")
+    return out
 
 
 def encode_rgb_im(rgb_im: np.ndarray) -> Optional[str]:
@@ -236,15 +258,17 @@ class KalmanPointTracker:
 
 class TrackerCtx:
     def __init__(self, update_wait_sec: float = 0.5, ewma_weight: float = 0.1, *, segmenter, encoder, vecs, data=None,
-                 clock: Callable[[], float] = time.time, thumbnails: bool = True):
+                 clock: Callable[[], float] = time.time, thumbnails: bool = True, jpeg_encoder=None):
         """segmenter(frame) -> list[InstanceSeg]; encoder: `mtgv.Encoder` (batched `.encode`) or anything with
         `.predict(rgb_im)`; vecs: `VectorStoreQdrant`; data: optional card index with `.get_card_by_id(id)`
-        (the reference's SyntheticBgFgMtgImages, server.py:190-193)."""
+        (the reference's SyntheticBgFgMtgImages, server.py:190-193); jpeg_encoder: optional `mtgv.jpeg.JpegEncoder`
+        that encodes the frame's thumbnails in one GPU call instead of one Pillow call per track (same bytes)."""
         self.update_wait_sec = update_wait_sec
         self.ewma_weight = ewma_weight
         self.segmenter, self.encoder, self.vecs, self.data = segmenter, encoder, vecs, data
         self.clock = clock
         self.thumbnails = thumbnails
+        self.jpeg_encoder = jpeg_encoder
         self.tracker = KalmanPointTracker(distance_threshold=300, hit_counter_max=5, initialization_delay=2)
         self.tracked_data: dict[int, TrackedData] = {}
 
@@ -266,10 +290,13 @@ class TrackerCtx:
                 self.tracked_data[tid] = trk
             trk.last_instance = seg
             trk.last_rgb_im = seg.extract_dewarped(rgb_frame)
-            trk.last_rgb_im_encoded = encode_rgb_im(trk.last_rgb_im) if self.thumbnails else None
+            trk.last_rgb_im_encoded = encode_rgb_im(trk.last_rgb_im) if self.thumbnails and self.jpeg_encoder is None else None
             if now - trk.last_update_time > self.update_wait_sec or trk.avg_z is None:
                 due.append(trk)
             objs.append(trk)
+        if self.thumbnails and self.jpeg_encoder is not None and objs:
+            for t, e in zip(objs, encode_rgb_images_gpu(self.jpeg_encoder, [t.last_rgb_im for t in objs])):
+                t.last_rgb_im_encoded = e
         if due:
             zs = self._embed([t.last_rgb_im for t in due])
             for t, z in zip(due, zs):
