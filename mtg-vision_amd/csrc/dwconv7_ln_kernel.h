@@ -2,6 +2,7 @@
 // packed-FP32 VALU instructions; PK is always 0 - it kept a packed build of round 3 apart at link time).
 #pragma once
 #include "common.h"
+#include "dwconv7_ln_image_kernel.h"
 #include "dwconv7_ln_stream_kernel.h"
 #include "sp8.h"
 
@@ -147,7 +148,7 @@ __global__ __launch_bounds__(256) void dwconv7_ln_rows_kernel(const float* __res
   const int tid = threadIdx.x;
   if (WL) {
     float* wdst = stat + ((S * P * 2 + 3) & ~3);
-    for (int i = tid; i < 49 * c4n; i += 256) reinterpret_cast<f32x4*>(wdst)[i] = reinterpret_cast<const f32x4*>(w49)[i];
+    for (int i = tid; i < 49 * c4n; i += blockDim.x) reinterpret_cast<f32x4*>(wdst)[i] = reinterpret_cast<const f32x4*>(w49)[i];
     wl = wdst;
     __syncthreads();
   }
@@ -274,7 +275,9 @@ static void dwconv7_ln_rows_launch(const float* in, const float* w49, const floa
       attr[dev] = true;
     }
   }
-  hipLaunchKernelGGL((dwconv7_ln_rows_kernel<TW, TH, SP8, WL>), dim3(grid), dim3(256), lds, s, in, w49, bias, ln_w, ln_b, out, H, W, C,
+  // S * c4n threads rounded up to a wave: at C = 384 / 640 / 768 a fourth wave would hold no strip and only sit at the barriers
+  const unsigned threads = (unsigned)((S * c4n + 63) / 64 * 64);
+  hipLaunchKernelGGL((dwconv7_ln_rows_kernel<TW, TH, SP8, WL>), dim3(grid), dim3(threads), lds, s, in, w49, bias, ln_w, ln_b, out, H, W, C,
                      nstrips, nhg, total_strips, S, eps);
   HIP_OK(hipGetLastError());
 }
@@ -292,6 +295,23 @@ static void dwconv7_ln_launch_t(const float* in, const float* w49, const float* 
   // bit-identical): one block per image, so it needs a batch that fills the CUs; measured against the row-group form
   // (tools/micro/dwconv_stream_probe.hip, profiles/r04_dwconv_stream_probe.txt) it wins where rows are long in pixels -
   // 48 x 32 x 96: 121 vs 129 us, 24 x 16 x 192: 61 vs 66 - and ties or loses at 12 x 8 x 384 / 6 x 4 x 768.
+  // Whole-image form (dwconv7_ln_image_kernel.h: one image per block in LDS, one channel per thread with its taps in
+  // registers, padded taps skipped at compile time, LayerNorm and output on channel quads; bit-identical) for the deep
+  // stages of the tiny encoder, where an image fits a CU's LDS and C or 2 C threads fill every SIMD alike; one block per
+  // image, so like the streaming form it needs a batch that fills the CUs (tools/micro/dwconv_image_probe.hip,
+  // profiles/dwconv_image_probe.txt: 12 x 8 x 384 25.3 vs 37.5 us per launch in the encoder, 6 x 4 x 768 16.5 vs 23.4).
+  // MTGV_DW_IMAGE=0: never, =1: at any batch size (tests).
+  const char* const image_env = getenv("MTGV_DW_IMAGE");  // read per call, like MTGV_DW_ROWS
+  const int image_mode = image_env ? atoi(image_env) : -1;
+  if constexpr (PK == 0)
+  if (rows_on && image_mode != 0 && (N >= 128 || image_mode == 1)) {
+#define DWIMAGE_GO(C_, H_, W_, SPLIT_)                                                                                    \
+  (out_fmt == 1 ? dwconv7_ln_image_launch<C_, H_, W_, SPLIT_, true>(in, w49, bias, ln_w, ln_b, out, N, eps, s)            \
+                : dwconv7_ln_image_launch<C_, H_, W_, SPLIT_, false>(in, w49, bias, ln_w, ln_b, out, N, eps, s))
+    if (C == 384 && H == 12 && W == 8) { DWIMAGE_GO(384, 12, 8, 2); return; }
+    if (C == 768 && H == 6 && W == 4) { DWIMAGE_GO(768, 6, 4, 1); return; }
+#undef DWIMAGE_GO
+  }
   if constexpr (PK == 0)
   if (rows_on && N >= 128) {
 #define DWSTREAM_GO(C_, G_)                                                                                                \
