@@ -306,15 +306,8 @@ MTGV_API int mtgv_op_conv2d(const float* x_dev, const float* w_dev, const float*
     MTGV_CHECK(stride > 0 && kh > 0 && kw > 0 && pad >= 0, ERR_INVALID, "bad conv geometry");
     const int oh = (h + 2 * pad - kh) / stride + 1, ow = (w + 2 * pad - kw) / stride + 1;
     MTGV_CHECK(oh > 0 && ow > 0, ERR_INVALID, "empty conv output");
-    GemmArgs g;
-    g.A = x_dev, g.W = w_dev, g.bias = bias_dev, g.Out = out_dev;
-    g.M = n * oh * ow, g.N = cout, g.K = kh * kw * cin;
-    g.H = h, g.Wd = w, g.c_total = cin, g.Cin = cin;
-    g.KH = kh, g.KW = kw, g.stride = stride, g.pad = pad;
-    g.OH = oh, g.OW = ow, g.OH2 = oh, g.OW2 = ow;
-    g.ldo = cout;
-    g.act = act;
-    gemm_launch(g, (hipStream_t)stream);
+    gemm_launch(conv_args({x_dev, n, h, w, cin, 0, cin, 0}, w_dev, bias_dev, cout, kh, kw, stride, pad, {out_dev, oh, ow, cout, 0, 0}, act),
+                (hipStream_t)stream);
   });
 }
 MTGV_API int mtgv_op_layernorm(const float* x_dev, const float* w_dev, const float* b_dev, float* out_dev, int64_t rows,
@@ -347,14 +340,7 @@ MTGV_API int mtgv_op_block(const float* x_dev, float* out_dev, int32_t n, int32_
     bw.w1 = (float*)w1, bw.b1 = (float*)b1, bw.gamma = (float*)gamma, bw.beta = (float*)beta;
     bw.w2 = (float*)w2, bw.b2 = (float*)b2;
     ScopedWeights reg1(w1, 4 * c, c, (hipStream_t)stream), reg2(w2, c, 4 * c, (hipStream_t)stream);
-    const BlockWsSize z = block_ws_size(n, h, w, c);
-    BlockWs ws;
-    ws.t1 = ws_dev;
-    ws.t2 = ws.t1 + z.t;
-    ws.hid = ws.t2 + z.t;
-    ws.part = ws.hid + z.hid;
-    ws.scale = ws.part + z.part;
-    ws.bfold = ws.scale + z.scale;
+    const BlockWs ws = block_ws_carve(ws_dev, block_ws_size(n, h, w, c));
     run_block(x_dev, out_dev, n, h, w, c, act, bw, ws, (hipStream_t)stream);
   });
 }

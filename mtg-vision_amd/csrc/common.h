@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include <stdio.h>
+#include <stdlib.h>
 #include <string>
 #include <stdexcept>
 
@@ -77,6 +78,39 @@ static inline int current_device() {
   MTGV_CHECK(d >= 0 && d < MTGV_MAX_DEVICES, ERR_RUNTIME, "device ordinal %d outside [0, %d)", d, MTGV_MAX_DEVICES);
   return d;
 }
+
+// Opt the kernel `Kern` in to `need_bytes` of dynamic LDS per block: beyond the default 64 KiB a kernel has to ask, once per
+// device (hipFuncSetAttribute is per device), for a limit of `limit_bytes` >= every size it will be launched with.
+template <auto Kern>
+static inline void lds_opt_in(size_t need_bytes, int limit_bytes) {
+  if (need_bytes <= 64 * 1024) return;
+  static bool done[MTGV_MAX_DEVICES] = {};
+  bool& d = done[current_device()];
+  if (d) return;
+  HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(Kern), hipFuncAttributeMaxDynamicSharedMemorySize, limit_bytes));
+  d = true;
+}
+
+// atoi of the environment variable `name`, `if_unset` when it is not set (on/off and small integer switches)
+static inline int env_int(const char* name, int if_unset) {
+  const char* const e = getenv(name);
+  return e != nullptr ? atoi(e) : if_unset;
+}
+
+// device buffer of floats owned by its holder
+struct DevBuf {
+  float* p = nullptr;
+  size_t n = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
+  void alloc(size_t floats);
+  void ensure(size_t floats) {
+    if (floats > n) alloc(floats);
+  }
+  void release();
+};
 
 static inline int ceil_div(int a, int b) { return (a + b - 1) / b; }
 static inline int64_t ceil_div64(int64_t a, int64_t b) { return (a + b - 1) / b; }

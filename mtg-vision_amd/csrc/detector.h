@@ -2,7 +2,7 @@
 // decode, NMS, mask logits.
 #pragma once
 #include "common.h"
-#include "encoder.h"
+#include "gemm_f32.h"
 #include "mtgv.h"
 
 #include <map>

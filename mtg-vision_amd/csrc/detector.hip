@@ -455,8 +455,7 @@ Detector::~Detector() {
 bool Detector::fork_enabled() const {
   if (count_flops_) return false;
   if (fork_mode_ >= 0) return fork_mode_ != 0;  // mtgv_detector_set_fork
-  const char* e = getenv("MTGV_DET_FORK");  // read per call: tests and tools compare both schedules in one process
-  return e == nullptr || atoi(e) != 0;
+  return env_int("MTGV_DET_FORK", 1) != 0;  // read per call: tests and tools compare both schedules in one process
 }
 
 hipStream_t Detector::fork_after(hipStream_t s, int i) {
@@ -688,18 +687,16 @@ void Detector::finalize() {
   count_flops_ = false;
 }
 
+// the k x k / pad k/2 conv `w` from view `in` to view `out` of n frames (out.H x out.W: the grid the conv enumerates)
+static GemmArgs conv_desc(const ConvW& w, const View& in, const View& out, int stride, int act, int n) {
+  return conv_args({in.p, n, in.H, in.W, in.ct, in.co, in.C, in.fmt}, w.w, w.b, w.cout, w.k, w.k, stride, w.k / 2,
+                   {out.p, out.H, out.W, out.ct, out.co, out.fmt}, act);
+}
+
 void Detector::conv(const ConvW& w, const View& in, const View& out, int stride, int act, const View* res, int n, hipStream_t s) {
   MTGV_CHECK(in.C == w.cin && out.C == w.cout, ERR_RUNTIME, "detector: conv channel mismatch (%d->%d vs %d->%d)", in.C, out.C, w.cin,
              w.cout);
-  GemmArgs g;
-  g.A = in.p, g.W = w.w, g.bias = w.b, g.Out = out.p;
-  g.M = n * out.H * out.W, g.N = w.cout, g.K = w.k * w.k * w.cin;
-  g.H = in.H, g.Wd = in.W, g.c_total = in.ct, g.c_off = in.co, g.Cin = in.C;
-  g.KH = w.k, g.KW = w.k, g.stride = stride, g.pad = w.k / 2;
-  g.OH = out.H, g.OW = out.W, g.OH2 = out.H, g.OW2 = out.W;
-  g.ldo = out.ct, g.o_off = out.co;
-  g.act = act;
-  g.a_fmt = in.fmt, g.out_fmt = out.fmt;
+  GemmArgs g = conv_desc(w, in, out, stride, act, n);
   if (res) g.res = res->p + res->co, g.ldr = res->ct, g.res_fmt = res->fmt;
   if (count_flops_) {
     flops_ += 2.0 * g.M * g.N * g.K;
@@ -712,17 +709,10 @@ void Detector::conv_pair(const ConvW& w1, const View& in, const View& mid, int s
                          hipStream_t s) {
   MTGV_CHECK(in.C == w1.cin && mid.C == w1.cout && w2.cin == w1.cout && w2.k == 1 && out2.C == w2.cout, ERR_RUNTIME,
              "detector: conv pair channel mismatch (%d->%d, %d->%d)", w1.cin, w1.cout, w2.cin, w2.cout);
-  const char* const ce = getenv("MTGV_DET_CHAIN");  // read per call (A/B in one process); 0: two launches
-  if (!count_flops_ && fmt_ == 1 && !(ce != nullptr && atoi(ce) == 0)) {
-    GemmArgs g;
-    g.A = in.p, g.W = w1.w, g.bias = w1.b, g.Out = nullptr;
-    g.M = n * mid.H * mid.W, g.N = w1.cout, g.K = w1.k * w1.k * w1.cin;
-    g.H = in.H, g.Wd = in.W, g.c_total = in.ct, g.c_off = in.co, g.Cin = in.C;
-    g.KH = w1.k, g.KW = w1.k, g.stride = stride, g.pad = w1.k / 2;
-    g.OH = mid.H, g.OW = mid.W, g.OH2 = mid.H, g.OW2 = mid.W;
-    g.ldo = mid.ct, g.o_off = mid.co;
-    g.act = ACT_SILU;
-    g.a_fmt = in.fmt, g.out_fmt = mid.fmt;
+  const bool chain = env_int("MTGV_DET_CHAIN", 1) != 0;  // read per call (A/B in one process); 0: two launches
+  if (!count_flops_ && fmt_ == 1 && chain) {
+    GemmArgs g = conv_desc(w1, in, mid, stride, ACT_SILU, n);
+    g.Out = nullptr;  // only the second layer's output is stored
     g.W2 = w2.w, g.bias2 = w2.b, g.Out2 = out2.p, g.N2 = w2.cout, g.ldo2 = out2.ct, g.o_off2 = out2.co, g.out_fmt2 = out2.fmt, g.act2 = act2;
     if (gemm_sp_chain_ok(g)) {
       gemm_launch(g, s);
@@ -780,31 +770,15 @@ void Detector::proto(const std::string& H, const View& p3, int n, hipStream_t s)
     // SP8 activations (LDS-DMA kernel): one launch with N = 4 * 64 columns whose epilogue scatters column group q to
     // output phase (q / 2, q % 2) - the input is read once instead of four times (round 3: 4 x 27 us at 3.9 TB/s, bound
     // by that re-read).  Same products in the same order per output element: bit-identical to the four launches.
-    const char* const up1 = getenv("MTGV_PROTO_UP1");  // read per call (A/B in one process); 0: the four-launch form
-    const bool one_launch = up1 == nullptr || atoi(up1) != 0;
+    const bool one_launch = env_int("MTGV_PROTO_UP1", 1) != 0;  // read per call (A/B in one process); 0: the four-launch form
     const bool single = one_launch && fmt_ == 1 && !count_flops_ && npr_ % 8 == 0;
-    if (single) {
-      const ConvW& w = proto_up_all_;
-      GemmArgs g;
-      g.A = in.p, g.W = w.w, g.bias = w.b, g.Out = out.p;
-      g.M = n * in.H * in.W, g.N = w.cout, g.K = w.cin;
-      g.H = in.H, g.Wd = in.W, g.c_total = in.ct, g.c_off = 0, g.Cin = w.cin;
-      g.OH = in.H, g.OW = in.W;
-      g.os = 2, g.oy = 0, g.ox = 0, g.os_nq = npr_, g.OH2 = out.H, g.OW2 = out.W;
-      g.ldo = out.ct;
-      g.a_fmt = in.fmt, g.out_fmt = out.fmt;
-      gemm_launch(g, s);
-    }
-    for (int q = 0; q < 4 && !single; ++q) {
-      const ConvW& w = proto_up_[q];
-      GemmArgs g;
-      g.A = in.p, g.W = w.w, g.bias = w.b, g.Out = out.p;
-      g.M = n * in.H * in.W, g.N = w.cout, g.K = w.cin;
-      g.H = in.H, g.Wd = in.W, g.c_total = in.ct, g.c_off = 0, g.Cin = w.cin;
-      g.OH = in.H, g.OW = in.W;
-      g.os = 2, g.oy = q >> 1, g.ox = q & 1, g.OH2 = out.H, g.OW2 = out.W;
-      g.ldo = out.ct;
-      g.a_fmt = in.fmt, g.out_fmt = out.fmt;
+    View grid = out;  // a 1x1 conv over the input grid whose rows scatter to the 2x grid of `out`
+    grid.H = in.H, grid.W = in.W;
+    for (int q = 0; q < (single ? 1 : 4); ++q) {
+      GemmArgs g = conv_desc(single ? proto_up_all_ : proto_up_[q], in, grid, 1, ACT_NONE, n);
+      g.os = 2, g.OH2 = out.H, g.OW2 = out.W;
+      if (single) g.os_nq = npr_;
+      else g.oy = q >> 1, g.ox = q & 1;
       if (count_flops_)
         flops_ += 2.0 * g.M * g.N * g.K;
       else
@@ -916,8 +890,7 @@ void Detector::sppf(const std::string& P, const View& in, const View& spp, const
   const int ch = spp.ct / 4;
   conv(cw_.at(P + ".cv1"), in, spp.slice(0, ch), 1, ACT_SILU, nullptr, n, s);
   const size_t pools_lds = (size_t)spp.H * spp.W * 64;  // two images of (hi, lo) pieces
-  const char* const pools_env = getenv("MTGV_SPPF_POOLS1");  // read per call (A/B in one process); 0: three launches
-  const bool pools1 = pools_env == nullptr || atoi(pools_env) != 0;
+  const bool pools1 = env_int("MTGV_SPPF_POOLS1", 1) != 0;  // read per call (A/B in one process); 0: three launches
   if (!count_flops_ && fmt_ == 1 && pools1 && pools_lds <= 64 * 1024 && ch % 8 == 0) {
     hipLaunchKernelGGL(sppf_pools_sp8_kernel, dim3((unsigned)(n * (ch / 8))), dim3(256), pools_lds, s, spp.p, spp.ct, ch, spp.H, spp.W);
     HIP_OK(hipGetLastError());

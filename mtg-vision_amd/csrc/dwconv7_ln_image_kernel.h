@@ -195,13 +195,8 @@ static void dwconv7_ln_image_launch(const float* in, const float* w49, const flo
                                     int N, float eps, hipStream_t s) {
   constexpr size_t lds = (size_t)H * W * C * sizeof(float);
   static_assert(lds <= 160 * 1024, "the image must fit one CU's LDS");
-  auto kern = dwconv7_ln_image_kernel<C, H, W, SPLIT, SP8>;
-  static bool attr[MTGV_MAX_DEVICES] = {};
-  const int dev = current_device();
-  if (!attr[dev]) {
-    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr[dev] = true;
-  }
+  constexpr auto kern = dwconv7_ln_image_kernel<C, H, W, SPLIT, SP8>;
+  lds_opt_in<kern>(lds, 160 * 1024);
   hipLaunchKernelGGL(kern, dim3((unsigned)N), dim3(C * SPLIT), lds, s, in, w49, bias, ln_w, ln_b, out, eps);
   HIP_OK(hipGetLastError());
 }

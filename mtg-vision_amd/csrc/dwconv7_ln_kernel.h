@@ -1,5 +1,4 @@
-// Depthwise 7x7 + LayerNorm kernel bodies (instantiated in rowops.hip, built like the rest of the library without
-// packed-FP32 VALU instructions; PK is always 0 - it kept a packed build of round 3 apart at link time).
+// Depthwise 7x7 + LayerNorm kernel bodies and the dispatcher that picks one (instantiated in rowops.hip).
 #pragma once
 #include "common.h"
 #include "dwconv7_ln_image_kernel.h"
@@ -16,7 +15,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // per-pixel mean / variance over channels are block-local: partial sums go through LDS in a fixed order
 // (two-pass variance like ln_rows_kernel, deterministic).
 // ---------------------------------------------------------------------------
-template <int TW, bool SP8, int PK, bool WL = false>
+template <int TW, bool SP8>
 __global__ __launch_bounds__(256) void dwconv7_ln_kernel(const float* __restrict__ in, const float* __restrict__ w49,
                                                         const float* __restrict__ bias, const float* __restrict__ ln_w,
                                                         const float* __restrict__ ln_b, float* __restrict__ out, int H, int W,
@@ -26,7 +25,6 @@ __global__ __launch_bounds__(256) void dwconv7_ln_kernel(const float* __restrict
   float* part = sm;                      // [S][c4n][TW]: a pixel's partial sums sit TW floats apart, so the lanes that reduce
                                          // pixels 0..TW-1 read consecutive words (no bank conflicts) in the same c4 order
   float* stat = sm + S * TW * c4n;       // [S][TW][2] mean, rstd
-  const float* wl = w49;                 // WL: the 49 x C tap table staged in LDS (a third of the kernel's L1 traffic otherwise)
   long blk;
   {
     const long nwg = gridDim.x, b = blockIdx.x;
@@ -34,12 +32,6 @@ __global__ __launch_bounds__(256) void dwconv7_ln_kernel(const float* __restrict
     blk = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
   }
   const int tid = threadIdx.x;
-  if (WL) {
-    float* wdst = stat + ((S * TW * 2 + 3) & ~3);
-    for (int i = tid; i < 49 * c4n; i += 256) reinterpret_cast<f32x4*>(wdst)[i] = reinterpret_cast<const f32x4*>(w49)[i];
-    wl = wdst;
-    __syncthreads();
-  }
   const int sl = tid / c4n, c4 = tid % c4n;  // strip slot in block, channel quad
   const long strip = blk * S + sl;
   const bool live = sl < S && strip < total_strips;
@@ -77,7 +69,7 @@ __global__ __launch_bounds__(256) void dwconv7_ln_kernel(const float* __restrict
       }
 #pragma unroll
       for (int kw = 0; kw < 7; ++kw) {
-        const f32x4 wv = *reinterpret_cast<const f32x4*>(wl + (kh * 7 + kw) * C + c);
+        const f32x4 wv = *reinterpret_cast<const f32x4*>(w49 + (kh * 7 + kw) * C + c);
 #pragma unroll
         for (int j = 0; j < TW; ++j) {
           if (DW_DBG == 2) acc[j] += (kw == 0 ? r[j] + r[j + 6] : wv);  // keeps every load alive, 1/7 of the arithmetic
@@ -144,7 +136,7 @@ __global__ __launch_bounds__(256) void dwconv7_ln_rows_kernel(const float* __res
   const int c4n = C >> 2;
   float* part = sm;                      // [S][c4n][P]
   float* stat = sm + S * P * c4n;        // [S][P][2] mean, rstd
-  const float* wl = w49;
+  const float* wl = w49;                 // WL: the 49 x C tap table staged in LDS (a third of the kernel's L1 traffic otherwise)
   const int tid = threadIdx.x;
   if (WL) {
     float* wdst = stat + ((S * P * 2 + 3) & ~3);
@@ -267,14 +259,7 @@ static void dwconv7_ln_rows_launch(const float* in, const float* w49, const floa
   const long total_strips = (long)N * nhg * nstrips;
   const unsigned grid = (unsigned)((total_strips + S - 1) / S);
   const size_t lds = (size_t)(S * TH * TW * (c4n + 2) + 4 + (WL ? 49 * C : 0)) * sizeof(float);
-  if (lds > 65536) {  // (not reached by the library's own launches: C <= 96)
-    static bool attr[MTGV_MAX_DEVICES] = {};
-    const int dev = current_device();
-    if (!attr[dev]) {
-      HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(&dwconv7_ln_rows_kernel<TW, TH, SP8, WL>), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-      attr[dev] = true;
-    }
-  }
+  lds_opt_in<dwconv7_ln_rows_kernel<TW, TH, SP8, WL>>(lds, 160 * 1024);  // (not reached by the library's own launches: C <= 96)
   // S * c4n threads rounded up to a wave: at C = 384 / 640 / 768 a fourth wave would hold no strip and only sit at the barriers
   const unsigned threads = (unsigned)((S * c4n + 63) / 64 * 64);
   hipLaunchKernelGGL((dwconv7_ln_rows_kernel<TW, TH, SP8, WL>), dim3(grid), dim3(threads), lds, s, in, w49, bias, ln_w, ln_b, out, H, W, C,
@@ -282,15 +267,14 @@ static void dwconv7_ln_rows_launch(const float* in, const float* w49, const floa
   HIP_OK(hipGetLastError());
 }
 
-template <int PK>
-static void dwconv7_ln_launch_t(const float* in, const float* w49, const float* bias, const float* ln_w, const float* ln_b,
-                                float* out, int N, int H, int W, int C, float eps, hipStream_t s, int out_fmt) {
+template <bool SP8>
+static void dwconv7_ln_launch_fmt(const float* in, const float* w49, const float* bias, const float* ln_w, const float* ln_b,
+                                  float* out, int N, int H, int W, int C, float eps, hipStream_t s) {
   // Row-group forms (tools/micro/dwconv_rows_probe.hip, profiles/r03_dwconv_rows_probe.txt; all bit-identical to the
   // single-row kernel): 4-pixel strips x 3 rows with the tap table in LDS while table + partial sums fit the default
   // 64 KB window (C <= 192: 121.5 vs 144-155 us at 256 x 48 x 32 x 96, 60.9 vs 66.7 at 24 x 16 x 192), else 3 rows of the
   // widest strip (34.7 vs 38.6 us at 12 x 8 x 384, 20.3 vs 24.7 at 6 x 4 x 768).  MTGV_DW_ROWS=0: single-row kernel.
-  const char* const rows_env = getenv("MTGV_DW_ROWS");  // read per call: tests compare the forms inside one process
-  const bool rows_on = !(rows_env && atoi(rows_env) == 0);
+  const bool rows_on = env_int("MTGV_DW_ROWS", 1) != 0;  // read per call: tests compare the forms inside one process
   // Row-streaming form (dwconv7_ln_stream_kernel.h: LDS-DMA row ring, one channel per thread, taps in registers;
   // bit-identical): one block per image, so it needs a batch that fills the CUs; measured against the row-group form
   // (tools/micro/dwconv_stream_probe.hip, profiles/r04_dwconv_stream_probe.txt) it wins where rows are long in pixels -
@@ -301,37 +285,21 @@ static void dwconv7_ln_launch_t(const float* in, const float* w49, const float* 
   // image, so like the streaming form it needs a batch that fills the CUs (tools/micro/dwconv_image_probe.hip,
   // profiles/dwconv_image_probe.txt: 12 x 8 x 384 25.3 vs 37.5 us per launch in the encoder, 6 x 4 x 768 16.5 vs 23.4).
   // MTGV_DW_IMAGE=0: never, =1: at any batch size (tests).
-  const char* const image_env = getenv("MTGV_DW_IMAGE");  // read per call, like MTGV_DW_ROWS
-  const int image_mode = image_env ? atoi(image_env) : -1;
-  if constexpr (PK == 0)
+  const int image_mode = env_int("MTGV_DW_IMAGE", -1);  // read per call, like MTGV_DW_ROWS
   if (rows_on && image_mode != 0 && (N >= 128 || image_mode == 1)) {
-#define DWIMAGE_GO(C_, H_, W_, SPLIT_)                                                                                    \
-  (out_fmt == 1 ? dwconv7_ln_image_launch<C_, H_, W_, SPLIT_, true>(in, w49, bias, ln_w, ln_b, out, N, eps, s)            \
-                : dwconv7_ln_image_launch<C_, H_, W_, SPLIT_, false>(in, w49, bias, ln_w, ln_b, out, N, eps, s))
-    if (C == 384 && H == 12 && W == 8) { DWIMAGE_GO(384, 12, 8, 2); return; }
-    if (C == 768 && H == 6 && W == 4) { DWIMAGE_GO(768, 6, 4, 1); return; }
-#undef DWIMAGE_GO
+    if (C == 384 && H == 12 && W == 8) return dwconv7_ln_image_launch<384, 12, 8, 2, SP8>(in, w49, bias, ln_w, ln_b, out, N, eps, s);
+    if (C == 768 && H == 6 && W == 4) return dwconv7_ln_image_launch<768, 6, 4, 1, SP8>(in, w49, bias, ln_w, ln_b, out, N, eps, s);
   }
-  if constexpr (PK == 0)
   if (rows_on && N >= 128) {
-#define DWSTREAM_GO(C_, G_)                                                                                                \
-  (out_fmt == 1 ? dwconv7_ln_stream_launch<C_, G_, 4, 3, true>(in, w49, bias, ln_w, ln_b, out, N, H, 1, eps, s)            \
-                : dwconv7_ln_stream_launch<C_, G_, 4, 3, false>(in, w49, bias, ln_w, ln_b, out, N, H, 1, eps, s))
-    if (C == 96 && W == 32) { DWSTREAM_GO(96, 8); return; }
-    if (C == 192 && W == 16) { DWSTREAM_GO(192, 4); return; }
-#undef DWSTREAM_GO
+    if (C == 96 && W == 32) return dwconv7_ln_stream_launch<96, 8, 4, 3, SP8>(in, w49, bias, ln_w, ln_b, out, N, H, 1, eps, s);
+    if (C == 192 && W == 16) return dwconv7_ln_stream_launch<192, 4, 4, 3, SP8>(in, w49, bias, ln_w, ln_b, out, N, H, 1, eps, s);
   }
-  if constexpr (PK == 0)  // the rows kernel is not keyed by PK: only the TU built without packed FP32 may instantiate it
   if (rows_on && W >= 4) {
     const int c4n_ = C / 4, S_ = 256 / c4n_;
     const bool table = (size_t)(S_ * 12 * (c4n_ + 2) + 4 + 49 * C) * sizeof(float) <= 65536;
-#define DWROWS_GO(TW_, WL_)                                                                                          \
-  (out_fmt == 1 ? dwconv7_ln_rows_launch<TW_, 3, true, WL_>(in, w49, bias, ln_w, ln_b, out, N, H, W, C, eps, s)        \
-                : dwconv7_ln_rows_launch<TW_, 3, false, WL_>(in, w49, bias, ln_w, ln_b, out, N, H, W, C, eps, s))
-    if (table) DWROWS_GO(4, true);
-    else if (W >= 8) DWROWS_GO(8, false);
-    else DWROWS_GO(4, false);
-#undef DWROWS_GO
+    if (table) dwconv7_ln_rows_launch<4, 3, SP8, true>(in, w49, bias, ln_w, ln_b, out, N, H, W, C, eps, s);
+    else if (W >= 8) dwconv7_ln_rows_launch<8, 3, SP8, false>(in, w49, bias, ln_w, ln_b, out, N, H, W, C, eps, s);
+    else dwconv7_ln_rows_launch<4, 3, SP8, false>(in, w49, bias, ln_w, ln_b, out, N, H, W, C, eps, s);
     return;
   }
   const int tw = W >= 8 ? 8 : (W >= 4 ? 4 : 2);
@@ -341,19 +309,16 @@ static void dwconv7_ln_launch_t(const float* in, const float* w49, const float* 
   const long total_strips = (long)N * H * nstrips;
   const unsigned grid = (unsigned)((total_strips + S - 1) / S);
   const size_t lds = (size_t)(S * tw * c4n + S * tw * 2) * sizeof(float);
-#define DWLN_GO(TW_, SP_) \
-  hipLaunchKernelGGL((dwconv7_ln_kernel<TW_, SP_, PK>), dim3(grid), dim3(256), lds, s, in, w49, bias, ln_w, ln_b, out, H, W, C, nstrips, total_strips, S, eps)
-  if (out_fmt == 1) {
-    if (tw == 8) DWLN_GO(8, true);
-    else if (tw == 4) DWLN_GO(4, true);
-    else DWLN_GO(2, true);
-  } else {
-    if (tw == 8) DWLN_GO(8, false);
-    else if (tw == 4) DWLN_GO(4, false);
-    else DWLN_GO(2, false);
-  }
-#undef DWLN_GO
+  auto kern = tw == 8 ? dwconv7_ln_kernel<8, SP8> : (tw == 4 ? dwconv7_ln_kernel<4, SP8> : dwconv7_ln_kernel<2, SP8>);
+  hipLaunchKernelGGL(kern, dim3(grid), dim3(256), lds, s, in, w49, bias, ln_w, ln_b, out, H, W, C, nstrips, total_strips, S, eps);
   HIP_OK(hipGetLastError());
+}
+
+// picks the kernel form for the shape and launches it; out_fmt 0: f32 rows, 1: SP8 rows
+static void dwconv7_ln_dispatch(const float* in, const float* w49, const float* bias, const float* ln_w, const float* ln_b,
+                                float* out, int N, int H, int W, int C, float eps, hipStream_t s, int out_fmt) {
+  out_fmt == 1 ? dwconv7_ln_launch_fmt<true>(in, w49, bias, ln_w, ln_b, out, N, H, W, C, eps, s)
+               : dwconv7_ln_launch_fmt<false>(in, w49, bias, ln_w, ln_b, out, N, H, W, C, eps, s);
 }
 
 }  // namespace mtgv

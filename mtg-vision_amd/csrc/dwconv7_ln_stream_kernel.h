@@ -212,13 +212,8 @@ static void dwconv7_ln_stream_launch(const float* in, const float* w49, const fl
                                      int N, int H, int bands, float eps, hipStream_t s) {
   constexpr size_t lds = dwconv7_ln_stream_lds<C, G, TW, TH>();
   static_assert(lds <= 160 * 1024, "the row ring must fit one CU's LDS");
-  auto kern = dwconv7_ln_stream_kernel<C, G, TW, TH, SP8>;
-  static bool attr[MTGV_MAX_DEVICES] = {};
-  const int dev = current_device();
-  if (!attr[dev]) {
-    HIP_OK(hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, 160 * 1024));
-    attr[dev] = true;
-  }
+  constexpr auto kern = dwconv7_ln_stream_kernel<C, G, TW, TH, SP8>;
+  lds_opt_in<kern>(lds, 160 * 1024);
   const int rows_per_band = ceil_div(ceil_div(H, bands), TH) * TH;
   hipLaunchKernelGGL(kern, dim3((unsigned)(N * bands)), dim3(C * G), lds, s, in, w49, bias, ln_w, ln_b, out, H, bands, rows_per_band, eps);
   HIP_OK(hipGetLastError());

@@ -11,20 +11,6 @@
 
 namespace mtgv {
 
-struct DevBuf {
-  float* p = nullptr;
-  size_t n = 0;
-  DevBuf() = default;
-  DevBuf(const DevBuf&) = delete;
-  DevBuf& operator=(const DevBuf&) = delete;
-  ~DevBuf() { release(); }
-  void alloc(size_t floats);
-  void ensure(size_t floats) {
-    if (floats > n) alloc(floats);
-  }
-  void release();
-};
-
 // weights of one Block (convnextv2.py:198-207), device pointers
 struct BlockW {
   float *dw_w49 = nullptr, *dw_b = nullptr, *ln_w = nullptr, *ln_b = nullptr;
@@ -43,6 +29,7 @@ struct BlockWsSize {
   size_t total() const { return 2 * t + hid + part + scale + bfold; }
 };
 BlockWsSize block_ws_size(int n, int h, int w, int c);
+BlockWs block_ws_carve(float* base, const BlockWsSize& z);  // the six buffers in a workspace of z.total() floats
 // Block.forward on NHWC x -> out (may not alias x)
 // The LayerNorm over C that follows a stage's last block (the downsample's): when the block runs fused (mlp_fused_kernel.h) its
 // output pass applies it in the epilogue and writes the normalised rows in SP8 form to `out_sp8` (which may be the block's own
@@ -55,9 +42,6 @@ struct BlockLn {
 };
 bool run_block(const float* x, float* out, int n, int h, int w, int c, int act, const BlockW& bw, const BlockWs& ws,
                hipStream_t s, const BlockLn* ln = nullptr);
-
-GemmArgs linear_args(const float* A, int lda, const float* W, const float* bias, float* Out, int ldo, int M, int N, int K,
-                     int act);
 
 enum Repack { R_NONE = 0, R_OIHW_OHWI = 1, R_DW49 = 2, R_HEADPERM = 3 };
 

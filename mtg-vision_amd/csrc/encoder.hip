@@ -8,7 +8,6 @@
 //   GRN finalize               -> scale[n][4C]  grn_finalize_kernel
 //   (hid*scale + beta) @ W2^T + b2 + residual -> out      gemm_f32 (A prologue + epilogue)
 #include "encoder.h"
-#include <stdlib.h>
 #include "rowops.h"
 #include "gemm_sp.h"
 #include "mlp_fused.h"
@@ -16,18 +15,6 @@
 #include <string.h>
 
 namespace mtgv {
-
-void DevBuf::alloc(size_t floats) {
-  release();
-  if (floats == 0) return;
-  HIP_OK(hipMalloc((void**)&p, floats * sizeof(float)));
-  n = floats;
-}
-void DevBuf::release() {
-  if (p) (void)hipFree(p);
-  p = nullptr;
-  n = 0;
-}
 
 // ---------------------------------------------------------------------------
 // parameter store
@@ -109,21 +96,6 @@ int ParamStore::missing() const {
 // ---------------------------------------------------------------------------
 // one block
 // ---------------------------------------------------------------------------
-GemmArgs linear_args(const float* A, int lda, const float* W, const float* bias, float* Out, int ldo, int M, int N, int K,
-                     int act) {
-  GemmArgs a;
-  a.A = A;
-  a.W = W;
-  a.Out = Out;
-  a.bias = bias;
-  a.M = M, a.N = N, a.K = K;
-  a.c_total = lda;
-  a.Cin = K;
-  a.ldo = ldo;
-  a.act = act;
-  return a;
-}
-
 BlockWsSize block_ws_size(int n, int h, int w, int c) {
   BlockWsSize z;
   const size_t M = (size_t)n * h * w;
@@ -133,6 +105,17 @@ BlockWsSize block_ws_size(int n, int h, int w, int c) {
   z.scale = (size_t)n * 4 * c;
   z.bfold = (size_t)c;
   return z;
+}
+
+BlockWs block_ws_carve(float* base, const BlockWsSize& z) {
+  BlockWs ws;
+  ws.t1 = base;
+  ws.t2 = ws.t1 + z.t;
+  ws.hid = ws.t2 + z.t;
+  ws.part = ws.hid + z.hid;
+  ws.scale = ws.part + z.part;
+  ws.bfold = ws.scale + z.scale;
+  return ws;
 }
 
 bool run_block(const float* x, float* out, int n, int h, int w, int c, int act, const BlockW& bw, const BlockWs& ws,
@@ -484,24 +467,15 @@ void Encoder::body(int n, float* z_out, hipStream_t s) {
 
   // stem: rows of 12 floats (4 pixels x RGB) are the "pixels" of a (4 x 1) conv, stride (4, 1)
   {
-    GemmArgs g;
-    g.A = x0_.p;
-    g.W = stem_w_;
-    g.bias = stem_b_;
-    g.Out = alt;
-    g.M = n * sh_[0] * sw_[0], g.N = d[0], g.K = 48;
-    g.H = H, g.Wd = W / 4, g.c_total = 12, g.Cin = 12;
-    g.KH = 4, g.KW = 1, g.stride = 4, g.stride_w = 1, g.pad = 0;
-    g.OH = sh_[0], g.OW = sw_[0], g.OH2 = sh_[0], g.OW2 = sw_[0];
-    g.ldo = d[0];
+    GemmArgs g = conv_args({x0_.p, n, H, W / 4, 12, 0, 12, 0}, stem_w_, stem_b_, d[0], 4, 1, 4, 0, {alt, sh_[0], sw_[0], d[0], 0, 0}, ACT_NONE);
+    g.stride_w = 1;
     const bool fuse_ln = gemm_ln_fusable(g);  // the stem's LayerNorm in the conv's epilogue: its output is written once
     if (fuse_ln) g.Out = cur, g.ln_w = stem_ln_w_, g.ln_b = stem_ln_b_, g.ln_eps = 1e-6f;
     gemm_launch(g, s);
     if (!fuse_ln) ln_rows_launch(alt, d[0], 0, cur, d[0], 0, stem_ln_w_, stem_ln_b_, g.M, d[0], 1e-6f, s);
   }
 
-  const char* const ln_env = getenv("MTGV_LN_FUSE");  // read per call: a test compares both forms in one process
-  const bool ln_fuse = ln_env == nullptr || atoi(ln_env) != 0;
+  const bool ln_fuse = env_int("MTGV_LN_FUSE", 1) != 0;  // read per call: a test compares both forms in one process
   bool ln_done = false;
   for (int st = 0; st < 4; ++st) {
     const int h = sh_[st], w = sw_[st], c = d[st];
@@ -518,27 +492,9 @@ void Encoder::body(int n, float* z_out, hipStream_t s) {
         ln_rows_launch(cur, cp, 0, alt, cp, 0, ds_ln_w_[st], ds_ln_b_[st], (long)n * hp * wp, cp, 1e-6f, s, fmt);
       }
       ln_done = false;
-      GemmArgs g;
-      g.a_fmt = fmt;
-      g.A = alt;
-      g.W = ds_w_[st];
-      g.bias = ds_b_[st];
-      g.Out = cur;
-      g.M = n * h * w, g.N = c, g.K = 4 * cp;
-      g.H = hp, g.Wd = wp, g.c_total = cp, g.Cin = cp;
-      g.KH = 2, g.KW = 2, g.stride = 2, g.pad = 0;
-      g.OH = h, g.OW = w, g.OH2 = h, g.OW2 = w;
-      g.ldo = c;
-      gemm_launch(g, s);
+      gemm_launch(conv_args({alt, n, hp, wp, cp, 0, cp, fmt}, ds_w_[st], ds_b_[st], c, 2, 2, 2, 0, {cur, h, w, c, 0, 0}, ACT_NONE), s);
     }
-    const BlockWsSize z = block_ws_size(n, h, w, c);
-    BlockWs ws;
-    ws.t1 = ws_.p;
-    ws.t2 = ws.t1 + z.t;
-    ws.hid = ws.t2 + z.t;
-    ws.part = ws.hid + z.hid;
-    ws.scale = ws.part + z.part;
-    ws.bfold = ws.scale + z.scale;
+    const BlockWs ws = block_ws_carve(ws_.p, block_ws_size(n, h, w, c));
     for (size_t j = 0; j < blocks_[st].size(); ++j) {
       // the stage's last block hands the downsample's LayerNorm to its fused output pass where it can (MTGV_LN_FUSE=0: off):
       // the normalised rows replace the block's input in place and the block's f32 output is never written

@@ -94,6 +94,24 @@ inline bool is_conv(const GemmArgs& a) { return !(a.KH == 1 && a.KW == 1 && a.st
 // output row m is scattered to another grid (orow != m)
 inline bool is_remap(const GemmArgs& a) { return !(a.os == 1 && a.oy == 0 && a.ox == 0 && a.OH2 == a.OH && a.OW2 == a.OW); }
 
+// The two ways a launch is described; a caller then sets only what is special about it (residual, GRN, chained layer ...).
+// Dense layer: Out[M][ldo] = act(A[M][lda] . W[N][K]^T + bias)
+GemmArgs linear_args(const float* A, int lda, const float* W, const float* bias, float* Out, int ldo, int M, int N, int K,
+                     int act);
+// Convolution over channels [co, co + c) of an NHWC tensor with ct floats per pixel, into channels [co, co + cout) of another
+struct ConvIn {
+  const float* p;
+  int n, h, w, ct, co, c, fmt;  // images, spatial size, floats per pixel, first channel, channels, format (GemmArgs::a_fmt)
+};
+struct ConvOut {
+  float* p;
+  int h, w, ct, co, fmt;        // output grid, floats per pixel, first channel, format (GemmArgs::out_fmt)
+};
+// Sets every geometry field (M, K, OH2 / OW2 included); W is [cout][kh][kw][in.c].  The stem's stride_w, the scatter of
+// a ConvTranspose (os, oy, ox, os_nq, OH2, OW2: out.h x out.w is then the grid that m enumerates) are the caller's.
+GemmArgs conv_args(const ConvIn& in, const float* W, const float* bias, int cout, int kh, int kw, int stride, int pad,
+                   const ConvOut& out, int act);
+
 // Runs the launch `a` describes.  The kernel and its tile follow from the arguments alone: the LDS-DMA kernel
 // (gemm_sp.h) when it takes the launch, else the convert-on-load kernel (gemm_kernel.h) with the tile of its cost model
 // (MTGV_GEMM_TILE=tm,tn,bk forces one; top-k launches have a fixed tile).

@@ -19,6 +19,37 @@
 
 namespace mtgv {
 
+GemmArgs linear_args(const float* A, int lda, const float* W, const float* bias, float* Out, int ldo, int M, int N, int K,
+                     int act) {
+  GemmArgs a;
+  a.A = A;
+  a.W = W;
+  a.Out = Out;
+  a.bias = bias;
+  a.M = M, a.N = N, a.K = K;
+  a.c_total = lda;
+  a.Cin = K;
+  a.ldo = ldo;
+  a.act = act;
+  return a;
+}
+
+GemmArgs conv_args(const ConvIn& in, const float* W, const float* bias, int cout, int kh, int kw, int stride, int pad,
+                   const ConvOut& out, int act) {
+  GemmArgs a;
+  a.A = in.p, a.a_fmt = in.fmt;
+  a.W = W;
+  a.bias = bias;
+  a.Out = out.p, a.out_fmt = out.fmt;
+  a.M = in.n * out.h * out.w, a.N = cout, a.K = kh * kw * in.c;
+  a.H = in.h, a.Wd = in.w, a.c_total = in.ct, a.c_off = in.co, a.Cin = in.c;
+  a.KH = kh, a.KW = kw, a.stride = stride, a.pad = pad;
+  a.OH = out.h, a.OW = out.w, a.OH2 = out.h, a.OW2 = out.w;
+  a.ldo = out.ct, a.o_off = out.co;
+  a.act = act;
+  return a;
+}
+
 bool gemm_dispatch_f32(const GemmDev& g, const GemmPlan& pl, bool conv, bool apro, int grid, hipStream_t s) {
   return gemm_dispatch<0>(g, pl, conv, apro, grid, s);
 }

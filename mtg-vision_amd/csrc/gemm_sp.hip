@@ -178,16 +178,13 @@ constexpr int kNumCfg = sizeof(kCfg) / sizeof(kCfg[0]);
 }  // namespace
 
 bool window_conv_on() {
-  static const bool on = [] { const char* e = getenv("MTGV_SP_WINDOW"); return e == nullptr || atoi(e) != 0; }();
+  static const bool on = env_int("MTGV_SP_WINDOW", 1) != 0;
   return on;
 }
 
 // 3x3 / stride 1 / pad 1 convs whose channels come in slices of 32: stage the tile's input window once per slice
 // instead of gathering every tap from L2 (1.65 - 2.2x fewer LDS fill bytes), while two blocks still fit a CU
-static size_t window_bytes(const SpCfg& k, int Wd) {
-  const int rpp = 1024 / k.rb();
-  return (size_t)((k.bm() + 2 * Wd + 2 + rpp - 1) / rpp * rpp) * k.rb();
-}
+static size_t window_bytes(const SpCfg& k, int Wd) { return sp_window_bytes(k.bm(), k.rb(), Wd); }
 
 bool window_conv_fits(const GemmArgs& a, const SpPlan& pl) {
   const SpCfg& k = kCfg[pl.cfg];
@@ -317,7 +314,7 @@ namespace {
 struct StampRec { int M, N, K, cfg, amode, act, tiles; long* buf; };
 std::vector<StampRec> g_stamps;
 bool stamps_on() {
-  static const bool on = [] { const char* e = getenv("MTGV_SP_STAMPS"); return e != nullptr && atoi(e) != 0; }();
+  static const bool on = env_int("MTGV_SP_STAMPS", 0) != 0;
   return on;
 }
 }  // namespace

@@ -22,19 +22,13 @@ void sp_launch_nst(const SpDev& g, hipStream_t s) {
   // chained 1x1 (EPI 32): after the main loop the block holds one accumulator column block and TN A2 stages per wave and W2
   constexpr size_t chain_lds = (size_t)SP_WM * SP_WN * 4096 * (1 + SP_TN) + (size_t)SP_TN * 96 * 128;
   if (AMODE == 5) {  // window of BM + 2 W + 2 pixels x (64 KS) B in front of the weight ring; the epilogue stages 32 rows per wave
-    constexpr int RB = 64 * SP_KS, RPP = 1024 / RB;
-    const size_t win = (size_t)((BM + 2 * g.Wd + 2 + RPP - 1) / RPP * RPP) * RB;
+    const size_t win = sp_window_bytes(BM, 64 * SP_KS, g.Wd);
     const size_t stage = (size_t)SP_WM * SP_WN * 32 * 128 * SP_TN;
     lds = win + ring > stage ? win + ring : stage;
   }
   if (EPI == 32 && lds < chain_lds) lds = chain_lds;
-  static bool attr_done_dev[MTGV_MAX_DEVICES] = {};  // hipFuncSetAttribute is per device
-  bool& attr_done = attr_done_dev[current_device()];
-  auto kern = gemm_sp_kernel<SP_WM, SP_WN, SP_TM, SP_TN, SP_KS, NST, AMODE, ACT, EPI>;
-  if (!attr_done) {
-    HIP_OK(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (AMODE == 5 || EPI == 32) ? 160 * 1024 : (int)lds));
-    attr_done = true;
-  }
+  constexpr auto kern = gemm_sp_kernel<SP_WM, SP_WN, SP_TM, SP_TN, SP_KS, NST, AMODE, ACT, EPI>;
+  lds_opt_in<kern>(lds, (AMODE == 5 || EPI == 32) ? 160 * 1024 : (int)lds);
   hipLaunchKernelGGL(kern, dim3((unsigned)(g.tiles_m * g.tiles_n)), dim3(64 * SP_WM * SP_WN), lds, s, g);
 }
 
@@ -44,8 +38,8 @@ void sp_launch_one(const SpDev& g, hipStream_t s) {
     // window conv: a four-deep weight ring (three taps ahead) for launches of at most one round of tiles - there a tile's
     // latency is the launch's duration (12800-row layers -15..-25 %); with several rounds the blocks per CU matter more
     // (the deeper ring costs one: 204800 x 32 layers +12 %) and the two-deep ring stays
-    constexpr int BM = 32 * SP_TM * SP_WM, BN = 32 * SP_TN * SP_WN, RB = 64 * SP_KS, RPP = 1024 / RB;
-    const size_t win = (size_t)((BM + 2 * g.Wd + 2 + RPP - 1) / RPP * RPP) * RB;
+    constexpr int BM = 32 * SP_TM * SP_WM, BN = 32 * SP_TN * SP_WN, RB = 64 * SP_KS;
+    const size_t win = sp_window_bytes(BM, RB, g.Wd);
     if ((long)g.tiles_m * g.tiles_n <= 512 && win + (size_t)4 * BN * RB <= 80 * 1024) {
       sp_launch_nst<AMODE, ACT, EPI, 4>(g, s);
       return;

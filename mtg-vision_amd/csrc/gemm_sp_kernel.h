@@ -58,6 +58,14 @@ __device__ __forceinline__ spf16 sp_mfma(sp_h8 b, sp_h8 a, spf16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_f16(b, a, c, 0, 0, 0);
 }
 
+// LDS bytes of the window conv's staged input window (host side; the kernel's win_px is the same count in pixels): the
+// tile's bm output pixels plus a row and a pixel on either side, in whole 1 KB pieces of rb bytes per staged pixel.  The
+// planner decides "fits" and the launcher sizes the allocation from this one function.
+constexpr size_t sp_window_bytes(int bm, int rb, int Wd) {
+  const int rpp = 1024 / rb;
+  return (size_t)((bm + 2 * Wd + 2 + rpp - 1) / rpp * rpp) * rb;
+}
+
 struct SpDev {
   float* cand_s = nullptr;      // EPI 16 (top-k): per (row, column tile, wave column) the k best (score, column) pairs
   int* cand_i = nullptr;

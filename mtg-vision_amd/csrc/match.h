@@ -1,7 +1,7 @@
 // Card bank: device-resident L2-normalised vectors + exact cosine top-k.
 #pragma once
 #include "common.h"
-#include "encoder.h"
+#include "gemm_f32.h"
 
 namespace mtgv {
 

@@ -372,8 +372,7 @@ int64_t Bank::prepass_fallbacks() const {
 }
 
 bool Bank::prepass_ok(int b, int k) const {
-  const char* e = getenv("MTGV_MATCH_PREPASS");  // read per call: tests and tools compare the two paths in one process
-  const bool on = e == nullptr || atoi(e) != 0;
+  const bool on = env_int("MTGV_MATCH_PREPASS", 1) != 0;  // read per call: tests and tools compare the two paths in one process
   return on && gemm_sp_active() && b >= 128 && k <= 4 && dim_ % 64 == 0 && size_ >= 4096 && hi_.p != nullptr;
 }
 

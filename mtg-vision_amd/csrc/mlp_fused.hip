@@ -17,14 +17,7 @@ void launch_pass(const MlpDev& g, hipStream_t s) {
   constexpr int NV = PASS == 2 ? 4 : 2;
   constexpr size_t lds = (size_t)((NV * 4 * C * 4 + (PASS == 2 ? 2 * C * 4 : 0) + 1023) / 1024) * 1024 + (size_t)(PASS == 2 ? 6 : 3) * KB * 4096;
   static_assert(lds <= 80 * 1024, "two blocks per CU");
-  if (lds > 64 * 1024) {  // beyond the default dynamic-LDS limit: opt in once per device
-    static bool attr_done_dev[MTGV_MAX_DEVICES] = {};
-    bool& attr_done = attr_done_dev[current_device()];
-    if (!attr_done) {
-      HIP_OK(hipFuncSetAttribute((const void*)mlp_fused_kernel<C16, ACT, PASS>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
-      attr_done = true;
-    }
-  }
+  lds_opt_in<mlp_fused_kernel<C16, ACT, PASS>>(lds, (int)lds);
   hipLaunchKernelGGL((mlp_fused_kernel<C16, ACT, PASS>), dim3((unsigned)ceil_div(g.M, 128)), dim3(256), lds, s, g);
   HIP_OK(hipGetLastError());
 }

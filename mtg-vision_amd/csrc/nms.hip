@@ -220,12 +220,7 @@ void nms_launch(const float* pred, int n, int nc, int nm, int na, float conf, fl
   const size_t lds = (size_t)cap * sizeof(unsigned long long);
   MTGV_CHECK(lds <= 150 * 1024, ERR_INVALID, "nms: %d anchors exceed the LDS sort capacity", na);
   MTGV_CHECK(ws != nullptr && ws_bytes >= nms_workspace_bytes(n, na), ERR_INVALID, "nms: workspace too small");
-  static bool attr_done_dev[MTGV_MAX_DEVICES] = {};  // hipFuncSetAttribute is per device
-  bool& attr_done = attr_done_dev[current_device()];
-  if (!attr_done) {
-    HIP_OK(hipFuncSetAttribute((const void*)nms_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024));
-    attr_done = true;
-  }
+  lds_opt_in<nms_kernel>(lds, 150 * 1024);
   hipLaunchKernelGGL(nms_kernel, dim3(n), dim3(NMS_THREADS), lds, s, pred, nc, nm, na, cap, conf, iou, max_det, max_wh, n_det,
                      boxes, conf_out, cls_out, keep_idx, coef_out, ws);
   HIP_OK(hipGetLastError());

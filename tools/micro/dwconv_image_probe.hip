@@ -50,12 +50,12 @@ static int shape(int N, bool zeros) {
   for (int fmt = 1; fmt >= 0; --fmt) {
     setenv("MTGV_DW_IMAGE", "0", 1);
     setenv("MTGV_DW_ROWS", "0", 1);
-    auto single = [&] { dwconv7_ln_launch_t<0>(in, w49, b, lw, lb, ref, N, H, W, C, 1e-6f, nullptr, fmt); };
+    auto single = [&] { dwconv7_ln_dispatch(in, w49, b, lw, lb, ref, N, H, W, C, 1e-6f, nullptr, fmt); };
     const float t_single = time_us(single);
     hipDeviceSynchronize();
     hipMemcpy(hr.data(), ref, n * 4, hipMemcpyDeviceToHost);
     setenv("MTGV_DW_ROWS", "1", 1);
-    auto rows = [&] { dwconv7_ln_launch_t<0>(in, w49, b, lw, lb, out, N, H, W, C, 1e-6f, nullptr, fmt); };
+    auto rows = [&] { dwconv7_ln_dispatch(in, w49, b, lw, lb, out, N, H, W, C, 1e-6f, nullptr, fmt); };
     printf("%dx%dx%dx%d %s%s  single row: %.1f us   row groups: %.1f us\n", N, H, W, C, fmt ? "SP8" : "f32", zeros ? " zeros" : "", t_single, time_us(rows));
     hipMemset(out, 0xff, n * 4);
     auto image = [&] {

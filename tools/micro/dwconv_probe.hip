@@ -18,9 +18,9 @@ int main() {
     hipMemset(in, 0x3c, n * 4), hipMemset(w49, 0x3c, 49 * C * 4), hipMemset(b, 0, C * 4), hipMemset(lw, 0x3c, C * 4), hipMemset(lb, 0, C * 4);
     hipEvent_t e0, e1;
     hipEventCreate(&e0), hipEventCreate(&e1);
-    for (int it = 0; it < 3; ++it) dwconv7_ln_launch_t<0>(in, w49, b, lw, lb, out, N, H, W, C, 1e-6f, nullptr, 1);
+    for (int it = 0; it < 3; ++it) dwconv7_ln_dispatch(in, w49, b, lw, lb, out, N, H, W, C, 1e-6f, nullptr, 1);
     hipEventRecord(e0);
-    for (int it = 0; it < 20; ++it) dwconv7_ln_launch_t<0>(in, w49, b, lw, lb, out, N, H, W, C, 1e-6f, nullptr, 1);
+    for (int it = 0; it < 20; ++it) dwconv7_ln_dispatch(in, w49, b, lw, lb, out, N, H, W, C, 1e-6f, nullptr, 1);
     hipEventRecord(e1);
     hipEventSynchronize(e1);
     float ms;

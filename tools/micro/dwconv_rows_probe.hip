@@ -42,7 +42,7 @@ int main() {
       for (size_t i = 0; i < m; ++i) h[i] = (rand() % 2001 - 1000) * 1e-3f;
       hipMemcpy(p, h.data(), m * 4, hipMemcpyHostToDevice);
     }
-    auto base = [&] { dwconv7_ln_launch_t<0>(in, w49, b, lw, lb, ref, N, H, W, C, 1e-6f, nullptr, 1); };
+    auto base = [&] { dwconv7_ln_dispatch(in, w49, b, lw, lb, ref, N, H, W, C, 1e-6f, nullptr, 1); };
     printf("%dx%dx%dx%d  single-row: %.1f us\n", N, H, W, C, time_us(base));
     std::vector<float> hr(n), ho(n);
     hipMemcpy(hr.data(), ref, n * 4, hipMemcpyDeviceToHost);

@@ -45,7 +45,7 @@ static void shape(int N, int H) {
   }
   std::vector<float> hr(n), ho(n);
   for (int fmt = 1; fmt >= 0; --fmt) {
-    auto base = [&] { dwconv7_ln_launch_t<0>(in, w49, b, lw, lb, ref, N, H, W, C, 1e-6f, nullptr, fmt); };
+    auto base = [&] { dwconv7_ln_dispatch(in, w49, b, lw, lb, ref, N, H, W, C, 1e-6f, nullptr, fmt); };
     printf("%dx%dx%dx%d %s  shipped (row groups): %.1f us\n", N, H, W, C, fmt ? "SP8" : "f32", time_us(base));
     hipMemcpy(hr.data(), ref, n * 4, hipMemcpyDeviceToHost);
     auto run = [&](const char* name, auto f) {
