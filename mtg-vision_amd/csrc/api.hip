@@ -11,6 +11,7 @@
 #include "match.h"
 #include "rowops.h"
 #include "gemm_sp.h"
+#include "operand_registry.h"
 
 namespace mtgv {
 const char* last_error_cstr();
@@ -31,15 +32,15 @@ struct ScopedWeights {
   std::unique_lock<std::recursive_mutex> lk;
   ScopedWeights(const float* W, int n, int k, hipStream_t stream) : s(stream), lk(g_op_mu) {
     if (W == nullptr || k % 8 != 0 || gemm_precision() != GEMM_PREC_F16X3 || ((uintptr_t)W % 16) != 0) return;
-    if (sp8_lookup(W, k, nullptr, nullptr)) return;  // the caller already owns a registration
-    sp8_register(W, (size_t)n * k, k);
-    sp8_refresh(W, 0, (size_t)n * k, s);
+    if (operand_sp8(W, k, nullptr, nullptr)) return;  // the caller already owns a registration
+    operand_register(W, (size_t)n * k, k, false);  // the SP kernel's copy only
+    operand_refresh(W, 0, (size_t)n * k, s);
     w = W;
   }
   ~ScopedWeights() {
     if (w == nullptr) return;
     (void)hipStreamSynchronize(s);
-    sp8_unregister(w);
+    operand_unregister(w);
   }
 };
 thread_local GrnLayout t_last_grn;

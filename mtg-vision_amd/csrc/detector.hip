@@ -7,6 +7,7 @@
 #include "nms.h"
 #include "rowops.h"
 #include "gemm_sp.h"
+#include "operand_registry.h"
 #include "sp8.h"
 #include "act.h"
 
@@ -441,7 +442,7 @@ Detector::Detector(const mtgv_detector_cfg& cfg) : cfg_(cfg) {
 
 Detector::~Detector() {
   for (float* p : dev_allocs_) {
-    gemm_split_unregister(p);
+    operand_unregister(p);
     (void)hipFree(p);
   }
   if (nms_ws_) (void)hipFree(nms_ws_);
@@ -495,8 +496,8 @@ float* Detector::upload(const std::vector<float>& v, int row_k) {
   HIP_OK(hipMalloc((void**)&d, std::max<size_t>(v.size(), 4) * sizeof(float)));
   HIP_OK(hipMemcpy(d, v.data(), v.size() * sizeof(float), hipMemcpyHostToDevice));
   dev_allocs_.push_back(d);
-  gemm_split_register(d, v.size(), row_k);  // weights become pre-split B operands for the f16x3 GEMMs (small vectors are skipped)
-  gemm_split_refresh(d, 0, v.size() % 4 == 0 ? v.size() : 0, nullptr);
+  operand_register(d, v.size(), row_k);  // weights become pre-split B operands for the f16x3 GEMMs (small vectors are skipped)
+  operand_refresh(d, 0, v.size() % 4 == 0 ? v.size() : 0, nullptr);
   HIP_OK(hipStreamSynchronize(nullptr));
   return d;
 }
@@ -611,7 +612,7 @@ void Detector::finalize() {
   MTGV_CHECK(missing() == 0, ERR_RUNTIME, "detector has %d unset parameters", missing());
   if (finalized_) return;
   for (float* p : dev_allocs_) {
-    gemm_split_unregister(p);
+    operand_unregister(p);
     (void)hipFree(p);
   }
   dev_allocs_.clear();

@@ -10,6 +10,7 @@
 #include "encoder.h"
 #include "rowops.h"
 #include "gemm_sp.h"
+#include "operand_registry.h"
 #include "mlp_fused.h"
 
 #include <string.h>
@@ -22,7 +23,7 @@ namespace mtgv {
 ParamStore::~ParamStore() {
   for (auto& kv : slots_)
     if (kv.second.dev) {
-      gemm_split_unregister(kv.second.dev);
+      operand_unregister(kv.second.dev);
       (void)hipFree(kv.second.dev);
     }
 }
@@ -38,7 +39,7 @@ float* ParamStore::add(const std::string& key, std::vector<int> shape, Repack r,
   for (int d : shape) sl.numel *= d;
   HIP_OK(hipMalloc((void**)&sl.dev, (size_t)sl.numel * sizeof(float)));
   if (shape.size() >= 2 && r != R_DW49)  // conv / linear weights: B operands, rows of numel / shape[0] floats
-    gemm_split_register(sl.dev, (size_t)sl.numel, (int)(sl.numel / shape[0]));
+    operand_register(sl.dev, (size_t)sl.numel, (int)(sl.numel / shape[0]));
   MTGV_CHECK(slots_.find(key) == slots_.end(), ERR_INVALID, "duplicate parameter %s", key.c_str());
   slots_[key] = sl;
   return sl.dev;
@@ -79,8 +80,8 @@ void ParamStore::set(const std::string& key, const float* host, int64_t numel) {
     src = tmp.data();
   }
   HIP_OK(hipMemcpy(sl.dev, src, (size_t)numel * sizeof(float), hipMemcpyHostToDevice));
-  if (gemm_split_lookup(sl.dev) != nullptr) {
-    gemm_split_refresh(sl.dev, 0, (size_t)numel, nullptr);
+  if (operand_registered(sl.dev)) {
+    operand_refresh(sl.dev, 0, (size_t)numel, nullptr);
     HIP_OK(hipStreamSynchronize(nullptr));
   }
   if (sl.keep_host) sl.host.assign(host, host + numel);

@@ -17,9 +17,9 @@ struct GemmArgs {
   int a_fmt = 0;                // 0: f32; 1: SP8 (sp8.h) - only launches gemm_sp_plan accepts (gemm_sp_takes_sp8)
   const float* W = nullptr;     // [N][K]
   // f16x3 only, optional: W with every aligned group of 4 floats replaced by their 4 fp16 hi + 4 fp16 lo halves
-  // (same byte layout, so the same offsets address it).  gemm_launch fills it in for registered weights.
+  // (same byte layout, so the same offsets address it).  gemm_launch fills it in for registered weights (operand_registry.h).
   const float* W_split = nullptr;
-  // per-column power-of-two scales of W_split (registered rows are stored scaled, gemm_sp.h); filled in by gemm_launch
+  // per-column power-of-two scales of W_split (registered rows are stored scaled, operand_registry.h); filled in by gemm_launch
   const float* wscale = nullptr;
   // f16x3 only: A is multiplied by a_mul (a power of two) before it is split and the accumulator by a_unmul = 1/a_mul.
   // For launches whose activations may exceed the fp16 range (|a| > 65504); 1 everywhere on the recognition path.
@@ -128,17 +128,6 @@ int gemm_precision();
 void gemm_set_precision(int prec);
 // out[n] = bias[n] + W[n][:] . shift  (GRN beta folded into the next Linear's bias; a_shift is not applied by the GEMM)
 void fold_shift_into_bias_launch(const float* W, const float* shift, const float* bias, float* out, int N, int K, hipStream_t s);
-
-// Pre-split copies of constant B operands (weights, the bank) for the f16x3 mode: the loader then moves 16 bytes of
-// ready fp16 halves instead of converting the same weights in every block that uses them.  An owner registers the
-// base pointer of a buffer it allocated, refreshes a range after writing it, and unregisters before freeing.
-// gemm_launch looks W up by exact base pointer; unregistered operands are split on the fly as before.
-// row_k > 0 (a multiple of 8): the buffer holds rows of row_k floats; an SP8 copy with per-row scales is kept as well
-// and launches with K == row_k go to the LDS-DMA kernel (gemm_sp.h).
-void gemm_split_register(const float* W, size_t n_floats, int row_k = 0);
-void gemm_split_refresh(const float* W, size_t offset_floats, size_t n_floats, hipStream_t s);
-void gemm_split_unregister(const float* W);
-const float* gemm_split_lookup(const float* W);
 
 // launch profiler for the roofline measurement (off by default; adds two event records per launch)
 void gemm_profile_enable(bool on);

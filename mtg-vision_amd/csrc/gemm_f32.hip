@@ -8,12 +8,11 @@
 //          measured error vs fp64 is at the f32 level (tools/micro/split_gemm.hip, tests/test_gpu_precision.py)
 #include "gemm_kernel.h"
 #include "gemm_sp.h"
+#include "operand_registry.h"
 
 #include <stdlib.h>
 #include <string.h>
 #include <algorithm>
-#include <map>
-#include <mutex>
 #include <string>
 #include <vector>
 
@@ -149,113 +148,6 @@ static void prof_end(hipStream_t s) {
   if (!g_prof.on) return;
   HIP_OK(hipEventRecord(g_prof.ev[g_prof.used + 1], s));
   g_prof.used += 2;
-}
-
-// ---------------------------------------------------------------------------
-// pre-split weight registry (f16x3)
-// ---------------------------------------------------------------------------
-__global__ __launch_bounds__(256) void split_pack_kernel(const float* __restrict__ in, float* __restrict__ out, long n4) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n4) return;
-  f16x4 hi, lo;
-  split_f16(reinterpret_cast<const f32x4*>(in)[i], hi, lo);
-  f16x8 o;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) o[j] = hi[j], o[4 + j] = lo[j];
-  reinterpret_cast<f16x8*>(out)[i] = o;
-}
-
-// rows of row_k floats, stored scaled by 1 / wscale[row] (the power of two the SP8 copy of the same buffer uses)
-__global__ __launch_bounds__(256) void split_pack_rows_kernel(const float* __restrict__ in, float* __restrict__ out,
-                                                             const float* __restrict__ wscale, long n4, int rk4) {
-  const long i = (long)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n4) return;
-  const float sc = 1.0f / wscale[i / rk4];  // exact: wscale is a power of two
-  f16x4 hi, lo;
-  split_f16(reinterpret_cast<const f32x4*>(in)[i] * sc, hi, lo);
-  f16x8 o;
-#pragma unroll
-  for (int j = 0; j < 4; ++j) o[j] = hi[j], o[4 + j] = lo[j];
-  reinterpret_cast<f16x8*>(out)[i] = o;
-}
-
-namespace {
-struct SplitEntry {
-  float* buf = nullptr;
-  size_t n = 0;
-  int row_k = 0;  // > 0: rows of row_k floats stored with the per-row scale of the SP8 registry
-};
-std::map<const float*, SplitEntry> g_split;
-std::mutex g_split_mu;
-}  // namespace
-
-void gemm_split_register(const float* W, size_t n_floats, int row_k) {
-  if (W == nullptr || n_floats < 64 || n_floats % 4 != 0 || ((uintptr_t)W % 16) != 0) return;
-  if (row_k > 0) sp8_register(W, n_floats, row_k);
-  std::lock_guard<std::mutex> lk(g_split_mu);
-  SplitEntry& e = g_split[W];
-  const int rk = (row_k > 0 && row_k % 8 == 0 && n_floats % (size_t)row_k == 0) ? row_k : 0;  // what sp8_register accepts
-  if (e.buf != nullptr && e.n == n_floats) {
-    e.row_k = rk;
-    return;
-  }
-  if (e.buf != nullptr) (void)hipFree(e.buf);
-  e.n = n_floats;
-  e.row_k = rk;
-  HIP_OK(hipMalloc((void**)&e.buf, n_floats * sizeof(float)));
-}
-
-void gemm_split_refresh(const float* W, size_t offset_floats, size_t n_floats, hipStream_t s) {
-  sp8_refresh(W, offset_floats, n_floats, s);  // also (re)computes the rows' scales
-  float* out = nullptr;
-  int row_k = 0;
-  {
-    std::lock_guard<std::mutex> lk(g_split_mu);
-    auto it = g_split.find(W);
-    if (it == g_split.end()) return;
-    MTGV_CHECK(offset_floats % 4 == 0 && n_floats % 4 == 0 && offset_floats + n_floats <= it->second.n, ERR_INVALID,
-               "split refresh outside the registered buffer");
-    out = it->second.buf;
-    row_k = it->second.row_k;
-  }
-  if (n_floats == 0) return;
-  const long n4 = (long)(n_floats / 4);
-  const float* wsc = nullptr;
-  if (row_k > 0) {
-    MTGV_CHECK(offset_floats % row_k == 0 && n_floats % row_k == 0, ERR_INVALID, "split refresh must cover whole rows");
-    MTGV_CHECK(sp8_lookup(W + offset_floats, row_k, nullptr, &wsc), ERR_RUNTIME, "split refresh: row scales missing");
-    hipLaunchKernelGGL(split_pack_rows_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, W + offset_floats,
-                       out + offset_floats, wsc, n4, row_k / 4);
-  } else {
-    hipLaunchKernelGGL(split_pack_kernel, dim3((unsigned)((n4 + 255) / 256)), dim3(256), 0, s, W + offset_floats, out + offset_floats, n4);
-  }
-  HIP_OK(hipGetLastError());
-}
-
-void gemm_split_unregister(const float* W) {
-  sp8_unregister(W);
-  std::lock_guard<std::mutex> lk(g_split_mu);
-  auto it = g_split.find(W);
-  if (it == g_split.end()) return;
-  if (it->second.buf != nullptr) (void)hipFree(it->second.buf);
-  g_split.erase(it);
-}
-
-const float* gemm_split_lookup(const float* W) {
-  std::lock_guard<std::mutex> lk(g_split_mu);
-  auto it = g_split.find(W);
-  return it == g_split.end() ? nullptr : it->second.buf;
-}
-
-// pre-split copy usable by a launch with rows of K floats: unscaled copies always, scaled ones only with their scales
-static const float* split_for_launch(const float* W, int K, const float** wscale) {
-  *wscale = nullptr;
-  std::lock_guard<std::mutex> lk(g_split_mu);
-  auto it = g_split.find(W);
-  if (it == g_split.end()) return nullptr;
-  if (it->second.row_k == 0) return it->second.buf;
-  if (it->second.row_k != K || !sp8_lookup(W, K, nullptr, wscale)) return nullptr;
-  return it->second.buf;
 }
 
 static int g_prec = -1;  // -1: not read from the environment yet
@@ -407,7 +299,7 @@ void gemm_launch(const GemmArgs& args, hipStream_t s) {
   GemmDev g;
   g.a = a;
   if (gemm_precision() == GEMM_PREC_F16X3 && g.a.W_split == nullptr && a.strideW == 0)
-    g.a.W_split = split_for_launch(a.W, a.K, &g.a.wscale);
+    g.a.W_split = operand_split(a.W, a.K, &g.a.wscale);
   if (gemm_precision() != GEMM_PREC_F16X3) g.a.W_split = nullptr, g.a.wscale = nullptr;
   g.d_ohw = make_fastdiv((uint32_t)(a.OH * a.OW));
   g.d_ow = make_fastdiv((uint32_t)a.OW);

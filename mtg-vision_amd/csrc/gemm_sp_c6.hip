@@ -2,9 +2,4 @@
 // conv (A mode 5) for 3x3 / stride-1 convs whose channels come in slices of 16 (the detector's 16-channel bottlenecks at
 // 160 x 160, which otherwise fall back to nine per-lane tap gathers with a K tail).
 #define SP_CFG_ID 6
-#define SP_WM 4
-#define SP_WN 1
-#define SP_TM 1
-#define SP_TN 1
-#define SP_KS_VALUE 1
 #include "gemm_sp_inst.h"

@@ -42,11 +42,15 @@
 //
 // Products: lo*hi + hi*lo + hi*hi per k16 step into the same accumulator, k ascending (WINDOW: slice-major): results
 // do not depend on the tile configuration.
+//
+// The code names the A modes SP_A_* and the EPI values SP_EPI_*, and takes its LDS layout from the functions the host
+// sizes a launch with: gemm_sp_cfg.h.
 #pragma once
 #include <type_traits>
 
 #include "act.h"
 #include "gemm_f32.h"
+#include "gemm_sp_cfg.h"
 #include "sp8.h"
 
 namespace mtgv {
@@ -56,14 +60,6 @@ typedef float spf16 __attribute__((ext_vector_type(16)));
 // One MFMA of the main loop.
 __device__ __forceinline__ spf16 sp_mfma(sp_h8 b, sp_h8 a, spf16 c) {
   return __builtin_amdgcn_mfma_f32_32x32x16_f16(b, a, c, 0, 0, 0);
-}
-
-// LDS bytes of the window conv's staged input window (host side; the kernel's win_px is the same count in pixels): the
-// tile's bm output pixels plus a row and a pixel on either side, in whole 1 KB pieces of rb bytes per staged pixel.  The
-// planner decides "fits" and the launcher sizes the allocation from this one function.
-constexpr size_t sp_window_bytes(int bm, int rb, int Wd) {
-  const int rpp = 1024 / rb;
-  return (size_t)((bm + 2 * Wd + 2 + rpp - 1) / rpp * rpp) * rb;
 }
 
 struct SpDev {
@@ -117,25 +113,26 @@ typedef __attribute__((address_space(3))) void* sp_lptr;
 template <int WM, int WN, int TM, int TN, int KS, int NST, int AMODE, int ACT, int EPI>
 __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_kernel(const SpDev g) {
 #pragma clang fp contract(off)
-  constexpr int NW = WM * WN, NT = 64 * NW, BM = 32 * TM * WM, BN = 32 * TN * WN;
+  constexpr SpTile T{WM, WN, TM, TN, KS};  // the LDS layout below is gemm_sp_cfg.h's: the host sizes launches from the same functions
+  constexpr int NW = T.waves(), NT = 64 * NW, BM = T.bm(), BN = T.bn();
   constexpr bool GEN = EPI < 0;  // epilogue shape read from the arguments (see the epilogue)
   static_assert(TM <= 2, "the epilogue names its slabs");
-  static_assert(NST >= 2 && NST <= 4 && (AMODE != 1 || NST == 2), "ring depth; the register A path is two-deep");
-  constexpr int RB = 64 * KS, RPP = 1024 / RB, SPR = RB / 16;
-  constexpr bool AWIN = AMODE == 5;  // 3x3 / stride 1 / pad 1 conv: the tile's input window is staged once per 32 channels
-  constexpr bool ADMA = AMODE != 1 && !AWIN;
-  constexpr bool AF32 = AMODE == 3 || AMODE == 4;  // f32 rows by DMA, split into hi / lo when a fragment is read
-  constexpr bool HI16 = AMODE == 6;                // fp16 rows on both sides: 2 bytes per element, 64 k per 128-byte stage row
+  static_assert(NST >= 2 && NST <= 4 && (AMODE != SP_A_REG || NST == 2), "ring depth; the register A path is two-deep");
+  constexpr int RB = T.rb(), RPP = kSpPiece / RB, SPR = RB / 16;
+  constexpr bool AWIN = AMODE == SP_A_WINDOW;  // 3x3 / stride 1 / pad 1 conv: the tile's input window is staged once per 32 channels
+  constexpr bool ADMA = AMODE != SP_A_REG && !AWIN;
+  constexpr bool AF32 = AMODE == SP_A_F32_MUL || AMODE == SP_A_F32;  // f32 rows by DMA, split into hi / lo when a fragment is read
+  constexpr bool HI16 = AMODE == SP_A_HI16;                // fp16 rows on both sides: 2 bytes per element, 64 k per 128-byte stage row
   constexpr int EB = HI16 ? 2 : 4;                 // bytes per operand element in memory
-  static_assert(!HI16 || (KS == 2 && EPI == 16), "fp16 rows: 128-byte stage rows, top-k epilogue");
-  constexpr int SA = AWIN ? 0 : BM * RB, SB = BN * RB, SSC = AMODE == 3 ? 1024 : 0, STG = SA + SB + SSC;
+  static_assert(!HI16 || (KS == 2 && EPI == SP_EPI_TOPK), "fp16 rows: 128-byte stage rows, top-k epilogue");
+  constexpr int SA = sp_stage_a(T, AMODE), SB = sp_stage_b(T), SSC = sp_stage_mul(AMODE), STG = sp_stage(T, AMODE);
   // (window conv: 32-channel stages with KS == 2, 16-channel stages - the detector's 16-channel bottlenecks - with KS == 1)
-  static_assert(AMODE != 3 || KS == 2, "the scale image is one DMA piece: 8 images x 32 k");
+  static_assert(AMODE != SP_A_F32_MUL || KS == 2, "the scale image is one DMA piece: 8 images x 32 k");
   constexpr int PA = ADMA ? BM / RPP : 0, PB = BN / RPP, NP = PA + PB;
   constexpr int PPW = (NP + NW - 1) / NW;
   constexpr int CPS = BM * 2 * KS;                  // REG: 8-float chunks of A per stage
-  constexpr int CPT = AMODE == 1 ? CPS / NT : 1;    // per thread
-  static_assert(AMODE != 1 || CPS % NT == 0, "A chunks must divide over the threads");
+  constexpr int CPT = AMODE == SP_A_REG ? CPS / NT : 1;    // per thread
+  static_assert(AMODE != SP_A_REG || CPS % NT == 0, "A chunks must divide over the threads");
   extern __shared__ __attribute__((aligned(1024))) char smem[];
 
   const int tid = threadIdx.x, lane = tid & 63;
@@ -165,7 +162,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
   bool tailz[PPW];
   int cslot[PPW], cih0[PPW], ciw0[PPW];  // CONV A pieces: logical slot, first input row / column of the window
   const char* csrc[PPW];             // CONV A pieces, fast form: address of the window's first pixel at this lane's chunk
-  const bool conv_fast = AMODE == 2 && g.Cin % (16 * KS) == 0;
+  const bool conv_fast = AMODE == SP_A_CONV && g.Cin % (16 * KS) == 0;
   // Dense pieces (B always, A unless it is gathered) of a launch without a K tail: the DMA's address is a uniform
   // base (SGPR pair, advanced per stage by scalar adds) plus a 32-bit lane offset fixed for the whole tile - the
   // saddr form of global_load_lds: no vector arithmetic per piece and half the address bytes per instruction.
@@ -187,7 +184,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
     if (isA) {
       int m = m0 + row;
       m = m < g.M ? m : g.M - 1;
-      if constexpr (AMODE == 2) {
+      if constexpr (AMODE == SP_A_CONV) {
         const uint32_t img = fdiv((uint32_t)m, g.d_ohw);
         const uint32_t rem = (uint32_t)m - img * (uint32_t)(g.OH * g.OW);
         const uint32_t oh = fdiv(rem, g.d_ow);
@@ -207,23 +204,23 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
     tailz[u] = ktail && ((nk - 1) * 2 * KS + (slot >> 1)) >= kchunks;
   }
   // AMODE 3: lane l of the scale piece fetches 16 bytes (4 k) of image img0 + l / 8
-  const int img0 = AMODE == 3 ? (int)fdiv((uint32_t)m0, g.d_hw) : 0;
+  const int img0 = AMODE == SP_A_F32_MUL ? (int)fdiv((uint32_t)m0, g.d_hw) : 0;
   const char* sc_src = nullptr;
   bool sc_tailz = false;
-  if constexpr (AMODE == 3) {
+  if constexpr (AMODE == SP_A_F32_MUL) {
     const int img_last = (int)fdiv((uint32_t)(g.M - 1), g.d_hw);
     const int im = img0 + (lane >> 3) < img_last ? img0 + (lane >> 3) : img_last;
     sc_src = reinterpret_cast<const char*>(g.a_scale + (long)im * g.K) + (lane & 7) * 16;
     sc_tailz = ktail && ((nk - 1) * 2 * KS + ((lane & 7) >> 1)) >= kchunks;
   }
   // AWIN: [window: win_px pixels x 128 B][weight ring]; otherwise the ring starts at the base
-  const int win_px = AWIN ? ((BM + 2 * g.Wd + 2 + RPP - 1) / RPP * RPP) : 0;  // whole 1 KB pieces
+  const int win_px = AWIN ? sp_window_px(BM, RB, g.Wd) : 0;  // whole 1 KB pieces
   char* const ring = smem + (AWIN ? win_px * RB : 0);
   // one piece the general way: per-lane 64-bit source (conv gather, K tail -> zero page)
   auto issue_piece = [&](int u, int t, int buf) {
     const int p = wave + NW * u;
     const char* s;
-    if (AMODE == 2 && p < PA && conv_fast) {
+    if (AMODE == SP_A_CONV && p < PA && conv_fast) {
       // Cin is a multiple of the stage depth: the whole stage lies inside one tap, so tap, kh, kw and the first
       // channel are wave-uniform (scalar registers) and a lane only tests its pixel against the padding
       const uint32_t k0 = (uint32_t)t * (16u * KS);
@@ -233,7 +230,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
       const long tap_off = ((long)kh * g.Wd + kw) * g.a_rowb + (long)(k0 - tap * (uint32_t)g.Cin) * 4;
       const bool ok = (unsigned)(cih0[u] + (int)kh) < (unsigned)g.H && (unsigned)(ciw0[u] + (int)kw) < (unsigned)g.Wd;
       s = ok ? csrc[u] + tap_off : g.zero;
-    } else if (AMODE == 2 && p < PA) {
+    } else if (AMODE == SP_A_CONV && p < PA) {
       // chunk -> (tap, channel); the tap's pixel may fall into the zero padding
       const int kc = t * 2 * KS + (cslot[u] >> 1);
       const uint32_t k = (uint32_t)(kc < kchunks ? kc : 0) * 8u;
@@ -259,7 +256,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
       for (int u = 0; u < PPW; ++u) {
         const int p = wave + NW * u;
         if (NP % NW == 0 || p < NP) {
-          if (AMODE == 2 && p < PA) issue_piece(u, t, buf);
+          if (AMODE == SP_A_CONV && p < PA) issue_piece(u, t, buf);
           else sp_dma16_saddr(p < PA ? abase : wbase, off32[u], ring + buf * STG + (SA - PA * 1024) + p * 1024);
         }
       }
@@ -268,7 +265,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
       for (int u = 0; u < PPW; ++u)
         if (NP % NW == 0 || wave + NW * u < NP) issue_piece(u, t, buf);
     }
-    if constexpr (AMODE == 3) {  // the stage's slice of the per-image A multipliers: [8 images from img0][32 k]
+    if constexpr (AMODE == SP_A_F32_MUL) {  // the stage's slice of the per-image A multipliers: [8 images from img0][32 k]
       if (wave == NP % NW) {
         const char* sp = sc_src + (long)t * RB;
         if (t == nk - 1 && sc_tailz) sp = g.zero;
@@ -283,7 +280,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
   unsigned a_lds[CPT];
   int a_ch[CPT];
   sp_f4 ra[CPT][2], rs[CPT][2];
-  if constexpr (AMODE == 1) {
+  if constexpr (AMODE == SP_A_REG) {
 #pragma unroll
     for (int v = 0; v < CPT; ++v) {
       const int c = tid + NT * v;
@@ -298,7 +295,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
     }
   }
   auto loadA = [&](int t) {
-    if constexpr (AMODE == 1) {
+    if constexpr (AMODE == SP_A_REG) {
 #pragma unroll
       for (int v = 0; v < CPT; ++v) {
         const bool ok = !ktail || (t * 2 * KS + a_ch[v]) < kchunks;
@@ -317,7 +314,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
     }
   };
   auto storeA = [&](int buf) {
-    if constexpr (AMODE == 1) {
+    if constexpr (AMODE == SP_A_REG) {
 #pragma unroll
       for (int v = 0; v < CPT; ++v) {
         sp_h8 hi, lo;
@@ -393,7 +390,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
     sc_off[i] = 0;
-    if constexpr (AMODE == 3) {
+    if constexpr (AMODE == SP_A_F32_MUL) {
       int m = m0 + wm * TM * 32 + i * 32 + r;
       m = m < g.M ? m : g.M - 1;
       sc_off[i] = (unsigned)(SA + SB + ((int)fdiv((uint32_t)m, g.d_hw) - img0) * 128 + h * 32);
@@ -439,7 +436,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
   int my_pieces = 0;
 #pragma unroll
   for (int u = 0; u < PPW; ++u) my_pieces += (NP % NW == 0 || wave + NW * u < NP) ? 1 : 0;
-  if (AMODE == 3 && wave == NP % NW) my_pieces += 1;
+  if (AMODE == SP_A_F32_MUL && wave == NP % NW) my_pieces += 1;
   constexpr int AHEAD = NST - 2;  // stages that may still be in flight when stage t is consumed
   auto wait_stage = [&](bool tail) {
     // steady state: everything but the AHEAD youngest stages has landed; near the end fewer stages are outstanding
@@ -574,7 +571,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
             for (int i = 0; i < TM; ++i) {
               xa[ks][i][0] = *reinterpret_cast<const sp_f4*>(sb + a_off[i] + shi);
               xa[ks][i][1] = *reinterpret_cast<const sp_f4*>(sb + a_off[i] + slo);
-              if constexpr (AMODE == 3) {
+              if constexpr (AMODE == SP_A_F32_MUL) {
                 xs[ks][i][0] = *reinterpret_cast<const sp_f4*>(sb + sc_off[i] + ks * 64);
                 xs[ks][i][1] = *reinterpret_cast<const sp_f4*>(sb + sc_off[i] + ks * 64 + 16);
               }
@@ -585,7 +582,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
               bl[ks][j] = *reinterpret_cast<const sp_h8*>(sb + b_off[j] + slo);
             }
           }
-          if constexpr (AMODE == 3) {
+          if constexpr (AMODE == SP_A_F32_MUL) {
   #pragma unroll
             for (int ks = 0; ks < 2; ++ks)
   #pragma unroll
@@ -615,8 +612,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
           }
           // issue order: every LDS read, the first step's conversion, then the first step's MFMAs one by one, each
           // followed by a share of the second step's conversion
-          constexpr int CV = (AMODE == 3 ? 8 : 0) + 16;  // vector instructions per fragment: scale, split
-          __builtin_amdgcn_sched_group_barrier(0x100, 2 * (TM * (AMODE == 3 ? 4 : 2) + 2 * TN), 0);  // DS read
+          constexpr int CV = (AMODE == SP_A_F32_MUL ? 8 : 0) + 16;  // vector instructions per fragment: scale, split
+          __builtin_amdgcn_sched_group_barrier(0x100, 2 * (TM * (AMODE == SP_A_F32_MUL ? 4 : 2) + 2 * TN), 0);  // DS read
           __builtin_amdgcn_sched_group_barrier(0x002, CV * TM, 0);                                     // VALU
   #pragma unroll
           for (int q = 0; q < 3 * TM * TN; ++q) {
@@ -636,7 +633,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
             if constexpr (AF32) {  // 8 consecutive k of row r as f32: (scale,) split, and the fragments are ready
               sp_f4 x0 = *reinterpret_cast<const sp_f4*>(sb + a_off[i] + shi);
               sp_f4 x1 = *reinterpret_cast<const sp_f4*>(sb + a_off[i] + slo);
-              if constexpr (AMODE == 3) {
+              if constexpr (AMODE == SP_A_F32_MUL) {
                 x0 = x0 * *reinterpret_cast<const sp_f4*>(sb + sc_off[i] + ks * 64);
                 x1 = x1 * *reinterpret_cast<const sp_f4*>(sb + sc_off[i] + ks * 64 + 16);
               }
@@ -667,7 +664,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
             for (int i = 0; i < TM; ++i) acc[i][j] = sp_mfma(bh[j], ah[i], acc[i][j]);
         }
       }
-      if (AMODE == 1 && t + 1 < nk) storeA(buf ^ 1);
+      if (AMODE == SP_A_REG && t + 1 < nk) storeA(buf ^ 1);
       buf = buf + 1 == NST ? 0 : buf + 1;
       nbuf = nbuf + 1 == NST ? 0 : nbuf + 1;
     }
@@ -684,14 +681,14 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
   __builtin_amdgcn_s_barrier();  // every wave is done with the ring: it becomes the store staging area
   const long st2 = g.stamps != nullptr ? (long)__builtin_amdgcn_s_memtime() : 0;
 
-  if constexpr (EPI == 32) {
-    static_assert(EPI != 32 || (WN == 1 && TM == 1 && KS == 2 && !HI16), "chained 1x1: one wave holds whole rows");
+  if constexpr (EPI == SP_EPI_CHAIN) {
+    static_assert(EPI != SP_EPI_CHAIN || (sp_tile_chains(T) && !HI16), "chained 1x1: one wave holds whole rows");
     // LDS after the main loop: [NW x 4 KB: one column block of each wave's accumulators][NW x TN x 4 KB: each wave's A2
     // stages, row-major 128-byte rows with the main loop's swizzle][TN stages x N2 rows x 128 B: W2]
-    constexpr int CB = 32 * 128;
+    constexpr int CB = kSpSlab;
     char* const stg1 = smem + wave * CB;
-    char* const a2 = smem + NW * CB + wave * (TN * CB);
-    char* const w2 = smem + NW * CB * (1 + TN);
+    char* const a2 = smem + sp_chain_a2(T) + wave * (TN * CB);
+    char* const w2 = smem + sp_chain_w2(T);
     const int n2g = g.N2 >> 3;  // 8-row DMA pieces per stage
     for (int p = wave; p < TN * n2g; p += NW) {
       const int s = p / n2g, rg = p - s * n2g;
@@ -786,7 +783,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
   }
   if (!wave_active) return;
 
-  if constexpr (EPI == 16) {
+  if constexpr (EPI == SP_EPI_TOPK) {
     // ---- fused top-k (match path): the scores never leave registers.  A lane holds 16 TN columns of its row, its
     // partner lane ^ 32 the other 16 TN; each round picks the (score desc, column asc) maximum of the wave's 32 TN
     // columns and retires it.  Candidates: cand[m][(tile_n * WN + wn) * topk + kk]; topk_merge_kernel finishes.
@@ -843,10 +840,9 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
   // squares live in registers, every store instruction writes whole lines, and scale / bias / activation / residual /
   // SP8 packing all happen on the read-back side.  Residual rows are loaded one column block ahead.
   constexpr int SROW = 128 * TN;   // bytes per staged row (32*TN floats)
-  constexpr int WREG = 32 * SROW;  // per wave
-  // Eight-wave blocks (two blocks of them per CU = four waves per SIMD) stage their slabs in two rounds, waves 0..3 first:
-  // the ring holds four slabs, not eight.
-  constexpr int ER = (!AWIN && NW * WREG > NST * STG) ? 2 : 1;
+  constexpr int WREG = sp_staging_wave(T);  // per wave: 32 rows
+  // Eight-wave blocks stage their slabs in two rounds, waves 0..3 first (sp_staging_rounds).
+  constexpr int ER = sp_staging_rounds(T, AMODE, NST);
   static_assert(AWIN || (NW / ER) * WREG <= NST * STG, "the store staging area must fit into the ring");  // AWIN: the host sizes LDS for it
   char* const stg = smem + (ER == 1 ? wave : wave % (NW / ER)) * WREG;
   if constexpr (ER == 2) {
@@ -857,12 +853,12 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
   // EPI >= 0 fixes the epilogue's shape at compile time (bit 0 SP8 output, 1 f32 residual, 2 SP8 residual, 3 GRN
   // partial sums; no output remap, N % 4 == 0) so that the read-back loop is one straight line of code the compiler can
   // interleave across steps; EPI < 0 reads all of it from the arguments.
-  const bool out_sp8 = GEN ? g.out_fmt == 1 : (EPI & 1) != 0;
-  const bool res_f32 = GEN ? (g.res != nullptr && g.res_fmt == 0) : (EPI & 2) != 0;
-  const bool res_sp8 = GEN ? (g.res != nullptr && g.res_fmt == 1) : (EPI & 4) != 0;
+  const bool out_sp8 = GEN ? g.out_fmt == 1 : (EPI & SP_EPI_SP8_OUT) != 0;
+  const bool res_f32 = GEN ? (g.res != nullptr && g.res_fmt == 0) : (EPI & SP_EPI_RES_F32) != 0;
+  const bool res_sp8 = GEN ? (g.res != nullptr && g.res_fmt == 1) : (EPI & SP_EPI_RES_SP8) != 0;
   const bool has_res = res_f32 || res_sp8;
   const bool remap = GEN ? g.remap : false;
-  const bool grn = GEN ? g.grn_part != nullptr : (EPI & 8) != 0;
+  const bool grn = GEN ? g.grn_part != nullptr : (EPI & SP_EPI_GRN) != 0;
   const int img_first = grn ? (int)fdiv((uint32_t)mw0, g.d_hw) : 0;
   const long unit = (long)tile_m * WM + wm;
   // per-lane element offsets of row mw0 + lrow, column block 0; every element this lane touches is a wave-uniform

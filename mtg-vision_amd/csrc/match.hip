@@ -5,6 +5,7 @@
 //   3. topk_merge_kernel         tiles_n*k candidates per query -> top k (score desc, id asc)
 #include "match.h"
 #include "gemm_sp.h"
+#include "operand_registry.h"
 #include "rowops.h"
 #include "sp8.h"
 
@@ -336,7 +337,7 @@ Bank::Bank(int dim, int64_t capacity) : dim_(dim), cap_(capacity) {
   MTGV_CHECK(capacity > 0 && capacity < (1ll << 31), ERR_INVALID, "bank: capacity=%lld", (long long)capacity);
   vecs_.alloc((size_t)capacity * dim);
   // the bank is the B operand of the match GEMM; rows of `dim` floats get per-row scaled split copies
-  gemm_split_register(vecs_.p, (size_t)capacity * dim, dim % 8 == 0 ? dim : 0);
+  operand_register(vecs_.p, (size_t)capacity * dim, dim % 8 == 0 ? dim : 0);
   // workspace for the usual query batches up front (1024 queries, k <= 8, the candidate layout with the most groups:
   // 64-column tiles), so that topk does not allocate on the hot path; larger requests still grow it once
   stat_.alloc(4);
@@ -350,14 +351,14 @@ Bank::Bank(int dim, int64_t capacity) : dim_(dim), cap_(capacity) {
   }
 }
 
-Bank::~Bank() { gemm_split_unregister(vecs_.p); }
+Bank::~Bank() { operand_unregister(vecs_.p); }
 
 // fp16 hi halves of rows [row0, row0 + rows) of the (row-scaled) bank: what the SP8 copy holds as its hi pieces, contiguous
 void Bank::refresh_hi(int64_t row0, int64_t rows, hipStream_t s) {
   if (dim_ % 64 != 0 || rows <= 0) return;
   hi_.ensure((size_t)cap_ * dim_ / 2 + 8);
   const float* wsc = nullptr;
-  if (!sp8_lookup(vecs_.p + (size_t)row0 * dim_, dim_, nullptr, &wsc)) return;
+  if (!operand_sp8(vecs_.p + (size_t)row0 * dim_, dim_, nullptr, &wsc)) return;
   const long n8 = (long)rows * (dim_ / 8);
   hipLaunchKernelGGL(f32_to_f16_rows_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, vecs_.p + (size_t)row0 * dim_, wsc,
                      reinterpret_cast<_Float16*>(hi_.p) + (size_t)row0 * dim_, (long)rows, dim_);
@@ -390,7 +391,7 @@ void Bank::topk_prepass(const float* q, int b, int k, int64_t id_base, float thr
                      reinterpret_cast<_Float16*>(qhi_.p), (long)b, dim_);
   HIP_OK(hipGetLastError());
   const float* wsc = nullptr;
-  MTGV_CHECK(sp8_lookup(vecs_.p, dim_, nullptr, &wsc), ERR_RUNTIME, "bank: row scales missing");
+  MTGV_CHECK(operand_sp8(vecs_.p, dim_, nullptr, &wsc), ERR_RUNTIME, "bank: row scales missing");
   int sl = 0;
   {  // recorded for the roofline like the one-pass launch it replaces (sp = 3: one fp16 MFMA per product, fp16 bank bytes)
     GemmArgs rec;
@@ -413,7 +414,7 @@ void Bank::append(const float* v, int64_t n, bool is_device, hipStream_t s) {
   float* dst = vecs_.p + (size_t)size_ * dim_;
   HIP_OK(hipMemcpyAsync(dst, v, (size_t)n * dim_ * sizeof(float), is_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, s));
   l2norm_rows_launch(dst, dst, n, dim_, s);
-  gemm_split_refresh(vecs_.p, (size_t)size_ * dim_, (size_t)n * dim_, s);
+  operand_refresh(vecs_.p, (size_t)size_ * dim_, (size_t)n * dim_, s);
   refresh_hi(size_, n, s);
   if (!is_device) HIP_OK(hipStreamSynchronize(s));  // host buffer may be freed by the caller
   size_ += n;
@@ -424,7 +425,7 @@ void Bank::set_row(int64_t row, const float* v_host, hipStream_t s) {
   float* dst = vecs_.p + (size_t)row * dim_;
   HIP_OK(hipMemcpyAsync(dst, v_host, (size_t)dim_ * sizeof(float), hipMemcpyHostToDevice, s));
   l2norm_rows_launch(dst, dst, 1, dim_, s);
-  gemm_split_refresh(vecs_.p, (size_t)row * dim_, (size_t)dim_, s);
+  operand_refresh(vecs_.p, (size_t)row * dim_, (size_t)dim_, s);
   refresh_hi(row, 1, s);
   HIP_OK(hipStreamSynchronize(s));
 }

@@ -6,6 +6,7 @@
 #include <vector>
 
 #include "gemm_sp.h"
+#include "operand_registry.h"
 #include "mlp_fused_kernel.h"
 
 namespace mtgv {
@@ -51,7 +52,7 @@ void mlp_fused_launch(const MlpArgs& a, hipStream_t s) {
   g.X = reinterpret_cast<const char*>(a.x_sp8);
   const char* w8 = nullptr;
   const float* wsc = nullptr;
-  MTGV_CHECK(sp8_lookup(a.w1, a.C, &w8, &wsc), ERR_RUNTIME, "mlp_fused: pwconv1 weights have no SP8 copy");
+  MTGV_CHECK(operand_sp8(a.w1, a.C, &w8, &wsc), ERR_RUNTIME, "mlp_fused: pwconv1 weights have no SP8 copy");
   g.W1 = w8, g.ws1 = wsc, g.b1 = a.b1;
   g.W2p = reinterpret_cast<const char*>(a.w2p), g.ws2 = a.ws2, g.b2 = a.b2;
   g.scale = a.scale, g.res = a.res, g.Out = a.out, g.part = a.part;

@@ -22,7 +22,7 @@ res = {}
 for tag in tags:
     env = dict(os.environ)
     env.setdefault("MTGV_DET_FORK", "0")  # every launch alone on the GPU (the detector's branches in sequence)
-    lib, *sets = tag.split("+")  # "base+MTGV_SP_ADIRECT=1": the product library with an environment switch
+    lib, *sets = tag.split("+")  # "base+NAME=value": the product library with an environment switch
     for kv in sets:
         k, v = kv.split("=", 1)
         env[k] = v
