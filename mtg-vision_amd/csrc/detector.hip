@@ -7,6 +7,7 @@
 #include "nms.h"
 #include "rowops.h"
 #include "gemm_sp.h"
+#include "c2f_tail.h"
 #include "operand_registry.h"
 #include "sp8.h"
 #include "act.h"
@@ -734,12 +735,28 @@ void Detector::c2f(int idx, const View& in, const View& out, int n, hipStream_t 
   // pre: the stride-2 Conv in front of this block, whose only consumer is cv1 - the pair runs as one launch where it can
   if (pre != nullptr) conv_pair(*pre, *pre_in, in, 2, cw_.at(P + ".cv1"), cat.slice(0, 2 * ch), ACT_SILU, n, s);
   else conv(cw_.at(P + ".cv1"), in, cat.slice(0, 2 * ch), 1, ACT_SILU, nullptr, n, s);
+  const bool fuse = env_int("MTGV_DET_C2F_FUSE", 1) != 0;  // read per call (A/B in one process); 0: three launches
   for (int j = 0; j < ci.n; ++j) {
     const View src = cat.slice((1 + j) * ch, ch);
     const View dst = cat.slice((2 + j) * ch, ch);
     const std::string M = P + ".m." + std::to_string(j);
-    conv(cw_.at(M + ".cv1"), src, tmp, 1, ACT_SILU, nullptr, n, s);
-    conv(cw_.at(M + ".cv2"), tmp, dst, 1, ACT_SILU, ci.shortcut ? &src : nullptr, n, s);
+    // the last bottleneck and cv2 as one launch where there is a kernel for the block (c2f_tail.h): tmp and dst stay on chip
+    const ConvW &w1 = cw_.at(M + ".cv1"), &w2 = cw_.at(M + ".cv2"), &w3 = cw_.at(P + ".cv2");
+    const bool tail_shapes = w1.k == 3 && w1.cin == ch && w1.cout == ch && w2.k == 3 && w2.cin == ch && w2.cout == ch && w3.k == 1 &&
+                             w3.cin == (2 + ci.n) * ch && w3.cout == out.C;  // (anything else: conv() below reports it)
+    if (j == ci.n - 1 && fuse && tail_shapes && !count_flops_ && fmt_ == 1 && cat.fmt == 1 && out.fmt == 1) {
+      C2fTailArgs a;
+      a.cat = cat.p, a.cat_ct = cat.ct, a.cat_co = cat.co, a.n_img = n, a.H = cat.H, a.W = cat.W;
+      a.ch = ch, a.nb = ci.n, a.shortcut = ci.shortcut;
+      a.w1 = w1.w, a.b1 = w1.b, a.w2 = w2.w, a.b2 = w2.b, a.w3 = w3.w, a.b3 = w3.b, a.cout = w3.cout;
+      a.out = out.p, a.out_ct = out.ct, a.out_co = out.co;
+      if (c2f_tail_ok(a)) {
+        c2f_tail_launch(a, s);
+        return;
+      }
+    }
+    conv(w1, src, tmp, 1, ACT_SILU, nullptr, n, s);
+    conv(w2, tmp, dst, 1, ACT_SILU, ci.shortcut ? &src : nullptr, n, s);
   }
   conv(cw_.at(P + ".cv2"), cat.slice(0, (2 + ci.n) * ch), out, 1, ACT_SILU, nullptr, n, s);
 }

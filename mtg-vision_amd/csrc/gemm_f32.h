@@ -136,8 +136,9 @@ void gemm_profile_read(double* ms, double* flops, long* launches);
 void gemm_profile_dump(const char* path);
 double gemm_profile_bytes();  // compulsory operand + result bytes of the launches recorded since enable
 // For launches that do the work of a GEMM layer outside gemm_launch (mlp_fused.hip): record `a`'s shape (M, N, K, act,
-// a_scale / grn_part / res as flags) with the given LDS fill and compulsory bytes, bracketed by events on s.
-void gemm_profile_begin(const GemmArgs& a, hipStream_t s, int sp, double fill, double bytes);
+// a_scale / grn_part / res as flags) with the given LDS fill and compulsory bytes, bracketed by events on s.  xflops: the
+// algorithmic FLOPs of further layers the launch runs besides `a` (c2f_tail.hip: three layers in one launch).
+void gemm_profile_begin(const GemmArgs& a, hipStream_t s, int sp, double fill, double bytes, double xflops = 0.0);
 void gemm_profile_end(hipStream_t s);
 
 // Layout of the GRN partial sums a launch with these arguments writes: [ceil(M / unit_rows)][segmax][N] floats.

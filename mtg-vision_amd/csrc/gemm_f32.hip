@@ -92,7 +92,7 @@ void gemm_profile_dump(const char* path) {
     float t = 0.f;
     HIP_OK(hipEventElapsedTime(&t, g_prof.ev[i], g_prof.ev[i + 1]));
     const auto& r = g_prof.recs[i / 2];
-    const double fl = 2.0 * r.M * r.N * r.K * r.batch + r.xflops;  // xflops: a second layer chained into the launch
+    const double fl = 2.0 * r.M * r.N * r.K * r.batch + r.xflops;  // xflops: further layers run inside the launch
     fprintf(f, "%zu,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%.4f,%.2f,%.0f,%d,%.0f,%.0f\n", i / 2, r.M, r.N, r.K, r.KH, r.stride, r.batch, r.act,
             r.apro, r.grn, r.topk, r.tm, r.tn, r.bk, t, fl / (t * 1e-3) / 1e12, r.bytes, r.sp, r.fill, r.xflops);
   }
@@ -118,7 +118,8 @@ void gemm_profile_read(double* ms, double* flops, long* launches) {
 
 // pl: the convert-on-load tile of the launch (recorded also for launches another kernel runs)
 // fill: bytes the launch's tiles pull into LDS (every tile its A and B panels; 4 bytes per element in either format)
-static void prof_begin(const GemmArgs& a, const GemmPlan& pl, hipStream_t s, int sp, double fill, double bytes_override = -1.0) {
+static void prof_begin(const GemmArgs& a, const GemmPlan& pl, hipStream_t s, int sp, double fill, double bytes_override = -1.0,
+                       double xflops = 0.0) {
   if (!g_prof.on) return;
   while (g_prof.ev.size() < g_prof.used + 2) {
     hipEvent_t e;
@@ -126,7 +127,7 @@ static void prof_begin(const GemmArgs& a, const GemmPlan& pl, hipStream_t s, int
     g_prof.ev.push_back(e);
   }
   HIP_OK(hipEventRecord(g_prof.ev[g_prof.used], s));
-  const double xfl = a.W2 != nullptr ? 2.0 * (double)a.M * a.N2 * a.N : 0.0;
+  const double xfl = (a.W2 != nullptr ? 2.0 * (double)a.M * a.N2 * a.N : 0.0) + xflops;  // layers run inside the launch besides the first
   g_prof.flops += 2.0 * (double)a.M * a.N * a.K * a.batch + xfl;
   {
     const double a_el = is_conv(a) ? (double)(a.M / (a.OH * a.OW)) * a.H * a.Wd * a.Cin : (double)a.M * a.K;
@@ -217,8 +218,8 @@ static GemmPlan plan_for(const GemmArgs& a) {
   return gemm_plan(a.M, a.N, a.K, a.act != ACT_NONE, a.a_scale != nullptr);
 }
 
-void gemm_profile_begin(const GemmArgs& a, hipStream_t s, int sp, double fill, double bytes) {
-  if (g_prof.on) prof_begin(a, plan_for(a), s, sp, fill, bytes);
+void gemm_profile_begin(const GemmArgs& a, hipStream_t s, int sp, double fill, double bytes, double xflops) {
+  if (g_prof.on) prof_begin(a, plan_for(a), s, sp, fill, bytes, xflops);
 }
 void gemm_profile_end(hipStream_t s) { prof_end(s); }
 
