@@ -371,6 +371,35 @@ MTGV_API int mtgv_op_linear_ex(const float* a_dev, const float* w_dev, const flo
 MTGV_API int mtgv_op_conv2d(const float* x_dev, const float* w_dev, const float* bias_dev, float* out_dev, int32_t n, int32_t h,
                             int32_t w, int32_t cin, int32_t cout, int32_t kh, int32_t kw, int32_t stride, int32_t pad,
                             int32_t act, void* stream);
+/* One conv launch as the detector describes it (Detector::conv, conv_pair, proto), for single-layer tests of the
+ * SP8 paths.  Tensors are NHWC views: a pointer to pixel 0, floats per pixel, first channel; fmt 0 = f32, 1 = SP8
+ * (sp8.h: per 8 channels 8 fp16 hi halves, then 8 fp16 lo halves - same bytes per pixel, same offsets).  The output
+ * grid is the conv's own ((h + 2 pad - kh) / stride + 1, likewise w) unless os > 1: then row (img, y, x) of that grid
+ * is written to pixel (img, y os + oy, x os + ox) of an (oh os, ow os) grid - one phase of a ConvTranspose2d(k = s = os) -
+ * or, with os_nq > 0, the cout = os os os_nq columns are os os groups of os_nq channels and group q goes to phase
+ * (q / os, q % os): the whole ConvTranspose in one launch.  w2 != NULL chains a 1x1 layer [cout2][cout] behind the
+ * activated output inside the same launch (act must be SiLU); only out2 is written and out may be NULL.  A chain the
+ * kernel cannot run is status 1, never two launches. */
+typedef struct {
+  const void* x;       /* input: n images of h x w pixels, x_ct floats per pixel, channels [x_co, x_co + cin) */
+  int32_t n, h, w, x_ct, x_co, cin, x_fmt;
+  const float* wt;     /* [cout][kh][kw][cin] */
+  const float* bias;   /* [cout] or NULL */
+  int32_t cout, kh, kw, stride, pad, act;
+  void* out;           /* channels [out_co, out_co + cout) of out_ct floats per pixel */
+  int32_t out_ct, out_co, out_fmt;
+  const void* res;     /* NULL, or a residual on the output grid: channels [res_co, res_co + cout) of res_ct */
+  int32_t res_ct, res_co, res_fmt;
+  int32_t os, oy, ox, os_nq; /* os <= 1: no scatter */
+  const float* w2;     /* NULL, or the chained layer [cout2][cout] */
+  const float* bias2;
+  int32_t cout2, act2;
+  void* out2;          /* channels [out2_co, out2_co + cout2) of out2_ct floats per pixel */
+  int32_t out2_ct, out2_co, out2_fmt;
+} mtgv_conv_ex;
+/* path, unless NULL, receives {tile configuration, A mode, epilogue id, ring depth} of the launch that ran (the
+ * values of gemm_sp_cfg.h); configuration -1 (the rest 0): the convert-on-load kernel. */
+MTGV_API int mtgv_op_conv2d_ex(const mtgv_conv_ex* d, int32_t* path, void* stream);
 MTGV_API int mtgv_op_layernorm(const float* x_dev, const float* w_dev, const float* b_dev, float* out_dev, int64_t rows,
                                int32_t c, float eps, void* stream);
 /* depthwise 7x7 pad 3; weight (49, c) tap-major */

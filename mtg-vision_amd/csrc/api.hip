@@ -311,6 +311,41 @@ MTGV_API int mtgv_op_conv2d(const float* x_dev, const float* w_dev, const float*
                 (hipStream_t)stream);
   });
 }
+MTGV_API int mtgv_op_conv2d_ex(const mtgv_conv_ex* d, int32_t* path, void* stream) {
+  return guarded([&] {
+    MTGV_CHECK(d && d->x && d->wt && (d->out || d->w2), ERR_INVALID, "null argument");
+    MTGV_CHECK(d->stride > 0 && d->kh > 0 && d->kw > 0 && d->pad >= 0 && d->n > 0 && d->cin > 0 && d->cout > 0, ERR_INVALID, "bad conv geometry");
+    const int oh = (d->h + 2 * d->pad - d->kh) / d->stride + 1, ow = (d->w + 2 * d->pad - d->kw) / d->stride + 1;
+    MTGV_CHECK(oh > 0 && ow > 0, ERR_INVALID, "empty conv output");
+    hipStream_t s = (hipStream_t)stream;
+    ScopedWeights reg(d->wt, d->cout, d->kh * d->kw * d->cin, s), reg2(d->w2, d->cout2, d->cout, s);
+    GemmArgs g = conv_args({(const float*)d->x, d->n, d->h, d->w, d->x_ct, d->x_co, d->cin, d->x_fmt}, d->wt, d->bias, d->cout, d->kh, d->kw,
+                           d->stride, d->pad, {(float*)d->out, oh, ow, d->out_ct, d->out_co, d->out_fmt}, d->act);
+    if (d->res) g.res = (const float*)d->res + d->res_co, g.ldr = d->res_ct, g.res_fmt = d->res_fmt;
+    if (d->os > 1) {  // Detector::proto
+      MTGV_CHECK(d->oy >= 0 && d->oy < d->os && d->ox >= 0 && d->ox < d->os && d->os_nq >= 0, ERR_INVALID, "bad scatter");
+      g.os = d->os, g.OH2 = oh * d->os, g.OW2 = ow * d->os;
+      if (d->os_nq > 0) g.os_nq = d->os_nq;
+      else g.oy = d->oy, g.ox = d->ox;
+    }
+    if (d->w2) {  // Detector::conv_pair
+      MTGV_CHECK(d->out2 && d->cout2 > 0, ERR_INVALID, "null argument");
+      g.Out = nullptr;  // only the second layer's output is stored
+      g.W2 = d->w2, g.bias2 = d->bias2, g.Out2 = (float*)d->out2, g.N2 = d->cout2, g.ldo2 = d->out2_ct, g.o_off2 = d->out2_co;
+      g.out_fmt2 = d->out2_fmt, g.act2 = d->act2;
+      MTGV_CHECK(gemm_sp_chain_ok(g), ERR_INVALID, "conv2d_ex: this pair cannot run as a chained launch");
+    }
+    if (path) {
+      path[0] = -1, path[1] = path[2] = path[3] = 0;
+      const SpPlan sp = gemm_sp_plan(g);  // gemm_launch decides by the same call
+      if (sp.cfg >= 0) {
+        const SpPath p = gemm_sp_path(g, sp);
+        path[0] = p.cfg, path[1] = p.amode, path[2] = p.epi, path[3] = p.ring;
+      }
+    }
+    gemm_launch(g, s);
+  });
+}
 MTGV_API int mtgv_op_layernorm(const float* x_dev, const float* w_dev, const float* b_dev, float* out_dev, int64_t rows,
                                int32_t c, float eps, void* stream) {
   return guarded([&] {

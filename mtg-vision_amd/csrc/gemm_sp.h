@@ -22,6 +22,12 @@ SpPlan gemm_sp_plan(const GemmArgs& a);
 bool gemm_sp_takes_sp8(const float* W, int M, int N, int K, int lda, int c_off);
 // only through gemm_launch, which has checked the arguments and filled in a.segmax for GRN launches
 void gemm_sp_launch(const GemmArgs& a, const SpPlan& pl, hipStream_t s);
+// The kernel gemm_sp_launch runs for (a, pl), from the code it launches with: tile configuration, A mode (SpAMode),
+// epilogue shape (sp_epi_of) and ring depth (sp_window_ring for the window conv).  Test surface.
+struct SpPath {
+  int cfg, amode, epi, ring;
+};
+SpPath gemm_sp_path(const GemmArgs& a, const SpPlan& pl);
 // can the launch described by `a` (W2 / bias2 / Out2 / N2 ... set) run with its second layer chained into the epilogue?
 bool gemm_sp_chain_ok(const GemmArgs& a);
 bool gemm_sp_topk_layout(const GemmArgs& a, int* slots, int* cols);  // gemm_topk_layout when the SP kernel takes the launch

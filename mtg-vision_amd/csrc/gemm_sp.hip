@@ -252,7 +252,19 @@ void gemm_sp_topk_hi16_launch(const void* q_hi, const void* bank_hi, const float
   HIP_OK(hipGetLastError());
 }
 
-void gemm_sp_launch(const GemmArgs& a, const SpPlan& pl, hipStream_t s) {
+// How A reaches LDS.  f32 A: by DMA and split at the fragment read when the rows are 16-byte aligned, need no range
+// multiplier and a tile's rows span at most 8 images of the per-image multipliers; through registers otherwise
+static int sp_amode_of(const GemmArgs& a, const SpPlan& pl) {
+  if (a.a_fmt == 1) return !is_conv(a) ? SP_A_SP8 : window_conv_fits(a, pl) ? SP_A_WINDOW : SP_A_CONV;
+  if (a.a_mul == 1.0f && ((uintptr_t)a.A & 15) == 0) {
+    if (a.a_scale == nullptr) return SP_A_F32;
+    if (((uintptr_t)a.a_scale & 15) == 0 && (kSpTile[pl.cfg].bm() - 1) / (a.hw > 0 ? a.hw : 1) + 2 <= 8) return SP_A_F32_MUL;
+  }
+  return SP_A_REG;
+}
+
+// the kernel arguments of launch `a` on plan `pl`
+static SpDev sp_dev_of(const GemmArgs& a, const SpPlan& pl) {
   MTGV_CHECK(pl.cfg >= 0 && pl.cfg < kSpNumCfg, ERR_INVALID, "gemm_sp: no plan");
   SpDev g;
   g.A = reinterpret_cast<const char*>(a.A);
@@ -301,14 +313,19 @@ void gemm_sp_launch(const GemmArgs& a, const SpPlan& pl, hipStream_t s) {
     MTGV_CHECK(g.remap && a.os_nq % 8 == 0 && a.N == a.os * a.os * a.os_nq && a.oy == 0 && a.ox == 0 && a.res == nullptr &&
                    a.grn_part == nullptr,
                ERR_INVALID, "gemm_sp: os_nq=%d does not describe a %dx%d scatter of N=%d columns", a.os_nq, a.os, a.os, a.N);
-  // f32 A: by DMA and split at the fragment read when the rows are 16-byte aligned, need no range multiplier and a
-  // tile's rows span at most 8 images of the per-image multipliers; through registers otherwise
-  int amode = a.a_fmt == 1 ? (is_conv(a) ? SP_A_CONV : SP_A_SP8) : SP_A_REG;
-  if (amode == SP_A_CONV && window_conv_fits(a, pl)) amode = SP_A_WINDOW;
-  if (amode == SP_A_REG && g.a_mul == 1.0f && ((uintptr_t)g.A & 15) == 0) {
-    if (g.a_scale == nullptr) amode = SP_A_F32;
-    else if (((uintptr_t)g.a_scale & 15) == 0 && (kSpTile[pl.cfg].bm() - 1) / g.hw + 2 <= 8) amode = SP_A_F32_MUL;
-  }
+  return g;
+}
+
+SpPath gemm_sp_path(const GemmArgs& a, const SpPlan& pl) {
+  SpPath p;
+  p.cfg = pl.cfg, p.amode = sp_amode_of(a, pl), p.epi = sp_epi_of(sp_dev_of(a, pl));
+  p.ring = p.amode == SP_A_WINDOW ? sp_window_ring(kSpTile[pl.cfg], a.Wd, (long)pl.tiles_m * pl.tiles_n) : kSpRing;
+  return p;
+}
+
+void gemm_sp_launch(const GemmArgs& a, const SpPlan& pl, hipStream_t s) {
+  SpDev g = sp_dev_of(a, pl);
+  const int amode = sp_amode_of(a, pl);
   if (stamps_on() && gemm_profile_enabled()) {
     const int tiles = pl.tiles_m * pl.tiles_n;
     long* buf = nullptr;

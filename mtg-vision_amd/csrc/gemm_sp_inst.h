@@ -18,14 +18,6 @@ void sp_launch_one(const SpDev& g, hipStream_t s) {
   hipLaunchKernelGGL(kern, dim3((unsigned)(g.tiles_m * g.tiles_n)), dim3(64 * T.waves()), lds, s, g);
 }
 
-// the compile-time epilogue shape of a launch (gemm_sp_kernel.h, EPI), or SP_EPI_ARGS when only the generic one fits
-int sp_epi_of(const SpDev& g) {
-  if (g.W2 != nullptr) return SP_EPI_CHAIN;
-  if (g.remap || g.N % 4 != 0) return SP_EPI_ARGS;
-  return (g.out_fmt == 1 ? SP_EPI_SP8_OUT : SP_EPI_F32) | (g.res != nullptr ? (g.res_fmt == 1 ? SP_EPI_RES_SP8 : SP_EPI_RES_F32) : 0) |
-         (g.grn_part != nullptr ? SP_EPI_GRN : 0);
-}
-
 // launches the instance whose EPI equals `epi` if it is one of those listed, the generic one otherwise
 template <int ID, int AMODE, int ACT>
 void sp_pick(const SpDev& g, int epi, hipStream_t s) {

@@ -107,6 +107,14 @@ struct SpDev {
   int o_off2 = 0, out_fmt2 = 0, act2 = 0, N2 = 0;
 };
 
+// the compile-time epilogue shape of a launch (EPI below), or SP_EPI_ARGS when only the generic one fits
+inline int sp_epi_of(const SpDev& g) {
+  if (g.W2 != nullptr) return SP_EPI_CHAIN;
+  if (g.remap || g.N % 4 != 0) return SP_EPI_ARGS;
+  return (g.out_fmt == 1 ? SP_EPI_SP8_OUT : SP_EPI_F32) | (g.res != nullptr ? (g.res_fmt == 1 ? SP_EPI_RES_SP8 : SP_EPI_RES_F32) : 0) |
+         (g.grn_part != nullptr ? SP_EPI_GRN : 0);
+}
+
 typedef const __attribute__((address_space(1))) void* sp_gptr;
 typedef __attribute__((address_space(3))) void* sp_lptr;
 

@@ -47,6 +47,23 @@ class DetectorCfg(C.Structure):
     ]
 
 
+class ConvEx(C.Structure):
+    """mtgv_conv_ex: one conv launch as the detector describes it (test surface)"""
+
+    _fields_ = (
+        [("x", c_vp)]
+        + [(k, c_i32) for k in ("n", "h", "w", "x_ct", "x_co", "cin", "x_fmt")]
+        + [("wt", c_vp), ("bias", c_vp)]
+        + [(k, c_i32) for k in ("cout", "kh", "kw", "stride", "pad", "act")]
+        + [("out", c_vp)]
+        + [(k, c_i32) for k in ("out_ct", "out_co", "out_fmt")]
+        + [("res", c_vp)]
+        + [(k, c_i32) for k in ("res_ct", "res_co", "res_fmt", "os", "oy", "ox", "os_nq")]
+        + [("w2", c_vp), ("bias2", c_vp), ("cout2", c_i32), ("act2", c_i32), ("out2", c_vp)]
+        + [(k, c_i32) for k in ("out2_ct", "out2_co", "out2_fmt")]
+    )
+
+
 # name -> (restype, argtypes); every symbol include/mtgv.h declares
 SIGNATURES = {
     "mtgv_last_error": (C.c_char_p, []),
@@ -116,6 +133,7 @@ SIGNATURES = {
     "mtgv_op_last_grn_layout": (C.c_int, [c_vp, c_vp]),
     "mtgv_op_linear_ex": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mtgv_op_conv2d": (C.c_int, [c_vp, c_vp, c_vp, c_vp] + [c_i32] * 10 + [c_vp]),
+    "mtgv_op_conv2d_ex": (C.c_int, [C.POINTER(ConvEx), C.POINTER(c_i32), c_vp]),
     "mtgv_op_layernorm": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_f32, c_vp]),
     "mtgv_op_dwconv7": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "mtgv_op_block": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32] + [c_vp] * 10 + [c_vp, c_vp]),
