@@ -400,6 +400,27 @@ typedef struct {
 /* path, unless NULL, receives {tile configuration, A mode, epilogue id, ring depth} of the launch that ran (the
  * values of gemm_sp_cfg.h); configuration -1 (the rest 0): the convert-on-load kernel. */
 MTGV_API int mtgv_op_conv2d_ex(const mtgv_conv_ex* d, int32_t* path, void* stream);
+/* The detector's prototype branch behind cv1 (Detector::proto runs the same function): ConvTranspose2d(k2, s2, bias) ->
+ * cv2 (3x3, BN folded, SiLU) -> cv3 (1x1, BN folded, SiLU), c -> c -> c -> nm channels.  pr1 is an SP8 view of n images of
+ * h x w pixels; protos an f32 view of (2 h, 2 w) pixels.  Weights are host pointers: wt (c, c, 2, 2) and bt (c) as
+ * ConvTranspose2d stores them, w2 [c][3][3][c], w3 [nm][c].  fold != 0: the ConvTranspose folded into cv2, four 2x2 phase
+ * convs over pr1 (where the kernel has the launch; *folded says whether it ran); fold == 0: the layers as launches of
+ * their own.  f16x3 operand mode only; synchronises the stream before it returns. */
+typedef struct {
+  const void* pr1;
+  int32_t n, h, w, pr1_ct, pr1_co, c;
+  const float *wt, *bt, *w2, *b2, *w3, *b3;
+  int32_t nm;
+  void* protos;
+  int32_t protos_ct, protos_co;
+  int32_t fold;
+} mtgv_proto_tail;
+MTGV_API int mtgv_op_proto_tail(const mtgv_proto_tail* d, int32_t* folded, void* stream);
+/* The weights of that fold, on the host: we [4 (phase 2 a + b)][cout][2][2][c] and bias9 [9 (3 row class + column class;
+ * 0 first, 1 inner, 2 last)][cout] from wt (c, mid, 2, 2), bt (mid), w2 [cout][3][3][mid], b2 [cout].  Sums in double,
+ * rounded to float once.  Needs no device. */
+MTGV_API int mtgv_op_proto_fold_compose(const float* wt_host, const float* bt_host, const float* w2_host, const float* b2_host, int32_t c,
+                                        int32_t mid, int32_t cout, float* we_host, float* bias9_host);
 MTGV_API int mtgv_op_layernorm(const float* x_dev, const float* w_dev, const float* b_dev, float* out_dev, int64_t rows,
                                int32_t c, float eps, void* stream);
 /* depthwise 7x7 pad 3; weight (49, c) tap-major */

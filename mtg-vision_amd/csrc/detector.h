@@ -32,6 +32,38 @@ struct View {
   }
 };
 
+// ---- Proto behind cv1: ConvTranspose2d(k2, s2, bias) -> cv2 (3x3 + BN + SiLU) -> cv3 (1x1 + BN + SiLU) ----
+// There is no activation between the ConvTranspose and cv2, so the two are one linear map of the low-resolution map:
+// output pixel (2i + a, 2j + b) of cv2 reads the 2x2 neighbourhood pr1[i + a - 1 .. i + a][j + b - 1 .. j + b] with
+// weights that depend on the phase (a, b) only,
+//   We[a, b][o][dy][dx][c] = sum over (ty, kh) in S(a, dy), (tx, kw) in S(b, dx), m of W2[o][ty][tx][m] * Wt[c][m][kh][kw]
+//   S(a, dy) = {(ty, kh): ty in 0..2, r = a + ty - 1, floor(r / 2) - (a - 1) == dy, kh = r mod 2}
+// and a bias that depends on which of cv2's 3x3 taps lie inside the upsampled frame (an upsampled pixel is outside
+// exactly when its low-resolution source is, so pr1's own zero padding is cv2's):
+//   bias9[3 rc + cc][o] = b2[o] + sum over taps (ty, tx) inside of W2[o][ty][tx][:] . bt,
+//   rc = 0 first row (ty = 0 outside), 1 inner, 2 last row (ty = 2 outside); cc likewise for columns.
+// Host code: wt [c][mid][2][2] and bt [mid] as ConvTranspose2d stores them, w2 [cout][3][3][mid] BN-folded, b2 [cout];
+// we [4 (phase 2a + b)][cout][2][2][c], bias9 [9][cout].  Sums in double, rounded to float once.
+void proto_fold_compose(const float* wt, const float* bt, const float* w2, const float* b2, int c, int mid, int cout, float* we,
+                        float* bias9);
+struct ProtoTailW {
+  ConvW up[4], up_all;       // the ConvTranspose as four phase matrices [mid][c], and stacked (kh, kw, o) for one launch
+  ConvW cv2, cv3;
+  ConvW fold[4];             // proto_fold_compose's phases as 2x2 convs [cout][2][2][c] without bias; w == nullptr: no fold
+  float* fold_bias = nullptr;  // [9][cout]
+};
+// Device copies (registered B operands, operand_registry.h) of everything above from the host ConvTranspose parameters
+// and the uploaded cv2 / cv3; the fold where its launches exist: c, mid, cout of cv2 equal and a chain tile's width,
+// cv3.cout % 32 == 0 and <= that width.  Allocations are appended to `allocs` (the caller frees and unregisters them).
+ProtoTailW proto_tail_weights(const float* wt, const float* bt, int c, int mid, const ConvW& cv2, const ConvW& cv3,
+                              std::vector<float*>& allocs);
+// The launches behind cv1: with `fold` (SP8 activations and fold weights present) four phase launches pr1 -> protos
+// (gemm_sp_kernel.h, EPI 96), pr2 and pr3 untouched; otherwise ConvTranspose pr1 -> pr2 (one launch, or four with
+// MTGV_PROTO_UP1=0 / f32 activations), then cv2 + cv3 as a chained pair (or two launches) pr2 -> (pr3) -> protos.
+// Returns whether the folded form ran.
+bool proto_tail_launch(const ProtoTailW& w, const View& pr1, const View& pr2, const View& pr3, const View& protos, int n, bool fold,
+                       hipStream_t s);
+
 class Detector {
  public:
   explicit Detector(const mtgv_detector_cfg& cfg);
@@ -121,8 +153,7 @@ class Detector {
   // head_first_: the first 3x3 convs of the branches that read the level's features, stacked (v8: box, class and
   // coefficient; v11: box and coefficient)
   ConvW head_first_[3], head_box2_[3], head_cls2_[3], head_coef2_[3], head_box3_[3], head_cls3_[3], head_coef3_[3];
-  ConvW proto_up_[4];
-  ConvW proto_up_all_;  // the four phase matrices stacked (kh, kw, cout): the ConvTranspose as one launch (GemmArgs::os_nq)
+  ProtoTailW proto_w_;  // the prototype branch behind cv1
 
   // activations (arena)
   DevBuf arena_;

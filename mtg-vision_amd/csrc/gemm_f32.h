@@ -87,10 +87,27 @@ struct GemmArgs {
   const float* ln_w = nullptr;
   const float* ln_b = nullptr;
   float ln_eps = 0.f;
+
+  // (LDS-DMA kernel only; appended: the convert-on-load kernel takes this struct as its argument and reads none of these)
+  // Asymmetric padding of the tap gather: rows of zero padding above / columns left of the image, < 0 = same as pad.
+  // The padding below and right follows from OH / OW: taps outside the image read zeros.
+  int pad_h = -1, pad_w = -1;
+  // Chained 1x1 in its phase form (gemm_sp_kernel.h, EPI 96): Out2's rows go through the output mapping above (os, oy,
+  // ox, OH2, OW2) and the first layer's bias of a row is bias_tab[3 * r + c][N], r / c = 0 first, 1 inner, 2 last row /
+  // column of the OH2 x OW2 grid (bias stays null).  One output phase of a ConvTranspose2d(k2, s2) folded into the 3x3
+  // conv behind it (Detector::proto).
+  const float* bias_tab = nullptr;
+  // algorithmic FLOPs the launch profiler credits this launch with besides its own 2 M N K (+ the chained layer's): a
+  // launch that stands for more arithmetic than it runs (folded layers)
+  double xflops = 0.0;
 };
 
 // A is gathered through a window (anything but a dense 1x1 / linear)
-inline bool is_conv(const GemmArgs& a) { return !(a.KH == 1 && a.KW == 1 && a.stride == 1 && a.stride_w <= 1 && a.pad == 0); }
+inline int conv_pad_h(const GemmArgs& a) { return a.pad_h >= 0 ? a.pad_h : a.pad; }
+inline int conv_pad_w(const GemmArgs& a) { return a.pad_w >= 0 ? a.pad_w : a.pad; }
+inline bool is_conv(const GemmArgs& a) {
+  return !(a.KH == 1 && a.KW == 1 && a.stride == 1 && a.stride_w <= 1 && a.pad == 0 && conv_pad_h(a) == 0 && conv_pad_w(a) == 0);
+}
 // output row m is scattered to another grid (orow != m)
 inline bool is_remap(const GemmArgs& a) { return !(a.os == 1 && a.oy == 0 && a.ox == 0 && a.OH2 == a.OH && a.OW2 == a.OW); }
 

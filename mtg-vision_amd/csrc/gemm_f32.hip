@@ -289,7 +289,7 @@ void gemm_launch(const GemmArgs& args, hipStream_t s) {
     a.grn_unit_rows = l.unit_rows;
   }
   if (sp.cfg >= 0) {
-    prof_begin(a, pl, s, 1, g_prof.on ? gemm_sp_fill_bytes(a, sp) : 0.0);
+    prof_begin(a, pl, s, 1, g_prof.on ? gemm_sp_fill_bytes(a, sp) : 0.0, -1.0, a.xflops);
     gemm_sp_launch(a, sp, s);
     prof_end(s);
     return;
@@ -297,6 +297,8 @@ void gemm_launch(const GemmArgs& args, hipStream_t s) {
 
   MTGV_CHECK(a.os_nq == 0, ERR_INVALID, "gemm: the grouped scatter epilogue (os_nq) exists on the LDS-DMA kernel only");
   MTGV_CHECK(a.W2 == nullptr, ERR_INVALID, "gemm: the chained 1x1 exists on the LDS-DMA kernel only");
+  MTGV_CHECK(conv_pad_h(a) == a.pad && conv_pad_w(a) == a.pad && a.bias_tab == nullptr, ERR_INVALID,
+             "gemm: asymmetric padding and the bias table exist on the LDS-DMA kernel only");
   GemmDev g;
   g.a = a;
   if (gemm_precision() == GEMM_PREC_F16X3 && g.a.W_split == nullptr && a.strideW == 0)

@@ -74,7 +74,7 @@ bool window_conv_on() {
 // the window conv (SP_A_WINDOW) takes this launch on the plan's tile
 bool window_conv_fits(const GemmArgs& a, const SpPlan& pl) {
   const SpTile& k = kSpTile[pl.cfg];
-  if (!(window_conv_on() && a.KH == 3 && a.KW == 3 && a.stride == 1 && a.pad == 1 && a.stride_w <= 0 && a.Cin % k.kps() == 0 &&
+  if (!(window_conv_on() && a.KH == 3 && a.KW == 3 && a.stride == 1 && conv_pad_h(a) == 1 && conv_pad_w(a) == 1 && a.stride_w <= 0 && a.Cin % k.kps() == 0 &&
         a.OH == a.H && a.OW == a.Wd))
     return false;
   return sp_window_fits(k, a.Wd);
@@ -90,12 +90,23 @@ bool gemm_sp_takes_sp8(const float* W, int M, int N, int K, int lda, int c_off) 
 
 // chained 1x1: SP8 conv input (SP_A_CONV / SP_A_WINDOW: the only ones with SP_EPI_CHAIN instances, gemm_sp_inst.h), SiLU
 // between the layers, the whole output row in one tile of a configuration that chains (sp_chain_cfg), plain epilogue
-// otherwise
+// otherwise.  Phase form (bias_tab, SP_EPI_CHAIN_PHASE: instances on the tap gather only): Out2's rows scattered to
+// phase (oy, ox) of the os-times larger grid, no bias vector.
 static int chain_cfg(const GemmArgs& a) {
   if (a.W2 == nullptr || a.Out2 == nullptr || !is_conv(a)) return -1;
   if (!(gemm_sp_active() && a.a_fmt == 1 && a.act == ACT_SILU && a.res == nullptr && a.grn_part == nullptr && a.topk == 0 && a.batch == 1 &&
-        a.os == 1 && a.os_nq == 0 && a.OH2 == a.OH && a.OW2 == a.OW && a.a_scale == nullptr && a.ln_w == nullptr))
+        a.os_nq == 0 && a.a_scale == nullptr && a.ln_w == nullptr))
     return -1;
+  if (a.bias_tab == nullptr) {
+    if (!(a.os == 1 && a.OH2 == a.OH && a.OW2 == a.OW)) return -1;
+  } else {
+    if (!(a.bias == nullptr && a.os >= 1 && a.oy >= 0 && a.oy < a.os && a.ox >= 0 && a.ox < a.os && a.OH2 == a.OH * a.os && a.OW2 == a.OW * a.os &&
+          ((uintptr_t)a.bias_tab & 15) == 0))
+      return -1;
+    SpPlan p;
+    p.cfg = sp_chain_cfg(a.N);
+    if (p.cfg < 0 || window_conv_fits(a, p)) return -1;  // (a 3x3 / pad 1 conv would take the window: no phase instance there)
+  }
   if (sp_chain_cfg(a.N) < 0 || a.N2 <= 0 || a.N2 % 32 != 0 || a.N2 > a.N) return -1;
   if (a.K % 8 != 0 || a.c_total % 8 != 0 || a.c_off % 8 != 0 || a.ldo2 % 4 != 0 || a.o_off2 % 4 != 0 || ((uintptr_t)a.Out2 & 15) != 0) return -1;
   if (a.out_fmt2 == 1 && (a.ldo2 % 8 != 0 || a.o_off2 % 8 != 0)) return -1;
@@ -295,7 +306,7 @@ static SpDev sp_dev_of(const GemmArgs& a, const SpPlan& pl) {
   g.tiles_m = pl.tiles_m, g.tiles_n = pl.tiles_n;
   g.cand_s = a.cand_s, g.cand_i = a.cand_i, g.topk = a.topk;
   g.act = a.act;
-  g.H = a.H, g.Wd = a.Wd, g.Cin = a.Cin, g.KW = a.KW, g.stride = a.stride, g.pad = a.pad, g.OH = a.OH, g.OW = a.OW;
+  g.H = a.H, g.Wd = a.Wd, g.Cin = a.Cin, g.KW = a.KW, g.stride = a.stride, g.pad = conv_pad_h(a), g.pad_w = conv_pad_w(a), g.OH = a.OH, g.OW = a.OW;
   g.d_ohw = make_fastdiv((uint32_t)(a.OH * a.OW));
   g.d_ow = make_fastdiv((uint32_t)a.OW);
   g.d_cin = make_fastdiv((uint32_t)(a.Cin > 0 ? a.Cin : 1));
@@ -306,6 +317,7 @@ static SpDev sp_dev_of(const GemmArgs& a, const SpPlan& pl) {
     MTGV_CHECK(operand_sp8(a.W2, a.N, &g.W2, &g.wscale2), ERR_RUNTIME, "gemm_sp: second-layer weights lost their SP8 copy");
     g.bias2 = a.bias2, g.Out2 = a.Out2, g.ldo2 = a.ldo2, g.o_off2 = a.o_off2, g.out_fmt2 = a.out_fmt2;
     g.act2 = a.act2, g.N2 = a.N2;
+    g.bias_tab = a.bias_tab;
   }
   g.nq = a.os_nq;
   g.d_nq = make_fastdiv((uint32_t)(a.os_nq > 0 ? a.os_nq : 1)), g.d_os = make_fastdiv((uint32_t)(a.os > 0 ? a.os : 1));

@@ -78,7 +78,9 @@ enum SpEpi : int {
   SP_EPI_GRN = 8,      //       + GRN sums (pwconv1)
   SP_EPI_TOPK = 16,    // fused top-k
   SP_EPI_CHAIN = 32,   // chained 1x1
+  SP_EPI_CHAIN_PHASE = 96,  // chained 1x1 + remapped Out2 rows + first-layer bias per row from a nine-class border table
 };
+constexpr bool sp_epi_chains(int epi) { return epi == SP_EPI_CHAIN || epi == SP_EPI_CHAIN_PHASE; }
 constexpr int SP_ACT_ARGS = -1;  // ACT: activation read from the arguments
 
 // ---- LDS of a launch ----
@@ -125,7 +127,7 @@ constexpr size_t sp_launch_lds(const SpTile& t, int amode, int epi, int nst, int
     const size_t win = sp_window_bytes(t, Wd) + lds, stage = (size_t)t.waves() * sp_staging_wave(t);
     lds = win > stage ? win : stage;
   }
-  if (epi == SP_EPI_CHAIN && lds < sp_chain_bytes(t, sp_chain_max_n())) lds = sp_chain_bytes(t, sp_chain_max_n());
+  if (sp_epi_chains(epi) && lds < sp_chain_bytes(t, sp_chain_max_n())) lds = sp_chain_bytes(t, sp_chain_max_n());
   return lds;
 }
 

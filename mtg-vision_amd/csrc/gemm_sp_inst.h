@@ -14,14 +14,14 @@ void sp_launch_one(const SpDev& g, hipStream_t s) {
   }
   const size_t lds = sp_launch_lds(T, AMODE, EPI, NST, g.Wd);
   constexpr auto kern = gemm_sp_kernel<T.wm, T.wn, T.tm, T.tn, T.ks, NST, AMODE, ACT, EPI>;
-  lds_opt_in<kern>(lds, (AMODE == SP_A_WINDOW || EPI == SP_EPI_CHAIN) ? 160 * 1024 : (int)lds);
+  lds_opt_in<kern>(lds, (AMODE == SP_A_WINDOW || sp_epi_chains(EPI)) ? 160 * 1024 : (int)lds);
   hipLaunchKernelGGL(kern, dim3((unsigned)(g.tiles_m * g.tiles_n)), dim3(64 * T.waves()), lds, s, g);
 }
 
 // launches the instance whose EPI equals `epi` if it is one of those listed, the generic one otherwise
 template <int ID, int AMODE, int ACT>
 void sp_pick(const SpDev& g, int epi, hipStream_t s) {
-  MTGV_CHECK(epi != SP_EPI_CHAIN, ERR_RUNTIME, "gemm_sp: no chained-1x1 instance for A mode %d in configuration %d", AMODE, ID);
+  MTGV_CHECK(!sp_epi_chains(epi), ERR_RUNTIME, "gemm_sp: no chained-1x1 instance for A mode %d in configuration %d", AMODE, ID);
   sp_launch_one<ID, AMODE, ACT, SP_EPI_ARGS>(g, s);
 }
 template <int ID, int AMODE, int ACT, int E0, int... ES>
@@ -34,10 +34,13 @@ void sp_pick(const SpDev& g, int epi, hipStream_t s) {
 constexpr int SP8_RES = SP_EPI_SP8_OUT | SP_EPI_RES_SP8;
 
 // convs (SP_A_CONV / SP_A_WINDOW): SiLU with the detector's epilogues - and the chained 1x1 on the tiles that chain
-// (sp_tile_chains) - get kernels of their own
+// (sp_tile_chains) - get kernels of their own; the phase form of the chain (Proto's folded ConvTranspose + cv2: 2x2 taps,
+// never a window conv) on the tap gather only
 template <int ID, int AMODE>
 void sp_pick_conv(const SpDev& g, int epi, hipStream_t s) {
   if (g.act != ACT_SILU) sp_pick<ID, AMODE, SP_ACT_ARGS>(g, epi, s);
+  else if constexpr (sp_tile_chains(kSpTile[ID]) && AMODE == SP_A_CONV)
+    sp_pick<ID, AMODE, ACT_SILU, SP_EPI_SP8_OUT, SP8_RES, SP_EPI_CHAIN, SP_EPI_CHAIN_PHASE>(g, epi, s);
   else if constexpr (sp_tile_chains(kSpTile[ID])) sp_pick<ID, AMODE, ACT_SILU, SP_EPI_SP8_OUT, SP8_RES, SP_EPI_CHAIN>(g, epi, s);
   else sp_pick<ID, AMODE, ACT_SILU, SP_EPI_SP8_OUT, SP8_RES>(g, epi, s);
 }

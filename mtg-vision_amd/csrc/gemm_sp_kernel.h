@@ -24,6 +24,10 @@
 //                        layer's output never goes to HBM (detector: C2f cv1 behind a stride-2 conv, Proto cv3 behind
 //                        cv2, the heads' final 1x1 behind their 3x3).  Same SP8 values, same product order as two
 //                        launches: bit-identical.
+//   EPI 96 (chain, phase form)  the chain with Out2's rows sent through the output row remap and the first layer's bias
+//                        read per row from a table of nine border classes: one output phase of ConvTranspose2d(k2, s2)
+//                        folded into the 3x3 conv behind it (detector: Proto), a 2x2 tap gather over the low-resolution
+//                        map whose bias depends on which of the 3x3 taps fell into the padding.  AMODE 2 only.
 //   A, AMODE 6 (HI16)    A and B are plain fp16 rows (the hi halves only, 2 bytes per element): a stage is 64 k, one MFMA
 //                        per k16 step.  The approximate first pass of the bank match (match.hip); K % 64 == 0.
 //   A, AMODE 1 (REG)     f32 rows: global -> VGPR (issued before the stage's MFMAs) -> optional per-image multiplier
@@ -105,11 +109,16 @@ struct SpDev {
   float* Out2 = nullptr;
   long ldo2 = 0;
   int o_off2 = 0, out_fmt2 = 0, act2 = 0, N2 = 0;
+  // (appended: the fields above keep their kernel-argument offsets)
+  int pad_w = 0;                     // AMODE 2: columns of zero padding left of the image (pad: rows above it)
+  // SP_EPI_CHAIN_PHASE: the first layer's bias of a row is bias_tab[class][N], class = 3 * {0 first, 1 inner, 2 last row of
+  // the OH2 x OW2 grid the row is written to} + the same for its column; Out2 rows go through the output row remap
+  const float* bias_tab = nullptr;
 };
 
 // the compile-time epilogue shape of a launch (EPI below), or SP_EPI_ARGS when only the generic one fits
 inline int sp_epi_of(const SpDev& g) {
-  if (g.W2 != nullptr) return SP_EPI_CHAIN;
+  if (g.W2 != nullptr) return g.bias_tab != nullptr ? SP_EPI_CHAIN_PHASE : SP_EPI_CHAIN;
   if (g.remap || g.N % 4 != 0) return SP_EPI_ARGS;
   return (g.out_fmt == 1 ? SP_EPI_SP8_OUT : SP_EPI_F32) | (g.res != nullptr ? (g.res_fmt == 1 ? SP_EPI_RES_SP8 : SP_EPI_RES_F32) : 0) |
          (g.grn_part != nullptr ? SP_EPI_GRN : 0);
@@ -198,7 +207,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
         const uint32_t oh = fdiv(rem, g.d_ow);
         const uint32_t ow = rem - oh * (uint32_t)g.OW;
         cih0[u] = (int)oh * g.stride - g.pad;
-        ciw0[u] = (int)ow * g.stride - g.pad;
+        ciw0[u] = (int)ow * g.stride - g.pad_w;
         csrc[u] = g.A + (((long)img * g.H + cih0[u]) * g.Wd + ciw0[u]) * g.a_rowb + g.a_offb + slot * 16;
         src[u] = g.A + (long)img * g.H * g.Wd * g.a_rowb + g.a_offb + (slot & 1) * 16;
       } else {
@@ -689,8 +698,10 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
   __builtin_amdgcn_s_barrier();  // every wave is done with the ring: it becomes the store staging area
   const long st2 = g.stamps != nullptr ? (long)__builtin_amdgcn_s_memtime() : 0;
 
-  if constexpr (EPI == SP_EPI_CHAIN) {
-    static_assert(EPI != SP_EPI_CHAIN || (sp_tile_chains(T) && !HI16), "chained 1x1: one wave holds whole rows");
+  if constexpr (sp_epi_chains(EPI)) {
+    static_assert(!sp_epi_chains(EPI) || (sp_tile_chains(T) && !HI16), "chained 1x1: one wave holds whole rows");
+    constexpr bool PHASE = EPI == SP_EPI_CHAIN_PHASE;
+    static_assert(!PHASE || AMODE == SP_A_CONV, "the phase form reads the conv geometry");
     // LDS after the main loop: [NW x 4 KB: one column block of each wave's accumulators][NW x TN x 4 KB: each wave's A2
     // stages, row-major 128-byte rows with the main loop's swizzle][TN stages x N2 rows x 128 B: W2]
     constexpr int CB = kSpSlab;
@@ -707,6 +718,23 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
     }
     const int slot = lane & 7, lrow = lane >> 3;
     const int mw0 = m0 + wm * 32;
+    // PHASE: where each of this lane's four rows goes in Out2, and its border class
+    long orow2[4];
+    int bcls[4];
+    if constexpr (PHASE) {
+#pragma unroll
+      for (int it = 0; it < 4; ++it) {
+        int m = mw0 + it * 8 + lrow;
+        m = m < g.M ? m : g.M - 1;
+        const uint32_t img = fdiv((uint32_t)m, g.d_ohw);
+        const uint32_t rem = (uint32_t)m - img * (uint32_t)(g.OH * g.OW);
+        const uint32_t oh = fdiv(rem, g.d_ow);
+        const uint32_t ow = rem - oh * (uint32_t)g.OW;
+        const int y = (int)oh * g.os + g.oy, x = (int)ow * g.os + g.ox;
+        orow2[it] = ((long)img * g.OH2 + y) * g.OW2 + x;
+        bcls[it] = (y == 0 ? 0 : (y == g.OH2 - 1 ? 2 : 1)) * 3 + (x == 0 ? 0 : (x == g.OW2 - 1 ? 2 : 1));
+      }
+    }
     if (wave_active) {
 #pragma unroll
       for (int j = 0; j < TN; ++j) {
@@ -721,9 +749,11 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
         for (int it = 0; it < 4; ++it) {
           const int row = it * 8 + lrow;
           const sp_f4 raw = *reinterpret_cast<const sp_f4*>(stg1 + row * 128 + ((slot ^ lrow) << 4));
+          sp_f4 br = b1;  // PHASE: the row's own bias (the launch has no bias vector)
+          if constexpr (PHASE) br = *reinterpret_cast<const sp_f4*>(g.bias_tab + bcls[it] * g.N + n);
           sp_f4 v;
 #pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = activate(__builtin_fmaf(raw[e], w1[e] * g.a_unmul, b1[e]));
+          for (int e = 0; e < 4; ++e) v[e] = activate(__builtin_fmaf(raw[e], w1[e] * g.a_unmul, br[e]));
           // this lane's 16-byte piece of the row's SP8 form (even quads: the chunk's hi halves, odd quads: its lo halves)
           *reinterpret_cast<sp_f4*>(a2 + j * CB + row * 128 + ((slot ^ ((row >> 1) & 7)) << 4)) =
               __builtin_bit_cast(sp_f4, sp8_piece_from_quad(v, slot));
@@ -784,7 +814,11 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
         }
         sp_f4 piece = v;
         if (g.out_fmt2 == 1) piece = __builtin_bit_cast(sp_f4, sp8_piece_from_quad(v, slot));  // every lane takes part
-        if (m < g.M) *reinterpret_cast<sp_f4*>(g.Out2 + (long)m * g.ldo2 + g.o_off2 + n) = piece;
+        if constexpr (PHASE) {
+          if (m < g.M) *reinterpret_cast<sp_f4*>(g.Out2 + orow2[it] * g.ldo2 + g.o_off2 + n) = piece;
+        } else {
+          if (m < g.M) *reinterpret_cast<sp_f4*>(g.Out2 + (long)m * g.ldo2 + g.o_off2 + n) = piece;
+        }
       }
     }
     return;

@@ -64,6 +64,17 @@ class ConvEx(C.Structure):
     )
 
 
+class ProtoTail(C.Structure):
+    """mtgv_proto_tail: the detector's prototype branch behind cv1 (test surface)"""
+
+    _fields_ = (
+        [("pr1", c_vp)]
+        + [(k, c_i32) for k in ("n", "h", "w", "pr1_ct", "pr1_co", "c")]
+        + [(k, c_vp) for k in ("wt", "bt", "w2", "b2", "w3", "b3")]
+        + [("nm", c_i32), ("protos", c_vp), ("protos_ct", c_i32), ("protos_co", c_i32), ("fold", c_i32)]
+    )
+
+
 # name -> (restype, argtypes); every symbol include/mtgv.h declares
 SIGNATURES = {
     "mtgv_last_error": (C.c_char_p, []),
@@ -134,6 +145,8 @@ SIGNATURES = {
     "mtgv_op_linear_ex": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mtgv_op_conv2d": (C.c_int, [c_vp, c_vp, c_vp, c_vp] + [c_i32] * 10 + [c_vp]),
     "mtgv_op_conv2d_ex": (C.c_int, [C.POINTER(ConvEx), C.POINTER(c_i32), c_vp]),
+    "mtgv_op_proto_tail": (C.c_int, [C.POINTER(ProtoTail), C.POINTER(c_i32), c_vp]),
+    "mtgv_op_proto_fold_compose": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mtgv_op_layernorm": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_f32, c_vp]),
     "mtgv_op_dwconv7": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "mtgv_op_block": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32] + [c_vp] * 10 + [c_vp, c_vp]),
