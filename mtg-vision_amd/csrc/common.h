@@ -54,6 +54,8 @@ static inline int guarded(F&& f) {
   }
 }
 
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
 // ---- exact unsigned division by a runtime constant (n * d < 2^40) ----
 struct FastDiv {
   uint64_t mul;  // ceil(2^40 / d)

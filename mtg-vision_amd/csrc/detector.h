@@ -5,11 +5,18 @@
 #include "gemm_f32.h"
 #include "mtgv.h"
 
+#include <algorithm>
 #include <map>
+#include <math.h>
 #include <string>
 #include <vector>
 
 namespace mtgv {
+
+// ultralytics' width and depth scaling at scale "n": channels c * 0.25 rounded up to a multiple of 8, repeats n * 0.33
+static inline int make_div8(double v) { return (int)(ceil(v / 8.0) * 8.0); }
+static inline int chn(int c) { return make_div8(std::min(c, 1024) * 0.25); }
+static inline int rep(int n) { return n > 1 ? std::max((int)lround(n * 0.33), 1) : n; }
 
 // raw head rows per anchor: [0,64) box logits (4 sides x 16 bins), [64,64+nc) class logits, [68,100) mask coefficients
 static constexpr int RAW_CT = 100, RAW_CLS = 64, RAW_COEF = 68;
@@ -32,7 +39,16 @@ struct View {
   }
 };
 
-// ---- Proto behind cv1: ConvTranspose2d(k2, s2, bias) -> cv2 (3x3 + BN + SiLU) -> cv3 (1x1 + BN + SiLU) ----
+// a constant vector on the device, registered as a B operand (operand_registry.h); row_k > 0: rows of row_k floats.
+// The allocation is appended to `allocs` (the caller frees and unregisters it).
+float* upload_operand(const std::vector<float>& v, int row_k, std::vector<float*>& allocs);
+// the k x k / pad k/2 conv `w` from view `in` to view `out` of n frames (out.H x out.W: the grid the conv enumerates)
+GemmArgs conv_desc(const ConvW& w, const View& in, const View& out, int stride, int act, int n);
+// Conv(w1, SiLU) + 1x1 conv w2 (act2): one chained launch where the kernel takes the pair (SP8 input), else two launches
+void conv_pair_launch(const ConvW& w1, const View& in, const View& mid, int stride, const ConvW& w2, const View& out2, int act2, int n,
+                      hipStream_t s);
+
+// ---- Proto behind cv1 (detector_proto.hip): ConvTranspose2d(k2, s2, bias) -> cv2 (3x3 + BN + SiLU) -> cv3 (1x1 + BN + SiLU) ----
 // There is no activation between the ConvTranspose and cv2, so the two are one linear map of the low-resolution map:
 // output pixel (2i + a, 2j + b) of cv2 reads the 2x2 neighbourhood pr1[i + a - 1 .. i + a][j + b - 1 .. j + b] with
 // weights that depend on the phase (a, b) only,
@@ -87,6 +103,9 @@ class Detector {
   };
   void expect(const std::string& key, std::vector<int> shape);
   void expect_conv_bn(const std::string& prefix, int cout, int cin, int k);
+  void expect_head(const int chs[3]);                               // head + Proto keys on features of chs channels
+  std::pair<double, double> bn_affine(const std::string& prefix, int o) const;  // BatchNorm of channel o: (scale, bias)
+  void free_weights();                                              // unregister and free every uploaded weight
   ConvW fold(const std::string& prefix, int cin_pad = 0);           // Conv+BN
   ConvW plain(const std::string& prefix);                           // Conv2d with bias
   ConvW concat_out(const std::vector<ConvW>& parts);                // stack along cout (same cin and k)

@@ -14,11 +14,6 @@
 
 namespace mtgv {
 
-typedef float f32x4 __attribute__((ext_vector_type(4)));
-
-static int make_div8(double v) { return (int)(ceil(v / 8.0) * 8.0); }
-static int chn(int c) { return make_div8(std::min(c, 1024) * 0.25); }
-
 // ---------------------------------------------------------------------------
 // depthwise 3x3, stride 1, pad 1.  One thread = one pixel x 8 channels.
 // input channel of output channel c: (c / g_size) * g_stride + c % g_size (+ the view's offset) - the positional
@@ -163,19 +158,13 @@ __global__ __launch_bounds__(256) void attn_kernel(const float* __restrict__ qkv
 ConvW Detector::fold_dw(const std::string& p) {
   const Raw& w = raw_.at(p + ".conv.weight");
   const int c = w.shape[0];
-  const auto& g = raw_.at(p + ".bn.weight").data;
-  const auto& b = raw_.at(p + ".bn.bias").data;
-  const auto& mu = raw_.at(p + ".bn.running_mean").data;
-  const auto& var = raw_.at(p + ".bn.running_var").data;
   std::vector<float> wf((size_t)9 * c), bf(c);
   for (int o = 0; o < c; ++o) {
-    const double sc = (double)g[o] / sqrt((double)var[o] + 1e-3);
-    bf[o] = (float)((double)b[o] - (double)mu[o] * sc);
+    const auto [sc, bias] = bn_affine(p, o);
+    bf[o] = (float)bias;
     for (int t = 0; t < 9; ++t) wf[(size_t)t * c + o] = (float)((double)w.data[(size_t)o * 9 + t] * sc);
   }
-  ConvW cw;
-  cw.w = upload(wf), cw.b = upload(bf), cw.cout = c, cw.cin = c, cw.k = 3;
-  return cw;
+  return ConvW{upload(wf), upload(bf), c, c, 3};
 }
 
 void Detector::dwconv(const ConvW& w, const View& in, const View& out, int act, const float* add, int g_size, int g_stride, int n,
@@ -256,35 +245,7 @@ void Detector::build_v11() {
   c3k2(22, c128 + c256, c256, true, 0.5);
 
   const int chs[3] = {c64, c128, c256};
-  const int c2 = std::max(std::max(16, chs[0] / 4), reg_max_ * 4);
-  const int c3 = std::max(chs[0], std::min(cfg_.nc, 100));
-  const int c4 = std::max(chs[0] / 4, nm_);
-  MTGV_CHECK(c2 == 64 && c3 == 64 && c4 == 32, ERR_INVALID, "detector: unexpected head widths");
-  const std::string H = head_;
-  for (int l = 0; l < 3; ++l) {
-    const std::string ls = std::to_string(l);
-    expect_conv_bn(H + ".cv2." + ls + ".0", c2, chs[l], 3);
-    expect_conv_bn(H + ".cv2." + ls + ".1", c2, c2, 3);
-    expect(H + ".cv2." + ls + ".2.weight", {4 * reg_max_, c2, 1, 1});
-    expect(H + ".cv2." + ls + ".2.bias", {4 * reg_max_});
-    // Detect(legacy=False): Sequential(DWConv(x, x, 3), Conv(x, c3, 1)), Sequential(DWConv(c3, c3, 3), Conv(c3, c3, 1)), Conv2d
-    expect_conv_bn(H + ".cv3." + ls + ".0.0", chs[l], 1, 3);
-    expect_conv_bn(H + ".cv3." + ls + ".0.1", c3, chs[l], 1);
-    expect_conv_bn(H + ".cv3." + ls + ".1.0", c3, 1, 3);
-    expect_conv_bn(H + ".cv3." + ls + ".1.1", c3, c3, 1);
-    expect(H + ".cv3." + ls + ".2.weight", {cfg_.nc, c3, 1, 1});
-    expect(H + ".cv3." + ls + ".2.bias", {cfg_.nc});
-    expect_conv_bn(H + ".cv4." + ls + ".0", c4, chs[l], 3);
-    expect_conv_bn(H + ".cv4." + ls + ".1", c4, c4, 3);
-    expect(H + ".cv4." + ls + ".2.weight", {nm_, c4, 1, 1});
-    expect(H + ".cv4." + ls + ".2.bias", {nm_});
-  }
-  expect(H + ".dfl.conv.weight", {1, reg_max_, 1, 1});
-  expect_conv_bn(H + ".proto.cv1", npr_, chs[0], 3);
-  expect(H + ".proto.upsample.weight", {npr_, npr_, 2, 2});
-  expect(H + ".proto.upsample.bias", {npr_});
-  expect_conv_bn(H + ".proto.cv2", npr_, npr_, 3);
-  expect_conv_bn(H + ".proto.cv3", nm_, npr_, 1);
+  expect_head(chs);
 }
 
 // ---------------------------------------------------------------------------

@@ -31,7 +31,7 @@ __device__ __forceinline__ long long cross3(const P2 o, const P2 a, const P2 b) 
 
 // LOGITS = false: `src` is the (n, H, W) uint8 mask.  LOGITS = true: `src` is the (n, H / scale, W / scale) float mask
 // logits of process_mask and a pixel is foreground when their bilinear x`scale` interpolation (align_corners = False) is
-// > 0 - exactly what mask_binarize_kernel (detector.hip) writes, so both paths give the same quads - but the
+// > 0 - exactly what mask_binarize_kernel (detector_kernel.h) writes, so both paths give the same quads - but the
 // full-resolution mask never exists: only output rows / columns near positive logits are evaluated.
 constexpr int QT = 512;  // threads per block
 template <bool LOGITS>

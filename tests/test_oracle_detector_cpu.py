@@ -152,7 +152,7 @@ def test_detector_config_for_state_picks_family_and_nc():
 
 
 def test_byte_over_255_without_a_division_is_the_ieee_quotient():
-    """conv0_u8_kernel (csrc/detector.hip) turns a frame byte u into u / 255 (ultralytics preprocess, img / 255) as
+    """conv0_u8_kernel (csrc/detector_kernel.h) turns a frame byte u into u / 255 (ultralytics preprocess, img / 255) as
     q = u * fl(1/255); q' = fma(fma(-q, 255, u), fl(1/255), q).  Checked here for all 256 bytes against the correctly
     rounded quotient, with the two fused operations evaluated in exact rational arithmetic."""
     from fractions import Fraction
