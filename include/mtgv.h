@@ -228,6 +228,22 @@ MTGV_API int mtgv_nms(const float* pred_dev, int32_t n, int32_t nc, int32_t nm, 
                       int32_t* keep_idx_dev, int32_t* workspace_dev, size_t workspace_bytes, void* stream);
 MTGV_API size_t mtgv_nms_workspace_bytes(int32_t n, int32_t na);
 
+/* Test surface of the segment head's tail.  Raw head rows of the three pyramid levels (strides 8 / 16 / 32), per level
+ * (n, (imgsz / stride)^2, ct) floats, 16-byte aligned: 4 sides x 16 box bins at [0, 64), class logits at [cls, cls + nc),
+ * mask coefficients at [coef, coef + nm); ct, cls and coef multiples of 4.  Anchors count P3's pixels first, then P4's,
+ * then P5's: na = sum of (imgsz / stride)^2. */
+typedef struct mtgv_head_rows {
+  const float *r0, *r1, *r2;
+  int32_t imgsz, ct, cls, coef;
+} mtgv_head_rows;
+/* the detector's decode pass: rows -> pred (n, 4+nc+nm, na) */
+MTGV_API int mtgv_op_decode(const mtgv_head_rows* rows, int32_t n, int32_t nc, int32_t nm, float* pred_dev, void* stream);
+/* NMS straight from the rows (what the detector's forward runs): bit-identical to mtgv_op_decode -> mtgv_nms; the boxes of
+ * candidates only are decoded.  coef_dev (n, max_det, nm) may be null: the kept detections' coefficients, zeros beyond n_det */
+MTGV_API int mtgv_op_nms_raw(const mtgv_head_rows* rows, int32_t n, int32_t nc, int32_t nm, float conf, float iou, int32_t max_det,
+                             float max_wh, int32_t* n_det_dev, float* boxes_dev, float* conf_dev, int32_t* cls_dev, int32_t* keep_idx_dev,
+                             float* coef_dev, int32_t* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* ------------------------------------------------------------------------- */
 /* Mask -> oriented card quad.                                                */
 /* Replaces the host geometry of InstanceSeg._orient                          */

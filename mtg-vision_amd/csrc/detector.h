@@ -3,6 +3,7 @@
 #pragma once
 #include "common.h"
 #include "gemm_f32.h"
+#include "head_decode.h"
 #include "mtgv.h"
 
 #include <algorithm>
@@ -18,8 +19,9 @@ static inline int make_div8(double v) { return (int)(ceil(v / 8.0) * 8.0); }
 static inline int chn(int c) { return make_div8(std::min(c, 1024) * 0.25); }
 static inline int rep(int n) { return n > 1 ? std::max((int)lround(n * 0.33), 1) : n; }
 
-// raw head rows per anchor: [0,64) box logits (4 sides x 16 bins), [64,64+nc) class logits, [68,100) mask coefficients
-static constexpr int RAW_CT = 100, RAW_CLS = 64, RAW_COEF = 68;
+// raw head rows per anchor, four whole 128-byte lines: [0,64) box logits (4 sides x 16 bins), [64,96) mask coefficients,
+// [96,96+nc) class logits; the rest of the 32 columns behind RAW_CLS is the zero padding of the chained class conv
+static constexpr int RAW_CT = 128, RAW_COEF = 64, RAW_CLS = 96;
 
 struct ConvW {
   float* w = nullptr;  // [cout][k][k][cin] BN-folded
@@ -44,9 +46,10 @@ struct View {
 float* upload_operand(const std::vector<float>& v, int row_k, std::vector<float*>& allocs);
 // the k x k / pad k/2 conv `w` from view `in` to view `out` of n frames (out.H x out.W: the grid the conv enumerates)
 GemmArgs conv_desc(const ConvW& w, const View& in, const View& out, int stride, int act, int n);
-// Conv(w1, SiLU) + 1x1 conv w2 (act2): one chained launch where the kernel takes the pair (SP8 input), else two launches
+// Conv(w1, SiLU) + 1x1 conv w2 (act2): one chained launch where the kernel takes the pair (SP8 input), else two launches.
+// xflops: what the launch profiler adds to the pair's 2 M N K (GemmArgs::xflops; negative for zero rows that pad w2).
 void conv_pair_launch(const ConvW& w1, const View& in, const View& mid, int stride, const ConvW& w2, const View& out2, int act2, int n,
-                      hipStream_t s);
+                      hipStream_t s, double xflops = 0.0);
 
 // ---- Proto behind cv1 (detector_proto.hip): ConvTranspose2d(k2, s2, bias) -> cv2 (3x3 + BN + SiLU) -> cv3 (1x1 + BN + SiLU) ----
 // There is no activation between the ConvTranspose and cv2, so the two are one linear map of the low-resolution map:
@@ -107,14 +110,14 @@ class Detector {
   std::pair<double, double> bn_affine(const std::string& prefix, int o) const;  // BatchNorm of channel o: (scale, bias)
   void free_weights();                                              // unregister and free every uploaded weight
   ConvW fold(const std::string& prefix, int cin_pad = 0);           // Conv+BN
-  ConvW plain(const std::string& prefix);                           // Conv2d with bias
+  ConvW plain(const std::string& prefix, int cout_pad = 0);         // Conv2d with bias (cout_pad: zero rows up to that many)
   ConvW concat_out(const std::vector<ConvW>& parts);                // stack along cout (same cin and k)
   float* upload(const std::vector<float>& v, int row_k = 0);  // row_k > 0: a GEMM B operand with rows of row_k floats
   void conv(const ConvW& w, const View& in, const View& out, int stride, int act, const View* res, int n, hipStream_t s);
   // Conv(w1, SiLU) followed by the 1x1 conv w2 (act2) with w1's output consumed on chip (gemm_sp_kernel.h, EPI 32): `mid` is
   // where w1's output would go in two launches (used when the pair cannot be chained: f32 mode, flop counting, shapes)
   void conv_pair(const ConvW& w1, const View& in, const View& mid, int stride, const ConvW& w2, const View& out2, int act2, int n,
-                 hipStream_t s);
+                 hipStream_t s, double xflops = 0.0);
   void c2f(int idx, const View& in, const View& out, int n, hipStream_t s, const ConvW* pre = nullptr, const View* pre_in = nullptr);
   // YOLO11 modules
   ConvW fold_dw(const std::string& prefix);                         // depthwise 3x3 Conv+BN -> weight [9][c], bias [c]
@@ -131,6 +134,8 @@ class Detector {
   void plan_arena(const std::vector<ArenaBuf>& bufs);
   void forward_v11(const uint8_t* frames, int n, int flip, hipStream_t s);
   void forward_v8(const uint8_t* frames, int n, int flip, hipStream_t s);
+  HeadRows head_rows() const;                                       // the arena's raw head rows (head_decode.h)
+  void decode(int n, hipStream_t s);                                // decode_kernel: raw head rows -> pred
   void head_tail(int n, int* n_det, float* boxes, float* conf, int* cls, int* keep_idx, float* mask_logits, int mask_rows,
                  hipStream_t s);
   void conv0(const uint8_t* frames, int n, int flip, hipStream_t s);
@@ -172,6 +177,7 @@ class Detector {
   // head_first_: the first 3x3 convs of the branches that read the level's features, stacked (v8: box, class and
   // coefficient; v11: box and coefficient)
   ConvW head_first_[3], head_box2_[3], head_cls2_[3], head_coef2_[3], head_box3_[3], head_cls3_[3], head_coef3_[3];
+  ConvW head_cls3_pad_[3];  // v8: head_cls3_ with zero rows up to 32 outputs (the chained form of the class branch)
   ProtoTailW proto_w_;  // the prototype branch behind cv1
 
   // activations (arena)
@@ -180,6 +186,8 @@ class Detector {
   int* nms_ws_ = nullptr;
   size_t nms_ws_bytes_ = 0;
   int last_n_ = 0;
+  int pred_n_ = 0;             // frames of the last forward whose `pred` exists (0 after a MTGV_DET_HEAD_DIRECT forward)
+  bool head_direct_ = true;    // MTGV_DET_HEAD_DIRECT of the forward in progress
   int fmt_ = 0;  // activation format of the forward in progress (0 f32, 1 SP8)
   static constexpr int NSIDE = 3;  // 0: prototype branch, 1: P3 head, 2: P4 head
   hipStream_t side_[NSIDE] = {nullptr, nullptr, nullptr};

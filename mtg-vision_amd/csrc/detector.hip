@@ -216,16 +216,18 @@ ConvW Detector::fold(const std::string& p, int cin_pad) {
   return ConvW{upload(wf, k * k * cp), upload(bf), cout, cp, k};
 }
 
-ConvW Detector::plain(const std::string& p) {
+ConvW Detector::plain(const std::string& p, int cout_pad) {
   const Raw& w = raw_.at(p + ".weight");
   const int cout = w.shape[0], cin = w.shape[1], k = w.shape[2];
-  std::vector<float> wf((size_t)cout * k * k * cin);
+  const int co = std::max(cout, cout_pad);
+  std::vector<float> wf((size_t)co * k * k * cin, 0.f), bf(raw_.at(p + ".bias").data);
+  bf.resize(co, 0.f);
   for (int o = 0; o < cout; ++o)
     for (int i = 0; i < cin; ++i)
       for (int kh = 0; kh < k; ++kh)
         for (int kw = 0; kw < k; ++kw)
           wf[(((size_t)o * k + kh) * k + kw) * cin + i] = w.data[(((size_t)o * cin + i) * k + kh) * k + kw];
-  return ConvW{upload(wf, k * k * cin), upload(raw_.at(p + ".bias").data), cout, cin, k};
+  return ConvW{upload(wf, k * k * cin), upload(bf), co, cin, k};
 }
 
 // ConvWs that read the same input stacked along cout, rows and biases in the order given: one launch for all of them
@@ -243,8 +245,8 @@ ConvW Detector::concat_out(const std::vector<ConvW>& parts) {
   return ConvW{upload(w, (int)per), upload(b), (int)b.size(), cin, k};
 }
 
-// Carve the activation arena for max_batch frames: each buffer 256-byte aligned, in table order.  Cleared once: the raw
-// head rows' class padding column (index 67) is never written by a conv.
+// Carve the activation arena for max_batch frames: each buffer 256-byte aligned, in table order.  Cleared once: of the raw
+// head rows' 32 columns behind RAW_CLS, those past the classes are written by the chained class conv only (as zeros).
 void Detector::plan_arena(const std::vector<ArenaBuf>& bufs) {
   auto floats = [&](const ArenaBuf& b) { return ((size_t)cfg_.max_batch * b.h * b.w * b.c + 63) / 64 * 64; };
   size_t total = 0;
@@ -333,6 +335,9 @@ void Detector::finalize() {
     head_coef2_[l] = cw_.at(M + ".1");
     head_box3_[l] = plain(B + ".2");
     head_cls3_[l] = plain(C + ".2");
+    // v8: the class branch's final 1x1 padded to a 32-column block (zero weights and bias past the classes), which the 3x3
+    // before it can chain (gemm_sp_chain_ok wants N2 % 32 == 0)
+    if (!v11()) head_cls3_pad_[l] = plain(C + ".2", 32);
     head_coef3_[l] = plain(M + ".2");
   }
   // DFL weights must be arange(16) (they are a fixed buffer upstream); the decode kernel hard-codes them
@@ -378,7 +383,7 @@ void Detector::conv(const ConvW& w, const View& in, const View& out, int stride,
 }
 
 void conv_pair_launch(const ConvW& w1, const View& in, const View& mid, int stride, const ConvW& w2, const View& out2, int act2, int n,
-                             hipStream_t s) {
+                      hipStream_t s, double xflops) {
   MTGV_CHECK(in.C == w1.cin && mid.C == w1.cout && w2.cin == w1.cout && w2.k == 1 && out2.C == w2.cout, ERR_RUNTIME,
              "detector: conv pair channel mismatch (%d->%d, %d->%d)", w1.cin, w1.cout, w2.cin, w2.cout);
   const bool chain = env_int("MTGV_DET_CHAIN", 1) != 0;  // read per call (A/B in one process); 0: two launches
@@ -386,23 +391,26 @@ void conv_pair_launch(const ConvW& w1, const View& in, const View& mid, int stri
     GemmArgs g = conv_desc(w1, in, mid, stride, ACT_SILU, n);
     g.Out = nullptr;  // only the second layer's output is stored
     g.W2 = w2.w, g.bias2 = w2.b, g.Out2 = out2.p, g.N2 = w2.cout, g.ldo2 = out2.ct, g.o_off2 = out2.co, g.out_fmt2 = out2.fmt, g.act2 = act2;
+    g.xflops = xflops;
     if (gemm_sp_chain_ok(g)) {
       gemm_launch(g, s);
       return;
     }
   }
   gemm_launch(conv_desc(w1, in, mid, stride, ACT_SILU, n), s);
-  gemm_launch(conv_desc(w2, mid, out2, 1, act2, n), s);
+  GemmArgs g2 = conv_desc(w2, mid, out2, 1, act2, n);
+  g2.xflops = xflops;
+  gemm_launch(g2, s);
 }
 
 void Detector::conv_pair(const ConvW& w1, const View& in, const View& mid, int stride, const ConvW& w2, const View& out2, int act2, int n,
-                         hipStream_t s) {
+                         hipStream_t s, double xflops) {
   if (count_flops_ || fmt_ != 1) {
     conv(w1, in, mid, stride, ACT_SILU, nullptr, n, s);
     conv(w2, mid, out2, 1, act2, nullptr, n, s);
     return;
   }
-  conv_pair_launch(w1, in, mid, stride, w2, out2, act2, n, s);
+  conv_pair_launch(w1, in, mid, stride, w2, out2, act2, n, s, xflops);
 }
 
 // C2f: cv1 -> 2 chunks; n bottlenecks (3x3,3x3, +shortcut) each appended; cv2 over the concat
@@ -459,18 +467,40 @@ void Detector::conv0(const uint8_t* frames, int n, int flip, hipStream_t s) {
 }
 
 
-// decode -> NMS -> mask logits of the kept detections
+// head rows of n frames -> pred (n, 4 + nc + nm, na)
+static void decode_launch(const HeadRows& rows, int n, int nc, int nm, float* pred, hipStream_t s) {
+  const int na = head_rows_anchors(rows.imgsz);
+  const long tot = (long)n * na;
+  hipLaunchKernelGGL(decode_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, rows, pred, n, nc, nm, na);
+  HIP_OK(hipGetLastError());
+}
+
+HeadRows Detector::head_rows() const {
+  return HeadRows{v_.at("rawhead0").p, v_.at("rawhead1").p, v_.at("rawhead2").p, cfg_.imgsz, RAW_CT, RAW_CLS, RAW_COEF};
+}
+
+// the raw head rows of the first n frames -> pred
+void Detector::decode(int n, hipStream_t s) {
+  decode_launch(head_rows(), n, cfg_.nc, nm_, v_.at("pred").p, s);
+  pred_n_ = n;
+}
+
+// (decode ->) NMS -> mask logits of the kept detections
 void Detector::head_tail(int n, int* n_det, float* boxes, float* conf, int* cls, int* keep_idx, float* mask_logits, int mask_rows,
                          hipStream_t s) {
   const int S = cfg_.imgsz;
-  const long tot = (long)n * na_;
-  float* const pred = v_.at("pred").p;
   float* const coef = v_.at("coef").p;
-  hipLaunchKernelGGL(decode_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, v_.at("rawhead0").p, v_.at("rawhead1").p,
-                     v_.at("rawhead2").p, pred, n, cfg_.nc, nm_, S, na_);
-  HIP_OK(hipGetLastError());
-  nms_launch(pred, n, cfg_.nc, nm_, na_, cfg_.conf, cfg_.iou, cfg_.max_det, 7680.0f, n_det, boxes, conf, cls, keep_idx, coef,
-             nms_ws_, nms_ws_bytes_, s);
+  if (head_direct_) {
+    // NMS reads the class logits of every anchor, and the box and the coefficients of candidates only, from the head
+    // rows: no pass that decodes every anchor into `pred` (raw() runs it when a caller asks for `pred`)
+    nms_rows_launch(head_rows(), n, cfg_.nc, nm_, cfg_.conf, cfg_.iou, cfg_.max_det, 7680.0f, n_det, boxes, conf, cls, keep_idx, coef, nms_ws_,
+                    nms_ws_bytes_, s);
+    pred_n_ = 0;
+  } else {
+    decode(n, s);
+    nms_launch(v_.at("pred").p, n, cfg_.nc, nm_, na_, cfg_.conf, cfg_.iou, cfg_.max_det, 7680.0f, n_det, boxes, conf, cls, keep_idx, coef,
+               nms_ws_, nms_ws_bytes_, s);
+  }
   join_into(s, 0);  // the prototype branch ran beside the heads, decode and NMS (one workgroup per frame: 32 of 256 CUs)
   if (mask_logits != nullptr) {
     // masks = coeffs @ protos^T per image, cropped to the box (process_mask / crop_mask)
@@ -509,6 +539,7 @@ void Detector::forward(const uint8_t* frames, int n, int flip, int* n_det, float
   // f16x3 on the LDS-DMA kernel: every intermediate activation is kept in SP8; the frame, the raw head rows and the
   // prototypes (decode / mask inputs) stay f32
   fmt_ = (!count_flops_ && gemm_sp_active()) ? 1 : 0;
+  head_direct_ = env_int("MTGV_DET_HEAD_DIRECT", 1) != 0;  // read per call (A/B in one process); 0: class 3x3 + 1x1, decode, NMS on pred
   if (v11()) {
     forward_v11(frames, n, flip, s);
   } else {
@@ -592,15 +623,23 @@ void Detector::head_level_v8(int l, int n, hipStream_t s) {
   const View f = view(feats[l]), t1 = view("t1_" + ls), t2 = view("t2_" + ls);
   const View rh = view("rawhead" + ls);
   conv(head_first_[l], f, t1, 1, ACT_SILU, nullptr, n, s);
-  // box and coefficient branches: the 3x3 and the final 1x1 as one launch each (the class branch's 3 outputs are no column quad)
+  // every branch: the 3x3 and the final 1x1 as one launch (the class branch with its 1x1 padded to the 32 columns behind
+  // RAW_CLS: its nc outputs alone are no column block of the chain)
   conv_pair(head_box2_[l], t1.slice(0, 64), t2.slice(0, 64), 1, head_box3_[l], rh.slice(0, 64), ACT_NONE, n, s);
-  conv(head_cls2_[l], t1.slice(64, 64), t2.slice(64, 64), 1, ACT_SILU, nullptr, n, s);
+  if (head_direct_ && !count_flops_ && fmt_ == 1) {  // (f32 activations chain nothing: the 1x1 keeps its nc columns)
+    // (the launch profiler keeps counting the nc real outputs of the 1x1)
+    const double pad_flops = 2.0 * n * rh.H * rh.W * (double)(head_cls3_pad_[l].cout - cfg_.nc) * head_cls3_pad_[l].cin;
+    conv_pair(head_cls2_[l], t1.slice(64, 64), t2.slice(64, 64), 1, head_cls3_pad_[l], rh.slice(RAW_CLS, 32), ACT_NONE, n, s, -pad_flops);
+  } else {
+    conv(head_cls2_[l], t1.slice(64, 64), t2.slice(64, 64), 1, ACT_SILU, nullptr, n, s);
+    conv(head_cls3_[l], t2.slice(64, 64), rh.slice(RAW_CLS, cfg_.nc), 1, ACT_NONE, nullptr, n, s);
+  }
   conv_pair(head_coef2_[l], t1.slice(128, 32), t2.slice(128, 32), 1, head_coef3_[l], rh.slice(RAW_COEF, nm_), ACT_NONE, n, s);
-  conv(head_cls3_[l], t2.slice(64, 64), rh.slice(RAW_CLS, cfg_.nc), 1, ACT_NONE, nullptr, n, s);
 }
 
 void Detector::raw(int n, float* pred, float* protos, hipStream_t s) {
   MTGV_CHECK(n > 0 && n <= last_n_, ERR_INVALID, "raw: n=%d but the last forward had %d frames", n, last_n_);
+  if (pred && pred_n_ < n) decode(n, s);  // the last forward ran NMS straight from the head rows
   if (pred) HIP_OK(hipMemcpyAsync(pred, v_.at("pred").p, (size_t)n * no() * na_ * sizeof(float), hipMemcpyDeviceToDevice, s));
   if (protos) {
     const View pr = v_.at("protos");
@@ -672,6 +711,27 @@ MTGV_API int mtgv_mask_binarize(const float* logits_dev, int32_t n, int32_t mh, 
                          out_dev, mh, mw, scale, npx);
     }
     HIP_OK(hipGetLastError());
+  });
+}
+static HeadRows op_head_rows(const mtgv_head_rows* r) {
+  MTGV_CHECK(r != nullptr && r->r0 && r->r1 && r->r2, ERR_INVALID, "null head rows");
+  return HeadRows{r->r0, r->r1, r->r2, r->imgsz, r->ct, r->cls, r->coef};
+}
+MTGV_API int mtgv_op_decode(const mtgv_head_rows* rows, int32_t n, int32_t nc, int32_t nm, float* pred_dev, void* stream) {
+  return guarded([&] {
+    const HeadRows h = op_head_rows(rows);
+    MTGV_CHECK(pred_dev && n > 0, ERR_INVALID, "decode: pred %p, n=%d", (void*)pred_dev, n);
+    head_rows_check(h, nc, nm);
+    decode_launch(h, n, nc, nm, pred_dev, (hipStream_t)stream);
+  });
+}
+MTGV_API int mtgv_op_nms_raw(const mtgv_head_rows* rows, int32_t n, int32_t nc, int32_t nm, float conf, float iou, int32_t max_det,
+                             float max_wh, int32_t* n_det_dev, float* boxes_dev, float* conf_dev, int32_t* cls_dev, int32_t* keep_idx_dev,
+                             float* coef_dev, int32_t* workspace_dev, size_t workspace_bytes, void* stream) {
+  return guarded([&] {
+    MTGV_CHECK(n_det_dev && boxes_dev && conf_dev && cls_dev && keep_idx_dev, ERR_INVALID, "null argument");
+    nms_rows_launch(op_head_rows(rows), n, nc, nm, conf, iou, max_det, max_wh, n_det_dev, boxes_dev, conf_dev, cls_dev, keep_idx_dev, coef_dev,
+                    workspace_dev, workspace_bytes, (hipStream_t)stream);
   });
 }
 MTGV_API int mtgv_detector_set_fork(mtgv_detector* h, int32_t mode) {

@@ -4,76 +4,38 @@
 #pragma once
 #include "act.h"
 #include "detector.h"
+#include "head_decode.h"
 #include "sp8.h"
 
 #include <math.h>
 
 namespace mtgv {
 
-// decode: DFL expectation -> ltrb -> xywh * stride; class sigmoid; coefficient copy
-// rawhead rows: [0,64) box logits (4 sides x 16 bins), [64,64+nc) class logits, [68,100) coeffs
+// decode: DFL expectation -> ltrb -> xywh * stride; class sigmoid; coefficient copy (the arithmetic is head_decode.h's,
+// shared with the row form of nms_kernel)
+// rows: [0,64) box logits (4 sides x 16 bins), [h.coef, +nm) coeffs, [h.cls, +nc) class logits (the detector's: detector.h)
 
-__global__ __launch_bounds__(256) void decode_kernel(const float* __restrict__ r0, const float* __restrict__ r1,
-                                                    const float* __restrict__ r2, float* __restrict__ pred, int n, int nc, int nm,
-                                                    int imgsz, int na) {
+__global__ __launch_bounds__(256) void decode_kernel(HeadRows h, float* __restrict__ pred, int n, int nc, int nm, int na) {
   const long idx = (long)blockIdx.x * 256 + threadIdx.x;
   if (idx >= (long)n * na) return;
   const int img = (int)(idx / na), a = (int)(idx % na);
-  const int w0 = imgsz / 8, w1 = imgsz / 16, w2 = imgsz / 32;
-  const int n0 = w0 * w0, n1 = w1 * w1;
-  const float* row;
-  int gw, pix;
-  float stride;
-  if (a < n0) {
-    pix = a, gw = w0, stride = 8.f;
-    row = r0 + ((long)img * n0 + pix) * RAW_CT;
-  } else if (a < n0 + n1) {
-    pix = a - n0, gw = w1, stride = 16.f;
-    row = r1 + ((long)img * n1 + pix) * RAW_CT;
-  } else {
-    pix = a - n0 - n1, gw = w2, stride = 32.f;
-    row = r2 + ((long)img * w2 * w2 + pix) * RAW_CT;
-  }
-  float d[4];
-#pragma unroll
-  for (int s = 0; s < 4; ++s) {
-    float v[16];
-    float mx = -INFINITY;
-#pragma unroll
-    for (int q = 0; q < 4; ++q) {  // rows are RAW_CT = 100 floats: 16-byte loads (a lane's row shares no line with its neighbours')
-      const f32x4 t = *reinterpret_cast<const f32x4*>(row + s * 16 + q * 4);
-#pragma unroll
-      for (int e = 0; e < 4; ++e) {
-        v[q * 4 + e] = t[e];
-        mx = fmaxf(mx, t[e]);
-      }
-    }
-    float sum = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      v[i] = expf(v[i] - mx);
-      sum += v[i];
-    }
-    float e = 0.f;
-#pragma unroll
-    for (int i = 0; i < 16; ++i) e += (v[i] / sum) * (float)i;
-    d[s] = e;
-  }
-  const float ax = (float)(pix % gw) + 0.5f, ay = (float)(pix / gw) + 0.5f;
-  const float x1 = ax - d[0], y1 = ay - d[1], x2 = ax + d[2], y2 = ay + d[3];
+  const HeadAnchor an = head_anchor(h, img, a);
+  const float* row = an.row;
+  float xywh[4];
+  head_box(an, xywh);
   float* P = pred + (long)img * (4 + nc + nm) * na + a;
-  P[0] = (x1 + x2) / 2.f * stride;
-  P[(long)na] = (y1 + y2) / 2.f * stride;
-  P[(long)2 * na] = (x2 - x1) * stride;
-  P[(long)3 * na] = (y2 - y1) * stride;
-  for (int c = 0; c < nc; ++c) P[(long)(4 + c) * na] = 1.0f / (1.0f + expf(-row[RAW_CLS + c]));
+  P[0] = xywh[0];
+  P[(long)na] = xywh[1];
+  P[(long)2 * na] = xywh[2];
+  P[(long)3 * na] = xywh[3];
+  for (int c = 0; c < nc; ++c) P[(long)(4 + c) * na] = head_score(row[h.cls + c]);
   for (int c = 0; c < nm; c += 4) {
     if (c + 4 <= nm) {
-      const f32x4 t = *reinterpret_cast<const f32x4*>(row + RAW_COEF + c);
+      const f32x4 t = *reinterpret_cast<const f32x4*>(row + h.coef + c);
 #pragma unroll
       for (int e = 0; e < 4; ++e) P[(long)(4 + nc + c + e) * na] = t[e];
     } else {
-      for (int e = 0; c + e < nm; ++e) P[(long)(4 + nc + c + e) * na] = row[RAW_COEF + c + e];
+      for (int e = 0; c + e < nm; ++e) P[(long)(4 + nc + c + e) * na] = row[h.coef + c + e];
     }
   }
 }

@@ -55,7 +55,7 @@ constexpr std::array<SpLaunchFn, sizeof...(ID)> sp_launchers(std::integer_sequen
 const auto kLaunch = sp_launchers(std::make_integer_sequence<int, kSpNumCfg>{});
 
 // relative efficiency of each tile's main loop (fitted to tools/gemm_sp_sweep.py); 0: chosen by name below, not searched
-const double kEff[kSpNumCfg] = {0.93, 1.00, 0.88, 0.80, 0.62, 0.00, 0.00};
+const double kEff[kSpNumCfg] = {0.93, 1.00, 0.88, 0.80, 0.62, 0.00, 0.00, 0.00};
 
 SpPlan plan_of(int cfg, int M, int N) {
   const SpTile& k = kSpTile[cfg];
@@ -78,6 +78,14 @@ bool window_conv_fits(const GemmArgs& a, const SpPlan& pl) {
         a.OH == a.H && a.OW == a.Wd))
     return false;
   return sp_window_fits(k, a.Wd);
+}
+
+// SP_CFG_N160 has one instance: a SiLU window conv from SP8 to SP8 without residual, GRN sums or output remap
+static bool n160_instance(const GemmArgs& a) {
+  SpPlan p;
+  p.cfg = SP_CFG_N160;
+  return is_conv(a) && a.a_fmt == 1 && a.W2 == nullptr && a.act == ACT_SILU && a.out_fmt == 1 && a.res == nullptr && a.grn_part == nullptr &&
+         !is_remap(a) && a.topk == 0 && window_conv_fits(a, p);
 }
 
 bool gemm_sp_active() { return gemm_precision() == GEMM_PREC_F16X3; }
@@ -159,7 +167,7 @@ SpPlan gemm_sp_plan(const GemmArgs& a) {
   double best_cost = 0;
   const int force = env_int("MTGV_SP_CFG", INT_MIN);  // tools/sp_cfg_sweep.py; read per plan
   const bool forced = force != INT_MIN;
-  if (forced && force >= 0 && force < kSpNumCfg && kSpTile[force].ks == 2) best = force;
+  if (forced && force >= 0 && force < kSpNumCfg && kSpTile[force].ks == 2 && (force != SP_CFG_N160 || n160_instance(a))) best = force;
   if (best < 0) {
     for (int c = 0; c < kSpNumCfg; ++c) {
       const SpTile& k = kSpTile[c];
@@ -182,6 +190,19 @@ SpPlan gemm_sp_plan(const GemmArgs& a) {
     if (!forced && conv && sp8_in && a.Cin % kSpTile[best].kps() != 0 && a.N <= kSpTile[SP_CFG_WIN16].bn() && window_conv_fits(a, p16))
       best = SP_CFG_WIN16;
   }
+  // the detector heads' stacked first 3x3 convs (64 box + 64 class + 32 coefficient columns): one 160-column tile instead
+  // of two 96-column ones - no MFMAs on columns that do not exist, one window fill per slice instead of two.  Only for
+  // launches of several rounds of these tiles (P3 of a batch of 640 x 640 frames: 1600), which are bound by what the tiles
+  // do.  A launch of one round is bound by how long one tile takes, and there narrower tiles win: P4 (400 row tiles) took
+  // 105.5 / 78.2 / 80.4 / 71.2 / 67.0 us on the 128-, 192-, 96-, 64- and 32-column tiles (profiles/r04_sp_cfg_sweep.txt,
+  // launch 46), and P5 has 100 row tiles.  Both keep the search's tile.
+  // The rule goes by the launch's shape, not by its caller: any SiLU 3x3 / stride-1 SP8 conv of 160 columns and more than
+  // a round of row tiles takes it, mtgv_op_conv2d_ex's included (that is how tests/test_gpu_sp8_tile160.py reaches it), and
+  // so the detector's switch MTGV_DET_HEAD_DIRECT=0, which restores the head's earlier launches, is read here and puts
+  // every such launch back on the search's tile.  Results do not depend on the tile.
+  if (!forced && a.N == kSpTile[SP_CFG_N160].bn() && n160_instance(a) && ceil_div(a.M, kSpTile[SP_CFG_N160].bm()) > kSpRoundTiles &&
+      env_int("MTGV_DET_HEAD_DIRECT", 1) != 0)
+    best = SP_CFG_N160;
   // eight-wave twin of the 128 x 192 tile (four waves per SIMD) for pwconv1-shaped launches: SP8 rows in, activation
   // + GRN sums out; measured -3..-4 % on the stage 2-3 layers, nothing on the others (not below 12288 rows: 6144 x
   // 3072 x 768, the stage-3 pwconv1, is 8 % faster on the four-wave tile - tools/sp_cfg_sweep.py,

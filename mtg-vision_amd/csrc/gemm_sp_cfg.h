@@ -29,6 +29,7 @@ constexpr SpTile kSpTile[] = {
     {4, 1, 1, 1, 2},  // 128 x  32
     {4, 2, 1, 3, 2},  // 128 x 192 on eight waves
     {4, 1, 1, 1, 1},  // 128 x  32 in 16-k stages
+    {4, 1, 1, 5, 2},  // 128 x 160: the detector heads' stacked first 3x3 convs in one column tile (window conv only)
 };
 constexpr int kSpNumCfg = sizeof(kSpTile) / sizeof(kSpTile[0]);
 
@@ -38,14 +39,16 @@ enum SpCfgId : int {
   SP_CFG_OS_NQ = 3,   // whole-ConvTranspose launches: one column group of 64 per tile
   SP_CFG_PW1_8W = 5,  // eight-wave twin of SP_CFG_TOPK's 128 x 192, swapped in for pwconv1-shaped launches
   SP_CFG_WIN16 = 6,   // window convs with 16-channel slices
+  SP_CFG_N160 = 7,    // window convs with 160 output columns: no dead columns, one window fill (SiLU, SP8 out: its only instance)
 };
 static_assert(kSpTile[SP_CFG_PW1_8W].bm() == kSpTile[SP_CFG_TOPK].bm() && kSpTile[SP_CFG_PW1_8W].bn() == kSpTile[SP_CFG_TOPK].bn(),
               "the eight-wave twin covers the same block");
-static_assert(kSpTile[SP_CFG_WIN16].ks == 1 && kSpTile[SP_CFG_OS_NQ].bn() == 64, "named configurations");
+static_assert(kSpTile[SP_CFG_WIN16].ks == 1 && kSpTile[SP_CFG_OS_NQ].bn() == 64 && kSpTile[SP_CFG_N160].bn() == 160, "named configurations");
 
-// Chained 1x1 (SP_EPI_CHAIN): one wave holds whole output rows.  The instance ladder builds those kernels for exactly
-// the tiles this admits, and the planner picks a chain tile through sp_chain_cfg, so it cannot name one without a kernel.
-constexpr bool sp_tile_chains(const SpTile& t) { return t.wn == 1 && t.tm == 1 && t.ks == 2; }
+// Chained 1x1 (SP_EPI_CHAIN): one wave holds whole output rows, of at most 96 columns.  The instance ladder builds those
+// kernels for exactly the tiles this admits, and the planner picks a chain tile through sp_chain_cfg, so it cannot name
+// one without a kernel.
+constexpr bool sp_tile_chains(const SpTile& t) { return t.wn == 1 && t.tm == 1 && t.ks == 2 && t.tn <= 3; }
 // the chain tile whose one column tile is N wide, or -1
 constexpr int sp_chain_cfg(int N) {
   for (int c = 0; c < kSpNumCfg; ++c)
@@ -144,5 +147,13 @@ constexpr bool sp_window_fits(const SpTile& t, int Wd) {
 constexpr int sp_window_ring(const SpTile& t, int Wd, long tiles) {
   return (tiles <= kSpRoundTiles && sp_window_bytes(t, Wd) + sp_ring(t, SP_A_WINDOW, kSpDeepRing) <= kSpTwoPerCu) ? kSpDeepRing : kSpRing;
 }
+// whether any map is narrow enough for the deep ring on this tile (SP_CFG_N160's four-deep ring never fits twice per
+// CU: no such instance is built)
+constexpr bool sp_window_ring_deepens(const SpTile& t) { return sp_window_ring(t, 1, 1) == kSpDeepRing; }
+// SP_CFG_N160 at the widest map it is named for (P3 of a 640 x 640 frame, Wd = 80): window + two-deep ring and the epilogue
+// staging both leave room for a second block on the CU
+static_assert(sp_window_fits(kSpTile[SP_CFG_N160], 80) && !sp_window_ring_deepens(kSpTile[SP_CFG_N160]) &&
+                  sp_launch_lds(kSpTile[SP_CFG_N160], SP_A_WINDOW, SP_EPI_SP8_OUT, kSpRing, 80) <= kSpTwoPerCu,
+              "the 128 x 160 tile runs two blocks per CU");
 
 }  // namespace mtgv

@@ -9,7 +9,7 @@ namespace {
 template <int ID, int AMODE, int ACT, int EPI, int NST = kSpRing>
 void sp_launch_one(const SpDev& g, hipStream_t s) {
   constexpr SpTile T = kSpTile[ID];
-  if constexpr (AMODE == SP_A_WINDOW && NST == kSpRing) {
+  if constexpr (AMODE == SP_A_WINDOW && NST == kSpRing && sp_window_ring_deepens(T)) {
     if (sp_window_ring(T, g.Wd, (long)g.tiles_m * g.tiles_n) == kSpDeepRing) return sp_launch_one<ID, AMODE, ACT, EPI, kSpDeepRing>(g, s);
   }
   const size_t lds = sp_launch_lds(T, AMODE, EPI, NST, g.Wd);
@@ -48,6 +48,20 @@ void sp_pick_conv(const SpDev& g, int epi, hipStream_t s) {
 
 // The instances of configuration ID (gemm_sp.hip dispatches on the plan's cfg): per A mode, the activations and
 // epilogue shapes the executors use get kernels of their own, everything else the generic one.
+template <int ID>
+void gemm_sp_launch_cfg(const SpDev& g, int amode, hipStream_t s);
+
+#if SP_CFG_ID == 7
+// SP_CFG_N160: one instance - the planner names this tile for that launch shape only (gemm_sp.hip)
+static_assert(SP_CFG_ID == SP_CFG_N160, "the single-instance configuration");
+template <>
+void gemm_sp_launch_cfg<SP_CFG_N160>(const SpDev& g, int amode, hipStream_t s) {
+  MTGV_CHECK(amode == SP_A_WINDOW && g.act == ACT_SILU && g.topk == 0 && sp_epi_of(g) == SP_EPI_SP8_OUT, ERR_RUNTIME,
+             "gemm_sp: configuration %d runs SiLU window convs with SP8 output only (A mode %d, act %d)", (int)SP_CFG_N160, amode, g.act);
+  sp_launch_one<SP_CFG_N160, SP_A_WINDOW, ACT_SILU, SP_EPI_SP8_OUT>(g, s);
+}
+#endif
+
 template <int ID>
 void gemm_sp_launch_cfg(const SpDev& g, int amode, hipStream_t s) {
   constexpr SpTile T = kSpTile[ID];
@@ -93,6 +107,8 @@ void gemm_sp_launch_cfg(const SpDev& g, int amode, hipStream_t s) {
   }
 }
 
+#if SP_CFG_ID != 7
 template void gemm_sp_launch_cfg<SP_CFG_ID>(const SpDev& g, int amode, hipStream_t s);
+#endif
 
 }  // namespace mtgv

@@ -1,0 +1,87 @@
+// The per-anchor decode of the segment head's raw rows, defined once for its two users: decode_kernel
+// (detector_kernel.h), which writes `pred` for every anchor, and the row form of nms_kernel (nms.hip), which decodes
+// the candidates only.  Both must give the same bits, so nothing here is left to the compiler's contraction: the
+// function bodies are compiled with contraction off and the one fused operation - the expectation's accumulate, which
+// is what decode_kernel compiled to when it was written in plain expressions - is spelled __builtin_fmaf.
+#pragma once
+#include "common.h"
+
+#include <math.h>
+
+namespace mtgv {
+
+// Raw head rows of the three pyramid levels (strides 8 / 16 / 32): per level [n][(imgsz / stride)^2] rows of `ct` floats,
+// 16-byte aligned; a row holds 4 sides x 16 box bins at [0, 64), class logits at [cls, cls + nc), mask coefficients at
+// [coef, coef + nm).  ct, cls and coef are multiples of 4.
+struct HeadRows {
+  const float *r0, *r1, *r2;
+  int imgsz, ct, cls, coef;
+};
+
+struct HeadAnchor {
+  const float* row;
+  int pix, gw;    // pixel index and width of the level's grid
+  float stride;
+};
+
+// anchor a of image img: P3's pixels first, then P4's, then P5's (the order of `pred`)
+__device__ __forceinline__ HeadAnchor head_anchor(const HeadRows& h, int img, int a) {
+  const int w0 = h.imgsz / 8, w1 = h.imgsz / 16, w2 = h.imgsz / 32;
+  const int n0 = w0 * w0, n1 = w1 * w1;
+  HeadAnchor an;
+  if (a < n0) {
+    an.pix = a, an.gw = w0, an.stride = 8.f;
+    an.row = h.r0 + ((long)img * n0 + an.pix) * h.ct;
+  } else if (a < n0 + n1) {
+    an.pix = a - n0, an.gw = w1, an.stride = 16.f;
+    an.row = h.r1 + ((long)img * n1 + an.pix) * h.ct;
+  } else {
+    an.pix = a - n0 - n1, an.gw = w2, an.stride = 32.f;
+    an.row = h.r2 + ((long)img * w2 * w2 + an.pix) * h.ct;
+  }
+  return an;
+}
+
+// DFL: per side the softmax over 16 bins and its expectation; ltrb around the anchor centre -> xywh * stride
+__device__ __forceinline__ void head_box(const HeadAnchor& an, float xywh[4]) {
+#pragma clang fp contract(off)
+  float d[4];
+#pragma unroll
+  for (int s = 0; s < 4; ++s) {
+    float v[16];
+    float mx = -INFINITY;
+#pragma unroll
+    for (int q = 0; q < 4; ++q) {  // 16-byte loads (a lane's row shares no line with its neighbours')
+      const f32x4 t = *reinterpret_cast<const f32x4*>(an.row + s * 16 + q * 4);
+#pragma unroll
+      for (int e = 0; e < 4; ++e) {
+        v[q * 4 + e] = t[e];
+        mx = fmaxf(mx, t[e]);
+      }
+    }
+    float sum = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      v[i] = expf(v[i] - mx);
+      sum = sum + v[i];
+    }
+    float e = 0.f;
+#pragma unroll
+    for (int i = 0; i < 16; ++i) e = __builtin_fmaf(v[i] / sum, (float)i, e);
+    d[s] = e;
+  }
+  const float ax = (float)(an.pix % an.gw) + 0.5f, ay = (float)(an.pix / an.gw) + 0.5f;
+  const float x1 = ax - d[0], y1 = ay - d[1], x2 = ax + d[2], y2 = ay + d[3];
+  xywh[0] = (x1 + x2) / 2.f * an.stride;
+  xywh[1] = (y1 + y2) / 2.f * an.stride;
+  xywh[2] = (x2 - x1) * an.stride;
+  xywh[3] = (y2 - y1) * an.stride;
+}
+
+// class score of a class logit
+__device__ __forceinline__ float head_score(float logit) {
+#pragma clang fp contract(off)
+  return 1.0f / (1.0f + expf(-logit));
+}
+
+}  // namespace mtgv

@@ -11,6 +11,11 @@
 //
 // All box arithmetic uses explicitly rounded single operations (no FMA contraction), so the
 // kept indices are bit-identical to the float32 CPU oracle (oracle/detector_ref.py nms_single).
+//
+// Two forms of the kernel.  ROWS = false reads decoded predictions `pred` (n, 4 + nc + nm, na).  ROWS = true reads the
+// segment head's raw rows instead (head_decode.h): step 1 takes the class scores of every anchor from the rows' class
+// logits, step 3 decodes the boxes of the sorted candidates only, and the kept detections copy their coefficients from
+// their rows - the values decode_kernel would have written to `pred`, bit for bit, without the pass over every anchor.
 #include "nms.h"
 
 namespace mtgv {
@@ -25,8 +30,30 @@ __device__ __forceinline__ float box_iou_rn(float ax1, float ay1, float ax2, flo
   return __fdiv_rn(inter, __fsub_rn(__fadd_rn(aarea, barea), inter));
 }
 
+// what the sweep needs of anchor a, from either source
+template <bool ROWS>
+struct NmsSrc {
+  const float* P;  // pred of this image (ROWS = false)
+  HeadRows h;      // (ROWS = true)
+  int img, na;
+  __device__ __forceinline__ HeadAnchor anchor(int a) const { return ROWS ? head_anchor(h, img, a) : HeadAnchor{}; }
+  __device__ __forceinline__ float score(const HeadAnchor& an, int a, int c) const {
+    if constexpr (ROWS) return head_score(an.row[h.cls + c]);
+    else return P[(long)(4 + c) * na + a];
+  }
+  __device__ __forceinline__ void xywh(const HeadAnchor& an, int a, float b[4]) const {
+    if constexpr (ROWS) head_box(an, b);
+    else b[0] = P[a], b[1] = P[(long)na + a], b[2] = P[(long)2 * na + a], b[3] = P[(long)3 * na + a];
+  }
+  __device__ __forceinline__ float coef(const HeadAnchor& an, int a, int nc, int c) const {
+    if constexpr (ROWS) return an.row[h.coef + c];
+    else return P[(long)(4 + nc + c) * na + a];
+  }
+};
+
 // ws layout per image (floats): obox[cap][4], area[cap], then ints: sidx[cap], scls[cap]
-__global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* __restrict__ pred, int nc, int nm, int na, int cap,
+template <bool ROWS>
+__global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* __restrict__ pred, HeadRows rows, int nc, int nm, int na, int cap,
                                                          float conf_thres, float iou_thres, int max_det, float max_wh,
                                                          int* __restrict__ n_det, float* __restrict__ boxes,
                                                          float* __restrict__ conf_out, int* __restrict__ cls_out,
@@ -38,7 +65,7 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* __restric
   __shared__ int s_keep[1024];
   const int img = blockIdx.x, tid = threadIdx.x;
   const int no = 4 + nc + nm;
-  const float* P = pred + (long)img * no * na;
+  const NmsSrc<ROWS> src{ROWS ? nullptr : pred + (long)img * no * na, rows, img, na};
 
   float* obox = reinterpret_cast<float*>(ws) + (long)img * cap * 7;
   float* area = obox + (long)cap * 4;
@@ -51,9 +78,10 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* __restric
 
   // 1. candidates
   for (int a = tid; a < na; a += NMS_THREADS) {
-    float best = P[(long)4 * na + a];
+    const HeadAnchor an = src.anchor(a);
+    float best = src.score(an, a, 0);
     for (int c = 1; c < nc; ++c) {
-      const float v = P[(long)(4 + c) * na + a];
+      const float v = src.score(an, a, c);
       if (v > best) best = v;
     }
     if (best > conf_thres) {
@@ -84,11 +112,14 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* __restric
   // 3. sorted boxes
   for (int i = tid; i < count; i += NMS_THREADS) {
     const int a = (int)(~(unsigned)(keys[i] & 0xffffffffull));
-    const float x = P[a], y = P[(long)na + a], w = P[(long)2 * na + a], h = P[(long)3 * na + a];
-    float best = P[(long)4 * na + a];
+    const HeadAnchor an = src.anchor(a);
+    float b[4];
+    src.xywh(an, a, b);
+    const float x = b[0], y = b[1], w = b[2], h = b[3];
+    float best = src.score(an, a, 0);
     int cls = 0;
     for (int c = 1; c < nc; ++c) {
-      const float v = P[(long)(4 + c) * na + a];
+      const float v = src.score(an, a, c);
       if (v > best) best = v, cls = c;
     }
     const float hw = __fmul_rn(w, 0.5f), hh = __fmul_rn(h, 0.5f);
@@ -173,14 +204,17 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* __restric
     const float off = __fmul_rn((float)cls, max_wh);
     const long o = (long)img * max_det + t;
     // un-offset boxes are recomputed from the prediction so they carry no offset rounding
-    const float x = P[a], y = P[(long)na + a], w = P[(long)2 * na + a], h = P[(long)3 * na + a];
+    const HeadAnchor an = src.anchor(a);
+    float b[4];
+    src.xywh(an, a, b);
+    const float x = b[0], y = b[1], w = b[2], h = b[3];
     const float hw = __fmul_rn(w, 0.5f), hh = __fmul_rn(h, 0.5f);
     boxes[o * 4 + 0] = __fsub_rn(x, hw);
     boxes[o * 4 + 1] = __fsub_rn(y, hh);
     boxes[o * 4 + 2] = __fadd_rn(x, hw);
     boxes[o * 4 + 3] = __fadd_rn(y, hh);
     (void)off;
-    conf_out[o] = P[(long)(4 + cls) * na + a];
+    conf_out[o] = src.score(an, a, cls);
     cls_out[o] = cls;
     keep_idx[o] = a;
   }
@@ -197,7 +231,10 @@ __global__ __launch_bounds__(NMS_THREADS) void nms_kernel(const float* __restric
     for (int t = tid; t < max_det * nm; t += NMS_THREADS) {
       const int d = t / nm, c = t - d * nm;
       float v = 0.f;
-      if (d < nkeep) v = P[(long)(4 + nc + c) * na + sidx[s_keep[d]]];
+      if (d < nkeep) {
+        const int a = sidx[s_keep[d]];
+        v = src.coef(src.anchor(a), a, nc, c);
+      }
       coef_out[((long)img * max_det + d) * nm + c] = v;
     }
   }
@@ -211,19 +248,45 @@ static int pow2_ge(int n) {
 
 size_t nms_workspace_bytes(int n, int na) { return (size_t)n * pow2_ge(na) * 7 * sizeof(float); }
 
-void nms_launch(const float* pred, int n, int nc, int nm, int na, float conf, float iou, int max_det, float max_wh, int* n_det,
-                float* boxes, float* conf_out, int* cls_out, int* keep_idx, float* coef_out, int* ws, size_t ws_bytes,
-                hipStream_t s) {
+template <bool ROWS>
+static void nms_launch_form(const float* pred, const HeadRows& rows, int n, int nc, int nm, int na, float conf, float iou, int max_det,
+                            float max_wh, int* n_det, float* boxes, float* conf_out, int* cls_out, int* keep_idx, float* coef_out, int* ws,
+                            size_t ws_bytes, hipStream_t s) {
   MTGV_CHECK(n > 0 && nc > 0 && nm >= 0 && na > 0, ERR_INVALID, "nms: n=%d nc=%d nm=%d na=%d", n, nc, nm, na);
   MTGV_CHECK(max_det > 0 && max_det <= 1024, ERR_INVALID, "nms: max_det=%d outside [1,1024]", max_det);
   const int cap = pow2_ge(na);
   const size_t lds = (size_t)cap * sizeof(unsigned long long);
   MTGV_CHECK(lds <= 150 * 1024, ERR_INVALID, "nms: %d anchors exceed the LDS sort capacity", na);
   MTGV_CHECK(ws != nullptr && ws_bytes >= nms_workspace_bytes(n, na), ERR_INVALID, "nms: workspace too small");
-  lds_opt_in<nms_kernel>(lds, 150 * 1024);
-  hipLaunchKernelGGL(nms_kernel, dim3(n), dim3(NMS_THREADS), lds, s, pred, nc, nm, na, cap, conf, iou, max_det, max_wh, n_det,
+  lds_opt_in<nms_kernel<ROWS>>(lds, 150 * 1024);
+  hipLaunchKernelGGL(nms_kernel<ROWS>, dim3(n), dim3(NMS_THREADS), lds, s, pred, rows, nc, nm, na, cap, conf, iou, max_det, max_wh, n_det,
                      boxes, conf_out, cls_out, keep_idx, coef_out, ws);
   HIP_OK(hipGetLastError());
+}
+
+void nms_launch(const float* pred, int n, int nc, int nm, int na, float conf, float iou, int max_det, float max_wh, int* n_det,
+                float* boxes, float* conf_out, int* cls_out, int* keep_idx, float* coef_out, int* ws, size_t ws_bytes,
+                hipStream_t s) {
+  nms_launch_form<false>(pred, HeadRows{}, n, nc, nm, na, conf, iou, max_det, max_wh, n_det, boxes, conf_out, cls_out, keep_idx, coef_out,
+                         ws, ws_bytes, s);
+}
+
+int head_rows_anchors(int imgsz) { return (imgsz / 8) * (imgsz / 8) + (imgsz / 16) * (imgsz / 16) + (imgsz / 32) * (imgsz / 32); }
+
+void head_rows_check(const HeadRows& rows, int nc, int nm) {
+  MTGV_CHECK(rows.r0 && rows.r1 && rows.r2 && rows.imgsz > 0 && rows.imgsz % 32 == 0 && nc > 0 && nm >= 0, ERR_INVALID,
+             "head rows: imgsz=%d nc=%d nm=%d", rows.imgsz, nc, nm);
+  MTGV_CHECK(rows.ct % 4 == 0 && rows.cls % 4 == 0 && rows.coef % 4 == 0 && rows.cls >= 64 && rows.coef >= 64 && rows.cls + nc <= rows.ct &&
+                 rows.coef + nm <= rows.ct && (((uintptr_t)rows.r0 | (uintptr_t)rows.r1 | (uintptr_t)rows.r2) & 15) == 0,
+             ERR_INVALID, "head rows: layout ct=%d cls=%d coef=%d (nc=%d nm=%d; 16-byte aligned rows)", rows.ct, rows.cls, rows.coef, nc, nm);
+}
+
+void nms_rows_launch(const HeadRows& rows, int n, int nc, int nm, float conf, float iou, int max_det, float max_wh, int* n_det,
+                     float* boxes, float* conf_out, int* cls_out, int* keep_idx, float* coef_out, int* ws, size_t ws_bytes,
+                     hipStream_t s) {
+  head_rows_check(rows, nc, nm);
+  nms_launch_form<true>(nullptr, rows, n, nc, nm, head_rows_anchors(rows.imgsz), conf, iou, max_det, max_wh, n_det, boxes, conf_out, cls_out,
+                        keep_idx, coef_out, ws, ws_bytes, s);
 }
 
 }  // namespace mtgv

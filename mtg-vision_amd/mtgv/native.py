@@ -64,6 +64,12 @@ class ConvEx(C.Structure):
     )
 
 
+class HeadRows(C.Structure):
+    """mtgv_head_rows: the segment head's raw rows of the three pyramid levels and their layout (test surface)"""
+
+    _fields_ = [(k, c_vp) for k in ("r0", "r1", "r2")] + [(k, c_i32) for k in ("imgsz", "ct", "cls", "coef")]
+
+
 class ProtoTail(C.Structure):
     """mtgv_proto_tail: the detector's prototype branch behind cv1 (test surface)"""
 
@@ -123,6 +129,11 @@ SIGNATURES = {
         [c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_size_t, c_vp],
     ),
     "mtgv_nms_workspace_bytes": (C.c_size_t, [c_i32, c_i32]),
+    "mtgv_op_decode": (C.c_int, [C.POINTER(HeadRows), c_i32, c_i32, c_i32, c_vp, c_vp]),
+    "mtgv_op_nms_raw": (
+        C.c_int,
+        [C.POINTER(HeadRows), c_i32, c_i32, c_i32, c_f32, c_f32, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_size_t, c_vp],
+    ),
     "mtgv_select_cards": (C.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mtgv_warp_workspace_bytes": (C.c_size_t, [c_i32]),
     "mtgv_warp_quads": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_i32, c_i32, c_i32, C.c_double, c_vp, c_vp, C.c_size_t, c_vp]),
