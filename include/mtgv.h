@@ -59,7 +59,7 @@ MTGV_API int mtgv_device_count(void);
  * onto library-owned streams and joins them before it returns control of the caller's stream (library kernels only;
  * MTGV_DET_FORK=0 keeps the forward on one stream).  mtgv.Pipeline overlaps its stages (detect + crop / embed / match: three streams, the
  * latter two at high priority, the detector's fork-join off) only with MTGV_OVERLAP=on, and then runs nothing but library kernels on them - its output tensors are uninitialised allocations filled by the
- * kernels, the glue between the stages is mtgv_select_cards - plus, with a sharded bank, RCCL's own all-gather kernels
+ * kernels, the glue between the stages is mtgv_select_cards / mtgv_obb_cards - plus, with a sharded bank, RCCL's own all-gather kernels
  * (mtgv_bank_topk_packed / mtgv_topk_merge_gathered keep every other step of the exchange inside the library).  A caller
  * that runs foreign kernels (PyTorch elementwise ops included) concurrently on a second stream must either serialise
  * them against the library's stream or select MTGV_PREC_F32. */
@@ -174,7 +174,8 @@ MTGV_API int mtgv_topk_merge_gathered(const int64_t* gathered_dev, int32_t n_ran
                                       float score_threshold, int64_t* ids_dev, float* scores_dev, void* stream);
 
 /* ------------------------------------------------------------------------- */
-/* Detector: YOLOv8n-seg forward + decode + NMS + mask logits.                */
+/* Detector: YOLOv8n / YOLO11n, -seg (forward + decode + NMS + mask logits)   */
+/* or -obb (forward + rotated decode + rotated NMS).                          */
 /* Replaces CardSegmenter.__call__ -> ultralytics YOLO predict                */
 /* (mtgvision/od_export.py:141-160; model built in od_train.py:46-70).        */
 /* ------------------------------------------------------------------------- */
@@ -187,8 +188,12 @@ typedef struct {
   float conf;        /* 0.25 */
   float iou;         /* 0.7 */
   int32_t max_det;   /* 300 */
-  int32_t arch;      /* 0 or 8: YOLOv8n-seg; 11: YOLO11n-seg (C3k2, C2PSA, depthwise class branch; od_train.py:20) */
+  int32_t arch;      /* 0 or 8: YOLOv8n; 11: YOLO11n (C3k2, C2PSA, depthwise class branch; od_train.py:20) */
+  int32_t task;      /* 0: segment head (-seg); 1: OBB head (-obb, what od_train.py:19, :101 builds by default): no prototypes,
+                      * one angle logit per anchor, rotated NMS.  (Added in version 101: the struct grew by this field.) */
 } mtgv_detector_cfg;
+#define MTGV_TASK_SEGMENT 0
+#define MTGV_TASK_OBB 1
 
 MTGV_API int mtgv_detector_create(const mtgv_detector_cfg* cfg, mtgv_detector** out);
 MTGV_API void mtgv_detector_destroy(mtgv_detector* h);
@@ -208,7 +213,18 @@ MTGV_API int mtgv_detector_finalize(mtgv_detector* h);
 MTGV_API int mtgv_detector_forward(mtgv_detector* h, const uint8_t* frames_dev, int32_t n, int32_t flip_rgb,
                                    int32_t* n_det_dev, float* boxes_dev, float* conf_dev, int32_t* cls_dev,
                                    int32_t* keep_idx_dev, float* mask_logits_dev, int32_t mask_rows, void* stream);
-/* raw head outputs of the last forward: pred (n, 4+nc+32, 8400) and protos (n, 32, 160, 160) */
+/* The forward of an OBB handle (task 1; mtgv_detector_forward on it, or this call on a segment handle, returns status 1):
+ * backbone, neck and head as above without the prototype branch, then the OBB decode
+ *   angle = (sigmoid(logit) - 0.25) pi;  xf = (r - l) / 2, yf = (b - t) / 2 from the DFL distances l, t, r, b;
+ *   x = (xf cos(angle) - yf sin(angle) + ax) stride, y = (xf sin(angle) + yf cos(angle) + ay) stride,
+ *   w = (l + r) stride, h = (t + b) stride
+ * and mtgv_nms_rotated on the result (class-aware, max_wh 7680).  Outputs as above with rboxes (n, max_det, 5) =
+ * x, y, w, h in pixels and the angle in radians, in place of boxes; there is no mask stage.  The arithmetic is
+ * ultralytics 8.3.x's as recalled (OBB.forward, dist2rbox): unpinned, like the rest of the detector. */
+MTGV_API int mtgv_detector_forward_obb(mtgv_detector* h, const uint8_t* frames_dev, int32_t n, int32_t flip_rgb, int32_t* n_det_dev,
+                                       float* rboxes_dev, float* conf_dev, int32_t* cls_dev, int32_t* keep_idx_dev, void* stream);
+/* raw head outputs of the last forward: pred (n, 4+nc+32, 8400) and protos (n, 32, 160, 160); on an OBB handle
+ * pred (n, 4+nc+1, 8400) = xywh, class scores, angle, and protos_dev must be NULL */
 MTGV_API int mtgv_detector_raw(mtgv_detector* h, int32_t n, float* pred_dev, float* protos_dev, void* stream);
 MTGV_API int mtgv_detector_flops(const mtgv_detector* h, double* flops_per_frame);
 /* The forward's internal fork-join (the prototype branch and the P3 / P4 head branches on library-owned streams, see the
@@ -227,6 +243,26 @@ MTGV_API int mtgv_nms(const float* pred_dev, int32_t n, int32_t nc, int32_t nm, 
                       int32_t max_det, float max_wh, int32_t* n_det_dev, float* boxes_dev, float* conf_dev, int32_t* cls_dev,
                       int32_t* keep_idx_dev, int32_t* workspace_dev, size_t workspace_bytes, void* stream);
 MTGV_API size_t mtgv_nms_workspace_bytes(int32_t n, int32_t na);
+
+/* Rotated NMS alone on OBB predictions pred (n, 4+nc+1, na) [xywh, class scores, angle]
+ * (ultralytics 8.3.x non_max_suppression(rotated=True) -> nms_rotated, as recalled: unpinned).  Candidates: best class
+ * score > conf, ordered score descending then anchor ascending; x and y get cls * max_wh added.  The rule is not the
+ * greedy sweep: candidate j is kept iff no candidate i < j of that order has probiou(i, j) >= iou, whether or not i was
+ * itself dropped; the first max_det kept are reported.  rboxes_dev (n, max_det, 5), conf_dev and keep_idx_dev are copies of
+ * pred's values; slots beyond n_det are zeros.  iou > 0 and max_wh >= 7680; box sides <= 1024 px and centres within
+ * [-512, 1536] (pairs of different classes are skipped on that ground).  One workgroup per image, all pairs of a class:
+ * measured 0.7 ms at 900 candidates, 32 ms at 8400 dissimilar ones of one class (profiles/README.md). */
+MTGV_API size_t mtgv_nms_rotated_workspace_bytes(int32_t n, int32_t na);
+MTGV_API int mtgv_nms_rotated(const float* pred_dev, int32_t n, int32_t nc, int32_t na, float conf, float iou, int32_t max_det, float max_wh,
+                              int32_t* n_det_dev, float* rboxes_dev, float* conf_dev, int32_t* cls_dev, int32_t* keep_idx_dev,
+                              int32_t* workspace_dev, size_t workspace_bytes, void* stream);
+/* Test surface of the pair function of mtgv_nms_rotated (the same device function): ProbIoU of boxes a[i] and b[i],
+ * (m, 5) x, y, w, h, angle each -> out (m).  With A = w^2/12, B = h^2/12: a = A cos^2 + B sin^2, b = A sin^2 + B cos^2,
+ * c = (A - B) cos sin per box; D = (a1+a2)(b1+b2) - (c1+c2)^2; bd = clamp(t1 + t2 + t3, eps, 100) with
+ * t1 = ((a1+a2)(y1-y2)^2 + (b1+b2)(x1-x2)^2) / (D + eps) / 4, t2 = (c1+c2)(x2-x1)(y1-y2) / (D + eps) / 2,
+ * t3 = log(D / (4 sqrt(max(a1 b1 - c1^2, 0) max(a2 b2 - c2^2, 0)) + eps) + eps) / 2; probiou = 1 - sqrt(1 - exp(-bd) + eps);
+ * eps = 1e-7, float32 throughout. */
+MTGV_API int mtgv_op_probiou(const float* a_dev, const float* b_dev, int64_t m, float* out_dev, void* stream);
 
 /* Test surface of the segment head's tail.  Raw head rows of the three pyramid levels (strides 8 / 16 / 32), per level
  * (n, (imgsz / stride)^2, ct) floats, 16-byte aligned: 4 sides x 16 box bins at [0, 64), class logits at [cls, cls + nc),
@@ -279,6 +315,22 @@ MTGV_API int mtgv_mask_quads_logits(const float* logits_dev, int32_t n, int32_t 
 MTGV_API int mtgv_select_cards(const int32_t* n_det_dev, const float* boxes_dev, const float* pad_boxes_dev, int32_t frames,
                                int32_t max_det, int32_t k, float* sel_boxes_dev, float* quads_dev, int32_t* frame_idx_dev,
                                void* stream);
+
+/* The OBB counterpart: the K cards of every frame from mtgv_detector_forward_obb's outputs (n_det (frames), rboxes
+ * (frames, max_det, 5), conf, cls (frames, max_det), score-descending), as oriented quads.  Slot k of a frame is its k-th
+ * detection of class card_cls, or pad_boxes_dev[k] where the frame has fewer.  The reference labels card, card_top and
+ * card_bottom regions (od_datasets.py:244-257) "so we can compute this later" and never does; the rule is this library's:
+ * h := the long side (w > h: swap, angle += pi/2), u = (-sin, cos) the long axis, v = (cos, sin); the first top_cls
+ * detection in score order whose centre p lies inside the card (|d.v| <= w/2, |d.u| <= h/2, d = p - centre), accepted if
+ * d.u != 0, gives up U = sign(d.u) u; otherwise a bottom_cls detection likewise gives U = -sign(d.u) u; otherwise U is
+ * whichever of +-u has negative y (negative x when u.y == 0).  top_cls / bottom_cls = -1: class not used.  With
+ * R = (-U.y, U.x) the corners are centre +- U h/2 +- R w/2 in the order mtgv_warp_quads expects (TL, TR, BR, BL).
+ * Writes quads_dev (frames*k, 4, 2), sel_boxes_dev (frames*k, 4) the quads' axis-aligned bounds (the pad box itself for a
+ * pad), frame_idx_dev (frames*k) and state_dev (frames*k) int32: 0 pad, 1 unoriented, 2 oriented. */
+MTGV_API int mtgv_obb_cards(const int32_t* n_det_dev, const float* rboxes_dev, const float* conf_dev, const int32_t* cls_dev,
+                            const float* pad_boxes_dev, int32_t frames, int32_t max_det, int32_t k, int32_t card_cls, int32_t top_cls,
+                            int32_t bottom_cls, float* quads_dev, float* sel_boxes_dev, int32_t* frame_idx_dev, int32_t* state_dev,
+                            void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Crop: perspective de-warp of card quads.                                   */

@@ -1,5 +1,5 @@
-// YOLOv8n-seg / YOLO11n-seg executor: conv stack on the implicit GEMM of gemm_launch (split-precision f16x3 or f32),
-// decode, NMS, mask logits.
+// YOLOv8n / YOLO11n executor, -seg or -obb: conv stack on the implicit GEMM of gemm_launch (split-precision f16x3 or
+// f32), decode, NMS, mask logits (segment) or rotated decode, rotated NMS (OBB).
 #pragma once
 #include "common.h"
 #include "gemm_f32.h"
@@ -20,7 +20,8 @@ static inline int chn(int c) { return make_div8(std::min(c, 1024) * 0.25); }
 static inline int rep(int n) { return n > 1 ? std::max((int)lround(n * 0.33), 1) : n; }
 
 // raw head rows per anchor, four whole 128-byte lines: [0,64) box logits (4 sides x 16 bins), [64,96) mask coefficients,
-// [96,96+nc) class logits; the rest of the 32 columns behind RAW_CLS is the zero padding of the chained class conv
+// [96,96+nc) class logits; the rest of the 32 columns behind RAW_CLS is the zero padding of the chained class conv.
+// OBB: the angle logit at RAW_COEF, the other 31 coefficient columns are the zero outputs of its padded branch.
 static constexpr int RAW_CT = 128, RAW_COEF = 64, RAW_CLS = 96;
 
 struct ConvW {
@@ -92,11 +93,15 @@ class Detector {
   void finalize();
   void forward(const uint8_t* frames, int n, int flip, int* n_det, float* boxes, float* conf, int* cls, int* keep_idx,
                float* mask_logits, int mask_rows, hipStream_t s);
+  // OBB handle: forward + rotated decode + rotated NMS; rboxes (n, max_det, 5) xywh + angle
+  void forward_obb(const uint8_t* frames, int n, int flip, int* n_det, float* rboxes, float* conf, int* cls, int* keep_idx,
+                   hipStream_t s);
   void raw(int n, float* pred, float* protos, hipStream_t s);
   double flops_per_frame() const { return flops_; }
   const mtgv_detector_cfg& cfg() const { return cfg_; }
   int na() const { return na_; }
-  int no() const { return 4 + cfg_.nc + nm_; }
+  bool obb() const { return cfg_.task == MTGV_TASK_OBB; }
+  int no() const { return 4 + cfg_.nc + (obb() ? 1 : nm_); }
 
  private:
   struct Raw {
@@ -112,6 +117,7 @@ class Detector {
   ConvW fold(const std::string& prefix, int cin_pad = 0);           // Conv+BN
   ConvW plain(const std::string& prefix, int cout_pad = 0);         // Conv2d with bias (cout_pad: zero rows up to that many)
   ConvW concat_out(const std::vector<ConvW>& parts);                // stack along cout (same cin and k)
+  ConvW zero_pad(const ConvW& q, int cout, int cin);                // q with zero rows / input channels up to cout x cin
   float* upload(const std::vector<float>& v, int row_k = 0);  // row_k > 0: a GEMM B operand with rows of row_k floats
   void conv(const ConvW& w, const View& in, const View& out, int stride, int act, const View* res, int n, hipStream_t s);
   // Conv(w1, SiLU) followed by the 1x1 conv w2 (act2) with w1's output consumed on chip (gemm_sp_kernel.h, EPI 32): `mid` is
@@ -131,11 +137,12 @@ class Detector {
   struct ArenaBuf { const char* name; int h, w, c; bool f32 = false; };  // f32: View::f32
   std::vector<ArenaBuf> arena_v8() const;
   std::vector<ArenaBuf> arena_v11() const;
-  void plan_arena(const std::vector<ArenaBuf>& bufs);
+  void plan_arena(std::vector<ArenaBuf> all);
   void forward_v11(const uint8_t* frames, int n, int flip, hipStream_t s);
   void forward_v8(const uint8_t* frames, int n, int flip, hipStream_t s);
   HeadRows head_rows() const;                                       // the arena's raw head rows (head_decode.h)
-  void decode(int n, hipStream_t s);                                // decode_kernel: raw head rows -> pred
+  void decode(int n, hipStream_t s);                                // decode_kernel / decode_obb_kernel: raw head rows -> pred
+  void run_graph(const uint8_t* frames, int n, int flip, hipStream_t s);  // backbone, neck, head rows (+ prototype branch)
   void head_tail(int n, int* n_det, float* boxes, float* conf, int* cls, int* keep_idx, float* mask_logits, int mask_rows,
                  hipStream_t s);
   void conv0(const uint8_t* frames, int n, int flip, hipStream_t s);
@@ -144,6 +151,7 @@ class Detector {
   void proto(const std::string& head, const View& p3, int n, hipStream_t s);
   void head_level_v8(int l, int n, hipStream_t s);
   void head_level_v11(int l, int n, hipStream_t s);
+  void obb_flops_fix(const View& f);                                // count mode: the angle branch's real widths
   // Fork-join inside one forward (library-owned streams and events, library kernels only - the concurrency contract
   // of include/mtgv.h): the prototype branch and the P3 / P4 head branches leave the caller's stream as soon as their
   // input exists and rejoin it before decode / the mask product.  fork_after(s, i): side stream i starts after

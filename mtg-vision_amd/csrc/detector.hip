@@ -37,6 +37,7 @@ Detector::Detector(const mtgv_detector_cfg& cfg) : cfg_(cfg) {
   MTGV_CHECK(cfg.max_batch > 0, ERR_INVALID, "detector: max_batch=%d", cfg.max_batch);
   MTGV_CHECK(cfg.max_det > 0 && cfg.max_det <= 1024, ERR_INVALID, "detector: max_det=%d", cfg.max_det);
   MTGV_CHECK(cfg.arch == 0 || cfg.arch == 8 || cfg.arch == 11, ERR_KEY, "detector: arch=%d (8: YOLOv8n-seg, 11: YOLO11n-seg)", cfg.arch);
+  MTGV_CHECK(cfg.task == MTGV_TASK_SEGMENT || cfg.task == MTGV_TASK_OBB, ERR_KEY, "detector: task=%d (0: segment, 1: OBB)", cfg.task);
   const int S = cfg.imgsz;
   na_ = (S / 8) * (S / 8) + (S / 16) * (S / 16) + (S / 32) * (S / 32);
   // The branch streams of the forward's fork-join are created with the handle, not at the first forward: the HIP runtime maps
@@ -86,12 +87,14 @@ Detector::Detector(const mtgv_detector_cfg& cfg) : cfg_(cfg) {
 }
 
 // Segment head (Detect + Segment + Proto) on features of chs[0..2] channels: the keys both architectures share; only
-// the class branch cv3 differs
+// the class branch cv3 differs.  OBB head (Detect + angle branch): cv4 carries ne = 1 angle logit through
+// c4 = max(chs[0] / 4, ne) = 16 channels, and there is no Proto.
 void Detector::expect_head(const int chs[3]) {
   const int c2 = std::max(std::max(16, chs[0] / 4), reg_max_ * 4);
   const int c3 = std::max(chs[0], std::min(cfg_.nc, 100));
-  const int c4 = std::max(chs[0] / 4, nm_);
-  MTGV_CHECK(c2 == 64 && c3 == 64 && c4 == 32, ERR_INVALID, "detector: unexpected head widths");
+  const int n4 = obb() ? 1 : nm_;
+  const int c4 = std::max(chs[0] / 4, n4);
+  MTGV_CHECK(c2 == 64 && c3 == 64 && c4 == (obb() ? 16 : 32), ERR_INVALID, "detector: unexpected head widths");
   const std::string H = head_;
   for (int l = 0; l < 3; ++l) {
     const std::string ls = std::to_string(l);
@@ -113,10 +116,11 @@ void Detector::expect_head(const int chs[3]) {
     expect(H + ".cv3." + ls + ".2.bias", {cfg_.nc});
     expect_conv_bn(H + ".cv4." + ls + ".0", c4, chs[l], 3);
     expect_conv_bn(H + ".cv4." + ls + ".1", c4, c4, 3);
-    expect(H + ".cv4." + ls + ".2.weight", {nm_, c4, 1, 1});
-    expect(H + ".cv4." + ls + ".2.bias", {nm_});
+    expect(H + ".cv4." + ls + ".2.weight", {n4, c4, 1, 1});
+    expect(H + ".cv4." + ls + ".2.bias", {n4});
   }
   expect(H + ".dfl.conv.weight", {1, reg_max_, 1, 1});
+  if (obb()) return;
   expect_conv_bn(H + ".proto.cv1", npr_, chs[0], 3);
   expect(H + ".proto.upsample.weight", {npr_, npr_, 2, 2});
   expect(H + ".proto.upsample.bias", {npr_});
@@ -245,10 +249,35 @@ ConvW Detector::concat_out(const std::vector<ConvW>& parts) {
   return ConvW{upload(w, (int)per), upload(b), (int)b.size(), cin, k};
 }
 
+// q with zero output rows (zero bias) up to `cout` and zero input channels up to `cin`: SiLU(0) = 0, so a padded
+// channel stays zero through a Conv+SiLU chain and adds nothing to the real ones
+ConvW Detector::zero_pad(const ConvW& q, int cout, int cin) {
+  MTGV_CHECK(cout >= q.cout && cin >= q.cin, ERR_RUNTIME, "detector: zero_pad to a smaller conv");
+  const int kk = q.k * q.k;
+  std::vector<float> w0((size_t)q.cout * kk * q.cin), b(q.cout);
+  HIP_OK(hipMemcpy(w0.data(), q.w, w0.size() * sizeof(float), hipMemcpyDeviceToHost));
+  HIP_OK(hipMemcpy(b.data(), q.b, b.size() * sizeof(float), hipMemcpyDeviceToHost));
+  std::vector<float> w((size_t)cout * kk * cin, 0.f);
+  for (int o = 0; o < q.cout; ++o)
+    for (int t = 0; t < kk; ++t)
+      for (int i = 0; i < q.cin; ++i) w[((size_t)o * kk + t) * cin + i] = w0[((size_t)o * kk + t) * q.cin + i];
+  b.resize(cout, 0.f);
+  return ConvW{upload(w, kk * cin), upload(b), cout, cin, q.k};
+}
+
 // Carve the activation arena for max_batch frames: each buffer 256-byte aligned, in table order.  Cleared once: of the raw
 // head rows' 32 columns behind RAW_CLS, those past the classes are written by the chained class conv only (as zeros).
-void Detector::plan_arena(const std::vector<ArenaBuf>& bufs) {
+void Detector::plan_arena(std::vector<ArenaBuf> all) {
   auto floats = [&](const ArenaBuf& b) { return ((size_t)cfg_.max_batch * b.h * b.w * b.c + 63) / 64 * 64; };
+  if (obb()) {  // no prototype branch, no mask coefficients
+    std::vector<ArenaBuf> kept;
+    for (const ArenaBuf& b : all) {
+      const std::string nm = b.name;
+      if (nm != "pr1" && nm != "pr2" && nm != "pr3" && nm != "protos" && nm != "coef") kept.push_back(b);
+    }
+    all = kept;
+  }
+  const std::vector<ArenaBuf>& bufs = all;
   size_t total = 0;
   for (const ArenaBuf& b : bufs) total += floats(b);
   arena_.alloc(total);
@@ -286,7 +315,7 @@ std::vector<Detector::ArenaBuf> Detector::arena_v8() const {
       {"t1_2", s32, s32, 160}, {"t2_2", s32, s32, 160},
       {"rawhead0", s8, s8, RAW_CT, true}, {"rawhead1", s16, s16, RAW_CT, true}, {"rawhead2", s32, s32, RAW_CT, true},
       {"pr1", s8, s8, npr_}, {"pr2", s4, s4, npr_}, {"pr3", s4, s4, npr_}, {"protos", s4, s4, nm_, true},
-      {"pred", 1, na_, 4 + cfg_.nc + nm_, true}, {"coef", 1, cfg_.max_det, nm_, true},
+      {"pred", 1, na_, no(), true}, {"coef", 1, cfg_.max_det, nm_, true},
   };
 }
 
@@ -321,6 +350,9 @@ void Detector::finalize() {
   for (int l = 0; l < 3; ++l) {
     const std::string ls = std::to_string(l);
     const std::string B = H + ".cv2." + ls, C = H + ".cv3." + ls, M = H + ".cv4." + ls;  // box, class, coefficient branches
+    // OBB: the angle branch (16 mid channels, 1 output) zero-padded to the coefficient branch's widths (32, 32), so the
+    // head runs on the segment head's launches and the angle logit lands in column RAW_COEF of the rows
+    if (obb()) cw_[M + ".0"] = zero_pad(cw_.at(M + ".0"), nm_, cw_.at(M + ".0").cin);
     if (v11()) {
       // box and coefficient branches start with a 3x3 conv on the same input: one conv with 64+32 outputs
       head_first_[l] = concat_out({cw_.at(B + ".0"), cw_.at(M + ".0")});
@@ -332,13 +364,13 @@ void Detector::finalize() {
       head_cls2_[l] = cw_.at(C + ".1");
     }
     head_box2_[l] = cw_.at(B + ".1");
-    head_coef2_[l] = cw_.at(M + ".1");
+    head_coef2_[l] = obb() ? zero_pad(cw_.at(M + ".1"), nm_, nm_) : cw_.at(M + ".1");
     head_box3_[l] = plain(B + ".2");
     head_cls3_[l] = plain(C + ".2");
     // v8: the class branch's final 1x1 padded to a 32-column block (zero weights and bias past the classes), which the 3x3
     // before it can chain (gemm_sp_chain_ok wants N2 % 32 == 0)
     if (!v11()) head_cls3_pad_[l] = plain(C + ".2", 32);
-    head_coef3_[l] = plain(M + ".2");
+    head_coef3_[l] = obb() ? zero_pad(plain(M + ".2"), nm_, nm_) : plain(M + ".2");
   }
   // DFL weights must be arange(16) (they are a fixed buffer upstream); the decode kernel hard-codes them
   {
@@ -346,7 +378,7 @@ void Detector::finalize() {
     for (int i = 0; i < reg_max_; ++i) MTGV_CHECK(d[i] == (float)i, ERR_INVALID, "dfl.conv.weight is not arange(16)");
   }
   // the prototype branch behind cv1: the ConvTranspose's phase matrices, and its fold into cv2
-  {
+  if (!obb()) {
     const Raw& w = raw_.at(H + ".proto.upsample.weight");
     proto_w_ = proto_tail_weights(w.data.data(), raw_.at(H + ".proto.upsample.bias").data.data(), w.shape[0], w.shape[1],
                                   cw_.at(H + ".proto.cv2"), cw_.at(H + ".proto.cv3"), dev_allocs_);
@@ -361,7 +393,7 @@ void Detector::finalize() {
   // algorithmic FLOPs of one frame: run the plan once in counting mode
   count_flops_ = true;
   flops_ = 0;
-  forward(nullptr, 1, 0, nullptr, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr);
+  run_graph(nullptr, 1, 0, nullptr);
   count_flops_ = false;
 }
 
@@ -481,7 +513,13 @@ HeadRows Detector::head_rows() const {
 
 // the raw head rows of the first n frames -> pred
 void Detector::decode(int n, hipStream_t s) {
-  decode_launch(head_rows(), n, cfg_.nc, nm_, v_.at("pred").p, s);
+  if (obb()) {
+    const long tot = (long)n * na_;
+    hipLaunchKernelGGL(decode_obb_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, head_rows(), v_.at("pred").p, n, cfg_.nc, na_);
+    HIP_OK(hipGetLastError());
+  } else {
+    decode_launch(head_rows(), n, cfg_.nc, nm_, v_.at("pred").p, s);
+  }
   pred_n_ = n;
 }
 
@@ -531,11 +569,30 @@ void Detector::head_tail(int n, int* n_det, float* boxes, float* conf, int* cls,
 void Detector::forward(const uint8_t* frames, int n, int flip, int* n_det, float* boxes, float* conf, int* cls, int* keep_idx,
                        float* mask_logits, int mask_rows, hipStream_t s) {
   MTGV_CHECK(finalized_, ERR_RUNTIME, "detector: finalize() has not been called");
-  if (!count_flops_) {
-    MTGV_CHECK(n > 0 && n <= cfg_.max_batch, ERR_INVALID, "batch %d outside [1, %d]", n, cfg_.max_batch);
-    MTGV_CHECK(frames && n_det && boxes && conf && cls && keep_idx, ERR_INVALID, "null tensor");
-    MTGV_CHECK(mask_logits == nullptr || (mask_rows > 0 && mask_rows <= cfg_.max_det), ERR_INVALID, "mask_rows=%d", mask_rows);
-  }
+  MTGV_CHECK(!obb(), ERR_INVALID, "mtgv_detector_forward on an OBB handle (task 1): call mtgv_detector_forward_obb");
+  MTGV_CHECK(n > 0 && n <= cfg_.max_batch, ERR_INVALID, "batch %d outside [1, %d]", n, cfg_.max_batch);
+  MTGV_CHECK(frames && n_det && boxes && conf && cls && keep_idx, ERR_INVALID, "null tensor");
+  MTGV_CHECK(mask_logits == nullptr || (mask_rows > 0 && mask_rows <= cfg_.max_det), ERR_INVALID, "mask_rows=%d", mask_rows);
+  run_graph(frames, n, flip, s);
+  head_tail(n, n_det, boxes, conf, cls, keep_idx, mask_logits, mask_rows, s);
+  last_n_ = n;
+}
+
+// OBB: the same graph without the prototype branch, then decode every anchor and rotated NMS on `pred`
+void Detector::forward_obb(const uint8_t* frames, int n, int flip, int* n_det, float* rboxes, float* conf, int* cls, int* keep_idx,
+                           hipStream_t s) {
+  MTGV_CHECK(finalized_, ERR_RUNTIME, "detector: finalize() has not been called");
+  MTGV_CHECK(obb(), ERR_INVALID, "mtgv_detector_forward_obb on a segment handle (task 0): call mtgv_detector_forward");
+  MTGV_CHECK(n > 0 && n <= cfg_.max_batch, ERR_INVALID, "batch %d outside [1, %d]", n, cfg_.max_batch);
+  MTGV_CHECK(frames && n_det && rboxes && conf && cls && keep_idx, ERR_INVALID, "null tensor");
+  run_graph(frames, n, flip, s);
+  decode(n, s);
+  nms_rotated_launch(v_.at("pred").p, n, cfg_.nc, na_, cfg_.conf, cfg_.iou, cfg_.max_det, 7680.0f, n_det, rboxes, conf, cls, keep_idx, nms_ws_,
+                     nms_ws_bytes_, s);
+  last_n_ = n;
+}
+
+void Detector::run_graph(const uint8_t* frames, int n, int flip, hipStream_t s) {
   // f16x3 on the LDS-DMA kernel: every intermediate activation is kept in SP8; the frame, the raw head rows and the
   // prototypes (decode / mask inputs) stay f32
   fmt_ = (!count_flops_ && gemm_sp_active()) ? 1 : 0;
@@ -545,9 +602,6 @@ void Detector::forward(const uint8_t* frames, int n, int flip, int* n_det, float
   } else {
     forward_v8(frames, n, flip, s);
   }
-  if (count_flops_) return;
-  head_tail(n, n_det, boxes, conf, cls, keep_idx, mask_logits, mask_rows, s);
-  last_n_ = n;
 }
 
 // SPPF: cv1, three chained 5x5 max pools, cv2 over the concat
@@ -605,7 +659,7 @@ void Detector::forward_v8(const uint8_t* frames, int n, int flip, hipStream_t s)
   c2f(15, cat14, V("p3"), n, s);
   // P3 exists: the prototype branch (0.5 ms of chip-filling launches) and the P3 head leave the caller's stream; the
   // rest of the neck - 100..400-tile launches that cannot fill 256 CUs on their own - runs beside them
-  proto(head_, V("p3"), n, fork_after(s, 0));
+  if (!obb()) proto(head_, V("p3"), n, fork_after(s, 0));
   head_level_v8(0, n, fork_after(s, 1));
   conv(cw_.at("model.16"), V("p3"), cat17.slice(0, c64), 2, ACT_SILU, nullptr, n, s);
   c2f(18, cat17, V("p4"), n, s);
@@ -635,10 +689,21 @@ void Detector::head_level_v8(int l, int n, hipStream_t s) {
     conv(head_cls3_[l], t2.slice(64, 64), rh.slice(RAW_CLS, cfg_.nc), 1, ACT_NONE, nullptr, n, s);
   }
   conv_pair(head_coef2_[l], t1.slice(128, 32), t2.slice(128, 32), 1, head_coef3_[l], rh.slice(RAW_COEF, nm_), ACT_NONE, n, s);
+  obb_flops_fix(f);
+}
+
+// the OBB angle branch runs zero-padded to the coefficient branch's widths; the algorithmic count is of the real
+// 16 -> 16 -> 1 branch
+void Detector::obb_flops_fix(const View& f) {
+  if (!count_flops_ || !obb()) return;
+  const double px = (double)f.H * f.W;
+  const int c4 = 16, ne = 1;
+  flops_ -= 2.0 * px * (9.0 * f.C * (nm_ - c4) + 9.0 * (nm_ * nm_ - c4 * c4) + (nm_ * nm_ - c4 * ne));
 }
 
 void Detector::raw(int n, float* pred, float* protos, hipStream_t s) {
   MTGV_CHECK(n > 0 && n <= last_n_, ERR_INVALID, "raw: n=%d but the last forward had %d frames", n, last_n_);
+  MTGV_CHECK(!obb() || protos == nullptr, ERR_INVALID, "raw: an OBB handle has no prototypes (protos_dev must be NULL)");
   if (pred && pred_n_ < n) decode(n, s);  // the last forward ran NMS straight from the head rows
   if (pred) HIP_OK(hipMemcpyAsync(pred, v_.at("pred").p, (size_t)n * no() * na_ * sizeof(float), hipMemcpyDeviceToDevice, s));
   if (protos) {
@@ -688,6 +753,13 @@ MTGV_API int mtgv_detector_forward(mtgv_detector* h, const uint8_t* frames_dev, 
     MTGV_CHECK(h != nullptr, ERR_INVALID, "null handle");
     h->impl.forward(frames_dev, n, flip_rgb, n_det_dev, boxes_dev, conf_dev, cls_dev, keep_idx_dev, mask_logits_dev, mask_rows,
                     (hipStream_t)stream);
+  });
+}
+MTGV_API int mtgv_detector_forward_obb(mtgv_detector* h, const uint8_t* frames_dev, int32_t n, int32_t flip_rgb, int32_t* n_det_dev,
+                                       float* rboxes_dev, float* conf_dev, int32_t* cls_dev, int32_t* keep_idx_dev, void* stream) {
+  return guarded([&] {
+    MTGV_CHECK(h != nullptr, ERR_INVALID, "null handle");
+    h->impl.forward_obb(frames_dev, n, flip_rgb, n_det_dev, rboxes_dev, conf_dev, cls_dev, keep_idx_dev, (hipStream_t)stream);
   });
 }
 MTGV_API int mtgv_detector_raw(mtgv_detector* h, int32_t n, float* pred_dev, float* protos_dev, void* stream) {

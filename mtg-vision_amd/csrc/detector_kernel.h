@@ -1,5 +1,5 @@
 // The detector's own device kernels (detector.hip launches them; the convolutions are gemm_launch's, gemm_f32.h):
-//   decode_kernel, nhwc_to_nchw_kernel, mask_binarize_kernel, conv0_u8_kernel, maxpool5_sp8_kernel,
+//   decode_kernel, decode_obb_kernel, nhwc_to_nchw_kernel, mask_binarize_kernel, conv0_u8_kernel, maxpool5_sp8_kernel,
 //   sppf_pools_sp8_kernel, mask_logits_kernel
 #pragma once
 #include "act.h"
@@ -38,6 +38,23 @@ __global__ __launch_bounds__(256) void decode_kernel(HeadRows h, float* __restri
       for (int e = 0; c + e < nm; ++e) P[(long)(4 + nc + c + e) * na] = row[h.coef + c + e];
     }
   }
+}
+
+// OBB decode: head rows -> pred (n, 4 + nc + 1, na) = xywh in pixels, class sigmoids, angle (head_decode.h: head_rbox)
+__global__ __launch_bounds__(256) void decode_obb_kernel(HeadRows h, float* __restrict__ pred, int n, int nc, int na) {
+  const long idx = (long)blockIdx.x * 256 + threadIdx.x;
+  if (idx >= (long)n * na) return;
+  const int img = (int)(idx / na), a = (int)(idx % na);
+  const HeadAnchor an = head_anchor(h, img, a);
+  float r[5];
+  head_rbox(an, an.row[h.coef], r);
+  float* P = pred + (long)img * (5 + nc) * na + a;
+  P[0] = r[0];
+  P[(long)na] = r[1];
+  P[(long)2 * na] = r[2];
+  P[(long)3 * na] = r[3];
+  for (int c = 0; c < nc; ++c) P[(long)(4 + c) * na] = head_score(an.row[h.cls + c]);
+  P[(long)(4 + nc) * na] = r[4];
 }
 
 // NHWC -> NCHW (raw protos for parity tests)

@@ -277,7 +277,7 @@ std::vector<Detector::ArenaBuf> Detector::arena_v11() const {
       {"t1_2", s32, s32, 96}, {"t2_2", s32, s32, 96}, {"dwa_2", s32, s32, c256}, {"dwb_2", s32, s32, 64}, {"dwc_2", s32, s32, 64}, {"dwd_2", s32, s32, 64},
       {"pr1", s8, s8, npr_}, {"pr2", s4, s4, npr_}, {"pr3", s4, s4, npr_}, {"protos", s4, s4, nm_, true},
       {"rawhead0", s8, s8, RAW_CT, true}, {"rawhead1", s16, s16, RAW_CT, true}, {"rawhead2", s32, s32, RAW_CT, true},
-      {"pred", 1, na_, 4 + cfg_.nc + nm_, true}, {"coef", 1, cfg_.max_det, nm_, true},
+      {"pred", 1, na_, no(), true}, {"coef", 1, cfg_.max_det, nm_, true},
   };
 }
 
@@ -371,7 +371,7 @@ void Detector::forward_v11(const uint8_t* frames, int n, int flip, hipStream_t s
   upsample2x(n13, cat15, n, s);
   c3k2(16, cat15, V("p3"), n, s);
   // the same fork-join as forward_v8: prototype branch and P3 / P4 heads beside the rest of the neck
-  proto(head_, V("p3"), n, fork_after(s, 0));
+  if (!obb()) proto(head_, V("p3"), n, fork_after(s, 0));
   head_level_v11(0, n, fork_after(s, 1));
   conv(cw_.at("model.17"), V("p3"), cat18.slice(0, c64), 2, ACT_SILU, nullptr, n, s);
   c3k2(19, cat18, V("p4"), n, s);
@@ -398,6 +398,7 @@ void Detector::head_level_v11(int l, int n, hipStream_t s) {
   dwconv(cls_dw2_[l], db, dc, ACT_SILU, nullptr, 0, 0, n, s);
   conv(cls_pw2_[l], dc, dd, 1, ACT_SILU, nullptr, n, s);
   conv(head_cls3_[l], dd, rh.slice(RAW_CLS, cfg_.nc), 1, ACT_NONE, nullptr, n, s);
+  obb_flops_fix(f);
 }
 
 }  // namespace mtgv

@@ -1,6 +1,6 @@
 // The per-anchor decode of the segment head's raw rows, defined once for its two users: decode_kernel
 // (detector_kernel.h), which writes `pred` for every anchor, and the row form of nms_kernel (nms.hip), which decodes
-// the candidates only.  Both must give the same bits, so nothing here is left to the compiler's contraction: the
+// the candidates only.  The OBB head's decode (decode_obb_kernel) shares the DFL distances.  Both must give the same bits, so nothing here is left to the compiler's contraction: the
 // function bodies are compiled with contraction off and the one fused operation - the expectation's accumulate, which
 // is what decode_kernel compiled to when it was written in plain expressions - is spelled __builtin_fmaf.
 #pragma once
@@ -42,10 +42,9 @@ __device__ __forceinline__ HeadAnchor head_anchor(const HeadRows& h, int img, in
   return an;
 }
 
-// DFL: per side the softmax over 16 bins and its expectation; ltrb around the anchor centre -> xywh * stride
-__device__ __forceinline__ void head_box(const HeadAnchor& an, float xywh[4]) {
+// DFL: per side the softmax over 16 bins and its expectation -> the distances l, t, r, b in grid units
+__device__ __forceinline__ void head_dfl(const HeadAnchor& an, float d[4]) {
 #pragma clang fp contract(off)
-  float d[4];
 #pragma unroll
   for (int s = 0; s < 4; ++s) {
     float v[16];
@@ -70,6 +69,13 @@ __device__ __forceinline__ void head_box(const HeadAnchor& an, float xywh[4]) {
     for (int i = 0; i < 16; ++i) e = __builtin_fmaf(v[i] / sum, (float)i, e);
     d[s] = e;
   }
+}
+
+// segment / detect box: ltrb around the anchor centre -> xywh * stride
+__device__ __forceinline__ void head_box(const HeadAnchor& an, float xywh[4]) {
+#pragma clang fp contract(off)
+  float d[4];
+  head_dfl(an, d);
   const float ax = (float)(an.pix % an.gw) + 0.5f, ay = (float)(an.pix / an.gw) + 0.5f;
   const float x1 = ax - d[0], y1 = ay - d[1], x2 = ax + d[2], y2 = ay + d[3];
   xywh[0] = (x1 + x2) / 2.f * an.stride;
@@ -82,6 +88,24 @@ __device__ __forceinline__ void head_box(const HeadAnchor& an, float xywh[4]) {
 __device__ __forceinline__ float head_score(float logit) {
 #pragma clang fp contract(off)
   return 1.0f / (1.0f + expf(-logit));
+}
+
+// OBB head (ultralytics 8.3.x OBB.forward + dist2rbox) [external - recalled]: the angle logit sits where the segment head
+// keeps its first mask coefficient (row[h.coef]); angle = (sigmoid(logit) - 0.25) pi in [-pi/4, 3 pi/4); the box centre is
+// the anchor centre plus the DFL box's own centre offset rotated by the angle.  xywhr: x, y, w, h in pixels, angle in rad.
+__device__ __forceinline__ void head_rbox(const HeadAnchor& an, float angle_logit, float xywhr[5]) {
+#pragma clang fp contract(off)
+  float d[4];
+  head_dfl(an, d);
+  const float angle = (head_score(angle_logit) - 0.25f) * 3.14159274101257324f;
+  const float cs = cosf(angle), sn = sinf(angle);
+  const float ax = (float)(an.pix % an.gw) + 0.5f, ay = (float)(an.pix / an.gw) + 0.5f;
+  const float xf = (d[2] - d[0]) / 2.f, yf = (d[3] - d[1]) / 2.f;
+  xywhr[0] = (xf * cs - yf * sn + ax) * an.stride;
+  xywhr[1] = (xf * sn + yf * cs + ay) * an.stride;
+  xywhr[2] = (d[0] + d[2]) * an.stride;
+  xywhr[3] = (d[1] + d[3]) * an.stride;
+  xywhr[4] = angle;
 }
 
 }  // namespace mtgv

@@ -12,6 +12,7 @@ _LAZY = {
     "Encoder": ("encoder", "Encoder"),
     "Detector": ("detector", "Detector"),
     "Detections": ("detector", "Detections"),
+    "ObbDetections": ("detector", "ObbDetections"),
     "Matcher": ("matcher", "Matcher"),
     "merge_topk": ("matcher", "merge_topk"),
     "Pipeline": ("pipeline", "Pipeline"),

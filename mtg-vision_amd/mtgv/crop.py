@@ -64,6 +64,32 @@ def select_cards(n_det: torch.Tensor, boxes: torch.Tensor, pad_boxes: torch.Tens
     return sel, quads, fidx
 
 
+def obb_cards(n_det: torch.Tensor, rboxes: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor, pad_boxes: torch.Tensor, k: int,
+              card_cls: int = 0, top_cls: int = 1, bottom_cls: int = 2):
+    """The K cards per frame of an OBB detector's padded outputs (n_det (F,), rboxes (F, max_det, 5), conf, cls (F, max_det),
+    score-descending) as oriented quads, in one library kernel (mtgv_obb_cards; the orientation rule is this library's,
+    DESIGN.md section 3): slot k is the frame's k-th `card_cls` detection, turned so that a `top_cls` / `bottom_cls`
+    detection inside it marks its top / bottom, or pad_boxes[k] where the frame has fewer.  top_cls / bottom_cls -1: unused.
+    -> (quads (F*K, 4, 2) TL TR BR BL, sel_boxes (F*K, 4) xyxy bounds, frame_idx (F*K,) int32, state (F*K,) int32:
+    0 pad, 1 unoriented, 2 oriented)."""
+    native.require_gpu()
+    F, md = rboxes.shape[0], rboxes.shape[1]
+    dev = rboxes.device
+    assert n_det.dtype == torch.int32 and cls.dtype == torch.int32 and rboxes.dtype == torch.float32 and conf.dtype == torch.float32
+    assert tuple(rboxes.shape) == (F, md, 5) and tuple(cls.shape) == (F, md) and tuple(conf.shape) == (F, md) and tuple(pad_boxes.shape) == (k, 4)
+    quads = torch.empty((F * k, 4, 2), dtype=torch.float32, device=dev)
+    sel = torch.empty((F * k, 4), dtype=torch.float32, device=dev)
+    fidx = torch.empty((F * k,), dtype=torch.int32, device=dev)
+    state = torch.empty((F * k,), dtype=torch.int32, device=dev)
+    if F == 0:
+        return quads, sel, fidx, state
+    with torch.cuda.device(dev):
+        native.check(native.lib().mtgv_obb_cards(native.ptr(n_det), native.ptr(rboxes.contiguous()), native.ptr(conf.contiguous()),
+                                                 native.ptr(cls.contiguous()), native.ptr(pad_boxes), F, md, k, card_cls, top_cls, bottom_cls,
+                                                 native.ptr(quads), native.ptr(sel), native.ptr(fidx), native.ptr(state), native.stream()))
+    return quads, sel, fidx, state
+
+
 def boxes_to_quads(boxes_xyxy: torch.Tensor) -> torch.Tensor:
     """(n, 4) xyxy -> (n, 4, 2) corners in the order extract_dewarped matches to [[0,0],[w,0],[w,h],[0,h]]."""
     x1, y1, x2, y2 = boxes_xyxy.unbind(-1)

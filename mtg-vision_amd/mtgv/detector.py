@@ -1,4 +1,5 @@
-"""Host side of the detect stage: YOLOv8n-seg forward + decode + NMS + mask logits on the GPU.
+"""Host side of the detect stage: YOLOv8n / YOLO11n forward + decode + NMS on the GPU - the segment family with mask
+logits, the OBB family (`DetectorConfig(task="obb")`) with rotated boxes and rotated NMS.
 
 `Detector.detect(frame)` is the north-star name; the reference's boundary is
 `CardSegmenter(model_path)(rgb_im) -> list[InstanceSeg]` (mtgvision/od_export.py:141-160), which
@@ -26,6 +27,16 @@ class Detections:
     cls: torch.Tensor  # (n,) int64
     keep_idx: torch.Tensor  # (n,) int64 anchor index in [0, 8400)
     mask_logits: Optional[torch.Tensor]  # (n, 160, 160) float32, zero outside the box
+
+
+@dataclass
+class ObbDetections:
+    """Raw per-frame output of an OBB detector (score-descending)."""
+
+    rboxes: torch.Tensor  # (n, 5) float32: x, y, w, h in pixels of the letterboxed frame, angle in radians [-pi/4, 3pi/4)
+    conf: torch.Tensor  # (n,) float32
+    cls: torch.Tensor  # (n,) int64
+    keep_idx: torch.Tensor  # (n,) int64 anchor index
 
 
 def letterbox_geometry(h: int, w: int, size: int = 640):
@@ -90,6 +101,7 @@ class Detector:
         c.nc, c.imgsz, c.max_batch = self.cfg.nc, self.cfg.imgsz, self.max_batch
         c.conf, c.iou, c.max_det = self.cfg.conf, self.cfg.iou, self.cfg.max_det
         c.arch = 11 if self.cfg.arch == "11" else 8
+        c.task = 1 if self.cfg.task == "obb" else 0
         self._h = native.c_vp(0)
         with torch.cuda.device(self.device):
             native.check(native.lib().mtgv_detector_create(C.byref(c), C.byref(self._h)))
@@ -117,12 +129,16 @@ class Detector:
         """frames (n, 640, 640, 3) uint8 on the GPU -> dict of padded device tensors.
 
         n_det (n,) int32; boxes (n, max_det, 4); conf (n, max_det); cls, keep_idx (n, max_det) int32;
-        mask_logits (n, mask_rows, 160, 160) if mask_rows > 0."""
+        mask_logits (n, mask_rows, 160, 160) if mask_rows > 0.
+        An OBB detector returns n_det, rboxes (n, max_det, 5) xywh + angle, conf, cls, keep_idx; it has no masks and
+        ignores mask_rows."""
         S, md = self.cfg.imgsz, self.cfg.max_det
         assert frames_u8.dtype == torch.uint8 and frames_u8.is_cuda and tuple(frames_u8.shape[1:]) == (S, S, 3), f"{tuple(frames_u8.shape)}"
         n = frames_u8.shape[0]
         assert 0 < n <= self.max_batch, f"batch {n} outside [1, {self.max_batch}]"
         dev = self.device
+        if self.cfg.task == "obb":
+            return self._forward_obb(frames_u8, n, flip_rgb)
         # every element is written by the library (slots / mask rows beyond n_det as zeros): no fill kernels here
         out = {
             "n_det": torch.empty((n,), dtype=torch.int32, device=dev),
@@ -141,26 +157,54 @@ class Detector:
             )
         return out
 
+    def _forward_obb(self, frames_u8: torch.Tensor, n: int, flip_rgb: bool):
+        md, dev = self.cfg.max_det, self.device
+        out = {
+            "n_det": torch.empty((n,), dtype=torch.int32, device=dev),
+            "rboxes": torch.empty((n, md, 5), dtype=torch.float32, device=dev),
+            "conf": torch.empty((n, md), dtype=torch.float32, device=dev),
+            "cls": torch.empty((n, md), dtype=torch.int32, device=dev),
+            "keep_idx": torch.empty((n, md), dtype=torch.int32, device=dev),
+        }
+        with torch.cuda.device(dev):
+            native.check(
+                native.lib().mtgv_detector_forward_obb(
+                    self._h, native.ptr(frames_u8.contiguous()), n, 1 if flip_rgb else 0, native.ptr(out["n_det"]), native.ptr(out["rboxes"]),
+                    native.ptr(out["conf"]), native.ptr(out["cls"]), native.ptr(out["keep_idx"]), native.stream(),
+                )
+            )
+        return out
+
     def set_fork(self, mode: int):
         """the forward's internal fork-join: 1 on, 0 off, -1 the default (on unless MTGV_DET_FORK=0); mtgv_detector_set_fork"""
         native.check(native.lib().mtgv_detector_set_fork(self._h, int(mode)))
 
     def raw_outputs(self, n: int):
-        """pred (n, 4+nc+32, 8400) and protos (n, 32, 160, 160) of the last forward (parity tests)."""
+        """pred (n, 4+nc+32, 8400) and protos (n, 32, 160, 160) of the last forward (parity tests); an OBB detector
+        gives (pred (n, 4+nc+1, 8400), None)."""
         S = self.cfg.imgsz
         pred = torch.empty((n, self.cfg.no, self.cfg.num_anchors), dtype=torch.float32, device=self.device)
+        if self.cfg.task == "obb":
+            with torch.cuda.device(self.device):
+                native.check(native.lib().mtgv_detector_raw(self._h, n, native.ptr(pred), native.c_vp(0), native.stream()))
+            return pred, None
         protos = torch.empty((n, self.cfg.nm, S // 4, S // 4), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             native.check(native.lib().mtgv_detector_raw(self._h, n, native.ptr(pred), native.ptr(protos), native.stream()))
         return pred, protos
 
     # ---- single-frame API -------------------------------------------------------
-    def detect(self, frame: np.ndarray, flip_rgb: bool = True, masks: bool = True) -> Detections:
-        """One HWC uint8 frame (any size) -> Detections in letterboxed 640x640 coordinates."""
+    def detect(self, frame: np.ndarray, flip_rgb: bool = True, masks: bool = True):
+        """One HWC uint8 frame (any size) -> Detections (ObbDetections from an OBB detector) in letterboxed 640x640
+        coordinates."""
         assert frame.ndim == 3 and frame.shape[-1] == 3 and frame.dtype == np.uint8, f"{frame.shape} {frame.dtype}"
         # the raw frame goes to the GPU as it is; scale-to-fit + pad there (the host `letterbox` only supplies the geometry
         # to callers that map coordinates back, e.g. CardSegmenter)
         x, _, _ = letterbox_device(torch.from_numpy(np.ascontiguousarray(frame)).to(self.device), self.cfg.imgsz)
+        if self.cfg.task == "obb":
+            out = self.forward(x, flip_rgb)
+            n = int(out["n_det"][0].item())
+            return ObbDetections(out["rboxes"][0, :n], out["conf"][0, :n], out["cls"][0, :n].long(), out["keep_idx"][0, :n].long())
         out = self.forward(x, flip_rgb, self.cfg.max_det if masks else 0)
         n = int(out["n_det"][0].item())
         return Detections(
@@ -206,6 +250,42 @@ def nms(pred: torch.Tensor, nc: int, conf: float = 0.25, iou: float = 0.7, max_d
             L.mtgv_nms(native.ptr(pred), n, nc, nm, na, conf, iou, max_det, max_wh, native.ptr(out["n_det"]), native.ptr(out["boxes"]),
                        native.ptr(out["conf"]), native.ptr(out["cls"]), native.ptr(out["keep_idx"]), native.ptr(ws), ws.numel() * 4, native.stream())
         )
+    return out
+
+
+def nms_rotated(pred: torch.Tensor, nc: int, conf: float = 0.25, iou: float = 0.7, max_det: int = 300, max_wh: float = 7680.0):
+    """Stand-alone rotated NMS kernel on OBB predictions (n, 4+nc+1, A) [xywh, class scores, angle] -> padded tensors like
+    an OBB Detector.forward: n_det, rboxes (n, max_det, 5), conf, cls, keep_idx."""
+    native.require_gpu()
+    assert pred.is_cuda and pred.dtype == torch.float32 and pred.ndim == 3 and pred.shape[1] == 4 + nc + 1, f"{tuple(pred.shape)}"
+    pred = pred.contiguous()
+    n, _, na = pred.shape
+    dev = pred.device
+    L = native.lib()
+    ws = torch.empty((int(L.mtgv_nms_rotated_workspace_bytes(n, na)) + 3) // 4, dtype=torch.int32, device=dev)
+    out = {
+        "n_det": torch.empty((n,), dtype=torch.int32, device=dev),
+        "rboxes": torch.empty((n, max_det, 5), dtype=torch.float32, device=dev),
+        "conf": torch.empty((n, max_det), dtype=torch.float32, device=dev),
+        "cls": torch.empty((n, max_det), dtype=torch.int32, device=dev),
+        "keep_idx": torch.empty((n, max_det), dtype=torch.int32, device=dev),
+    }
+    with torch.cuda.device(dev):
+        native.check(
+            L.mtgv_nms_rotated(native.ptr(pred), n, nc, na, conf, iou, max_det, max_wh, native.ptr(out["n_det"]), native.ptr(out["rboxes"]),
+                               native.ptr(out["conf"]), native.ptr(out["cls"]), native.ptr(out["keep_idx"]), native.ptr(ws), ws.numel() * 4, native.stream())
+        )
+    return out
+
+
+def probiou(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
+    """ProbIoU of the box pairs a[i], b[i] ((m, 5) x, y, w, h, angle each): the pair function of `nms_rotated` (test surface)"""
+    native.require_gpu()
+    assert a.is_cuda and a.dtype == torch.float32 and a.ndim == 2 and a.shape[1] == 5 and a.shape == b.shape and b.dtype == torch.float32
+    a, b = a.contiguous(), b.to(a.device).contiguous()
+    out = torch.empty((a.shape[0],), dtype=torch.float32, device=a.device)
+    with torch.cuda.device(a.device):
+        native.check(native.lib().mtgv_op_probiou(native.ptr(a), native.ptr(b), a.shape[0], native.ptr(out), native.stream()))
     return out
 
 

@@ -6,7 +6,8 @@ The reference exports its trained detector with `YOLO(pt).export(format="onnx", 
 `.export(format="coreml", nms=False)` (mtgvision/od_export.py:163-176); ultralytics and coremltools are absent here, so
 this module mirrors the `nms=False` form: frames (B, 3, 640, 640) float in [0, 1] -> (pred (B, 4 + nc + nm, A) decoded
 boxes / class scores / mask coefficients, protos (B, nm, 160, 160)).  NMS and mask assembly stay outside the graph
-(`mtgv.detector.nms`, `Detector.forward`).
+(`mtgv.detector.nms`, `Detector.forward`).  With `task="obb"` (what od_train.py builds by default) the head is `OBB` and
+the only output is pred (B, 4 + nc + 1, A) = xywh, class scores, angle (`mtgv.detector.nms_rotated` outside the graph).
 
 NOT on the recognition path: `mtgv.Detector` never calls it and there is no fallback to it.  Checked on CPU against
 oracle/detector_ref.py (tests/test_export_cpu.py).
@@ -212,6 +213,54 @@ class Segment(nn.Module):
         return torch.cat((dbox, cls.sigmoid(), mc), 1), protos
 
 
+class OBB(nn.Module):
+    """OBB head (Detect + one angle logit per anchor), inference form: pred (B, 4 + nc + 1, A) = xywh in pixels, class
+    sigmoids, angle in radians.  [external - recalled from ultralytics 8.3.x OBB.forward / dist2rbox; unpinned]"""
+
+    def __init__(self, cfg: spec.DetectorConfig, ch):
+        super().__init__()
+        self.cfg = cfg
+        nc, ne, rm = cfg.nc, cfg.ne, cfg.reg_max
+        c2 = max(16, ch[0] // 4, rm * 4)
+        c3 = max(ch[0], min(nc, 100))
+        c4 = max(ch[0] // 4, ne)
+        self.cv2 = nn.ModuleList(nn.Sequential(Conv(x, c2, 3), Conv(c2, c2, 3), nn.Conv2d(c2, 4 * rm, 1)) for x in ch)
+        if cfg.arch == "11":
+            self.cv3 = nn.ModuleList(
+                nn.Sequential(nn.Sequential(Conv(x, x, 3, g=x), Conv(x, c3, 1)), nn.Sequential(Conv(c3, c3, 3, g=c3), Conv(c3, c3, 1)), nn.Conv2d(c3, nc, 1))
+                for x in ch
+            )
+        else:
+            self.cv3 = nn.ModuleList(nn.Sequential(Conv(x, c3, 3), Conv(c3, c3, 3), nn.Conv2d(c3, nc, 1)) for x in ch)
+        self.dfl = _DFL(rm)
+        self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), nn.Conv2d(c4, ne, 1)) for x in ch)
+        pts, st = [], []
+        for s in (8, 16, 32):
+            n = cfg.imgsz // s
+            sx = torch.arange(n, dtype=torch.float32) + 0.5
+            sy, sxx = torch.meshgrid(sx, sx, indexing="ij")
+            pts.append(torch.stack((sxx, sy), -1).view(-1, 2))
+            st.append(torch.full((n * n, 1), float(s)))
+        self.anchors: torch.Tensor
+        self.strides: torch.Tensor
+        self.register_buffer("anchors", torch.cat(pts).T.contiguous(), persistent=False)
+        self.register_buffer("strides", torch.cat(st).T.contiguous(), persistent=False)
+
+    def forward(self, feats):
+        cfg = self.cfg
+        b = feats[0].shape[0]
+        angle = torch.cat([self.cv4[i](f).view(b, cfg.ne, -1) for i, f in enumerate(feats)], 2)
+        angle = (angle.sigmoid() - 0.25) * torch.pi
+        x = torch.cat([torch.cat((self.cv2[i](f), self.cv3[i](f)), 1).view(b, 4 * cfg.reg_max + cfg.nc, -1) for i, f in enumerate(feats)], 2)
+        box, cls = x.split((4 * cfg.reg_max, cfg.nc), 1)
+        lt, rb = self.dfl(box).chunk(2, 1)
+        cos, sin = torch.cos(angle), torch.sin(angle)
+        xf, yf = ((rb - lt) / 2).split(1, 1)
+        xy = torch.cat((xf * cos - yf * sin, xf * sin + yf * cos), 1) + self.anchors.unsqueeze(0)
+        dbox = torch.cat((xy, lt + rb), 1) * self.strides
+        return torch.cat((dbox, cls.sigmoid(), angle), 1)
+
+
 class DetectorModule(nn.Module):
     """`self.model` is an nn.ModuleList indexed like ultralytics' `model.model`: same state_dict keys."""
 
@@ -240,7 +289,7 @@ class DetectorModule(nn.Module):
                 raise KeyError(kind)
             chans[idx] = prev
             mods.append(m)
-        mods.append(Segment(cfg, [chans[f] for f in feats]))
+        mods.append((OBB if cfg.task == "obb" else Segment)(cfg, [chans[f] for f in feats]))
         self.model = nn.ModuleList(mods)
 
     def forward(self, x):
@@ -276,4 +325,5 @@ def export_onnx(cfg: spec.DetectorConfig, state_dict: Mapping, path: str):
         raise RuntimeError("the onnx package is not installed")
     m = to_torch_module(cfg, state_dict)
     ex = torch.rand((1, 3, cfg.imgsz, cfg.imgsz))
-    torch.onnx.export(m, ex, path, input_names=["images"], output_names=["pred", "protos"], dynamic_axes={"images": {0: "n"}, "pred": {0: "n"}, "protos": {0: "n"}})
+    outs = ["pred"] if cfg.task == "obb" else ["pred", "protos"]
+    torch.onnx.export(m, ex, path, input_names=["images"], output_names=outs, dynamic_axes={k: {0: "n"} for k in ["images"] + outs})

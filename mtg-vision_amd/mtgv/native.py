@@ -44,6 +44,7 @@ class DetectorCfg(C.Structure):
         ("iou", c_f32),
         ("max_det", c_i32),
         ("arch", c_i32),
+        ("task", c_i32),  # 0 segment, 1 OBB (mtgv_version >= 101)
     ]
 
 
@@ -120,6 +121,7 @@ SIGNATURES = {
     "mtgv_detector_missing_params": (C.c_int, [c_vp]),
     "mtgv_detector_finalize": (C.c_int, [c_vp]),
     "mtgv_detector_forward": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_vp]),
+    "mtgv_detector_forward_obb": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mtgv_detector_raw": (C.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp]),
     "mtgv_detector_flops": (C.c_int, [c_vp, C.POINTER(C.c_double)]),
     "mtgv_detector_set_fork": (C.c_int, [c_vp, c_i32]),
@@ -129,6 +131,13 @@ SIGNATURES = {
         [c_vp, c_i32, c_i32, c_i32, c_i32, c_f32, c_f32, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_size_t, c_vp],
     ),
     "mtgv_nms_workspace_bytes": (C.c_size_t, [c_i32, c_i32]),
+    "mtgv_nms_rotated": (
+        C.c_int,
+        [c_vp, c_i32, c_i32, c_i32, c_f32, c_f32, c_i32, c_f32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, C.c_size_t, c_vp],
+    ),
+    "mtgv_nms_rotated_workspace_bytes": (C.c_size_t, [c_i32, c_i32]),
+    "mtgv_op_probiou": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "mtgv_obb_cards": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mtgv_op_decode": (C.c_int, [C.POINTER(HeadRows), c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mtgv_op_nms_raw": (
         C.c_int,

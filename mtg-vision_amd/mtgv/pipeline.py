@@ -13,7 +13,7 @@ from typing import Callable, Optional
 import torch
 
 from . import native
-from .crop import mask_quads_from_logits, select_cards, warp_quads, warp_workspace
+from .crop import mask_quads_from_logits, obb_cards, select_cards, warp_quads, warp_workspace
 from .detector import Detector
 from .encoder import Encoder
 from .matcher import Matcher
@@ -95,12 +95,17 @@ class Pipeline:
                  match_fn: Optional[Callable] = None, quad_source: str = "box", thumbnail_quality: Optional[int] = None):
         """quad_source: "box" crops the detection boxes (the synthetic bench workload, SURVEY.md section 8d config 4);
         "mask" crops the oriented quad fitted to each detection's mask, as the reference does
-        (od_export.py:52-111: InstanceSeg._orient + extract_dewarped).
+        (od_export.py:52-111: InstanceSeg._orient + extract_dewarped); "obb" (an OBB detector, spec.DetectorConfig(task="obb"))
+        crops the oriented quad of each card-class rotated box, turned by the card_top / card_bottom detections inside it
+        (crop.obb_cards, classes 0 / 1 / 2 as od_datasets.py:244-257 labels them) - the output gains `quads` (F, K, 4, 2) and
+        `card_state` (F, K) (0 pad, 1 unoriented, 2 oriented).
         thumbnail_quality: when set, every step's crops are also encoded as 4:2:0 JPEG files at that quality on the GPU
         right after the de-warp, on the stream that made them (the thumbnails of mtgvision/server.py:222-225); the
         output gains `thumbs` (packed files, device) and `thumb_offsets` ((F * K + 1,) int64, device), file j being
         thumbs[thumb_offsets[j]:thumb_offsets[j + 1]].  None (default): no encode, no extra launch."""
-        assert quad_source in ("box", "mask"), quad_source
+        assert quad_source in ("box", "mask", "obb"), quad_source
+        task = getattr(getattr(detector, "cfg", None), "task", "seg")
+        assert (quad_source == "obb") == (task == "obb"), f'quad_source "{quad_source}" with a {task} detector'
         self.quad_source = quad_source
         self.thumbnail_quality = None if thumbnail_quality is None else int(thumbnail_quality)
         self._jpeg = None
@@ -135,6 +140,10 @@ class Pipeline:
     def _crop(self, frames_u8: torch.Tensor, det, lease=None):
         """detections -> (boxes (F, K, 4), crops (F * K, h, w, 3) uint8): the K best boxes or mask quadrilaterals, de-warped"""
         F, K = frames_u8.shape[0], self.K
+        if self.quad_source == "obb":
+            quads, sel, frame_idx, state = obb_cards(det["n_det"], det["rboxes"], det["conf"], det["cls"], self._pad, K, 0, 1, 2)
+            det["quads"], det["card_state"] = quads.view(F, K, 4, 2), state.view(F, K)
+            return self._warp(frames_u8, sel.view(F, K, 4), quads, frame_idx, lease)
         # the K highest-confidence detections per frame (NMS output is score-descending), pad boxes where a frame has
         # fewer; every step of the glue is a library kernel (no PyTorch arithmetic on the streams of the step)
         want_mask = self.quad_source == "mask"
@@ -146,7 +155,10 @@ class Pipeline:
             ml = det["mask_logits"]
             assert ml.shape[1] == K, f"mask rows {ml.shape[1]} != cards per frame {K}"
             quads, _ = mask_quads_from_logits(ml.view(F * K, *ml.shape[-2:]), sel)
-        boxes = sel.view(F, K, 4)
+        return self._warp(frames_u8, sel.view(F, K, 4), quads, frame_idx, lease)
+
+    def _warp(self, frames_u8, boxes, quads, frame_idx, lease):
+        F, K = frames_u8.shape[0], self.K
         if self._warp_ws is None or self._warp_ws.numel() < 9 * F * K:
             self._warp_ws = warp_workspace(F * K, frames_u8.device)  # once per pipeline (the largest batch seen so far)
         crops = warp_quads(frames_u8, quads, frame_idx, self.encoder.cfg.image_hw, 0.05, self._warp_ws)
@@ -177,6 +189,8 @@ class Pipeline:
         }
         if thumbs is not None:
             out["thumbs"], out["thumb_offsets"] = thumbs, thumb_offsets
+        if "quads" in det:  # quad_source "obb"
+            out["quads"], out["card_state"] = det["quads"], det["card_state"]
         return out
 
     @staticmethod

@@ -278,6 +278,14 @@ class DetectorConfig:
     max_wh: float = 7680.0
     max_nms: int = 30000
     bn_eps: float = 1e-3
+    # "seg": Segment head (prototypes + nm mask coefficients); "obb": OBB head (ne angle logits, no prototypes) - what
+    # od_train.py:19, :101 builds by default (kind="obb").  [external - recalled from ultralytics 8.3.x]
+    task: str = "seg"
+    ne: int = 1  # OBB: extra outputs per anchor (the angle logit)
+
+    def __post_init__(self):
+        if self.task not in ("seg", "obb"):
+            raise KeyError(f"task={self.task} not recognized")
 
     def ch(self, c: int) -> int:
         # make_divisible(min(c, max_ch) * width, 8)
@@ -297,7 +305,7 @@ class DetectorConfig:
 
     @property
     def no(self) -> int:
-        return 4 + self.nc + self.nm
+        return 4 + self.nc + (self.ne if self.task == "obb" else self.nm)
 
 
 # ---- YOLOv8n-seg graph (ultralytics cfg/models/v8/yolov8-seg.yaml, scale "n") ----------
@@ -336,10 +344,13 @@ def yolo11_config(**kw) -> DetectorConfig:
 
 
 def detector_config_for_state(state_dict, **kw) -> DetectorConfig:
-    """The scale-"n" family a ultralytics `state_dict` belongs to, from its key set: YOLO11-seg has its Segment head at
-    index 23 (`model.23.*`; C2PSA at 10), YOLOv8-seg at 22.  `nc` is read from the class branch's last conv."""
+    """The scale-"n" family a ultralytics `state_dict` belongs to, from its key set: YOLO11 has its head at index 23
+    (`model.23.*`; C2PSA at 10), YOLOv8 at 22; a head without `.proto.` keys is an OBB head.  `nc` is read from the class
+    branch's last conv."""
     keys = list(state_dict.keys())
     head = 23 if any(k.startswith("model.23.") for k in keys) else 22
+    if not any(".proto." in k for k in keys):
+        kw.setdefault("task", "obb")
     w = state_dict.get(f"model.{head}.cv3.0.2.weight")
     if w is not None:
         kw.setdefault("nc", int(w.shape[0]))
@@ -410,7 +421,7 @@ def _c3k_keys(prefix: str, c1: int, c2: int, n: int = 2):
 
 
 def detector_param_shapes(cfg: DetectorConfig) -> "OrderedDict[str, tuple]":
-    """ultralytics state_dict keys of YOLOv8n-seg / YOLO11n-seg (``num_batches_tracked`` buffers omitted).
+    """ultralytics state_dict keys of YOLOv8n / YOLO11n, -seg or -obb (``num_batches_tracked`` buffers omitted).
 
     Third-party layout, recalled from ultralytics 8.3.x (pyproject.toml:32 pins ~=8.3.80); it
     cannot be checked against the package in this environment.
@@ -475,7 +486,9 @@ def detector_param_shapes(cfg: DetectorConfig) -> "OrderedDict[str, tuple]":
     p = f"model.{cfg.head_index}"
     c2 = max(16, ch[0] // 4, cfg.reg_max * 4)
     c3 = max(ch[0], min(cfg.nc, 100))
-    c4 = max(ch[0] // 4, cfg.nm)
+    obb = cfg.task == "obb"
+    n4 = cfg.ne if obb else cfg.nm  # OBB(Detect): cv4 carries ne angle logits, c4 = max(ch[0] // 4, ne)
+    c4 = max(ch[0] // 4, n4)
     for l, cl in enumerate(ch):
         out.update(_conv_bn_keys(f"{p}.cv2.{l}.0", c2, cl, 3))
         out.update(_conv_bn_keys(f"{p}.cv2.{l}.1", c2, c2, 3))
@@ -493,16 +506,17 @@ def detector_param_shapes(cfg: DetectorConfig) -> "OrderedDict[str, tuple]":
         out[f"{p}.cv3.{l}.2.weight"] = (cfg.nc, c3, 1, 1)
         out[f"{p}.cv3.{l}.2.bias"] = (cfg.nc,)
     out[f"{p}.dfl.conv.weight"] = (1, cfg.reg_max, 1, 1)
-    out.update(_conv_bn_keys(f"{p}.proto.cv1", cfg.npr, ch[0], 3))
-    out[f"{p}.proto.upsample.weight"] = (cfg.npr, cfg.npr, 2, 2)  # ConvTranspose2d: (in, out, kh, kw)
-    out[f"{p}.proto.upsample.bias"] = (cfg.npr,)
-    out.update(_conv_bn_keys(f"{p}.proto.cv2", cfg.npr, cfg.npr, 3))
-    out.update(_conv_bn_keys(f"{p}.proto.cv3", cfg.nm, cfg.npr, 1))
+    if not obb:
+        out.update(_conv_bn_keys(f"{p}.proto.cv1", cfg.npr, ch[0], 3))
+        out[f"{p}.proto.upsample.weight"] = (cfg.npr, cfg.npr, 2, 2)  # ConvTranspose2d: (in, out, kh, kw)
+        out[f"{p}.proto.upsample.bias"] = (cfg.npr,)
+        out.update(_conv_bn_keys(f"{p}.proto.cv2", cfg.npr, cfg.npr, 3))
+        out.update(_conv_bn_keys(f"{p}.proto.cv3", cfg.nm, cfg.npr, 1))
     for l, cl in enumerate(ch):
         out.update(_conv_bn_keys(f"{p}.cv4.{l}.0", c4, cl, 3))
         out.update(_conv_bn_keys(f"{p}.cv4.{l}.1", c4, c4, 3))
-        out[f"{p}.cv4.{l}.2.weight"] = (cfg.nm, c4, 1, 1)
-        out[f"{p}.cv4.{l}.2.bias"] = (cfg.nm,)
+        out[f"{p}.cv4.{l}.2.weight"] = (n4, c4, 1, 1)
+        out[f"{p}.cv4.{l}.2.bias"] = (n4,)
     return out
 
 
