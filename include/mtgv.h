@@ -191,6 +191,12 @@ typedef struct {
   int32_t arch;      /* 0 or 8: YOLOv8n; 11: YOLO11n (C3k2, C2PSA, depthwise class branch; od_train.py:20) */
   int32_t task;      /* 0: segment head (-seg); 1: OBB head (-obb, what od_train.py:19, :101 builds by default): no prototypes,
                       * one angle logit per anchor, rotated NMS.  (Added in version 101: the struct grew by this field.) */
+  int32_t in_h, in_w; /* the input rectangle (added in version 102: the struct grew by these two fields).  Both 0: imgsz x imgsz.
+                      * Otherwise each a multiple of 32 in [32, imgsz] (anything else: status 1) - what ultralytics'
+                      * LetterBox(auto=True) feeds a .pt checkpoint: 480 x 640 for a webcam frame, 384 x 640 for 720p.  On such a
+                      * handle anchors keep their order (P3's pixels row-major, then P4's, then P5's) with
+                      * na = sum over s = 8, 16, 32 of (in_h / s)(in_w / s); boxes and rboxes are pixels of the in_h x in_w frame;
+                      * mask_logits is (n, mask_rows, in_h / 4, in_w / 4); mtgv_detector_raw and mtgv_detector_flops follow. */
 } mtgv_detector_cfg;
 #define MTGV_TASK_SEGMENT 0
 #define MTGV_TASK_OBB 1
@@ -202,12 +208,12 @@ MTGV_API int mtgv_detector_set_param(mtgv_detector* h, const char* key, const fl
 MTGV_API int mtgv_detector_missing_params(const mtgv_detector* h);
 /* fold BatchNorm into the conv weights and repack; call once after all params are set */
 MTGV_API int mtgv_detector_finalize(mtgv_detector* h);
-/* frames_dev: (n, imgsz, imgsz, 3) uint8, already letterboxed; flip_rgb reverses the channel
- * order first (ultralytics treats ndarray input as BGR).
+/* frames_dev: (n, in_h, in_w, 3) uint8 (imgsz x imgsz unless the cfg names a rectangle), already letterboxed, 8-byte
+ * aligned; flip_rgb reverses the channel order first (ultralytics treats ndarray input as BGR).
  * Outputs (device): n_det (n) int32; per frame up to max_det rows of
  *   boxes (n, max_det, 4) xyxy pixels, conf (n, max_det), cls (n, max_det) int32,
- *   keep_idx (n, max_det) int32 anchor index in [0, 8400),
- *   mask_logits (n, mask_rows, 160, 160): coeffs @ protos cropped to the box (process_mask before
+ *   keep_idx (n, max_det) int32 anchor index in [0, na) (8400 at 640 x 640),
+ *   mask_logits (n, mask_rows, in_h / 4, in_w / 4) (160 x 160 at 640 x 640): coeffs @ protos cropped to the box (process_mask before
  *   the upsample) for the first min(n_det, mask_rows) detections of each frame; rows beyond
  *   n_det are left untouched; NULL skips the mask stage. */
 MTGV_API int mtgv_detector_forward(mtgv_detector* h, const uint8_t* frames_dev, int32_t n, int32_t flip_rgb,
@@ -223,8 +229,8 @@ MTGV_API int mtgv_detector_forward(mtgv_detector* h, const uint8_t* frames_dev, 
  * ultralytics 8.3.x's as recalled (OBB.forward, dist2rbox): unpinned, like the rest of the detector. */
 MTGV_API int mtgv_detector_forward_obb(mtgv_detector* h, const uint8_t* frames_dev, int32_t n, int32_t flip_rgb, int32_t* n_det_dev,
                                        float* rboxes_dev, float* conf_dev, int32_t* cls_dev, int32_t* keep_idx_dev, void* stream);
-/* raw head outputs of the last forward: pred (n, 4+nc+32, 8400) and protos (n, 32, 160, 160); on an OBB handle
- * pred (n, 4+nc+1, 8400) = xywh, class scores, angle, and protos_dev must be NULL */
+/* raw head outputs of the last forward: pred (n, 4+nc+32, na) and protos (n, 32, in_h / 4, in_w / 4) (8400 and 160 x 160
+ * at 640 x 640); on an OBB handle pred (n, 4+nc+1, na) = xywh, class scores, angle, and protos_dev must be NULL */
 MTGV_API int mtgv_detector_raw(mtgv_detector* h, int32_t n, float* pred_dev, float* protos_dev, void* stream);
 MTGV_API int mtgv_detector_flops(const mtgv_detector* h, double* flops_per_frame);
 /* The forward's internal fork-join (the prototype branch and the P3 / P4 head branches on library-owned streams, see the
@@ -264,13 +270,15 @@ MTGV_API int mtgv_nms_rotated(const float* pred_dev, int32_t n, int32_t nc, int3
  * eps = 1e-7, float32 throughout. */
 MTGV_API int mtgv_op_probiou(const float* a_dev, const float* b_dev, int64_t m, float* out_dev, void* stream);
 
-/* Test surface of the segment head's tail.  Raw head rows of the three pyramid levels (strides 8 / 16 / 32), per level
- * (n, (imgsz / stride)^2, ct) floats, 16-byte aligned: 4 sides x 16 box bins at [0, 64), class logits at [cls, cls + nc),
- * mask coefficients at [coef, coef + nm); ct, cls and coef multiples of 4.  Anchors count P3's pixels first, then P4's,
- * then P5's: na = sum of (imgsz / stride)^2. */
+/* Test surface of the segment head's tail.  Raw head rows of the three pyramid levels (strides 8 / 16 / 32) of an h x w
+ * input, per level (n, (h / stride)(w / stride), ct) floats, 16-byte aligned: 4 sides x 16 box bins at [0, 64), class logits
+ * at [cls, cls + nc), mask coefficients at [coef, coef + nm); ct, cls and coef multiples of 4.  Anchors count P3's pixels
+ * first (row-major), then P4's, then P5's: na = sum of (h / stride)(w / stride).  h = w = 0: the square imgsz x imgsz input;
+ * otherwise both multiples of 32 (added in version 102: the struct grew by these two fields). */
 typedef struct mtgv_head_rows {
   const float *r0, *r1, *r2;
   int32_t imgsz, ct, cls, coef;
+  int32_t h, w;
 } mtgv_head_rows;
 /* the detector's decode pass: rows -> pred (n, 4+nc+nm, na) */
 MTGV_API int mtgv_op_decode(const mtgv_head_rows* rows, int32_t n, int32_t nc, int32_t nm, float* pred_dev, void* stream);
@@ -361,11 +369,20 @@ MTGV_API int mtgv_make_cropped(const uint8_t* images_dev, const int64_t* offsets
  * (mtgv.detector.letterbox_geometry: r = min(size / h, size / w), nh = round(h r), ...). */
 MTGV_API int mtgv_letterbox_u8(const uint8_t* src_dev, int32_t h, int32_t w, uint8_t* dst_dev, int32_t size, int32_t nh, int32_t nw,
                                int32_t top, int32_t left, int32_t pad_value, void* stream);
+/* the same into a (dst_h, dst_w, 3) image, for n same-sized frames in one launch: src_dev (n, h, w, 3), dst_dev
+ * (n, dst_h, dst_w, 3).  With mtgv.detector.rect_geometry this is LetterBox(auto=True), what ultralytics runs in front of a
+ * .pt checkpoint: the pad only reaches the next multiple of the stride.  The resample arithmetic is mtgv_letterbox_u8's (which
+ * is the n = 1, dst_h = dst_w case of the same kernel); a frame with (nh, nw) == (h, w) is copied exactly. */
+MTGV_API int mtgv_letterbox_rect_u8(const uint8_t* src_dev, int32_t n, int32_t h, int32_t w, uint8_t* dst_dev, int32_t dst_h, int32_t dst_w,
+                                    int32_t nh, int32_t nw, int32_t top, int32_t left, int32_t pad_value, void* stream);
 /* fills the pad of n letterboxed (size, size, 3) uint8 frames with pad_value: every pixel outside the (nh, nw) rectangle
  * at (top, left), which someone else writes (mtgv.jpeg.JpegDecoder.decode_frames decodes a frame that already fits
  * straight into it) */
 MTGV_API int mtgv_letterbox_pad_u8(uint8_t* frames_dev, int32_t n, int32_t size, int32_t nh, int32_t nw, int32_t top, int32_t left,
                                    int32_t pad_value, void* stream);
+/* the same for (dst_h, dst_w, 3) frames (mtgv_letterbox_pad_u8 is its dst_h = dst_w case) */
+MTGV_API int mtgv_letterbox_pad_rect_u8(uint8_t* frames_dev, int32_t n, int32_t dst_h, int32_t dst_w, int32_t nh, int32_t nw, int32_t top,
+                                        int32_t left, int32_t pad_value, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* JPEG decode: the frames of mtgvision/server.py:272-280 (cv2.imdecode on the host) and the */

@@ -89,7 +89,7 @@ struct mtgv_bank {
 extern "C" {
 
 MTGV_API const char* mtgv_last_error(void) { return last_error_cstr(); }
-MTGV_API int mtgv_version(void) { return 101; }  // 101: mtgv_detector_cfg.task, the OBB calls
+MTGV_API int mtgv_version(void) { return 102; }  // 101: mtgv_detector_cfg.task, the OBB calls; 102: in_h / in_w, mtgv_head_rows h / w, the rect letterbox calls
 MTGV_API int mtgv_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;

@@ -38,8 +38,13 @@ Detector::Detector(const mtgv_detector_cfg& cfg) : cfg_(cfg) {
   MTGV_CHECK(cfg.max_det > 0 && cfg.max_det <= 1024, ERR_INVALID, "detector: max_det=%d", cfg.max_det);
   MTGV_CHECK(cfg.arch == 0 || cfg.arch == 8 || cfg.arch == 11, ERR_KEY, "detector: arch=%d (8: YOLOv8n-seg, 11: YOLO11n-seg)", cfg.arch);
   MTGV_CHECK(cfg.task == MTGV_TASK_SEGMENT || cfg.task == MTGV_TASK_OBB, ERR_KEY, "detector: task=%d (0: segment, 1: OBB)", cfg.task);
-  const int S = cfg.imgsz;
-  na_ = (S / 8) * (S / 8) + (S / 16) * (S / 16) + (S / 32) * (S / 32);
+  // the input rectangle: in_h = in_w = 0 is the square imgsz x imgsz
+  if (cfg.in_h == 0 && cfg.in_w == 0) cfg_.in_h = cfg_.in_w = cfg.imgsz;
+  MTGV_CHECK(cfg_.in_h >= 32 && cfg_.in_w >= 32 && cfg_.in_h % 32 == 0 && cfg_.in_w % 32 == 0 && cfg_.in_h <= cfg.imgsz && cfg_.in_w <= cfg.imgsz,
+             ERR_INVALID, "detector: in_h=%d in_w=%d must both be 0 (imgsz x imgsz) or multiples of 32 in [32, imgsz=%d]", cfg.in_h, cfg.in_w,
+             cfg.imgsz);
+  const int IH = cfg_.in_h, IW = cfg_.in_w;
+  na_ = (IH / 8) * (IW / 8) + (IH / 16) * (IW / 16) + (IH / 32) * (IW / 32);
   // The branch streams of the forward's fork-join are created with the handle, not at the first forward: the HIP runtime maps
   // streams to its hardware queues in creation order, and branch streams created after an application's high-priority
   // stream (mtgv.Pipeline's embed stream) ended up sharing a queue with the caller's stream - the forward on ONE stream then
@@ -293,28 +298,30 @@ void Detector::plan_arena(std::vector<ArenaBuf> all) {
 }
 
 std::vector<Detector::ArenaBuf> Detector::arena_v8() const {
-  const int S = cfg_.imgsz, s2 = S / 2, s4 = S / 4, s8 = S / 8, s16 = S / 16, s32 = S / 32;
+  const int IH = cfg_.in_h, IW = cfg_.in_w;
+  const int h2 = IH / 2, h4 = IH / 4, h8 = IH / 8, h16 = IH / 16, h32 = IH / 32;
+  const int w2 = IW / 2, w4 = IW / 4, w8 = IW / 8, w16 = IW / 16, w32 = IW / 32;
   const int c16 = chn(64), c32 = chn(128), c64 = chn(256), c128 = chn(512), c256 = chn(1024);
   return {
-      {"l0", s2, s2, c16}, {"l1", s4, s4, c32},
-      {"cat2", s4, s4, 3 * c32 / 2}, {"tmp2", s4, s4, c32 / 2}, {"l2", s4, s4, c32},
-      {"l3", s8, s8, c64}, {"cat4", s8, s8, 4 * c64 / 2}, {"tmp4", s8, s8, c64 / 2},
-      {"cat14", s8, s8, c128 + c64},                                      // concat 14 = [up(12), 4]
-      {"l5", s16, s16, c128}, {"cat6", s16, s16, 4 * c128 / 2}, {"tmp6", s16, s16, c128 / 2},
-      {"cat11", s16, s16, c256 + c128},                                   // concat 11 = [up(9), 6]
-      {"l7", s32, s32, c256}, {"cat8", s32, s32, 3 * c256 / 2}, {"tmp8", s32, s32, c256 / 2}, {"l8", s32, s32, c256},
-      {"sppcat", s32, s32, 2 * c256},
-      {"cat20", s32, s32, c128 + c256},                                   // concat 20 = [19, 9]
-      {"cat12", s16, s16, 3 * c128 / 2}, {"tmp12", s16, s16, c128 / 2},
-      {"cat17", s16, s16, c64 + c128},                                    // concat 17 = [16, 12]
-      {"cat15", s8, s8, 3 * c64 / 2}, {"tmp15", s8, s8, c64 / 2}, {"p3", s8, s8, c64},
-      {"cat18", s16, s16, 3 * c128 / 2}, {"tmp18", s16, s16, c128 / 2}, {"p4", s16, s16, c128},
-      {"cat21", s32, s32, 3 * c256 / 2}, {"tmp21", s32, s32, c256 / 2}, {"p5", s32, s32, c256},
+      {"l0", h2, w2, c16}, {"l1", h4, w4, c32},
+      {"cat2", h4, w4, 3 * c32 / 2}, {"tmp2", h4, w4, c32 / 2}, {"l2", h4, w4, c32},
+      {"l3", h8, w8, c64}, {"cat4", h8, w8, 4 * c64 / 2}, {"tmp4", h8, w8, c64 / 2},
+      {"cat14", h8, w8, c128 + c64},                                      // concat 14 = [up(12), 4]
+      {"l5", h16, w16, c128}, {"cat6", h16, w16, 4 * c128 / 2}, {"tmp6", h16, w16, c128 / 2},
+      {"cat11", h16, w16, c256 + c128},                                   // concat 11 = [up(9), 6]
+      {"l7", h32, w32, c256}, {"cat8", h32, w32, 3 * c256 / 2}, {"tmp8", h32, w32, c256 / 2}, {"l8", h32, w32, c256},
+      {"sppcat", h32, w32, 2 * c256},
+      {"cat20", h32, w32, c128 + c256},                                   // concat 20 = [19, 9]
+      {"cat12", h16, w16, 3 * c128 / 2}, {"tmp12", h16, w16, c128 / 2},
+      {"cat17", h16, w16, c64 + c128},                                    // concat 17 = [16, 12]
+      {"cat15", h8, w8, 3 * c64 / 2}, {"tmp15", h8, w8, c64 / 2}, {"p3", h8, w8, c64},
+      {"cat18", h16, w16, 3 * c128 / 2}, {"tmp18", h16, w16, c128 / 2}, {"p4", h16, w16, c128},
+      {"cat21", h32, w32, 3 * c256 / 2}, {"tmp21", h32, w32, c256 / 2}, {"p5", h32, w32, c256},
       // head temporaries per level (the levels' branches run concurrently)
-      {"t1_0", s8, s8, 160}, {"t2_0", s8, s8, 160}, {"t1_1", s16, s16, 160}, {"t2_1", s16, s16, 160},
-      {"t1_2", s32, s32, 160}, {"t2_2", s32, s32, 160},
-      {"rawhead0", s8, s8, RAW_CT, true}, {"rawhead1", s16, s16, RAW_CT, true}, {"rawhead2", s32, s32, RAW_CT, true},
-      {"pr1", s8, s8, npr_}, {"pr2", s4, s4, npr_}, {"pr3", s4, s4, npr_}, {"protos", s4, s4, nm_, true},
+      {"t1_0", h8, w8, 160}, {"t2_0", h8, w8, 160}, {"t1_1", h16, w16, 160}, {"t2_1", h16, w16, 160},
+      {"t1_2", h32, w32, 160}, {"t2_2", h32, w32, 160},
+      {"rawhead0", h8, w8, RAW_CT, true}, {"rawhead1", h16, w16, RAW_CT, true}, {"rawhead2", h32, w32, RAW_CT, true},
+      {"pr1", h8, w8, npr_}, {"pr2", h4, w4, npr_}, {"pr3", h4, w4, npr_}, {"protos", h4, w4, nm_, true},
       {"pred", 1, na_, no(), true}, {"coef", 1, cfg_.max_det, nm_, true},
   };
 }
@@ -483,32 +490,34 @@ void Detector::c2f(int idx, const View& in, const View& out, int n, hipStream_t 
 
 // model.0 (Conv 3 -> 16, k3 s2) on its own kernel straight from the uint8 frame
 void Detector::conv0(const uint8_t* frames, int n, int flip, hipStream_t s) {
-  const int S = cfg_.imgsz;
+  const int H = cfg_.in_h, W = cfg_.in_w;
   const ConvW& w0 = cw_.at("model.0");
   const View l0 = view("l0");
-  MTGV_CHECK((S / 2) % 4 == 0 && w0.cout == 16 && w0.cin == 4 && w0.k == 3, ERR_RUNTIME, "detector: unexpected model.0 geometry");
+  // (the kernel's whole-word loads and its four output columns per thread need W % 8 == 0)
+  MTGV_CHECK(H % 2 == 0 && W % 8 == 0 && l0.H == H / 2 && l0.W == W / 2 && w0.cout == 16 && w0.cin == 4 && w0.k == 3, ERR_RUNTIME,
+             "detector: unexpected model.0 geometry");
   if (count_flops_) {  // K = 27: the weights' zero 4th input channel is not counted
     flops_ += 2.0 * n * l0.H * l0.W * w0.cout * 27.0;
     return;
   }
   MTGV_CHECK(((uintptr_t)frames & 7) == 0, ERR_INVALID, "detector: the frame buffer must be 8-byte aligned");
-  const long total = (long)n * (S / 2) * (S / 8);
+  const long total = (long)n * (H / 2) * (W / 8);
   const auto kern = fmt_ == 1 ? conv0_u8_kernel<true> : conv0_u8_kernel<false>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, frames, w0.w, w0.b, l0.p, S, flip, total);
+  hipLaunchKernelGGL(kern, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, frames, w0.w, w0.b, l0.p, H, W, flip, total);
   HIP_OK(hipGetLastError());
 }
 
 
 // head rows of n frames -> pred (n, 4 + nc + nm, na)
 static void decode_launch(const HeadRows& rows, int n, int nc, int nm, float* pred, hipStream_t s) {
-  const int na = head_rows_anchors(rows.imgsz);
+  const int na = head_rows_anchors(rows);
   const long tot = (long)n * na;
   hipLaunchKernelGGL(decode_kernel, dim3((unsigned)((tot + 255) / 256)), dim3(256), 0, s, rows, pred, n, nc, nm, na);
   HIP_OK(hipGetLastError());
 }
 
 HeadRows Detector::head_rows() const {
-  return HeadRows{v_.at("rawhead0").p, v_.at("rawhead1").p, v_.at("rawhead2").p, cfg_.imgsz, RAW_CT, RAW_CLS, RAW_COEF};
+  return HeadRows{v_.at("rawhead0").p, v_.at("rawhead1").p, v_.at("rawhead2").p, cfg_.imgsz, RAW_CT, RAW_CLS, RAW_COEF, cfg_.in_h, cfg_.in_w};
 }
 
 // the raw head rows of the first n frames -> pred
@@ -526,7 +535,6 @@ void Detector::decode(int n, hipStream_t s) {
 // (decode ->) NMS -> mask logits of the kept detections
 void Detector::head_tail(int n, int* n_det, float* boxes, float* conf, int* cls, int* keep_idx, float* mask_logits, int mask_rows,
                          hipStream_t s) {
-  const int S = cfg_.imgsz;
   float* const coef = v_.at("coef").p;
   if (head_direct_) {
     // NMS reads the class logits of every anchor, and the box and the coefficients of candidates only, from the head
@@ -544,9 +552,11 @@ void Detector::head_tail(int n, int* n_det, float* boxes, float* conf, int* cls,
     // masks = coeffs @ protos^T per image, cropped to the box (process_mask / crop_mask)
     const View pr = view("protos");
     const int npx = pr.H * pr.W;
+    // the prototypes are a quarter of the input in both directions: one crop scale (pr.W / in_w, = pr.H / in_h)
+    const float crop_scale = (float)pr.W / (float)cfg_.in_w;
     if (nm_ == 32 && mask_rows <= 16 && !count_flops_) {  // a handful of masks per frame: one pass over the prototypes
       hipLaunchKernelGGL(mask_logits_kernel, dim3((unsigned)((npx + 255) / 256), (unsigned)n), dim3(256), 0, s, coef, pr.p, n_det, boxes,
-                         mask_logits, npx, pr.W, mask_rows, cfg_.max_det, (float)pr.W / (float)S);
+                         mask_logits, npx, pr.W, mask_rows, cfg_.max_det, crop_scale);
       HIP_OK(hipGetLastError());
       return;
     }
@@ -560,7 +570,7 @@ void Detector::head_tail(int n, int* n_det, float* boxes, float* conf, int* cls,
     g.m_count = n_det;
     g.crop_boxes = boxes;
     g.crop_rows = cfg_.max_det;
-    g.crop_scale = (float)pr.W / (float)S;
+    g.crop_scale = crop_scale;
     g.crop_w = pr.W;
     gemm_launch(g, s);
   }
@@ -787,7 +797,7 @@ MTGV_API int mtgv_mask_binarize(const float* logits_dev, int32_t n, int32_t mh, 
 }
 static HeadRows op_head_rows(const mtgv_head_rows* r) {
   MTGV_CHECK(r != nullptr && r->r0 && r->r1 && r->r2, ERR_INVALID, "null head rows");
-  return HeadRows{r->r0, r->r1, r->r2, r->imgsz, r->ct, r->cls, r->coef};
+  return HeadRows{r->r0, r->r1, r->r2, r->imgsz, r->ct, r->cls, r->coef, r->h, r->w};
 }
 MTGV_API int mtgv_op_decode(const mtgv_head_rows* rows, int32_t n, int32_t nc, int32_t nm, float* pred_dev, void* stream) {
   return guarded([&] {

@@ -118,13 +118,13 @@ __global__ __launch_bounds__(256) void mask_binarize_kernel(const float* __restr
 // conversion (img / 255, ultralytics preprocess) that used to be a separate pass over a 4-channel float copy.
 template <bool SP8>
 __global__ __launch_bounds__(256) void conv0_u8_kernel(const uint8_t* __restrict__ frames, const float* __restrict__ w,
-                                                      const float* __restrict__ bias, float* __restrict__ out, int S, int flip,
+                                                      const float* __restrict__ bias, float* __restrict__ out, int H, int W, int flip,
                                                       long total) {
   __shared__ __attribute__((aligned(16))) float ws[16 * 9 * 4 + 16];  // [o][tap][4] (cin padded to 4) + bias
   for (int i = threadIdx.x; i < 16 * 9 * 4; i += 256) ws[i] = w[i];
   if (threadIdx.x < 16) ws[16 * 9 * 4 + threadIdx.x] = bias[threadIdx.x];
   __syncthreads();
-  const int OS = S >> 1, OQ = OS >> 2;  // output size, groups of 4 output columns per row
+  const int OS = H >> 1, OQ = W >> 3;  // output rows, groups of 4 output columns per row (W % 8 == 0)
   // Output staging: a thread's four pixels are 256 contiguous bytes and thread i + 1 continues where thread i ends, so
   // a store issued by every lane for its own piece would touch 64 different lines.  Each wave passes its pieces through
   // LDS (two pixels = 8 pieces of 16 B per thread at a time, rows padded to 144 B) and stores them back transposed:
@@ -145,11 +145,11 @@ __global__ __launch_bounds__(256) void conv0_u8_kernel(const uint8_t* __restrict
 #pragma unroll
   for (int kh = 0; kh < 3; ++kh) {
     const int ih = 2 * oh - 1 + kh;
-    if (ih < 0 || ih >= S) continue;
-    const uint8_t* const rowp = frames + ((n * S + ih) * (long)S) * 3;
+    if (ih < 0 || ih >= H) continue;
+    const uint8_t* const rowp = frames + ((n * H + ih) * (long)W) * 3;
     float x[9][3];  // input columns 2*ow0-1 .. 2*ow0+7
     // The nine pixels are bytes 24 q - 3 .. 24 q + 23 of the row: one dword for the pixel left of the strip (zero padding
-    // at q == 0 - the only column that can fall outside, S = 8 OQ) and three aligned 8-byte loads for the other eight.
+    // at q == 0 - the only column that can fall outside, W = 8 OQ) and three aligned 8-byte loads for the other eight.
     uint32_t d[7];
     d[0] = q > 0 ? *reinterpret_cast<const uint32_t*>(rowp + 24 * q - 4) : 0u;
 #pragma unroll

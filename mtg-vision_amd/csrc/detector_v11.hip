@@ -252,31 +252,33 @@ void Detector::build_v11() {
 // activation arena
 // ---------------------------------------------------------------------------
 std::vector<Detector::ArenaBuf> Detector::arena_v11() const {
-  const int S = cfg_.imgsz, s2 = S / 2, s4 = S / 4, s8 = S / 8, s16 = S / 16, s32 = S / 32;
+  const int IH = cfg_.in_h, IW = cfg_.in_w;
+  const int h2 = IH / 2, h4 = IH / 4, h8 = IH / 8, h16 = IH / 16, h32 = IH / 32;
+  const int w2 = IW / 2, w4 = IW / 4, w8 = IW / 8, w16 = IW / 16, w32 = IW / 32;
   const int c16 = chn(64), c32 = chn(128), c64 = chn(256), c128 = chn(512), c256 = chn(1024);
   return {
-      {"l0", s2, s2, c16}, {"l1", s4, s4, c32},
-      {"cat2", s4, s4, 48}, {"tmp2", s4, s4, 8}, {"l2", s4, s4, c64},
-      {"l3", s8, s8, c64}, {"cat4", s8, s8, 96}, {"tmp4", s8, s8, 16},
-      {"cat15", s8, s8, c128 + c128},                                     // concat 15 = [up(13), 4]
-      {"l5", s16, s16, c128}, {"cat6", s16, s16, 192}, {"kcat6", s16, s16, 64}, {"tmp6", s16, s16, 32},
-      {"cat12", s16, s16, c256 + c128},                                   // concat 12 = [up(10), 6]
-      {"l7", s32, s32, c256}, {"cat8", s32, s32, 384}, {"kcat8", s32, s32, 128}, {"tmp8", s32, s32, 64}, {"l8", s32, s32, c256},
-      {"sppcat", s32, s32, 2 * c256}, {"l9", s32, s32, c256},
+      {"l0", h2, w2, c16}, {"l1", h4, w4, c32},
+      {"cat2", h4, w4, 48}, {"tmp2", h4, w4, 8}, {"l2", h4, w4, c64},
+      {"l3", h8, w8, c64}, {"cat4", h8, w8, 96}, {"tmp4", h8, w8, 16},
+      {"cat15", h8, w8, c128 + c128},                                     // concat 15 = [up(13), 4]
+      {"l5", h16, w16, c128}, {"cat6", h16, w16, 192}, {"kcat6", h16, w16, 64}, {"tmp6", h16, w16, 32},
+      {"cat12", h16, w16, c256 + c128},                                   // concat 12 = [up(10), 6]
+      {"l7", h32, w32, c256}, {"cat8", h32, w32, 384}, {"kcat8", h32, w32, 128}, {"tmp8", h32, w32, 64}, {"l8", h32, w32, c256},
+      {"sppcat", h32, w32, 2 * c256}, {"l9", h32, w32, c256},
       // (the attention core and the positional encoding read qkv and att in f32)
-      {"psacat", s32, s32, c256}, {"qkv", s32, s32, c256, true}, {"att", s32, s32, c128, true}, {"atty", s32, s32, c128}, {"ffn", s32, s32, c256},
-      {"cat21", s32, s32, c128 + c256},                                   // concat 21 = [20, 10]
-      {"cat13", s16, s16, 192}, {"tmp13", s16, s16, 32},
-      {"cat18", s16, s16, c64 + c128},                                    // concat 18 = [17, 13]
-      {"cat16", s8, s8, 96}, {"tmp16", s8, s8, 16}, {"p3", s8, s8, c64},
-      {"cat19", s16, s16, 192}, {"tmp19", s16, s16, 32}, {"p4", s16, s16, c128},
-      {"cat22", s32, s32, 384}, {"kcat22", s32, s32, 128}, {"tmp22", s32, s32, 64}, {"p5", s32, s32, c256},
+      {"psacat", h32, w32, c256}, {"qkv", h32, w32, c256, true}, {"att", h32, w32, c128, true}, {"atty", h32, w32, c128}, {"ffn", h32, w32, c256},
+      {"cat21", h32, w32, c128 + c256},                                   // concat 21 = [20, 10]
+      {"cat13", h16, w16, 192}, {"tmp13", h16, w16, 32},
+      {"cat18", h16, w16, c64 + c128},                                    // concat 18 = [17, 13]
+      {"cat16", h8, w8, 96}, {"tmp16", h8, w8, 16}, {"p3", h8, w8, c64},
+      {"cat19", h16, w16, 192}, {"tmp19", h16, w16, 32}, {"p4", h16, w16, c128},
+      {"cat22", h32, w32, 384}, {"kcat22", h32, w32, 128}, {"tmp22", h32, w32, 64}, {"p5", h32, w32, c256},
       // head temporaries per level (the levels' branches run concurrently): box + coefficient branches, class branch
-      {"t1_0", s8, s8, 96}, {"t2_0", s8, s8, 96}, {"dwa_0", s8, s8, c64}, {"dwb_0", s8, s8, 64}, {"dwc_0", s8, s8, 64}, {"dwd_0", s8, s8, 64},
-      {"t1_1", s16, s16, 96}, {"t2_1", s16, s16, 96}, {"dwa_1", s16, s16, c128}, {"dwb_1", s16, s16, 64}, {"dwc_1", s16, s16, 64}, {"dwd_1", s16, s16, 64},
-      {"t1_2", s32, s32, 96}, {"t2_2", s32, s32, 96}, {"dwa_2", s32, s32, c256}, {"dwb_2", s32, s32, 64}, {"dwc_2", s32, s32, 64}, {"dwd_2", s32, s32, 64},
-      {"pr1", s8, s8, npr_}, {"pr2", s4, s4, npr_}, {"pr3", s4, s4, npr_}, {"protos", s4, s4, nm_, true},
-      {"rawhead0", s8, s8, RAW_CT, true}, {"rawhead1", s16, s16, RAW_CT, true}, {"rawhead2", s32, s32, RAW_CT, true},
+      {"t1_0", h8, w8, 96}, {"t2_0", h8, w8, 96}, {"dwa_0", h8, w8, c64}, {"dwb_0", h8, w8, 64}, {"dwc_0", h8, w8, 64}, {"dwd_0", h8, w8, 64},
+      {"t1_1", h16, w16, 96}, {"t2_1", h16, w16, 96}, {"dwa_1", h16, w16, c128}, {"dwb_1", h16, w16, 64}, {"dwc_1", h16, w16, 64}, {"dwd_1", h16, w16, 64},
+      {"t1_2", h32, w32, 96}, {"t2_2", h32, w32, 96}, {"dwa_2", h32, w32, c256}, {"dwb_2", h32, w32, 64}, {"dwc_2", h32, w32, 64}, {"dwd_2", h32, w32, 64},
+      {"pr1", h8, w8, npr_}, {"pr2", h4, w4, npr_}, {"pr3", h4, w4, npr_}, {"protos", h4, w4, nm_, true},
+      {"rawhead0", h8, w8, RAW_CT, true}, {"rawhead1", h16, w16, RAW_CT, true}, {"rawhead2", h32, w32, RAW_CT, true},
       {"pred", 1, na_, no(), true}, {"coef", 1, cfg_.max_det, nm_, true},
   };
 }

@@ -10,12 +10,15 @@
 
 namespace mtgv {
 
-// Raw head rows of the three pyramid levels (strides 8 / 16 / 32): per level [n][(imgsz / stride)^2] rows of `ct` floats,
-// 16-byte aligned; a row holds 4 sides x 16 box bins at [0, 64), class logits at [cls, cls + nc), mask coefficients at
-// [coef, coef + nm).  ct, cls and coef are multiples of 4.
+// Raw head rows of the three pyramid levels (strides 8 / 16 / 32) of an h x w input: per level [n][(h / stride)(w / stride)]
+// rows of `ct` floats, 16-byte aligned; a row holds 4 sides x 16 box bins at [0, 64), class logits at [cls, cls + nc), mask
+// coefficients at [coef, coef + nm).  ct, cls and coef are multiples of 4.  h = w = 0: the square imgsz x imgsz input.
 struct HeadRows {
   const float *r0, *r1, *r2;
   int imgsz, ct, cls, coef;
+  int h = 0, w = 0;
+  __host__ __device__ int in_h() const { return h > 0 ? h : imgsz; }
+  __host__ __device__ int in_w() const { return w > 0 ? w : imgsz; }
 };
 
 struct HeadAnchor {
@@ -26,8 +29,9 @@ struct HeadAnchor {
 
 // anchor a of image img: P3's pixels first, then P4's, then P5's (the order of `pred`)
 __device__ __forceinline__ HeadAnchor head_anchor(const HeadRows& h, int img, int a) {
-  const int w0 = h.imgsz / 8, w1 = h.imgsz / 16, w2 = h.imgsz / 32;
-  const int n0 = w0 * w0, n1 = w1 * w1;
+  const int ih = h.in_h(), iw = h.in_w();
+  const int w0 = iw / 8, w1 = iw / 16, w2 = iw / 32;
+  const int n0 = (ih / 8) * w0, n1 = (ih / 16) * w1, n2 = (ih / 32) * w2;
   HeadAnchor an;
   if (a < n0) {
     an.pix = a, an.gw = w0, an.stride = 8.f;
@@ -37,7 +41,7 @@ __device__ __forceinline__ HeadAnchor head_anchor(const HeadRows& h, int img, in
     an.row = h.r1 + ((long)img * n1 + an.pix) * h.ct;
   } else {
     an.pix = a - n0 - n1, an.gw = w2, an.stride = 32.f;
-    an.row = h.r2 + ((long)img * w2 * w2 + an.pix) * h.ct;
+    an.row = h.r2 + ((long)img * n2 + an.pix) * h.ct;
   }
   return an;
 }

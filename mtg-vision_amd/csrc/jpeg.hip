@@ -1163,32 +1163,3 @@ MTGV_API int mtgv_jpeg_decode(mtgv_jpeg_decoder* h, const uint8_t* data_host, co
     HIP_OK(hipGetLastError());
   });
 }
-
-namespace {
-// pad of n letterboxed size x size x 3 frames whose (nh, nw) image at (top, left) is written by someone else
-__global__ __launch_bounds__(256) void letterbox_pad_kernel(uint8_t* __restrict__ f, int64_t npix, int size, int nh, int nw, int top,
-                                                            int left, uint8_t v) {
-  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (g >= npix) return;
-  const int p = (int)(g % ((int64_t)size * size));
-  const int y = p / size - top, x = p % size - left;
-  if (y >= 0 && y < nh && x >= 0 && x < nw) return;
-  uint8_t* o = f + g * 3;
-  o[0] = o[1] = o[2] = v;
-}
-}  // namespace
-
-MTGV_API int mtgv_letterbox_pad_u8(uint8_t* frames_dev, int32_t n, int32_t size, int32_t nh, int32_t nw, int32_t top, int32_t left,
-                                   int32_t pad_value, void* stream) {
-  return guarded([&] {
-    MTGV_CHECK(frames_dev != nullptr || n == 0, ERR_INVALID, "null frames");
-    MTGV_CHECK(n >= 0 && size > 0 && nh >= 0 && nw >= 0 && top >= 0 && left >= 0 && top + nh <= size && left + nw <= size, ERR_INVALID,
-               "letterbox pad: image %dx%d at (%d, %d) outside a %d frame", nh, nw, top, left, size);
-    MTGV_CHECK(pad_value >= 0 && pad_value <= 255, ERR_INVALID, "pad value %d outside [0, 255]", pad_value);
-    const int64_t npix = (int64_t)n * size * size;
-    if (npix == 0) return;
-    hipLaunchKernelGGL(letterbox_pad_kernel, dim3((unsigned)ceil_div64(npix, 256)), dim3(256), 0, (hipStream_t)stream, frames_dev, npix,
-                       size, nh, nw, top, left, (uint8_t)pad_value);
-    HIP_OK(hipGetLastError());
-  });
-}

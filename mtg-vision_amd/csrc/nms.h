@@ -14,9 +14,9 @@ void nms_launch(const float* pred, int n, int nc, int nm, int na, float conf, fl
 // rboxes (n, max_det, 5) xywh + angle.  Workspace: nms_workspace_bytes(n, na).  iou > 0, max_wh >= 7680.
 void nms_rotated_launch(const float* pred, int n, int nc, int na, float conf, float iou, int max_det, float max_wh, int* n_det,
                         float* rboxes, float* conf_out, int* cls_out, int* keep_idx, int* ws, size_t ws_bytes, hipStream_t s);
-// the same on the segment head's raw rows (head_decode.h) of n images, na = head_rows_anchors(rows.imgsz): bit-identical
+// the same on the segment head's raw rows (head_decode.h) of n images, na = head_rows_anchors(rows): bit-identical
 // to decode_kernel -> nms_launch on those rows
-int head_rows_anchors(int imgsz);
+int head_rows_anchors(const HeadRows& rows);
 // the layout a HeadRows promises its kernels (head_decode.h), checked once for every launch that takes one
 void head_rows_check(const HeadRows& rows, int nc, int nm);
 void nms_rows_launch(const HeadRows& rows, int n, int nc, int nm, float conf, float iou, int max_det, float max_wh, int* n_det,

@@ -439,11 +439,16 @@ void nms_rotated_launch(const float* pred, int n, int nc, int na, float conf, fl
   HIP_OK(hipGetLastError());
 }
 
-int head_rows_anchors(int imgsz) { return (imgsz / 8) * (imgsz / 8) + (imgsz / 16) * (imgsz / 16) + (imgsz / 32) * (imgsz / 32); }
+int head_rows_anchors(const HeadRows& rows) {
+  const int h = rows.in_h(), w = rows.in_w();
+  return (h / 8) * (w / 8) + (h / 16) * (w / 16) + (h / 32) * (w / 32);
+}
 
 void head_rows_check(const HeadRows& rows, int nc, int nm) {
   MTGV_CHECK(rows.r0 && rows.r1 && rows.r2 && rows.imgsz > 0 && rows.imgsz % 32 == 0 && nc > 0 && nm >= 0, ERR_INVALID,
              "head rows: imgsz=%d nc=%d nm=%d", rows.imgsz, nc, nm);
+  MTGV_CHECK((rows.h == 0 && rows.w == 0) || (rows.h > 0 && rows.w > 0 && rows.h % 32 == 0 && rows.w % 32 == 0), ERR_INVALID,
+             "head rows: h=%d w=%d (both 0: imgsz x imgsz; otherwise multiples of 32)", rows.h, rows.w);
   MTGV_CHECK(rows.ct % 4 == 0 && rows.cls % 4 == 0 && rows.coef % 4 == 0 && rows.cls >= 64 && rows.coef >= 64 && rows.cls + nc <= rows.ct &&
                  rows.coef + nm <= rows.ct && (((uintptr_t)rows.r0 | (uintptr_t)rows.r1 | (uintptr_t)rows.r2) & 15) == 0,
              ERR_INVALID, "head rows: layout ct=%d cls=%d coef=%d (nc=%d nm=%d; 16-byte aligned rows)", rows.ct, rows.cls, rows.coef, nc, nm);
@@ -453,7 +458,7 @@ void nms_rows_launch(const HeadRows& rows, int n, int nc, int nm, float conf, fl
                      float* boxes, float* conf_out, int* cls_out, int* keep_idx, float* coef_out, int* ws, size_t ws_bytes,
                      hipStream_t s) {
   head_rows_check(rows, nc, nm);
-  nms_launch_form<true>(nullptr, rows, n, nc, nm, head_rows_anchors(rows.imgsz), conf, iou, max_det, max_wh, n_det, boxes, conf_out, cls_out,
+  nms_launch_form<true>(nullptr, rows, n, nc, nm, head_rows_anchors(rows), conf, iou, max_det, max_wh, n_det, boxes, conf_out, cls_out,
                         keep_idx, coef_out, ws, ws_bytes, s);
 }
 

@@ -56,18 +56,19 @@ __global__ __launch_bounds__(256) void make_cropped_kernel(const uint8_t* __rest
 }
 
 // ultralytics LetterBox ahead of the detector (behind CardSegmenter.__call__, od_export.py:147-150): the frame scaled to
-// fit size x size (bilinear; cv2.resize(INTER_LINEAR) upstream - absent here, parity unpinned), centred, the border
+// fit dst_h x dst_w (square for exported backends, the stride-padded rectangle of LetterBox(auto=True) for a .pt; bilinear; cv2.resize(INTER_LINEAR) upstream - absent here, parity unpinned), centred, the border
 // filled with pad_value.  Thread = one output pixel.  The resample is the align_corners = False form PyTorch's
 // interpolate uses, in float32 in this order: src = scale * (dst + 0.5) - 0.5 clamped at 0, h0 * (w0 * v00 + w1 * v01) +
 // h1 * (w0 * v10 + w1 * v11), rounded to nearest even, clamped to [0, 255] (oracle/resize_ref.py: letterbox).  A frame
-// that already has the target size is copied exactly (all weights 0 or 1).
-__global__ __launch_bounds__(256) void letterbox_u8_kernel(const uint8_t* __restrict__ src, int h, int w, uint8_t* __restrict__ dst, int size,
-                                                          int nh, int nw, int top, int left, int pad_value) {
+// that already has the target size is copied exactly (all weights 0 or 1).  blockIdx.y: one of n same-sized frames.
+__global__ __launch_bounds__(256) void letterbox_u8_kernel(const uint8_t* __restrict__ src, int h, int w, uint8_t* __restrict__ dst, int dst_h,
+                                                          int dst_w, int nh, int nw, int top, int left, int pad_value) {
 #pragma clang fp contract(off)
   const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= size * size) return;
-  const int y = idx / size, x = idx - y * size;
-  uint8_t* o = dst + (long)idx * 3;
+  if (idx >= dst_h * dst_w) return;
+  const int y = idx / dst_w, x = idx - y * dst_w;
+  src += (long)blockIdx.y * h * w * 3;
+  uint8_t* o = dst + ((long)blockIdx.y * dst_h * dst_w + idx) * 3;
   const int ry = y - top, rx = x - left;
   if (ry < 0 || ry >= nh || rx < 0 || rx >= nw) {
     o[0] = o[1] = o[2] = (uint8_t)pad_value;
@@ -94,21 +95,63 @@ __global__ __launch_bounds__(256) void letterbox_u8_kernel(const uint8_t* __rest
   }
 }
 
+// pad of n letterboxed dst_h x dst_w x 3 frames whose (nh, nw) image at (top, left) is written by someone else
+__global__ __launch_bounds__(256) void letterbox_pad_kernel(uint8_t* __restrict__ f, int64_t npix, int dst_h, int dst_w, int nh, int nw,
+                                                            int top, int left, uint8_t v) {
+  const int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (g >= npix) return;
+  const int p = (int)(g % ((int64_t)dst_h * dst_w));
+  const int y = p / dst_w - top, x = p % dst_w - left;
+  if (y >= 0 && y < nh && x >= 0 && x < nw) return;
+  uint8_t* o = f + g * 3;
+  o[0] = o[1] = o[2] = v;
+}
+
+static void letterbox_launch(const uint8_t* src, int n, int h, int w, uint8_t* dst, int dst_h, int dst_w, int nh, int nw, int top, int left,
+                             int pad_value, hipStream_t s) {
+  MTGV_CHECK(src && dst, ERR_INVALID, "null argument");
+  MTGV_CHECK(n > 0 && n <= 65535 && h > 0 && w > 0 && dst_h > 0 && dst_w > 0 && (long)dst_h * dst_w < (1l << 30) && nh > 0 && nw > 0 && top >= 0 &&
+                 left >= 0 && top + nh <= dst_h && left + nw <= dst_w && pad_value >= 0 && pad_value <= 255,
+             ERR_INVALID, "letterbox: %d frames %dx%d -> %dx%d at (%d, %d) of %dx%d", n, h, w, nh, nw, top, left, dst_h, dst_w);
+  hipLaunchKernelGGL(letterbox_u8_kernel, dim3((dst_h * dst_w + 255) / 256, n), dim3(256), 0, s, src, h, w, dst, dst_h, dst_w, nh, nw, top,
+                     left, pad_value);
+  HIP_OK(hipGetLastError());
+}
+
+static void letterbox_pad_launch(uint8_t* frames, int n, int dst_h, int dst_w, int nh, int nw, int top, int left, int pad_value,
+                                 hipStream_t s) {
+  MTGV_CHECK(frames != nullptr || n == 0, ERR_INVALID, "null frames");
+  MTGV_CHECK(n >= 0 && dst_h > 0 && dst_w > 0 && (long)dst_h * dst_w < (1l << 30) && nh >= 0 && nw >= 0 && top >= 0 && left >= 0 &&
+                 top + nh <= dst_h && left + nw <= dst_w,
+             ERR_INVALID, "letterbox pad: image %dx%d at (%d, %d) outside a %dx%d frame", nh, nw, top, left, dst_h, dst_w);
+  MTGV_CHECK(pad_value >= 0 && pad_value <= 255, ERR_INVALID, "pad value %d outside [0, 255]", pad_value);
+  const int64_t npix = (int64_t)n * dst_h * dst_w;
+  if (npix == 0) return;
+  MTGV_CHECK(ceil_div64(npix, 256) <= 0x7fffffffl, ERR_INVALID, "letterbox pad: %d frames of %dx%d are too many for one launch", n, dst_h, dst_w);
+  hipLaunchKernelGGL(letterbox_pad_kernel, dim3((unsigned)ceil_div64(npix, 256)), dim3(256), 0, s, frames, npix, dst_h, dst_w, nh, nw, top, left,
+                     (uint8_t)pad_value);
+  HIP_OK(hipGetLastError());
+}
+
 }  // namespace mtgv
 
 using namespace mtgv;
 extern "C" {
 MTGV_API int mtgv_letterbox_u8(const uint8_t* src_dev, int32_t h, int32_t w, uint8_t* dst_dev, int32_t size, int32_t nh, int32_t nw,
                                int32_t top, int32_t left, int32_t pad_value, void* stream) {
-  return guarded([&] {
-    MTGV_CHECK(src_dev && dst_dev, ERR_INVALID, "null argument");
-    MTGV_CHECK(h > 0 && w > 0 && size > 0 && nh > 0 && nw > 0 && top >= 0 && left >= 0 && top + nh <= size && left + nw <= size &&
-                   pad_value >= 0 && pad_value <= 255,
-               ERR_INVALID, "letterbox: %dx%d -> %dx%d at (%d, %d) of %d", h, w, nh, nw, top, left, size);
-    hipLaunchKernelGGL(letterbox_u8_kernel, dim3((size * size + 255) / 256), dim3(256), 0, (hipStream_t)stream, src_dev, h, w, dst_dev, size,
-                       nh, nw, top, left, pad_value);
-    HIP_OK(hipGetLastError());
-  });
+  return guarded([&] { letterbox_launch(src_dev, 1, h, w, dst_dev, size, size, nh, nw, top, left, pad_value, (hipStream_t)stream); });
+}
+MTGV_API int mtgv_letterbox_rect_u8(const uint8_t* src_dev, int32_t n, int32_t h, int32_t w, uint8_t* dst_dev, int32_t dst_h, int32_t dst_w,
+                                    int32_t nh, int32_t nw, int32_t top, int32_t left, int32_t pad_value, void* stream) {
+  return guarded([&] { letterbox_launch(src_dev, n, h, w, dst_dev, dst_h, dst_w, nh, nw, top, left, pad_value, (hipStream_t)stream); });
+}
+MTGV_API int mtgv_letterbox_pad_u8(uint8_t* frames_dev, int32_t n, int32_t size, int32_t nh, int32_t nw, int32_t top, int32_t left,
+                                   int32_t pad_value, void* stream) {
+  return guarded([&] { letterbox_pad_launch(frames_dev, n, size, size, nh, nw, top, left, pad_value, (hipStream_t)stream); });
+}
+MTGV_API int mtgv_letterbox_pad_rect_u8(uint8_t* frames_dev, int32_t n, int32_t dst_h, int32_t dst_w, int32_t nh, int32_t nw, int32_t top,
+                                        int32_t left, int32_t pad_value, void* stream) {
+  return guarded([&] { letterbox_pad_launch(frames_dev, n, dst_h, dst_w, nh, nw, top, left, pad_value, (hipStream_t)stream); });
 }
 MTGV_API int mtgv_make_cropped(const uint8_t* images_dev, const int64_t* offsets_dev, const int32_t* hw_dev, int32_t n,
                                int32_t out_h, int32_t out_w, float* out_dev, void* stream) {

@@ -11,6 +11,8 @@ Everything numeric goes to the GPU library; these classes only translate types.
 
 from __future__ import annotations
 
+import dataclasses
+from collections import OrderedDict
 from copy import deepcopy
 from dataclasses import dataclass
 from pathlib import Path
@@ -21,7 +23,7 @@ import torch
 
 from . import spec
 from .crop import mask_quads_from_logits, warp_quads
-from .detector import Detector, binarize_masks, letterbox
+from .detector import Detector, binarize_masks, fit_geometry, rect_geometry
 from .encoder import Encoder
 from .matcher import Matcher
 
@@ -307,10 +309,12 @@ class CardSegmenter:
     `weights_only=True`; or pass `detector=` / `state_dict=`.  `.pt` pickles of whole ultralytics
     models are not loadable without the package (and are never unpickled here)."""
 
+    RECT_HANDLES = 4  # rect=True: Detector handles kept at a time, one per input rectangle
+
     def __init__(self, model_path: str | Path = None, *, state_dict=None, detector: Optional[Detector] = None, max_batch: int = 1,
-                 contours="trace"):
+                 contours="trace", rect: bool = False):
         """contours: what `InstanceSeg.points` holds (the reference: ultralytics `masks.xy`, od_export.py:152-153).
-        "trace" (default; True is accepted for it): the reference-shaped points - every 640 x 640 mask is copied to the
+        "trace" (default; True is accepted for it): the reference-shaped points - every mask (640 x 640; in_h x in_w of a rectangular handle) is copied to the
         host and its blobs are traced there like cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE) (`_mask_segments`;
         scipy), notches of the reference's U-shaped card masks (od_export.py:57-60) included; the quad and the closed
         polygon are derived lazily on the host as `InstanceSeg._orient` does.
@@ -319,12 +323,21 @@ class CardSegmenter:
         copy of those integers per call, no mask leaves the device.  A row-extent outline FILLS any notch that opens
         upwards or downwards, so `points` / `points_closed` differ from the reference for upright and upside-down cards
         (tests/test_adapters_cpu.py pins what they hold); quads, direction vectors and crops do not.
-        False: only the four GPU-fitted corners per card (they double as `points`) - for tracking loops."""
+        False: only the four GPU-fitted corners per card (they double as `points`) - for tracking loops.
+        rect: False (default) letterboxes every frame to imgsz x imgsz, what ultralytics does for exported backends
+        (.mlpackage, .onnx).  True is what its predictor does for a .pt checkpoint, LetterBox(auto=True): the pad only
+        reaches the next multiple of 32 and the network runs on that rectangle (`detector.rect_geometry`: 480 x 640 for a
+        webcam frame, 384 x 640 for 720p).  A handle's arena is laid out for one rectangle, so there is one `Detector`
+        per rectangle, created from the same state dict when a frame shape first needs it; at most RECT_HANDLES are
+        kept, the least recently used is dropped.  `self.yolo` is then the handle of the last call (None before the first)."""
         if contours is True:
             contours = "trace"
         assert contours in ("outline", "trace", False), contours
         self.contours = contours
+        self.rect = bool(rect)
+        self._rect_handles: "OrderedDict[tuple, Detector]" = OrderedDict()
         if detector is not None:
+            assert not rect, "CardSegmenter(rect=True) builds its own handles: pass model_path= or state_dict=, not detector="
             self.yolo = detector
         else:
             if state_dict is None:
@@ -335,11 +348,32 @@ class CardSegmenter:
             cfg = spec.detector_config_for_state(state_dict)
             # (the reference's class is YOLO(path, task="segment"), od_export.py:141-146: it has no OBB counterpart to mirror)
             assert cfg.task == "seg", 'CardSegmenter takes a segment checkpoint; an OBB one runs on mtgv.Detector / Pipeline(quad_source="obb")'
-            self.yolo = Detector(cfg, state_dict, max_batch=max_batch)  # v8n-seg or 11n-seg
+            self._cfg, self._state_dict, self._max_batch = cfg, state_dict, max_batch
+            self.yolo = None if rect else Detector(cfg, state_dict, max_batch=max_batch)  # v8n-seg or 11n-seg
+
+    def _handle_for(self, h: int, w: int):
+        """(Detector, ratio, left, top) for an (h, w) frame: the square handle, or with rect=True the handle of the
+        frame shape's own rectangle"""
+        if not self.rect:
+            # (what Detector.detect does: the frame scaled to fit the handle's own input, centred - letterbox_geometry on a
+            # square handle; a rectangular handle passed as detector= maps back with its own offsets)
+            cfg = self.yolo.cfg
+            ratio, _, _, top, left = fit_geometry(h, w, getattr(cfg, "in_h", cfg.imgsz), getattr(cfg, "in_w", cfg.imgsz))
+            return self.yolo, ratio, left, top
+        ratio, _, _, top, left, out_h, out_w = rect_geometry(h, w, self._cfg.imgsz)
+        key = (out_h, out_w)
+        det = self._rect_handles.pop(key, None)
+        if det is None:
+            while len(self._rect_handles) >= self.RECT_HANDLES:
+                self._rect_handles.popitem(last=False)
+            det = Detector(dataclasses.replace(self._cfg, input_hw=key), self._state_dict, max_batch=self._max_batch)
+        self._rect_handles[key] = det  # most recently used last
+        self.yolo = det
+        return det, ratio, left, top
 
     def __call__(self, rgb_im: np.ndarray) -> list[InstanceSeg]:
-        img, ratio, (left, top) = letterbox(rgb_im, self.yolo.cfg.imgsz)
-        det = self.yolo.detect(rgb_im)
+        yolo, ratio, left, top = self._handle_for(rgb_im.shape[0], rgb_im.shape[1])
+        det = yolo.detect(rgb_im)
         detections = []
         if det.mask_logits is None or det.conf.numel() == 0:
             return detections

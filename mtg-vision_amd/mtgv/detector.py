@@ -22,11 +22,11 @@ from . import native, spec
 class Detections:
     """Raw per-frame detector output (score-descending)."""
 
-    boxes_xyxy: torch.Tensor  # (n, 4) float32, pixels of the letterboxed 640x640 frame
+    boxes_xyxy: torch.Tensor  # (n, 4) float32, pixels of the letterboxed frame (640 x 640, or the handle's in_h x in_w)
     conf: torch.Tensor  # (n,) float32
     cls: torch.Tensor  # (n,) int64
-    keep_idx: torch.Tensor  # (n,) int64 anchor index in [0, 8400)
-    mask_logits: Optional[torch.Tensor]  # (n, 160, 160) float32, zero outside the box
+    keep_idx: torch.Tensor  # (n,) int64 anchor index in [0, num_anchors)
+    mask_logits: Optional[torch.Tensor]  # (n, in_h / 4, in_w / 4) float32 (160 x 160 at 640 x 640), zero outside the box
 
 
 @dataclass
@@ -47,12 +47,44 @@ def letterbox_geometry(h: int, w: int, size: int = 640):
     return r, nh, nw, int(round(dh - 0.1)), int(round(dw - 0.1))
 
 
-def letterbox_device(frame: torch.Tensor, size: int = 640, pad_value: int = 114):
+def rect_geometry(h: int, w: int, size: int = 640, stride: int = 32):
+    """ultralytics LetterBox(auto=True) geometry, what the predictor runs in front of a .pt checkpoint [external - recalled
+    from ultralytics 8.3.x, unpinned like the rest of the detector]: scale to fit `size`, then pad only up to the next
+    multiple of `stride`.  (ratio, nh, nw, top, left, out_h, out_w): the (nh, nw) image sits at (top, left) of an
+    (out_h, out_w) input - 480 x 640 for a 640 x 480 webcam frame, 384 x 640 for 720p."""
+    r = min(size / h, size / w)
+    nh, nw = int(round(h * r)), int(round(w * r))
+    dh, dw = ((size - nh) % stride) / 2, ((size - nw) % stride) / 2
+    top, bottom = int(round(dh - 0.1)), int(round(dh + 0.1))
+    left, right = int(round(dw - 0.1)), int(round(dw + 0.1))
+    return r, nh, nw, top, left, nh + top + bottom, nw + left + right
+
+
+def fit_geometry(h: int, w: int, out_h: int, out_w: int):
+    """an (h, w) frame scaled to fit and centred in an (out_h, out_w) input: (ratio, nh, nw, top, left).  Equals
+    `letterbox_geometry` on a square and `rect_geometry` whenever (out_h, out_w) is that frame shape's own rectangle."""
+    r = min(out_h / h, out_w / w)
+    nh, nw = min(int(round(h * r)), out_h), min(int(round(w * r)), out_w)
+    return r, nh, nw, int(round((out_h - nh) / 2 - 0.1)), int(round((out_w - nw) / 2 - 0.1))
+
+
+def letterbox_device(frame: torch.Tensor, size=640, pad_value: int = 114):
     """(H, W, 3) uint8 frame on the GPU -> ((1, size, size, 3) uint8 letterboxed image on the GPU, ratio, (left, top)): one
-    library kernel (resize.hip: letterbox_u8_kernel) instead of a host resample + pad."""
+    library kernel (resize.hip: letterbox_u8_kernel) instead of a host resample + pad.  `size` = (out_h, out_w): the
+    rectangular form - (n, H, W, 3) same-sized frames are also taken - scaled to fit and centred (`fit_geometry`)."""
     native.require_gpu()
-    assert frame.is_cuda and frame.dtype == torch.uint8 and frame.ndim == 3 and frame.shape[-1] == 3, f"{tuple(frame.shape)} {frame.dtype}"
-    h, w = int(frame.shape[0]), int(frame.shape[1])
+    assert frame.is_cuda and frame.dtype == torch.uint8 and frame.ndim in (3, 4) and frame.shape[-1] == 3, f"{tuple(frame.shape)} {frame.dtype}"
+    h, w = int(frame.shape[-3]), int(frame.shape[-2])
+    if isinstance(size, (tuple, list)):
+        out_h, out_w = int(size[0]), int(size[1])
+        n = int(frame.shape[0]) if frame.ndim == 4 else 1
+        r, nh, nw, top, left = fit_geometry(h, w, out_h, out_w)
+        out = torch.empty((n, out_h, out_w, 3), dtype=torch.uint8, device=frame.device)
+        with torch.cuda.device(frame.device):
+            native.check(native.lib().mtgv_letterbox_rect_u8(native.ptr(frame.contiguous()), n, h, w, native.ptr(out), out_h, out_w, nh, nw, top,
+                                                             left, pad_value, native.stream()))
+        return out, r, (left, top)
+    assert frame.ndim == 3, f"{tuple(frame.shape)}"
     r, nh, nw, top, left = letterbox_geometry(h, w, size)
     out = torch.empty((1, size, size, 3), dtype=torch.uint8, device=frame.device)
     with torch.cuda.device(frame.device):
@@ -102,6 +134,8 @@ class Detector:
         c.conf, c.iou, c.max_det = self.cfg.conf, self.cfg.iou, self.cfg.max_det
         c.arch = 11 if self.cfg.arch == "11" else 8
         c.task = 1 if self.cfg.task == "obb" else 0
+        if self.cfg.input_hw is not None:  # (0, 0: the square imgsz x imgsz)
+            c.in_h, c.in_w = self.cfg.in_h, self.cfg.in_w
         self._h = native.c_vp(0)
         with torch.cuda.device(self.device):
             native.check(native.lib().mtgv_detector_create(C.byref(c), C.byref(self._h)))
@@ -126,14 +160,17 @@ class Detector:
 
     # ---- batched device API (what the pipeline uses) ---------------------------
     def forward(self, frames_u8: torch.Tensor, flip_rgb: bool = True, mask_rows: int = 0):
-        """frames (n, 640, 640, 3) uint8 on the GPU -> dict of padded device tensors.
+        """frames (n, in_h, in_w, 3) uint8 on the GPU (640 x 640 unless cfg.input_hw names a rectangle) -> dict of padded
+        device tensors.
 
         n_det (n,) int32; boxes (n, max_det, 4); conf (n, max_det); cls, keep_idx (n, max_det) int32;
-        mask_logits (n, mask_rows, 160, 160) if mask_rows > 0.
+        mask_logits (n, mask_rows, in_h / 4, in_w / 4) if mask_rows > 0.
         An OBB detector returns n_det, rboxes (n, max_det, 5) xywh + angle, conf, cls, keep_idx; it has no masks and
         ignores mask_rows."""
-        S, md = self.cfg.imgsz, self.cfg.max_det
-        assert frames_u8.dtype == torch.uint8 and frames_u8.is_cuda and tuple(frames_u8.shape[1:]) == (S, S, 3), f"{tuple(frames_u8.shape)}"
+        H, W, md = self.cfg.in_h, self.cfg.in_w, self.cfg.max_det
+        assert frames_u8.dtype == torch.uint8 and frames_u8.is_cuda and frames_u8.ndim == 4 and tuple(frames_u8.shape[1:]) == (H, W, 3), (
+            f"frames {tuple(frames_u8.shape)} {frames_u8.dtype}: expected (n, {H}, {W}, 3) uint8 on the GPU"
+        )
         n = frames_u8.shape[0]
         assert 0 < n <= self.max_batch, f"batch {n} outside [1, {self.max_batch}]"
         dev = self.device
@@ -146,7 +183,7 @@ class Detector:
             "conf": torch.empty((n, md), dtype=torch.float32, device=dev),
             "cls": torch.empty((n, md), dtype=torch.int32, device=dev),
             "keep_idx": torch.empty((n, md), dtype=torch.int32, device=dev),
-            "mask_logits": torch.empty((n, mask_rows, S // 4, S // 4), dtype=torch.float32, device=dev) if mask_rows > 0 else None,
+            "mask_logits": torch.empty((n, mask_rows, H // 4, W // 4), dtype=torch.float32, device=dev) if mask_rows > 0 else None,
         }
         with torch.cuda.device(dev):
             native.check(
@@ -180,27 +217,27 @@ class Detector:
         native.check(native.lib().mtgv_detector_set_fork(self._h, int(mode)))
 
     def raw_outputs(self, n: int):
-        """pred (n, 4+nc+32, 8400) and protos (n, 32, 160, 160) of the last forward (parity tests); an OBB detector
-        gives (pred (n, 4+nc+1, 8400), None)."""
-        S = self.cfg.imgsz
+        """pred (n, 4+nc+32, na) and protos (n, 32, in_h / 4, in_w / 4) of the last forward (parity tests; 8400 and
+        160 x 160 at 640 x 640); an OBB detector gives (pred (n, 4+nc+1, na), None)."""
         pred = torch.empty((n, self.cfg.no, self.cfg.num_anchors), dtype=torch.float32, device=self.device)
         if self.cfg.task == "obb":
             with torch.cuda.device(self.device):
                 native.check(native.lib().mtgv_detector_raw(self._h, n, native.ptr(pred), native.c_vp(0), native.stream()))
             return pred, None
-        protos = torch.empty((n, self.cfg.nm, S // 4, S // 4), dtype=torch.float32, device=self.device)
+        protos = torch.empty((n, self.cfg.nm, self.cfg.in_h // 4, self.cfg.in_w // 4), dtype=torch.float32, device=self.device)
         with torch.cuda.device(self.device):
             native.check(native.lib().mtgv_detector_raw(self._h, n, native.ptr(pred), native.ptr(protos), native.stream()))
         return pred, protos
 
     # ---- single-frame API -------------------------------------------------------
     def detect(self, frame: np.ndarray, flip_rgb: bool = True, masks: bool = True):
-        """One HWC uint8 frame (any size) -> Detections (ObbDetections from an OBB detector) in letterboxed 640x640
-        coordinates."""
+        """One HWC uint8 frame (any size) -> Detections (ObbDetections from an OBB detector) in the coordinates of the
+        letterboxed input (640 x 640; a rectangular handle: the frame scaled to fit its in_h x in_w, centred)."""
         assert frame.ndim == 3 and frame.shape[-1] == 3 and frame.dtype == np.uint8, f"{frame.shape} {frame.dtype}"
         # the raw frame goes to the GPU as it is; scale-to-fit + pad there (the host `letterbox` only supplies the geometry
         # to callers that map coordinates back, e.g. CardSegmenter)
-        x, _, _ = letterbox_device(torch.from_numpy(np.ascontiguousarray(frame)).to(self.device), self.cfg.imgsz)
+        size = self.cfg.imgsz if self.cfg.input_hw is None else (self.cfg.in_h, self.cfg.in_w)
+        x, _, _ = letterbox_device(torch.from_numpy(np.ascontiguousarray(frame)).to(self.device), size)
         if self.cfg.task == "obb":
             out = self.forward(x, flip_rgb)
             n = int(out["n_det"][0].item())
@@ -290,7 +327,8 @@ def probiou(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
 
 
 def binarize_masks(mask_logits: torch.Tensor, scale: int = 4) -> torch.Tensor:
-    """(n, 160, 160) cropped logits -> (n, 640, 640) uint8 {0,1}: bilinear x4 (align_corners=False), > 0."""
+    """(n, mh, mw) cropped logits -> (n, mh * scale, mw * scale) uint8 {0,1}: bilinear x`scale` (align_corners=False), > 0.
+    (160 x 160 -> 640 x 640 for a square handle, in_h / 4 x in_w / 4 -> in_h x in_w for a rectangular one.)"""
     native.require_gpu()
     assert mask_logits.is_cuda and mask_logits.dtype == torch.float32 and mask_logits.ndim == 3
     n, mh, mw = mask_logits.shape

@@ -4,8 +4,9 @@ built from the same graph tables as the GPU executor (`spec.detector_graph`), fo
 
 The reference exports its trained detector with `YOLO(pt).export(format="onnx", nms=True)` and
 `.export(format="coreml", nms=False)` (mtgvision/od_export.py:163-176); ultralytics and coremltools are absent here, so
-this module mirrors the `nms=False` form: frames (B, 3, 640, 640) float in [0, 1] -> (pred (B, 4 + nc + nm, A) decoded
-boxes / class scores / mask coefficients, protos (B, nm, 160, 160)).  NMS and mask assembly stay outside the graph
+this module mirrors the `nms=False` form: frames (B, 3, in_h, in_w) float in [0, 1] (640 x 640 unless cfg.input_hw names a
+rectangle) -> (pred (B, 4 + nc + nm, A) decoded boxes / class scores / mask coefficients, protos (B, nm, in_h / 4, in_w / 4)).
+NMS and mask assembly stay outside the graph
 (`mtgv.detector.nms`, `Detector.forward`).  With `task="obb"` (what od_train.py builds by default) the head is `OBB` and
 the only output is pred (B, 4 + nc + 1, A) = xywh, class scores, angle (`mtgv.detector.nms_rotated` outside the graph).
 
@@ -166,6 +167,16 @@ class _Proto(nn.Module):
         return self.cv3(self.cv2(self.upsample(self.cv1(x))))
 
 
+def _make_anchors(cfg: spec.DetectorConfig):
+    """anchor centres (2, A) in grid units and strides (1, A): the pixels of cfg.grids row-major, P3 first"""
+    pts, st = [], []
+    for s, (gh, gw) in zip((8, 16, 32), cfg.grids):
+        sy, sx = torch.meshgrid(torch.arange(gh, dtype=torch.float32) + 0.5, torch.arange(gw, dtype=torch.float32) + 0.5, indexing="ij")
+        pts.append(torch.stack((sx, sy), -1).view(-1, 2))
+        st.append(torch.full((gh * gw, 1), float(s)))
+    return torch.cat(pts).T.contiguous(), torch.cat(st).T.contiguous()
+
+
 class Segment(nn.Module):
     """Segment head (Detect + prototypes + mask coefficients), inference form"""
 
@@ -187,17 +198,11 @@ class Segment(nn.Module):
         self.dfl = _DFL(rm)
         self.proto = _Proto(ch[0], cfg.npr, nm)
         self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), nn.Conv2d(c4, nm, 1)) for x in ch)
-        pts, st = [], []
-        for s in (8, 16, 32):
-            n = cfg.imgsz // s
-            sx = torch.arange(n, dtype=torch.float32) + 0.5
-            sy, sxx = torch.meshgrid(sx, sx, indexing="ij")
-            pts.append(torch.stack((sxx, sy), -1).view(-1, 2))
-            st.append(torch.full((n * n, 1), float(s)))
+        anchors, strides = _make_anchors(cfg)
         self.anchors: torch.Tensor
         self.strides: torch.Tensor
-        self.register_buffer("anchors", torch.cat(pts).T.contiguous(), persistent=False)
-        self.register_buffer("strides", torch.cat(st).T.contiguous(), persistent=False)
+        self.register_buffer("anchors", anchors, persistent=False)
+        self.register_buffer("strides", strides, persistent=False)
 
     def forward(self, feats):
         cfg = self.cfg
@@ -234,17 +239,11 @@ class OBB(nn.Module):
             self.cv3 = nn.ModuleList(nn.Sequential(Conv(x, c3, 3), Conv(c3, c3, 3), nn.Conv2d(c3, nc, 1)) for x in ch)
         self.dfl = _DFL(rm)
         self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), nn.Conv2d(c4, ne, 1)) for x in ch)
-        pts, st = [], []
-        for s in (8, 16, 32):
-            n = cfg.imgsz // s
-            sx = torch.arange(n, dtype=torch.float32) + 0.5
-            sy, sxx = torch.meshgrid(sx, sx, indexing="ij")
-            pts.append(torch.stack((sxx, sy), -1).view(-1, 2))
-            st.append(torch.full((n * n, 1), float(s)))
+        anchors, strides = _make_anchors(cfg)
         self.anchors: torch.Tensor
         self.strides: torch.Tensor
-        self.register_buffer("anchors", torch.cat(pts).T.contiguous(), persistent=False)
-        self.register_buffer("strides", torch.cat(st).T.contiguous(), persistent=False)
+        self.register_buffer("anchors", anchors, persistent=False)
+        self.register_buffer("strides", strides, persistent=False)
 
     def forward(self, feats):
         cfg = self.cfg
@@ -310,9 +309,9 @@ def to_torch_module(cfg: spec.DetectorConfig, state_dict: Mapping) -> DetectorMo
 
 
 def export_torchscript(cfg: spec.DetectorConfig, state_dict: Mapping, path: str):
-    """`torch.jit.trace` of the detector on a (1, 3, imgsz, imgsz) example, saved to `path`"""
+    """`torch.jit.trace` of the detector on a (1, 3, in_h, in_w) example, saved to `path`"""
     m = to_torch_module(cfg, state_dict)
-    ts = torch.jit.trace(m, torch.rand((1, 3, cfg.imgsz, cfg.imgsz)))
+    ts = torch.jit.trace(m, torch.rand((1, 3, cfg.in_h, cfg.in_w)))
     ts.save(path)
     return ts
 
@@ -324,6 +323,6 @@ def export_onnx(cfg: spec.DetectorConfig, state_dict: Mapping, path: str):
     if importlib.util.find_spec("onnx") is None:
         raise RuntimeError("the onnx package is not installed")
     m = to_torch_module(cfg, state_dict)
-    ex = torch.rand((1, 3, cfg.imgsz, cfg.imgsz))
+    ex = torch.rand((1, 3, cfg.in_h, cfg.in_w))
     outs = ["pred"] if cfg.task == "obb" else ["pred", "protos"]
     torch.onnx.export(m, ex, path, input_names=["images"], output_names=outs, dynamic_axes={k: {0: "n"} for k in ["images"] + outs})

@@ -5,7 +5,7 @@ reads card scans from JPEG files for the bank build (qdrant_populate.py:70-90). 
 device in one copy per batch and are decoded there:
 
     dec = JpegDecoder(max_images=32, max_bytes=4 << 20, max_pixels=32 * 640 * 480)
-    frames = dec.decode_frames(list_of_jpeg_bytes)          # (n, 640, 640, 3) uint8, letterboxed, on the GPU
+    frames = dec.decode_frames(list_of_jpeg_bytes)          # (n, 640, 640, 3) uint8, letterboxed, on the GPU; input_hw=(480, 640): (n, 480, 640, 3)
     buf, offsets, hw, status = dec.decode(list_of_jpeg_bytes)  # ragged RGB, the layout mtgv_make_cropped takes
 
 Supported: baseline / extended sequential Huffman 8-bit (SOF0 / SOF1), greyscale or YCbCr 4:4:4 / 4:2:2 / 4:2:0,
@@ -23,7 +23,7 @@ import numpy as np
 import torch
 
 from . import native
-from .detector import letterbox_geometry
+from .detector import fit_geometry, letterbox_geometry
 
 
 class JpegInfo(NamedTuple):
@@ -127,20 +127,26 @@ class JpegDecoder:
         hw = hw.cpu().tolist() if torch.is_tensor(hw) else list(hw)
         return [buf[o : o + h * w * 3].view(h, w, 3) for o, (h, w) in zip(offsets, hw)]
 
-    def decode_frames(self, datas: Sequence[bytes], size: int = 640, pad_value: int = 114, out: torch.Tensor = None, check: bool = True):
-        """JPEG frames -> (n, size, size, 3) uint8 letterboxed frames on the GPU (mtgv.detector.letterbox_geometry).  A frame
+    def decode_frames(self, datas: Sequence[bytes], size: int = 640, pad_value: int = 114, out: torch.Tensor = None, check: bool = True,
+                      input_hw=None):
+        """JPEG frames -> (n, size, size, 3) - with input_hw (n, in_h, in_w, 3) - uint8 letterboxed frames on the GPU
+        (mtgv.detector.letterbox_geometry / fit_geometry).  A frame
         that already fits (640x480 webcam frames) is decoded straight into its padded frame through offset and pitch and only
-        the pad is filled; any other is decoded to scratch and resampled by mtgv_letterbox_u8."""
+        the pad is filled; any other is decoded to scratch and resampled by mtgv_letterbox_rect_u8.
+        input_hw = (in_h, in_w): the input of a rectangular detector (spec.DetectorConfig(input_hw=...)) instead, every frame
+        scaled to fit and centred in it (mtgv.detector.fit_geometry) -> (n, in_h, in_w, 3).  A frame of exactly that size (a
+        640x480 JPEG into (480, 640)) is decoded straight into the detector's input: no pad pass, no resample."""
         infos = self._infos(datas)
         n = len(datas)
+        oh, ow = (size, size) if input_hw is None else (int(input_hw[0]), int(input_hw[1]))
         if out is None:
-            out = torch.empty((n, size, size, 3), dtype=torch.uint8, device=self.device)
-        assert out.shape == (n, size, size, 3) and out.dtype == torch.uint8 and out.is_contiguous()
+            out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=self.device)
+        assert out.shape == (n, oh, ow, 3) and out.dtype == torch.uint8 and out.is_contiguous()
         if n == 0:
             return out
         L = native.lib()
-        fsz = size * size * 3
-        geo = [letterbox_geometry(f.h, f.w, size) for f in infos]
+        fsz = oh * ow * 3
+        geo = [letterbox_geometry(f.h, f.w, size) if input_hw is None else fit_geometry(f.h, f.w, oh, ow) for f in infos]
         direct = [i for i, f in enumerate(infos) if (geo[i][1], geo[i][2]) == (f.h, f.w)]
         other = [i for i in range(n) if (geo[i][1], geo[i][2]) != (infos[i].h, infos[i].w)]
         dst_off = np.zeros(n, np.int64)
@@ -156,8 +162,8 @@ class JpegDecoder:
         b0 = base.data_ptr()
         for i in direct:
             _, nh, nw, top, left = geo[i]
-            dst_off[i] = out.data_ptr() - b0 + i * fsz + (top * size + left) * 3
-            pitch[i] = size * 3
+            dst_off[i] = out.data_ptr() - b0 + i * fsz + (top * ow + left) * 3
+            pitch[i] = ow * 3
         for j, i in enumerate(other):
             dst_off[i] = scratch.data_ptr() - b0 + int(soff[j])
             pitch[i] = infos[i].w * 3
@@ -167,15 +173,17 @@ class JpegDecoder:
             for i in direct:
                 groups.setdefault(geo[i][1:], []).append(i)
             for (nh, nw, top, left), idx in groups.items():
+                if (nh, nw) == (oh, ow):
+                    continue  # the frame fills its input: there is no pad
                 runs = _runs(idx)
                 for a, b in runs:  # consecutive frames of one geometry: one launch
-                    native.check(L.mtgv_letterbox_pad_u8(C.c_void_p(out.data_ptr() + a * fsz), b - a, size, nh, nw, top, left, pad_value,
-                                                         native.stream()))
+                    native.check(L.mtgv_letterbox_pad_rect_u8(C.c_void_p(out.data_ptr() + a * fsz), b - a, oh, ow, nh, nw, top, left, pad_value,
+                                                              native.stream()))
             for j, i in enumerate(other):
                 f = infos[i]
                 _, nh, nw, top, left = geo[i]
-                native.check(L.mtgv_letterbox_u8(C.c_void_p(scratch.data_ptr() + int(soff[j])), f.h, f.w, C.c_void_p(out.data_ptr() + i * fsz),
-                                                 size, nh, nw, top, left, pad_value, native.stream()))
+                native.check(L.mtgv_letterbox_rect_u8(C.c_void_p(scratch.data_ptr() + int(soff[j])), 1, f.h, f.w, C.c_void_p(out.data_ptr() + i * fsz),
+                                                      oh, ow, nh, nw, top, left, pad_value, native.stream()))
         if scratch is not None:
             scratch.record_stream(torch.cuda.current_stream(self.device))
         if check:
@@ -215,11 +223,14 @@ class JpegFrames:
     which the caller reads once the pipeline's outputs are synchronised (reading it earlier would stall the overlap)."""
 
     def __init__(self, jpeg_batches: Sequence[Sequence[bytes]], device, size: int = 640, pad_value: int = 114, depth: int = 3,
-                 decoder: JpegDecoder = None):
+                 decoder: JpegDecoder = None, input_hw=None):
+        """input_hw = (in_h, in_w): buffers of a rectangular detector's input (JpegDecoder.decode_frames)"""
         assert depth >= 2 and len(jpeg_batches) > 0
         self.batches = [list(b) for b in jpeg_batches]
         self.device = torch.device(device)
         self.size, self.pad_value, self.depth = size, pad_value, depth
+        self.input_hw = None if input_hw is None else (int(input_hw[0]), int(input_hw[1]))
+        oh, ow = (size, size) if self.input_hw is None else self.input_hw
         n = max(len(b) for b in self.batches)
         if decoder is None:
             nbytes = max(sum(len(d) for d in b) for b in self.batches)
@@ -227,7 +238,7 @@ class JpegFrames:
             decoder = JpegDecoder(n, nbytes, pix, self.device)
         self.dec = decoder
         self.s_dec = torch.cuda.Stream(self.device)
-        self.bufs = [torch.empty((n, size, size, 3), dtype=torch.uint8, device=self.device) for _ in range(depth)]
+        self.bufs = [torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=self.device) for _ in range(depth)]
         self.decoded = [torch.cuda.Event() for _ in range(depth)]
         self.released = [None] * depth
         self._issued = 0
@@ -253,7 +264,7 @@ class JpegFrames:
             if self.released[j] is not None:
                 self.s_dec.wait_event(self.released[j])  # the batch that used this buffer has been de-warped
             n = len(datas)
-            self.dec.decode_frames(datas, self.size, self.pad_value, out=self.bufs[j][:n], check=False)
+            self.dec.decode_frames(datas, self.size, self.pad_value, out=self.bufs[j][:n], check=False, input_hw=self.input_hw)
             status = self.dec.last_status
             self.decoded[j].record(self.s_dec)
         return JpegFrames._Lease(self, j, n, status)

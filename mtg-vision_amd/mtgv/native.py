@@ -45,6 +45,8 @@ class DetectorCfg(C.Structure):
         ("max_det", c_i32),
         ("arch", c_i32),
         ("task", c_i32),  # 0 segment, 1 OBB (mtgv_version >= 101)
+        ("in_h", c_i32),  # the input rectangle, both 0: imgsz x imgsz (mtgv_version >= 102)
+        ("in_w", c_i32),
     ]
 
 
@@ -68,7 +70,7 @@ class ConvEx(C.Structure):
 class HeadRows(C.Structure):
     """mtgv_head_rows: the segment head's raw rows of the three pyramid levels and their layout (test surface)"""
 
-    _fields_ = [(k, c_vp) for k in ("r0", "r1", "r2")] + [(k, c_i32) for k in ("imgsz", "ct", "cls", "coef")]
+    _fields_ = [(k, c_vp) for k in ("r0", "r1", "r2")] + [(k, c_i32) for k in ("imgsz", "ct", "cls", "coef", "h", "w")]
 
 
 class ProtoTail(C.Structure):
@@ -92,6 +94,7 @@ SIGNATURES = {
     "mtgv_bank_topk_packed": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i64, c_vp, c_vp]),
     "mtgv_topk_merge_gathered": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp]),
     "mtgv_letterbox_u8": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "mtgv_letterbox_rect_u8": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "mtgv_profile_gemm": (C.c_int, [c_i32]),
     "mtgv_profile_gemm_read": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(c_i64)]),
     "mtgv_profile_gemm_bytes": (C.c_int, [C.POINTER(C.c_double)]),
@@ -150,6 +153,7 @@ SIGNATURES = {
     "mtgv_mask_quads_logits": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mtgv_make_cropped": (C.c_int, [c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mtgv_letterbox_pad_u8": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "mtgv_letterbox_pad_rect_u8": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "mtgv_jpeg_info": (C.c_int, [c_vp, c_i64, C.POINTER(c_i32)]),
     "mtgv_jpeg_decoder_create": (C.c_int, [c_i32, c_i64, c_i64, C.POINTER(c_vp)]),
     "mtgv_jpeg_decoder_destroy": (None, [c_vp]),

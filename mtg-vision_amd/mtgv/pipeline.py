@@ -18,7 +18,7 @@ from .detector import Detector
 from .encoder import Encoder
 from .matcher import Matcher
 
-# fixed quads (pixels of the 640x640 frame) used when a frame has fewer than K detections, so that
+# fixed quads (pixels of the 640x640 frame; scaled with a rectangular detector's input, Pipeline.__init__) used when a frame has fewer than K detections, so that
 # cards/sec is well defined on synthetic frames
 _PAD_BOXES = torch.tensor(
     [[40.0, 60.0, 168.0, 252.0], [200.0, 60.0, 328.0, 252.0], [360.0, 60.0, 488.0, 252.0], [500.0, 60.0, 628.0, 252.0],
@@ -124,7 +124,12 @@ class Pipeline:
         self._plain_match = match_fn is None
         self.match_fn = match_fn or (lambda z, k: matcher.match(z, k))
         reps = (self.K + _PAD_BOXES.shape[0] - 1) // _PAD_BOXES.shape[0]
-        self._pad = _PAD_BOXES.repeat(reps, 1)[: self.K].to(detector.device).contiguous()
+        # a rectangular detector (cfg.input_hw): the pad boxes shrink with the frame, (in_w / imgsz, in_h / imgsz), and stay
+        # inside it; a square handle keeps the numbers above
+        dcfg = getattr(detector, "cfg", None)
+        sx, sy = (dcfg.in_w / dcfg.imgsz, dcfg.in_h / dcfg.imgsz) if getattr(dcfg, "input_hw", None) is not None else (1.0, 1.0)
+        pad = _PAD_BOXES * torch.tensor([sx, sy, sx, sy])
+        self._pad = pad.repeat(reps, 1)[: self.K].to(detector.device).contiguous()
         self._warp_ws = None
 
     def _embed_match(self, frames_u8: torch.Tensor, det, lease=None):
@@ -298,7 +303,8 @@ class Pipeline:
         return outs
 
     def run(self, frames_u8: torch.Tensor, flip_rgb: bool = True):
-        """frames (F, 640, 640, 3) uint8 on the GPU -> dict with ids (F, K, top_k) int64, scores, n_det (F,)
+        """frames (F, in_h, in_w, 3) uint8 on the GPU (640 x 640 unless the detector's cfg.input_hw names a rectangle; the mask
+        quads, the OBB quads and the de-warp work in the pixels of that frame) -> dict with ids (F, K, top_k) int64, scores, n_det (F,)
         and the intermediate crops / embeddings (device tensors)."""
         frames_u8, lease = _frames_of(frames_u8)
         det = self.detector.forward(frames_u8, flip_rgb, mask_rows=self.K)

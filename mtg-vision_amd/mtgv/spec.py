@@ -17,7 +17,7 @@ from __future__ import annotations
 
 from collections import OrderedDict
 from dataclasses import dataclass, field, asdict
-from typing import Dict, Tuple
+from typing import Dict, Optional, Tuple
 
 import numpy as np
 
@@ -282,10 +282,32 @@ class DetectorConfig:
     # od_train.py:19, :101 builds by default (kind="obb").  [external - recalled from ultralytics 8.3.x]
     task: str = "seg"
     ne: int = 1  # OBB: extra outputs per anchor (the angle logit)
+    # (in_h, in_w) of a rectangular handle - what ultralytics' LetterBox(auto=True) feeds a .pt checkpoint, e.g. (480, 640)
+    # for a webcam frame (mtgv.detector.rect_geometry); each a multiple of 32 in [32, imgsz].  None: imgsz x imgsz.
+    input_hw: Optional[Tuple[int, int]] = None
 
     def __post_init__(self):
         if self.task not in ("seg", "obb"):
             raise KeyError(f"task={self.task} not recognized")
+        if self.input_hw is not None:
+            hw = tuple(int(v) for v in self.input_hw)
+            assert len(hw) == 2 and all(32 <= v <= self.imgsz and v % 32 == 0 for v in hw), (
+                f"input_hw={self.input_hw}: two multiples of 32 in [32, {self.imgsz}]"
+            )
+            object.__setattr__(self, "input_hw", hw)
+
+    @property
+    def in_h(self) -> int:
+        return self.imgsz if self.input_hw is None else self.input_hw[0]
+
+    @property
+    def in_w(self) -> int:
+        return self.imgsz if self.input_hw is None else self.input_hw[1]
+
+    @property
+    def grids(self) -> Tuple[Tuple[int, int], ...]:
+        """(gh, gw) of P3, P4, P5 (strides 8, 16, 32): the anchors are their pixels row-major, in this order"""
+        return tuple((self.in_h // s, self.in_w // s) for s in (8, 16, 32))
 
     def ch(self, c: int) -> int:
         # make_divisible(min(c, max_ch) * width, 8)
@@ -301,7 +323,7 @@ class DetectorConfig:
 
     @property
     def num_anchors(self) -> int:
-        return sum((self.imgsz // s) ** 2 for s in (8, 16, 32))
+        return sum(gh * gw for gh, gw in self.grids)
 
     @property
     def no(self) -> int:
