@@ -14,7 +14,7 @@
 //   6. R = (-U.y, U.x); TL = c + U h/2 - R w/2, TR = c + U h/2 + R w/2, BR = c - U h/2 + R w/2, BL = c - U h/2 - R w/2
 // One thread per (frame, slot): the slot's card is the slot-th detection of card_cls in score order, or pad_boxes[slot]
 // where the frame has fewer.  Single rounded float32 operations in the order written (contraction off), accurate
-// sinf / cosf; tests/obb_ref.py restates it operation for operation.
+// sinf / cosf; oracle/obb_ref.py restates it operation for operation.
 #include "common.h"
 #include "mtgv.h"
 

@@ -4,7 +4,7 @@
 // derived from the Bhattacharyya distance bd of the two Gaussians.  Defined once for its two users, the rotated NMS
 // kernel and mtgv_op_probiou (nms.hip).  Every operation is a single rounded float32 operation in the order written
 // (contraction off), with the accurate sinf / cosf / logf / expf / sqrtf, so that the CPU restatement of the tests
-// (tests/obb_ref.py) differs by the math libraries' few ulp per transcendental only.
+// (oracle/obb_ref.py) differs by the math libraries' few ulp per transcendental only.
 #pragma once
 #include "common.h"
 

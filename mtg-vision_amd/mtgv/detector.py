@@ -40,11 +40,9 @@ class ObbDetections:
 
 
 def letterbox_geometry(h: int, w: int, size: int = 640):
-    """ultralytics LetterBox geometry: (ratio, nh, nw, top, left) - scale to fit, centre (round(d - 0.1) like upstream)"""
-    r = min(size / h, size / w)
-    nh, nw = int(round(h * r)), int(round(w * r))
-    dh, dw = (size - nh) / 2, (size - nw) / 2
-    return r, nh, nw, int(round(dh - 0.1)), int(round(dw - 0.1))
+    """ultralytics LetterBox geometry: (ratio, nh, nw, top, left) - scale to fit, centre (round(d - 0.1) like upstream):
+    `fit_geometry` on a square"""
+    return fit_geometry(h, w, size, size)
 
 
 def rect_geometry(h: int, w: int, size: int = 640, stride: int = 32):
@@ -62,34 +60,26 @@ def rect_geometry(h: int, w: int, size: int = 640, stride: int = 32):
 
 def fit_geometry(h: int, w: int, out_h: int, out_w: int):
     """an (h, w) frame scaled to fit and centred in an (out_h, out_w) input: (ratio, nh, nw, top, left).  Equals
-    `letterbox_geometry` on a square and `rect_geometry` whenever (out_h, out_w) is that frame shape's own rectangle."""
+    `rect_geometry` whenever (out_h, out_w) is that frame shape's own rectangle."""
     r = min(out_h / h, out_w / w)
     nh, nw = min(int(round(h * r)), out_h), min(int(round(w * r)), out_w)
     return r, nh, nw, int(round((out_h - nh) / 2 - 0.1)), int(round((out_w - nw) / 2 - 0.1))
 
 
 def letterbox_device(frame: torch.Tensor, size=640, pad_value: int = 114):
-    """(H, W, 3) uint8 frame on the GPU -> ((1, size, size, 3) uint8 letterboxed image on the GPU, ratio, (left, top)): one
-    library kernel (resize.hip: letterbox_u8_kernel) instead of a host resample + pad.  `size` = (out_h, out_w): the
-    rectangular form - (n, H, W, 3) same-sized frames are also taken - scaled to fit and centred (`fit_geometry`)."""
+    """(H, W, 3) uint8 frame on the GPU, or (n, H, W, 3) same-sized frames -> ((n, out_h, out_w, 3) uint8 letterboxed images
+    on the GPU, ratio, (left, top)): one library kernel (resize.hip: letterbox_u8_kernel) instead of a host resample + pad.
+    `size` = (out_h, out_w), or one int for a square: scaled to fit and centred (`fit_geometry`)."""
     native.require_gpu()
     assert frame.is_cuda and frame.dtype == torch.uint8 and frame.ndim in (3, 4) and frame.shape[-1] == 3, f"{tuple(frame.shape)} {frame.dtype}"
     h, w = int(frame.shape[-3]), int(frame.shape[-2])
-    if isinstance(size, (tuple, list)):
-        out_h, out_w = int(size[0]), int(size[1])
-        n = int(frame.shape[0]) if frame.ndim == 4 else 1
-        r, nh, nw, top, left = fit_geometry(h, w, out_h, out_w)
-        out = torch.empty((n, out_h, out_w, 3), dtype=torch.uint8, device=frame.device)
-        with torch.cuda.device(frame.device):
-            native.check(native.lib().mtgv_letterbox_rect_u8(native.ptr(frame.contiguous()), n, h, w, native.ptr(out), out_h, out_w, nh, nw, top,
-                                                             left, pad_value, native.stream()))
-        return out, r, (left, top)
-    assert frame.ndim == 3, f"{tuple(frame.shape)}"
-    r, nh, nw, top, left = letterbox_geometry(h, w, size)
-    out = torch.empty((1, size, size, 3), dtype=torch.uint8, device=frame.device)
+    out_h, out_w = (int(size[0]), int(size[1])) if isinstance(size, (tuple, list)) else (int(size), int(size))
+    n = int(frame.shape[0]) if frame.ndim == 4 else 1
+    r, nh, nw, top, left = fit_geometry(h, w, out_h, out_w)
+    out = torch.empty((n, out_h, out_w, 3), dtype=torch.uint8, device=frame.device)
     with torch.cuda.device(frame.device):
-        native.check(native.lib().mtgv_letterbox_u8(native.ptr(frame.contiguous()), h, w, native.ptr(out), size, nh, nw, top, left, pad_value,
-                                                    native.stream()))
+        native.check(native.lib().mtgv_letterbox_rect_u8(native.ptr(frame.contiguous()), n, h, w, native.ptr(out), out_h, out_w, nh, nw, top,
+                                                         left, pad_value, native.stream()))
     return out, r, (left, top)
 
 
@@ -101,18 +91,28 @@ def letterbox(frame: np.ndarray, size: int = 640, pad_value: int = 114):
     resized bilinearly on the host (cv2.resize is not available here: that resample is unpinned).
     """
     h, w = frame.shape[:2]
-    r = min(size / h, size / w)
-    nh, nw = int(round(h * r)), int(round(w * r))
+    r, nh, nw, top, left = letterbox_geometry(h, w, size)
     img = frame
     if (nh, nw) != (h, w):
         t = torch.from_numpy(np.ascontiguousarray(frame)).permute(2, 0, 1)[None].float()
         t = torch.nn.functional.interpolate(t, (nh, nw), mode="bilinear", align_corners=False)
         img = t[0].permute(1, 2, 0).round().clamp(0, 255).to(torch.uint8).numpy()
-    dh, dw = (size - nh) / 2, (size - nw) / 2
-    top, left = int(round(dh - 0.1)), int(round(dw - 0.1))
     out = np.full((size, size, 3), pad_value, np.uint8)
     out[top : top + nh, left : left + nw] = img
     return out, r, (left, top)
+
+
+def _padded_outputs(n: int, max_det: int, box_name: str, box_width: int, dev):
+    """the padded output tensors of a forward or an NMS: n_det (n,) int32, `box_name` (n, max_det, box_width) float32, conf
+    (n, max_det) float32, cls and keep_idx (n, max_det) int32.  Uninitialised: the library writes every element (slots
+    beyond n_det as zeros), so there are no fill kernels here."""
+    return {
+        "n_det": torch.empty((n,), dtype=torch.int32, device=dev),
+        box_name: torch.empty((n, max_det, box_width), dtype=torch.float32, device=dev),
+        "conf": torch.empty((n, max_det), dtype=torch.float32, device=dev),
+        "cls": torch.empty((n, max_det), dtype=torch.int32, device=dev),
+        "keep_idx": torch.empty((n, max_det), dtype=torch.int32, device=dev),
+    }
 
 
 class Detector:
@@ -176,15 +176,9 @@ class Detector:
         dev = self.device
         if self.cfg.task == "obb":
             return self._forward_obb(frames_u8, n, flip_rgb)
-        # every element is written by the library (slots / mask rows beyond n_det as zeros): no fill kernels here
-        out = {
-            "n_det": torch.empty((n,), dtype=torch.int32, device=dev),
-            "boxes": torch.empty((n, md, 4), dtype=torch.float32, device=dev),
-            "conf": torch.empty((n, md), dtype=torch.float32, device=dev),
-            "cls": torch.empty((n, md), dtype=torch.int32, device=dev),
-            "keep_idx": torch.empty((n, md), dtype=torch.int32, device=dev),
-            "mask_logits": torch.empty((n, mask_rows, H // 4, W // 4), dtype=torch.float32, device=dev) if mask_rows > 0 else None,
-        }
+        out = _padded_outputs(n, md, "boxes", 4, dev)
+        # mask rows beyond n_det are written too (zeros)
+        out["mask_logits"] = torch.empty((n, mask_rows, H // 4, W // 4), dtype=torch.float32, device=dev) if mask_rows > 0 else None
         with torch.cuda.device(dev):
             native.check(
                 native.lib().mtgv_detector_forward(
@@ -195,14 +189,8 @@ class Detector:
         return out
 
     def _forward_obb(self, frames_u8: torch.Tensor, n: int, flip_rgb: bool):
-        md, dev = self.cfg.max_det, self.device
-        out = {
-            "n_det": torch.empty((n,), dtype=torch.int32, device=dev),
-            "rboxes": torch.empty((n, md, 5), dtype=torch.float32, device=dev),
-            "conf": torch.empty((n, md), dtype=torch.float32, device=dev),
-            "cls": torch.empty((n, md), dtype=torch.int32, device=dev),
-            "keep_idx": torch.empty((n, md), dtype=torch.int32, device=dev),
-        }
+        dev = self.device
+        out = _padded_outputs(n, self.cfg.max_det, "rboxes", 5, dev)
         with torch.cuda.device(dev):
             native.check(
                 native.lib().mtgv_detector_forward_obb(
@@ -275,13 +263,7 @@ def nms(pred: torch.Tensor, nc: int, conf: float = 0.25, iou: float = 0.7, max_d
     dev = pred.device
     L = native.lib()
     ws = torch.empty((int(L.mtgv_nms_workspace_bytes(n, na)) + 3) // 4, dtype=torch.int32, device=dev)
-    out = {
-        "n_det": torch.zeros((n,), dtype=torch.int32, device=dev),
-        "boxes": torch.zeros((n, max_det, 4), dtype=torch.float32, device=dev),
-        "conf": torch.zeros((n, max_det), dtype=torch.float32, device=dev),
-        "cls": torch.zeros((n, max_det), dtype=torch.int32, device=dev),
-        "keep_idx": torch.zeros((n, max_det), dtype=torch.int32, device=dev),
-    }
+    out = _padded_outputs(n, max_det, "boxes", 4, dev)
     with torch.cuda.device(dev):
         native.check(
             L.mtgv_nms(native.ptr(pred), n, nc, nm, na, conf, iou, max_det, max_wh, native.ptr(out["n_det"]), native.ptr(out["boxes"]),
@@ -300,13 +282,7 @@ def nms_rotated(pred: torch.Tensor, nc: int, conf: float = 0.25, iou: float = 0.
     dev = pred.device
     L = native.lib()
     ws = torch.empty((int(L.mtgv_nms_rotated_workspace_bytes(n, na)) + 3) // 4, dtype=torch.int32, device=dev)
-    out = {
-        "n_det": torch.empty((n,), dtype=torch.int32, device=dev),
-        "rboxes": torch.empty((n, max_det, 5), dtype=torch.float32, device=dev),
-        "conf": torch.empty((n, max_det), dtype=torch.float32, device=dev),
-        "cls": torch.empty((n, max_det), dtype=torch.int32, device=dev),
-        "keep_idx": torch.empty((n, max_det), dtype=torch.int32, device=dev),
-    }
+    out = _padded_outputs(n, max_det, "rboxes", 5, dev)
     with torch.cuda.device(dev):
         native.check(
             L.mtgv_nms_rotated(native.ptr(pred), n, nc, na, conf, iou, max_det, max_wh, native.ptr(out["n_det"]), native.ptr(out["rboxes"]),

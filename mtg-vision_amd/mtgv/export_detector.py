@@ -177,16 +177,18 @@ def _make_anchors(cfg: spec.DetectorConfig):
     return torch.cat(pts).T.contiguous(), torch.cat(st).T.contiguous()
 
 
-class Segment(nn.Module):
-    """Segment head (Detect + prototypes + mask coefficients), inference form"""
+class _Detect(nn.Module):
+    """what the two heads share: the box branch cv2, the class branch cv3 (either architecture's), the DFL, a cv4 branch
+    with `n4` outputs per anchor, and the anchors and strides of cfg.grids.  `proto` (Segment's) is registered between dfl
+    and cv4, where the upstream state_dict has it."""
 
-    def __init__(self, cfg: spec.DetectorConfig, ch):
+    def __init__(self, cfg: spec.DetectorConfig, ch, n4, proto=None):
         super().__init__()
-        self.cfg = cfg
-        nc, nm, rm = cfg.nc, cfg.nm, cfg.reg_max
+        self.cfg, self.n4 = cfg, n4
+        nc, rm = cfg.nc, cfg.reg_max
         c2 = max(16, ch[0] // 4, rm * 4)
         c3 = max(ch[0], min(nc, 100))
-        c4 = max(ch[0] // 4, nm)
+        c4 = max(ch[0] // 4, n4)
         self.cv2 = nn.ModuleList(nn.Sequential(Conv(x, c2, 3), Conv(c2, c2, 3), nn.Conv2d(c2, 4 * rm, 1)) for x in ch)
         if cfg.arch == "11":
             self.cv3 = nn.ModuleList(
@@ -196,63 +198,50 @@ class Segment(nn.Module):
         else:
             self.cv3 = nn.ModuleList(nn.Sequential(Conv(x, c3, 3), Conv(c3, c3, 3), nn.Conv2d(c3, nc, 1)) for x in ch)
         self.dfl = _DFL(rm)
-        self.proto = _Proto(ch[0], cfg.npr, nm)
-        self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), nn.Conv2d(c4, nm, 1)) for x in ch)
+        if proto is not None:
+            self.proto = proto
+        self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), nn.Conv2d(c4, n4, 1)) for x in ch)
         anchors, strides = _make_anchors(cfg)
         self.anchors: torch.Tensor
         self.strides: torch.Tensor
         self.register_buffer("anchors", anchors, persistent=False)
         self.register_buffer("strides", strides, persistent=False)
 
-    def forward(self, feats):
+    def logits(self, feats):
+        """(lt, rb) DFL distances (B, 2, A) each, class logits (B, nc, A), cv4 outputs (B, n4, A): levels concatenated, P3 first"""
         cfg = self.cfg
         b = feats[0].shape[0]
-        protos = self.proto(feats[0])
-        mc = torch.cat([self.cv4[i](f).view(b, cfg.nm, -1) for i, f in enumerate(feats)], 2)
+        extra = torch.cat([self.cv4[i](f).view(b, self.n4, -1) for i, f in enumerate(feats)], 2)
         x = torch.cat([torch.cat((self.cv2[i](f), self.cv3[i](f)), 1).view(b, 4 * cfg.reg_max + cfg.nc, -1) for i, f in enumerate(feats)], 2)
         box, cls = x.split((4 * cfg.reg_max, cfg.nc), 1)
-        dist = self.dfl(box)
-        lt, rb = dist.chunk(2, 1)
+        lt, rb = self.dfl(box).chunk(2, 1)
+        return lt, rb, cls, extra
+
+
+class Segment(_Detect):
+    """Segment head (Detect + prototypes + mask coefficients), inference form"""
+
+    def __init__(self, cfg: spec.DetectorConfig, ch):
+        super().__init__(cfg, ch, cfg.nm, proto=_Proto(ch[0], cfg.npr, cfg.nm))
+
+    def forward(self, feats):
+        protos = self.proto(feats[0])
+        lt, rb, cls, mc = self.logits(feats)
         x1y1, x2y2 = self.anchors.unsqueeze(0) - lt, self.anchors.unsqueeze(0) + rb
         dbox = torch.cat(((x1y1 + x2y2) / 2, x2y2 - x1y1), 1) * self.strides
         return torch.cat((dbox, cls.sigmoid(), mc), 1), protos
 
 
-class OBB(nn.Module):
+class OBB(_Detect):
     """OBB head (Detect + one angle logit per anchor), inference form: pred (B, 4 + nc + 1, A) = xywh in pixels, class
     sigmoids, angle in radians.  [external - recalled from ultralytics 8.3.x OBB.forward / dist2rbox; unpinned]"""
 
     def __init__(self, cfg: spec.DetectorConfig, ch):
-        super().__init__()
-        self.cfg = cfg
-        nc, ne, rm = cfg.nc, cfg.ne, cfg.reg_max
-        c2 = max(16, ch[0] // 4, rm * 4)
-        c3 = max(ch[0], min(nc, 100))
-        c4 = max(ch[0] // 4, ne)
-        self.cv2 = nn.ModuleList(nn.Sequential(Conv(x, c2, 3), Conv(c2, c2, 3), nn.Conv2d(c2, 4 * rm, 1)) for x in ch)
-        if cfg.arch == "11":
-            self.cv3 = nn.ModuleList(
-                nn.Sequential(nn.Sequential(Conv(x, x, 3, g=x), Conv(x, c3, 1)), nn.Sequential(Conv(c3, c3, 3, g=c3), Conv(c3, c3, 1)), nn.Conv2d(c3, nc, 1))
-                for x in ch
-            )
-        else:
-            self.cv3 = nn.ModuleList(nn.Sequential(Conv(x, c3, 3), Conv(c3, c3, 3), nn.Conv2d(c3, nc, 1)) for x in ch)
-        self.dfl = _DFL(rm)
-        self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), nn.Conv2d(c4, ne, 1)) for x in ch)
-        anchors, strides = _make_anchors(cfg)
-        self.anchors: torch.Tensor
-        self.strides: torch.Tensor
-        self.register_buffer("anchors", anchors, persistent=False)
-        self.register_buffer("strides", strides, persistent=False)
+        super().__init__(cfg, ch, cfg.ne)
 
     def forward(self, feats):
-        cfg = self.cfg
-        b = feats[0].shape[0]
-        angle = torch.cat([self.cv4[i](f).view(b, cfg.ne, -1) for i, f in enumerate(feats)], 2)
+        lt, rb, cls, angle = self.logits(feats)
         angle = (angle.sigmoid() - 0.25) * torch.pi
-        x = torch.cat([torch.cat((self.cv2[i](f), self.cv3[i](f)), 1).view(b, 4 * cfg.reg_max + cfg.nc, -1) for i, f in enumerate(feats)], 2)
-        box, cls = x.split((4 * cfg.reg_max, cfg.nc), 1)
-        lt, rb = self.dfl(box).chunk(2, 1)
         cos, sin = torch.cos(angle), torch.sin(angle)
         xf, yf = ((rb - lt) / 2).split(1, 1)
         xy = torch.cat((xf * cos - yf * sin, xf * sin + yf * cos), 1) + self.anchors.unsqueeze(0)

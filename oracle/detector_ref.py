@@ -1,12 +1,14 @@
 """ORACLE (test infrastructure, never shipped or measured as the product).
 
-CPU restatement of the YOLO-seg detector (YOLOv8n-seg, and YOLO11n-seg with C3k2 / C2PSA / DWConv class branch - the
-architecture od_train.py:20, :55-56 trains by default) that mtg-vision's `CardSegmenter` delegates to
-(mtgvision/od_export.py:141-160: `YOLO(path, task="segment")([rgb_im])[0]`, then
-`results.masks.xy` / `results.boxes.conf`; model family fixed by od_train.py:46-70).
+CPU restatement of the YOLO detector, both families, on square or rectangular inputs (`cfg.grids`): the segment family
+(YOLOv8n-seg, and YOLO11n-seg with C3k2 / C2PSA / DWConv class branch) that mtg-vision's `CardSegmenter` delegates to
+(mtgvision/od_export.py:141-160: `YOLO(path, task="segment")([rgb_im])[0]`, then `results.masks.xy` /
+`results.boxes.conf`; model family fixed by od_train.py:46-70), and the OBB family that od_train.py:19, :101 builds by
+default (its head and decode below; ProbIoU, rotated NMS and the card rule in oracle/obb_ref.py, recalled and unpinned as
+that file states).  `head`, `forward` and `detect` dispatch on `cfg.task`.
 
 PARITY UNPINNED: the arithmetic lives in the third-party package `ultralytics~=8.3.80`
-(pyproject.toml:32), which is absent from /root/reference and not installed here, and the
+(pyproject.toml:32), which is absent from the reference and not installed here, and the
 reference holds no tests or golden vectors for it.  What is restated below is the
 published YOLOv8-seg algorithm (module graph of yolov8-seg.yaml at scale "n", Conv =
 Conv2d(bias=False)+BatchNorm2d(eps=1e-3)+SiLU, C2f, SPPF, Segment/Detect head with DFL
@@ -24,6 +26,7 @@ import torch
 import torch.nn.functional as F
 
 from mtgv import spec
+from oracle import obb_ref
 
 
 def _conv(x, p, prefix, k, s=1, eps=1e-3, act=True):
@@ -146,38 +149,46 @@ def backbone_neck(x, p, cfg: spec.DetectorConfig):
 
 
 def make_anchors(cfg: spec.DetectorConfig):
-    """anchor centres (2, A) and strides (1, A): grid (x+0.5, y+0.5), row-major per level."""
+    """anchor centres (2, A) and strides (1, A): grid (x + 0.5, y + 0.5) of cfg.grids, row-major per level, P3 first"""
     pts, st = [], []
-    for s in (8, 16, 32):
-        n = cfg.imgsz // s
-        sx = torch.arange(n, dtype=torch.float32) + 0.5
-        sy, sxx = torch.meshgrid(sx, sx, indexing="ij")
-        pts.append(torch.stack((sxx, sy), -1).view(-1, 2))
-        st.append(torch.full((n * n, 1), float(s)))
+    for s, (gh, gw) in zip((8, 16, 32), cfg.grids):
+        sy, sx = torch.meshgrid(torch.arange(gh, dtype=torch.float32) + 0.5, torch.arange(gw, dtype=torch.float32) + 0.5, indexing="ij")
+        pts.append(torch.stack((sx, sy), -1).view(-1, 2))
+        st.append(torch.full((gh * gw, 1), float(s)))
     return torch.cat(pts).T.contiguous(), torch.cat(st).T.contiguous()
 
 
-def head(feats, p, cfg: spec.DetectorConfig):
-    """Segment head: returns pred (B, 4+nc+nm, A) [xywh px, class sigmoid, coeffs] and protos (B, nm, 160, 160)."""
+def _head_logits(feats, p, cfg: spec.DetectorConfig, n4):
+    """what the two heads share, on feature maps of cfg.grids: box logits (B, 4 * reg_max, A), class logits (B, nc, A) and
+    the cv4 branch's outputs (B, n4, A), levels concatenated P3 first; anchors (2, A) and strides (1, A) in their dtype"""
+    for f, (gh, gw) in zip(feats, cfg.grids):
+        assert tuple(f.shape[2:]) == (gh, gw), (tuple(f.shape), cfg.grids)
     pre = f"model.{cfg.head_index}"
     eps = cfg.bn_eps
     b = feats[0].shape[0]
     cls_branch = _branch_dw if cfg.arch == "11" else _branch
+    extra = torch.cat([_branch(f, p, f"{pre}.cv4.{l}", eps).view(b, n4, -1) for l, f in enumerate(feats)], 2)
+    xs = [torch.cat((_branch(f, p, f"{pre}.cv2.{l}", eps), cls_branch(f, p, f"{pre}.cv3.{l}", eps)), 1) for l, f in enumerate(feats)]
+    x_cat = torch.cat([xi.view(b, 4 * cfg.reg_max + cfg.nc, -1) for xi in xs], 2)
+    box, cls = x_cat.split((4 * cfg.reg_max, cfg.nc), 1)
+    anchors, strides = make_anchors(cfg)
+    return box, cls, extra, anchors.to(box.dtype), strides.to(box.dtype)
+
+
+def _head_segment(feats, p, cfg: spec.DetectorConfig):
+    """Segment head: pred (B, 4 + nc + nm, A) [xywh px, class sigmoid, coeffs] and protos (B, nm, in_h / 4, in_w / 4)"""
+    pre = f"model.{cfg.head_index}"
+    eps = cfg.bn_eps
     # Proto: Conv3 -> ConvTranspose2d(k2,s2,bias) -> Conv3 -> Conv1
     x = _conv(feats[0], p, f"{pre}.proto.cv1", 3, eps=eps)
     x = F.conv_transpose2d(x, p[f"{pre}.proto.upsample.weight"], p[f"{pre}.proto.upsample.bias"], stride=2)
     x = _conv(x, p, f"{pre}.proto.cv2", 3, eps=eps)
     protos = _conv(x, p, f"{pre}.proto.cv3", 1, eps=eps)
-    mc = torch.cat([_branch(f, p, f"{pre}.cv4.{l}", eps).view(b, cfg.nm, -1) for l, f in enumerate(feats)], 2)
-    xs = [torch.cat((_branch(f, p, f"{pre}.cv2.{l}", eps), cls_branch(f, p, f"{pre}.cv3.{l}", eps)), 1) for l, f in enumerate(feats)]
-    x_cat = torch.cat([xi.view(b, 4 * cfg.reg_max + cfg.nc, -1) for xi in xs], 2)
-    box, cls = x_cat.split((4 * cfg.reg_max, cfg.nc), 1)
+    box, cls, mc, anchors, strides = _head_logits(feats, p, cfg, cfg.nm)
     # DFL: softmax over the 16 bins, expectation with weights arange(16)
-    a = box.shape[-1]
+    b, a = box.shape[0], box.shape[-1]
     w = p[f"{pre}.dfl.conv.weight"].view(1, cfg.reg_max, 1, 1)
     dist = (box.view(b, 4, cfg.reg_max, a).transpose(2, 1).softmax(1) * w).sum(1)  # (b, 4, a) l,t,r,b
-    anchors, strides = make_anchors(cfg)
-    anchors, strides = anchors.to(dist.dtype), strides.to(dist.dtype)
     lt, rb = dist.chunk(2, 1)
     x1y1 = anchors.unsqueeze(0) - lt
     x2y2 = anchors.unsqueeze(0) + rb
@@ -186,8 +197,32 @@ def head(feats, p, cfg: spec.DetectorConfig):
     return pred, protos
 
 
+def _head_obb(feats, p, cfg: spec.DetectorConfig):
+    """OBB head: pred (B, 4 + nc + 1, A) = xywh px, class sigmoids, angle.  [external - recalled from ultralytics 8.3.x
+    OBB.forward / dist2rbox, unpinned: see oracle/obb_ref.py]"""
+    box, cls, logit, anchors, strides = _head_logits(feats, p, cfg, cfg.ne)
+    angle = (logit.sigmoid() - 0.25) * torch.pi
+    # DFL as upstream writes it: softmax over the 16 bins, then the fixed 1x1 conv with weights arange(16)
+    b, a = box.shape[0], box.shape[-1]
+    w = p[f"model.{cfg.head_index}.dfl.conv.weight"].view(1, cfg.reg_max, 1, 1)
+    dist = F.conv2d(box.view(b, 4, cfg.reg_max, a).transpose(2, 1).softmax(1), w).view(b, 4, a)  # l, t, r, b
+    l_, t_, r_, b_ = dist.unbind(1)
+    ang = angle[:, 0]
+    cs, sn = torch.cos(ang), torch.sin(ang)
+    xf, yf = (r_ - l_) / 2, (b_ - t_) / 2
+    x = (xf * cs - yf * sn + anchors[0]) * strides[0]
+    y = (xf * sn + yf * cs + anchors[1]) * strides[0]
+    wh = torch.stack(((l_ + r_) * strides[0], (t_ + b_) * strides[0]), 1)
+    return torch.cat((torch.stack((x, y), 1), wh, cls.sigmoid(), angle), 1)
+
+
+def head(feats, p, cfg: spec.DetectorConfig):
+    """the head of cfg.task: (pred, protos) for segment, pred for OBB"""
+    return _head_obb(feats, p, cfg) if cfg.task == "obb" else _head_segment(feats, p, cfg)
+
+
 def preprocess(frames_u8: np.ndarray, flip_rgb: bool = True, dtype=torch.float32):
-    """(B, 640, 640, 3) uint8 letterboxed frames -> (B, 3, 640, 640) float in [0,1].
+    """(B, H, W, 3) uint8 letterboxed frames -> (B, 3, H, W) float in [0,1].
 
     ultralytics treats ndarray input as BGR and reverses the channel order first
     (`im[..., ::-1]`), which the reference's callers rely on (server.py:272-274 hands RGB,
@@ -200,6 +235,8 @@ def preprocess(frames_u8: np.ndarray, flip_rgb: bool = True, dtype=torch.float32
 
 
 def forward(params, cfg: spec.DetectorConfig, frames_u8, flip_rgb=True, dtype=torch.float32):
+    """(B, in_h, in_w, 3) uint8 frames -> (pred, protos) (segment) or pred (OBB), torch tensors of `dtype`"""
+    assert tuple(np.asarray(frames_u8).shape[1:]) == (cfg.in_h, cfg.in_w, 3), (np.asarray(frames_u8).shape, cfg.in_h, cfg.in_w)
     p = {k: (v if isinstance(v, torch.Tensor) else torch.from_numpy(np.asarray(v))).to(dtype) for k, v in params.items()}
     with torch.no_grad():
         x = preprocess(frames_u8, flip_rgb, dtype)
@@ -252,16 +289,19 @@ def nms_single(pred: np.ndarray, nc: int, conf_thres=0.25, iou_thres=0.7, max_de
     }
 
 
-def mask_logits(pred_img: np.ndarray, protos_img: np.ndarray, det: dict, nc: int, imgsz: int = 640) -> np.ndarray:
-    """process_mask up to the crop: (n, 160, 160) float32 logits, zero outside the box.
+def mask_logits(pred_img: np.ndarray, protos_img: np.ndarray, det: dict, nc: int, imgsz=640) -> np.ndarray:
+    """process_mask up to the crop: (n, mh, mw) float32 logits (160 x 160 at 640 x 640), zero outside the box.  `imgsz`: the
+    input's side, or its (in_h, in_w).
 
-    coeffs @ protos, then crop_mask with the box scaled to mask units, x in [x1, x2), y in [y1, y2)."""
+    coeffs @ protos (summed in float64 and rounded once, whichever dtype the inputs come in), then crop_mask with the box
+    scaled to mask units per direction, x in [x1, x2), y in [y1, y2)."""
+    in_h, in_w = imgsz if isinstance(imgsz, (tuple, list)) else (imgsz, imgsz)
     c, mh, mw = protos_img.shape
     coef = np.asarray(pred_img, np.float32)[4 + nc :, det["keep_idx"]].T  # (n, nm)
     m = (coef.astype(np.float64) @ protos_img.reshape(c, -1).astype(np.float64)).reshape(-1, mh, mw).astype(np.float32)
     b = det["boxes"].astype(np.float32).copy()
-    b[:, [0, 2]] *= np.float32(mw / imgsz)
-    b[:, [1, 3]] *= np.float32(mh / imgsz)
+    b[:, [0, 2]] *= np.float32(mw / in_w)
+    b[:, [1, 3]] *= np.float32(mh / in_h)
     r = np.arange(mw, dtype=np.float32)[None, None, :]
     cc = np.arange(mh, dtype=np.float32)[None, :, None]
     inside = (r >= b[:, 0, None, None]) & (r < b[:, 2, None, None]) & (cc >= b[:, 1, None, None]) & (cc < b[:, 3, None, None])
@@ -276,13 +316,20 @@ def masks_binary(logits: np.ndarray, imgsz: int = 640) -> np.ndarray:
     return (t > 0).numpy()
 
 
-def detect(params, cfg: spec.DetectorConfig, frames_u8, flip_rgb=True):
-    """Full detector on a batch: list of per-image dicts (keep_idx, boxes, conf, cls, mask_logits)."""
-    pred, protos = forward(params, cfg, frames_u8, flip_rgb)
+def detect(params, cfg: spec.DetectorConfig, frames_u8, flip_rgb=True, dtype=torch.float32):
+    """Full detector on a batch: (list of per-image dicts (keep_idx, boxes, conf, cls, mask_logits), pred, protos); OBB:
+    (list of dicts of obb_ref.nms_rotated_single, pred, None).  NMS and the mask crop run on pred rounded to float32 in
+    either dtype."""
+    if cfg.task == "obb":
+        pred = forward(params, cfg, frames_u8, flip_rgb, dtype).numpy()
+        p32 = pred.astype(np.float32)
+        return [obb_ref.nms_rotated_single(p32[i], cfg.nc, cfg.conf, cfg.iou, cfg.max_det, cfg.max_wh) for i in range(len(p32))], pred, None
+    pred, protos = forward(params, cfg, frames_u8, flip_rgb, dtype)
     pred, protos = pred.numpy(), protos.numpy()
+    p32 = pred.astype(np.float32)
     out = []
     for i in range(pred.shape[0]):
-        d = nms_single(pred[i], cfg.nc, cfg.conf, cfg.iou, cfg.max_det, cfg.max_wh)
-        d["mask_logits"] = mask_logits(pred[i], protos[i], d, cfg.nc, cfg.imgsz)
+        d = nms_single(p32[i], cfg.nc, cfg.conf, cfg.iou, cfg.max_det, cfg.max_wh)
+        d["mask_logits"] = mask_logits(p32[i], protos[i], d, cfg.nc, (cfg.in_h, cfg.in_w))
         out.append(d)
     return out, pred, protos

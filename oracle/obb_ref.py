@@ -1,7 +1,7 @@
 """ORACLE for the OBB detector family (test infrastructure, never shipped or measured as the product).
 
-CPU restatement of what the OBB tests check the GPU against: the OBB head on top of oracle/detector_ref.py's backbone and
-neck, ProbIoU, the rotated NMS rule and this project's card-orientation rule.
+CPU restatement of what the OBB tests check the GPU against beside the network itself: ProbIoU, the rotated NMS rule and
+this project's card-orientation rule.  The OBB head and its decode sit with the segment head in oracle/detector_ref.py.
 
 [external - recalled] PARITY UNPINNED: head, decode (`dist2rbox`), ProbIoU (`batch_probiou`) and the rotated NMS rule
 (`non_max_suppression(rotated=True)` -> `nms_rotated`) are ultralytics 8.3.x's as recalled; the package is absent and the
@@ -17,49 +17,8 @@ yardstick for both.
 from __future__ import annotations
 
 import numpy as np
-import torch
-import torch.nn.functional as F
-
-from mtgv import spec
-from oracle import detector_ref as D
 
 EPS = 1e-7
-
-
-# ---------------------------------------------------------------------------
-# head + decode
-# ---------------------------------------------------------------------------
-def head(feats, p, cfg: spec.DetectorConfig):
-    """OBB head: pred (B, 4 + nc + 1, A) = xywh px, class sigmoids, angle."""
-    pre = f"model.{cfg.head_index}"
-    eps = cfg.bn_eps
-    b = feats[0].shape[0]
-    cls_branch = D._branch_dw if cfg.arch == "11" else D._branch
-    logit = torch.cat([D._branch(f, p, f"{pre}.cv4.{l}", eps).view(b, cfg.ne, -1) for l, f in enumerate(feats)], 2)
-    angle = (logit.sigmoid() - 0.25) * torch.pi
-    xs = [torch.cat((D._branch(f, p, f"{pre}.cv2.{l}", eps), cls_branch(f, p, f"{pre}.cv3.{l}", eps)), 1) for l, f in enumerate(feats)]
-    x_cat = torch.cat([xi.view(b, 4 * cfg.reg_max + cfg.nc, -1) for xi in xs], 2)
-    box, cls = x_cat.split((4 * cfg.reg_max, cfg.nc), 1)
-    a = box.shape[-1]
-    # DFL as upstream writes it: softmax over the 16 bins, then the fixed 1x1 conv with weights arange(16)
-    w = p[f"{pre}.dfl.conv.weight"].view(1, cfg.reg_max, 1, 1)
-    dist = F.conv2d(box.view(b, 4, cfg.reg_max, a).transpose(2, 1).softmax(1), w).view(b, 4, a)  # l, t, r, b
-    anchors, strides = D.make_anchors(cfg)
-    anchors, strides = anchors.to(dist.dtype), strides.to(dist.dtype)
-    l_, t_, r_, b_ = dist.unbind(1)
-    ang = angle[:, 0]
-    cs, sn = torch.cos(ang), torch.sin(ang)
-    xf, yf = (r_ - l_) / 2, (b_ - t_) / 2
-    x = (xf * cs - yf * sn + anchors[0]) * strides[0]
-    y = (xf * sn + yf * cs + anchors[1]) * strides[0]
-    wh = torch.stack(((l_ + r_) * strides[0], (t_ + b_) * strides[0]), 1)
-    return torch.cat((torch.stack((x, y), 1), wh, cls.sigmoid(), angle), 1)
-
-
-def forward(params, cfg: spec.DetectorConfig, frames_u8, flip_rgb=True, dtype=torch.float32):
-    p = {k: (v if isinstance(v, torch.Tensor) else torch.from_numpy(np.asarray(v))).to(dtype) for k, v in params.items()}
-    with torch.no_grad():
-        return head(D.backbone_neck(D.preprocess(frames_u8, flip_rgb, dtype), p, cfg), p, cfg)
 
 
 # ---------------------------------------------------------------------------

@@ -73,3 +73,20 @@ def letterbox(frame_u8: np.ndarray, size: int = 640, pad_value: int = 114) -> np
     out = np.full((size, size, 3), pad_value, np.uint8)
     out[top : top + nh, left : left + nw] = img
     return out
+
+
+def letterbox_rect(frame: np.ndarray, size: int = 640, stride: int = 32, pad_value: int = 114):
+    """the expected LetterBox(auto=True) image of `frame`: `letterbox` holds the same resampled (nh, nw) image (r, nh and nw
+    are the square letterbox's); it is cut out and placed at (top, left) of a pad_value-filled (out_h, out_w) image.
+    Returns (image, geometry of mtgv.detector.rect_geometry)."""
+    from mtgv.detector import letterbox_geometry, rect_geometry
+
+    h, w = frame.shape[:2]
+    geo = rect_geometry(h, w, size, stride)
+    r, nh, nw, top, left, out_h, out_w = geo
+    r0, nh0, nw0, top0, left0 = letterbox_geometry(h, w, size)
+    assert (r0, nh0, nw0) == (r, nh, nw)
+    sq = letterbox(frame, size)
+    out = np.full((out_h, out_w, 3), pad_value, np.uint8)
+    out[top : top + nh, left : left + nw] = sq[top0 : top0 + nh, left0 : left0 + nw]
+    return out, geo

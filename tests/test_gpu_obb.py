@@ -1,12 +1,13 @@
 """The OBB detector family on the GPU (YOLOv8n-obb / YOLO11n-obb: what the reference's trainer builds by default,
-od_train.py:19, :101) against tests/obb_ref.py: head + rotated decode, ProbIoU, the rotated NMS rule, Detector.forward,
+od_train.py:19, :101) against oracle/detector_ref.py and oracle/obb_ref.py: head + rotated decode, ProbIoU, the rotated NMS rule, Detector.forward,
 the card-orientation kernel and Pipeline(quad_source="obb").  Parity unpinned upstream (ultralytics is absent): the
 restatement is the oracle."""
 import numpy as np
 import pytest
 import torch
 
-import obb_ref as R
+from oracle import detector_ref as D
+from oracle import obb_ref as R
 
 pytestmark = pytest.mark.gpu
 
@@ -32,7 +33,7 @@ def obb_det(request):
     sd = spec.random_detector_state(cfg, 3, cls_bias=-0.9)
     frames = np.random.default_rng(4).integers(0, 256, (3, 640, 640, 3), dtype=np.uint8)
     det = Detector(cfg, sd, max_batch=4)
-    return cfg, frames, det, R.forward(sd, cfg, frames).numpy()
+    return cfg, frames, det, D.forward(sd, cfg, frames).numpy()
 
 
 def _check_pred(pred, ref, nc, scale, tag):
@@ -80,7 +81,7 @@ def test_obb_forward_small_shapes(arch, mode):
     cfg = _cfg(arch, imgsz=64)
     sd = spec.random_detector_state(cfg, 3, cls_bias=-0.9)
     frames = np.random.default_rng(4).integers(0, 256, (2, 64, 64, 3), dtype=np.uint8)
-    ref = R.forward(sd, cfg, frames).numpy()
+    ref = D.forward(sd, cfg, frames).numpy()
     det = Detector(cfg, sd, max_batch=2)
     before = native.get_gemm_precision()
     native.set_gemm_precision(mode)

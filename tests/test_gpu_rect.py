@@ -1,5 +1,5 @@
 """Rectangular detector inputs on the GPU (`DetectorConfig(input_hw=...)`, mtgv_detector_cfg.in_h / in_w) against
-tests/rect_ref.py: forward, NMS, end to end, mask logits, the rectangular letterbox, and the callers (Detector.detect,
+oracle/detector_ref.py: forward, NMS, end to end, mask logits, the rectangular letterbox, and the callers (Detector.detect,
 JpegDecoder.decode_frames, CardSegmenter(rect=True), Pipeline).
 
 Square-assumption bugs are swaps of H and W, a grid width used as a height, and an image stride of S x S.  The small
@@ -13,14 +13,14 @@ import numpy as np
 import pytest
 import torch
 
-import obb_ref
-import rect_ref as R
+from oracle import detector_ref as D
+from oracle import obb_ref, resize_ref
 
 pytestmark = pytest.mark.gpu
 
 SMALL = [(96, 160), (160, 96)]
 FULL = [(480, 640), (640, 480)]
-# Full size: frame seeds and YOLO11's class bias were chosen on the CPU, out of seeds 1000 H + W + 0 .. 13: rect_ref in float32
+# Full size: frame seeds and YOLO11's class bias were chosen on the CPU, out of seeds 1000 H + W + 0 .. 13: the oracle in float32
 # and in float64 keep identical anchor sets, in the same order, on both frames of every case, the kept counts lie inside
 # (10, max_det), and of the candidates the seed with the class score nearest to the 0.25 threshold furthest away was taken.
 #   v8 (cls_bias default, -2.1)  480 x 640 seed 480649: kept 212, 149, nearest score 2.4e-5 away
@@ -57,8 +57,8 @@ def _case(arch, task, hw, n, bias, seed):
     sd = spec.random_detector_state(cfg, 3) if bias is None else spec.random_detector_state(cfg, 3, cls_bias=bias)
     frames = np.random.default_rng(seed).integers(0, 256, (n, hw[0], hw[1], 3), dtype=np.uint8)
     det = Detector(cfg, sd, max_batch=n + 1 if n == 3 else n)
-    dets64, pred64, protos64 = R.detect(sd, cfg, frames, dtype=torch.float64)
-    dets32, _, _ = R.detect(sd, cfg, frames)
+    dets64, pred64, protos64 = D.detect(sd, cfg, frames, dtype=torch.float64)
+    dets32, _, _ = D.detect(sd, cfg, frames)
     _DETS64[arch, task, hw, n] = dets64
     return cfg, frames, det, (pred64, protos64), dets32
 
@@ -237,7 +237,7 @@ def test_head_rows_on_a_rectangle(hw):
     n, nc, nm, na = 2, 3, 32, cfg.num_anchors
     rows = _synthetic_rows(cfg.grids, n, nc, nm, _seed(hw))
     pred, ref, got = _decode_and_nms_raw(rows, 640, hw[0], hw[1], n, nc, nm, na)
-    anchors, strides = R.make_anchors(cfg)
+    anchors, strides = D.make_anchors(cfg)
     centres = (anchors * strides).numpy()  # (2, na) pixels
     p = pred.cpu().numpy()
     assert np.isfinite(p).all()
@@ -279,7 +279,7 @@ def test_head_rows_zero_hw_is_the_square():
 # 4. mask logits
 # ---------------------------------------------------------------------------
 def _check_masks(case, mask_rows, tag):
-    """(k, in_h / 4, in_w / 4): within 1e-4 of the reference's, within 2e-5 of rect_ref.mask_logits on the GPU's own pred and
+    """(k, in_h / 4, in_w / 4): within 1e-4 of the reference's, within 2e-5 of the oracle's mask_logits on the GPU's own pred and
     protos, not all zero; rows beyond n_det are zeros"""
     from oracle import detector_ref as D
 
@@ -293,7 +293,7 @@ def _check_masks(case, mask_rows, tag):
         same_in = D.nms_single(pred[i], cfg.nc, cfg.conf, cfg.iou, cfg.max_det, cfg.max_wh)
         first = {key: v[:kk] for key, v in same_in.items()}
         ml = o["mask_logits"][i, :kk]
-        same = R.mask_logits(pred[i], protos[i], first, cfg.nc, cfg.in_h, cfg.in_w)
+        same = D.mask_logits(pred[i], protos[i], first, cfg.nc, (cfg.in_h, cfg.in_w))
         own_err = np.abs(ml - same).max()
         ref = ref_dets[i]
         ri = {a: j for j, a in enumerate(ref["keep_idx"])}
@@ -371,7 +371,7 @@ def test_square_handle_is_unchanged(arch, task, S):
 # ---------------------------------------------------------------------------
 @pytest.mark.parametrize("h,w", [(480, 640), (720, 1280), (1080, 810), (300, 200), (33, 1000), (640, 640)])
 def test_letterbox_rect_kernel_bit_exact(h, w):
-    """mtgv_letterbox_rect_u8 on a batch of 3 same-sized frames against rect_ref.letterbox, every byte"""
+    """mtgv_letterbox_rect_u8 on a batch of 3 same-sized frames against resize_ref.letterbox_rect, every byte"""
     from mtgv import native as nv
     from mtgv.detector import letterbox_device, rect_geometry
 
@@ -382,7 +382,7 @@ def test_letterbox_rect_kernel_bit_exact(h, w):
     nv.check(nv.lib().mtgv_letterbox_rect_u8(nv.ptr(src), 3, h, w, nv.ptr(dst), out_h, out_w, nh, nw, top, left, 114, nv.stream()))
     got = dst.cpu().numpy()
     for i in range(3):
-        ref, geo = R.letterbox(frames[i])
+        ref, geo = resize_ref.letterbox_rect(frames[i])
         np.testing.assert_array_equal(got[i], ref)
         if (nh, nw) == (h, w):
             np.testing.assert_array_equal(got[i, top : top + nh, left : left + nw], frames[i])
@@ -444,7 +444,7 @@ def _noise_720p(seed):
 
 def test_detect_equals_forward_on_a_fitting_frame():
     """Detector.detect on a 480 x 640 frame through a (480, 640) handle: the letterbox is the identity, so it equals forward
-    on the raw frame, bit for bit; a 720 x 1280 frame through a (384, 640) handle equals forward on rect_ref's letterbox"""
+    on the raw frame, bit for bit; a 720 x 1280 frame through a (384, 640) handle equals forward on resize_ref's letterbox_rect"""
     cfg, frames, det, _, _ = _full("v8", (480, 640))
     d = det.detect(frames[0])
     o = det.forward(torch.from_numpy(frames[:1]).cuda(), True, cfg.max_det)
@@ -459,7 +459,7 @@ def test_detect_equals_forward_on_a_fitting_frame():
     cfg2 = spec.DetectorConfig(input_hw=(384, 640))
     det2 = Detector(cfg2, spec.random_detector_state(cfg2, 3), max_batch=1)
     frame = _noise_720p(720 * 7 + 1280)
-    img, geo = R.letterbox(frame)
+    img, geo = resize_ref.letterbox_rect(frame)
     assert img.shape == (384, 640, 3) and np.array_equal(img[12:372], frame[::2, ::2]) and (img[:12] == 114).all()
     d2 = det2.detect(frame, masks=False)
     pred_detect, _ = det2.raw_outputs(1)

@@ -1,12 +1,12 @@
-"""CPU: the OBB family's key tables, the restatement the GPU tests compare against (tests/obb_ref.py: ProbIoU, the
+"""CPU: the OBB family's key tables, the restatement the GPU tests compare against (oracle/obb_ref.py: ProbIoU, the
 not-greedy rotated NMS rule, this project's card-orientation rule) and the export mirror of the OBB head.  The arithmetic
 is ultralytics 8.3.x's as recalled - unpinned."""
 import numpy as np
 import pytest
 import torch
 
-import obb_ref as R
 from mtgv import spec
+from oracle import obb_ref as R
 
 
 def _cfg(arch, **kw):
@@ -201,7 +201,7 @@ def test_obb_export_mirror(arch, tmp_path):
     assert have == [(k, tuple(s)) for k, s in want.items()]
     sd = spec.random_detector_state(cfg, 3)
     frames = np.random.default_rng(4).integers(0, 256, (2, 64, 64, 3), dtype=np.uint8)
-    ref = R.forward(sd, cfg, frames)
+    ref = D.forward(sd, cfg, frames)
     assert tuple(ref.shape) == (2, cfg.no, cfg.num_anchors)
     ang = ref[:, -1].numpy()
     assert (ang >= -np.pi / 4 - 1e-6).all() and (ang < 3 * np.pi / 4 + 1e-6).all() and ang.std() > 1e-3

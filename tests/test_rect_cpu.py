@@ -1,10 +1,11 @@
 """Rectangular detector inputs, the parts that need no GPU: LetterBox(auto=True) geometry, the config's grids and anchor
-count, the export mirror on a rectangle, and the restated reference (tests/rect_ref.py) pinned to the oracle on a square."""
+count, the export mirror on a rectangle, and the oracle (oracle/detector_ref.py) on a square and on a rectangle."""
 import numpy as np
 import pytest
 import torch
 
-import rect_ref as R
+from oracle import detector_ref as D
+from oracle import resize_ref
 
 # frame (h, w) -> r, (nh, nw), top, left, (out_h, out_w): hand-derived from the formula in rect_geometry's docstring
 GEOMETRY = [
@@ -61,16 +62,17 @@ def test_config_rectangle():
 @pytest.mark.parametrize("arch", ["v8", "11"])
 @pytest.mark.parametrize("task", ["seg", "obb"])
 def test_export_mirror_on_a_rectangle(arch, task):
-    """export_detector's module (anchors from cfg.grids) against rect_ref at 96 x 160, float32 both: the two run the same
+    """export_detector's module (anchors from cfg.grids) against the oracle at 96 x 160, float32 both: the two run the same
     torch ops on the same weights, so only the fusion order of a few sums can differ"""
     from mtgv import spec
-    from mtgv.export_detector import to_torch_module
+    from mtgv.export_detector import _make_anchors, to_torch_module
 
     kw = dict(task=task, input_hw=(96, 160))
     cfg = spec.yolo11_config(**kw) if arch == "11" else spec.DetectorConfig(**kw)
     sd = spec.random_detector_state(cfg, 3, cls_bias=-0.9)
     frames = np.random.default_rng(1000 * 96 + 160).integers(0, 256, (2, 96, 160, 3), dtype=np.uint8)
-    ref = R.forward(sd, cfg, frames, flip_rgb=False)
+    assert all(torch.equal(a, b) for a, b in zip(_make_anchors(cfg), D.make_anchors(cfg)))
+    ref = D.forward(sd, cfg, frames, flip_rgb=False)
     m = to_torch_module(cfg, sd)
     with torch.no_grad():
         got = m(torch.from_numpy(frames).permute(0, 3, 1, 2).float() / 255.0)
@@ -90,49 +92,40 @@ def test_export_mirror_on_a_rectangle(arch, task):
 
 
 @pytest.mark.parametrize("arch", ["v8", "11"])
-def test_rect_ref_equals_the_oracle_on_a_square(arch):
-    """the restatement with a square grid gives oracle.detector_ref's bits: head, mask_logits, and the OBB head"""
-    import obb_ref
+def test_oracle_on_a_square(arch):
+    """imgsz = 64: the segment oracle keeps detections with non-zero mask logits; the OBB oracle's forward gives one
+    (2, no, A) tensor in the dtype asked for"""
     from mtgv import spec
-    from oracle import detector_ref as D
 
     cfg = spec.yolo11_config(imgsz=64) if arch == "11" else spec.DetectorConfig(imgsz=64)
     sd = spec.random_detector_state(cfg, 3, cls_bias=-0.9)
     frames = np.random.default_rng(5).integers(0, 256, (2, 64, 64, 3), dtype=np.uint8)
-    for dtype in (torch.float32, torch.float64):
-        pred, protos = D.forward(sd, cfg, frames, dtype=dtype)
-        got_pred, got_protos = R.forward(sd, cfg, frames, dtype=dtype)
-        assert got_pred.dtype == dtype and torch.equal(got_pred, pred) and torch.equal(got_protos, protos)
-    a0, s0 = D.make_anchors(cfg)
-    a1, s1 = R.make_anchors(cfg)
-    assert torch.equal(a0, a1) and torch.equal(s0, s1)
     dets, pred, protos = D.detect(sd, cfg, frames)
-    rdets, rpred, rprotos = R.detect(sd, cfg, frames)
     assert sum(len(d["keep_idx"]) for d in dets) > 4
-    for d, r in zip(dets, rdets):
-        np.testing.assert_array_equal(d["keep_idx"], r["keep_idx"])
-        np.testing.assert_array_equal(d["mask_logits"], r["mask_logits"])
+    for d in dets:
         assert (d["mask_logits"] != 0).any()
     ocfg = spec.yolo11_config(imgsz=64, task="obb") if arch == "11" else spec.DetectorConfig(imgsz=64, task="obb")
     osd = spec.random_detector_state(ocfg, 3, cls_bias=-0.9)
-    assert torch.equal(R.forward(osd, ocfg, frames), obb_ref.forward(osd, ocfg, frames))
+    for dtype in (torch.float32, torch.float64):
+        opred = D.forward(osd, ocfg, frames, dtype=dtype)
+        assert isinstance(opred, torch.Tensor) and opred.dtype == dtype and tuple(opred.shape) == (2, ocfg.no, ocfg.num_anchors)
 
 
-def test_rect_ref_shapes_and_letterbox():
+def test_rect_shapes_and_letterbox():
     """96 x 160: 315 anchors, prototypes (n, 32, 24, 40); the expected rectangular letterbox of the geometry table's frames"""
     from mtgv import spec
 
     cfg = spec.DetectorConfig(input_hw=(96, 160))
     sd = spec.random_detector_state(cfg, 3, cls_bias=-0.9)
     frames = np.random.default_rng(1000 * 96 + 160).integers(0, 256, (3, 96, 160, 3), dtype=np.uint8)
-    pred, protos = R.forward(sd, cfg, frames)
+    pred, protos = D.forward(sd, cfg, frames)
     assert tuple(pred.shape) == (3, 39, 315) and tuple(protos.shape) == (3, 32, 24, 40)
     # anchors: x runs over the grid's width first; box centres stay near their anchors for this random head
-    a, s = R.make_anchors(cfg)
+    a, s = D.make_anchors(cfg)
     assert a[0, :20].tolist() == [i + 0.5 for i in range(20)] and a[1, 20] == 1.5 and s[0, 240] == 16 and s[0, 300] == 32
     for hw, r, nhw, top, left, out in GEOMETRY:
         frame = np.random.default_rng(hw[0] * 7 + hw[1]).integers(0, 256, (hw[0], hw[1], 3), dtype=np.uint8)
-        img, geo = R.letterbox(frame)
+        img, geo = resize_ref.letterbox_rect(frame)
         assert img.shape == (out[0], out[1], 3)
         inner = np.zeros(img.shape[:2], bool)
         inner[top : top + nhw[0], left : left + nhw[1]] = True
