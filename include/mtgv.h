@@ -174,8 +174,8 @@ MTGV_API int mtgv_topk_merge_gathered(const int64_t* gathered_dev, int32_t n_ran
                                       float score_threshold, int64_t* ids_dev, float* scores_dev, void* stream);
 
 /* ------------------------------------------------------------------------- */
-/* Detector: YOLOv8n / YOLO11n, -seg (forward + decode + NMS + mask logits)   */
-/* or -obb (forward + rotated decode + rotated NMS).                          */
+/* Detector: YOLOv8 / YOLO11 at scales n, s, m, -seg (forward + decode + NMS  */
+/* + mask logits) or -obb (forward + rotated decode + rotated NMS).           */
 /* Replaces CardSegmenter.__call__ -> ultralytics YOLO predict                */
 /* (mtgvision/od_export.py:141-160; model built in od_train.py:46-70).        */
 /* ------------------------------------------------------------------------- */
@@ -197,6 +197,16 @@ typedef struct {
                       * handle anchors keep their order (P3's pixels row-major, then P4's, then P5's) with
                       * na = sum over s = 8, 16, 32 of (in_h / s)(in_w / s); boxes and rboxes are pixels of the in_h x in_w frame;
                       * mask_logits is (n, mask_rows, in_h / 4, in_w / 4); mtgv_detector_raw and mtgv_detector_flops follow. */
+  int32_t scale;     /* the model size, od_train.py's --size (added in version 103: the struct grew by this field).  0: n (what a
+                      * zero-initialised caller gets), 1: s, 2: m run on the GPU.  3 (l) and 4 (x) return status 2 with a message
+                      * naming the scales that run: the library's 1e-4 contract cannot be tested at those widths yet.  Anything
+                      * else: status 1.  (depth, width, max channels), recalled from ultralytics 8.3.x and unpinned like the rest
+                      * of the detector: YOLOv8 n (.33, .25, 1024), s (.33, .50, 1024), m (.67, .75, 768); YOLO11 n (.50, .25,
+                      * 1024), s (.50, .50, 1024), m (.50, 1.0, 512) with c3k = True in every C3k2.  Only layer widths and
+                      * repeats change with the scale.  The anchors and what every anchor carries do not - 4 x 16 box bins, 32
+                      * mask coefficients or one angle, nc classes - so mtgv_detector_raw and the mask stage keep their shapes;
+                      * mtgv_detector_flops reports the scale's own count.  A state_dict of another scale fails in
+                      * mtgv_detector_set_param on the element count (status 1). */
 } mtgv_detector_cfg;
 #define MTGV_TASK_SEGMENT 0
 #define MTGV_TASK_OBB 1
@@ -485,6 +495,12 @@ typedef struct {
 /* path, unless NULL, receives {tile configuration, A mode, epilogue id, ring depth} of the launch that ran (the
  * values of gemm_sp_cfg.h); configuration -1 (the rest 0): the convert-on-load kernel. */
 MTGV_API int mtgv_op_conv2d_ex(const mtgv_conv_ex* d, int32_t* path, void* stream);
+/* The detector's stem alone (version 103): Conv(3 -> cout, k3, s2, p1) + SiLU straight from uint8 frames (n, h, w, 3), h even,
+ * w a multiple of 8, frames 8-byte and out 128-byte aligned; w_dev [cout][3][3][4] with BatchNorm folded and a zero 4th
+ * input channel, out (n, h / 2, w / 2, cout) in SP8 (out_sp8) or f32.  cout 16 runs scale n's kernel, 32 / 48 / 64 the wide
+ * one; `wide` != 0 runs the wide kernel at 16 channels too (it must give scale n's bits).  Other widths: status 1. */
+MTGV_API int mtgv_op_stem_u8(const uint8_t* frames_dev, const float* w_dev, const float* bias_dev, float* out_dev, int32_t n, int32_t h,
+                             int32_t w, int32_t cout, int32_t flip_rgb, int32_t out_sp8, int32_t wide, void* stream);
 /* The detector's prototype branch behind cv1 (Detector::proto runs the same function): ConvTranspose2d(k2, s2, bias) ->
  * cv2 (3x3, BN folded, SiLU) -> cv3 (1x1, BN folded, SiLU), c -> c -> c -> nm channels.  pr1 is an SP8 view of n images of
  * h x w pixels; protos an f32 view of (2 h, 2 w) pixels.  Weights are host pointers: wt (c, c, 2, 2) and bt (c) as

@@ -89,7 +89,9 @@ struct mtgv_bank {
 extern "C" {
 
 MTGV_API const char* mtgv_last_error(void) { return last_error_cstr(); }
-MTGV_API int mtgv_version(void) { return 102; }  // 101: mtgv_detector_cfg.task, the OBB calls; 102: in_h / in_w, mtgv_head_rows h / w, the rect letterbox calls
+// 101: mtgv_detector_cfg.task, the OBB calls; 102: in_h / in_w, mtgv_head_rows h / w, the rect letterbox calls;
+// 103: mtgv_detector_cfg.scale, mtgv_op_stem_u8
+MTGV_API int mtgv_version(void) { return 103; }
 MTGV_API int mtgv_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;

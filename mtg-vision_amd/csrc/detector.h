@@ -1,4 +1,4 @@
-// YOLOv8n / YOLO11n executor, -seg or -obb: conv stack on the implicit GEMM of gemm_launch (split-precision f16x3 or
+// YOLOv8 / YOLO11 executor at scales n, s and m, -seg or -obb: conv stack on the implicit GEMM of gemm_launch (split-precision f16x3 or
 // f32), decode, NMS, mask logits (segment) or rotated decode, rotated NMS (OBB).
 #pragma once
 #include "common.h"
@@ -14,14 +14,30 @@
 
 namespace mtgv {
 
-// ultralytics' width and depth scaling at scale "n": channels c * 0.25 rounded up to a multiple of 8, repeats n * 0.33
+// ultralytics' width and depth scaling: channels min(c, max_ch) * width rounded up to a multiple of 8, repeats n * depth.
+// The scales the executor runs (mtgv_detector_cfg.scale; recalled from ultralytics 8.3.x, unpinned - DESIGN.md section 3):
+//        v8 (depth, width, max_ch)   11 (depth, width, max_ch)
+//   n    0.33, 0.25, 1024            0.50, 0.25, 1024
+//   s    0.33, 0.50, 1024            0.50, 0.50, 1024
+//   m    0.67, 0.75,  768            0.50, 1.00,  512   (YOLO11 m: every C3k2 has c3k = True)
 static inline int make_div8(double v) { return (int)(ceil(v / 8.0) * 8.0); }
-static inline int chn(int c) { return make_div8(std::min(c, 1024) * 0.25); }
-static inline int rep(int n) { return n > 1 ? std::max((int)lround(n * 0.33), 1) : n; }
+struct DetScale {
+  double depth, width;
+  int max_ch;
+  int chn(int c) const { return make_div8(std::min(c, max_ch) * width); }
+  int rep(int n) const { return n > 1 ? std::max((int)lround(n * depth), 1) : n; }
+};
+static constexpr int kDetScales = 3;  // n, s, m
+static inline DetScale det_scale(int arch, int scale) {
+  static const DetScale v8[kDetScales] = {{0.33, 0.25, 1024}, {0.33, 0.50, 1024}, {0.67, 0.75, 768}};
+  static const DetScale v11[kDetScales] = {{0.50, 0.25, 1024}, {0.50, 0.50, 1024}, {0.50, 1.00, 512}};
+  return (arch == 11 ? v11 : v8)[scale];
+}
 
 // raw head rows per anchor, four whole 128-byte lines: [0,64) box logits (4 sides x 16 bins), [64,96) mask coefficients,
 // [96,96+nc) class logits; the rest of the 32 columns behind RAW_CLS is the zero padding of the chained class conv.
 // OBB: the angle logit at RAW_COEF, the other 31 coefficient columns are the zero outputs of its padded branch.
+// The rows do not change with the scale: 4 x 16 box bins, nm = 32 coefficients (or one angle) and nc classes at every width.
 static constexpr int RAW_CT = 128, RAW_COEF = 64, RAW_CLS = 96;
 
 struct ConvW {
@@ -51,6 +67,11 @@ GemmArgs conv_desc(const ConvW& w, const View& in, const View& out, int stride, 
 // xflops: what the launch profiler adds to the pair's 2 M N K (GemmArgs::xflops; negative for zero rows that pad w2).
 void conv_pair_launch(const ConvW& w1, const View& in, const View& mid, int stride, const ConvW& w2, const View& out2, int act2, int n,
                       hipStream_t s, double xflops = 0.0);
+
+// model.0 straight from uint8 frames (detector.hip; kernels in detector_kernel.h): cout 16 on conv0_u8_kernel, 32 / 48 / 64
+// on conv0_u8_wide_kernel (`wide`: that kernel at 16 channels too - test surface)
+void stem_u8_launch(const uint8_t* frames, const float* w, const float* bias, float* out, int n, int H, int W, int cout, int flip, bool sp8,
+                    bool wide, hipStream_t s);
 
 // ---- Proto behind cv1 (detector_proto.hip): ConvTranspose2d(k2, s2, bias) -> cv2 (3x3 + BN + SiLU) -> cv3 (1x1 + BN + SiLU) ----
 // There is no activation between the ConvTranspose and cv2, so the two are one linear map of the low-resolution map:
@@ -132,6 +153,8 @@ class Detector {
   void bottleneck(const std::string& prefix, const View& x, const View& tmp, const View& out, bool shortcut, int n, hipStream_t s);
   void c3k2(int idx, const View& in, const View& out, int n, hipStream_t s);
   void c2psa(int idx, const View& in, const View& out, int n, hipStream_t s);
+  int chn(int c) const { return sc_.chn(c); }
+  int rep(int n) const { return sc_.rep(n); }
   void build_v11();
   // activation arena: one entry per buffer of max_batch frames, carved in this order
   struct ArenaBuf { const char* name; int h, w, c; bool f32 = false; };  // f32: View::f32
@@ -167,7 +190,11 @@ class Detector {
   View view(const std::string& k) const;
 
   mtgv_detector_cfg cfg_;
+  DetScale sc_{0.33, 0.25, 1024};
   int nm_ = 32, npr_ = 64, reg_max_ = 16, na_ = 0;
+  // head widths on P3 features of ch0 channels (expect_head): box and class branches, the cv4 branch as the model has it
+  // (hc4_) and as it runs (hc4p_: an OBB angle branch narrower than nm_ is zero-padded to nm_), attention heads of C2PSA
+  int hc2_ = 64, hc3_ = 64, hc4_ = 32, hc4p_ = 32, psa_n_ = 1;
   std::map<std::string, Raw> raw_;
   bool finalized_ = false;
   std::vector<float*> dev_allocs_;

@@ -1,5 +1,5 @@
-// YOLOv8n-seg forward on the GPU, NHWC fp32.  Module graph: ultralytics yolov8-seg.yaml at
-// scale "n" (third-party to the reference; call site mtgvision/od_export.py:141-160, model
+// YOLOv8-seg / -obb forward on the GPU, NHWC fp32.  Module graph: ultralytics yolov8-seg.yaml at
+// scales n, s and m (detector.h: det_scale; third-party to the reference; call site mtgvision/od_export.py:141-160, model
 // family od_train.py:46-70).  BatchNorm (eps 1e-3) is folded into the conv weights at
 // finalize(); Concat is free (producers write channel slices of the consumer's buffer);
 // every Conv+SiLU is one launch of the implicit GEMM (gemm_launch, gemm_f32.hip).
@@ -38,6 +38,12 @@ Detector::Detector(const mtgv_detector_cfg& cfg) : cfg_(cfg) {
   MTGV_CHECK(cfg.max_det > 0 && cfg.max_det <= 1024, ERR_INVALID, "detector: max_det=%d", cfg.max_det);
   MTGV_CHECK(cfg.arch == 0 || cfg.arch == 8 || cfg.arch == 11, ERR_KEY, "detector: arch=%d (8: YOLOv8n-seg, 11: YOLO11n-seg)", cfg.arch);
   MTGV_CHECK(cfg.task == MTGV_TASK_SEGMENT || cfg.task == MTGV_TASK_OBB, ERR_KEY, "detector: task=%d (0: segment, 1: OBB)", cfg.task);
+  MTGV_CHECK(cfg.scale >= 0 && cfg.scale <= 4, ERR_INVALID, "detector: scale=%d (0: n, 1: s, 2: m)", cfg.scale);
+  // l and x: spec.py knows their keys and the oracle runs them, but the 1e-4 contract cannot be tested at those widths yet
+  MTGV_CHECK(cfg.scale < kDetScales, ERR_KEY, "detector: scale=%d (%s) is not supported: the scales that run are n, s, m (0, 1, 2)", cfg.scale,
+             cfg.scale == 3 ? "l" : "x");
+  sc_ = det_scale(cfg.arch, cfg.scale);
+  npr_ = make_div8(std::min(256, sc_.max_ch) * sc_.width);
   // the input rectangle: in_h = in_w = 0 is the square imgsz x imgsz
   if (cfg.in_h == 0 && cfg.in_w == 0) cfg_.in_h = cfg_.in_w = cfg.imgsz;
   MTGV_CHECK(cfg_.in_h >= 32 && cfg_.in_w >= 32 && cfg_.in_h % 32 == 0 && cfg_.in_w % 32 == 0 && cfg_.in_h <= cfg.imgsz && cfg_.in_w <= cfg.imgsz,
@@ -99,7 +105,10 @@ void Detector::expect_head(const int chs[3]) {
   const int c3 = std::max(chs[0], std::min(cfg_.nc, 100));
   const int n4 = obb() ? 1 : nm_;
   const int c4 = std::max(chs[0] / 4, n4);
-  MTGV_CHECK(c2 == 64 && c3 == 64 && c4 == (obb() ? 16 : 32), ERR_INVALID, "detector: unexpected head widths");
+  hc2_ = c2, hc3_ = c3, hc4_ = c4, hc4p_ = std::max(c4, nm_);
+  // (the box branch's final 1x1 fills the rows' 64 box columns, the class branch's chained form the 32 behind RAW_CLS)
+  MTGV_CHECK(c2 % 8 == 0 && c3 % 8 == 0 && c4 % 8 == 0 && 4 * reg_max_ == RAW_COEF && RAW_COEF + nm_ == RAW_CLS, ERR_INVALID,
+             "detector: unexpected head widths");
   const std::string H = head_;
   for (int l = 0; l < 3; ++l) {
     const std::string ls = std::to_string(l);
@@ -302,24 +311,26 @@ std::vector<Detector::ArenaBuf> Detector::arena_v8() const {
   const int h2 = IH / 2, h4 = IH / 4, h8 = IH / 8, h16 = IH / 16, h32 = IH / 32;
   const int w2 = IW / 2, w4 = IW / 4, w8 = IW / 8, w16 = IW / 16, w32 = IW / 32;
   const int c16 = chn(64), c32 = chn(128), c64 = chn(256), c128 = chn(512), c256 = chn(1024);
+  const int r3 = 2 + rep(3), r6 = 2 + rep(6);  // chunks of a C2f's concat: cv1's two and one per bottleneck
+  const int ht = hc2_ + hc3_ + hc4p_;          // the three head branches side by side (160 at scale n)
   return {
       {"l0", h2, w2, c16}, {"l1", h4, w4, c32},
-      {"cat2", h4, w4, 3 * c32 / 2}, {"tmp2", h4, w4, c32 / 2}, {"l2", h4, w4, c32},
-      {"l3", h8, w8, c64}, {"cat4", h8, w8, 4 * c64 / 2}, {"tmp4", h8, w8, c64 / 2},
+      {"cat2", h4, w4, r3 * c32 / 2}, {"tmp2", h4, w4, c32 / 2}, {"l2", h4, w4, c32},
+      {"l3", h8, w8, c64}, {"cat4", h8, w8, r6 * c64 / 2}, {"tmp4", h8, w8, c64 / 2},
       {"cat14", h8, w8, c128 + c64},                                      // concat 14 = [up(12), 4]
-      {"l5", h16, w16, c128}, {"cat6", h16, w16, 4 * c128 / 2}, {"tmp6", h16, w16, c128 / 2},
+      {"l5", h16, w16, c128}, {"cat6", h16, w16, r6 * c128 / 2}, {"tmp6", h16, w16, c128 / 2},
       {"cat11", h16, w16, c256 + c128},                                   // concat 11 = [up(9), 6]
-      {"l7", h32, w32, c256}, {"cat8", h32, w32, 3 * c256 / 2}, {"tmp8", h32, w32, c256 / 2}, {"l8", h32, w32, c256},
+      {"l7", h32, w32, c256}, {"cat8", h32, w32, r3 * c256 / 2}, {"tmp8", h32, w32, c256 / 2}, {"l8", h32, w32, c256},
       {"sppcat", h32, w32, 2 * c256},
       {"cat20", h32, w32, c128 + c256},                                   // concat 20 = [19, 9]
-      {"cat12", h16, w16, 3 * c128 / 2}, {"tmp12", h16, w16, c128 / 2},
+      {"cat12", h16, w16, r3 * c128 / 2}, {"tmp12", h16, w16, c128 / 2},
       {"cat17", h16, w16, c64 + c128},                                    // concat 17 = [16, 12]
-      {"cat15", h8, w8, 3 * c64 / 2}, {"tmp15", h8, w8, c64 / 2}, {"p3", h8, w8, c64},
-      {"cat18", h16, w16, 3 * c128 / 2}, {"tmp18", h16, w16, c128 / 2}, {"p4", h16, w16, c128},
-      {"cat21", h32, w32, 3 * c256 / 2}, {"tmp21", h32, w32, c256 / 2}, {"p5", h32, w32, c256},
+      {"cat15", h8, w8, r3 * c64 / 2}, {"tmp15", h8, w8, c64 / 2}, {"p3", h8, w8, c64},
+      {"cat18", h16, w16, r3 * c128 / 2}, {"tmp18", h16, w16, c128 / 2}, {"p4", h16, w16, c128},
+      {"cat21", h32, w32, r3 * c256 / 2}, {"tmp21", h32, w32, c256 / 2}, {"p5", h32, w32, c256},
       // head temporaries per level (the levels' branches run concurrently)
-      {"t1_0", h8, w8, 160}, {"t2_0", h8, w8, 160}, {"t1_1", h16, w16, 160}, {"t2_1", h16, w16, 160},
-      {"t1_2", h32, w32, 160}, {"t2_2", h32, w32, 160},
+      {"t1_0", h8, w8, ht}, {"t2_0", h8, w8, ht}, {"t1_1", h16, w16, ht}, {"t2_1", h16, w16, ht},
+      {"t1_2", h32, w32, ht}, {"t2_2", h32, w32, ht},
       {"rawhead0", h8, w8, RAW_CT, true}, {"rawhead1", h16, w16, RAW_CT, true}, {"rawhead2", h32, w32, RAW_CT, true},
       {"pr1", h8, w8, npr_}, {"pr2", h4, w4, npr_}, {"pr3", h4, w4, npr_}, {"protos", h4, w4, nm_, true},
       {"pred", 1, na_, no(), true}, {"coef", 1, cfg_.max_det, nm_, true},
@@ -357,27 +368,28 @@ void Detector::finalize() {
   for (int l = 0; l < 3; ++l) {
     const std::string ls = std::to_string(l);
     const std::string B = H + ".cv2." + ls, C = H + ".cv3." + ls, M = H + ".cv4." + ls;  // box, class, coefficient branches
-    // OBB: the angle branch (16 mid channels, 1 output) zero-padded to the coefficient branch's widths (32, 32), so the
-    // head runs on the segment head's launches and the angle logit lands in column RAW_COEF of the rows
-    if (obb()) cw_[M + ".0"] = zero_pad(cw_.at(M + ".0"), nm_, cw_.at(M + ".0").cin);
+    // OBB: the angle branch (max(ch0 / 4, 1) mid channels - 16 at scale n -, 1 output) zero-padded to the coefficient
+    // branch's widths (at least nm_ = 32 mid channels, 32 outputs), so the head runs on the segment head's launches and the
+    // angle logit lands in column RAW_COEF of the rows
+    if (obb()) cw_[M + ".0"] = zero_pad(cw_.at(M + ".0"), hc4p_, cw_.at(M + ".0").cin);
     if (v11()) {
       // box and coefficient branches start with a 3x3 conv on the same input: one conv with 64+32 outputs
       head_first_[l] = concat_out({cw_.at(B + ".0"), cw_.at(M + ".0")});
       cls_dw1_[l] = cw_.at(C + ".0.0"), cls_pw1_[l] = cw_.at(C + ".0.1");
       cls_dw2_[l] = cw_.at(C + ".1.0"), cls_pw2_[l] = cw_.at(C + ".1.1");
     } else {
-      // the three branches' first 3x3 convs read the same input: one conv with 64+64+32 outputs
+      // the three branches' first 3x3 convs read the same input: one conv with 64+64+32 outputs (scale n)
       head_first_[l] = concat_out({cw_.at(B + ".0"), cw_.at(C + ".0"), cw_.at(M + ".0")});
       head_cls2_[l] = cw_.at(C + ".1");
     }
     head_box2_[l] = cw_.at(B + ".1");
-    head_coef2_[l] = obb() ? zero_pad(cw_.at(M + ".1"), nm_, nm_) : cw_.at(M + ".1");
+    head_coef2_[l] = obb() ? zero_pad(cw_.at(M + ".1"), hc4p_, hc4p_) : cw_.at(M + ".1");
     head_box3_[l] = plain(B + ".2");
     head_cls3_[l] = plain(C + ".2");
     // v8: the class branch's final 1x1 padded to a 32-column block (zero weights and bias past the classes), which the 3x3
     // before it can chain (gemm_sp_chain_ok wants N2 % 32 == 0)
     if (!v11()) head_cls3_pad_[l] = plain(C + ".2", 32);
-    head_coef3_[l] = obb() ? zero_pad(plain(M + ".2"), nm_, nm_) : plain(M + ".2");
+    head_coef3_[l] = obb() ? zero_pad(plain(M + ".2"), nm_, hc4p_) : plain(M + ".2");
   }
   // DFL weights must be arange(16) (they are a fixed buffer upstream); the decode kernel hard-codes them
   {
@@ -488,23 +500,47 @@ void Detector::c2f(int idx, const View& in, const View& out, int n, hipStream_t 
   conv(cw_.at(P + ".cv2"), cat.slice(0, (2 + ci.n) * ch), out, 1, ACT_SILU, nullptr, n, s);
 }
 
-// model.0 (Conv 3 -> 16, k3 s2) on its own kernel straight from the uint8 frame
+// The stem kernels (detector_kernel.h) on n frames of H x W: cout = 16 (scale n) is conv0_u8_kernel, 32 / 48 / 64 (s,
+// YOLOv8 m, YOLO11 m) conv0_u8_wide_kernel; `wide` asks for the wide kernel at 16 channels too (test surface).
+// w [cout][3][3][4] BN-folded with a zero 4th input channel, out (n, H / 2, W / 2, cout) dense, SP8 or f32.
+void stem_u8_launch(const uint8_t* frames, const float* w, const float* bias, float* out, int n, int H, int W, int cout, int flip, bool sp8,
+                    bool wide, hipStream_t s) {
+  // (the kernels' whole-word loads and their two or four output columns per thread need W % 8 == 0)
+  MTGV_CHECK(n > 0 && H >= 2 && H % 2 == 0 && W >= 8 && W % 8 == 0, ERR_INVALID, "stem: n=%d frames of %d x %d (H even, W a multiple of 8)", n, H, W);
+  MTGV_CHECK(cout == 16 || cout == 32 || cout == 48 || cout == 64, ERR_INVALID, "stem: cout=%d (16, 32, 48, 64)", cout);
+  MTGV_CHECK(((uintptr_t)frames & 7) == 0, ERR_INVALID, "detector: the frame buffer must be 8-byte aligned");
+  MTGV_CHECK(((uintptr_t)out & 127) == 0, ERR_INVALID, "stem: the output must be 128-byte aligned");
+  if (cout == 16 && !wide) {
+    const long total = (long)n * (H / 2) * (W / 8);
+    const auto kern = sp8 ? conv0_u8_kernel<true> : conv0_u8_kernel<false>;
+    hipLaunchKernelGGL(kern, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, frames, w, bias, out, H, W, flip, total);
+  } else {
+    const long total = (long)n * (H / 2) * (W / 4);
+    const unsigned grid = (unsigned)((total + 255) / 256);
+#define STEM_GO(C_)                                                                                                            \
+  hipLaunchKernelGGL((sp8 ? conv0_u8_wide_kernel<true, C_> : conv0_u8_wide_kernel<false, C_>), dim3(grid), dim3(256), 0, s, frames, w, \
+                     bias, out, H, W, flip, total)
+    if (cout == 16) STEM_GO(16);
+    else if (cout == 32) STEM_GO(32);
+    else if (cout == 48) STEM_GO(48);
+    else STEM_GO(64);
+#undef STEM_GO
+  }
+  HIP_OK(hipGetLastError());
+}
+
+// model.0 (Conv 3 -> 16 / 32 / 48 / 64, k3 s2) on its own kernel straight from the uint8 frame
 void Detector::conv0(const uint8_t* frames, int n, int flip, hipStream_t s) {
   const int H = cfg_.in_h, W = cfg_.in_w;
   const ConvW& w0 = cw_.at("model.0");
   const View l0 = view("l0");
-  // (the kernel's whole-word loads and its four output columns per thread need W % 8 == 0)
-  MTGV_CHECK(H % 2 == 0 && W % 8 == 0 && l0.H == H / 2 && l0.W == W / 2 && w0.cout == 16 && w0.cin == 4 && w0.k == 3, ERR_RUNTIME,
+  MTGV_CHECK(l0.H == H / 2 && l0.W == W / 2 && l0.ct == w0.cout && l0.co == 0 && w0.cin == 4 && w0.k == 3, ERR_RUNTIME,
              "detector: unexpected model.0 geometry");
   if (count_flops_) {  // K = 27: the weights' zero 4th input channel is not counted
     flops_ += 2.0 * n * l0.H * l0.W * w0.cout * 27.0;
     return;
   }
-  MTGV_CHECK(((uintptr_t)frames & 7) == 0, ERR_INVALID, "detector: the frame buffer must be 8-byte aligned");
-  const long total = (long)n * (H / 2) * (W / 8);
-  const auto kern = fmt_ == 1 ? conv0_u8_kernel<true> : conv0_u8_kernel<false>;
-  hipLaunchKernelGGL(kern, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, frames, w0.w, w0.b, l0.p, H, W, flip, total);
-  HIP_OK(hipGetLastError());
+  stem_u8_launch(frames, w0.w, w0.b, l0.p, n, H, W, w0.cout, flip, fmt_ == 1, false, s);
 }
 
 
@@ -689,26 +725,27 @@ void Detector::head_level_v8(int l, int n, hipStream_t s) {
   conv(head_first_[l], f, t1, 1, ACT_SILU, nullptr, n, s);
   // every branch: the 3x3 and the final 1x1 as one launch (the class branch with its 1x1 padded to the 32 columns behind
   // RAW_CLS: its nc outputs alone are no column block of the chain)
-  conv_pair(head_box2_[l], t1.slice(0, 64), t2.slice(0, 64), 1, head_box3_[l], rh.slice(0, 64), ACT_NONE, n, s);
+  const int c2 = hc2_, c3 = hc3_, c4 = hc4p_;  // 64, 64, 32 at scale n
+  conv_pair(head_box2_[l], t1.slice(0, c2), t2.slice(0, c2), 1, head_box3_[l], rh.slice(0, 4 * reg_max_), ACT_NONE, n, s);
   if (head_direct_ && !count_flops_ && fmt_ == 1) {  // (f32 activations chain nothing: the 1x1 keeps its nc columns)
     // (the launch profiler keeps counting the nc real outputs of the 1x1)
     const double pad_flops = 2.0 * n * rh.H * rh.W * (double)(head_cls3_pad_[l].cout - cfg_.nc) * head_cls3_pad_[l].cin;
-    conv_pair(head_cls2_[l], t1.slice(64, 64), t2.slice(64, 64), 1, head_cls3_pad_[l], rh.slice(RAW_CLS, 32), ACT_NONE, n, s, -pad_flops);
+    conv_pair(head_cls2_[l], t1.slice(c2, c3), t2.slice(c2, c3), 1, head_cls3_pad_[l], rh.slice(RAW_CLS, 32), ACT_NONE, n, s, -pad_flops);
   } else {
-    conv(head_cls2_[l], t1.slice(64, 64), t2.slice(64, 64), 1, ACT_SILU, nullptr, n, s);
-    conv(head_cls3_[l], t2.slice(64, 64), rh.slice(RAW_CLS, cfg_.nc), 1, ACT_NONE, nullptr, n, s);
+    conv(head_cls2_[l], t1.slice(c2, c3), t2.slice(c2, c3), 1, ACT_SILU, nullptr, n, s);
+    conv(head_cls3_[l], t2.slice(c2, c3), rh.slice(RAW_CLS, cfg_.nc), 1, ACT_NONE, nullptr, n, s);
   }
-  conv_pair(head_coef2_[l], t1.slice(128, 32), t2.slice(128, 32), 1, head_coef3_[l], rh.slice(RAW_COEF, nm_), ACT_NONE, n, s);
+  conv_pair(head_coef2_[l], t1.slice(c2 + c3, c4), t2.slice(c2 + c3, c4), 1, head_coef3_[l], rh.slice(RAW_COEF, nm_), ACT_NONE, n, s);
   obb_flops_fix(f);
 }
 
-// the OBB angle branch runs zero-padded to the coefficient branch's widths; the algorithmic count is of the real
-// 16 -> 16 -> 1 branch
+// the OBB angle branch runs zero-padded to the coefficient branch's widths (hc4p_ mid channels, nm_ outputs); the
+// algorithmic count is of the real c4 -> c4 -> 1 branch (c4 = 16 at scale n)
 void Detector::obb_flops_fix(const View& f) {
   if (!count_flops_ || !obb()) return;
   const double px = (double)f.H * f.W;
-  const int c4 = 16, ne = 1;
-  flops_ -= 2.0 * px * (9.0 * f.C * (nm_ - c4) + 9.0 * (nm_ * nm_ - c4 * c4) + (nm_ * nm_ - c4 * ne));
+  const int c4 = hc4_, c4p = hc4p_, ne = 1;
+  flops_ -= 2.0 * px * (9.0 * f.C * (c4p - c4) + 9.0 * (c4p * c4p - c4 * c4) + (c4p * nm_ - c4 * ne));
 }
 
 void Detector::raw(int n, float* pred, float* protos, hipStream_t s) {
@@ -814,6 +851,13 @@ MTGV_API int mtgv_op_nms_raw(const mtgv_head_rows* rows, int32_t n, int32_t nc, 
     MTGV_CHECK(n_det_dev && boxes_dev && conf_dev && cls_dev && keep_idx_dev, ERR_INVALID, "null argument");
     nms_rows_launch(op_head_rows(rows), n, nc, nm, conf, iou, max_det, max_wh, n_det_dev, boxes_dev, conf_dev, cls_dev, keep_idx_dev, coef_dev,
                     workspace_dev, workspace_bytes, (hipStream_t)stream);
+  });
+}
+MTGV_API int mtgv_op_stem_u8(const uint8_t* frames_dev, const float* w_dev, const float* bias_dev, float* out_dev, int32_t n, int32_t h,
+                             int32_t w, int32_t cout, int32_t flip_rgb, int32_t out_sp8, int32_t wide, void* stream) {
+  return guarded([&] {
+    MTGV_CHECK(frames_dev && w_dev && bias_dev && out_dev, ERR_INVALID, "null argument");
+    stem_u8_launch(frames_dev, w_dev, bias_dev, out_dev, n, h, w, cout, flip_rgb, out_sp8 != 0, wide != 0, (hipStream_t)stream);
   });
 }
 MTGV_API int mtgv_detector_set_fork(mtgv_detector* h, int32_t mode) {

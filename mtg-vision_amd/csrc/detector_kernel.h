@@ -1,5 +1,5 @@
 // The detector's own device kernels (detector.hip launches them; the convolutions are gemm_launch's, gemm_f32.h):
-//   decode_kernel, decode_obb_kernel, nhwc_to_nchw_kernel, mask_binarize_kernel, conv0_u8_kernel, maxpool5_sp8_kernel,
+//   decode_kernel, decode_obb_kernel, nhwc_to_nchw_kernel, mask_binarize_kernel, conv0_u8_kernel, conv0_u8_wide_kernel, maxpool5_sp8_kernel,
 //   sppf_pools_sp8_kernel, mask_logits_kernel
 #pragma once
 #include "act.h"
@@ -214,6 +214,107 @@ __global__ __launch_bounds__(256) void conv0_u8_kernel(const uint8_t* __restrict
       const int T = i * 8 + (lane >> 3), k = lane & 7;
       const f32x4 piece = stage[wave][T][k];
       if (wave_idx0 + T < total) *reinterpret_cast<f32x4*>(out + (wave_idx0 + T) * 64 + half * 32 + k * 4) = piece;
+    }
+  }
+}
+
+// model.0 at the wider scales: Conv(3 -> COUT, k3, s2, p1) + folded BN + SiLU for COUT = 32 (s), 48 (YOLOv8 m), 64
+// (YOLO11 m); COUT = 16 exists for the test that compares this kernel with conv0_u8_kernel bit for bit.  The same
+// arithmetic per output - the exactly rounded u / 255, the flip swap, bias then FMAs in (kh, kw, c) order, SiLU - on TWO
+// neighbouring output pixels x COUT channels per thread: 2 COUT accumulators (4 x 16 = 64 in conv0_u8_kernel; 64 / 96 /
+// 128 here) stay in registers without scratch, and a thread's output is still one contiguous run of 2 COUT floats that
+// starts where its neighbour's ends.  The five input pixels are bytes 12 q - 3 .. 12 q + 11 of the row: four aligned dwords
+// (W % 8 == 0 keeps every row 8-byte aligned).  Stores go through the same per-wave LDS transpose in chunks of 128 bytes =
+// four 8-channel groups (SP8: hi and lo piece of each): eight lanes write one thread's chunk, a store instruction writes
+// eight whole lines.  With COUT = 48 a chunk straddles the two pixels; the groups are enumerated in memory order.
+template <bool SP8, int COUT>
+__global__ __launch_bounds__(256) void conv0_u8_wide_kernel(const uint8_t* __restrict__ frames, const float* __restrict__ w,
+                                                           const float* __restrict__ bias, float* __restrict__ out, int H, int W, int flip,
+                                                           long total) {
+  static_assert(COUT % 16 == 0 && COUT >= 16 && COUT <= 64, "whole 128-byte chunks per thread, accumulators in registers");
+  constexpr int NW = COUT * 9 * 4;
+  __shared__ __attribute__((aligned(16))) float ws[NW + COUT];  // [o][tap][4] (cin padded to 4) + bias
+  for (int i = threadIdx.x; i < NW; i += 256) ws[i] = w[i];
+  if (threadIdx.x < COUT) ws[NW + threadIdx.x] = bias[threadIdx.x];
+  __syncthreads();
+  const int OS = H >> 1, OQ = W >> 2;  // output rows, groups of 2 output columns per row
+  __shared__ __attribute__((aligned(16))) f32x4 stage[4][64][9];  // (rows padded to 144 B)
+  const long idx_raw = (long)blockIdx.x * 256 + threadIdx.x;  // over n * OS * OQ
+  const long idx = idx_raw < total ? idx_raw : total - 1;     // (threads past the end compute a duplicate and store nothing)
+  const int q = (int)(idx % OQ);
+  const long t = idx / OQ;
+  const int oh = (int)(t % OS);
+  const long n = t / OS;
+  float acc[2][COUT];
+#pragma unroll
+  for (int p = 0; p < 2; ++p)
+#pragma unroll
+    for (int o = 0; o < COUT; ++o) acc[p][o] = ws[NW + o];
+#pragma unroll
+  for (int kh = 0; kh < 3; ++kh) {
+    const int ih = 2 * oh - 1 + kh;
+    if (ih < 0 || ih >= H) continue;
+    const uint8_t* const rowp = frames + ((n * H + ih) * (long)W) * 3;
+    // input columns 4 q - 1 .. 4 q + 3: one dword for the pixel left of the pair (zero padding at q == 0 - the only column
+    // that can fall outside, W = 4 OQ) and three for the other four
+    uint32_t d[4];
+    d[0] = q > 0 ? *reinterpret_cast<const uint32_t*>(rowp + 12 * q - 4) : 0u;
+#pragma unroll
+    for (int k = 0; k < 3; ++k) d[1 + k] = *reinterpret_cast<const uint32_t*>(rowp + 12 * q + 4 * k);
+    float x[5][3];
+#pragma unroll
+    for (int j = 0; j < 5; ++j) {
+      float b[3];
+#pragma unroll
+      for (int ch = 0; ch < 3; ++ch) {
+        const int k = 1 + 3 * j + ch;  // byte index in d[]
+        const float u = (float)((d[k >> 2] >> (8 * (k & 3))) & 0xffu);
+        const float r255 = 1.0f / 255.0f;  // (conv0_u8_kernel: one Newton step gives the IEEE quotient u / 255)
+        const float q0 = u * r255;
+        b[ch] = __builtin_fmaf(__builtin_fmaf(-q0, 255.0f, u), r255, q0);
+      }
+      x[j][0] = flip ? b[2] : b[0], x[j][1] = b[1], x[j][2] = flip ? b[0] : b[2];
+    }
+#pragma unroll
+    for (int kw = 0; kw < 3; ++kw)
+#pragma unroll
+      for (int o = 0; o < COUT; ++o) {
+        const f32x4 wv = *reinterpret_cast<const f32x4*>(&ws[(o * 9 + kh * 3 + kw) * 4]);
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+          float a = acc[p][o];
+          a = __builtin_fmaf(x[2 * p + kw][0], wv[0], a);
+          a = __builtin_fmaf(x[2 * p + kw][1], wv[1], a);
+          a = __builtin_fmaf(x[2 * p + kw][2], wv[2], a);
+          acc[p][o] = a;
+        }
+      }
+  }
+  const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+  const long wave_idx0 = (long)blockIdx.x * 256 + wave * 64;  // output is contiguous in idx order: 2 COUT floats per thread
+  constexpr int G = COUT / 8;                                  // 8-channel groups per pixel
+#pragma unroll
+  for (int c = 0; c < COUT / 16; ++c) {  // 128-byte chunks of the thread's output
+#pragma unroll
+    for (int g4 = 0; g4 < 4; ++g4) {
+      const int gi = c * 4 + g4, p = gi / G, o0 = (gi % G) * 8;
+      f32x4 v0, v1;
+#pragma unroll
+      for (int e = 0; e < 4; ++e) v0[e] = act_silu(acc[p][o0 + e]), v1[e] = act_silu(acc[p][o0 + 4 + e]);
+      if (SP8) {
+        sp_h8 hi, lo;
+        sp8_split8(v0, v1, hi, lo);
+        stage[wave][lane][g4 * 2] = __builtin_bit_cast(f32x4, hi), stage[wave][lane][g4 * 2 + 1] = __builtin_bit_cast(f32x4, lo);
+      } else {
+        stage[wave][lane][g4 * 2] = v0, stage[wave][lane][g4 * 2 + 1] = v1;
+      }
+    }
+    // (one wave reads only what it wrote itself: LDS operations of a wave complete in order)
+#pragma unroll
+    for (int i = 0; i < 8; ++i) {
+      const int T = i * 8 + (lane >> 3), k = lane & 7;
+      const f32x4 piece = stage[wave][T][k];
+      if (wave_idx0 + T < total) *reinterpret_cast<f32x4*>(out + (wave_idx0 + T) * (2 * COUT) + c * 32 + k * 4) = piece;
     }
   }
 }

@@ -1,4 +1,4 @@
-// YOLO11n-seg on the GPU: the modules YOLOv8 does not have (ultralytics 8.3.x nn/modules: C3k2, C3k, C2PSA / PSABlock /
+// YOLO11-seg / -obb (scales n, s, m) on the GPU: the modules YOLOv8 does not have (ultralytics 8.3.x nn/modules: C3k2, C3k, C2PSA / PSABlock /
 // Attention, DWConv, Detect(legacy=False) class branch - third-party to the reference, which trains this family by
 // default: mtgvision/od_train.py:20, :55-56, :138-151).  Conv / C2f-skeleton / SPPF / Proto / decode / NMS / masks are
 // shared with detector.hip; every 1x1 and 3x3 convolution runs on the split-precision implicit GEMM.
@@ -189,7 +189,7 @@ void Detector::dwconv(const ConvW& w, const View& in, const View& out, int act, 
 }
 
 // ---------------------------------------------------------------------------
-// construction: expected ultralytics keys of yolo11n-seg
+// construction: expected ultralytics keys of yolo11{n,s,m}-seg / -obb
 // ---------------------------------------------------------------------------
 void Detector::build_v11() {
   auto P = [](int i) { return "model." + std::to_string(i); };
@@ -198,7 +198,11 @@ void Detector::build_v11() {
     expect_conv_bn(p + ".cv1", c_, c1, 3);
     expect_conv_bn(p + ".cv2", c2, c_, 3);
   };
+  const bool all_c3k = cfg_.scale >= 2;  // scales m, l, x: ultralytics sets c3k = True on every C3k2
+  const int nrep = rep(2);
+  MTGV_CHECK(nrep == 1, ERR_RUNTIME, "detector: C3k2 / C2PSA with %d inner modules", nrep);  // (l and x: 2)
   auto c3k2 = [&](int idx, int cin, int cout, bool c3k, double e) {
+    c3k = c3k || all_c3k;
     const int ch = (int)(cout * e);
     const std::string p = P(idx);
     expect_conv_bn(p + ".cv1", 2 * ch, cin, 1);
@@ -225,8 +229,9 @@ void Detector::build_v11() {
   c3k2(8, c256, c256, true, 0.5);
   expect_conv_bn(P(9) + ".cv1", c256 / 2, c256, 1);
   expect_conv_bn(P(9) + ".cv2", c256, c256 / 2 * 4, 1);
-  {  // C2PSA(c256, n = 1): c = 128, heads = c / 64, key_dim = head_dim / 2
+  {  // C2PSA(c256, n = 1): c = c256 / 2 (128 at scale n, 256 at s and m), heads = c / 64, key_dim = head_dim / 2
     const int c = c256 / 2, nh = std::max(c / 64, 1), kd = (c / nh) / 2;
+    psa_n_ = nh;
     const std::string p = P(10);
     expect_conv_bn(p + ".cv1", 2 * c, c256, 1);
     expect_conv_bn(p + ".cv2", c256, 2 * c, 1);
@@ -235,7 +240,8 @@ void Detector::build_v11() {
     expect_conv_bn(p + ".m.0.attn.pe", c, 1, 3);
     expect_conv_bn(p + ".m.0.ffn.0", 2 * c, c, 1);
     expect_conv_bn(p + ".m.0.ffn.1", c, 2 * c, 1);
-    MTGV_CHECK(nh == 2 && kd == 32 && c / nh == 64, ERR_INVALID, "detector: unexpected C2PSA geometry");
+    // (attn_kernel<32, 64> is the one instance: heads of 64 channels with 32-wide keys, any number of them)
+    MTGV_CHECK(nh >= 1 && kd == 32 && c == nh * 64, ERR_INVALID, "detector: unexpected C2PSA geometry");
   }
   c3k2(13, c256 + c128, c128, false, 0.5);
   c3k2(16, c128 + c128, c64, false, 0.5);
@@ -256,31 +262,55 @@ std::vector<Detector::ArenaBuf> Detector::arena_v11() const {
   const int h2 = IH / 2, h4 = IH / 4, h8 = IH / 8, h16 = IH / 16, h32 = IH / 32;
   const int w2 = IW / 2, w4 = IW / 4, w8 = IW / 8, w16 = IW / 16, w32 = IW / 32;
   const int c16 = chn(64), c32 = chn(128), c64 = chn(256), c128 = chn(512), c256 = chn(1024);
-  return {
-      {"l0", h2, w2, c16}, {"l1", h4, w4, c32},
-      {"cat2", h4, w4, 48}, {"tmp2", h4, w4, 8}, {"l2", h4, w4, c64},
-      {"l3", h8, w8, c64}, {"cat4", h8, w8, 96}, {"tmp4", h8, w8, 16},
-      {"cat15", h8, w8, c128 + c128},                                     // concat 15 = [up(13), 4]
-      {"l5", h16, w16, c128}, {"cat6", h16, w16, 192}, {"kcat6", h16, w16, 64}, {"tmp6", h16, w16, 32},
-      {"cat12", h16, w16, c256 + c128},                                   // concat 12 = [up(10), 6]
-      {"l7", h32, w32, c256}, {"cat8", h32, w32, 384}, {"kcat8", h32, w32, 128}, {"tmp8", h32, w32, 64}, {"l8", h32, w32, c256},
-      {"sppcat", h32, w32, 2 * c256}, {"l9", h32, w32, c256},
-      // (the attention core and the positional encoding read qkv and att in f32)
-      {"psacat", h32, w32, c256}, {"qkv", h32, w32, c256, true}, {"att", h32, w32, c128, true}, {"atty", h32, w32, c128}, {"ffn", h32, w32, c256},
-      {"cat21", h32, w32, c128 + c256},                                   // concat 21 = [20, 10]
-      {"cat13", h16, w16, 192}, {"tmp13", h16, w16, 32},
-      {"cat18", h16, w16, c64 + c128},                                    // concat 18 = [17, 13]
-      {"cat16", h8, w8, 96}, {"tmp16", h8, w8, 16}, {"p3", h8, w8, c64},
-      {"cat19", h16, w16, 192}, {"tmp19", h16, w16, 32}, {"p4", h16, w16, c128},
-      {"cat22", h32, w32, 384}, {"kcat22", h32, w32, 128}, {"tmp22", h32, w32, 64}, {"p5", h32, w32, c256},
-      // head temporaries per level (the levels' branches run concurrently): box + coefficient branches, class branch
-      {"t1_0", h8, w8, 96}, {"t2_0", h8, w8, 96}, {"dwa_0", h8, w8, c64}, {"dwb_0", h8, w8, 64}, {"dwc_0", h8, w8, 64}, {"dwd_0", h8, w8, 64},
-      {"t1_1", h16, w16, 96}, {"t2_1", h16, w16, 96}, {"dwa_1", h16, w16, c128}, {"dwb_1", h16, w16, 64}, {"dwc_1", h16, w16, 64}, {"dwd_1", h16, w16, 64},
-      {"t1_2", h32, w32, 96}, {"t2_2", h32, w32, 96}, {"dwa_2", h32, w32, c256}, {"dwb_2", h32, w32, 64}, {"dwc_2", h32, w32, 64}, {"dwd_2", h32, w32, 64},
-      {"pr1", h8, w8, npr_}, {"pr2", h4, w4, npr_}, {"pr3", h4, w4, npr_}, {"protos", h4, w4, nm_, true},
-      {"rawhead0", h8, w8, RAW_CT, true}, {"rawhead1", h16, w16, RAW_CT, true}, {"rawhead2", h32, w32, RAW_CT, true},
-      {"pred", 1, na_, no(), true}, {"coef", 1, cfg_.max_det, nm_, true},
+  const int pc = c256 / 2;  // C2PSA's hidden width: qkv is pc + 2 heads x 32 keys = 2 pc wide
+  const int ht = hc2_ + hc4p_, c3 = hc3_;  // box + coefficient branches side by side (96 at scale n); class branch (64)
+  std::vector<ArenaBuf> a;
+  // C3k2 `idx` on an h x w map: the concat of cv1's two chunks and the inner module's output, C3k's own concat where the
+  // inner module is one, and the bottlenecks' temporary (half the chunk width in both forms)
+  auto c3k2 = [&](int idx, int h, int w) {
+    static const char* const names[][3] = {{"cat2", "kcat2", "tmp2"},    {"cat4", "kcat4", "tmp4"},    {"cat6", "kcat6", "tmp6"},
+                                           {"cat8", "kcat8", "tmp8"},    {"cat13", "kcat13", "tmp13"}, {"cat16", "kcat16", "tmp16"},
+                                           {"cat19", "kcat19", "tmp19"}, {"cat22", "kcat22", "tmp22"}};
+    static const int ids[] = {2, 4, 6, 8, 13, 16, 19, 22};
+    const C3k2Info& ci = c3k2_.at(idx);
+    for (size_t i = 0; i < sizeof(ids) / sizeof(ids[0]); ++i)
+      if (ids[i] == idx) {
+        a.push_back({names[i][0], h, w, 3 * ci.ch});
+        if (ci.c3k) a.push_back({names[i][1], h, w, ci.ch});
+        a.push_back({names[i][2], h, w, ci.ch / 2});
+      }
   };
+  auto add = [&](std::initializer_list<ArenaBuf> l) { a.insert(a.end(), l); };
+  add({{"l0", h2, w2, c16}, {"l1", h4, w4, c32}});
+  c3k2(2, h4, w4);
+  add({{"l2", h4, w4, c64}, {"l3", h8, w8, c64}});
+  c3k2(4, h8, w8);
+  add({{"cat15", h8, w8, c128 + c128},  // concat 15 = [up(13), 4]
+       {"l5", h16, w16, c128}});
+  c3k2(6, h16, w16);
+  add({{"cat12", h16, w16, c256 + c128},  // concat 12 = [up(10), 6]
+       {"l7", h32, w32, c256}});
+  c3k2(8, h32, w32);
+  add({{"l8", h32, w32, c256}, {"sppcat", h32, w32, 2 * c256}, {"l9", h32, w32, c256},
+       // (the attention core and the positional encoding read qkv and att in f32)
+       {"psacat", h32, w32, 2 * pc}, {"qkv", h32, w32, 2 * pc, true}, {"att", h32, w32, pc, true}, {"atty", h32, w32, pc}, {"ffn", h32, w32, 2 * pc},
+       {"cat21", h32, w32, c128 + c256}});  // concat 21 = [20, 10]
+  c3k2(13, h16, w16);
+  add({{"cat18", h16, w16, c64 + c128}});  // concat 18 = [17, 13]
+  c3k2(16, h8, w8);
+  add({{"p3", h8, w8, c64}});
+  c3k2(19, h16, w16);
+  add({{"p4", h16, w16, c128}});
+  c3k2(22, h32, w32);
+  add({{"p5", h32, w32, c256},
+       // head temporaries per level (the levels' branches run concurrently): box + coefficient branches, class branch
+       {"t1_0", h8, w8, ht}, {"t2_0", h8, w8, ht}, {"dwa_0", h8, w8, c64}, {"dwb_0", h8, w8, c3}, {"dwc_0", h8, w8, c3}, {"dwd_0", h8, w8, c3},
+       {"t1_1", h16, w16, ht}, {"t2_1", h16, w16, ht}, {"dwa_1", h16, w16, c128}, {"dwb_1", h16, w16, c3}, {"dwc_1", h16, w16, c3}, {"dwd_1", h16, w16, c3},
+       {"t1_2", h32, w32, ht}, {"t2_2", h32, w32, ht}, {"dwa_2", h32, w32, c256}, {"dwb_2", h32, w32, c3}, {"dwc_2", h32, w32, c3}, {"dwd_2", h32, w32, c3},
+       {"pr1", h8, w8, npr_}, {"pr2", h4, w4, npr_}, {"pr3", h4, w4, npr_}, {"protos", h4, w4, nm_, true},
+       {"rawhead0", h8, w8, RAW_CT, true}, {"rawhead1", h16, w16, RAW_CT, true}, {"rawhead2", h32, w32, RAW_CT, true},
+       {"pred", 1, na_, no(), true}, {"coef", 1, cfg_.max_det, nm_, true}});
+  return a;
 }
 
 // ---------------------------------------------------------------------------
@@ -323,7 +353,8 @@ void Detector::c2psa(int idx, const View& in, const View& out, int n, hipStream_
   const std::string P = "model." + std::to_string(idx);
   const View cat = view("psacat");
   const int c = cat.ct / 2;
-  constexpr int NH = 2, KD = 32, HD = 64;
+  constexpr int KD = 32, HD = 64;
+  const int NH = psa_n_;  // c / 64 heads: 2 at scale n, 4 at s and m
   conv(cw_.at(P + ".cv1"), in, cat, 1, ACT_SILU, nullptr, n, s);
   const View b = cat.slice(c, c);
   const std::string A = P + ".m.0.attn";
@@ -391,8 +422,9 @@ void Detector::head_level_v11(int l, int n, hipStream_t s) {
   const View f = view(feats[l]), t1 = view("t1_" + ls), t2 = view("t2_" + ls);
   const View rh = view("rawhead" + ls);
   conv(head_first_[l], f, t1, 1, ACT_SILU, nullptr, n, s);
-  conv_pair(head_box2_[l], t1.slice(0, 64), t2.slice(0, 64), 1, head_box3_[l], rh.slice(0, 64), ACT_NONE, n, s);
-  conv_pair(head_coef2_[l], t1.slice(64, 32), t2.slice(64, 32), 1, head_coef3_[l], rh.slice(RAW_COEF, nm_), ACT_NONE, n, s);
+  const int c2 = hc2_, c4 = hc4p_;  // 64, 32 at scale n
+  conv_pair(head_box2_[l], t1.slice(0, c2), t2.slice(0, c2), 1, head_box3_[l], rh.slice(0, 4 * reg_max_), ACT_NONE, n, s);
+  conv_pair(head_coef2_[l], t1.slice(c2, c4), t2.slice(c2, c4), 1, head_coef3_[l], rh.slice(RAW_COEF, nm_), ACT_NONE, n, s);
   // class branch: (depthwise 3x3, 1x1) twice, then the plain 1x1
   const View da = view("dwa_" + ls), db = view("dwb_" + ls), dc = view("dwc_" + ls), dd = view("dwd_" + ls);
   dwconv(cls_dw1_[l], f, da, ACT_SILU, nullptr, 0, 0, n, s);

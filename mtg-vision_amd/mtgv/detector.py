@@ -1,4 +1,4 @@
-"""Host side of the detect stage: YOLOv8n / YOLO11n forward + decode + NMS on the GPU - the segment family with mask
+"""Host side of the detect stage: YOLOv8 / YOLO11 (scales n, s, m: `spec.detector_scale_config`) forward + decode + NMS on the GPU - the segment family with mask
 logits, the OBB family (`DetectorConfig(task="obb")`) with rotated boxes and rotated NMS.
 
 `Detector.detect(frame)` is the north-star name; the reference's boundary is
@@ -124,7 +124,8 @@ class Detector:
         device=None,
     ):
         native.require_gpu()
-        self.cfg = cfg or spec.DetectorConfig()
+        # (no cfg: the family and scale of the state dict, spec.detector_config_for_state; neither: yolov8n-seg)
+        self.cfg = cfg or (spec.DetectorConfig() if state_dict is None else spec.detector_config_for_state(state_dict))
         self.max_batch = int(max_batch)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         if self.device.index is None:
@@ -134,6 +135,7 @@ class Detector:
         c.conf, c.iou, c.max_det = self.cfg.conf, self.cfg.iou, self.cfg.max_det
         c.arch = 11 if self.cfg.arch == "11" else 8
         c.task = 1 if self.cfg.task == "obb" else 0
+        c.scale = spec.SCALE_NAMES.index(self.cfg.scale)  # (l and x: the library refuses them, status 2)
         if self.cfg.input_hw is not None:  # (0, 0: the square imgsz x imgsz)
             c.in_h, c.in_w = self.cfg.in_h, self.cfg.in_w
         self._h = native.c_vp(0)

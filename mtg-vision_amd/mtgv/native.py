@@ -47,6 +47,7 @@ class DetectorCfg(C.Structure):
         ("task", c_i32),  # 0 segment, 1 OBB (mtgv_version >= 101)
         ("in_h", c_i32),  # the input rectangle, both 0: imgsz x imgsz (mtgv_version >= 102)
         ("in_w", c_i32),
+        ("scale", c_i32),  # 0 n, 1 s, 2 m; 3 l and 4 x are refused (mtgv_version >= 103)
     ]
 
 
@@ -169,6 +170,7 @@ SIGNATURES = {
     "mtgv_op_linear_ex": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mtgv_op_conv2d": (C.c_int, [c_vp, c_vp, c_vp, c_vp] + [c_i32] * 10 + [c_vp]),
     "mtgv_op_conv2d_ex": (C.c_int, [C.POINTER(ConvEx), C.POINTER(c_i32), c_vp]),
+    "mtgv_op_stem_u8": (C.c_int, [c_vp, c_vp, c_vp, c_vp] + [c_i32] * 7 + [c_vp]),
     "mtgv_op_proto_tail": (C.c_int, [C.POINTER(ProtoTail), C.POINTER(c_i32), c_vp]),
     "mtgv_op_proto_fold_compose": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mtgv_op_layernorm": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_f32, c_vp]),

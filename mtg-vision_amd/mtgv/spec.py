@@ -259,6 +259,17 @@ def strip_checkpoint_prefix(state_dict, prefix: str = "model.encoder."):
 # sites mtgvision/od_export.py:141-160, od_train.py:46-70).
 # ----------------------------------------------------------------------------
 
+# (depth, width, max_channels) of ultralytics' model scales - od_train.py's --size (:17, :55, :86-91 builds
+# yolo{arch}{size}-{kind}).  [external - recalled from ultralytics 8.3.x cfg/models/v8/yolov8-seg.yaml and
+# cfg/models/11/yolo11-seg.yaml, unpinned like the rest of the detector]  YOLO11 m, l and x also set c3k = True on every
+# C3k2 (yolo11_seg_graph).  The GPU executor runs n, s and m (GPU_SCALES); l and x are here for keys, shapes and the oracle.
+DETECTOR_SCALES = {
+    "v8": {"n": (0.33, 0.25, 1024), "s": (0.33, 0.50, 1024), "m": (0.67, 0.75, 768), "l": (1.00, 1.00, 512), "x": (1.00, 1.25, 512)},
+    "11": {"n": (0.50, 0.25, 1024), "s": (0.50, 0.50, 1024), "m": (0.50, 1.00, 512), "l": (1.00, 1.00, 512), "x": (1.00, 1.50, 512)},
+}
+SCALE_NAMES = "nsmlx"  # index: mtgv_detector_cfg.scale
+GPU_SCALES = "nsm"
+
 
 @dataclass(frozen=True)
 class DetectorConfig:
@@ -285,8 +296,12 @@ class DetectorConfig:
     # (in_h, in_w) of a rectangular handle - what ultralytics' LetterBox(auto=True) feeds a .pt checkpoint, e.g. (480, 640)
     # for a webcam frame (mtgv.detector.rect_geometry); each a multiple of 32 in [32, imgsz].  None: imgsz x imgsz.
     input_hw: Optional[Tuple[int, int]] = None
+    # the model size the width / depth / max_ch / npr above belong to (detector_scale_config fills all five together)
+    scale: str = "n"
 
     def __post_init__(self):
+        if self.scale not in SCALE_NAMES or len(self.scale) != 1:
+            raise KeyError(f"scale={self.scale} not recognized")
         if self.task not in ("seg", "obb"):
             raise KeyError(f"task={self.task} not recognized")
         if self.input_hw is not None:
@@ -365,25 +380,50 @@ def yolo11_config(**kw) -> DetectorConfig:
     return DetectorConfig(arch="11", depth=0.50, **kw)
 
 
+def detector_scale_config(arch: str, scale: str, **kw) -> DetectorConfig:
+    """yolov8{scale} / yolo11{scale}: DETECTOR_SCALES' depth, width and max_channels, and the prototype width
+    npr = make_divisible(min(256, max_ch) * width, 8) (64 at n, 128 at s, 192 at YOLOv8 m, 256 at YOLO11 m)"""
+    arch = "11" if str(arch) in ("11", "v11") else "v8"
+    depth, width, max_ch = DETECTOR_SCALES[arch][scale]
+    npr = int(-(-(min(256, max_ch) * width) // 8) * 8)
+    return DetectorConfig(arch=arch, scale=scale, depth=depth, width=width, max_ch=max_ch, npr=npr, **kw)
+
+
+# width of model.0 (make_divisible(64 * width, 8)) -> scale
+_STEM_SCALE = {"v8": {16: "n", 32: "s", 48: "m", 64: "l", 80: "x"}, "11": {16: "n", 32: "s", 64: "ml", 96: "x"}}
+
+
 def detector_config_for_state(state_dict, **kw) -> DetectorConfig:
-    """The scale-"n" family a ultralytics `state_dict` belongs to, from its key set: YOLO11 has its head at index 23
+    """The family and scale a ultralytics `state_dict` belongs to, from its key set: YOLO11 has its head at index 23
     (`model.23.*`; C2PSA at 10), YOLOv8 at 22; a head without `.proto.` keys is an OBB head.  `nc` is read from the class
-    branch's last conv."""
+    branch's last conv, the scale from the stem's width (`model.0.conv.weight`; KeyError for a width no scale has) -
+    YOLO11 m and l share theirs and differ in depth: l has a second inner module `model.2.m.1.*`."""
     keys = list(state_dict.keys())
     head = 23 if any(k.startswith("model.23.") for k in keys) else 22
+    arch = "11" if head == 23 else "v8"
     if not any(".proto." in k for k in keys):
         kw.setdefault("task", "obb")
     w = state_dict.get(f"model.{head}.cv3.0.2.weight")
     if w is not None:
         kw.setdefault("nc", int(w.shape[0]))
-    return yolo11_config(**kw) if head == 23 else DetectorConfig(**kw)
+    w0 = state_dict.get("model.0.conv.weight")
+    scale = "n"
+    if w0 is not None:
+        c0 = int(w0.shape[0])
+        if c0 not in _STEM_SCALE[arch]:
+            raise KeyError(f"model.0.conv.weight has {c0} output channels: no {arch} scale has that stem ({sorted(_STEM_SCALE[arch])})")
+        scale = _STEM_SCALE[arch][c0]
+        if scale == "ml":
+            scale = "l" if any(k.startswith("model.2.m.1.") for k in keys) else "m"
+    return detector_scale_config(arch, scale, **kw)
 
 
 # ---- YOLO11n-seg graph (ultralytics cfg/models/11/yolo11-seg.yaml, scale "n") ----------
 # C3k2(cout, n, c3k, e) | C2PSA(cout, n); the rest as above.  [external - recalled from ultralytics 8.3.x]
 def yolo11_seg_graph(cfg: DetectorConfig):
     c, r = cfg.ch, cfg.rep
-    return [
+    k = cfg.scale in "mlx"  # ultralytics' parse_model: `if scale in "mlx": args[3] = True` - every C3k2 gets C3k modules
+    g = [
         (0, "Conv", (c(64), 3, 2)),
         (1, "Conv", (c(128), 3, 2)),
         (2, "C3k2", (c(256), r(2), False, 0.25)),
@@ -408,6 +448,7 @@ def yolo11_seg_graph(cfg: DetectorConfig):
         (21, "Concat", (20, 10)),
         (22, "C3k2", (c(1024), r(2), True, 0.5)),
     ]
+    return [(i, kind, (a[0], a[1], a[2] or k, a[3]) if kind == "C3k2" else a) for i, kind, a in g]
 
 
 def detector_graph(cfg: DetectorConfig):
@@ -443,7 +484,7 @@ def _c3k_keys(prefix: str, c1: int, c2: int, n: int = 2):
 
 
 def detector_param_shapes(cfg: DetectorConfig) -> "OrderedDict[str, tuple]":
-    """ultralytics state_dict keys of YOLOv8n / YOLO11n, -seg or -obb (``num_batches_tracked`` buffers omitted).
+    """ultralytics state_dict keys of YOLOv8 / YOLO11 at cfg's scale, -seg or -obb (``num_batches_tracked`` buffers omitted).
 
     Third-party layout, recalled from ultralytics 8.3.x (pyproject.toml:32 pins ~=8.3.80); it
     cannot be checked against the package in this environment.

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Detector b=32 under the schedule switches (MTGV_DET_FORK, MTGV_PROTO_UP1), in one process: ms per forward.
-    python tools/det_probe.py [yolov8n-seg|yolo11n-seg|yolov8n-obb|yolo11n-obb] [--default-only]
-An -obb model also times the batch-1 forward and the OBB stages alone: rotated NMS at a few hundred and at 8400 candidates,
+    python tools/det_probe.py [yolov8n-seg|yolo11n-seg|yolov8n-obb|yolo11n-obb] [--default-only] [--scale n|s|m]
+--scale (or the size letter in the model name: yolov8s-seg, yolo11m-obb) picks the model scale; the default-only line then also
+gives mtgv_detector_flops and the algorithmic TFLOP/s.  An -obb model also times the batch-1 forward and the OBB stages alone: rotated NMS at a few hundred and at 8400 candidates,
 mtgv_obb_cards for 32 x 8 slots.  --default-only: the default switches only (one line per model)."""
 import os, sys
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -10,10 +11,20 @@ import torch
 from mtgv import spec
 from mtgv.detector import Detector
 
-args = [a for a in sys.argv[1:] if not a.startswith("--")]
+argv = sys.argv[1:]
+opt_scale = None
+if "--scale" in argv:
+    i = argv.index("--scale")
+    opt_scale = argv[i + 1]
+    del argv[i : i + 2]
+args = [a for a in argv if not a.startswith("--")]
 arch = args[0] if args else "yolov8n-seg"
 task = "obb" if arch.endswith("-obb") else "seg"
-cfg = spec.DetectorConfig(task=task) if arch.startswith("yolov8n") else spec.yolo11_config(task=task)
+family = "v8" if arch.startswith("yolov8") else "11"
+stem = "yolov8" if family == "v8" else "yolo11"
+scale = opt_scale or arch[len(stem)]
+arch = f"{stem}{scale}-{task}"
+cfg = spec.detector_scale_config(family, scale, task=task)
 det = Detector(cfg, spec.random_detector_state(cfg, 3), max_batch=32)
 fr = torch.randint(0, 256, (32, 640, 640, 3), device="cuda", dtype=torch.uint8)
 
@@ -29,7 +40,8 @@ def timeit(fn, warm=5, it=30):
 if "--default-only" in sys.argv or task == "obb":
     for rep in range(2):
         ms = timeit(lambda: det.forward(fr, True, 8))
-        print(f"{arch} b=32 defaults: {ms:.3f} ms  {32 / ms * 1e3:.0f} frames/s", flush=True)
+        gf = det.flops_per_frame() / 1e9
+        print(f"{arch} b=32 defaults: {ms:.3f} ms  {32 / ms * 1e3:.0f} frames/s  {gf:.2f} GFLOP/frame  {32 * gf / ms:.1f} TFLOP/s", flush=True)
     ms1 = timeit(lambda: det.forward(fr[:1], True, 8))
     print(f"{arch} b=1 defaults: {ms1:.3f} ms", flush=True)
 if task == "obb":
