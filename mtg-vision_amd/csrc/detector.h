@@ -1,5 +1,8 @@
 // YOLOv8 / YOLO11 executor at scales n, s and m, -seg or -obb: conv stack on the implicit GEMM of gemm_launch (split-precision f16x3 or
 // f32), decode, NMS, mask logits (segment) or rotated decode, rotated NMS (OBB).
+// The two architectures differ in their backbones only (backbone_v8 in detector.hip, backbone_v11 in detector_v11.hip): the
+// CSP block, the neck from the first upsample on, the head levels, the key expectations behind the backbone and the
+// arena table are written once (detector.hip), the neck's node numbers shifted by one for YOLO11 (its node 10 is C2PSA).
 #pragma once
 #include "common.h"
 #include "gemm_f32.h"
@@ -132,6 +135,16 @@ class Detector {
   };
   void expect(const std::string& key, std::vector<int> shape);
   void expect_conv_bn(const std::string& prefix, int cout, int cin, int k);
+  // CSP block (C2f / C3k2) of node idx: cv1 -> two chunks of ch = cout * e channels, n inner modules each appended to the
+  // concat, cv2 over the concat.  The inner module: C2f's Bottleneck(ch -> ch -> ch), C3k2's Bottleneck(ch -> ch / 2 -> ch)
+  // or C3k(ch, ch, 2).
+  enum class Csp { C2f, Half, C3k };
+  struct CspInfo { int cout, n, ch; bool shortcut; Csp kind; };
+  void expect_csp(int idx, int cin, int cout, int n, bool shortcut, Csp kind, double e = 0.5);
+  void expect_sppf(const std::string& prefix, int c);
+  // nodes 10 + k .. 22 + k (k = 1 for YOLO11): the neck's four CSP blocks (`kind`, the P5 one `kind_p5`) and two stride-2
+  // convs, then the head
+  void expect_neck(int n, bool shortcut, Csp kind, Csp kind_p5);
   void expect_head(const int chs[3]);                               // head + Proto keys on features of chs channels
   std::pair<double, double> bn_affine(const std::string& prefix, int o) const;  // BatchNorm of channel o: (scale, bias)
   void free_weights();                                              // unregister and free every uploaded weight
@@ -145,24 +158,29 @@ class Detector {
   // where w1's output would go in two launches (used when the pair cannot be chained: f32 mode, flop counting, shapes)
   void conv_pair(const ConvW& w1, const View& in, const View& mid, int stride, const ConvW& w2, const View& out2, int act2, int n,
                  hipStream_t s, double xflops = 0.0);
-  void c2f(int idx, const View& in, const View& out, int n, hipStream_t s, const ConvW* pre = nullptr, const View* pre_in = nullptr);
+  void bottleneck(const std::string& prefix, const View& x, const View& tmp, const View& out, bool shortcut, int n, hipStream_t s);
+  // pre: the stride-2 Conv in front of the block (input pre_in) where cv1 is its only consumer: `in` is then that conv's output
+  void csp_block(int idx, const View& in, const View& out, int n, hipStream_t s, const ConvW* pre = nullptr, const View* pre_in = nullptr);
   // YOLO11 modules
   ConvW fold_dw(const std::string& prefix);                         // depthwise 3x3 Conv+BN -> weight [9][c], bias [c]
   void dwconv(const ConvW& w, const View& in, const View& out, int act, const float* add, int g_size, int g_stride, int n,
               hipStream_t s);
-  void bottleneck(const std::string& prefix, const View& x, const View& tmp, const View& out, bool shortcut, int n, hipStream_t s);
-  void c3k2(int idx, const View& in, const View& out, int n, hipStream_t s);
+  void c3k(const std::string& prefix, const View& x, const View& kcat, const View& tmp, const View& out, bool shortcut, int n, hipStream_t s);
   void c2psa(int idx, const View& in, const View& out, int n, hipStream_t s);
   int chn(int c) const { return sc_.chn(c); }
   int rep(int n) const { return sc_.rep(n); }
+  int shift() const { return v11() ? 1 : 0; }                       // k: node i of the YOLOv8 neck and head is node i + k
+  void build_v8();
   void build_v11();
   // activation arena: one entry per buffer of max_batch frames, carved in this order
-  struct ArenaBuf { const char* name; int h, w, c; bool f32 = false; };  // f32: View::f32
-  std::vector<ArenaBuf> arena_v8() const;
-  std::vector<ArenaBuf> arena_v11() const;
-  void plan_arena(std::vector<ArenaBuf> all);
-  void forward_v11(const uint8_t* frames, int n, int flip, hipStream_t s);
-  void forward_v8(const uint8_t* frames, int n, int flip, hipStream_t s);
+  struct ArenaBuf { std::string name; int h, w, c; bool f32 = false, seg_only = false; };  // f32: View::f32; seg_only: not on an OBB handle
+  std::vector<ArenaBuf> arena() const;
+  void plan_arena(const std::vector<ArenaBuf>& all);
+  // conv0, the architecture's backbone (returns its last node, a slice of concat 20 + k), the neck and the heads
+  void forward_graph(const uint8_t* frames, int n, int flip, hipStream_t s);
+  View backbone_v8(int n, hipStream_t s);
+  View backbone_v11(int n, hipStream_t s);
+  void neck_and_heads(const View& top, int n, hipStream_t s);
   HeadRows head_rows() const;                                       // the arena's raw head rows (head_decode.h)
   void decode(int n, hipStream_t s);                                // decode_kernel / decode_obb_kernel: raw head rows -> pred
   void run_graph(const uint8_t* frames, int n, int flip, hipStream_t s);  // backbone, neck, head rows (+ prototype branch)
@@ -172,8 +190,11 @@ class Detector {
   void sppf(const std::string& prefix, const View& in, const View& spp, const View& out, int n, hipStream_t s);
   void upsample2x(const View& in, const View& out, int n, hipStream_t s);
   void proto(const std::string& head, const View& p3, int n, hipStream_t s);
-  void head_level_v8(int l, int n, hipStream_t s);
-  void head_level_v11(int l, int n, hipStream_t s);
+  void head_level(int l, int n, hipStream_t s);
+  // the class branch of level l into the raw head rows rh: YOLOv8's on its slices of the head temporaries, YOLO11's
+  // (Detect(legacy=False): depthwise / pointwise pairs) on the level's features f
+  void head_cls_v8(int l, const View& t1, const View& t2, const View& rh, int n, hipStream_t s);
+  void head_cls_v11(int l, const View& f, const View& rh, int n, hipStream_t s);
   void obb_flops_fix(const View& f);                                // count mode: the angle branch's real widths
   // Fork-join inside one forward (library-owned streams and events, library kernels only - the concurrency contract
   // of include/mtgv.h): the prototype branch and the P3 / P4 head branches leave the caller's stream as soon as their
@@ -203,10 +224,7 @@ class Detector {
 
   // weights
   std::map<std::string, ConvW> cw_;
-  struct C2fInfo { int cout, n; bool shortcut; int cin; };
-  std::map<int, C2fInfo> c2f_;
-  struct C3k2Info { int cout, n, ch; bool c3k; };
-  std::map<int, C3k2Info> c3k2_;
+  std::map<int, CspInfo> csp_;
   ConvW cls_dw1_[3], cls_pw1_[3], cls_dw2_[3], cls_pw2_[3];
   std::string head_ = "model.22";
   // head_first_: the first 3x3 convs of the branches that read the level's features, stacked (v8: box, class and

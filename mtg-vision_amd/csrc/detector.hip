@@ -3,8 +3,10 @@
 // family od_train.py:46-70).  BatchNorm (eps 1e-3) is folded into the conv weights at
 // finalize(); Concat is free (producers write channel slices of the consumer's buffer);
 // every Conv+SiLU is one launch of the implicit GEMM (gemm_launch, gemm_f32.hip).
+// This file also holds what YOLO11 shares with it: the CSP block (csp_block: C2f and C3k2), the neck and the head levels
+// (neck_and_heads, head_level), their key expectations (expect_csp, expect_neck, expect_head) and the arena table (arena).
 // The device kernels are in detector_kernel.h, the prototype branch behind cv1 in detector_proto.hip, the YOLO11
-// modules in detector_v11.hip.
+// backbone and the modules only it has in detector_v11.hip.
 #include "detector.h"
 #include "detector_kernel.h"
 #include "nms.h"
@@ -60,41 +62,69 @@ Detector::Detector(const mtgv_detector_cfg& cfg) : cfg_(cfg) {
     HIP_OK(hipEventCreateWithFlags(&ev_fork_[i], hipEventDisableTiming));
     HIP_OK(hipEventCreateWithFlags(&ev_join_[i], hipEventDisableTiming));
   }
-  if (v11()) {
-    head_ = "model.23";
-    build_v11();
-    return;
-  }
+  head_ = "model." + std::to_string(22 + shift());
+  if (v11()) build_v11();
+  else build_v8();
+}
 
-  auto P = [](int i) { return "model." + std::to_string(i); };
-  // backbone + neck
-  struct L { int idx; char kind; int cin, cout, n; bool sc; };  // kind: c conv, f c2f, s sppf
-  const int c16 = chn(64), c32 = chn(128), c64 = chn(256), c128 = chn(512), c256 = chn(1024);
-  const L layers[] = {{0, 'c', 3, c16, 0, false},         {1, 'c', c16, c32, 0, false},           {2, 'f', c32, c32, rep(3), true},
-                      {3, 'c', c32, c64, 0, false},       {4, 'f', c64, c64, rep(6), true},       {5, 'c', c64, c128, 0, false},
-                      {6, 'f', c128, c128, rep(6), true}, {7, 'c', c128, c256, 0, false},         {8, 'f', c256, c256, rep(3), true},
-                      {9, 's', c256, c256, 0, false},     {12, 'f', c256 + c128, c128, rep(3), false}, {15, 'f', c128 + c64, c64, rep(3), false},
-                      {16, 'c', c64, c64, 0, false},      {18, 'f', c64 + c128, c128, rep(3), false},  {19, 'c', c128, c128, 0, false},
-                      {21, 'f', c128 + c256, c256, rep(3), false}};
-  for (const L& l : layers) {
-    if (l.kind == 'c') {
-      expect_conv_bn(P(l.idx), l.cout, l.cin, 3);
-    } else if (l.kind == 'f') {
-      const int ch = l.cout / 2;
-      expect_conv_bn(P(l.idx) + ".cv1", 2 * ch, l.cin, 1);
-      expect_conv_bn(P(l.idx) + ".cv2", l.cout, (2 + l.n) * ch, 1);
-      for (int j = 0; j < l.n; ++j) {
-        expect_conv_bn(P(l.idx) + ".m." + std::to_string(j) + ".cv1", ch, ch, 3);
-        expect_conv_bn(P(l.idx) + ".m." + std::to_string(j) + ".cv2", ch, ch, 3);
-      }
-      c2f_[l.idx] = {l.cout, l.n, l.sc, l.cin};
+static std::string node(int i) { return "model." + std::to_string(i); }
+
+void Detector::expect_csp(int idx, int cin, int cout, int n, bool shortcut, Csp kind, double e) {
+  const int ch = (int)(cout * e), c_ = ch / 2;
+  const std::string p = node(idx);
+  auto bott = [&](const std::string& q, int c1, int cm, int c2) {
+    expect_conv_bn(q + ".cv1", cm, c1, 3);
+    expect_conv_bn(q + ".cv2", c2, cm, 3);
+  };
+  expect_conv_bn(p + ".cv1", 2 * ch, cin, 1);
+  expect_conv_bn(p + ".cv2", cout, (2 + n) * ch, 1);
+  for (int j = 0; j < n; ++j) {
+    const std::string m = p + ".m." + std::to_string(j);
+    if (kind == Csp::C3k) {
+      expect_conv_bn(m + ".cv1", c_, ch, 1);
+      expect_conv_bn(m + ".cv2", c_, ch, 1);
+      expect_conv_bn(m + ".cv3", ch, 2 * c_, 1);
+      for (int i = 0; i < 2; ++i) bott(m + ".m." + std::to_string(i), c_, c_, c_);
     } else {
-      expect_conv_bn(P(l.idx) + ".cv1", l.cin / 2, l.cin, 1);
-      expect_conv_bn(P(l.idx) + ".cv2", l.cout, l.cin / 2 * 4, 1);
+      bott(m, ch, kind == Csp::Half ? c_ : ch, ch);
     }
   }
+  csp_[idx] = {cout, n, ch, shortcut, kind};
+}
+
+void Detector::expect_sppf(const std::string& p, int c) {
+  expect_conv_bn(p + ".cv1", c / 2, c, 1);
+  expect_conv_bn(p + ".cv2", c, c / 2 * 4, 1);
+}
+
+void Detector::expect_neck(int n, bool shortcut, Csp kind, Csp kind_p5) {
+  const int k = shift();
+  const int c64 = chn(256), c128 = chn(512), c256 = chn(1024);
+  expect_csp(12 + k, c256 + c128, c128, n, shortcut, kind);            // on concat [up(9 + k), 6]
+  expect_csp(15 + k, c128 + csp_.at(4).cout, c64, n, shortcut, kind);  // on concat [up(12 + k), 4]: P3
+  expect_conv_bn(node(16 + k), c64, c64, 3);
+  expect_csp(18 + k, c64 + c128, c128, n, shortcut, kind);             // on concat [16 + k, 12 + k]: P4
+  expect_conv_bn(node(19 + k), c128, c128, 3);
+  expect_csp(21 + k, c128 + c256, c256, n, shortcut, kind_p5);         // on concat [19 + k, 9 + k]: P5
   const int chs[3] = {c64, c128, c256};
   expect_head(chs);
+}
+
+// yolov8-seg.yaml / yolov8-obb.yaml
+void Detector::build_v8() {
+  const int c16 = chn(64), c32 = chn(128), c64 = chn(256), c128 = chn(512), c256 = chn(1024);
+  const int n3 = rep(3), n6 = rep(6);
+  expect_conv_bn(node(0), c16, 3, 3);
+  expect_conv_bn(node(1), c32, c16, 3);
+  expect_csp(2, c32, c32, n3, true, Csp::C2f);
+  expect_conv_bn(node(3), c64, c32, 3);
+  expect_csp(4, c64, c64, n6, true, Csp::C2f);
+  expect_conv_bn(node(5), c128, c64, 3);
+  expect_csp(6, c128, c128, n6, true, Csp::C2f);
+  expect_conv_bn(node(7), c256, c128, 3);
+  expect_csp(8, c256, c256, n3, true, Csp::C2f);
+  expect_sppf(node(9), c256);
+  expect_neck(n3, false, Csp::C2f, Csp::C2f);
 }
 
 // Segment head (Detect + Segment + Proto) on features of chs[0..2] channels: the keys both architectures share; only
@@ -281,17 +311,11 @@ ConvW Detector::zero_pad(const ConvW& q, int cout, int cin) {
 
 // Carve the activation arena for max_batch frames: each buffer 256-byte aligned, in table order.  Cleared once: of the raw
 // head rows' 32 columns behind RAW_CLS, those past the classes are written by the chained class conv only (as zeros).
-void Detector::plan_arena(std::vector<ArenaBuf> all) {
+void Detector::plan_arena(const std::vector<ArenaBuf>& all) {
   auto floats = [&](const ArenaBuf& b) { return ((size_t)cfg_.max_batch * b.h * b.w * b.c + 63) / 64 * 64; };
-  if (obb()) {  // no prototype branch, no mask coefficients
-    std::vector<ArenaBuf> kept;
-    for (const ArenaBuf& b : all) {
-      const std::string nm = b.name;
-      if (nm != "pr1" && nm != "pr2" && nm != "pr3" && nm != "protos" && nm != "coef") kept.push_back(b);
-    }
-    all = kept;
-  }
-  const std::vector<ArenaBuf>& bufs = all;
+  std::vector<ArenaBuf> bufs;
+  for (const ArenaBuf& b : all)
+    if (!(obb() && b.seg_only)) bufs.push_back(b);  // OBB: no prototype branch, no mask coefficients
   size_t total = 0;
   for (const ArenaBuf& b : bufs) total += floats(b);
   arena_.alloc(total);
@@ -300,41 +324,76 @@ void Detector::plan_arena(std::vector<ArenaBuf> all) {
   for (const ArenaBuf& b : bufs) {
     View v;
     v.p = p, v.H = b.h, v.W = b.w, v.ct = b.c, v.C = b.c, v.f32 = b.f32;
-    MTGV_CHECK(v_.emplace(b.name, v).second, ERR_RUNTIME, "detector: arena buffer '%s' listed twice", b.name);
+    MTGV_CHECK(v_.emplace(b.name, v).second, ERR_RUNTIME, "detector: arena buffer '%s' listed twice", b.name.c_str());
     p += floats(b);
   }
   HIP_OK(hipMemset(arena_.p, 0, arena_.n * sizeof(float)));
 }
 
-std::vector<Detector::ArenaBuf> Detector::arena_v8() const {
-  const int IH = cfg_.in_h, IW = cfg_.in_w;
+// The arena table of either architecture (node numbers in the comments are YOLOv8's; k = 1 shifts the neck's for YOLO11).
+// The order is the carve order: it decides every buffer's address, so a buffer is added where it is first written.
+std::vector<Detector::ArenaBuf> Detector::arena() const {
+  const int IH = cfg_.in_h, IW = cfg_.in_w, k = shift();
   const int h2 = IH / 2, h4 = IH / 4, h8 = IH / 8, h16 = IH / 16, h32 = IH / 32;
   const int w2 = IW / 2, w4 = IW / 4, w8 = IW / 8, w16 = IW / 16, w32 = IW / 32;
   const int c16 = chn(64), c32 = chn(128), c64 = chn(256), c128 = chn(512), c256 = chn(1024);
-  const int r3 = 2 + rep(3), r6 = 2 + rep(6);  // chunks of a C2f's concat: cv1's two and one per bottleneck
-  const int ht = hc2_ + hc3_ + hc4p_;          // the three head branches side by side (160 at scale n)
-  return {
-      {"l0", h2, w2, c16}, {"l1", h4, w4, c32},
-      {"cat2", h4, w4, r3 * c32 / 2}, {"tmp2", h4, w4, c32 / 2}, {"l2", h4, w4, c32},
-      {"l3", h8, w8, c64}, {"cat4", h8, w8, r6 * c64 / 2}, {"tmp4", h8, w8, c64 / 2},
-      {"cat14", h8, w8, c128 + c64},                                      // concat 14 = [up(12), 4]
-      {"l5", h16, w16, c128}, {"cat6", h16, w16, r6 * c128 / 2}, {"tmp6", h16, w16, c128 / 2},
-      {"cat11", h16, w16, c256 + c128},                                   // concat 11 = [up(9), 6]
-      {"l7", h32, w32, c256}, {"cat8", h32, w32, r3 * c256 / 2}, {"tmp8", h32, w32, c256 / 2}, {"l8", h32, w32, c256},
-      {"sppcat", h32, w32, 2 * c256},
-      {"cat20", h32, w32, c128 + c256},                                   // concat 20 = [19, 9]
-      {"cat12", h16, w16, r3 * c128 / 2}, {"tmp12", h16, w16, c128 / 2},
-      {"cat17", h16, w16, c64 + c128},                                    // concat 17 = [16, 12]
-      {"cat15", h8, w8, r3 * c64 / 2}, {"tmp15", h8, w8, c64 / 2}, {"p3", h8, w8, c64},
-      {"cat18", h16, w16, r3 * c128 / 2}, {"tmp18", h16, w16, c128 / 2}, {"p4", h16, w16, c128},
-      {"cat21", h32, w32, r3 * c256 / 2}, {"tmp21", h32, w32, c256 / 2}, {"p5", h32, w32, c256},
-      // head temporaries per level (the levels' branches run concurrently)
-      {"t1_0", h8, w8, ht}, {"t2_0", h8, w8, ht}, {"t1_1", h16, w16, ht}, {"t2_1", h16, w16, ht},
-      {"t1_2", h32, w32, ht}, {"t2_2", h32, w32, ht},
-      {"rawhead0", h8, w8, RAW_CT, true}, {"rawhead1", h16, w16, RAW_CT, true}, {"rawhead2", h32, w32, RAW_CT, true},
-      {"pr1", h8, w8, npr_}, {"pr2", h4, w4, npr_}, {"pr3", h4, w4, npr_}, {"protos", h4, w4, nm_, true},
-      {"pred", 1, na_, no(), true}, {"coef", 1, cfg_.max_det, nm_, true},
+  std::vector<ArenaBuf> a;
+  auto add = [&](std::initializer_list<ArenaBuf> l) { a.insert(a.end(), l); };
+  auto cat = [&](int i) { return "cat" + std::to_string(i + k); };
+  // CSP block `idx` on an h x w map: the concat of cv1's two chunks and the inner modules' outputs, C3k's own concat where
+  // the inner module is one, and the bottlenecks' temporary (their hidden width: the chunk's, or half of it in C3k2)
+  auto csp = [&](int idx, int h, int w) {
+    const CspInfo& ci = csp_.at(idx);
+    const std::string id = std::to_string(idx);
+    a.push_back({"cat" + id, h, w, (2 + ci.n) * ci.ch});
+    if (ci.kind == Csp::C3k) a.push_back({"kcat" + id, h, w, ci.ch});
+    a.push_back({"tmp" + id, h, w, ci.kind == Csp::C2f ? ci.ch : ci.ch / 2});
   };
+  auto rows = [&] { add({{"rawhead0", h8, w8, RAW_CT, true}, {"rawhead1", h16, w16, RAW_CT, true}, {"rawhead2", h32, w32, RAW_CT, true}}); };
+  // backbone (nodes 4, 6 and the last one write into the neck's concats)
+  add({{"l0", h2, w2, c16}, {"l1", h4, w4, c32}});
+  csp(2, h4, w4);
+  add({{"l2", h4, w4, csp_.at(2).cout}, {"l3", h8, w8, c64}});
+  csp(4, h8, w8);
+  add({{cat(14), h8, w8, c128 + csp_.at(4).cout},  // concat 14 = [up(12), 4]
+       {"l5", h16, w16, c128}});
+  csp(6, h16, w16);
+  add({{cat(11), h16, w16, c256 + c128},  // concat 11 = [up(9), 6]
+       {"l7", h32, w32, c256}});
+  csp(8, h32, w32);
+  add({{"l8", h32, w32, c256}, {"sppcat", h32, w32, 2 * c256}});
+  if (v11()) {  // SPPF's own output and C2PSA (the attention core and the positional encoding read qkv and att in f32)
+    const int pc = c256 / 2;  // C2PSA's hidden width: qkv is pc + 2 heads x 32 keys = 2 pc wide
+    add({{"l9", h32, w32, c256}, {"psacat", h32, w32, 2 * pc}, {"qkv", h32, w32, 2 * pc, true}, {"att", h32, w32, pc, true},
+         {"atty", h32, w32, pc}, {"ffn", h32, w32, 2 * pc}});
+  }
+  add({{cat(20), h32, w32, c128 + c256}});  // concat 20 = [19, 9]
+  // neck
+  csp(12 + k, h16, w16);
+  add({{cat(17), h16, w16, c64 + c128}});  // concat 17 = [16, 12]
+  csp(15 + k, h8, w8);
+  add({{"p3", h8, w8, c64}});
+  csp(18 + k, h16, w16);
+  add({{"p4", h16, w16, c128}});
+  csp(21 + k, h32, w32);
+  add({{"p5", h32, w32, c256}});
+  // head temporaries per level (the levels' branches run concurrently): the branches head_first_ stacks side by side (160
+  // channels at YOLOv8 n, 96 at YOLO11 n), and YOLO11's class branch
+  const int hs[3] = {h8, h16, h32}, ws[3] = {w8, w16, w32}, chs[3] = {c64, c128, c256};
+  const int ht = hc2_ + (v11() ? 0 : hc3_) + hc4p_;
+  for (int l = 0; l < 3; ++l) {
+    const std::string ls = std::to_string(l);
+    const int h = hs[l], w = ws[l];
+    add({{"t1_" + ls, h, w, ht}, {"t2_" + ls, h, w, ht}});
+    if (v11()) add({{"dwa_" + ls, h, w, chs[l]}, {"dwb_" + ls, h, w, hc3_}, {"dwc_" + ls, h, w, hc3_}, {"dwd_" + ls, h, w, hc3_}});
+  }
+  // (the raw head rows are carved in front of the prototype buffers for YOLOv8 and behind them for YOLO11)
+  if (!v11()) rows();
+  add({{"pr1", h8, w8, npr_, false, true}, {"pr2", h4, w4, npr_, false, true}, {"pr3", h4, w4, npr_, false, true},
+       {"protos", h4, w4, nm_, true, true}});
+  if (v11()) rows();
+  add({{"pred", 1, na_, no(), true}, {"coef", 1, cfg_.max_det, nm_, true, true}});
+  return a;
 }
 
 // activation view by name, in the format of the current forward (fmt_) unless the buffer is kept f32
@@ -372,13 +431,13 @@ void Detector::finalize() {
     // branch's widths (at least nm_ = 32 mid channels, 32 outputs), so the head runs on the segment head's launches and the
     // angle logit lands in column RAW_COEF of the rows
     if (obb()) cw_[M + ".0"] = zero_pad(cw_.at(M + ".0"), hc4p_, cw_.at(M + ".0").cin);
+    // the first 3x3 convs of the branches that start on the level's features as one conv (scale n: 64+64+32 outputs, box,
+    // class and coefficient; YOLO11's class branch starts with a depthwise conv: 64+32)
     if (v11()) {
-      // box and coefficient branches start with a 3x3 conv on the same input: one conv with 64+32 outputs
       head_first_[l] = concat_out({cw_.at(B + ".0"), cw_.at(M + ".0")});
       cls_dw1_[l] = cw_.at(C + ".0.0"), cls_pw1_[l] = cw_.at(C + ".0.1");
       cls_dw2_[l] = cw_.at(C + ".1.0"), cls_pw2_[l] = cw_.at(C + ".1.1");
     } else {
-      // the three branches' first 3x3 convs read the same input: one conv with 64+64+32 outputs (scale n)
       head_first_[l] = concat_out({cw_.at(B + ".0"), cw_.at(C + ".0"), cw_.at(M + ".0")});
       head_cls2_[l] = cw_.at(C + ".1");
     }
@@ -403,7 +462,7 @@ void Detector::finalize() {
                                   cw_.at(H + ".proto.cv2"), cw_.at(H + ".proto.cv3"), dev_allocs_);
   }
 
-  plan_arena(v11() ? arena_v11() : arena_v8());
+  plan_arena(arena());
   if (nms_ws_) (void)hipFree(nms_ws_);
   nms_ws_bytes_ = nms_workspace_bytes(cfg_.max_batch, na_);
   HIP_OK(hipMalloc((void**)&nms_ws_, nms_ws_bytes_));
@@ -464,13 +523,20 @@ void Detector::conv_pair(const ConvW& w1, const View& in, const View& mid, int s
   conv_pair_launch(w1, in, mid, stride, w2, out2, act2, n, s, xflops);
 }
 
-// C2f: cv1 -> 2 chunks; n bottlenecks (3x3,3x3, +shortcut) each appended; cv2 over the concat
-void Detector::c2f(int idx, const View& in, const View& out, int n, hipStream_t s, const ConvW* pre, const View* pre_in) {
-  const C2fInfo& ci = c2f_.at(idx);
-  const int ch = ci.cout / 2;
-  const std::string P = "model." + std::to_string(idx);
-  const View cat = view("cat" + std::to_string(idx));
-  const View tmp = view("tmp" + std::to_string(idx));
+// Bottleneck(c1, c2, shortcut, k = (3, 3)): out = cv2(cv1(x)) (+ x).  `out` may be x itself (in place: every output
+// element is read as the residual by the wave that later stores it).
+void Detector::bottleneck(const std::string& p, const View& x, const View& tmp, const View& out, bool shortcut, int n, hipStream_t s) {
+  conv(cw_.at(p + ".cv1"), x, tmp, 1, ACT_SILU, nullptr, n, s);
+  conv(cw_.at(p + ".cv2"), tmp, out, 1, ACT_SILU, shortcut ? &x : nullptr, n, s);
+}
+
+// CSP block (C2f, C3k2): cv1 -> 2 chunks; n inner modules (+shortcut), each reading the chunk before it and appended to
+// the concat; cv2 over the concat
+void Detector::csp_block(int idx, const View& in, const View& out, int n, hipStream_t s, const ConvW* pre, const View* pre_in) {
+  const CspInfo& ci = csp_.at(idx);
+  const int ch = ci.ch;
+  const std::string id = std::to_string(idx), P = "model." + id;
+  const View cat = view("cat" + id), tmp = view("tmp" + id);
   // pre: the stride-2 Conv in front of this block, whose only consumer is cv1 - the pair runs as one launch where it can
   if (pre != nullptr) conv_pair(*pre, *pre_in, in, 2, cw_.at(P + ".cv1"), cat.slice(0, 2 * ch), ACT_SILU, n, s);
   else conv(cw_.at(P + ".cv1"), in, cat.slice(0, 2 * ch), 1, ACT_SILU, nullptr, n, s);
@@ -479,7 +545,9 @@ void Detector::c2f(int idx, const View& in, const View& out, int n, hipStream_t 
     const View src = cat.slice((1 + j) * ch, ch);
     const View dst = cat.slice((2 + j) * ch, ch);
     const std::string M = P + ".m." + std::to_string(j);
-    // the last bottleneck and cv2 as one launch where there is a kernel for the block (c2f_tail.h): tmp and dst stay on chip
+    // the last bottleneck and cv2 as one launch where there is a kernel for the block (c2f_tail.h): tmp and dst stay on chip.
+    // The shapes are those of C2f's Bottleneck(ch -> ch -> ch): a half-width bottleneck (cv1 has ch / 2 outputs) and C3k
+    // (its cv1 and cv2 are 1x1) fail them by construction, so the inner module's kind need not be asked.
     const ConvW &w1 = cw_.at(M + ".cv1"), &w2 = cw_.at(M + ".cv2"), &w3 = cw_.at(P + ".cv2");
     const bool tail_shapes = w1.k == 3 && w1.cin == ch && w1.cout == ch && w2.k == 3 && w2.cin == ch && w2.cout == ch && w3.k == 1 &&
                              w3.cin == (2 + ci.n) * ch && w3.cout == out.C;  // (anything else: conv() below reports it)
@@ -494,8 +562,8 @@ void Detector::c2f(int idx, const View& in, const View& out, int n, hipStream_t 
         return;
       }
     }
-    conv(w1, src, tmp, 1, ACT_SILU, nullptr, n, s);
-    conv(w2, tmp, dst, 1, ACT_SILU, ci.shortcut ? &src : nullptr, n, s);
+    if (ci.kind == Csp::C3k) c3k(M, src, view("kcat" + id), tmp, dst, ci.shortcut, n, s);
+    else bottleneck(M, src, tmp, dst, ci.shortcut, n, s);
   }
   conv(cw_.at(P + ".cv2"), cat.slice(0, (2 + ci.n) * ch), out, 1, ACT_SILU, nullptr, n, s);
 }
@@ -643,11 +711,7 @@ void Detector::run_graph(const uint8_t* frames, int n, int flip, hipStream_t s) 
   // prototypes (decode / mask inputs) stay f32
   fmt_ = (!count_flops_ && gemm_sp_active()) ? 1 : 0;
   head_direct_ = env_int("MTGV_DET_HEAD_DIRECT", 1) != 0;  // read per call (A/B in one process); 0: class 3x3 + 1x1, decode, NMS on pred
-  if (v11()) {
-    forward_v11(frames, n, flip, s);
-  } else {
-    forward_v8(frames, n, flip, s);
-  }
+  forward_graph(frames, n, flip, s);
 }
 
 // SPPF: cv1, three chained 5x5 max pools, cv2 over the concat
@@ -679,63 +743,88 @@ void Detector::upsample2x(const View& in, const View& out, int n, hipStream_t s)
   upsample2x_launch(in.p, in.ct, in.co, out.p, out.ct, out.co, n, in.H, in.W, in.C, s);
 }
 
-void Detector::forward_v8(const uint8_t* frames, int n, int flip, hipStream_t s) {
+void Detector::forward_graph(const uint8_t* frames, int n, int flip, hipStream_t s) {
+  conv0(frames, n, flip, s);
+  neck_and_heads(v11() ? backbone_v11(n, s) : backbone_v8(n, s), n, s);
+}
+
+// yolov8 nodes 1 .. 9 behind conv0; returns node 9
+View Detector::backbone_v8(int n, hipStream_t s) {
   const int c64 = chn(256), c128 = chn(512), c256 = chn(1024);
   auto V = [&](const char* k) -> View { return view(k); };
-  conv0(frames, n, flip, s);
   const View l0 = V("l0");
-  c2f(2, V("l1"), V("l2"), n, s, &cw_.at("model.1"), &l0);  // model.1 (3x3 s2) + cv1 in one launch: l1 is never stored
+  csp_block(2, V("l1"), V("l2"), n, s, &cw_.at("model.1"), &l0);  // model.1 (3x3 s2) + cv1 in one launch: l1 is never stored
   // (model.3 + node 4's cv1 measured 6 us SLOWER chained - 94 vs 61 + 27 - and stay two launches)
   conv(cw_.at("model.3"), V("l2"), V("l3"), 2, ACT_SILU, nullptr, n, s);
   const View n4 = V("cat14").slice(c128, c64);      // node 4 output lives in concat 14 = [up(12), 4]
-  c2f(4, V("l3"), n4, n, s);
+  csp_block(4, V("l3"), n4, n, s);
   conv(cw_.at("model.5"), n4, V("l5"), 2, ACT_SILU, nullptr, n, s);
   const View n6 = V("cat11").slice(c256, c128);     // concat 11 = [up(9), 6]
-  c2f(6, V("l5"), n6, n, s);
+  csp_block(6, V("l5"), n6, n, s);
   conv(cw_.at("model.7"), n6, V("l7"), 2, ACT_SILU, nullptr, n, s);
-  c2f(8, V("l7"), V("l8"), n, s);
+  csp_block(8, V("l7"), V("l8"), n, s);
   const View n9 = V("cat20").slice(c128, c256);     // concat 20 = [19, 9]
   sppf("model.9", V("l8"), V("sppcat"), n9, n, s);
+  return n9;
+}
+
+// From the first upsample to the P5 head, on the backbone's last node `top` (9 + k, in concat 20 + k) and its nodes 4
+// and 6 (in concats 14 + k and 11 + k).  Node numbers are YOLOv8's; YOLO11's are one higher.  A concat's slices are as wide
+// as the views that fill them.
+void Detector::neck_and_heads(const View& top, int n, hipStream_t s) {
+  const int k = shift();
+  auto cat = [&](int i) { return view("cat" + std::to_string(i + k)); };
+  auto w = [&](int i) -> const ConvW& { return cw_.at("model." + std::to_string(i + k)); };
+  const View cat11 = cat(11), cat14 = cat(14), cat17 = cat(17), cat20 = cat(20);
+  const View p3 = view("p3"), p4 = view("p4"), p5 = view("p5");
   // top-down
-  const View cat11 = V("cat11"), cat14 = V("cat14"), cat17 = V("cat17"), cat20 = V("cat20");
-  upsample2x(n9, cat11, n, s);
-  const View n12 = cat17.slice(c64, c128);          // concat 17 = [16, 12]
-  c2f(12, cat11, n12, n, s);
+  upsample2x(top, cat11, n, s);
+  const View n12 = cat17.slice(p3.C, cat17.ct - p3.C);  // concat 17 = [16, 12]
+  csp_block(12 + k, cat11, n12, n, s);
   upsample2x(n12, cat14, n, s);
-  c2f(15, cat14, V("p3"), n, s);
+  csp_block(15 + k, cat14, p3, n, s);
   // P3 exists: the prototype branch (0.5 ms of chip-filling launches) and the P3 head leave the caller's stream; the
   // rest of the neck - 100..400-tile launches that cannot fill 256 CUs on their own - runs beside them
-  if (!obb()) proto(head_, V("p3"), n, fork_after(s, 0));
-  head_level_v8(0, n, fork_after(s, 1));
-  conv(cw_.at("model.16"), V("p3"), cat17.slice(0, c64), 2, ACT_SILU, nullptr, n, s);
-  c2f(18, cat17, V("p4"), n, s);
-  head_level_v8(1, n, fork_after(s, 2));
-  conv(cw_.at("model.19"), V("p4"), cat20.slice(0, c128), 2, ACT_SILU, nullptr, n, s);
-  c2f(21, cat20, V("p5"), n, s);
-  head_level_v8(2, n, s);
+  if (!obb()) proto(head_, p3, n, fork_after(s, 0));
+  head_level(0, n, fork_after(s, 1));
+  conv(w(16), p3, cat17.slice(0, p3.C), 2, ACT_SILU, nullptr, n, s);
+  csp_block(18 + k, cat17, p4, n, s);
+  head_level(1, n, fork_after(s, 2));
+  conv(w(19), p4, cat20.slice(0, p4.C), 2, ACT_SILU, nullptr, n, s);
+  csp_block(21 + k, cat20, p5, n, s);
+  head_level(2, n, s);
   join_into(s, 1), join_into(s, 2);  // (the prototype branch is joined in head_tail, after decode + NMS)
 }
 
-// Segment head of level l (P3 / P4 / P5): the three branches' first 3x3 convs as one launch, then per branch 3x3 -> 1x1
-void Detector::head_level_v8(int l, int n, hipStream_t s) {
+// YOLOv8's class branch behind head_first_: 3x3 t1 -> t2, 1x1 t2 -> the rows' class columns
+void Detector::head_cls_v8(int l, const View& t1, const View& t2, const View& rh, int n, hipStream_t s) {
+  if (head_direct_ && !count_flops_ && fmt_ == 1) {  // (f32 activations chain nothing: the 1x1 keeps its nc columns)
+    // one launch, the 1x1 padded to the 32 columns behind RAW_CLS (its nc outputs alone are no column block of the
+    // chain); the launch profiler keeps counting the nc real outputs of the 1x1
+    const double pad_flops = 2.0 * n * rh.H * rh.W * (double)(head_cls3_pad_[l].cout - cfg_.nc) * head_cls3_pad_[l].cin;
+    conv_pair(head_cls2_[l], t1, t2, 1, head_cls3_pad_[l], rh.slice(RAW_CLS, 32), ACT_NONE, n, s, -pad_flops);
+  } else {
+    conv(head_cls2_[l], t1, t2, 1, ACT_SILU, nullptr, n, s);
+    conv(head_cls3_[l], t2, rh.slice(RAW_CLS, cfg_.nc), 1, ACT_NONE, nullptr, n, s);
+  }
+}
+
+// Head of level l (P3 / P4 / P5): the first 3x3 convs of the branches that start on the features as one launch
+// (head_first_), then per branch 3x3 -> 1x1; YOLO11's class branch is a chain of its own on the features
+void Detector::head_level(int l, int n, hipStream_t s) {
   const char* feats[3] = {"p3", "p4", "p5"};
   const std::string ls = std::to_string(l);
   const View f = view(feats[l]), t1 = view("t1_" + ls), t2 = view("t2_" + ls);
   const View rh = view("rawhead" + ls);
   conv(head_first_[l], f, t1, 1, ACT_SILU, nullptr, n, s);
-  // every branch: the 3x3 and the final 1x1 as one launch (the class branch with its 1x1 padded to the 32 columns behind
-  // RAW_CLS: its nc outputs alone are no column block of the chain)
-  const int c2 = hc2_, c3 = hc3_, c4 = hc4p_;  // 64, 64, 32 at scale n
+  // every branch: the 3x3 and the final 1x1 as one launch.  head_first_ stacks the box branch first and the coefficient
+  // branch last (64 and 32 channels at scale n), YOLOv8's class branch (64) between them.
+  const int c2 = hc2_, c4 = hc4p_, o4 = head_first_[l].cout - c4;
   conv_pair(head_box2_[l], t1.slice(0, c2), t2.slice(0, c2), 1, head_box3_[l], rh.slice(0, 4 * reg_max_), ACT_NONE, n, s);
-  if (head_direct_ && !count_flops_ && fmt_ == 1) {  // (f32 activations chain nothing: the 1x1 keeps its nc columns)
-    // (the launch profiler keeps counting the nc real outputs of the 1x1)
-    const double pad_flops = 2.0 * n * rh.H * rh.W * (double)(head_cls3_pad_[l].cout - cfg_.nc) * head_cls3_pad_[l].cin;
-    conv_pair(head_cls2_[l], t1.slice(c2, c3), t2.slice(c2, c3), 1, head_cls3_pad_[l], rh.slice(RAW_CLS, 32), ACT_NONE, n, s, -pad_flops);
-  } else {
-    conv(head_cls2_[l], t1.slice(c2, c3), t2.slice(c2, c3), 1, ACT_SILU, nullptr, n, s);
-    conv(head_cls3_[l], t2.slice(c2, c3), rh.slice(RAW_CLS, cfg_.nc), 1, ACT_NONE, nullptr, n, s);
-  }
-  conv_pair(head_coef2_[l], t1.slice(c2 + c3, c4), t2.slice(c2 + c3, c4), 1, head_coef3_[l], rh.slice(RAW_COEF, nm_), ACT_NONE, n, s);
+  // (the class branch is enqueued between the two pairs for YOLOv8 and behind them for YOLO11)
+  if (!v11()) head_cls_v8(l, t1.slice(c2, hc3_), t2.slice(c2, hc3_), rh, n, s);
+  conv_pair(head_coef2_[l], t1.slice(o4, c4), t2.slice(o4, c4), 1, head_coef3_[l], rh.slice(RAW_COEF, nm_), ACT_NONE, n, s);
+  if (v11()) head_cls_v11(l, f, rh, n, s);
   obb_flops_fix(f);
 }
 

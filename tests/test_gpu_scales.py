@@ -307,6 +307,78 @@ def test_scale_n_is_untouched(arch):
     assert (launches, sha) == PARENT_N[arch]
 
 
+# The same for every (architecture, scale, task), measured on commit b6479f1 - the parent of the change that gave YOLOv8 and
+# YOLO11 one CSP block, one neck, one head level and one arena table - with this function's code on an MI355X: GEMM launches of
+# one forward of SMALL_N frames of SMALL_HW on a max_batch = 4 handle (f16x3, fork off), mtgv_detector_flops (compared as a
+# double, exactly), SHA-256 of `pred`'s bytes and, on a segment handle, of `protos`'.  Weights and frames: scales_common.inputs.
+PARENT_ALL = {
+    ("v8", "n", "seg"): (60, 170138880.0, '8a8444ac49a683be978887b773bc184075499d68b27d650df9369a42e72f8c95',
+                         '2d8ef0a395ccce2d6982d3c12b146f4fdca5ff395f15a79d0cb0b3c7039d6287'),
+    ("v8", "n", "obb"): (55, 124938432.0, 'b27a6d0272bc98ebdd526119025df699fff4b7a57573ab827cd6b5dc8f749341',
+                         None),
+    ("v8", "s", "seg"): (62, 598792704.0, '3507bb69b7ef77debf2240ca0226e468ffa6b8e10347872da70420f12262e108',
+                         '7643355e5acecc02c7f2cbae0262cc8e199b289a04356a0e24008284cda915bb'),
+    ("v8", "s", "obb"): (58, 441256320.0, 'a5c049ca607a94266b802ca76442fb41badc1641cf761cddbe3581d77cbfb758',
+                         None),
+    ("v8", "m", "seg"): (85, 1564330752.0, '9ad56e4def622f6b6c7eadc3b2260e7253979d9527e1dbf992429d517165c91d',
+                         'd77679b39351bbc5dff0a098839aad9fd6e0ece71e1c769e214b37ec9e4f3369'),
+    ("v8", "m", "obb"): (81, 1212420672.0, '45cfc7710c7c6dac71a946b989b2e1b6e7999545f434c1ab6d765837f38096bd',
+                         None),
+    ("11", "n", "seg"): (84, 143569920.0, 'daada1b81319c471d9df7c4c02f5a091ab6dc0b009746717688b0c8a5d162452',
+                         '01b020d220c267764ac575219131d0cea3001f9dac09b68d326ed01ac46bdec2'),
+    ("11", "n", "obb"): (79, 98369472.0, 'c7fe6bb65b489eb2431310746707605856e04cd8b50853aec47cdb0371777004',
+                         None),
+    ("11", "s", "seg"): (83, 491784192.0, '16cd546259906f6c24d85f86fb49755c2d0b4fcc114f2143408e53a5947f1e90',
+                         'a032caec62b4b0cfc5df1d97f08d6e7beac9d060300adf556eb31380922596a8'),
+    ("11", "s", "obb"): (79, 334247808.0, '46e68edfef55c6f9bf3e3087b2a026ef6af8c61731bbbf4b4579460689716386',
+                         None),
+    ("11", "m", "seg"): (108, 1693433856.0, '7e76e1b0125661101213c422aaf11f36a72cf4c3b29f09e647769aa68d59e0d2',
+                         'bf7f61530dc965cc45511665317fab0a8762bc9f93721ae295c82e87be166237'),
+    ("11", "m", "obb"): (104, 1070079744.0, '7e3ca9b8f1c3ec57e83b0097db5cc03b0d3218cdc421ca433d114e7c49e24ad2',
+                         None),
+}
+
+
+def small_fingerprint(arch, scale, task):
+    """(GEMM launches, flops per frame, SHA-256 of pred, SHA-256 of protos or None) of one forward of the small case"""
+    from mtgv import native
+
+    case = (arch, scale, task, S.SMALL_HW, S.SMALL_N)
+    _, _, frames = S.inputs(*case)
+    det = _detector(*case)
+    x = torch.from_numpy(frames).cuda()
+    L = native.lib()
+    det.set_fork(0)
+
+    def run():
+        native.check(L.mtgv_profile_gemm(1))
+        try:
+            det.forward(x, True, 0)
+            torch.cuda.synchronize()
+            nl = C.c_int64()
+            native.check(L.mtgv_profile_gemm_read(None, None, C.byref(nl)))
+        finally:
+            native.check(L.mtgv_profile_gemm(0))
+        pred, protos = det.raw_outputs(len(frames))
+        sha = lambda t: hashlib.sha256(t.cpu().numpy().tobytes()).hexdigest()
+        return int(nl.value), det.flops_per_frame(), sha(pred), None if protos is None else sha(protos)
+
+    try:
+        return _with_mode("f16x3", run)
+    finally:
+        det.set_fork(-1)  # (the handle is shared with the other tests of this module)
+
+
+@pytest.mark.parametrize("task", ["seg", "obb"])
+@pytest.mark.parametrize("scale", ["n", "s", "m"])
+@pytest.mark.parametrize("arch", ["v8", "11"])
+def test_every_scale_runs_the_parents_launches(arch, scale, task):
+    got = small_fingerprint(arch, scale, task)
+    print(f'    ("{arch}", "{scale}", "{task}"): {got!r},')
+    assert (got[3] is None) == (task == "obb")
+    assert got == PARENT_ALL[(arch, scale, task)]
+
+
 # ---------------------------------------------------------------------------
 # 5. errors
 # ---------------------------------------------------------------------------
