@@ -1,8 +1,11 @@
 // Baseline JPEG decode on the GPU (SOF0 / SOF1, Huffman, 8-bit; 1 component or YCbCr 4:4:4 / 4:2:2 / 4:2:0).
 //
-// Host: walk the markers of every image, build descriptors (geometry, quantisation tables, Huffman lookup tables,
-// restart interval, entropy-coded segment), pack them with the entropy-coded bytes into the handle's pinned staging
-// buffer and copy it in one transfer.  Anything outside the supported subset is refused before any launch.
+// Host (jpeg_host.h / jpeg_host.cpp, no HIP; the records it writes for the kernels are in jpeg_desc.h): walk the markers
+// of every image, build descriptors (geometry, quantisation tables, Huffman lookup tables, restart interval,
+// entropy-coded segment) and lay out the staging image.  This file keeps the kernels, the handle and the C ABI:
+// mtgv_jpeg_decode plans the batch, waits for the previous upload, stages descriptors and entropy-coded bytes into the
+// handle's pinned buffer, copies it in one transfer and launches.  Anything outside the supported subset is refused
+// before any launch.
 //
 // Device, one batch in eleven launches (all integer arithmetic):
 //   unstuff_count / unstuff_scan / unstuff_scatter  drop the 0x00 after each 0xFF and the RSTn markers (prefix-sum
@@ -26,54 +29,25 @@
 //                              (jdcolor tables) -> RGB uint8 at the caller's offset / pitch
 // Every decode loop is bounded by the stream length.  A stream that does not decode sets its image's status word; the
 // write, dc, idct and color launches then skip that image, so nothing is written outside its workspace and slot.
-#include <stdarg.h>
 #include <string.h>
 
 #include <algorithm>
-#include <map>
 #include <string>
-#include <vector>
 
 #include "common.h"
 #include "jpeg_common.h"
+#include "jpeg_host.h"
 #include "mtgv.h"
 
 using namespace mtgv;
+using namespace mtgv::jpeg;
 
 namespace {
 
-constexpr int CHUNK_BYTES = 64;    // self-synchronising decode: bytes of stream per thread
-constexpr int SYNC_WG = 256;       // chunks per workgroup of the in-workgroup synchronisation
-constexpr int TILE_BYTES = 4096;   // unstuffing: 256 threads x 16 bytes
+constexpr int SYNC_WG = 256;  // chunks per workgroup of the in-workgroup synchronisation
 constexpr uint32_t POS_END = 0xFFFFFFFFu, POS_ERR = 0xFFFFFFFEu;
 
-struct HuffTab {
-  uint16_t lut[512];    // 9-bit lookahead: (length << 8) | symbol; 0: the code is longer than 9 bits
-  int32_t maxcode[17];  // largest code of each length, -1 if none
-  int32_t valoff[17];   // symbol index = code + valoff[length]
-  uint8_t val[256];
-};
-
-struct CompDesc {
-  uint16_t q[64];  // natural order
-  int32_t dc, ac;  // Huffman table index within the batch
-  int32_t h, v;    // sampling factors (1 x 1 for a single-component scan)
-  int32_t bw, bh;  // plane size in blocks
-  int64_t plane;   // byte offset of the plane in the plane workspace
-};
-
-struct ImgDesc {
-  int32_t h, w, ncomp, mode;  // mode: 0 grey, 1 4:4:4, 2 4:2:2, 3 4:2:0
-  int32_t mcux, mcuy, bpm, ri, nseg, nchunks, ntiles, pad_;
-  int8_t bcomp[8], bdx[8], bdy[8];  // MCU slot -> component, block offset inside the MCU
-  int64_t ecs;                      // byte offset of the entropy-coded data (staging) and of the bit stream (workspace)
-  int64_t ecs_len;
-  int64_t chunk0, seg0, tile0, blk0, pix0, nblocks;
-  int64_t dst_off, pitch;
-  CompDesc c[3];
-};
-
-struct Params {
+struct Staged {  // what one call uploads: pointers into the device copy of the staging image
   const ImgDesc* d;
   const HuffTab* tabs;
   const int64_t* chunk_base;  // n + 1 prefix arrays for the ragged launches
@@ -83,6 +57,9 @@ struct Params {
   const int64_t* pix_base;
   const uint8_t* ecs;  // staged entropy-coded bytes
   int n;
+};
+
+struct Work {  // the handle's workspaces, allocated at creation
   uint8_t* cs;          // compacted bit streams
   int32_t* tile_cnt;    // per tile: kept bytes, markers, offset, marker offset
   uint32_t* slen;       // stream bytes per image
@@ -95,6 +72,9 @@ struct Params {
   uint32_t* ccnt;       // blocks started in each chunk, then their exclusive scan
   int16_t* coef;        // 64 per block, natural order
   uint8_t* plane;
+};
+
+struct Params : Staged, Work {
   uint8_t* dst;
   int32_t* status;
 };
@@ -665,248 +645,13 @@ __global__ __launch_bounds__(256) void color_kernel(Params P, int64_t npix) {
   o[2] = rgb[2];
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// host: marker walk
-
-struct Parsed {
-  int h = 0, w = 0, ncomp = 0, sampling = 0, ri = 0, supported = 0;
-  std::string why;  // first unsupported feature
-  struct Comp {
-    int id, h, v, tq, td, ta;
-  } comp[4];
-  uint16_t qt[4][64];
-  bool qdef[4] = {false, false, false, false};
-  uint8_t hbits[2][4][17];
-  uint8_t hval[2][4][256];
-  bool hdef[2][4] = {{false, false, false, false}, {false, false, false, false}};
-  int64_t ecs = 0, ecs_len = 0;
-};
-
-[[noreturn]] void bad(const char* fmt, ...) __attribute__((format(printf, 1, 2)));
-void bad(const char* fmt, ...) {
-  char b[256];
-  va_list ap;
-  va_start(ap, fmt);
-  vsnprintf(b, sizeof(b), fmt, ap);
-  va_end(ap);
-  throw Error(ERR_INVALID, std::string("jpeg: ") + b);
-}
-
-void unsupported(Parsed& p, const std::string& why) {
-  if (p.why.empty()) p.why = why;
-}
-
-inline int be16(const uint8_t* d) { return d[0] << 8 | d[1]; }
-
-// canonical codes of a DHT table; false if a code does not fit its length (libjpeg: no all-ones code)
-bool huff_codes(const uint8_t* bits, int* maxcode, int* valoff, uint16_t* lut, const uint8_t* val) {
-  int code = 0, k = 0;
-  if (lut) memset(lut, 0, 512 * sizeof(uint16_t));
-  for (int l = 1; l <= 16; ++l) {
-    const int first = code, firstk = k;
-    for (int j = 0; j < bits[l]; ++j, ++code, ++k) {
-      if (lut && l <= 9) {
-        const int sh = 9 - l;
-        for (int e = 0; e < (1 << sh); ++e) lut[(code << sh) | e] = (uint16_t)(l << 8 | val[k]);
-      }
-    }
-    if (code >= (1 << l)) return false;
-    if (maxcode) {
-      maxcode[l] = bits[l] ? code - 1 : -1;
-      valoff[l] = firstk - first;
-    }
-    code <<= 1;
-  }
-  return true;
-}
-
-// walks the markers of one file; throws ERR_INVALID on malformed input, sets p.why on unsupported input
-void parse(const uint8_t* d, int64_t n, Parsed& p) {
-  if (d == nullptr || n <= 0) bad("empty input (%lld bytes)", (long long)n);
-  if (n < 2 || d[0] != 0xFF || d[1] != 0xD8) bad("no SOI marker at the start");
-  int64_t q = 2;
-  bool sof = false, jfif = false, adobe = false;
-  int adobe_transform = -1;
-  for (;;) {
-    if (q >= n) bad("truncated before SOS (byte %lld)", (long long)q);
-    if (d[q] != 0xFF) bad("expected a marker at byte %lld, found 0x%02X", (long long)q, d[q]);
-    while (q < n && d[q] == 0xFF) ++q;
-    if (q >= n) bad("truncated before SOS");
-    const int m = d[q++];
-    if (m == 0xD8) bad("second SOI marker at byte %lld", (long long)q - 2);
-    if (m == 0xD9) bad("EOI before any SOS: no image data");
-    if ((m >= 0xD0 && m <= 0xD7) || m == 0x01) continue;
-    if (q + 2 > n) bad("truncated marker 0x%02X", m);
-    const int len = be16(d + q);
-    if (len < 2 || q + len > n) bad("truncated marker segment 0x%02X (length %d, %lld bytes left)", m, len, (long long)(n - q));
-    const uint8_t* s = d + q + 2;
-    const int sl = len - 2;
-    q += len;
-    if (m >= 0xC0 && m <= 0xCF && m != 0xC4 && m != 0xC8 && m != 0xCC) {
-      if (sof) bad("second SOF marker 0x%02X", m);
-      sof = true;
-      if (sl < 6) bad("SOF segment too short");
-      const int prec = s[0];
-      p.h = be16(s + 1);
-      p.w = be16(s + 3);
-      p.ncomp = s[5];
-      if (sl < 6 + 3 * p.ncomp) bad("SOF segment too short for %d components", p.ncomp);
-      if (p.w == 0) bad("image width 0");
-      for (int c = 0; c < std::min(p.ncomp, 4); ++c) {
-        p.comp[c].id = s[6 + 3 * c];
-        p.comp[c].h = s[7 + 3 * c] >> 4;
-        p.comp[c].v = s[7 + 3 * c] & 15;
-        p.comp[c].tq = s[8 + 3 * c];
-        if (p.comp[c].h < 1 || p.comp[c].h > 4 || p.comp[c].v < 1 || p.comp[c].v > 4) bad("invalid sampling factors of component %d", c);
-        if (p.comp[c].tq > 3) bad("invalid quantisation table index %d", p.comp[c].tq);
-      }
-      if (m == 0xC2 || m == 0xC6) unsupported(p, "progressive JPEG (SOF" + std::to_string(m - 0xC0) + ")");
-      else if (m == 0xC3 || m == 0xC7 || m == 0xCB || m == 0xCF) unsupported(p, "lossless JPEG (SOF" + std::to_string(m - 0xC0) + ")");
-      else if (m >= 0xC9) unsupported(p, "arithmetic coding (SOF" + std::to_string(m - 0xC0) + ")");
-      else if (m == 0xC5) unsupported(p, "hierarchical JPEG (SOF5)");
-      if (prec != 8) unsupported(p, std::to_string(prec) + "-bit samples");
-      if (p.h == 0) unsupported(p, "height given by a DNL marker");
-      if (p.ncomp == 4) unsupported(p, "4 components (CMYK / YCCK)");
-      else if (p.ncomp != 1 && p.ncomp != 3) unsupported(p, std::to_string(p.ncomp) + " components");
-      if (p.ncomp == 3) {
-        const auto& c = p.comp;
-        if (c[1].h != 1 || c[1].v != 1 || c[2].h != 1 || c[2].v != 1) unsupported(p, "chroma sampling factors other than 1x1");
-        else if (c[0].h == 1 && c[0].v == 1) p.sampling = 444;
-        else if (c[0].h == 2 && c[0].v == 1) p.sampling = 422;
-        else if (c[0].h == 2 && c[0].v == 2) p.sampling = 420;
-        else unsupported(p, "luma sampling " + std::to_string(c[0].h) + "x" + std::to_string(c[0].v));
-      } else if (p.ncomp == 1) {
-        p.sampling = 400;
-      }
-    } else if (m == 0xDB) {  // DQT
-      int o = 0;
-      while (o < sl) {
-        const int pq = s[o] >> 4, tq = s[o] & 15;
-        ++o;
-        if (pq > 1 || tq > 3) bad("invalid DQT table %d precision %d", tq, pq);
-        if (o + 64 * (pq + 1) > sl) bad("truncated DQT segment");
-        for (int k = 0; k < 64; ++k) p.qt[tq][h_natural[k]] = pq ? (uint16_t)be16(s + o + 2 * k) : s[o + k];
-        o += 64 * (pq + 1);
-        p.qdef[tq] = true;
-      }
-    } else if (m == 0xC4) {  // DHT
-      int o = 0;
-      while (o < sl) {
-        if (o + 17 > sl) bad("truncated DHT segment");
-        const int tc = s[o] >> 4, th = s[o] & 15;
-        if (tc > 1 || th > 3) bad("invalid DHT class %d / index %d", tc, th);
-        int total = 0;
-        uint8_t bits[17] = {0};
-        for (int l = 1; l <= 16; ++l) total += bits[l] = s[o + l];
-        if (total > 256) bad("DHT table with %d codes (more than 256)", total);
-        if (o + 17 + total > sl) bad("truncated DHT segment");
-        if (!huff_codes(bits, nullptr, nullptr, nullptr, nullptr)) bad("bad Huffman table (class %d, index %d): codes do not fit their lengths", tc, th);
-        memcpy(p.hbits[tc][th], bits, 17);
-        memset(p.hval[tc][th], 0, 256);
-        memcpy(p.hval[tc][th], s + o + 17, total);
-        if (tc == 0)
-          for (int k = 0; k < total; ++k)
-            if (p.hval[tc][th][k] > 15) bad("DC Huffman table %d has a symbol %d > 15", th, p.hval[tc][th][k]);
-        p.hdef[tc][th] = true;
-        o += 17 + total;
-      }
-    } else if (m == 0xDD) {  // DRI
-      if (sl != 2) bad("DRI segment of length %d", len);
-      p.ri = be16(s);
-    } else if (m == 0xE0) {
-      if (sl >= 5 && memcmp(s, "JFIF\0", 5) == 0) jfif = true;
-    } else if (m == 0xEE) {
-      if (sl >= 12 && memcmp(s, "Adobe", 5) == 0) adobe = true, adobe_transform = s[11];
-    } else if (m == 0xDC) {
-      unsupported(p, "DNL marker");
-    } else if (m == 0xDA) {  // SOS
-      if (!sof) bad("SOS before SOF");
-      if (sl < 1) bad("SOS segment too short");
-      const int ns = s[0];
-      if (sl != 4 + 2 * ns || ns < 1 || ns > 4) bad("malformed SOS segment");
-      if (ns != p.ncomp) unsupported(p, "non-interleaved scans (" + std::to_string(ns) + " of " + std::to_string(p.ncomp) + " components)");
-      for (int j = 0; j < ns && j < p.ncomp && p.ncomp <= 4; ++j) {
-        int c = 0;
-        while (c < p.ncomp && p.comp[c].id != s[1 + 2 * j]) ++c;
-        if (c == p.ncomp) bad("SOS names component %d, absent from SOF", s[1 + 2 * j]);
-        if (c != j) unsupported(p, "scan component order differs from the frame's");
-        p.comp[c].td = s[2 + 2 * j] >> 4;
-        p.comp[c].ta = s[2 + 2 * j] & 15;
-        if (p.comp[c].td > 3 || p.comp[c].ta > 3) bad("invalid Huffman table index in SOS");
-      }
-      const int ss = s[1 + 2 * ns], se = s[2 + 2 * ns], ah = s[3 + 2 * ns] >> 4, al = s[3 + 2 * ns] & 15;
-      if (ss != 0 || se != 63 || ah != 0 || al != 0) unsupported(p, "spectral selection / successive approximation in the scan");
-      p.ecs = q;
-      break;
-    }
-    // APPn, COM and every other segment: skipped
-  }
-  if (p.ncomp == 3 && !jfif && ((adobe && adobe_transform == 0) || (!adobe && p.comp[0].id == 'R' && p.comp[1].id == 'G' && p.comp[2].id == 'B')))
-    unsupported(p, "RGB colour space (no YCbCr transform)");
-  // end of the entropy-coded segment: the first marker other than RSTn
-  int64_t e = p.ecs;
-  for (;;) {
-    const void* f = memchr(d + e, 0xFF, (size_t)(n - e));
-    if (f == nullptr) bad("truncated entropy-coded data (no EOI marker)");
-    e = (const uint8_t*)f - d;
-    int64_t k = e + 1;
-    while (k < n && d[k] == 0xFF) ++k;
-    if (k >= n) bad("truncated entropy-coded data (no EOI marker)");
-    if (d[k] == 0x00 || (d[k] >= 0xD0 && d[k] <= 0xD7)) {
-      e = k + 1;
-      continue;
-    }
-    break;
-  }
-  p.ecs_len = e - p.ecs;
-  // what follows: EOI, or segments after which another scan would be unsupported
-  int64_t q2 = e;
-  for (;;) {
-    while (q2 < n && d[q2] == 0xFF) ++q2;
-    if (q2 >= n) bad("truncated after the scan (no EOI marker)");
-    const int m = d[q2++];
-    if (m == 0xD9) break;
-    if (m == 0xDA) {
-      unsupported(p, "more than one scan");
-      break;
-    }
-    if (m == 0xDC) unsupported(p, "DNL marker");
-    if (q2 + 2 > n) bad("truncated marker 0x%02X after the scan", m);
-    const int len = be16(d + q2);
-    if (len < 2 || q2 + len > n) bad("truncated marker segment 0x%02X after the scan", m);
-    q2 += len;
-    if (q2 < n && d[q2] != 0xFF) bad("expected a marker at byte %lld after the scan", (long long)q2);
-  }
-  if (p.why.empty()) {
-    for (int c = 0; c < p.ncomp; ++c) {
-      if (!p.qdef[p.comp[c].tq]) bad("component %d uses undefined quantisation table %d", c, p.comp[c].tq);
-      if (!p.hdef[0][p.comp[c].td]) bad("component %d uses undefined DC Huffman table %d", c, p.comp[c].td);
-      if (!p.hdef[1][p.comp[c].ta]) bad("component %d uses undefined AC Huffman table %d", c, p.comp[c].ta);
-    }
-    p.supported = 1;
-  }
-}
-
 }  // namespace
 
 struct mtgv_jpeg_decoder {
-  int max_images;
-  int64_t max_bytes, max_pixels;
-  int64_t cap_stage, cap_chunks, cap_tiles, cap_segs, cap_blocks, cap_plane;
+  DecoderCaps caps;
   uint8_t* h_stage = nullptr;
   uint8_t* d_stage = nullptr;
-  uint8_t* d_cs = nullptr;
-  int32_t* d_tile = nullptr;
-  uint32_t* d_slen = nullptr;
-  int32_t* d_err = nullptr;
-  int32_t* d_ok = nullptr;
-  uint32_t* d_seg = nullptr;
-  uint32_t* d_segcnt = nullptr;
-  uint64_t* d_cstart = nullptr;
-  uint64_t* d_cexit = nullptr;
-  uint32_t* d_ccnt = nullptr;
-  int16_t* d_coef = nullptr;
-  uint8_t* d_plane = nullptr;
+  Work work = {};
   hipEvent_t staged = nullptr;  // the last upload from h_stage
   bool pending = false;
   int device = 0;
@@ -914,15 +659,13 @@ struct mtgv_jpeg_decoder {
 
 namespace {
 
-int64_t align_up(int64_t x, int64_t a) { return (x + a - 1) / a * a; }
-
 void destroy(mtgv_jpeg_decoder* h) {
   if (!h) return;
   if (h->pending) (void)hipEventSynchronize(h->staged);
   if (h->staged) (void)hipEventDestroy(h->staged);
   if (h->h_stage) (void)hipHostFree(h->h_stage);
-  void* dev[] = {h->d_stage, h->d_cs,     h->d_tile,   h->d_slen, h->d_err,  h->d_ok,   h->d_seg,
-                 h->d_segcnt, h->d_cstart, h->d_cexit, h->d_ccnt, h->d_coef, h->d_plane};
+  const Work& w = h->work;
+  void* dev[] = {h->d_stage, w.cs, w.tile_cnt, w.slen, w.err, w.ok, w.seg_start, w.seg_cnt, w.cstart, w.cexit, w.ccnt, w.coef, w.plane};
   for (void* p : dev)
     if (p) (void)hipFree(p);
   delete h;
@@ -953,33 +696,25 @@ MTGV_API int mtgv_jpeg_decoder_create(int32_t max_images, int64_t max_bytes, int
                max_images, (long long)max_bytes, (long long)max_pixels);
     MTGV_CHECK(max_bytes < (1ll << 31) && max_pixels < (1ll << 34), ERR_INVALID, "limits too large");
     auto* h = new mtgv_jpeg_decoder();
-    h->max_images = max_images;
-    h->max_bytes = max_bytes;
-    h->max_pixels = max_pixels;
+    const DecoderCaps& c = h->caps = decoder_caps(max_images, max_bytes, max_pixels);
     const int64_t n = max_images;
-    h->cap_chunks = max_bytes / CHUNK_BYTES + n;
-    h->cap_tiles = max_bytes / TILE_BYTES + n;
-    h->cap_segs = max_bytes / 2 + n;
-    h->cap_blocks = 3 * ceil_div64(max_pixels, 64);
-    h->cap_plane = 3 * max_pixels;
-    h->cap_stage = align_up(n * (int64_t)sizeof(ImgDesc), 256) + align_up(4 * n * (int64_t)sizeof(HuffTab), 256) +
-                   align_up(5 * (n + 1) * 8, 256) + max_bytes + 16 * n + 256;
+    Work& w = h->work;
     try {
       HIP_OK(hipGetDevice(&h->device));
-      HIP_OK(hipHostMalloc((void**)&h->h_stage, h->cap_stage, hipHostMallocDefault));
-      HIP_OK(hipMalloc((void**)&h->d_stage, h->cap_stage));
-      HIP_OK(hipMalloc((void**)&h->d_cs, max_bytes + 16 * n + 256));
-      HIP_OK(hipMalloc((void**)&h->d_tile, h->cap_tiles * 4 * sizeof(int32_t)));
-      HIP_OK(hipMalloc((void**)&h->d_slen, n * sizeof(uint32_t)));
-      HIP_OK(hipMalloc((void**)&h->d_err, n * sizeof(int32_t)));
-      HIP_OK(hipMalloc((void**)&h->d_ok, n * sizeof(int32_t)));
-      HIP_OK(hipMalloc((void**)&h->d_seg, h->cap_segs * sizeof(uint32_t)));
-      HIP_OK(hipMalloc((void**)&h->d_segcnt, h->cap_segs * sizeof(uint32_t)));
-      HIP_OK(hipMalloc((void**)&h->d_cstart, h->cap_chunks * sizeof(uint64_t)));
-      HIP_OK(hipMalloc((void**)&h->d_cexit, h->cap_chunks * sizeof(uint64_t)));
-      HIP_OK(hipMalloc((void**)&h->d_ccnt, h->cap_chunks * sizeof(uint32_t)));
-      HIP_OK(hipMalloc((void**)&h->d_coef, h->cap_blocks * 64 * sizeof(int16_t)));
-      HIP_OK(hipMalloc((void**)&h->d_plane, h->cap_plane));
+      HIP_OK(hipHostMalloc((void**)&h->h_stage, c.stage, hipHostMallocDefault));
+      HIP_OK(hipMalloc((void**)&h->d_stage, c.stage));
+      HIP_OK(hipMalloc((void**)&w.cs, c.ecs + 256));
+      HIP_OK(hipMalloc((void**)&w.tile_cnt, c.tiles * 4 * sizeof(int32_t)));
+      HIP_OK(hipMalloc((void**)&w.slen, n * sizeof(uint32_t)));
+      HIP_OK(hipMalloc((void**)&w.err, n * sizeof(int32_t)));
+      HIP_OK(hipMalloc((void**)&w.ok, n * sizeof(int32_t)));
+      HIP_OK(hipMalloc((void**)&w.seg_start, c.segs * sizeof(uint32_t)));
+      HIP_OK(hipMalloc((void**)&w.seg_cnt, c.segs * sizeof(uint32_t)));
+      HIP_OK(hipMalloc((void**)&w.cstart, c.chunks * sizeof(uint64_t)));
+      HIP_OK(hipMalloc((void**)&w.cexit, c.chunks * sizeof(uint64_t)));
+      HIP_OK(hipMalloc((void**)&w.ccnt, c.chunks * sizeof(uint32_t)));
+      HIP_OK(hipMalloc((void**)&w.coef, c.blocks * 64 * sizeof(int16_t)));
+      HIP_OK(hipMalloc((void**)&w.plane, c.plane));
       HIP_OK(hipEventCreateWithFlags(&h->staged, hipEventDisableTiming));
     } catch (...) {
       destroy(h);
@@ -996,170 +731,49 @@ MTGV_API int mtgv_jpeg_decode(mtgv_jpeg_decoder* h, const uint8_t* data_host, co
                               void* stream) {
   return guarded([&] {
     MTGV_CHECK(h != nullptr, ERR_INVALID, "null decoder");
-    MTGV_CHECK(n >= 0 && n <= h->max_images, ERR_INVALID, "jpeg: %d images, the decoder holds at most %d", n, h->max_images);
+    MTGV_CHECK(n >= 0 && n <= h->caps.max_images, ERR_INVALID, "jpeg: %d images, the decoder holds at most %d", n, h->caps.max_images);
     if (n == 0) return;
     MTGV_CHECK(data_host && offsets && sizes && dst_dev && dst_offset && dst_pitch && status_dev, ERR_INVALID, "null argument");
     hipStream_t s = (hipStream_t)stream;
-    // ---- parse every image before touching the staging buffer or launching anything
-    std::vector<Parsed> ps(n);
-    int64_t in_bytes = 0, pix = 0;
-    for (int i = 0; i < n; ++i) {
-      MTGV_CHECK(sizes[i] >= 0 && offsets[i] >= 0, ERR_INVALID, "jpeg: image %d: negative offset or size", i);
-      try {
-        parse(data_host + offsets[i], sizes[i], ps[i]);
-      } catch (const Error& e) {
-        throw Error(e.code, std::string(e.what()) + " (image " + std::to_string(i) + ")");
-      }
-      MTGV_CHECK(ps[i].supported, ERR_INVALID, "jpeg: image %d unsupported: %s", i, ps[i].why.c_str());
-      in_bytes += sizes[i];
-      MTGV_CHECK(dst_pitch[i] >= 3ll * ps[i].w && dst_offset[i] >= 0, ERR_INVALID, "jpeg: image %d: pitch %lld < 3 * width %d", i,
-                 (long long)dst_pitch[i], ps[i].w);
-    }
-    MTGV_CHECK(in_bytes <= h->max_bytes, ERR_INVALID, "jpeg: batch of %lld bytes, the decoder holds at most %lld", (long long)in_bytes,
-               (long long)h->max_bytes);
-    // ---- descriptors, Huffman tables (deduplicated), ragged bases
-    std::vector<ImgDesc> ds(n);
-    std::vector<HuffTab> tabs;
-    std::map<std::string, int> tab_ix;
-    std::vector<int64_t> bases(5 * (size_t)(n + 1), 0);
-    int64_t* cb = bases.data();
-    int64_t* bb = cb + (n + 1);
-    int64_t* sb = bb + (n + 1);
-    int64_t* tb = sb + (n + 1);
-    int64_t* pb = tb + (n + 1);
-    int64_t ecs_off = 0, plane_off = 0;
-    auto table = [&](const uint8_t* bits, const uint8_t* val) {
-      std::string key((const char*)bits, 17);
-      key.append((const char*)val, 256);
-      auto it = tab_ix.find(key);
-      if (it != tab_ix.end()) return it->second;
-      HuffTab t;
-      memset(&t, 0, sizeof(t));
-      memcpy(t.val, val, 256);
-      huff_codes(bits, t.maxcode, t.valoff, t.lut, val);
-      t.maxcode[0] = -1;
-      tabs.push_back(t);
-      return tab_ix[key] = (int)tabs.size() - 1;
-    };
-    for (int i = 0; i < n; ++i) {
-      const Parsed& p = ps[i];
-      ImgDesc& D = ds[i];
-      memset(&D, 0, sizeof(D));
-      D.h = p.h;
-      D.w = p.w;
-      D.ncomp = p.ncomp;
-      D.mode = p.ncomp == 1 ? 0 : p.sampling == 444 ? 1 : p.sampling == 422 ? 2 : 3;
-      const int hm = p.ncomp == 1 ? 1 : p.comp[0].h, vm = p.ncomp == 1 ? 1 : p.comp[0].v;
-      D.mcux = ceil_div(p.w, 8 * hm);
-      D.mcuy = ceil_div(p.h, 8 * vm);
-      const int64_t nmcu = (int64_t)D.mcux * D.mcuy;
-      D.ri = p.ri ? p.ri : (int)std::min<int64_t>(nmcu, 1 << 30);
-      D.nseg = (int)ceil_div64(nmcu, D.ri);
-      MTGV_CHECK(2 * (int64_t)(D.nseg - 1) <= p.ecs_len, ERR_INVALID,
-                 "jpeg: image %d: %d restart intervals cannot fit in %lld bytes of entropy-coded data", i, D.nseg, (long long)p.ecs_len);
-      D.bpm = 0;
-      for (int c = 0; c < p.ncomp; ++c) {
-        const int ch = p.ncomp == 1 ? 1 : p.comp[c].h, cv = p.ncomp == 1 ? 1 : p.comp[c].v;
-        CompDesc& C = D.c[c];
-        memcpy(C.q, p.qt[p.comp[c].tq], sizeof(C.q));
-        C.dc = table(p.hbits[0][p.comp[c].td], p.hval[0][p.comp[c].td]);
-        C.ac = table(p.hbits[1][p.comp[c].ta], p.hval[1][p.comp[c].ta]);
-        C.h = ch;
-        C.v = cv;
-        C.bw = D.mcux * ch;
-        C.bh = D.mcuy * cv;
-        C.plane = plane_off;
-        plane_off += (int64_t)C.bw * 8 * C.bh * 8;
-        for (int y = 0; y < cv; ++y)
-          for (int x = 0; x < ch; ++x, ++D.bpm) {
-            D.bcomp[D.bpm] = (int8_t)c;
-            D.bdx[D.bpm] = (int8_t)x;
-            D.bdy[D.bpm] = (int8_t)y;
-          }
-      }
-      D.nblocks = nmcu * D.bpm;
-      D.ecs = ecs_off;
-      D.ecs_len = p.ecs_len;
-      ecs_off += align_up(p.ecs_len, 8) + 8;
-      D.nchunks = (int)std::max<int64_t>(1, ceil_div64(p.ecs_len, CHUNK_BYTES));
-      D.ntiles = (int)std::max<int64_t>(1, ceil_div64(p.ecs_len, TILE_BYTES));
-      D.chunk0 = cb[i];
-      D.seg0 = sb[i];
-      D.tile0 = tb[i];
-      D.blk0 = bb[i];
-      D.pix0 = pb[i];
-      D.dst_off = dst_offset[i];
-      D.pitch = dst_pitch[i];
-      cb[i + 1] = cb[i] + D.nchunks;
-      bb[i + 1] = bb[i] + D.nblocks;
-      sb[i + 1] = sb[i] + D.nseg;
-      tb[i + 1] = tb[i] + D.ntiles;
-      pb[i + 1] = pb[i] + (int64_t)p.h * p.w;
-      pix += (int64_t)D.mcux * 8 * hm * D.mcuy * 8 * vm;
-    }
-    MTGV_CHECK(pix <= h->max_pixels, ERR_INVALID, "jpeg: batch needs %lld pixels padded to whole MCUs, the decoder holds %lld",
-               (long long)pix, (long long)h->max_pixels);
-    MTGV_CHECK(bb[n] <= h->cap_blocks && plane_off <= h->cap_plane && cb[n] <= h->cap_chunks && tb[n] <= h->cap_tiles &&
-                   sb[n] <= h->cap_segs && ecs_off <= h->max_bytes + 16ll * h->max_images,
-               ERR_INVALID, "jpeg: batch exceeds the decoder's workspace");
-    // ---- staging layout: descriptors | tables | bases | entropy-coded bytes
-    const int64_t o_tab = align_up((int64_t)n * sizeof(ImgDesc), 256);
-    const int64_t o_base = o_tab + align_up((int64_t)tabs.size() * sizeof(HuffTab), 256);
-    const int64_t o_ecs = o_base + align_up((int64_t)bases.size() * 8, 256);
-    const int64_t total = o_ecs + ecs_off;
-    MTGV_CHECK(total <= h->cap_stage, ERR_RUNTIME, "jpeg: staging overflow (%lld > %lld)", (long long)total, (long long)h->cap_stage);
-    if (h->pending) HIP_OK(hipEventSynchronize(h->staged));  // the previous upload has left the pinned buffer
+    // ---- plan: every image parsed and the whole batch checked before the staging buffer is touched or anything launched
+    const DecodePlan plan = plan_decode(h->caps, data_host, offsets, sizes, n, dst_offset, dst_pitch);
+    // ---- the previous upload has left the pinned buffer
+    if (h->pending) HIP_OK(hipEventSynchronize(h->staged));
     h->pending = false;
-    uint8_t* st = h->h_stage;
-    memcpy(st, ds.data(), n * sizeof(ImgDesc));
-    memcpy(st + o_tab, tabs.data(), tabs.size() * sizeof(HuffTab));
-    memcpy(st + o_base, bases.data(), bases.size() * 8);
-    for (int i = 0; i < n; ++i) {
-      memcpy(st + o_ecs + ds[i].ecs, data_host + offsets[i] + ps[i].ecs, ps[i].ecs_len);
-      memset(st + o_ecs + ds[i].ecs + ps[i].ecs_len, 0, align_up(ps[i].ecs_len, 8) + 8 - ps[i].ecs_len);
-    }
-    HIP_OK(hipMemcpyAsync(h->d_stage, st, total, hipMemcpyHostToDevice, s));
+    // ---- stage, copy
+    stage(plan, data_host, offsets, h->h_stage);
+    HIP_OK(hipMemcpyAsync(h->d_stage, h->h_stage, plan.total, hipMemcpyHostToDevice, s));
     HIP_OK(hipEventRecord(h->staged, s));
     h->pending = true;
-    HIP_OK(hipMemsetAsync(h->d_err, 0, n * sizeof(int32_t), s));
-    HIP_OK(hipMemsetAsync(h->d_segcnt, 0, sb[n] * sizeof(uint32_t), s));
+    const int64_t nch = plan.cb()[n], nblk = plan.bb()[n], nseg = plan.sb()[n], ntile = plan.tb()[n], npix = plan.pb()[n];
+    HIP_OK(hipMemsetAsync(h->work.err, 0, n * sizeof(int32_t), s));
+    HIP_OK(hipMemsetAsync(h->work.seg_cnt, 0, nseg * sizeof(uint32_t), s));
+    // ---- launch
     Params P;
-    P.d = (const ImgDesc*)h->d_stage;
-    P.tabs = (const HuffTab*)(h->d_stage + o_tab);
-    const int64_t* db = (const int64_t*)(h->d_stage + o_base);
-    P.chunk_base = db;
-    P.blk_base = db + (n + 1);
-    P.seg_base = db + 2 * (n + 1);
-    P.tile_base = db + 3 * (n + 1);
-    P.pix_base = db + 4 * (n + 1);
-    P.ecs = h->d_stage + o_ecs;
-    P.n = n;
-    P.cs = h->d_cs;
-    P.tile_cnt = h->d_tile;
-    P.slen = h->d_slen;
-    P.err = h->d_err;
-    P.ok = h->d_ok;
-    P.seg_start = h->d_seg;
-    P.seg_cnt = h->d_segcnt;
-    P.cstart = h->d_cstart;
-    P.cexit = h->d_cexit;
-    P.ccnt = h->d_ccnt;
-    P.coef = h->d_coef;
-    P.plane = h->d_plane;
+    const int64_t* db = (const int64_t*)(h->d_stage + plan.o_base);
+    static_cast<Staged&>(P) = {(const ImgDesc*)h->d_stage,
+                               (const HuffTab*)(h->d_stage + plan.o_tab),
+                               db,
+                               db + (n + 1),
+                               db + 2 * (n + 1),
+                               db + 3 * (n + 1),
+                               db + 4 * (n + 1),
+                               h->d_stage + plan.o_ecs,
+                               n};
+    static_cast<Work&>(P) = h->work;
     P.dst = dst_dev;
     P.status = status_dev;
-    const int64_t nch = cb[n];
-    hipLaunchKernelGGL(unstuff_count_kernel, dim3((unsigned)tb[n]), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(unstuff_count_kernel, dim3((unsigned)ntile), dim3(256), 0, s, P);
     hipLaunchKernelGGL(unstuff_scan_kernel, dim3(ceil_div(n, 64)), dim3(64), 0, s, P);
-    hipLaunchKernelGGL(unstuff_scatter_kernel, dim3((unsigned)tb[n]), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(unstuff_scatter_kernel, dim3((unsigned)ntile), dim3(256), 0, s, P);
     hipLaunchKernelGGL(sync_kernel, dim3((unsigned)ceil_div64(nch, SYNC_WG)), dim3(SYNC_WG), 0, s, P, nch);
     hipLaunchKernelGGL(sync_fix_kernel, dim3(ceil_div(n, 64)), dim3(64), 0, s, P);
     hipLaunchKernelGGL(count_kernel, dim3((unsigned)ceil_div64(nch, 256)), dim3(256), 0, s, P, nch);
     hipLaunchKernelGGL(verify_kernel, dim3(n), dim3(64), 0, s, P);
     hipLaunchKernelGGL(write_kernel, dim3((unsigned)ceil_div64(nch, 256)), dim3(256), 0, s, P, nch);
-    hipLaunchKernelGGL(dc_kernel, dim3((unsigned)sb[n]), dim3(256), 0, s, P);
-    hipLaunchKernelGGL(idct_kernel, dim3((unsigned)ceil_div64(bb[n], 32)), dim3(256), 0, s, P, bb[n]);
-    hipLaunchKernelGGL(color_kernel, dim3((unsigned)ceil_div64(pb[n], 256)), dim3(256), 0, s, P, pb[n]);
+    hipLaunchKernelGGL(dc_kernel, dim3((unsigned)nseg), dim3(256), 0, s, P);
+    hipLaunchKernelGGL(idct_kernel, dim3((unsigned)ceil_div64(nblk, 32)), dim3(256), 0, s, P, nblk);
+    hipLaunchKernelGGL(color_kernel, dim3((unsigned)ceil_div64(npix, 256)), dim3(256), 0, s, P, npix);
     HIP_OK(hipGetLastError());
   });
 }

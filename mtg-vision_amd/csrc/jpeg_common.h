@@ -1,5 +1,5 @@
-// Pieces shared by the JPEG decoder (jpeg.hip) and encoder (jpeg_enc.hip): the zig-zag order and the scans that the
-// ragged / prefix-sum launches of both are built from.
+// Device pieces shared by the JPEG decoder (jpeg.hip) and encoder (jpeg_enc.hip): the zig-zag order and the scans that
+// the ragged / prefix-sum launches of both are built from.  (The host side's zig-zag table is in jpeg_tables.h.)
 #pragma once
 
 #include <stdint.h>
@@ -12,9 +12,6 @@ namespace {
 __constant__ uint8_t k_natural[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
                                       41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
                                       30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
-const uint8_t h_natural[64] = {0,  1,  8,  16, 9,  2,  3,  10, 17, 24, 32, 25, 18, 11, 4,  5,  12, 19, 26, 33, 40, 48,
-                               41, 34, 27, 20, 13, 6,  7,  14, 21, 28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23,
-                               30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63};
 
 __device__ inline int find_base(const int64_t* base, int n, int64_t x) {  // largest i < n with base[i] <= x
   int lo = 0, hi = n - 1;

@@ -21,59 +21,30 @@
 // The bit stream must be zero where `write` ORs into it.  It is cleared once when the handle is created and `scatter`
 // clears every word a call wrote, so no call needs a clearing launch.  Workspaces are sized at creation; per-call
 // parameters (geometry, the two scaled quantisation tables, the header bytes) travel as kernel arguments.
+//
+// The host arithmetic behind those parameters (geometry, bounds, scaled tables, header) is in jpeg_host.h /
+// jpeg_host.cpp, their records in jpeg_desc.h and the Annex K tables in jpeg_tables.h, all without HIP; this file
+// keeps the kernels, the handle and the C ABI.
 #include <string.h>
 
-#include <string>
-#include <vector>
+#include <algorithm>
 
 #include "common.h"
 #include "jpeg_common.h"
+#include "jpeg_host.h"
+#include "jpeg_tables.h"
 #include "mtgv.h"
 
 using namespace mtgv;
+using jpeg::HDR_BYTES;
+using jpeg::MAX_BLOCK_BITS;
+using jpeg::TILE;
 
 namespace {
 
-constexpr int MAX_BLOCK_BITS = 1660;  // DC: 11-bit chroma code + 11 bits; 63 AC: 16-bit code + 10 bits each
-constexpr int TILE = 4096;            // bytes of the byte stage per workgroup: 256 threads x 16
-constexpr int HDR_BYTES = 623;        // SOI .. SOS with two DQT and four DHT markers (same for both samplings)
-constexpr int MAX_TILE_WG = 2048;     // workgroups of the ff / scatter launches (they stride over the tiles)
+constexpr int MAX_TILE_WG = 2048;  // workgroups of the ff / scatter launches (they stride over the tiles)
 
-// ---------------------------------------------------------------------------------------------------------------------
-// Annex K tables (jcparam.c / jstdhuff.c)
-
-constexpr uint8_t k_basic_q[2][64] = {
-    {16, 11, 10, 16, 24,  40,  51,  61,  12, 12, 14, 19, 26,  58,  60,  55,  14, 13, 16, 24, 40,  57,  69,  56,
-     14, 17, 22, 29, 51,  87,  80,  62,  18, 22, 37, 56, 68,  109, 103, 77,  24, 35, 55, 64, 81,  104, 113, 92,
-     49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99},
-    {17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99, 47, 66, 99, 99,
-     99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99, 99,
-     99, 99, 99, 99, 99, 99, 99, 99}};
-
-// code counts per length 1..16 (index 0 unused): DC luma, AC luma, DC chroma, AC chroma
-constexpr uint8_t k_bits[4][17] = {{0, 0, 1, 5, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0, 0, 0},
-                                   {0, 0, 2, 1, 3, 3, 2, 4, 3, 5, 5, 4, 4, 0, 0, 1, 0x7d},
-                                   {0, 0, 3, 1, 1, 1, 1, 1, 1, 1, 1, 1, 0, 0, 0, 0, 0},
-                                   {0, 0, 2, 1, 2, 4, 4, 3, 4, 7, 5, 4, 4, 0, 1, 2, 0x77}};
-constexpr uint8_t k_val_dc[12] = {0, 1, 2, 3, 4, 5, 6, 7, 8, 9, 10, 11};
-constexpr uint8_t k_val_ac[2][162] = {
-    {0x01, 0x02, 0x03, 0x00, 0x04, 0x11, 0x05, 0x12, 0x21, 0x31, 0x41, 0x06, 0x13, 0x51, 0x61, 0x07, 0x22, 0x71, 0x14, 0x32, 0x81,
-     0x91, 0xa1, 0x08, 0x23, 0x42, 0xb1, 0xc1, 0x15, 0x52, 0xd1, 0xf0, 0x24, 0x33, 0x62, 0x72, 0x82, 0x09, 0x0a, 0x16, 0x17, 0x18,
-     0x19, 0x1a, 0x25, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x34, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47, 0x48,
-     0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74, 0x75,
-     0x76, 0x77, 0x78, 0x79, 0x7a, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97, 0x98, 0x99,
-     0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba, 0xc2, 0xc3,
-     0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe1, 0xe2, 0xe3, 0xe4, 0xe5,
-     0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf1, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa},
-    {0x00, 0x01, 0x02, 0x03, 0x11, 0x04, 0x05, 0x21, 0x31, 0x06, 0x12, 0x41, 0x51, 0x07, 0x61, 0x71, 0x13, 0x22, 0x32, 0x81, 0x08,
-     0x14, 0x42, 0x91, 0xa1, 0xb1, 0xc1, 0x09, 0x23, 0x33, 0x52, 0xf0, 0x15, 0x62, 0x72, 0xd1, 0x0a, 0x16, 0x24, 0x34, 0xe1, 0x25,
-     0xf1, 0x17, 0x18, 0x19, 0x1a, 0x26, 0x27, 0x28, 0x29, 0x2a, 0x35, 0x36, 0x37, 0x38, 0x39, 0x3a, 0x43, 0x44, 0x45, 0x46, 0x47,
-     0x48, 0x49, 0x4a, 0x53, 0x54, 0x55, 0x56, 0x57, 0x58, 0x59, 0x5a, 0x63, 0x64, 0x65, 0x66, 0x67, 0x68, 0x69, 0x6a, 0x73, 0x74,
-     0x75, 0x76, 0x77, 0x78, 0x79, 0x7a, 0x82, 0x83, 0x84, 0x85, 0x86, 0x87, 0x88, 0x89, 0x8a, 0x92, 0x93, 0x94, 0x95, 0x96, 0x97,
-     0x98, 0x99, 0x9a, 0xa2, 0xa3, 0xa4, 0xa5, 0xa6, 0xa7, 0xa8, 0xa9, 0xaa, 0xb2, 0xb3, 0xb4, 0xb5, 0xb6, 0xb7, 0xb8, 0xb9, 0xba,
-     0xc2, 0xc3, 0xc4, 0xc5, 0xc6, 0xc7, 0xc8, 0xc9, 0xca, 0xd2, 0xd3, 0xd4, 0xd5, 0xd6, 0xd7, 0xd8, 0xd9, 0xda, 0xe2, 0xe3, 0xe4,
-     0xe5, 0xe6, 0xe7, 0xe8, 0xe9, 0xea, 0xf2, 0xf3, 0xf4, 0xf5, 0xf6, 0xf7, 0xf8, 0xf9, 0xfa}};
-
+// the Annex K Huffman tables (jpeg_tables.h) as codes
 struct HuffEnc {
   uint32_t dc[2][12];   // (code << 8) | length, by category; [0] luma, [1] chroma
   uint32_t ac[2][256];  // by run/size symbol; 0 where the table has no code
@@ -83,13 +54,13 @@ constexpr HuffEnc make_huff() {
   HuffEnc t{};
   for (int c = 0; c < 2; ++c) {
     for (int ac = 0; ac < 2; ++ac) {
-      const uint8_t* bits = k_bits[2 * c + ac];
+      const uint8_t* bits = jpeg::k_bits[2 * c + ac];
       uint32_t code = 0;
       int k = 0;
       for (int l = 1; l <= 16; ++l) {
         for (int j = 0; j < bits[l]; ++j, ++code, ++k) {
-          if (ac) t.ac[c][k_val_ac[c][k]] = code << 8 | (uint32_t)l;
-          else t.dc[c][k_val_dc[k]] = code << 8 | (uint32_t)l;
+          if (ac) t.ac[c][jpeg::k_val_ac[c][k]] = code << 8 | (uint32_t)l;
+          else t.dc[c][jpeg::k_val_dc[k]] = code << 8 | (uint32_t)l;
         }
         code <<= 1;
       }
@@ -100,25 +71,11 @@ constexpr HuffEnc make_huff() {
 
 __constant__ HuffEnc k_huff = make_huff();
 
-// ---------------------------------------------------------------------------------------------------------------------
-// per-call parameters (kernel arguments)
-
-struct Geo {
-  int32_t n, h, w, s420;  // s420: 1 for 4:2:0, 0 for 4:4:4
-  int32_t bpm, mcux;      // blocks per MCU, MCUs across
-  int32_t wb, hb;         // luma plane in blocks (4:2:0 luma blocks past it are dummy blocks)
-  int32_t tpi, hlen;      // byte tiles per image (worst case), header bytes
-  int64_t bpi;            // blocks per image
-  int64_t words;          // bit-stream words per image (tpi * TILE / 4)
-};
-
-struct QTab {
-  uint8_t q[2][64];  // scaled quantisation tables, natural order: [0] luma, [1] chroma
-};
-
-struct Hdr {
-  uint8_t b[HDR_BYTES];
-};
+// per-call parameters (kernel arguments): the records of jpeg_desc.h under this file's own names, which the kernels'
+// symbols carry
+struct Geo : jpeg::Geo {};
+struct QTab : jpeg::QTab {};
+struct Hdr : jpeg::Hdr {};
 
 struct Work {
   int16_t* coef;      // 64 per block, zig-zag order
@@ -129,6 +86,7 @@ struct Work {
   int32_t* tile_ff;   // 0xFF bytes per tile
   int64_t* tile_out;  // output position of each tile's first byte
 };
+
 
 // ---------------------------------------------------------------------------------------------------------------------
 // fdct
@@ -499,108 +457,20 @@ __global__ __launch_bounds__(256) void scatter_kernel(Geo g, Hdr hdr, uint32_t* 
   }
 }
 
-// ---------------------------------------------------------------------------------------------------------------------
-// host
-
-void check_geometry(int32_t h, int32_t w, int32_t sampling) {
-  MTGV_CHECK(h >= 1 && w >= 1 && h <= 65535 && w <= 65535, ERR_INVALID, "jpeg: image size %dx%d outside 1..65535", h, w);
-  MTGV_CHECK(sampling == 420 || sampling == 444, ERR_INVALID, "jpeg: sampling %d not supported (420 or 444)", sampling);
-}
-
-void check_quality(int32_t quality) { MTGV_CHECK(quality >= 1 && quality <= 100, ERR_INVALID, "jpeg: quality %d outside 1..100", quality); }
-
-Geo geometry(int32_t h, int32_t w, int32_t sampling) {
-  Geo g{};
-  g.h = h;
-  g.w = w;
-  g.s420 = sampling == 420;
-  g.bpm = g.s420 ? 6 : 3;
-  const int mcu = g.s420 ? 16 : 8;
-  g.mcux = ceil_div(w, mcu);
-  const int mcuy = ceil_div(h, mcu);
-  g.wb = ceil_div(w, 8);
-  g.hb = ceil_div(h, 8);
-  g.bpi = (int64_t)g.mcux * mcuy * g.bpm;
-  const int64_t ebytes = ceil_div64(g.bpi * MAX_BLOCK_BITS, 8);  // entropy-coded bytes before stuffing, at most
-  g.tpi = (int)ceil_div64(ebytes, TILE);
-  g.words = (int64_t)g.tpi * (TILE / 4);
-  g.hlen = HDR_BYTES;
-  return g;
-}
-
-// pixels of one image once padded to whole MCUs
-int64_t padded_pixels(const Geo& g) { return g.bpi / g.bpm * (g.s420 ? 256 : 64); }
-
-int64_t bound_of(const Geo& g) { return HDR_BYTES + 2 * ceil_div64(g.bpi * MAX_BLOCK_BITS, 8) + 2; }
-
-void scaled_tables(int quality, uint8_t q[2][64]) {  // jpeg_quality_scaling + jpeg_add_quant_table(force_baseline)
-  const int scale = quality < 50 ? 5000 / quality : 200 - 2 * quality;
-  for (int t = 0; t < 2; ++t)
-    for (int k = 0; k < 64; ++k) q[t][k] = (uint8_t)std::min(std::max((k_basic_q[t][k] * scale + 50) / 100, 1), 255);
-}
-
-// jcmarker.c with libjpeg's defaults: SOI, JFIF APP0, DQT 0, DQT 1, SOF0, DHT DC0 AC0 DC1 AC1, SOS
-void build_header(int32_t h, int32_t w, int32_t quality, int32_t sampling, uint8_t* o) {
-  uint8_t q[2][64];
-  scaled_tables(quality, q);
-  int p = 0;
-  auto b1 = [&](int v) { o[p++] = (uint8_t)v; };
-  auto b2 = [&](int v) {
-    b1(v >> 8);
-    b1(v & 255);
-  };
-  b2(0xFFD8);
-  b2(0xFFE0);
-  b2(16);
-  for (char c : {'J', 'F', 'I', 'F', '\0'}) b1(c);
-  b1(1), b1(1), b1(0), b2(1), b2(1), b1(0), b1(0);  // version 1.01, units 0, density 1 x 1, no thumbnail
-  for (int t = 0; t < 2; ++t) {
-    b2(0xFFDB);
-    b2(67);
-    b1(t);
-    for (int k = 0; k < 64; ++k) b1(q[t][h_natural[k]]);
-  }
-  b2(0xFFC0);
-  b2(17);
-  b1(8), b2(h), b2(w), b1(3);
-  b1(1), b1(sampling == 420 ? 0x22 : 0x11), b1(0);
-  b1(2), b1(0x11), b1(1);
-  b1(3), b1(0x11), b1(1);
-  for (int t = 0; t < 4; ++t) {  // DC0, AC0, DC1, AC1
-    const int c = t >> 1, ac = t & 1, nv = ac ? 162 : 12;
-    b2(0xFFC4);
-    b2(2 + 17 + nv);
-    b1(ac << 4 | c);
-    for (int l = 1; l <= 16; ++l) b1(k_bits[t][l]);
-    for (int k = 0; k < nv; ++k) b1(ac ? k_val_ac[c][k] : k_val_dc[k]);
-  }
-  b2(0xFFDA);
-  b2(12);
-  b1(3);
-  b1(1), b1(0x00), b1(2), b1(0x11), b1(3), b1(0x11);
-  b1(0), b1(63), b1(0);
-  if (p != HDR_BYTES) throw Error(ERR_RUNTIME, "jpeg: header of " + std::to_string(p) + " bytes");
-}
-
 }  // namespace
 
 struct mtgv_jpeg_encoder {
   int max_images;
   int64_t max_pixels;
   int64_t cap_blocks, cap_stream_words, cap_tiles;
-  int16_t* d_coef = nullptr;
-  uint32_t* d_bits = nullptr;
-  uint64_t* d_boff = nullptr;
-  uint64_t* d_nbits = nullptr;
-  uint32_t* d_stream = nullptr;
-  int32_t* d_tile_ff = nullptr;
-  int64_t* d_tile_out = nullptr;
+  Work work = {};
 };
 
 namespace {
 void destroy_enc(mtgv_jpeg_encoder* h) {
   if (!h) return;
-  void* dev[] = {h->d_coef, h->d_bits, h->d_boff, h->d_nbits, h->d_stream, h->d_tile_ff, h->d_tile_out};
+  const Work& w = h->work;
+  void* dev[] = {w.coef, w.bits, w.boff, w.nbits, w.stream, w.tile_ff, w.tile_out};
   for (void* p : dev)
     if (p) (void)hipFree(p);
   delete h;
@@ -610,8 +480,8 @@ void destroy_enc(mtgv_jpeg_encoder* h) {
 MTGV_API int mtgv_jpeg_encode_bound(int32_t h, int32_t w, int32_t sampling, int64_t* nbytes) {
   return guarded([&] {
     MTGV_CHECK(nbytes != nullptr, ERR_INVALID, "null nbytes");
-    check_geometry(h, w, sampling);
-    *nbytes = bound_of(geometry(h, w, sampling));
+    jpeg::check_geometry(h, w, sampling);
+    *nbytes = jpeg::bound_of(jpeg::geometry(h, w, sampling));
   });
 }
 
@@ -619,10 +489,10 @@ MTGV_API int mtgv_jpeg_encode_header(int32_t h, int32_t w, int32_t quality, int3
                                      int64_t* nbytes) {
   return guarded([&] {
     MTGV_CHECK(out_host != nullptr && nbytes != nullptr, ERR_INVALID, "null argument");
-    check_geometry(h, w, sampling);
-    check_quality(quality);
+    jpeg::check_geometry(h, w, sampling);
+    jpeg::check_quality(quality);
     MTGV_CHECK(capacity >= HDR_BYTES, ERR_INVALID, "jpeg: header needs %d bytes, capacity %lld", HDR_BYTES, (long long)capacity);
-    build_header(h, w, quality, sampling, out_host);
+    jpeg::build_header(h, w, quality, sampling, out_host);
     *nbytes = HDR_BYTES;
   });
 }
@@ -642,15 +512,16 @@ MTGV_API int mtgv_jpeg_encoder_create(int32_t max_images, int64_t max_pixels, mt
     h->cap_blocks = 3 * ceil_div64(max_pixels, 64);
     h->cap_tiles = ceil_div64(ceil_div64(h->cap_blocks * MAX_BLOCK_BITS, 8), TILE) + max_images;
     h->cap_stream_words = h->cap_tiles * (TILE / 4);
+    Work& w = h->work;
     try {
-      HIP_OK(hipMalloc((void**)&h->d_coef, h->cap_blocks * 64 * sizeof(int16_t)));
-      HIP_OK(hipMalloc((void**)&h->d_bits, h->cap_blocks * sizeof(uint32_t)));
-      HIP_OK(hipMalloc((void**)&h->d_boff, h->cap_blocks * sizeof(uint64_t)));
-      HIP_OK(hipMalloc((void**)&h->d_nbits, max_images * sizeof(uint64_t)));
-      HIP_OK(hipMalloc((void**)&h->d_stream, h->cap_stream_words * sizeof(uint32_t)));
-      HIP_OK(hipMalloc((void**)&h->d_tile_ff, h->cap_tiles * sizeof(int32_t)));
-      HIP_OK(hipMalloc((void**)&h->d_tile_out, h->cap_tiles * sizeof(int64_t)));
-      HIP_OK(hipMemset(h->d_stream, 0, h->cap_stream_words * sizeof(uint32_t)));  // kept zero between calls (scatter)
+      HIP_OK(hipMalloc((void**)&w.coef, h->cap_blocks * 64 * sizeof(int16_t)));
+      HIP_OK(hipMalloc((void**)&w.bits, h->cap_blocks * sizeof(uint32_t)));
+      HIP_OK(hipMalloc((void**)&w.boff, h->cap_blocks * sizeof(uint64_t)));
+      HIP_OK(hipMalloc((void**)&w.nbits, max_images * sizeof(uint64_t)));
+      HIP_OK(hipMalloc((void**)&w.stream, h->cap_stream_words * sizeof(uint32_t)));
+      HIP_OK(hipMalloc((void**)&w.tile_ff, h->cap_tiles * sizeof(int32_t)));
+      HIP_OK(hipMalloc((void**)&w.tile_out, h->cap_tiles * sizeof(int64_t)));
+      HIP_OK(hipMemset(w.stream, 0, h->cap_stream_words * sizeof(uint32_t)));  // kept zero between calls (scatter)
       HIP_OK(hipDeviceSynchronize());
     } catch (...) {
       destroy_enc(h);
@@ -667,8 +538,8 @@ MTGV_API int mtgv_jpeg_encode(mtgv_jpeg_encoder* h, const uint8_t* src_dev, int3
   return guarded([&] {
     MTGV_CHECK(h != nullptr, ERR_INVALID, "null encoder");
     MTGV_CHECK(n >= 0 && n <= h->max_images, ERR_INVALID, "jpeg: %d images, the encoder holds at most %d", n, h->max_images);
-    check_geometry(height, width, sampling);
-    check_quality(quality);
+    jpeg::check_geometry(height, width, sampling);
+    jpeg::check_quality(quality);
     MTGV_CHECK(out_offsets_dev != nullptr, ERR_INVALID, "null out_offsets");
     hipStream_t s = (hipStream_t)stream;
     if (n == 0) {
@@ -676,21 +547,21 @@ MTGV_API int mtgv_jpeg_encode(mtgv_jpeg_encoder* h, const uint8_t* src_dev, int3
       return;
     }
     MTGV_CHECK(src_dev != nullptr && out_dev != nullptr, ERR_INVALID, "null argument");
-    Geo g = geometry(height, width, sampling);
+    Geo g{jpeg::geometry(height, width, sampling)};
     g.n = n;
-    const int64_t pix = n * padded_pixels(g);
+    const int64_t pix = n * jpeg::padded_pixels(g);
     MTGV_CHECK(pix <= h->max_pixels, ERR_INVALID, "jpeg: batch needs %lld pixels padded to whole MCUs, the encoder holds %lld",
                (long long)pix, (long long)h->max_pixels);
     const int64_t nblk = n * g.bpi, ntiles = (int64_t)n * g.tpi;
     MTGV_CHECK(nblk <= h->cap_blocks && ntiles <= h->cap_tiles, ERR_INVALID, "jpeg: batch exceeds the encoder's workspace");
-    const int64_t bound = bound_of(g);
+    const int64_t bound = jpeg::bound_of(g);
     MTGV_CHECK(out_capacity >= n * bound, ERR_INVALID, "jpeg: output capacity %lld < %d images x %lld bytes (mtgv_jpeg_encode_bound)",
                (long long)out_capacity, n, (long long)bound);
     QTab qt;
-    scaled_tables(quality, qt.q);
+    jpeg::scaled_tables(quality, qt.q);
     Hdr hdr;
-    build_header(height, width, quality, sampling, hdr.b);
-    Work W{h->d_coef, h->d_bits, h->d_boff, h->d_nbits, h->d_stream, h->d_tile_ff, h->d_tile_out};
+    jpeg::build_header(height, width, quality, sampling, hdr.b);
+    const Work& W = h->work;
     const unsigned tile_wg = (unsigned)std::min<int64_t>(ntiles, MAX_TILE_WG);
     hipLaunchKernelGGL(fdct_kernel, dim3((unsigned)ceil_div64(nblk, 32)), dim3(256), 0, s, g, qt, src_dev, W.coef, nblk);
     hipLaunchKernelGGL(count_kernel, dim3((unsigned)ceil_div64(nblk, 4)), dim3(256), 0, s, g, W.coef, W.bits, nblk);
