@@ -536,6 +536,60 @@ MTGV_API int mtgv_op_block(const float* x_dev, float* out_dev, int32_t n, int32_
 MTGV_API int64_t mtgv_op_block_workspace_floats(int32_t n, int32_t h, int32_t w, int32_t c);
 MTGV_API int mtgv_op_l2norm(const float* x_dev, float* out_dev, int64_t rows, int32_t d, void* stream);
 
+/* ---- tracker (version 104): the temporal logic of mtgvision/server.py:100-106, :133-207 for `streams` independent cameras,
+ * state on the device.  Per stream it is mtgv/tracker.py's KalmanPointTracker (norfair.Tracker(mean_euclidean, 300,
+ * hit_counter_max 5, initialization_delay 2) restated: parity with norfair itself is unpinned, as for the host class)
+ * followed by TrackerCtx's gating: a track is embedded when it is new or update_wait_sec have passed, an exponentially
+ * weighted mean of its embeddings queries the bank, the last top_k matches stay on the track.  Filter state is fp64 and the
+ * arithmetic is the host class's, operation for operation (no FMA contraction): ids, due sets and filter state are equal.
+ * Caps the host class does not have: at most max_tracks (<= 64) live tracks per stream - a detection that finds no free slot
+ * is dropped and counted - at most 16 cards per frame, and every stream at most once per update.
+ * Zero in a policy field selects the reference's value (300, 5, 2, 1, 0.5 s, 0.1).  To run without an initialisation delay
+ * pass initialization_delay = -1 (an id at creation); a negative update_wait_sec makes every reported track due. */
+typedef struct {
+  int32_t streams;         /* S >= 1 */
+  int32_t max_tracks;      /* T, 1..64 slots per stream */
+  int32_t cards_per_frame; /* K, 1..16 */
+  int32_t dim;             /* embedding size */
+  int32_t top_k;           /* 1..8 matches kept per track */
+  int32_t hit_counter_max, initialization_delay, period;
+  double distance_threshold, update_wait_sec, ewma_weight;
+} mtgv_tracker_cfg;
+typedef struct mtgv_tracker mtgv_tracker;
+/* Anything out of range: status 1, checked before the first HIP call (needs no device). */
+MTGV_API int mtgv_tracker_create(const mtgv_tracker_cfg* cfg, mtgv_tracker** out);
+MTGV_API void mtgv_tracker_destroy(mtgv_tracker* h);
+/* forget the tracks of one stream, or of all (-1): ids start again at 1.  Asynchronous on `stream`. */
+MTGV_API int mtgv_tracker_reset(mtgv_tracker* h, int32_t stream_or_minus_1, void* stream);
+/* One step: frame f (quads (frames, K, 4, 2) f32, pixels) belongs to stream stream_of_frame_host[f] - distinct values in
+ * [0, S), else status 1 - and was taken at now_host[f] seconds.  Slot k of frame f is a detection iff k < min(n_det[f], K)
+ * (n_det given) and state[f][k] > 0 (state given); at least one of the two.  The valid slots in ascending k are the frame's
+ * detection list.  Writes track_id (frames, K): the id of the initialised track matched to the slot, 0 none; due_idx
+ * (frames * K): the flat indices f K + k of the slots whose track is due, ascending, -1 behind them; n_due: their count.
+ * The host arrays are read before the call returns; nothing is copied and the stream is not synchronised.  due_idx_dev and
+ * n_due_dev must stay valid until the step's commit / store have run. */
+MTGV_API int mtgv_tracker_update(mtgv_tracker* h, const float* quads_dev, const int32_t* n_det_dev, const int32_t* state_dev, int32_t frames,
+                                 const int32_t* stream_of_frame_host, const double* now_host, int32_t* track_id_dev, int32_t* due_idx_dev,
+                                 int32_t* n_due_dev, void* stream);
+/* dst row r = src row due_idx[r] for r < min(n_due, max_rows), rows of row_bytes bytes; indices outside [0, src_rows) are
+ * skipped.  n_due is read on the device: launched over max_rows rows, nothing written when it is 0. */
+MTGV_API int mtgv_tracker_gather_u8(const uint8_t* src_dev, int64_t src_rows, int64_t row_bytes, const int32_t* due_idx_dev,
+                                    const int32_t* n_due_dev, int32_t max_rows, uint8_t* dst_dev, void* stream);
+/* z (rows, dim): the embeddings of the due slots in due_idx order.  avg = w z + (1 - w) avg in f32 (the first time avg = z,
+ * then the same formula); q (rows, dim) receives the averaged vectors, the queries of the match.  n_due is read on the
+ * device and min(n_due, rows) rows are processed: rows is what the buffers hold (n_due, or frames * K without the count). */
+MTGV_API int mtgv_tracker_commit(mtgv_tracker* h, const float* z_dev, float* q_dev, int32_t rows, void* stream);
+/* ids / scores (rows, top_k): the matches of q, rows as in commit.  They are kept on the due tracks; then every slot of the step with a track id
+ * emits its track's kept matches into out_ids (frames, K, top_k) / out_scores - a track that was not due its older ones - and
+ * a slot without a track -1 / -inf.  rows 0 (nothing was due): ids_dev / scores_dev may be NULL. */
+MTGV_API int mtgv_tracker_store(mtgv_tracker* h, const int64_t* ids_dev, const float* scores_dev, int32_t rows, int64_t* out_ids_dev,
+                                float* out_scores_dev, void* stream);
+/* Test surface: one stream's slots on the host (synchronises).  Any output may be NULL.  kal (40, T): rows 8 c + j = position,
+ * velocity, pp, pv, vv (c) of corner coordinate j; ints (6, T): live, hit_counter, is_initializing, id, birth, has_z;
+ * last_update (T); avg_z (T, dim); match_ids / match_scores (T, top_k); counters (4): next_id, next_birth, overflow, 0. */
+MTGV_API int mtgv_tracker_get_state(mtgv_tracker* h, int32_t stream_index, double* kal_host, int32_t* ints_host, double* last_update_host,
+                                    float* avg_z_host, int64_t* match_ids_host, float* match_scores_host, int32_t* counters_host, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

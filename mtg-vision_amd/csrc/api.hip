@@ -12,6 +12,7 @@
 #include "rowops.h"
 #include "gemm_sp.h"
 #include "operand_registry.h"
+#include "track.h"
 
 namespace mtgv {
 const char* last_error_cstr();
@@ -86,12 +87,17 @@ struct mtgv_bank {
   mtgv_bank(int d, int64_t c) : impl(d, c) {}
 };
 
+struct mtgv_tracker {
+  Tracker impl;
+  explicit mtgv_tracker(const mtgv_tracker_cfg& c) : impl(c) {}
+};
+
 extern "C" {
 
 MTGV_API const char* mtgv_last_error(void) { return last_error_cstr(); }
 // 101: mtgv_detector_cfg.task, the OBB calls; 102: in_h / in_w, mtgv_head_rows h / w, the rect letterbox calls;
-// 103: mtgv_detector_cfg.scale, mtgv_op_stem_u8
-MTGV_API int mtgv_version(void) { return 103; }
+// 103: mtgv_detector_cfg.scale, mtgv_op_stem_u8; 104: the mtgv_tracker_* calls
+MTGV_API int mtgv_version(void) { return 104; }
 MTGV_API int mtgv_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -249,6 +255,56 @@ MTGV_API int mtgv_topk_merge(float* cand_scores_dev, const int64_t* cand_ids_dev
     MTGV_CHECK(cand_scores_dev && cand_ids_dev && ids_dev && scores_dev, ERR_INVALID, "null argument");
     MTGV_CHECK(!(score_threshold != score_threshold), ERR_INVALID, "topk_merge: score_threshold is NaN");
     topk_merge_launch_i64(cand_scores_dev, cand_ids_dev, b, ncand, k, score_threshold, ids_dev, scores_dev, (hipStream_t)stream);
+  });
+}
+
+// ---- tracker ----
+MTGV_API int mtgv_tracker_create(const mtgv_tracker_cfg* cfg, mtgv_tracker** out) {
+  return guarded([&] {
+    MTGV_CHECK(cfg != nullptr && out != nullptr, ERR_INVALID, "null argument");
+    (void)tracker_resolve_cfg(*cfg);  // the range check before any HIP call
+    *out = new mtgv_tracker(*cfg);
+  });
+}
+MTGV_API void mtgv_tracker_destroy(mtgv_tracker* h) { delete h; }
+MTGV_API int mtgv_tracker_reset(mtgv_tracker* h, int32_t stream_or_minus_1, void* stream) {
+  return guarded([&] {
+    MTGV_CHECK(h != nullptr, ERR_INVALID, "null handle");
+    h->impl.reset(stream_or_minus_1, (hipStream_t)stream);
+  });
+}
+MTGV_API int mtgv_tracker_update(mtgv_tracker* h, const float* quads_dev, const int32_t* n_det_dev, const int32_t* state_dev, int32_t frames,
+                                 const int32_t* stream_of_frame_host, const double* now_host, int32_t* track_id_dev, int32_t* due_idx_dev,
+                                 int32_t* n_due_dev, void* stream) {
+  return guarded([&] {
+    MTGV_CHECK(h != nullptr, ERR_INVALID, "null handle");
+    h->impl.update(quads_dev, n_det_dev, state_dev, frames, stream_of_frame_host, now_host, track_id_dev, due_idx_dev, n_due_dev,
+                   (hipStream_t)stream);
+  });
+}
+MTGV_API int mtgv_tracker_gather_u8(const uint8_t* src_dev, int64_t src_rows, int64_t row_bytes, const int32_t* due_idx_dev,
+                                    const int32_t* n_due_dev, int32_t max_rows, uint8_t* dst_dev, void* stream) {
+  return guarded([&] { tracker_gather_u8_launch(src_dev, src_rows, row_bytes, due_idx_dev, n_due_dev, max_rows, dst_dev, (hipStream_t)stream); });
+}
+MTGV_API int mtgv_tracker_commit(mtgv_tracker* h, const float* z_dev, float* q_dev, int32_t rows, void* stream) {
+  return guarded([&] {
+    MTGV_CHECK(h != nullptr, ERR_INVALID, "null handle");
+    h->impl.commit(z_dev, q_dev, rows, (hipStream_t)stream);
+  });
+}
+MTGV_API int mtgv_tracker_store(mtgv_tracker* h, const int64_t* ids_dev, const float* scores_dev, int32_t rows, int64_t* out_ids_dev,
+                                float* out_scores_dev, void* stream) {
+  return guarded([&] {
+    MTGV_CHECK(h != nullptr, ERR_INVALID, "null handle");
+    h->impl.store(ids_dev, scores_dev, rows, out_ids_dev, out_scores_dev, (hipStream_t)stream);
+  });
+}
+MTGV_API int mtgv_tracker_get_state(mtgv_tracker* h, int32_t stream_index, double* kal_host, int32_t* ints_host, double* last_update_host,
+                                    float* avg_z_host, int64_t* match_ids_host, float* match_scores_host, int32_t* counters_host, void* stream) {
+  return guarded([&] {
+    MTGV_CHECK(h != nullptr, ERR_INVALID, "null handle");
+    h->impl.get_state(stream_index, kal_host, ints_host, last_update_host, avg_z_host, match_ids_host, match_scores_host, counters_host,
+                      (hipStream_t)stream);
   });
 }
 

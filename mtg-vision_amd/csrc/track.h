@@ -1,0 +1,57 @@
+// Device-resident card tracker: mtgv/tracker.py's KalmanPointTracker + TrackerCtx gating for S independent streams,
+// one wave per stream, all state on the GPU (include/mtgv.h: mtgv_tracker_*).
+#pragma once
+#include "common.h"
+#include "mtgv.h"
+
+namespace mtgv {
+
+constexpr int TRACK_MAX_TRACKS = 64;   // one lane of the wave per slot
+constexpr int TRACK_MAX_CARDS = 16;    // detections of a frame held in LDS
+constexpr int TRACK_MAX_TOPK = 8;
+constexpr int TRACK_KAL = 40;          // doubles per slot: pos, vel, pp, pv, vv of the 8 corner coordinates
+constexpr int TRACK_INTS = 6;          // live, hit_counter, is_initializing, id, birth, has_z
+constexpr int TRACK_CTRS = 4;          // per stream: next_id, next_birth, overflow, (unused)
+
+// Policy with the zero fields replaced by the reference's values; throws ERR_INVALID on anything out of range.
+// No HIP call: works on a machine without a GPU.
+mtgv_tracker_cfg tracker_resolve_cfg(const mtgv_tracker_cfg& c);
+
+class Tracker {
+ public:
+  explicit Tracker(const mtgv_tracker_cfg& c);
+  ~Tracker();
+  Tracker(const Tracker&) = delete;
+  Tracker& operator=(const Tracker&) = delete;
+
+  void reset(int stream_or_all, hipStream_t s);
+  void update(const float* quads, const int32_t* n_det, const int32_t* state, int frames, const int32_t* stream_of_frame, const double* now,
+              int32_t* track_id, int32_t* due_idx, int32_t* n_due, hipStream_t s);
+  void commit(const float* z, float* q, int rows, hipStream_t s);
+  void store(const int64_t* ids, const float* scores, int rows, int64_t* out_ids, float* out_scores, hipStream_t s);
+  void get_state(int stream, double* kal, int32_t* ints, double* last_t, float* avg_z, int64_t* m_ids, float* m_scores, int32_t* ctrs,
+                 hipStream_t s);
+
+ private:
+  mtgv_tracker_cfg c_;
+  int frames_ = 0;  // of the last update: commit / store run over frames_ * K rows
+  // state, per (stream, slot); lane-major so that the wave's loads coalesce
+  double* kal_ = nullptr;       // (S, TRACK_KAL, T)
+  int32_t* ints_ = nullptr;     // (S, TRACK_INTS, T)
+  double* last_t_ = nullptr;    // (S, T)
+  float* avg_z_ = nullptr;      // (S, T, dim)
+  int64_t* m_ids_ = nullptr;    // (S, T, top_k)
+  float* m_scores_ = nullptr;   // (S, T, top_k)
+  int32_t* ctrs_ = nullptr;     // (S, TRACK_CTRS)
+  // per step, per frame slot f * K + k
+  int32_t* slot_of_ = nullptr;  // s * T + slot of the reported track, -1 none
+  int32_t* due_flag_ = nullptr;
+  int32_t* rank_of_ = nullptr;  // position in due_idx, -1 not due
+  const int32_t* due_idx_ = nullptr;  // the caller's buffers of the last update (read by commit / store)
+  const int32_t* n_due_ = nullptr;
+};
+
+void tracker_gather_u8_launch(const uint8_t* src, int64_t src_rows, int64_t row_bytes, const int32_t* due_idx, const int32_t* n_due,
+                              int max_rows, uint8_t* dst, hipStream_t s);
+
+}  // namespace mtgv

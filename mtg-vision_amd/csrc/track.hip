@@ -1,0 +1,458 @@
+// Device-resident card tracker (track.h).  update: one wave64 workgroup per frame = stream, lane t owns track slot t with its
+// filter state in registers, the frame's detections in LDS, the greedy association as at most K rounds of a wave-wide
+// lexicographic minimum over (distance, birth, detection index).  A second, single-workgroup launch compacts the due slots in
+// ascending order.  Everything the host tracker computes in fp64 is computed here in fp64 with the same operations in the
+// same order: this translation unit must not contract a * b + c into an FMA.
+#include "track.h"
+
+#include <math.h>
+#include <limits.h>
+#include <algorithm>
+#include <set>
+
+#pragma clang fp contract(off)
+
+namespace mtgv {
+
+namespace {
+
+constexpr int FRAMES_PER_LAUNCH = 32;  // stream and clock of each frame travel as kernel arguments: no copy, no staging buffer
+struct FrameArgs {
+  int32_t stream[FRAMES_PER_LAUNCH];
+  double now[FRAMES_PER_LAUNCH];
+};
+
+struct Params {
+  int T, K, top_k, hmax, delay, period;
+  double thr, wait;
+};
+
+struct State {
+  double* kal;
+  int32_t* ints;
+  double* last_t;
+  int64_t* m_ids;
+  float* m_scores;
+  int32_t* ctrs;
+};
+
+// _KalmanTrack's constants (mtgv/tracker.py): norfair's OptimizedKalmanFilter defaults
+constexpr double KAL_R = 4.0, KAL_Q = 0.1, KAL_POS_VAR = 10.0, KAL_VEL_VAR = 1.0;
+
+__global__ __launch_bounds__(64) void track_update_kernel(State st, Params p, FrameArgs fr, int f0, const float* __restrict__ quads,
+                                                          const int32_t* __restrict__ n_det, const int32_t* __restrict__ state,
+                                                          int32_t* __restrict__ track_id, int32_t* __restrict__ slot_of,
+                                                          int32_t* __restrict__ due_flag) {
+  __shared__ double det[TRACK_MAX_CARDS][8];
+  __shared__ int det_k[TRACK_MAX_CARDS];
+  __shared__ int o_id[TRACK_MAX_CARDS], o_slot[TRACK_MAX_CARDS], o_due[TRACK_MAX_CARDS];
+  const int lane = threadIdx.x;
+  const int f = f0 + blockIdx.x, s = fr.stream[blockIdx.x];
+  const double now = fr.now[blockIdx.x];
+  const int T = p.T, K = p.K;
+
+  // the frame's detection list: the valid slots in ascending k
+  bool valid = lane < K;
+  if (valid && n_det != nullptr) valid = lane < min(n_det[f], K);
+  if (valid && state != nullptr) valid = state[(size_t)f * K + lane] > 0;
+  const unsigned long long vm = __ballot(valid);
+  const int nd = __popcll(vm);
+  if (lane < TRACK_MAX_CARDS) o_id[lane] = 0, o_slot[lane] = -1, o_due[lane] = 0;
+  if (valid) {
+    const int di = __popcll(vm & ((1ull << lane) - 1ull));
+    det_k[di] = lane;
+    const float* q = quads + ((size_t)f * K + lane) * 8;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) det[di][j] = (double)q[j];
+  }
+  __syncthreads();
+
+  const bool own = lane < T;
+  int32_t* I = st.ints + (size_t)s * TRACK_INTS * T;
+  double* Kal = st.kal + (size_t)s * TRACK_KAL * T;
+  int32_t* C = st.ctrs + (size_t)s * TRACK_CTRS;
+  int live = 0, hit = 0, init = 0, id = 0, birth = 0, has_z = 0;
+  double last_t = 0.0;
+  if (own) {
+    live = I[0 * T + lane], hit = I[1 * T + lane], init = I[2 * T + lane], id = I[3 * T + lane], birth = I[4 * T + lane];
+    has_z = I[5 * T + lane];
+    last_t = st.last_t[(size_t)s * T + lane];
+  }
+  double pos[8], vel[8], pp[8], pv[8], vv[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    pos[j] = vel[j] = pp[j] = pv[j] = vv[j] = 0.0;
+    if (live) {
+      pos[j] = Kal[(0 + j) * T + lane], vel[j] = Kal[(8 + j) * T + lane], pp[j] = Kal[(16 + j) * T + lane];
+      pv[j] = Kal[(24 + j) * T + lane], vv[j] = Kal[(32 + j) * T + lane];
+    }
+  }
+  int next_id = C[0], next_birth = C[1], overflow = C[2];
+
+  // 1. drop, 2. age and predict
+  if (live && hit < 0) live = 0, id = 0;
+  if (live) {
+    hit -= 1;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) pos[j] = pos[j] + vel[j];
+  }
+
+  // 3. greedy association, closest pair first: the initialised tracks, then the initialising ones on what is left
+  int mdi = -1;  // detection this lane's track took in this frame
+  unsigned free_d = nd > 0 ? (0xffffffffu >> (32 - nd)) : 0u;
+  for (int phase = 0; phase < 2; ++phase) {
+    const bool cand = live && init == phase;
+    double d[TRACK_MAX_CARDS];
+#pragma unroll
+    for (int di = 0; di < TRACK_MAX_CARDS; ++di) {
+      d[di] = INFINITY;
+      if (di < nd && cand && ((free_d >> di) & 1u)) {
+        double sum = 0.0;
+#pragma unroll
+        for (int c = 0; c < 4; ++c) {
+          const double dx = det[di][2 * c] - pos[2 * c], dy = det[di][2 * c + 1] - pos[2 * c + 1];
+          const double r = __dsqrt_rn(dx * dx + dy * dy);
+          sum = c == 0 ? r : sum + r;
+        }
+        const double dist = sum / 4.0;
+        if (dist < p.thr) d[di] = dist;  // a NaN never matches
+      }
+    }
+    bool used = false;
+    for (int round = 0; round < nd; ++round) {
+      double best = INFINITY;
+      int bdi = -1;
+      if (cand && !used) {
+#pragma unroll
+        for (int di = 0; di < TRACK_MAX_CARDS; ++di)
+          if (((free_d >> di) & 1u) && d[di] < best) best = d[di], bdi = di;  // strict: the lowest index wins a tie
+      }
+      double m = best;
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) m = fmin(m, __shfl_xor(m, off));
+      if (!(m < INFINITY)) break;  // wave-uniform
+      int b = best == m ? birth : INT_MAX;  // ties between tracks: creation order, as the host's list order
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) b = min(b, __shfl_xor(b, off));
+      const bool win = best == m && birth == b;
+      const int wl = __ffsll((unsigned long long)__ballot(win)) - 1;
+      const int wdi = __shfl(bdi, wl);
+      free_d &= ~(1u << wdi);
+      int gets_id = 0;
+      if (lane == wl) {
+        used = true;
+        mdi = wdi;
+        hit = min(hit + 2 * p.period, p.hmax);
+        if (init && hit > p.delay) init = 0, id = next_id, gets_id = 1, has_z = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {  // _KalmanTrack.kalman_update
+          const double e = det[wdi][j] - pos[j];
+          const double sv = pp[j] + 2.0 * pv[j] + vv[j] + KAL_Q + KAL_R;
+          const double k0 = 1.0 - KAL_R / sv, k1 = (pv[j] + vv[j]) / sv;
+          pos[j] = pos[j] + k0 * e;
+          vel[j] = vel[j] + k1 * e;
+          const double nvv = vv[j] + KAL_Q - k1 * k1 * sv;
+          pp[j] = k0 * KAL_R, pv[j] = k1 * KAL_R, vv[j] = nvv;
+        }
+      }
+      next_id += __shfl(gets_id, wl);
+    }
+  }
+
+  // 4. unmatched detections, ascending, take the lowest free slot
+  unsigned long long freem = __ballot(own && !live);
+  const bool new_init = p.period <= p.delay;
+  bool fresh = false;
+  for (int di = 0; di < nd; ++di) {
+    if (!((free_d >> di) & 1u)) continue;
+    if (freem == 0ull) {
+      overflow += 1;
+      continue;
+    }
+    const int sl = __ffsll(freem) - 1;
+    freem &= freem - 1ull;
+    if (lane == sl) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) pos[j] = det[di][j], vel[j] = 0.0, pp[j] = KAL_POS_VAR, pv[j] = 0.0, vv[j] = KAL_VEL_VAR;
+      live = 1, hit = p.period, init = new_init ? 1 : 0, id = new_init ? 0 : next_id, birth = next_birth;
+      has_z = 0, last_t = 0.0, mdi = di, fresh = true;
+    }
+    if (!new_init) next_id += 1;
+    next_birth += 1;
+  }
+
+  // 5. report and gate
+  const bool rep = live && id > 0 && mdi >= 0 && hit >= 0;
+  const bool due = rep && (!has_z || now - last_t > p.wait);
+  if (due) last_t = now;
+  if (rep) {
+    const int k = det_k[mdi];
+    o_id[k] = id, o_slot[k] = s * T + lane, o_due[k] = due ? 1 : 0;
+  }
+
+  if (own) {
+    I[0 * T + lane] = live, I[1 * T + lane] = hit, I[2 * T + lane] = init, I[3 * T + lane] = id, I[4 * T + lane] = birth;
+    I[5 * T + lane] = has_z;
+    st.last_t[(size_t)s * T + lane] = last_t;
+    if (live) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        Kal[(0 + j) * T + lane] = pos[j], Kal[(8 + j) * T + lane] = vel[j], Kal[(16 + j) * T + lane] = pp[j];
+        Kal[(24 + j) * T + lane] = pv[j], Kal[(32 + j) * T + lane] = vv[j];
+      }
+    }
+    if (fresh) {
+      for (int t = 0; t < p.top_k; ++t) {
+        st.m_ids[((size_t)s * T + lane) * p.top_k + t] = -1;
+        st.m_scores[((size_t)s * T + lane) * p.top_k + t] = -INFINITY;
+      }
+    }
+  }
+  if (lane == 0) C[0] = next_id, C[1] = next_birth, C[2] = overflow;
+  __syncthreads();
+  if (lane < K) {
+    const size_t o = (size_t)f * K + lane;
+    track_id[o] = o_id[lane], slot_of[o] = o_slot[lane], due_flag[o] = o_due[lane];
+  }
+}
+
+// ordered compaction of the due slots: one wave walks the n = F * K flags in ascending order (no atomics, so the order of
+// due_idx does not depend on which workgroup finished first); entries behind n_due are -1
+__global__ __launch_bounds__(64) void track_compact_kernel(const int32_t* __restrict__ due_flag, int n, int32_t* __restrict__ due_idx,
+                                                           int32_t* __restrict__ rank_of, int32_t* __restrict__ n_due) {
+  const int lane = threadIdx.x;
+  int base = 0;
+  for (int i0 = 0; i0 < n; i0 += 64) {
+    const int i = i0 + lane;
+    const bool flag = i < n && due_flag[i] != 0;
+    const unsigned long long m = __ballot(flag);
+    if (i < n) {
+      const int r = flag ? base + __popcll(m & ((1ull << lane) - 1ull)) : -1;
+      rank_of[i] = r;
+      if (flag) due_idx[r] = i;
+    }
+    base += __popcll(m);
+  }
+  for (int i = base + lane; i < n; i += 64) due_idx[i] = -1;
+  if (lane == 0) *n_due = base;
+}
+
+// row r < n_due: avg = w z + (1 - w) avg in f32 (avg = z the first time, then the same formula), q[r] = avg
+__global__ __launch_bounds__(128) void track_commit_kernel(const float* __restrict__ z, float* __restrict__ q, const int32_t* __restrict__ due_idx,
+                                                           const int32_t* __restrict__ n_due, const int32_t* __restrict__ slot_of,
+                                                           int32_t* __restrict__ ints, float* __restrict__ avg_z, int T, int dim, float w,
+                                                           float omw) {
+  const int r = blockIdx.x;  // (the grid is min(rows of z, F * K) blocks)
+  if (r >= *n_due) return;
+  const int slot = slot_of[due_idx[r]];
+  if (slot < 0) return;  // (cannot happen: a due slot has a track)
+  int32_t* has = ints + (size_t)(slot / T) * TRACK_INTS * T + 5 * T + slot % T;
+  const bool had = *has != 0;
+  __syncthreads();
+  float* a = avg_z + (size_t)slot * dim;
+  for (int c = threadIdx.x; c < dim; c += 128) {
+    const float zc = z[(size_t)r * dim + c];
+    const float prev = had ? a[c] : zc;
+    const float v = w * zc + omw * prev;
+    a[c] = v;
+    q[(size_t)r * dim + c] = v;
+  }
+  if (threadIdx.x == 0) *has = 1;
+}
+
+// slot i of the step: a due track takes (and keeps) row rank_of[i] of the new matches, a track that was not due emits what
+// it kept, a slot without a track -1 / -inf.  A track owns at most one slot of a step, so no two threads touch one track.
+__global__ __launch_bounds__(256) void track_store_kernel(const int64_t* __restrict__ ids, const float* __restrict__ scores,
+                                                          const int32_t* __restrict__ slot_of, const int32_t* __restrict__ rank_of,
+                                                          int64_t* __restrict__ m_ids, float* __restrict__ m_scores, int64_t* __restrict__ out_ids,
+                                                          float* __restrict__ out_scores, int n, int top_k, int rows) {
+  const int i = blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const int slot = slot_of[i];
+  const int r = rank_of[i] < rows ? rank_of[i] : -1;  // never past the caller's rows
+  for (int t = 0; t < top_k; ++t) {
+    int64_t id = -1;
+    float sc = -INFINITY;
+    if (slot >= 0) {
+      if (r >= 0) {
+        id = ids[(size_t)r * top_k + t], sc = scores[(size_t)r * top_k + t];
+        m_ids[(size_t)slot * top_k + t] = id, m_scores[(size_t)slot * top_k + t] = sc;
+      } else {
+        id = m_ids[(size_t)slot * top_k + t], sc = m_scores[(size_t)slot * top_k + t];
+      }
+    }
+    out_ids[(size_t)i * top_k + t] = id, out_scores[(size_t)i * top_k + t] = sc;
+  }
+}
+
+__global__ __launch_bounds__(256) void track_reset_kernel(State st, float* __restrict__ avg_z, int s0, int T, int dim, int top_k) {
+  const int s = s0 + blockIdx.x;
+  for (int i = threadIdx.x; i < TRACK_KAL * T; i += 256) st.kal[(size_t)s * TRACK_KAL * T + i] = 0.0;
+  for (int i = threadIdx.x; i < TRACK_INTS * T; i += 256) st.ints[(size_t)s * TRACK_INTS * T + i] = 0;
+  for (int i = threadIdx.x; i < T; i += 256) st.last_t[(size_t)s * T + i] = 0.0;
+  for (int i = threadIdx.x; i < T * dim; i += 256) avg_z[(size_t)s * T * dim + i] = 0.f;
+  for (int i = threadIdx.x; i < T * top_k; i += 256) st.m_ids[(size_t)s * T * top_k + i] = -1, st.m_scores[(size_t)s * T * top_k + i] = -INFINITY;
+  if (threadIdx.x == 0) {
+    int32_t* C = st.ctrs + (size_t)s * TRACK_CTRS;
+    C[0] = 1, C[1] = 0, C[2] = 0, C[3] = 0;
+  }
+}
+
+// dst row r = src row due_idx[r], r < min(n_due, max_rows); 16 bytes per thread where the rows allow it
+__global__ __launch_bounds__(256) void track_gather_u8_kernel(const uint8_t* __restrict__ src, long src_rows, long row_bytes,
+                                                              const int32_t* __restrict__ due_idx, const int32_t* __restrict__ n_due,
+                                                              uint8_t* __restrict__ dst, int vec) {
+  const int r = blockIdx.x;
+  if (r >= *n_due) return;
+  const long i = due_idx[r];
+  if (i < 0 || i >= src_rows) return;
+  const uint8_t* a = src + i * row_bytes;
+  uint8_t* b = dst + (long)r * row_bytes;
+  if (vec) {
+    const uint4* a4 = (const uint4*)a;
+    uint4* b4 = (uint4*)b;
+    for (long c = (long)blockIdx.y * 256 + threadIdx.x; c < row_bytes / 16; c += (long)gridDim.y * 256) b4[c] = a4[c];
+  } else {
+    for (long c = (long)blockIdx.y * 256 + threadIdx.x; c < row_bytes; c += (long)gridDim.y * 256) b[c] = a[c];
+  }
+}
+
+template <class P>
+void dev_alloc(P*& p, size_t count) {
+  HIP_OK(hipMalloc((void**)&p, count * sizeof(P)));
+}
+
+}  // namespace
+
+mtgv_tracker_cfg tracker_resolve_cfg(const mtgv_tracker_cfg& in) {
+  mtgv_tracker_cfg c = in;
+  MTGV_CHECK(c.streams >= 1 && c.streams <= 4096, ERR_INVALID, "tracker: streams %d outside 1..4096", c.streams);
+  MTGV_CHECK(c.max_tracks >= 1 && c.max_tracks <= TRACK_MAX_TRACKS, ERR_INVALID, "tracker: max_tracks %d outside 1..%d", c.max_tracks, TRACK_MAX_TRACKS);
+  MTGV_CHECK(c.cards_per_frame >= 1 && c.cards_per_frame <= TRACK_MAX_CARDS, ERR_INVALID, "tracker: cards_per_frame %d outside 1..%d",
+             c.cards_per_frame, TRACK_MAX_CARDS);
+  MTGV_CHECK(c.dim >= 1 && c.dim <= 65536, ERR_INVALID, "tracker: dim %d outside 1..65536", c.dim);
+  MTGV_CHECK(c.top_k >= 1 && c.top_k <= TRACK_MAX_TOPK, ERR_INVALID, "tracker: top_k %d outside 1..%d", c.top_k, TRACK_MAX_TOPK);
+  // zero: the reference's value (mtgvision/server.py:100-106, :41-43)
+  if (c.distance_threshold == 0.0) c.distance_threshold = 300.0;
+  if (c.hit_counter_max == 0) c.hit_counter_max = 5;
+  if (c.initialization_delay == 0) c.initialization_delay = 2;
+  if (c.period == 0) c.period = 1;
+  if (c.update_wait_sec == 0.0) c.update_wait_sec = 0.5;
+  if (c.ewma_weight == 0.0) c.ewma_weight = 0.1;
+  MTGV_CHECK(c.distance_threshold > 0.0 && c.distance_threshold < INFINITY, ERR_INVALID, "tracker: distance_threshold %g must be positive and finite",
+             c.distance_threshold);
+  MTGV_CHECK(c.hit_counter_max >= 1 && c.hit_counter_max <= (1 << 20), ERR_INVALID, "tracker: hit_counter_max %d outside 1..2^20", c.hit_counter_max);
+  MTGV_CHECK(c.period >= 1 && c.period <= (1 << 20), ERR_INVALID, "tracker: period %d outside 1..2^20", c.period);
+  MTGV_CHECK(c.initialization_delay >= -1 && c.initialization_delay <= (1 << 20), ERR_INVALID, "tracker: initialization_delay %d outside -1..2^20",
+             c.initialization_delay);
+  MTGV_CHECK(c.update_wait_sec == c.update_wait_sec, ERR_INVALID, "tracker: update_wait_sec is NaN");
+  MTGV_CHECK(c.ewma_weight > 0.0 && c.ewma_weight <= 1.0, ERR_INVALID, "tracker: ewma_weight %g outside (0, 1]", c.ewma_weight);
+  return c;
+}
+
+Tracker::Tracker(const mtgv_tracker_cfg& c) : c_(tracker_resolve_cfg(c)) {
+  const size_t S = c_.streams, T = c_.max_tracks, K = c_.cards_per_frame;
+  dev_alloc(kal_, S * TRACK_KAL * T);
+  dev_alloc(ints_, S * TRACK_INTS * T);
+  dev_alloc(last_t_, S * T);
+  dev_alloc(avg_z_, S * T * c_.dim);
+  dev_alloc(m_ids_, S * T * c_.top_k);
+  dev_alloc(m_scores_, S * T * c_.top_k);
+  dev_alloc(ctrs_, S * TRACK_CTRS);
+  dev_alloc(slot_of_, S * K);
+  dev_alloc(due_flag_, S * K);
+  dev_alloc(rank_of_, S * K);
+  reset(-1, nullptr);
+  HIP_OK(hipStreamSynchronize(nullptr));
+}
+
+Tracker::~Tracker() {
+  for (void* p : {(void*)kal_, (void*)ints_, (void*)last_t_, (void*)avg_z_, (void*)m_ids_, (void*)m_scores_, (void*)ctrs_, (void*)slot_of_,
+                  (void*)due_flag_, (void*)rank_of_})
+    if (p != nullptr) (void)hipFree(p);
+}
+
+void Tracker::reset(int stream_or_all, hipStream_t s) {
+  MTGV_CHECK(stream_or_all >= -1 && stream_or_all < c_.streams, ERR_INVALID, "tracker: stream %d outside [-1, %d)", stream_or_all, c_.streams);
+  const State st{kal_, ints_, last_t_, m_ids_, m_scores_, ctrs_};
+  const int s0 = stream_or_all < 0 ? 0 : stream_or_all, n = stream_or_all < 0 ? c_.streams : 1;
+  hipLaunchKernelGGL(track_reset_kernel, dim3(n), dim3(256), 0, s, st, avg_z_, s0, c_.max_tracks, c_.dim, c_.top_k);
+  HIP_OK(hipGetLastError());
+  frames_ = 0;  // the step's slot table refers to the tracks that were
+}
+
+void Tracker::update(const float* quads, const int32_t* n_det, const int32_t* state, int frames, const int32_t* stream_of_frame, const double* now,
+                     int32_t* track_id, int32_t* due_idx, int32_t* n_due, hipStream_t s) {
+  MTGV_CHECK(quads && stream_of_frame && now && track_id && due_idx && n_due, ERR_INVALID, "tracker: null argument");
+  MTGV_CHECK(n_det != nullptr || state != nullptr, ERR_INVALID, "tracker: one of n_det and state must be given");
+  MTGV_CHECK(frames >= 1 && frames <= c_.streams, ERR_INVALID, "tracker: %d frames for %d streams", frames, c_.streams);
+  std::set<int32_t> seen;
+  for (int f = 0; f < frames; ++f) {
+    MTGV_CHECK(stream_of_frame[f] >= 0 && stream_of_frame[f] < c_.streams, ERR_INVALID, "tracker: frame %d names stream %d outside [0, %d)", f,
+               stream_of_frame[f], c_.streams);
+    MTGV_CHECK(seen.insert(stream_of_frame[f]).second, ERR_INVALID, "tracker: stream %d appears twice in one step", stream_of_frame[f]);
+    MTGV_CHECK(now[f] == now[f], ERR_INVALID, "tracker: the clock of frame %d is NaN", f);
+  }
+  const State st{kal_, ints_, last_t_, m_ids_, m_scores_, ctrs_};
+  const Params p{c_.max_tracks, c_.cards_per_frame, c_.top_k, c_.hit_counter_max, c_.initialization_delay, c_.period,
+                 c_.distance_threshold, c_.update_wait_sec};
+  for (int f0 = 0; f0 < frames; f0 += FRAMES_PER_LAUNCH) {
+    const int n = std::min(FRAMES_PER_LAUNCH, frames - f0);
+    FrameArgs fr = {};
+    for (int i = 0; i < n; ++i) fr.stream[i] = stream_of_frame[f0 + i], fr.now[i] = now[f0 + i];
+    hipLaunchKernelGGL(track_update_kernel, dim3(n), dim3(64), 0, s, st, p, fr, f0, quads, n_det, state, track_id, slot_of_, due_flag_);
+  }
+  hipLaunchKernelGGL(track_compact_kernel, dim3(1), dim3(64), 0, s, due_flag_, frames * c_.cards_per_frame, due_idx, rank_of_, n_due);
+  HIP_OK(hipGetLastError());
+  frames_ = frames, due_idx_ = due_idx, n_due_ = n_due;
+}
+
+void Tracker::commit(const float* z, float* q, int rows, hipStream_t s) {
+  MTGV_CHECK(z && q && rows >= 1, ERR_INVALID, "tracker: null argument or no rows");
+  MTGV_CHECK(frames_ > 0, ERR_INVALID, "tracker: commit without an update");
+  const double w = c_.ewma_weight;
+  hipLaunchKernelGGL(track_commit_kernel, dim3(std::min(rows, frames_ * c_.cards_per_frame)), dim3(128), 0, s, z, q, due_idx_, n_due_, slot_of_, ints_, avg_z_,
+                     c_.max_tracks, c_.dim, (float)w, (float)(1.0 - w));
+  HIP_OK(hipGetLastError());
+}
+
+void Tracker::store(const int64_t* ids, const float* scores, int rows, int64_t* out_ids, float* out_scores, hipStream_t s) {
+  MTGV_CHECK(out_ids && out_scores && rows >= 0 && (rows == 0 || (ids && scores)), ERR_INVALID, "tracker: null argument");
+  MTGV_CHECK(frames_ > 0, ERR_INVALID, "tracker: store without an update");
+  const int n = frames_ * c_.cards_per_frame;
+  // rows == 0 (nothing was due): ids / scores are never read
+  hipLaunchKernelGGL(track_store_kernel, dim3(ceil_div(n, 256)), dim3(256), 0, s, ids, scores, slot_of_, rank_of_, m_ids_, m_scores_, out_ids,
+                     out_scores, n, c_.top_k, rows);
+  HIP_OK(hipGetLastError());
+}
+
+void Tracker::get_state(int stream, double* kal, int32_t* ints, double* last_t, float* avg_z, int64_t* m_ids, float* m_scores, int32_t* ctrs,
+                        hipStream_t s) {
+  MTGV_CHECK(stream >= 0 && stream < c_.streams, ERR_INVALID, "tracker: stream %d outside [0, %d)", stream, c_.streams);
+  const size_t T = c_.max_tracks, i = stream;
+  HIP_OK(hipStreamSynchronize(s));
+  auto get = [&](void* dst, const void* src, size_t bytes) {
+    if (dst != nullptr) HIP_OK(hipMemcpy(dst, src, bytes, hipMemcpyDeviceToHost));
+  };
+  get(kal, kal_ + i * TRACK_KAL * T, TRACK_KAL * T * sizeof(double));
+  get(ints, ints_ + i * TRACK_INTS * T, TRACK_INTS * T * sizeof(int32_t));
+  get(last_t, last_t_ + i * T, T * sizeof(double));
+  get(avg_z, avg_z_ + i * T * c_.dim, T * c_.dim * sizeof(float));
+  get(m_ids, m_ids_ + i * T * c_.top_k, T * c_.top_k * sizeof(int64_t));
+  get(m_scores, m_scores_ + i * T * c_.top_k, T * c_.top_k * sizeof(float));
+  get(ctrs, ctrs_ + i * TRACK_CTRS, TRACK_CTRS * sizeof(int32_t));
+}
+
+void tracker_gather_u8_launch(const uint8_t* src, int64_t src_rows, int64_t row_bytes, const int32_t* due_idx, const int32_t* n_due, int max_rows,
+                              uint8_t* dst, hipStream_t s) {
+  MTGV_CHECK(src && due_idx && n_due && dst, ERR_INVALID, "tracker_gather: null argument");
+  MTGV_CHECK(src_rows >= 0 && row_bytes > 0 && max_rows >= 0 && max_rows <= 65535, ERR_INVALID, "tracker_gather: bad shape");
+  if (max_rows == 0) return;
+  const int vec = row_bytes % 16 == 0 && (uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0;
+  const long units = vec ? row_bytes / 16 : row_bytes;
+  const int gy = (int)std::min<long>(std::max<long>(1, units / 1024), 32);
+  hipLaunchKernelGGL(track_gather_u8_kernel, dim3(max_rows, gy), dim3(256), 0, s, src, (long)src_rows, (long)row_bytes, due_idx, n_due, dst, vec);
+  HIP_OK(hipGetLastError());
+}
+
+}  // namespace mtgv

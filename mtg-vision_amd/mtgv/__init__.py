@@ -17,6 +17,8 @@ _LAZY = {
     "merge_topk": ("matcher", "merge_topk"),
     "Pipeline": ("pipeline", "Pipeline"),
     "warp_quads": ("crop", "warp_quads"),
+    "DeviceTracker": ("track", "DeviceTracker"),
+    "TrackedPipeline": ("track", "TrackedPipeline"),
 }
 
 

@@ -85,6 +85,15 @@ class ProtoTail(C.Structure):
     )
 
 
+class TrackerCfg(C.Structure):
+    """mtgv_tracker_cfg (mtgv_version >= 104); zero in a policy field selects the reference's value"""
+
+    _fields_ = (
+        [(k, c_i32) for k in ("streams", "max_tracks", "cards_per_frame", "dim", "top_k", "hit_counter_max", "initialization_delay", "period")]
+        + [(k, C.c_double) for k in ("distance_threshold", "update_wait_sec", "ewma_weight")]
+    )
+
+
 # name -> (restype, argtypes); every symbol include/mtgv.h declares
 SIGNATURES = {
     "mtgv_last_error": (C.c_char_p, []),
@@ -178,6 +187,14 @@ SIGNATURES = {
     "mtgv_op_block": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32] + [c_vp] * 10 + [c_vp, c_vp]),
     "mtgv_op_block_workspace_floats": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
     "mtgv_op_l2norm": (C.c_int, [c_vp, c_vp, c_i64, c_i32, c_vp]),
+    "mtgv_tracker_create": (C.c_int, [C.POINTER(TrackerCfg), C.POINTER(c_vp)]),
+    "mtgv_tracker_destroy": (None, [c_vp]),
+    "mtgv_tracker_reset": (C.c_int, [c_vp, c_i32, c_vp]),
+    "mtgv_tracker_update": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mtgv_tracker_gather_u8": (C.c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "mtgv_tracker_commit": (C.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp]),
+    "mtgv_tracker_store": (C.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
+    "mtgv_tracker_get_state": (C.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
 }
 
 _lib = None
