@@ -153,6 +153,28 @@ MTGV_API int mtgv_bank_get_rows(const mtgv_bank* h, int64_t row, int64_t n, floa
  * fewer than k rows); -INFINITY keeps everything, NaN is rejected. */
 MTGV_API int mtgv_bank_topk(mtgv_bank* h, const float* q_dev, int32_t b, int32_t k, int64_t id_base, float score_threshold,
                             int64_t* ids_dev, float* scores_dev, void* stream);
+/* Row labels (version 105): the payload filters and grouped queries of a vector store, kept on the device beside the rows.
+ *   tags   uint64 bit set per row; what a bit means is the caller's business.  Default 0.
+ *   group  int32 per row, >= 0, or -1 (the default): the row is its own group.
+ * A bank whose labels were never set behaves as all-default and allocates nothing for them.  mtgv_bank_append gives new rows
+ * the defaults, mtgv_bank_set_row keeps the row's labels (an upsert changes the vector, not the card), mtgv_bank_clear resets
+ * them.  Labels are indexed by local row (id_base plays no part).  set: a null array leaves that label unchanged; rows
+ * outside [0, size) and groups below -1 are refused.  get: a null array is not written. */
+MTGV_API int mtgv_bank_set_labels(mtgv_bank* h, int64_t row0, int64_t n, const uint64_t* tags_host, const int32_t* groups_host, void* stream);
+MTGV_API int mtgv_bank_get_labels(const mtgv_bank* h, int64_t row0, int64_t n, uint64_t* tags_host, int32_t* groups_host);
+/* mtgv_bank_topk over labelled rows.  masks_dev: (b, 3) uint64 per query = (all_of, any_of, none_of), or NULL.  Row n is
+ * eligible for query m when (tags[n] & all_of) == all_of, and any_of == 0 or (tags[n] & any_of) != 0, and
+ * (tags[n] & none_of) == 0.  distinct != 0: among the eligible rows a group >= 0 is represented by its best row (score
+ * desc, id asc) only - no two results share a non-negative group; rows of group -1 never suppress one another.  Order,
+ * id_base and pads as mtgv_bank_topk; score_threshold is applied last (a representative below it becomes a pad, it is
+ * not replaced by another row of its group).  Masks that admit no row are not an error: k pads.  The result is the
+ * exact filtered / distinct top k.  With masks_dev == NULL and distinct == 0 the call IS mtgv_bank_topk (two-pass
+ * pre-pass included); otherwise it always runs the one-pass exact kernel with the labelled epilogue, whatever b is.
+ * Single-bank: the sharded exchange (mtgv_bank_topk_packed) does not carry labels.
+ * The first labelled call on a bank whose labels were never set allocates the label arrays and synchronises the device
+ * once (so do mtgv_bank_set_labels and, on a labelled bank, mtgv_bank_clear): make it before capturing a stream. */
+MTGV_API int mtgv_bank_topk_ex(mtgv_bank* h, const float* q_dev, int32_t b, int32_t k, int64_t id_base, float score_threshold,
+                               const uint64_t* masks_dev, int32_t distinct, int64_t* ids_dev, float* scores_dev, void* stream);
 /* Batches of >= 128 queries (dim % 64 == 0, k <= 4, F16X3 mode) are matched in two passes: approximate fp16 scores over a
  * hi-only copy of the bank, then an exact re-rank of the best candidates with a bound that proves no other row can enter
  * the top k; a query whose bound fails is scanned exactly, so the answer is always the exact top k.  count: how many

@@ -96,8 +96,9 @@ extern "C" {
 
 MTGV_API const char* mtgv_last_error(void) { return last_error_cstr(); }
 // 101: mtgv_detector_cfg.task, the OBB calls; 102: in_h / in_w, mtgv_head_rows h / w, the rect letterbox calls;
-// 103: mtgv_detector_cfg.scale, mtgv_op_stem_u8; 104: the mtgv_tracker_* calls
-MTGV_API int mtgv_version(void) { return 104; }
+// 103: mtgv_detector_cfg.scale, mtgv_op_stem_u8; 104: the mtgv_tracker_* calls;
+// 105: bank row labels (mtgv_bank_set_labels / _get_labels / mtgv_bank_topk_ex)
+MTGV_API int mtgv_version(void) { return 105; }
 MTGV_API int mtgv_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -226,6 +227,29 @@ MTGV_API int mtgv_bank_topk(mtgv_bank* h, const float* q_dev, int32_t b, int32_t
     MTGV_CHECK(h != nullptr, ERR_INVALID, "null handle");
     MTGV_CHECK(!(score_threshold != score_threshold), ERR_INVALID, "bank: score_threshold is NaN");
     h->impl.topk(q_dev, b, k, id_base, score_threshold, ids_dev, scores_dev, (hipStream_t)stream);
+  });
+}
+MTGV_API int mtgv_bank_set_labels(mtgv_bank* h, int64_t row0, int64_t n, const uint64_t* tags_host, const int32_t* groups_host, void* stream) {
+  return guarded([&] {
+    MTGV_CHECK(h != nullptr, ERR_INVALID, "null handle");
+    h->impl.set_labels(row0, n, tags_host, groups_host, (hipStream_t)stream);
+  });
+}
+MTGV_API int mtgv_bank_get_labels(const mtgv_bank* h, int64_t row0, int64_t n, uint64_t* tags_host, int32_t* groups_host) {
+  return guarded([&] {
+    MTGV_CHECK(h != nullptr, ERR_INVALID, "null handle");
+    h->impl.get_labels(row0, n, tags_host, groups_host);
+  });
+}
+MTGV_API int mtgv_bank_topk_ex(mtgv_bank* h, const float* q_dev, int32_t b, int32_t k, int64_t id_base, float score_threshold,
+                               const uint64_t* masks_dev, int32_t distinct, int64_t* ids_dev, float* scores_dev, void* stream) {
+  return guarded([&] {
+    MTGV_CHECK(h != nullptr, ERR_INVALID, "null handle");
+    MTGV_CHECK(!(score_threshold != score_threshold), ERR_INVALID, "bank: score_threshold is NaN");
+    if (masks_dev == nullptr && distinct == 0)  // nothing to honour: mtgv_bank_topk itself, two-pass pre-pass included
+      h->impl.topk(q_dev, b, k, id_base, score_threshold, ids_dev, scores_dev, (hipStream_t)stream);
+    else
+      h->impl.topk_labelled(q_dev, b, k, id_base, score_threshold, masks_dev, distinct != 0, ids_dev, scores_dev, (hipStream_t)stream);
   });
 }
 MTGV_API int mtgv_bank_topk_packed(mtgv_bank* h, const float* q_dev, int32_t b, int32_t k, int64_t id_base, int64_t* packed_dev,

@@ -100,7 +100,16 @@ struct GemmArgs {
   // algorithmic FLOPs the launch profiler credits this launch with besides its own 2 M N K (+ the chained layer's): a
   // launch that stands for more arithmetic than it runs (folded layers)
   double xflops = 0.0;
+  // Labelled top-k (topk > 0; appended, read only by the labelled epilogues: gemm_kernel.h EPI 3, gemm_sp_kernel.h
+  // SP_EPI_TOPK_LABELS).  Column n is eligible for row m when col_tags[n] passes row_masks[m] = (all_of, any_of, none_of);
+  // with topk_distinct a candidate group keeps only the best column of every col_groups value >= 0.  gemm_launch takes
+  // the labelled kernels when row_masks is set or topk_distinct is; launches without them are the plain top-k.
+  const uint64_t* col_tags = nullptr;    // [N]
+  const int* col_groups = nullptr;       // [N]
+  const uint64_t* row_masks = nullptr;   // [M][3] or null: no filter
+  int topk_distinct = 0;
 };
+inline bool topk_labelled(const GemmArgs& a) { return a.topk > 0 && (a.row_masks != nullptr || a.topk_distinct != 0); }
 
 // A is gathered through a window (anything but a dense 1x1 / linear)
 inline int conv_pad_h(const GemmArgs& a) { return a.pad_h >= 0 ? a.pad_h : a.pad; }

@@ -282,6 +282,9 @@ void gemm_launch(const GemmArgs& args, hipStream_t s) {
   MTGV_CHECK(a.a_shift == nullptr, ERR_INVALID, "gemm: fold the GRN shift into the bias (fold_shift_into_bias_launch)");
   if (!conv) MTGV_CHECK(a.OH == a.H && a.OW == a.Wd, ERR_INVALID, "gemm: 1x1 geometry mismatch");
   if (apro || a.grn_part) MTGV_CHECK(a.hw > 0 && a.M % a.hw == 0, ERR_INVALID, "gemm: hw=%d must divide M=%d", a.hw, a.M);
+  if (topk_labelled(a))
+    MTGV_CHECK((a.row_masks == nullptr || a.col_tags != nullptr) && (a.topk_distinct == 0 || a.col_groups != nullptr), ERR_INVALID,
+               "gemm: labelled top-k without its label arrays");
   const SpPlan sp = gemm_sp_plan(a);  // the LDS-DMA split kernel takes every launch it can run
   if (a.grn_part) {
     const GrnLayout l = grn_layout(a, sp, pl);

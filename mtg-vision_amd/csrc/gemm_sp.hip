@@ -45,6 +45,7 @@ const char* sp_zero_page() {
 // ---- tile configurations (one translation unit each: gemm_sp_c<id>.hip) ----
 template <int ID>
 void gemm_sp_launch_cfg(const SpDev& g, int amode, hipStream_t s);  // gemm_sp_inst.h, instantiated by gemm_sp_c<ID>.hip
+void gemm_sp_topk_labels_launch(const SpDev& g, hipStream_t s);     // gemm_sp_topk_labels.hip
 
 namespace {
 typedef void (*SpLaunchFn)(const SpDev&, int, hipStream_t);
@@ -326,6 +327,10 @@ static SpDev sp_dev_of(const GemmArgs& a, const SpPlan& pl) {
   }
   g.tiles_m = pl.tiles_m, g.tiles_n = pl.tiles_n;
   g.cand_s = a.cand_s, g.cand_i = a.cand_i, g.topk = a.topk;
+  if (topk_labelled(a)) {
+    g.col_tags = reinterpret_cast<const unsigned long*>(a.col_tags), g.col_groups = a.col_groups;
+    g.row_masks = reinterpret_cast<const unsigned long*>(a.row_masks), g.distinct = a.topk_distinct;
+  }
   g.act = a.act;
   g.H = a.H, g.Wd = a.Wd, g.Cin = a.Cin, g.KW = a.KW, g.stride = a.stride, g.pad = conv_pad_h(a), g.pad_w = conv_pad_w(a), g.OH = a.OH, g.OW = a.OW;
   g.d_ohw = make_fastdiv((uint32_t)(a.OH * a.OW));
@@ -367,7 +372,12 @@ void gemm_sp_launch(const GemmArgs& a, const SpPlan& pl, hipStream_t s) {
     g.stamps = buf;
     g_stamps.push_back({a.M, a.N, a.K, pl.cfg, amode, a.act, tiles, buf});
   }
-  kLaunch[pl.cfg](g, amode, s);
+  if (topk_labelled(a)) {
+    MTGV_CHECK(pl.cfg == SP_CFG_TOPK && amode == SP_A_F32, ERR_RUNTIME, "gemm_sp: labelled top-k planned on configuration %d, A mode %d", pl.cfg, amode);
+    gemm_sp_topk_labels_launch(g, s);
+  } else {
+    kLaunch[pl.cfg](g, amode, s);
+  }
   HIP_OK(hipGetLastError());
 }
 

@@ -80,6 +80,7 @@ enum SpEpi : int {
   SP_EPI_RES_SP8 = 4,  //       + SP8 residual (detector, with SP8_OUT),
   SP_EPI_GRN = 8,      //       + GRN sums (pwconv1)
   SP_EPI_TOPK = 16,    // fused top-k
+  SP_EPI_TOPK_LABELS = 17,  // fused top-k that honours row labels: tag filter and one row per group (own translation unit)
   SP_EPI_CHAIN = 32,   // chained 1x1
   SP_EPI_CHAIN_PHASE = 96,  // chained 1x1 + remapped Out2 rows + first-layer bias per row from a nine-class border table
 };

@@ -28,6 +28,9 @@
 //                        read per row from a table of nine border classes: one output phase of ConvTranspose2d(k2, s2)
 //                        folded into the 3x3 conv behind it (detector: Proto), a 2x2 tap gather over the low-resolution
 //                        map whose bias depends on which of the 3x3 taps fell into the padding.  AMODE 2 only.
+//   EPI 17 (top-k, labels)  the fused top-k (EPI 16) over labelled bank rows: columns whose tags fail the row's masks score
+//                        -inf, and with `distinct` a wave range reports one column per group (match.hip, Bank::topk_labelled).
+//                        One instance, in gemm_sp_topk_labels.hip.
 //   A, AMODE 6 (HI16)    A and B are plain fp16 rows (the hi halves only, 2 bytes per element): a stage is 64 k, one MFMA
 //                        per k16 step.  The approximate first pass of the bank match (match.hip); K % 64 == 0.
 //   A, AMODE 1 (REG)     f32 rows: global -> VGPR (issued before the stage's MFMAs) -> optional per-image multiplier
@@ -114,6 +117,11 @@ struct SpDev {
   // SP_EPI_CHAIN_PHASE: the first layer's bias of a row is bias_tab[class][N], class = 3 * {0 first, 1 inner, 2 last row of
   // the OH2 x OW2 grid the row is written to} + the same for its column; Out2 rows go through the output row remap
   const float* bias_tab = nullptr;
+  // SP_EPI_TOPK_LABELS (GemmArgs::col_tags ...): the bank rows' labels by column, the queries' masks by row
+  const unsigned long* col_tags = nullptr;   // [N]; read only when row_masks is set
+  const int* col_groups = nullptr;           // [N]; read only when distinct is set
+  const unsigned long* row_masks = nullptr;  // [M][3] (all_of, any_of, none_of) or null: every column eligible
+  int distinct = 0;
 };
 
 // the compile-time epilogue shape of a launch (EPI below), or SP_EPI_ARGS when only the generic one fits
@@ -871,6 +879,98 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
 #pragma unroll
           for (int q = 0; q < 16; ++q)
             if (ncol0 + j * 32 + (q >> 2) * 8 + 4 * h + (q & 3) == bi) acc[i][j][q] = -INFINITY;
+      }
+    }
+    return;
+  }
+
+  if constexpr (EPI == SP_EPI_TOPK_LABELS) {
+    // ---- fused top-k with row labels (Bank::topk_labelled): the twin of the epilogue above.  A column whose tags fail
+    // the row's (all_of, any_of, none_of) masks scores -inf like a column past N; with g.distinct the winner's group
+    // travels with (score, column) through the lane exchange and the retire step retires every column of that group
+    // (group >= 0), so a wave range reports its best eligible rows of pairwise different groups.  A lane keeps the groups
+    // of its 16 TN columns in registers (the operand registers are dead); tags are read once per tile and dropped.
+    const int ncolh = n0 + wn * TN * 32 + 4 * h;  // the lane's first column; its columns are ncolh + 32 j + 8 gq + e
+    unsigned long m_all[TM], m_any[TM], m_none[TM];
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+      const int m = m0 + wm * TM * 32 + i * 32 + r;
+      const bool mok = g.row_masks != nullptr && m < g.M;
+      m_all[i] = mok ? g.row_masks[3 * (long)m] : 0ul;
+      m_any[i] = mok ? g.row_masks[3 * (long)m + 1] : 0ul;
+      m_none[i] = mok ? g.row_masks[3 * (long)m + 2] : 0ul;
+    }
+    typedef unsigned long sp_u2 __attribute__((ext_vector_type(2)));
+    typedef int sp_i4 __attribute__((ext_vector_type(4)));
+    int grp[TN][16];
+#pragma unroll
+    for (int j = 0; j < TN; ++j)
+#pragma unroll
+      for (int gq = 0; gq < 4; ++gq) {
+        const int n = ncolh + j * 32 + gq * 8;
+        unsigned long tg[4] = {0ul, 0ul, 0ul, 0ul};
+        sp_i4 gr = {-1, -1, -1, -1};
+        if (n + 3 < g.N) {  // a whole quad of columns: 16-byte loads (n % 4 == 0; gemm_sp_topk_labels_launch checks the bases)
+          if (g.row_masks != nullptr) {
+            const sp_u2 t0 = *reinterpret_cast<const sp_u2*>(g.col_tags + n), t1 = *reinterpret_cast<const sp_u2*>(g.col_tags + n + 2);
+            tg[0] = t0[0], tg[1] = t0[1], tg[2] = t1[0], tg[3] = t1[1];
+          }
+          if (g.distinct != 0) gr = *reinterpret_cast<const sp_i4*>(g.col_groups + n);
+        } else {
+#pragma unroll
+          for (int e = 0; e < 4; ++e) {
+            if (g.row_masks != nullptr && n + e < g.N) tg[e] = g.col_tags[n + e];
+            if (g.distinct != 0 && n + e < g.N) gr[e] = g.col_groups[n + e];
+          }
+        }
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+          const bool nok = n + e < g.N;
+          const float ws = (g.wscale != nullptr && nok) ? g.wscale[n + e] * g.a_unmul : g.a_unmul;
+          grp[j][4 * gq + e] = gr[e];
+#pragma unroll
+          for (int i = 0; i < TM; ++i) {
+            // (short-circuit form on purpose: written with & and | the step becomes one straight line, the compiler takes all
+            // 48 columns' loads and tests at once and the kernel needs 256 VGPRs and 344 bytes of scratch per lane; in this
+            // form it is 236 VGPRs without scratch.  tests/test_gpu_match_labels.py::test_filter runs it at b = 130.)
+            const bool el = (tg[e] & m_all[i]) == m_all[i] && (m_any[i] == 0ul || (tg[e] & m_any[i]) != 0ul) && (tg[e] & m_none[i]) == 0ul;
+            acc[i][j][4 * gq + e] = (nok && el) ? acc[i][j][4 * gq + e] * ws : -INFINITY;
+          }
+        }
+      }
+    const long slots = (long)g.tiles_n * WN;
+#pragma unroll
+    for (int i = 0; i < TM; ++i) {
+      const int m = m0 + wm * TM * 32 + i * 32 + r;
+      for (int kk = 0; kk < g.topk; ++kk) {
+        // the lane's columns are named by their compile-time offset from ncolh (no register per column index); ascending
+        // column order inside the lane, so the first strict maximum has the lowest column
+        float bs = -INFINITY;
+        int br = -1, bg = -1;
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+          for (int q = 0; q < 16; ++q) {
+            const float v = acc[i][j][q];
+            if (v > bs) bs = v, br = j * 32 + (q >> 2) * 8 + (q & 3), bg = grp[j][q];
+          }
+        int bi = br >= 0 ? ncolh + br : 0x7fffffff;
+        const float os = __shfl_xor(bs, 32);
+        const int oi = __shfl_xor(bi, 32);
+        const int og = __shfl_xor(bg, 32);
+        if (os > bs || (os == bs && oi < bi)) bs = os, bi = oi, bg = og;
+        if (h == 0 && m < g.M) {
+          const long o = ((long)m * slots + (long)tile_n * WN + wn) * g.topk + kk;
+          g.cand_s[o] = bs;
+          g.cand_i[o] = (bs == -INFINITY) ? -1 : bi;
+        }
+        // (the partner's winner is 4 columns off every offset of this lane: rr matches none of them)
+        const int rr = bi - ncolh;
+#pragma unroll
+        for (int j = 0; j < TN; ++j)
+#pragma unroll
+          for (int q = 0; q < 16; ++q)
+            if (j * 32 + (q >> 2) * 8 + (q & 3) == rr || (bg >= 0 && grp[j][q] == bg)) acc[i][j][q] = -INFINITY;
       }
     }
     return;

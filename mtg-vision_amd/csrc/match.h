@@ -12,13 +12,22 @@ class Bank {
   int dim() const { return dim_; }
   int64_t size() const { return size_; }
   int64_t capacity() const { return cap_; }
-  void clear() { size_ = 0; }
+  void clear();  // labels go back to their defaults
   void append(const float* v, int64_t n, bool is_device, hipStream_t s);
   void set_row(int64_t row, const float* v_host, hipStream_t s);
   void get_rows(int64_t row, int64_t n, float* out_host) const;
   // thr: results scoring below it are dropped (id -1, score -inf); -INFINITY keeps everything.
   // scores == nullptr: ids receives [b][k][2] int64 = (id, float32 bits of the score) - the sharded match's exchange format
   void topk(const float* q, int b, int k, int64_t id_base, float thr, int64_t* ids, float* scores, hipStream_t s);
+  // Row labels: tags (uint64 bit set, default 0) and group (int32, default -1 = the row is its own group).  Allocated on
+  // first use; append gives new rows the defaults, set_row keeps a row's labels, clear resets them.  A null host pointer
+  // leaves that label as it is (set) or is not written (get).
+  void set_labels(int64_t row0, int64_t n, const uint64_t* tags_host, const int32_t* groups_host, hipStream_t s);
+  void get_labels(int64_t row0, int64_t n, uint64_t* tags_host, int32_t* groups_host) const;
+  // topk over the rows whose tags pass the query's masks[b][3] = (all_of, any_of, none_of) (device; null: no filter);
+  // distinct: a group >= 0 is represented by its best row only.  Same order, threshold and pad rules as topk.
+  void topk_labelled(const float* q, int b, int k, int64_t id_base, float thr, const uint64_t* masks, bool distinct, int64_t* ids,
+                     float* scores, hipStream_t s);
   // queries of two-pass matches so far whose answer the first pass could not prove and that were scanned exactly
   // (synchronises the device)
   int64_t prepass_fallbacks() const;
@@ -28,10 +37,14 @@ class Bank {
   bool prepass_ok(int b, int k) const;
   void topk_prepass(const float* q, int b, int k, int64_t id_base, float thr, int64_t* ids, float* scores, hipStream_t s);
   void refresh_hi(int64_t row0, int64_t rows, hipStream_t s);
+  void ensure_labels();
+  void topk_one_pass(const float* q, int b, int k, int64_t id_base, float thr, bool labelled, const uint64_t* masks, bool distinct,
+                     int64_t* ids, float* scores, hipStream_t s);
 
   int dim_;
   int64_t cap_, size_ = 0;
   DevBuf vecs_, qn_, cand_s_, cand_i_;
+  DevBuf tags_, groups_;     // row labels, capacity rows each (uint64 / int32); null until a label is set or a labelled match runs
   DevBuf hi_, qhi_, stat_;   // fp16 hi halves of the (row-scaled) bank rows / of the normalised queries, 2 bytes per element
 };
 

@@ -25,10 +25,13 @@ __device__ __forceinline__ void store_result(long* __restrict__ out_ids, float* 
   }
 }
 
-template <typename IdT>
+// DISTINCT (labelled matches, Bank::topk_labelled): candidate ids are bank rows, so a candidate's group is groups[id];
+// after a pick every candidate of the winner's group (>= 0) is retired with it.  The candidate ranges dedupe too
+// (gemm_sp_kernel.h SP_EPI_TOPK_LABELS, gemm_kernel.h EPI 3): a merge-only dedupe would miss rows hidden inside a range.
+template <typename IdT, bool DISTINCT = false>
 __global__ __launch_bounds__(256) void topk_merge_kernel(float* __restrict__ cs, const IdT* __restrict__ ci, int ncand, int k,
                                                         long id_base, float thr, long* __restrict__ out_ids,
-                                                        float* __restrict__ out_scores) {
+                                                        float* __restrict__ out_scores, const int* __restrict__ groups = nullptr) {
   __shared__ float rs[256];
   __shared__ long ri[256];
   __shared__ int rp[256];
@@ -63,6 +66,15 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(float* __restrict__ cs,
       if (rp[0] >= 0) s[rp[0]] = -INFINITY;  // retire
     }
     __syncthreads();
+    if constexpr (DISTINCT) {
+      const int wg = rp[0] >= 0 ? groups[id[rp[0]]] : -1;  // rp[0] is rewritten only after the barrier below
+      if (wg >= 0)
+        for (int p = tid; p < ncand; p += 256) {
+          const long i = (long)id[p];
+          if (i >= 0 && groups[i] == wg) s[p] = -INFINITY;
+        }
+      __syncthreads();
+    }
   }
 }
 
@@ -328,7 +340,8 @@ void topk_merge_gathered_launch(const int64_t* gathered, int R, int b_total, int
 void topk_merge_launch_i64(float* cs, const int64_t* ci, int b, int ncand, int k, float thr, int64_t* ids, float* scores,
                            hipStream_t s) {
   MTGV_CHECK(b > 0 && ncand > 0 && k > 0, ERR_INVALID, "topk_merge: b=%d ncand=%d k=%d", b, ncand, k);
-  hipLaunchKernelGGL((topk_merge_kernel<long>), dim3(b), dim3(256), 0, s, cs, (const long*)ci, ncand, k, 0L, thr, (long*)ids, scores);
+  hipLaunchKernelGGL((topk_merge_kernel<long>), dim3(b), dim3(256), 0, s, cs, (const long*)ci, ncand, k, 0L, thr, (long*)ids, scores,
+                     (const int*)nullptr);
   HIP_OK(hipGetLastError());
 }
 
@@ -437,16 +450,74 @@ void Bank::get_rows(int64_t row, int64_t n, float* out_host) const {
   HIP_OK(hipMemcpy(out_host, vecs_.p + (size_t)row * dim_, (size_t)n * dim_ * sizeof(float), hipMemcpyDeviceToHost));
 }
 
-void Bank::topk(const float* q, int b, int k, int64_t id_base, float thr, int64_t* ids, float* scores, hipStream_t s) {
-  MTGV_CHECK(b > 0 && k > 0 && k <= 65536, ERR_INVALID, "bank: b=%d k=%d (k must be in [1,65536])", b, k);
-  MTGV_CHECK(q != nullptr && ids != nullptr, ERR_INVALID, "bank: null tensor");  // scores == nullptr: exchange format in ids (store_result)
-  MTGV_CHECK(size_ > 0, ERR_RUNTIME, "bank is empty");
-  if (prepass_ok(b, k)) {
-    topk_prepass(q, b, k, id_base, thr, ids, scores, s);
+// ---- row labels ----
+// Invariant: once allocated, every row at or beyond size_ holds the defaults (tags 0, group -1), so append has nothing to do.
+void Bank::ensure_labels() {
+  if (tags_.p != nullptr) return;
+  tags_.alloc((size_t)cap_ * 2);  // uint64 per row
+  groups_.alloc((size_t)cap_);    // int32 per row
+  HIP_OK(hipMemset(tags_.p, 0, (size_t)cap_ * sizeof(uint64_t)));
+  HIP_OK(hipMemset(groups_.p, 0xff, (size_t)cap_ * sizeof(int32_t)));  // -1
+  HIP_OK(hipStreamSynchronize(nullptr));  // the caller's stream need not wait on the null stream by itself
+}
+
+void Bank::clear() {
+  if (tags_.p != nullptr && size_ > 0) {
+    HIP_OK(hipDeviceSynchronize());  // matches in flight still read the labels
+    HIP_OK(hipMemset(tags_.p, 0, (size_t)size_ * sizeof(uint64_t)));
+    HIP_OK(hipMemset(groups_.p, 0xff, (size_t)size_ * sizeof(int32_t)));
+    HIP_OK(hipStreamSynchronize(nullptr));
+  }
+  size_ = 0;
+}
+
+void Bank::set_labels(int64_t row0, int64_t n, const uint64_t* tags_host, const int32_t* groups_host, hipStream_t s) {
+  MTGV_CHECK(row0 >= 0 && n >= 0 && row0 + n <= size_, ERR_INVALID, "bank: label rows [%lld, %lld) outside [0, %lld)", (long long)row0,
+             (long long)(row0 + n), (long long)size_);
+  if (groups_host != nullptr)
+    for (int64_t i = 0; i < n; ++i)
+      MTGV_CHECK(groups_host[i] >= -1, ERR_INVALID, "bank: group %d of row %lld (groups are >= 0, or -1 for none)", groups_host[i],
+                 (long long)(row0 + i));
+  if (n == 0 || (tags_host == nullptr && groups_host == nullptr)) return;
+  ensure_labels();
+  if (tags_host != nullptr)
+    HIP_OK(hipMemcpyAsync(reinterpret_cast<uint64_t*>(tags_.p) + row0, tags_host, (size_t)n * sizeof(uint64_t), hipMemcpyHostToDevice, s));
+  if (groups_host != nullptr)
+    HIP_OK(hipMemcpyAsync(reinterpret_cast<int32_t*>(groups_.p) + row0, groups_host, (size_t)n * sizeof(int32_t), hipMemcpyHostToDevice, s));
+  HIP_OK(hipStreamSynchronize(s));  // host buffers may be freed by the caller
+}
+
+void Bank::get_labels(int64_t row0, int64_t n, uint64_t* tags_host, int32_t* groups_host) const {
+  MTGV_CHECK(row0 >= 0 && n >= 0 && row0 + n <= size_, ERR_INVALID, "bank: label rows [%lld, %lld) outside [0, %lld)", (long long)row0,
+             (long long)(row0 + n), (long long)size_);
+  if (n == 0) return;
+  if (tags_.p == nullptr) {  // never labelled: all defaults
+    for (int64_t i = 0; i < n; ++i) {
+      if (tags_host != nullptr) tags_host[i] = 0;
+      if (groups_host != nullptr) groups_host[i] = -1;
+    }
     return;
   }
+  if (tags_host != nullptr)
+    HIP_OK(hipMemcpy(tags_host, reinterpret_cast<const uint64_t*>(tags_.p) + row0, (size_t)n * sizeof(uint64_t), hipMemcpyDeviceToHost));
+  if (groups_host != nullptr)
+    HIP_OK(hipMemcpy(groups_host, reinterpret_cast<const int32_t*>(groups_.p) + row0, (size_t)n * sizeof(int32_t), hipMemcpyDeviceToHost));
+}
+
+// One-pass exact match: normalise the queries, one GEMM launch with the fused top-k epilogue, one merge.  labelled: the
+// launch and the merge honour the row labels (masks may be null: no filter; distinct: one row per group) - every candidate
+// range reports its kt best eligible rows, with `distinct` of pairwise different groups, and the merge dedupes again: the
+// result is the exact filtered / distinct top k (match).
+void Bank::topk_one_pass(const float* q, int b, int k, int64_t id_base, float thr, bool labelled, const uint64_t* masks, bool distinct,
+                         int64_t* ids, float* scores, hipStream_t s) {
   qn_.ensure((size_t)b * dim_);
   GemmArgs g = linear_args(qn_.p, dim_, vecs_.p, nullptr, nullptr, 0, b, (int)size_, dim_, ACT_NONE);
+  if (labelled) {
+    g.col_tags = reinterpret_cast<const uint64_t*>(tags_.p);
+    g.col_groups = reinterpret_cast<const int*>(groups_.p);
+    g.row_masks = masks;
+    g.topk_distinct = distinct ? 1 : 0;
+  }
   // candidate groups: 64-column tiles of the convert-on-load kernel, or the per-wave column ranges of the LDS-DMA kernel
   int slots = 0, cols = 0;
   g.topk = 1;
@@ -460,9 +531,35 @@ void Bank::topk(const float* q, int b, int k, int64_t id_base, float thr, int64_
   g.cand_i = reinterpret_cast<int*>(cand_i_.p);
   g.topk = kt;
   gemm_launch(g, s);
-  hipLaunchKernelGGL((topk_merge_kernel<int>), dim3(b), dim3(256), 0, s, cand_s_.p, (const int*)cand_i_.p, (int)ncand, k,
-                     (long)id_base, thr, (long*)ids, scores);
+  if (labelled && distinct)
+    hipLaunchKernelGGL((topk_merge_kernel<int, true>), dim3(b), dim3(256), 0, s, cand_s_.p, (const int*)cand_i_.p, (int)ncand, k,
+                       (long)id_base, thr, (long*)ids, scores, g.col_groups);
+  else
+    hipLaunchKernelGGL((topk_merge_kernel<int>), dim3(b), dim3(256), 0, s, cand_s_.p, (const int*)cand_i_.p, (int)ncand, k,
+                       (long)id_base, thr, (long*)ids, scores, (const int*)nullptr);
   HIP_OK(hipGetLastError());
+}
+
+// Labelled match: always the one-pass kernel with the labelled epilogue (the fp16 pre-pass's bound does not cover labels).
+void Bank::topk_labelled(const float* q, int b, int k, int64_t id_base, float thr, const uint64_t* masks, bool distinct, int64_t* ids,
+                         float* scores, hipStream_t s) {
+  MTGV_CHECK(b > 0 && k > 0 && k <= 65536, ERR_INVALID, "bank: b=%d k=%d (k must be in [1,65536])", b, k);
+  MTGV_CHECK(q != nullptr && ids != nullptr && scores != nullptr, ERR_INVALID, "bank: null tensor");
+  MTGV_CHECK(masks != nullptr || distinct, ERR_INVALID, "bank: a labelled match needs masks or distinct");
+  MTGV_CHECK(size_ > 0, ERR_RUNTIME, "bank is empty");
+  ensure_labels();  // (first labelled call on a bank without labels: allocates and synchronises once)
+  topk_one_pass(q, b, k, id_base, thr, true, masks, distinct, ids, scores, s);
+}
+
+void Bank::topk(const float* q, int b, int k, int64_t id_base, float thr, int64_t* ids, float* scores, hipStream_t s) {
+  MTGV_CHECK(b > 0 && k > 0 && k <= 65536, ERR_INVALID, "bank: b=%d k=%d (k must be in [1,65536])", b, k);
+  MTGV_CHECK(q != nullptr && ids != nullptr, ERR_INVALID, "bank: null tensor");  // scores == nullptr: exchange format in ids (store_result)
+  MTGV_CHECK(size_ > 0, ERR_RUNTIME, "bank is empty");
+  if (prepass_ok(b, k)) {
+    topk_prepass(q, b, k, id_base, thr, ids, scores, s);
+    return;
+  }
+  topk_one_pass(q, b, k, id_base, thr, false, nullptr, false, ids, scores, s);
 }
 
 }  // namespace mtgv

@@ -488,18 +488,55 @@ class VectorStoreQdrant:
             self._row[pid] = r
             self._ids.append(pid)
 
+    def set_labels(self, ids: Iterable[str], tags=None, groups=None):
+        """Row labels by point id (Qdrant's payload filters and `query_points_groups`, kept on the device): `tags` one
+        uint64 bit set per id, `groups` one group number (>= 0, or -1 for none) per id; None leaves that label as it
+        is.  Unknown ids raise KeyError."""
+        rows = [self._row[str(i)] for i in ids]
+        tags = None if tags is None else np.asarray(tags).reshape(-1)
+        groups = None if groups is None else np.asarray(groups).reshape(-1)
+        assert (tags is None or len(tags) == len(rows)) and (groups is None or len(groups) == len(rows)), "one label per id"
+        start = 0
+        while start < len(rows):  # one call per run of consecutive rows
+            end = start + 1
+            while end < len(rows) and rows[end] == rows[end - 1] + 1:
+                end += 1
+            self._bank.set_labels(rows[start], None if tags is None else tags[start:end], None if groups is None else groups[start:end])
+            start = end
+
+    def group_by_payload(self, key: str) -> dict:
+        """Give every distinct value of `payload[key]` one group number (in order of first appearance by row) and label
+        the rows with it; rows whose payload lacks the key get -1.  Returns the value -> group dict.  With
+        key="oracle_id", `query_nearby(..., distinct=True)` then returns k different cards instead of k printings."""
+        table: dict = {}
+        groups = np.full(len(self._ids), -1, np.int32)
+        for r, pid in enumerate(self._ids):
+            payload = self._payload.get(pid)
+            if payload is not None and key in payload:
+                groups[r] = table.setdefault(payload[key], len(table))
+        if len(groups):
+            self._bank.set_labels(0, None, groups)
+        return table
+
     def query_nearby(self, vector: list[float], k: int, *, with_payload: bool = True, with_vectors: bool = False,
-                     score_threshold: float = None) -> list[ScoredPoint]:
-        return self.query_nearby_batch([vector], k, with_payload=with_payload, with_vectors=with_vectors, score_threshold=score_threshold)[0]
+                     score_threshold: float = None, tags_all: int = 0, tags_any: int = 0, tags_none: int = 0,
+                     distinct: bool = False) -> list[ScoredPoint]:
+        return self.query_nearby_batch([vector], k, with_payload=with_payload, with_vectors=with_vectors, score_threshold=score_threshold,
+                                       tags_all=tags_all, tags_any=tags_any, tags_none=tags_none, distinct=distinct)[0]
 
     def query_nearby_batch(self, vectors, k: int, *, with_payload: bool = True, with_vectors: bool = False,
-                           score_threshold: float = None) -> list[list[ScoredPoint]]:
-        """`query_nearby` for several query vectors in one GPU pass (one list of hits per query)."""
+                           score_threshold: float = None, tags_all: int = 0, tags_any: int = 0, tags_none: int = 0,
+                           distinct: bool = False) -> list[list[ScoredPoint]]:
+        """`query_nearby` for several query vectors in one GPU pass (one list of hits per query).  Beyond the reference's
+        parameters: `tags_all` / `tags_any` / `tags_none` filter by the rows' tag bits (`set_labels`), `distinct` keeps
+        one hit per group (`group_by_payload`); the defaults make the reference's query."""
         vectors = np.asarray(vectors, np.float32).reshape(-1, self._VECTOR_SIZE)
         if len(self._bank) == 0 or k <= 0 or len(vectors) == 0:
             return [[] for _ in range(len(vectors))]
         kk = min(int(k), len(self._bank))
-        ids, scores = self._bank.match(vectors, kk, threshold=score_threshold)  # score_threshold applied on the device
+        flt = (int(tags_all), int(tags_any), int(tags_none)) if (tags_all or tags_any or tags_none) else None
+        # score_threshold (and the labels) applied on the device
+        ids, scores = self._bank.match(vectors, kk, threshold=score_threshold, filter=flt, distinct=bool(distinct))
         ids, scores = ids.cpu().numpy(), scores.cpu().numpy()
         res = []
         for row_ids, row_scores in zip(ids, scores):

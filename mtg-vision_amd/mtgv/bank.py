@@ -135,10 +135,14 @@ def build_bank(cards: Iterable[Tuple[str, np.ndarray]], encoder: Encoder, store:
 
 def save_store(store: VectorStoreQdrant, path: str) -> None:
     """On-disk bank: <path>.npz (ids as fixed-width strings + float32 matrix of the stored, normalised vectors)
-    and <path>.payload.json."""
+    and <path>.payload.json.  A store whose rows were labelled (`set_labels` / `group_by_payload`) also writes their
+    `tags` (uint64) and `groups` (int32) arrays; an unlabelled store writes the same file as before."""
     n = len(store._ids)
     vecs = store._bank.rows(0, n) if n else np.zeros((0, store._VECTOR_SIZE), np.float32)
-    np.savez(path + ".npz", ids=np.asarray(store._ids, dtype=np.str_), vectors=vecs)
+    arrays = dict(ids=np.asarray(store._ids, dtype=np.str_), vectors=vecs)
+    if n and store._bank.labelled:
+        arrays["tags"], arrays["groups"] = store._bank.labels(0, n)
+    np.savez(path + ".npz", **arrays)
     with open(path + ".payload.json", "w") as f:
         json.dump({k: v for k, v in store._payload.items()}, f)
 
@@ -152,4 +156,6 @@ def load_store(path: str, capacity: int = 131072) -> VectorStoreQdrant:
         payload = json.load(open(path + ".payload.json"))
     for s in range(0, len(ids), 4096):
         store.save_points(QdrantPoint(id=i, vector=v, payload=payload.get(i)) for i, v in zip(ids[s : s + 4096], vecs[s : s + 4096]))
+    if "tags" in d.files and len(ids):  # ids are unique in a saved store: row r holds ids[r]
+        store._bank.set_labels(0, d["tags"], d["groups"])
     return store

@@ -33,6 +33,7 @@ class Matcher:
         if self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
         self._h = native.c_vp(0)
+        self.labelled = False  # set_labels was called since the last clear (bank.save_store writes labels only then)
         with torch.cuda.device(self.device):
             native.check(native.lib().mtgv_bank_create(self.dim, self.capacity, C.byref(self._h)))
 
@@ -72,15 +73,66 @@ class Matcher:
         return out
 
     def clear(self):
-        native.check(native.lib().mtgv_bank_clear(self._h))
+        with torch.cuda.device(self.device):  # (a labelled bank waits for its device's matches in flight before it resets the labels)
+            native.check(native.lib().mtgv_bank_clear(self._h))
+        self.labelled = False
 
-    def match(self, embedding, k: int = 1, threshold: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+    def set_labels(self, start: int, tags=None, groups=None):
+        """Label the rows from local row `start` on: `tags` uint64 bit sets (the bits' meaning is the caller's), `groups`
+        int32 group numbers >= 0, or -1 for "its own group".  Either may be None: that label stays as it is.  New rows
+        start with tag 0 / group -1; `set_row` keeps a row's labels, `clear` resets them."""
+        t = None if tags is None else np.ascontiguousarray(np.asarray(tags).reshape(-1).astype(np.uint64, copy=False))
+        g = None if groups is None else np.asarray(groups).reshape(-1)
+        if g is not None:
+            assert g.size == 0 or (g.min() >= -(2**31) and g.max() < 2**31), "groups must fit int32"
+            g = np.ascontiguousarray(g.astype(np.int32))
+        if t is None and g is None:
+            return
+        n = t.size if t is not None else g.size
+        assert g is None or t is None or g.size == t.size, f"{t.size} tags for {g.size} groups"
+        with torch.cuda.device(self.device):
+            native.check(
+                native.lib().mtgv_bank_set_labels(
+                    self._h, int(start), int(n), None if t is None else t.ctypes.data_as(native.c_vp),
+                    None if g is None else g.ctypes.data_as(native.c_vp), native.stream()
+                )
+            )
+        self.labelled = True
+
+    def labels(self, start: int, n: int) -> Tuple[np.ndarray, np.ndarray]:
+        """(tags uint64 (n,), groups int32 (n,)) of the local rows [start, start + n)."""
+        t = np.empty(int(n), np.uint64)
+        g = np.empty(int(n), np.int32)
+        with torch.cuda.device(self.device):
+            native.check(native.lib().mtgv_bank_get_labels(self._h, int(start), int(n), t.ctypes.data_as(native.c_vp), g.ctypes.data_as(native.c_vp)))
+        return t, g
+
+    def _masks(self, filter, b: int) -> torch.Tensor:
+        """`filter` of match() -> (b, 3) int64 bit patterns on the device"""
+        if isinstance(filter, torch.Tensor):
+            assert filter.dtype == torch.int64 and tuple(filter.shape) == (b, 3), f"filter: {tuple(filter.shape)} {filter.dtype}, expected ({b}, 3) int64"
+            return filter.to(self.device).contiguous()
+        if isinstance(filter, np.ndarray):
+            assert filter.dtype == np.uint64 and filter.shape == (b, 3), f"filter: {filter.shape} {filter.dtype}, expected ({b}, 3) uint64"
+            return torch.from_numpy(np.ascontiguousarray(filter).view(np.int64)).to(self.device)
+        assert len(filter) == 3 and all(isinstance(v, (int, np.integer)) and 0 <= int(v) < 2**64 for v in filter), (
+            "filter: one (all_of, any_of, none_of) triple of 64-bit masks, or a (B, 3) array"
+        )
+        row = np.array([int(v) for v in filter], np.uint64).view(np.int64)
+        return torch.from_numpy(np.broadcast_to(row, (b, 3)).copy()).to(self.device)
+
+    def match(self, embedding, k: int = 1, threshold: Optional[float] = None, *, filter=None, distinct: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
         """(D,) or (B,D) raw embeddings -> (ids int64 (B,k), scores float32 (B,k)) on the GPU.
 
         Sorted by cosine score descending, ties by ascending id; id -1 / score -inf pads
         when the bank holds fewer than k rows.  `threshold` is `score_threshold` of
         `query_nearby` (mtgvision/qdrant.py:83,93): hits scoring below it are dropped on the
-        device (they become pads)."""
+        device (they become pads).
+
+        `filter`: only rows whose tags pass (all_of, any_of, none_of) take part - one triple of ints for all queries, or
+        a (B, 3) array (numpy uint64, or a torch int64 bit pattern).  `distinct`: a group >= 0 is represented by its
+        best row only, so the k hits are k different cards.  Both are exact (include/mtgv.h, mtgv_bank_topk_ex); the
+        defaults make the same call as before."""
         if isinstance(embedding, np.ndarray) or isinstance(embedding, (list, tuple)):
             embedding = torch.from_numpy(np.ascontiguousarray(np.asarray(embedding, dtype=np.float32)))
         q = embedding.to(self.device, torch.float32)
@@ -91,13 +143,20 @@ class Matcher:
         b = q.shape[0]
         ids = torch.empty((b, k), dtype=torch.int64, device=self.device)
         scores = torch.empty((b, k), dtype=torch.float32, device=self.device)
+        masks = None if filter is None else self._masks(filter, b)
         if b == 0:
             return ids, scores
         with torch.cuda.device(self.device):
-            native.check(
-                native.lib().mtgv_bank_topk(self._h, native.ptr(q), b, int(k), self.id_base, _thr(threshold), native.ptr(ids), native.ptr(scores),
-                                            native.stream())
-            )
+            if masks is None and not distinct:
+                native.check(
+                    native.lib().mtgv_bank_topk(self._h, native.ptr(q), b, int(k), self.id_base, _thr(threshold), native.ptr(ids), native.ptr(scores),
+                                                native.stream())
+                )
+            else:
+                native.check(
+                    native.lib().mtgv_bank_topk_ex(self._h, native.ptr(q), b, int(k), self.id_base, _thr(threshold), native.ptr(masks),
+                                                   1 if distinct else 0, native.ptr(ids), native.ptr(scores), native.stream())
+                )
         return ids, scores
 
     def match_packed(self, q: torch.Tensor, k: int = 1) -> torch.Tensor:

@@ -183,9 +183,12 @@ class TrackedPipeline:
     the current stream.  The overlapped schedule of `Pipeline.run_many` is not offered: the read-back of n_due would stall
     the stream that holds it."""
 
-    def __init__(self, pipeline, streams: int, top_k: int = 3, max_tracks: int = 64, **policy):
+    def __init__(self, pipeline, streams: int, top_k: int = 3, max_tracks: int = 64, match_opts: Optional[dict] = None, **policy):
+        """match_opts: keyword arguments for `Matcher.match` (`filter`, `distinct`, `threshold`): {"distinct": True} makes a
+        track's top_k matches top_k different cards (the bank's rows carry groups).  None: the plain match."""
         self.pipeline = pipeline
         self.top_k = int(top_k)
+        self.match_opts = dict(match_opts) if match_opts else None
         self.tracker = DeviceTracker(streams, pipeline.K, pipeline.encoder.cfg.z_size, self.top_k, max_tracks, pipeline.detector.device, **policy)
         self.last_z = None  # the embeddings committed by the last step (n_due, dim), None when nothing was due
 
@@ -229,7 +232,8 @@ class TrackedPipeline:
         if n_due > 0:
             z = p.encoder.encode(trk.gather(crops)[:n_due])
             q = trk.commit(z)
-            ids, scores = trk.store(*p.matcher.match(q, self.top_k))
+            hits = p.matcher.match(q, self.top_k) if self.match_opts is None else p.matcher.match(q, self.top_k, **self.match_opts)
+            ids, scores = trk.store(*hits)
             self.last_z = z
         else:
             ids, scores = trk.store()
