@@ -442,6 +442,24 @@ MTGV_API void mtgv_jpeg_decoder_destroy(mtgv_jpeg_decoder* h);
 MTGV_API int mtgv_jpeg_decode(mtgv_jpeg_decoder* h, const uint8_t* data_host, const int64_t* offsets, const int64_t* sizes,
                               int32_t n, uint8_t* dst_dev, const int64_t* dst_offset, const int64_t* dst_pitch,
                               int32_t* status_dev, void* stream);
+/* Progressive files (version 106): SOF2, Huffman, 8-bit, the same component layouts, restart intervals, Huffman tables
+ * redefined between scans, any scan script T.81 Annex G allows whose progression is complete (every coefficient of
+ * every component is in some scan and the last scan over it has Al = 0; libjpeg would smooth an incomplete file, which
+ * is not restated).  Output equals libjpeg-turbo's default decode, as for baseline.  Opt-in per call and per handle: */
+#define MTGV_JPEG_PROGRESSIVE 1
+/* mtgv_jpeg_info with flags: 0 is mtgv_jpeg_info; with MTGV_JPEG_PROGRESSIVE a progressive file inside the subset is
+ * reported as supported.  info[0..5] as above, info[6] = progressive (0 / 1), info[7] = number of scans (1 when
+ * info[6] = 0).  An illegal scan script is malformed input (1, the message names the SOS); an incomplete progression
+ * and arithmetic coding (SOF10) are unsupported (0, info[5] = 0, the message names the reason). */
+MTGV_API int mtgv_jpeg_info_ex(const uint8_t* data, int64_t nbytes, int32_t flags, int32_t* info);
+/* mtgv_jpeg_decoder_create with flags.  With MTGV_JPEG_PROGRESSIVE, mtgv_jpeg_decode on this handle takes batches that
+ * mix baseline and progressive files (a handle from mtgv_jpeg_decoder_create refuses progressive files as before);
+ * baseline images are decoded exactly as on a plain handle.  max_scans: scans of all progressive files of one batch
+ * (Pillow writes 10 per colour file, 6 per greyscale file), 0 selects 16 * max_images; a batch with more is refused
+ * before any launch.  The extra workspace (scan records, two more Huffman tables per scan, restart-segment offsets:
+ * about 2 * max_bytes more pinned and device memory) is allocated here, never inside a decode. */
+MTGV_API int mtgv_jpeg_decoder_create_ex(int32_t max_images, int64_t max_bytes, int64_t max_pixels, int32_t flags, int64_t max_scans,
+                                         mtgv_jpeg_decoder** out);
 
 /* ------------------------------------------------------------------------- */
 /* JPEG encode: the card thumbnails of mtgvision/server.py:222-225 (encode_rgb_im:           */

@@ -29,6 +29,11 @@
 //                              (jdcolor tables) -> RGB uint8 at the caller's offset / pitch
 // Every decode loop is bounded by the stream length.  A stream that does not decode sets its image's status word; the
 // write, dc, idct and color launches then skip that image, so nothing is written outside its workspace and slot.
+//
+// Progressive files (SOF2) are taken by a handle created with MTGV_JPEG_PROGRESSIVE only.  Such an image has no stream of
+// its own in the launches above (ImgDesc.prog: no tiles, chunks or restart segments); its coefficient blocks are
+// assembled scan by scan by jpeg_prog.hip, launched between dc and idct, and idct / color then run over the whole batch.
+// A batch without progressive files runs exactly the eleven launches above, on either kind of handle.
 #include <string.h>
 
 #include <algorithm>
@@ -37,6 +42,7 @@
 #include "common.h"
 #include "jpeg_common.h"
 #include "jpeg_host.h"
+#include "jpeg_prog.h"
 #include "mtgv.h"
 
 using namespace mtgv;
@@ -124,6 +130,7 @@ __global__ __launch_bounds__(64) void unstuff_scan_kernel(Params P) {
   const int i = blockIdx.x * 64 + threadIdx.x;
   if (i >= P.n) return;
   const ImgDesc& D = P.d[i];
+  if (D.prog) return;  // no stream of its own: jpeg_prog.hip
   int off = 0, moff = 0;
   for (int64_t t = P.tile_base[i]; t < P.tile_base[i + 1]; ++t) {
     P.tile_cnt[t * 4 + 2] = off;
@@ -407,6 +414,7 @@ __global__ __launch_bounds__(256) void count_kernel(Params P, int64_t nchunks) {
 __global__ __launch_bounds__(64) void verify_kernel(Params P) {
   const int i = blockIdx.x;
   const ImgDesc& D = P.d[i];
+  if (D.prog) return;  // prog_finish_kernel sets its ok / status
   const int lane = threadIdx.x;
   const int64_t cb = P.chunk_base[i], ce = P.chunk_base[i + 1];
   int64_t run_total = 0;
@@ -688,15 +696,59 @@ MTGV_API int mtgv_jpeg_info(const uint8_t* data, int64_t nbytes, int32_t* info) 
   });
 }
 
+MTGV_API int mtgv_jpeg_info_ex(const uint8_t* data, int64_t nbytes, int32_t flags, int32_t* info) {
+  return guarded([&] {
+    MTGV_CHECK(info != nullptr, ERR_INVALID, "null info");
+    MTGV_CHECK((flags & ~MTGV_JPEG_PROGRESSIVE) == 0, ERR_INVALID, "jpeg: unknown flags 0x%x", flags);
+    Parsed p;
+    parse(data, nbytes, p);
+    info[0] = p.h;
+    info[1] = p.w;
+    info[2] = p.ncomp;
+    info[3] = p.sampling;
+    info[4] = p.ri;
+    info[5] = p.supported;
+    info[6] = 0;
+    info[7] = 1;
+    std::string why = p.why;
+    if (!p.supported && (flags & MTGV_JPEG_PROGRESSIVE)) {
+      ProgParsed pp;
+      parse_progressive(data, nbytes, pp);
+      if (pp.progressive) {
+        info[0] = pp.h;
+        info[1] = pp.w;
+        info[2] = pp.ncomp;
+        info[3] = pp.sampling;
+        info[4] = pp.ri;
+        info[5] = pp.supported;
+        info[6] = 1;
+        info[7] = (int32_t)pp.scans.size();
+        why = pp.why;
+      }
+    }
+    set_last_error(info[5] ? std::string() : "jpeg: unsupported: " + why);
+  });
+}
+
 MTGV_API int mtgv_jpeg_decoder_create(int32_t max_images, int64_t max_bytes, int64_t max_pixels, mtgv_jpeg_decoder** out) {
+  return mtgv_jpeg_decoder_create_ex(max_images, max_bytes, max_pixels, 0, 0, out);
+}
+
+MTGV_API int mtgv_jpeg_decoder_create_ex(int32_t max_images, int64_t max_bytes, int64_t max_pixels, int32_t flags, int64_t max_scans,
+                                         mtgv_jpeg_decoder** out) {
   return guarded([&] {
     MTGV_CHECK(out != nullptr, ERR_INVALID, "null out");
     *out = nullptr;
+    MTGV_CHECK((flags & ~MTGV_JPEG_PROGRESSIVE) == 0, ERR_INVALID, "jpeg: unknown flags 0x%x", flags);
+    const bool prog = (flags & MTGV_JPEG_PROGRESSIVE) != 0;
+    MTGV_CHECK(max_scans >= 0 && max_scans <= (1 << 24) && (prog || max_scans == 0), ERR_INVALID,
+               "jpeg: max_scans %lld (0 .. 2^24, and 0 without MTGV_JPEG_PROGRESSIVE)", (long long)max_scans);
     MTGV_CHECK(max_images >= 1 && max_bytes >= 1 && max_pixels >= 1, ERR_INVALID, "limits must be positive: %d images, %lld bytes, %lld pixels",
                max_images, (long long)max_bytes, (long long)max_pixels);
     MTGV_CHECK(max_bytes < (1ll << 31) && max_pixels < (1ll << 34), ERR_INVALID, "limits too large");
     auto* h = new mtgv_jpeg_decoder();
-    const DecoderCaps& c = h->caps = decoder_caps(max_images, max_bytes, max_pixels);
+    const DecoderCaps& c = h->caps = !prog ? decoder_caps(max_images, max_bytes, max_pixels)
+                                           : decoder_caps(max_images, max_bytes, max_pixels, max_scans ? max_scans : 16ll * max_images);
     const int64_t n = max_images;
     Work& w = h->work;
     try {
@@ -747,7 +799,7 @@ MTGV_API int mtgv_jpeg_decode(mtgv_jpeg_decoder* h, const uint8_t* data_host, co
     h->pending = true;
     const int64_t nch = plan.cb()[n], nblk = plan.bb()[n], nseg = plan.sb()[n], ntile = plan.tb()[n], npix = plan.pb()[n];
     HIP_OK(hipMemsetAsync(h->work.err, 0, n * sizeof(int32_t), s));
-    HIP_OK(hipMemsetAsync(h->work.seg_cnt, 0, nseg * sizeof(uint32_t), s));
+    if (nseg) HIP_OK(hipMemsetAsync(h->work.seg_cnt, 0, nseg * sizeof(uint32_t), s));
     // ---- launch
     Params P;
     const int64_t* db = (const int64_t*)(h->d_stage + plan.o_base);
@@ -763,15 +815,34 @@ MTGV_API int mtgv_jpeg_decode(mtgv_jpeg_decoder* h, const uint8_t* data_host, co
     static_cast<Work&>(P) = h->work;
     P.dst = dst_dev;
     P.status = status_dev;
-    hipLaunchKernelGGL(unstuff_count_kernel, dim3((unsigned)ntile), dim3(256), 0, s, P);
-    hipLaunchKernelGGL(unstuff_scan_kernel, dim3(ceil_div(n, 64)), dim3(64), 0, s, P);
-    hipLaunchKernelGGL(unstuff_scatter_kernel, dim3((unsigned)ntile), dim3(256), 0, s, P);
-    hipLaunchKernelGGL(sync_kernel, dim3((unsigned)ceil_div64(nch, SYNC_WG)), dim3(SYNC_WG), 0, s, P, nch);
-    hipLaunchKernelGGL(sync_fix_kernel, dim3(ceil_div(n, 64)), dim3(64), 0, s, P);
-    hipLaunchKernelGGL(count_kernel, dim3((unsigned)ceil_div64(nch, 256)), dim3(256), 0, s, P, nch);
-    hipLaunchKernelGGL(verify_kernel, dim3(n), dim3(64), 0, s, P);
-    hipLaunchKernelGGL(write_kernel, dim3((unsigned)ceil_div64(nch, 256)), dim3(256), 0, s, P, nch);
-    hipLaunchKernelGGL(dc_kernel, dim3((unsigned)nseg), dim3(256), 0, s, P);
+    if (plan.nprog < n) {  // the baseline images (always, on a handle without MTGV_JPEG_PROGRESSIVE)
+      hipLaunchKernelGGL(unstuff_count_kernel, dim3((unsigned)ntile), dim3(256), 0, s, P);
+      hipLaunchKernelGGL(unstuff_scan_kernel, dim3(ceil_div(n, 64)), dim3(64), 0, s, P);
+      hipLaunchKernelGGL(unstuff_scatter_kernel, dim3((unsigned)ntile), dim3(256), 0, s, P);
+      hipLaunchKernelGGL(sync_kernel, dim3((unsigned)ceil_div64(nch, SYNC_WG)), dim3(SYNC_WG), 0, s, P, nch);
+      hipLaunchKernelGGL(sync_fix_kernel, dim3(ceil_div(n, 64)), dim3(64), 0, s, P);
+      hipLaunchKernelGGL(count_kernel, dim3((unsigned)ceil_div64(nch, 256)), dim3(256), 0, s, P, nch);
+      hipLaunchKernelGGL(verify_kernel, dim3(n), dim3(64), 0, s, P);
+      hipLaunchKernelGGL(write_kernel, dim3((unsigned)ceil_div64(nch, 256)), dim3(256), 0, s, P, nch);
+      hipLaunchKernelGGL(dc_kernel, dim3((unsigned)nseg), dim3(256), 0, s, P);
+    }
+    if (plan.nprog > 0) {  // the progressive ones: their coefficients assembled scan by scan (jpeg_prog.hip)
+      ProgArgs A;
+      A.d = P.d;
+      A.tabs = P.tabs;
+      A.scans = (const ScanDesc*)(h->d_stage + plan.o_scan);
+      A.item_base = (const int64_t*)(h->d_stage + plan.o_item);
+      A.seg_off = (const uint32_t*)(h->d_stage + plan.o_seg);
+      A.ecs = P.ecs;
+      A.blk_base = P.blk_base;
+      A.coef = P.coef;
+      A.err = P.err;
+      A.ok = P.ok;
+      A.status = P.status;
+      A.n = n;
+      A.nscans = (int32_t)plan.scans.size();
+      launch_progressive(A, plan, s);
+    }
     hipLaunchKernelGGL(idct_kernel, dim3((unsigned)ceil_div64(nblk, 32)), dim3(256), 0, s, P, nblk);
     hipLaunchKernelGGL(color_kernel, dim3((unsigned)ceil_div64(npix, 256)), dim3(256), 0, s, P, npix);
     HIP_OK(hipGetLastError());

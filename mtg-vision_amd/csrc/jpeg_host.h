@@ -39,6 +39,39 @@ void parse(const uint8_t* d, int64_t n, Parsed& p);
 // canonical codes of a DHT table; false if a code does not fit its length (libjpeg: no all-ones code)
 bool huff_codes(const uint8_t* bits, int* maxcode, int* valoff, uint16_t* lut, const uint8_t* val);
 
+// One scan of a progressive file (SOF2), as parse_progressive() reads it
+struct ProgScan {
+  int ns = 0;                // components in the scan
+  int comp[4] = {0, 0, 0, 0};  // index of each in the frame
+  int ss = 0, se = 0, ah = 0, al = 0;
+  int ri = 0;                // restart interval in force at this SOS (0: none)
+  int64_t ecs = 0, ecs_len = 0;  // entropy-coded bytes, stuffing and RSTn markers included
+  std::vector<uint32_t> rst;     // for each RSTn marker: the byte after it, relative to ecs
+  bool rst_in_order = true;      // the markers count 0..7 cyclically
+  // the Huffman tables the scan decodes with, as defined when its SOS was read: tab[j] of component j for a DC first
+  // scan, tab[0] for an AC scan, none for a DC refinement scan
+  struct Tab {
+    uint8_t bits[17];
+    uint8_t val[256];
+  };
+  std::vector<Tab> tab;
+};
+
+struct ProgParsed {
+  bool progressive = false;  // false: the frame is not SOF2 and nothing else below is set; parse() has the verdict
+  int h = 0, w = 0, ncomp = 0, sampling = 0, ri = 0, supported = 0;  // ri: the first scan's restart interval
+  std::string why;
+  Parsed::Comp comp[4];
+  uint16_t qt[4][64];  // by table index, natural order, as defined when the first SOS was read
+  std::vector<ProgScan> scans;
+};
+
+// The second walk, for progressive files: frame header, then every scan with its components, Ss / Se / Ah / Al, restart
+// interval, table snapshot and entropy-coded byte range.  Throws ERR_INVALID (naming the marker) on malformed input and
+// on a scan script T.81 Annex G does not allow; sets p.why on a well-formed file outside the subset, among them an
+// incomplete progression (some coefficient of some component is never brought to Al = 0).  Never reads past d[n - 1].
+void parse_progressive(const uint8_t* d, int64_t n, ProgParsed& p);
+
 // what a decoder handle holds: the caller's limits and the element counts of the workspaces sized from them
 struct DecoderCaps {
   int max_images;
@@ -47,9 +80,13 @@ struct DecoderCaps {
   int64_t ecs;     // bytes of entropy-coded data, each image padded to 8 bytes + 8 (the bit-stream workspace adds 256)
   int64_t chunks, tiles, segs, blocks;
   int64_t plane;   // bytes of the plane workspace
+  // progressive handles (0 otherwise): scans per batch, restart segments of all scans (+ one entry per scan)
+  int64_t max_scans, prog_segs;
 };
 
 DecoderCaps decoder_caps(int max_images, int64_t max_bytes, int64_t max_pixels);
+// a handle that also takes progressive files; max_scans: scans per batch over all its progressive images
+DecoderCaps decoder_caps(int max_images, int64_t max_bytes, int64_t max_pixels, int64_t max_scans);
 
 // one batch, checked against the capacities: everything the launches trust
 struct DecodePlan {
@@ -64,10 +101,22 @@ struct DecodePlan {
   const int64_t* sb() const { return bases.data() + 2 * (n + 1); }  // restart segments
   const int64_t* tb() const { return bases.data() + 3 * (n + 1); }  // unstuffing tiles
   const int64_t* pb() const { return bases.data() + 4 * (n + 1); }  // pixels
+  // progressive images (caps.max_scans > 0 only; all empty / zero for a batch without one).  Such an image has
+  // ds[i].prog = 1 and no chunks, tiles or restart segments in the arrays above; its scans are records of their own,
+  // sorted by dependency level, staged between the bases and the entropy-coded bytes.
+  int nprog = 0;
+  std::vector<ProgParsed> pps;      // n entries; progressive == false for a baseline image
+  std::vector<ScanDesc> scans;      // level 1 first
+  std::vector<int64_t> item_base;   // scans.size() + 1: prefix of nseg, the work items (scan, restart segment)
+  std::vector<uint32_t> seg_off;    // per scan nseg + 1 byte offsets within its entropy-coded bytes
+  std::vector<int32_t> level_scan;  // levels + 1: scans [level_scan[l], level_scan[l + 1]) have level l + 1
+  std::vector<int64_t> scan_src;    // per scan: byte offset of its entropy-coded bytes in the caller's data
+  int64_t o_scan = 0, o_item = 0, o_seg = 0;
+  int levels() const { return level_scan.empty() ? 0 : (int)level_scan.size() - 1; }
 };
 
 // parses every image (n >= 1) and lays the batch out; throws before anything is written if an image is malformed or
-// unsupported or the batch does not fit `caps`
+// unsupported or the batch does not fit `caps`.  Progressive files are accepted when caps.max_scans > 0.
 DecodePlan plan_decode(const DecoderCaps& caps, const uint8_t* data_host, const int64_t* offsets, const int64_t* sizes, int n,
                        const int64_t* dst_offset, const int64_t* dst_pitch);
 

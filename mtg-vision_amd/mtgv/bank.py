@@ -50,7 +50,8 @@ def make_cropped(images: Sequence[np.ndarray], size_hw=(192, 128), device=None) 
 
 def make_cropped_jpeg(datas: Sequence[bytes], size_hw=(192, 128), device=None, decoder=None) -> torch.Tensor:
     """list of JPEG card scans -> (n, h, w, 3) float32 in [0,1] on the GPU: one batched GPU decode into the ragged layout,
-    then the same make_cropped launch.  Unsupported or corrupt files raise (mtgv.jpeg.JpegDecoder)."""
+    then the same make_cropped launch.  Baseline and progressive files, in any mix (a `decoder` passed in is used as
+    given).  Unsupported or corrupt files raise (mtgv.jpeg.JpegDecoder)."""
     from .jpeg import JpegDecoder, _padded_pixels, jpeg_info
 
     native.require_gpu()
@@ -61,7 +62,9 @@ def make_cropped_jpeg(datas: Sequence[bytes], size_hw=(192, 128), device=None, d
     if n == 0:
         return out
     if decoder is None:
-        decoder = JpegDecoder(n, sum(len(d) for d in datas), sum(_padded_pixels(jpeg_info(d)) for d in datas), dev)
+        infos = [jpeg_info(d, progressive=True) for d in datas]
+        decoder = JpegDecoder(n, sum(len(d) for d in datas), sum(_padded_pixels(f) for f in infos), dev, progressive=True,
+                              max_scans=max(1, sum(f.scans for f in infos if f.progressive)))
     buf, offs_t, hw_t, _ = decoder.decode(datas)
     with torch.cuda.device(dev):
         native.check(native.lib().mtgv_make_cropped(native.ptr(buf), native.ptr(offs_t), native.ptr(hw_t), n, oh, ow, native.ptr(out), native.stream()))
@@ -69,8 +72,8 @@ def make_cropped_jpeg(datas: Sequence[bytes], size_hw=(192, 128), device=None, d
 
 
 def build_bank_jpeg(cards: Iterable[Tuple[str, bytes]], encoder: Encoder, store: VectorStoreQdrant, batch_size: int = 256) -> int:
-    """build_bank over (id, JPEG bytes) pairs: each batch is decoded on the GPU (make_cropped_jpeg).  Returns the number
-    of cards added."""
+    """build_bank over (id, JPEG bytes) pairs: each batch is decoded on the GPU (make_cropped_jpeg), baseline and progressive
+    files alike - downloaded card scans are routinely progressive.  Returns the number of cards added."""
     from .jpeg import JpegDecoder, _padded_pixels, jpeg_info
 
     h, w, _ = encoder.input_hwc
@@ -88,9 +91,12 @@ def build_bank_jpeg(cards: Iterable[Tuple[str, bytes]], encoder: Encoder, store:
         if not todo:
             return
         datas = [d for _, d in todo]
-        nb, pix = sum(len(d) for d in datas), sum(_padded_pixels(jpeg_info(d)) for d in datas)
-        if dec is None or dec.max_images < len(datas) or dec.max_bytes < nb or dec.max_pixels < pix:
-            dec = JpegDecoder(batch_size, max(nb, dec.max_bytes if dec else 0), max(pix, dec.max_pixels if dec else 0), encoder.device)
+        infos = [jpeg_info(d, progressive=True) for d in datas]
+        nb, pix = sum(len(d) for d in datas), sum(_padded_pixels(f) for f in infos)
+        scans = sum(f.scans for f in infos if f.progressive)
+        if dec is None or dec.max_images < len(datas) or dec.max_bytes < nb or dec.max_pixels < pix or dec.max_scans < scans:
+            dec = JpegDecoder(batch_size, max(nb, dec.max_bytes if dec else 0), max(pix, dec.max_pixels if dec else 0), encoder.device,
+                              progressive=True, max_scans=max(scans, 16 * batch_size, dec.max_scans if dec else 0))
         x = make_cropped_jpeg(datas, (h, w), encoder.device, dec)
         z = encoder.encode(x).cpu().numpy()
         store.save_points(QdrantPoint(id=str(cid), vector=zi, payload=None) for (cid, _), zi in zip(todo, z))

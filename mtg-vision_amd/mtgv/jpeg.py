@@ -1,4 +1,4 @@
-"""Baseline JPEG decode on the GPU (csrc/jpeg.hip).
+"""JPEG decode on the GPU: baseline, and progressive on request (csrc/jpeg.hip, csrc/jpeg_prog.hip).
 
 The reference decodes every frame on the host (mtgvision/server.py:272-280: cv2.imdecode(..., IMREAD_COLOR_RGB)) and
 reads card scans from JPEG files for the bank build (qdrant_populate.py:70-90).  Here the compressed bytes go to the
@@ -12,6 +12,13 @@ Supported: baseline / extended sequential Huffman 8-bit (SOF0 / SOF1), greyscale
 restart intervals.  The output equals libjpeg-turbo's default decode (Pillow's `Image.open(f).convert("RGB")`).
 Anything else raises before a launch; there is no host fallback inside the library - a caller that wants one checks
 `jpeg_info(data).supported` itself.
+
+Progressive files (SOF2, Huffman, 8-bit, the same component layouts; what optimising encoders such as mozjpeg write by
+default) are opt-in: `jpeg_info(data, progressive=True)`, `JpegDecoder(..., progressive=True)`,
+`JpegFrames(..., progressive=True)`.  Such a decoder takes batches that mix baseline and progressive files, with the same
+exact output; the bank-build helpers (mtgv.bank.make_cropped_jpeg / build_bank_jpeg) create theirs that way.  Refused:
+an illegal scan script, arithmetic coding, more scans per batch than `max_scans`, and an incomplete progression (some
+coefficient never reaches Al = 0: libjpeg would smooth such a file).  Without the option everything behaves as before.
 """
 
 from __future__ import annotations
@@ -34,17 +41,24 @@ class JpegInfo(NamedTuple):
     restart_interval: int  # MCUs per restart segment, 0 none
     supported: bool
     reason: str  # first unsupported feature ("" when supported)
+    progressive: bool = False  # SOF2 (only reported by jpeg_info(..., progressive=True))
+    scans: int = 1
 
 
-def jpeg_info(data: bytes) -> JpegInfo:
-    """Header probe on the host (no device needed).  Raises AssertionError for malformed input."""
+def jpeg_info(data: bytes, progressive: bool = False) -> JpegInfo:
+    """Header probe on the host (no device needed).  Raises AssertionError for malformed input.  progressive=True: what a
+    JpegDecoder(progressive=True) takes - a progressive file inside the subset is supported, with its number of scans."""
     L = native.lib()
-    info = (C.c_int32 * 6)()
+    info = (C.c_int32 * 8)()
     buf = C.create_string_buffer(bytes(data), len(data)) if len(data) else None
-    native.check(L.mtgv_jpeg_info(buf, len(data), info))
+    if progressive:
+        native.check(L.mtgv_jpeg_info_ex(buf, len(data), native.JPEG_PROGRESSIVE, info))
+    else:
+        native.check(L.mtgv_jpeg_info(buf, len(data), info))
+        info[6], info[7] = 0, 1
     sup = bool(info[5])
     reason = "" if sup else (L.mtgv_last_error() or b"").decode("utf-8", "replace")
-    return JpegInfo(info[0], info[1], info[2], info[3], info[4], sup, reason)
+    return JpegInfo(info[0], info[1], info[2], info[3], info[4], sup, reason, bool(info[6]), info[7])
 
 
 def _pack(datas: Sequence[bytes]):
@@ -64,18 +78,27 @@ def _p(a: np.ndarray):
 class JpegDecoder:
     """Batched GPU JPEG decoder.  Limits (fixed here, workspace allocated once): max_images per call, max_bytes of
     compressed data per call, max_pixels per call counted after padding each image to whole MCUs (8 or 16 pixels).
+    progressive=True: the decoder also takes progressive files, mixed with baseline ones in any batch; max_scans bounds
+    the scans of all progressive files of one batch (None: 16 * max_images; Pillow writes 10 per colour file).
     Not thread-safe; calls run on the current stream of `device`."""
 
-    def __init__(self, max_images: int, max_bytes: int, max_pixels: int, device=None):
+    def __init__(self, max_images: int, max_bytes: int, max_pixels: int, device=None, progressive: bool = False, max_scans: int = None):
         native.require_gpu()
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
         self.max_images, self.max_bytes, self.max_pixels = int(max_images), int(max_bytes), int(max_pixels)
+        self.progressive = bool(progressive)
+        assert max_scans is None or self.progressive, "max_scans needs progressive=True"
+        self.max_scans = 0 if max_scans is None else int(max_scans)
         self._h = native.c_vp(0)
         with torch.cuda.device(self.device):
-            native.check(native.lib().mtgv_jpeg_decoder_create(self.max_images, self.max_bytes, self.max_pixels, C.byref(self._h)))
+            if self.progressive:
+                native.check(native.lib().mtgv_jpeg_decoder_create_ex(self.max_images, self.max_bytes, self.max_pixels, native.JPEG_PROGRESSIVE,
+                                                                      self.max_scans, C.byref(self._h)))
+            else:
+                native.check(native.lib().mtgv_jpeg_decoder_create(self.max_images, self.max_bytes, self.max_pixels, C.byref(self._h)))
 
     def _infos(self, datas: Sequence[bytes]) -> List[JpegInfo]:
-        infos = [jpeg_info(d) for d in datas]
+        infos = [jpeg_info(d, self.progressive) for d in datas]
         bad = [(i, f.reason) for i, f in enumerate(infos) if not f.supported]
         if bad:
             raise AssertionError(f"jpeg: unsupported input (no GPU decode; decode these on the host): {bad}")
@@ -223,8 +246,9 @@ class JpegFrames:
     which the caller reads once the pipeline's outputs are synchronised (reading it earlier would stall the overlap)."""
 
     def __init__(self, jpeg_batches: Sequence[Sequence[bytes]], device, size: int = 640, pad_value: int = 114, depth: int = 3,
-                 decoder: JpegDecoder = None, input_hw=None):
-        """input_hw = (in_h, in_w): buffers of a rectangular detector's input (JpegDecoder.decode_frames)"""
+                 decoder: JpegDecoder = None, input_hw=None, progressive: bool = False):
+        """input_hw = (in_h, in_w): buffers of a rectangular detector's input (JpegDecoder.decode_frames);
+        progressive: the decoder created here also takes progressive frames (a `decoder` passed in is used as given)"""
         assert depth >= 2 and len(jpeg_batches) > 0
         self.batches = [list(b) for b in jpeg_batches]
         self.device = torch.device(device)
@@ -234,8 +258,10 @@ class JpegFrames:
         n = max(len(b) for b in self.batches)
         if decoder is None:
             nbytes = max(sum(len(d) for d in b) for b in self.batches)
-            pix = max(sum(_padded_pixels(jpeg_info(d)) for d in b) for b in self.batches)
-            decoder = JpegDecoder(n, nbytes, pix, self.device)
+            infos = [[jpeg_info(d, progressive) for d in b] for b in self.batches]
+            pix = max(sum(_padded_pixels(f) for f in b) for b in infos)
+            scans = max(sum(f.scans for f in b if f.progressive) for b in infos) if progressive else None
+            decoder = JpegDecoder(n, nbytes, pix, self.device, progressive=progressive, max_scans=max(scans, 1) if progressive else None)
         self.dec = decoder
         self.s_dec = torch.cuda.Stream(self.device)
         self.bufs = [torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=self.device) for _ in range(depth)]

@@ -94,6 +94,8 @@ class TrackerCfg(C.Structure):
     )
 
 
+JPEG_PROGRESSIVE = 1  # MTGV_JPEG_PROGRESSIVE: the flag of mtgv_jpeg_info_ex / mtgv_jpeg_decoder_create_ex
+
 # name -> (restype, argtypes); every symbol include/mtgv.h declares
 SIGNATURES = {
     "mtgv_last_error": (C.c_char_p, []),
@@ -169,6 +171,8 @@ SIGNATURES = {
     "mtgv_letterbox_pad_rect_u8": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "mtgv_jpeg_info": (C.c_int, [c_vp, c_i64, C.POINTER(c_i32)]),
     "mtgv_jpeg_decoder_create": (C.c_int, [c_i32, c_i64, c_i64, C.POINTER(c_vp)]),
+    "mtgv_jpeg_info_ex": (C.c_int, [c_vp, c_i64, c_i32, C.POINTER(c_i32)]),  # mtgv_version >= 106
+    "mtgv_jpeg_decoder_create_ex": (C.c_int, [c_i32, c_i64, c_i64, c_i32, c_i64, C.POINTER(c_vp)]),
     "mtgv_jpeg_decoder_destroy": (None, [c_vp]),
     "mtgv_jpeg_decode": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "mtgv_jpeg_encode_bound": (C.c_int, [c_i32, c_i32, c_i32, C.POINTER(c_i64)]),
