@@ -347,6 +347,40 @@ MTGV_API int mtgv_mask_quads(const uint8_t* masks_dev, int32_t n, int32_t h, int
 MTGV_API int mtgv_mask_quads_logits(const float* logits_dev, int32_t n, int32_t mh, int32_t mw, int32_t scale,
                                     const float* boxes_dev, float* quads_dev, int32_t* ok_dev, int32_t* extents_dev, void* stream);
 
+/* Mask -> contour points: ultralytics `masks.xy` (ops.masks2segments behind od_export.py:152-153:
+ * cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE) per mask), added in version 107.  unpinned: cv2 / ultralytics absent -
+ * the specification is the host function mtgv.adapters._mask_segments, which the kernel reproduces point for point:
+ *   - foreground: masks_dev (n, h, w) uint8 != 0.  Pixels outside the image are background.
+ *   - blobs are 8-connected and numbered in raster order of their first pixel (scipy.ndimage.label, 3 x 3 structure); a blob
+ *     inside another blob's hole is a blob of its own, holes are not reported.
+ *   - one blob's trace starts at the leftmost pixel of its top row with back = 0; neighbour order W, NW, N, NE, E, SE, S, SW;
+ *     from cur, the first set neighbour d in the order back, back + 1, ... (mod 8) becomes cur and back = (d + 5) % 8; the walk
+ *     stops as soon as cur is the start pixel again, from whatever direction, or when no neighbour is set.  That rule cuts
+ *     some shapes short - of an inverted V only the apex and one arm are visited - and the kernel cuts them the same way.
+ *   - CHAIN_APPROX_SIMPLE: on the closed chain point i is kept iff p[i] - p[i-1] != p[i+1] - p[i] (cyclic); chains of at most
+ *     two points are kept whole; trace order is preserved.
+ *   - strategy 0 ("all"): the blobs' chains concatenated in blob order; 1 ("largest"): the chain with the most kept points,
+ *     the first of equals.
+ * points_dev (n, max_points, 2) int32 receives (x, y) in mask pixels, n_points_dev (n) the number written, n_blobs_dev (n) or
+ * NULL the number of blobs, status_dev (n): 0 ok, 1 over a cap - more than max_points points (n_points = max_points, the
+ * first max_points of the result are written), more than 4096 row runs or more than 1024 blobs in the mask (n_points = 0).
+ * Nothing is written outside a mask's own slot, slots behind n_points are left as they were; an empty mask has 0 points,
+ * 0 blobs, status 0.  One workgroup per mask with the mask as a bit image in LDS; every loop is bounded before it starts (a
+ * trace by 8 x the mask's foreground pixels).  Deterministic: no atomic decides a position.  workspace_dev: at least
+ * mtgv_mask_contours_workspace_bytes(n, h, w, max_points) bytes, 16-byte aligned.  Status 1 ("mask_contours: ...", checked
+ * before any device call): n, h, w or max_points < 1, an unknown strategy, a mask too large for LDS (640 x 640 fits), a short
+ * workspace, scale < 1.  Asynchronous on `stream`; library kernels only. */
+MTGV_API size_t mtgv_mask_contours_workspace_bytes(int32_t n, int32_t h, int32_t w, int32_t max_points);
+MTGV_API int mtgv_mask_contours(const uint8_t* masks_dev, int32_t n, int32_t h, int32_t w, int32_t strategy, int32_t max_points,
+                                int32_t* points_dev, int32_t* n_points_dev, int32_t* n_blobs_dev, int32_t* status_dev,
+                                void* workspace_dev, size_t workspace_bytes, void* stream);
+/* the same from the cropped mask logits (n, mh, mw): foreground is what mtgv_mask_binarize writes for them (bilinear x`scale`,
+ * align_corners = False, > 0); the (mh*scale, mw*scale) mask is never materialised (workspace: h = mh*scale, w = mw*scale).
+ * Identical points to mtgv_mask_binarize + mtgv_mask_contours. */
+MTGV_API int mtgv_mask_contours_logits(const float* logits_dev, int32_t n, int32_t mh, int32_t mw, int32_t scale, int32_t strategy,
+                                       int32_t max_points, int32_t* points_dev, int32_t* n_points_dev, int32_t* n_blobs_dev,
+                                       int32_t* status_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+
 /* The K cards of every frame that go on to the crop stage: the K highest-confidence detections of the padded
  * mtgv_detector_forward outputs (n_det (frames), boxes (frames, max_det, 4), score-descending) or, where a frame has
  * fewer, pad_boxes_dev[k] (k, 4).  Writes sel_boxes_dev (frames*k, 4) xyxy, frame_idx_dev (frames*k) and, unless null,

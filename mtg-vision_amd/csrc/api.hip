@@ -99,7 +99,7 @@ MTGV_API const char* mtgv_last_error(void) { return last_error_cstr(); }
 // 103: mtgv_detector_cfg.scale, mtgv_op_stem_u8; 104: the mtgv_tracker_* calls;
 // 105: bank row labels (mtgv_bank_set_labels / _get_labels / mtgv_bank_topk_ex);
 // 106: progressive JPEG (mtgv_jpeg_info_ex / mtgv_jpeg_decoder_create_ex, MTGV_JPEG_PROGRESSIVE)
-MTGV_API int mtgv_version(void) { return 106; }
+MTGV_API int mtgv_version(void) { return 107; }
 MTGV_API int mtgv_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;

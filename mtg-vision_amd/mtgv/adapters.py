@@ -22,7 +22,7 @@ import numpy as np
 import torch
 
 from . import spec
-from .crop import mask_quads_from_logits, warp_quads
+from .crop import contours_from_logits_packed, mask_quads_from_logits, warp_quads
 from .detector import Detector, binarize_masks, fit_geometry, rect_geometry
 from .encoder import Encoder
 from .matcher import Matcher
@@ -310,14 +310,21 @@ class CardSegmenter:
     models are not loadable without the package (and are never unpickled here)."""
 
     RECT_HANDLES = 4  # rect=True: Detector handles kept at a time, one per input rectangle
+    TRACE_MAX_POINTS = 4096  # contours="trace": point capacity per mask on the GPU; a mask with more is traced on the host
 
     def __init__(self, model_path: str | Path = None, *, state_dict=None, detector: Optional[Detector] = None, max_batch: int = 1,
                  contours="trace", rect: bool = False):
         """contours: what `InstanceSeg.points` holds (the reference: ultralytics `masks.xy`, od_export.py:152-153).
-        "trace" (default; True is accepted for it): the reference-shaped points - every mask (640 x 640; in_h x in_w of a rectangular handle) is copied to the
-        host and its blobs are traced there like cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE) (`_mask_segments`;
-        scipy), notches of the reference's U-shaped card masks (od_export.py:57-60) included; the quad and the closed
-        polygon are derived lazily on the host as `InstanceSeg._orient` does.
+        "trace" (default; True is accepted for it): the reference-shaped points - the blobs of every mask (640 x 640; in_h x
+        in_w of a rectangular handle) traced like cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE), notches of the
+        reference's U-shaped card masks (od_export.py:57-60) included.  The trace runs on the GPU straight from the mask
+        logits (contours.hip, `mtgv.crop.mask_contours_from_logits`): no mask is materialised or leaves the device; the
+        host receives the point counts, then the used part of the point buffer (at most TRACE_MAX_POINTS points per
+        card).  A mask over one of the kernel's caps (status 1: too many points, row runs or blobs - speckle, not a
+        card), and only that mask, is binarised, copied and traced on the host instead; the points are the same either
+        way.  The quad and the closed polygon are derived lazily on the host as `InstanceSeg._orient` does.
+        "trace_host": the same points with every mask copied to the host and traced there (`_mask_segments`; scipy and
+        a Python Moore tracer, about 10 ms per card mask) - the specification of "trace" and its fallback.
         "outline": the opt-in fast path - the mask's outline as the GPU's row extents (left edge top to bottom, right edge
         bottom to top, at most 2 x 640 points) with the oriented quad fitted on the GPU (quads.hip); one device-to-host
         copy of those integers per call, no mask leaves the device.  A row-extent outline FILLS any notch that opens
@@ -332,7 +339,7 @@ class CardSegmenter:
         kept, the least recently used is dropped.  `self.yolo` is then the handle of the last call (None before the first)."""
         if contours is True:
             contours = "trace"
-        assert contours in ("outline", "trace", False), contours
+        assert contours in ("outline", "trace", "trace_host", False), contours
         self.contours = contours
         self.rect = bool(rect)
         self._rect_handles: "OrderedDict[tuple, Detector]" = OrderedDict()
@@ -385,10 +392,25 @@ class CardSegmenter:
             p[..., 1] = np.clip(p[..., 1], 0, fh)
             return p
 
-        if self.contours == "trace":
+        if self.contours == "trace_host":
             masks = binarize_masks(det.mask_logits).cpu().numpy()
             for m, conf in zip(masks, det.conf.cpu().numpy()):
                 pts = _mask_segments(m)  # masks.xy: all blobs' outlines, run end points
+                if len(pts) == 0:
+                    continue
+                detections.append(InstanceSeg(points=to_frame(pts).astype(np.float32), label=0, conf=np.asarray(conf).tolist()))
+            return detections
+        if self.contours == "trace":
+            # masks.xy traced on the GPU (contours.hip): the counts first, then the used part of the point buffer
+            points, counts = contours_from_logits_packed(det.mask_logits, max_points=self.TRACE_MAX_POINTS)
+            counts = counts.cpu().numpy()
+            n_pts, status = counts[0], counts[2]
+            used = points[:, : max(int(n_pts.max()), 1)].cpu().numpy()
+            for i, conf in enumerate(det.conf.cpu().numpy()):
+                if status[i] != 0:  # over a cap of the kernel: this mask alone is traced on the host
+                    pts = _mask_segments(binarize_masks(det.mask_logits[i : i + 1])[0].cpu().numpy())
+                else:
+                    pts = used[i, : n_pts[i]].astype(np.float32)
                 if len(pts) == 0:
                     continue
                 detections.append(InstanceSeg(points=to_frame(pts).astype(np.float32), label=0, conf=np.asarray(conf).tolist()))

@@ -121,6 +121,57 @@ def mask_quads(masks_u8: torch.Tensor, boxes_xyxy: torch.Tensor = None, extents:
     return (quads, ok, ext) if extents else (quads, ok)
 
 
+CONTOUR_STRATEGIES = {"all": 0, "largest": 1}
+
+
+def _contours_call(entry, src: torch.Tensor, dims, h: int, w: int, strategy: str, max_points: int):
+    """shared tail of `mask_contours` / `mask_contours_from_logits`: outputs, workspace, one library call"""
+    if strategy not in CONTOUR_STRATEGIES:
+        raise ValueError(f"unknown strategy {strategy!r}")
+    n, dev, max_points = src.shape[0], src.device, int(max_points)
+    points = torch.empty((n, max_points, 2), dtype=torch.int32, device=dev)  # only [:n_points] of a row is written
+    counts = torch.empty((3, n), dtype=torch.int32, device=dev)  # rows: n_points, n_blobs, status
+    if n > 0:
+        L = native.lib()
+        ws_bytes = int(L.mtgv_mask_contours_workspace_bytes(n, h, w, max_points))
+        ws = torch.empty((ws_bytes + 15) // 16 * 4, dtype=torch.int32, device=dev)
+        with torch.cuda.device(dev):
+            native.check(entry(L)(native.ptr(src.contiguous()), n, *dims, CONTOUR_STRATEGIES[strategy], max_points, native.ptr(points),
+                                  native.ptr(counts[0]), native.ptr(counts[1]), native.ptr(counts[2]), native.ptr(ws), ws.numel() * 4,
+                                  native.stream()))
+    return points, counts
+
+
+def mask_contours(masks_u8: torch.Tensor, strategy: str = "all", max_points: int = 4096):
+    """masks (n, H, W) uint8 on the GPU (non-zero = card) -> (points (n, max_points, 2) int32, n_points (n,), n_blobs (n,),
+    status (n,)) int32 device tensors: ultralytics' `masks.xy` of every mask, what `mtgv.adapters._mask_segments(mask, strategy)`
+    returns on the host (the outlines of the 8-connected blobs as cv2.findContours(RETR_EXTERNAL, CHAIN_APPROX_SIMPLE) reports
+    them, "all" blobs in raster order or the "largest" chain), traced on the GPU (contours.hip; include/mtgv.h has the rules).
+    points[i, :n_points[i]] are (x, y) mask pixels; the rest of a row is uninitialised.  status 1: the mask is over a cap
+    (max_points, or the kernel's run / blob capacity) and its points are incomplete - trace that mask on the host."""
+    native.require_gpu()
+    assert masks_u8.is_cuda and masks_u8.dtype == torch.uint8 and masks_u8.ndim == 3, f"{tuple(masks_u8.shape)} {masks_u8.dtype}"
+    _, h, w = masks_u8.shape
+    points, counts = _contours_call(lambda L: L.mtgv_mask_contours, masks_u8, (h, w), h, w, strategy, max_points)
+    return points, counts[0], counts[1], counts[2]
+
+
+def mask_contours_from_logits(mask_logits: torch.Tensor, scale: int = 4, strategy: str = "all", max_points: int = 4096):
+    """(n, mh, mw) cropped mask logits -> `mask_contours` of the (mh*scale, mw*scale) masks `binarize_masks` would produce,
+    without materialising them (one kernel: interpolate, threshold, label, trace)."""
+    points, counts = contours_from_logits_packed(mask_logits, scale, strategy, max_points)
+    return points, counts[0], counts[1], counts[2]
+
+
+def contours_from_logits_packed(mask_logits: torch.Tensor, scale: int = 4, strategy: str = "all", max_points: int = 4096):
+    """`mask_contours_from_logits` with the three count vectors as the rows of one (3, n) tensor (n_points, n_blobs, status):
+    a caller that wants them on the host makes one copy"""
+    native.require_gpu()
+    assert mask_logits.is_cuda and mask_logits.dtype == torch.float32 and mask_logits.ndim == 3
+    _, mh, mw = mask_logits.shape
+    return _contours_call(lambda L: L.mtgv_mask_contours_logits, mask_logits, (mh, mw, int(scale)), mh * int(scale), mw * int(scale), strategy, max_points)
+
+
 def mask_quads_from_logits(mask_logits: torch.Tensor, boxes_xyxy: torch.Tensor = None, scale: int = 4, extents: bool = False):
     """(n, mh, mw) cropped mask logits -> (quads, ok [, extents]) of the (mh*scale, mw*scale) masks `binarize_masks` would
     produce, without materialising them (one kernel: interpolate, threshold, row extents, hull, approxPolyN, orientation)."""
