@@ -60,7 +60,7 @@ MTGV_API int mtgv_device_count(void);
  * MTGV_DET_FORK=0 keeps the forward on one stream).  mtgv.Pipeline overlaps its stages (detect + crop / embed / match: three streams, the
  * latter two at high priority, the detector's fork-join off) only with MTGV_OVERLAP=on, and then runs nothing but library kernels on them - its output tensors are uninitialised allocations filled by the
  * kernels, the glue between the stages is mtgv_select_cards / mtgv_obb_cards - plus, with a sharded bank, RCCL's own all-gather kernels
- * (mtgv_bank_topk_packed / mtgv_topk_merge_gathered keep every other step of the exchange inside the library).  A caller
+ * (mtgv_bank_topk_packed / mtgv_topk_merge_gathered and their _ex forms keep every other step of the exchange inside the library).  A caller
  * that runs foreign kernels (PyTorch elementwise ops included) concurrently on a second stream must either serialise
  * them against the library's stream or select MTGV_PREC_F32. */
 #define MTGV_PREC_F32 0
@@ -170,7 +170,7 @@ MTGV_API int mtgv_bank_get_labels(const mtgv_bank* h, int64_t row0, int64_t n, u
  * not replaced by another row of its group).  Masks that admit no row are not an error: k pads.  The result is the
  * exact filtered / distinct top k.  With masks_dev == NULL and distinct == 0 the call IS mtgv_bank_topk (two-pass
  * pre-pass included); otherwise it always runs the one-pass exact kernel with the labelled epilogue, whatever b is.
- * Single-bank: the sharded exchange (mtgv_bank_topk_packed) does not carry labels.
+ * Over a row-sharded bank the same answer comes from mtgv_bank_topk_packed_ex / mtgv_topk_merge_gathered_ex (below).
  * The first labelled call on a bank whose labels were never set allocates the label arrays and synchronises the device
  * once (so do mtgv_bank_set_labels and, on a labelled bank, mtgv_bank_clear): make it before capturing a stream. */
 MTGV_API int mtgv_bank_topk_ex(mtgv_bank* h, const float* q_dev, int32_t b, int32_t k, int64_t id_base, float score_threshold,
@@ -194,6 +194,31 @@ MTGV_API int mtgv_bank_topk_packed(mtgv_bank* h, const float* q_dev, int32_t b, 
                                    void* stream);
 MTGV_API int mtgv_topk_merge_gathered(const int64_t* gathered_dev, int32_t n_ranks, int32_t b_total, int32_t k, int32_t row0, int32_t b,
                                       float score_threshold, int64_t* ids_dev, float* scores_dev, void* stream);
+/* Row labels across the sharded exchange (version 108): mtgv_bank_topk_ex over a bank split by rows.  Group numbers are the
+ * caller's and mean the same on every shard; the rows of one group may lie on several shards.
+ *   mtgv_bank_topk_packed_ex   the labelled match (masks_dev, distinct as mtgv_bank_topk_ex; both absent: status 1) of ALL
+ *     ranks' queries over this rank's shard - always the one-pass exact kernel; with distinct the shard's duplicates of a
+ *     group are removed here already - written in the labelled exchange format packed[b][k][2] int64:
+ *       word 0            global id (row + id_base), or -1
+ *       word 1, low 32    float32 bit pattern of the score (as in the unlabelled format)
+ *       word 1, high 32   the row's group as uint32 (group -1 = 0xFFFFFFFF)
+ *     Pads are (id -1, -inf, group -1).  The message has the size of the unlabelled one, and mtgv_topk_merge_gathered reads
+ *     it as it is (it takes the low half of word 1): a filter-only exchange needs no other merge.  No threshold here - it
+ *     belongs to the merge.  An empty shard is not an error for this call: it writes b * k pads and returns 0, since a
+ *     rank that failed would leave the others waiting in the collective.  (mtgv_bank_topk_packed keeps its zero high half
+ *     and its error on an empty bank.)  The note on the first labelled call of mtgv_bank_topk_ex applies.
+ *   mtgv_topk_merge_gathered_ex   distinct == 0: mtgv_topk_merge_gathered itself.  distinct != 0: gathered must be in the
+ *     labelled format; the n_ranks * k candidates of a query are walked in order (score desc, global id asc), a picked
+ *     candidate retires every other candidate of its non-negative group, the first k picks are the result, and the
+ *     threshold is applied last (a representative below it becomes a pad and is not replaced).  n_ranks * k <= 4096.
+ *     The result does not depend on the order of the ranks.
+ * Together they return exactly what mtgv_bank_topk_ex returns over the whole bank, ids and score bits (DESIGN.md section
+ * 6 has the argument).  Every rank must make the same choice of masks-or-not and of distinct.  masks_dev holds the masks
+ * of all b queries, so with per-query filters the caller gathers them beside the queries (mtgv/dist.py). */
+MTGV_API int mtgv_bank_topk_packed_ex(mtgv_bank* h, const float* q_dev, int32_t b, int32_t k, int64_t id_base, const uint64_t* masks_dev,
+                                      int32_t distinct, int64_t* packed_dev, void* stream);
+MTGV_API int mtgv_topk_merge_gathered_ex(const int64_t* gathered_dev, int32_t n_ranks, int32_t b_total, int32_t k, int32_t row0, int32_t b,
+                                         float score_threshold, int32_t distinct, int64_t* ids_dev, float* scores_dev, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Detector: YOLOv8 / YOLO11 at scales n, s, m, -seg (forward + decode + NMS  */

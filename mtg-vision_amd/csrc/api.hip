@@ -99,7 +99,8 @@ MTGV_API const char* mtgv_last_error(void) { return last_error_cstr(); }
 // 103: mtgv_detector_cfg.scale, mtgv_op_stem_u8; 104: the mtgv_tracker_* calls;
 // 105: bank row labels (mtgv_bank_set_labels / _get_labels / mtgv_bank_topk_ex);
 // 106: progressive JPEG (mtgv_jpeg_info_ex / mtgv_jpeg_decoder_create_ex, MTGV_JPEG_PROGRESSIVE)
-MTGV_API int mtgv_version(void) { return 107; }
+// 108: labels across the sharded exchange (mtgv_bank_topk_packed_ex / mtgv_topk_merge_gathered_ex)
+MTGV_API int mtgv_version(void) { return 108; }
 MTGV_API int mtgv_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -266,6 +267,25 @@ MTGV_API int mtgv_topk_merge_gathered(const int64_t* gathered_dev, int32_t n_ran
     MTGV_CHECK(gathered_dev && ids_dev && scores_dev, ERR_INVALID, "null argument");
     MTGV_CHECK(!(score_threshold != score_threshold), ERR_INVALID, "topk_merge_gathered: score_threshold is NaN");
     topk_merge_gathered_launch(gathered_dev, n_ranks, b_total, k, row0, b, score_threshold, ids_dev, scores_dev, (hipStream_t)stream);
+  });
+}
+MTGV_API int mtgv_bank_topk_packed_ex(mtgv_bank* h, const float* q_dev, int32_t b, int32_t k, int64_t id_base, const uint64_t* masks_dev,
+                                      int32_t distinct, int64_t* packed_dev, void* stream) {
+  return guarded([&] {
+    MTGV_CHECK(h != nullptr && packed_dev != nullptr, ERR_INVALID, "null argument");
+    h->impl.topk_packed_labelled(q_dev, b, k, id_base, masks_dev, distinct != 0, packed_dev, (hipStream_t)stream);
+  });
+}
+MTGV_API int mtgv_topk_merge_gathered_ex(const int64_t* gathered_dev, int32_t n_ranks, int32_t b_total, int32_t k, int32_t row0, int32_t b,
+                                         float score_threshold, int32_t distinct, int64_t* ids_dev, float* scores_dev, void* stream) {
+  return guarded([&] {
+    MTGV_CHECK(gathered_dev && ids_dev && scores_dev, ERR_INVALID, "null argument");
+    MTGV_CHECK(!(score_threshold != score_threshold), ERR_INVALID, "topk_merge_gathered: score_threshold is NaN");
+    if (distinct == 0)  // groups play no part: mtgv_topk_merge_gathered itself
+      topk_merge_gathered_launch(gathered_dev, n_ranks, b_total, k, row0, b, score_threshold, ids_dev, scores_dev, (hipStream_t)stream);
+    else
+      topk_merge_gathered_distinct_launch(gathered_dev, n_ranks, b_total, k, row0, b, score_threshold, ids_dev, scores_dev,
+                                          (hipStream_t)stream);
   });
 }
 MTGV_API int mtgv_bank_prepass_fallbacks(const mtgv_bank* h, int64_t* count) {

@@ -145,8 +145,12 @@ SpPlan gemm_sp_plan(const GemmArgs& a) {
   if (a.batch != 1 || a.crop_boxes != nullptr || a.m_count != nullptr || a.ln_w != nullptr) return none();
   if (a.topk > 0) {  // match path: SP_CFG_TOPK tiles, f32 queries by DMA (SP_A_F32), fused top-k (gemm_sp_kernel.h, SP_EPI_TOPK)
     const SpTile& k1 = kSpTile[SP_CFG_TOPK];
+    // A labelled match keeps this kernel however few rows the bank has (one ragged tile: rows past N are clamped on load and
+    // score -inf): a row shard of a small bank then runs the kernel the whole bank runs, and the sharded labelled match
+    // returns the single bank's score bits (mtgv_bank_topk_packed_ex).  Unlabelled launches keep their rule.
+    const bool narrow = a.N < k1.bn() && !topk_labelled(a);
     if (sp8_in || conv || a.K % 8 != 0 || a.c_total % 8 != 0 || a.c_off % 8 != 0 || ((uintptr_t)a.A & 15) != 0 || a.a_scale != nullptr ||
-        a.a_mul != 1.0f || a.res != nullptr || a.act != ACT_NONE || a.M < k1.bm() || a.N < k1.bn() || !operand_sp8(a.W, a.K, nullptr, nullptr))
+        a.a_mul != 1.0f || a.res != nullptr || a.act != ACT_NONE || a.M < k1.bm() || narrow || !operand_sp8(a.W, a.K, nullptr, nullptr))
       return none();
     return plan_of(SP_CFG_TOPK, a.M, a.N);
   }

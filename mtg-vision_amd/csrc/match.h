@@ -28,6 +28,11 @@ class Bank {
   // distinct: a group >= 0 is represented by its best row only.  Same order, threshold and pad rules as topk.
   void topk_labelled(const float* q, int b, int k, int64_t id_base, float thr, const uint64_t* masks, bool distinct, int64_t* ids,
                      float* scores, hipStream_t s);
+  // topk_labelled over this bank as one row shard, in the labelled exchange format: packed[b][k][2] int64 = (id, the row's
+  // group as uint32 << 32 | float32 bits of the score); pads are (-1, group -1, -inf).  No threshold (the merge applies
+  // it); an empty bank writes pads.
+  void topk_packed_labelled(const float* q, int b, int k, int64_t id_base, const uint64_t* masks, bool distinct, int64_t* packed,
+                            hipStream_t s);
   // queries of two-pass matches so far whose answer the first pass could not prove and that were scanned exactly
   // (synchronises the device)
   int64_t prepass_fallbacks() const;
@@ -52,6 +57,10 @@ class Bank {
 // the queries [row0, row0 + b)
 void topk_merge_gathered_launch(const int64_t* gathered, int R, int b_total, int k, int row0, int b, float thr, int64_t* ids,
                                 float* scores, hipStream_t s);
+// the same over candidates in the labelled exchange format, one result per group >= 0: picking a candidate retires every
+// other candidate of its group
+void topk_merge_gathered_distinct_launch(const int64_t* gathered, int R, int b_total, int k, int row0, int b, float thr, int64_t* ids,
+                                         float* scores, hipStream_t s);
 void topk_merge_launch_i64(float* cs, const int64_t* ci, int b, int ncand, int k, float thr, int64_t* ids, float* scores,
                            hipStream_t s);
 

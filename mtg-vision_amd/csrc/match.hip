@@ -25,10 +25,28 @@ __device__ __forceinline__ void store_result(long* __restrict__ out_ids, float* 
   }
 }
 
+// The labelled exchange format (Bank::topk_packed_labelled): word 1 also carries the row's group in its high half (uint32;
+// -1 = 0xFFFFFFFF, pads too), which is all the cross-shard merge needs to dedupe; readers of the unlabelled format take
+// the low half only.
+__device__ __forceinline__ long pack_score_group(float score, int group) {
+  return (long)(((unsigned long)(unsigned)group << 32) | (unsigned long)__float_as_uint(score));
+}
+__device__ __forceinline__ void store_result(long* __restrict__ packed, long slot, long id, float score, int group) {
+  packed[2 * slot] = id;
+  packed[2 * slot + 1] = pack_score_group(score, group);
+}
+
+// the labelled exchange message of an empty shard: every slot a pad (id -1, -inf, group -1)
+__global__ __launch_bounds__(256) void packed_pads_kernel(long* __restrict__ packed, long slots) {
+  const long i = (long)blockIdx.x * 256 + threadIdx.x;
+  if (i < slots) store_result(packed, i, -1, -INFINITY, -1);
+}
+
 // DISTINCT (labelled matches, Bank::topk_labelled): candidate ids are bank rows, so a candidate's group is groups[id];
 // after a pick every candidate of the winner's group (>= 0) is retired with it.  The candidate ranges dedupe too
 // (gemm_sp_kernel.h SP_EPI_TOPK_LABELS, gemm_kernel.h EPI 3): a merge-only dedupe would miss rows hidden inside a range.
-template <typename IdT, bool DISTINCT = false>
+// PACK_GROUP: out_ids is the labelled exchange format (out_scores is not read).
+template <typename IdT, bool DISTINCT = false, bool PACK_GROUP = false>
 __global__ __launch_bounds__(256) void topk_merge_kernel(float* __restrict__ cs, const IdT* __restrict__ ci, int ncand, int k,
                                                         long id_base, float thr, long* __restrict__ out_ids,
                                                         float* __restrict__ out_scores, const int* __restrict__ groups = nullptr) {
@@ -62,7 +80,10 @@ __global__ __launch_bounds__(256) void topk_merge_kernel(float* __restrict__ cs,
       // score_threshold (qdrant.py:83,93): candidates below it are not results - id -1 / score -inf pads, like a
       // bank with fewer than k rows
       const bool ok = rp[0] >= 0 && rs[0] >= thr;
-      store_result(out_ids, out_scores, (long)b * k + kk, ok ? ri[0] + id_base : -1, ok ? rs[0] : -INFINITY);
+      if constexpr (PACK_GROUP)
+        store_result(out_ids, (long)b * k + kk, ok ? ri[0] + id_base : -1, ok ? rs[0] : -INFINITY, ok ? groups[ri[0]] : -1);
+      else
+        store_result(out_ids, out_scores, (long)b * k + kk, ok ? ri[0] + id_base : -1, ok ? rs[0] : -INFINITY);
       if (rp[0] >= 0) s[rp[0]] = -INFINITY;  // retire
     }
     __syncthreads();
@@ -337,6 +358,86 @@ void topk_merge_gathered_launch(const int64_t* gathered, int R, int b_total, int
   HIP_OK(hipGetLastError());
 }
 
+// The same merge for distinct matches over candidates in the labelled exchange format (Bank::topk_packed_labelled): a
+// candidate's group is the high half of its word 1, and after a pick every other candidate of the winner's group (>= 0)
+// is retired with it - two shards may each report a row of one card, and only the better one represents it.  LDS holds
+// (score, group) per candidate: 32 KiB at the 4096-candidate cap, so with the reduction scratch the block stays inside
+// the 64 KiB a launch gets without an opt-in; ids stay in the gathered buffer and are read where a candidate leads or
+// ties.  Picks are decided by (score desc, id asc) alone, never by which rank a candidate came from.
+__global__ __launch_bounds__(256) void topk_merge_gathered_distinct_kernel(const long* __restrict__ gathered, int R, int b_total, int k,
+                                                                          int row0, float thr, long* __restrict__ out_ids,
+                                                                          float* __restrict__ out_scores) {
+  extern __shared__ __attribute__((aligned(16))) char gd_sm[];
+  const int ncand = R * k;
+  float* cs = reinterpret_cast<float*>(gd_sm);
+  int* cg = reinterpret_cast<int*>(gd_sm + (size_t)ncand * sizeof(float));
+  __shared__ float rs[256];
+  __shared__ long ri[256];
+  __shared__ int rp[256];
+  const int b = blockIdx.x, tid = threadIdx.x;
+  auto cand = [&](int p) {
+    const int r = p / k;
+    return gathered + (((long)r * b_total + row0 + b) * k + (p - r * k)) * 2;
+  };
+  for (int p = tid; p < ncand; p += 256) {
+    const long* e = cand(p);
+    const long w = e[1];
+    cs[p] = e[0] >= 0 ? __uint_as_float((unsigned)w) : -INFINITY;  // a pad never takes part
+    cg[p] = (int)(w >> 32);
+  }
+  __syncthreads();
+  for (int kk = 0; kk < k; ++kk) {
+    float bs = -INFINITY;
+    long bi = 0x7fffffffffffffffL;
+    int bp = -1;
+    for (int p = tid; p < ncand; p += 256) {
+      const float v = cs[p];
+      if (v > -INFINITY && v >= bs) {
+        const long i = cand(p)[0];
+        if (v > bs || i < bi) bs = v, bi = i, bp = p;
+      }
+    }
+    rs[tid] = bs, ri[tid] = bi, rp[tid] = bp;
+    __syncthreads();
+    for (int st = 128; st > 0; st >>= 1) {
+      if (tid < st) {
+        const float os = rs[tid + st];
+        const long oi = ri[tid + st];
+        const int op = rp[tid + st];
+        if (op >= 0 && (rp[tid] < 0 || os > rs[tid] || (os == rs[tid] && oi < ri[tid]))) rs[tid] = os, ri[tid] = oi, rp[tid] = op;
+      }
+      __syncthreads();
+    }
+    if (tid == 0) {
+      const bool ok = rp[0] >= 0 && rs[0] >= thr;  // the threshold comes last: a representative below it is a pad, not replaced
+      out_scores[(long)b * k + kk] = ok ? rs[0] : -INFINITY;
+      out_ids[(long)b * k + kk] = ok ? ri[0] : -1;
+    }
+    const int wp = rp[0];  // rp[0] is rewritten only after the barrier below
+    if (wp >= 0) {
+      const int wg = cg[wp];
+      if (wg >= 0) {
+        for (int p = tid; p < ncand; p += 256)
+          if (cg[p] == wg) cs[p] = -INFINITY;  // the winner with its group
+      } else if (tid == 0) {
+        cs[wp] = -INFINITY;  // retire
+      }
+    }
+    __syncthreads();
+  }
+}
+
+void topk_merge_gathered_distinct_launch(const int64_t* gathered, int R, int b_total, int k, int row0, int b, float thr, int64_t* ids,
+                                         float* scores, hipStream_t s) {
+  MTGV_CHECK(R > 0 && k > 0 && b > 0 && row0 >= 0 && row0 + b <= b_total, ERR_INVALID, "topk_merge_gathered: R=%d k=%d rows [%d, %d) of %d", R,
+             k, row0, row0 + b, b_total);
+  MTGV_CHECK((long)R * k <= 4096, ERR_INVALID, "topk_merge_gathered: %d x %d candidates per query (at most 4096)", R, k);
+  const size_t lds = (size_t)R * k * (sizeof(float) + sizeof(int));
+  hipLaunchKernelGGL(topk_merge_gathered_distinct_kernel, dim3(b), dim3(256), lds, s, (const long*)gathered, R, b_total, k, row0, thr,
+                     (long*)ids, scores);
+  HIP_OK(hipGetLastError());
+}
+
 void topk_merge_launch_i64(float* cs, const int64_t* ci, int b, int ncand, int k, float thr, int64_t* ids, float* scores,
                            hipStream_t s) {
   MTGV_CHECK(b > 0 && ncand > 0 && k > 0, ERR_INVALID, "topk_merge: b=%d ncand=%d k=%d", b, ncand, k);
@@ -507,7 +608,8 @@ void Bank::get_labels(int64_t row0, int64_t n, uint64_t* tags_host, int32_t* gro
 // One-pass exact match: normalise the queries, one GEMM launch with the fused top-k epilogue, one merge.  labelled: the
 // launch and the merge honour the row labels (masks may be null: no filter; distinct: one row per group) - every candidate
 // range reports its kt best eligible rows, with `distinct` of pairwise different groups, and the merge dedupes again: the
-// result is the exact filtered / distinct top k (match).
+// result is the exact filtered / distinct top k (match).  labelled with scores == nullptr: ids receives the
+// labelled exchange format, (id, group << 32 | score bits) per result.
 void Bank::topk_one_pass(const float* q, int b, int k, int64_t id_base, float thr, bool labelled, const uint64_t* masks, bool distinct,
                          int64_t* ids, float* scores, hipStream_t s) {
   qn_.ensure((size_t)b * dim_);
@@ -531,7 +633,14 @@ void Bank::topk_one_pass(const float* q, int b, int k, int64_t id_base, float th
   g.cand_i = reinterpret_cast<int*>(cand_i_.p);
   g.topk = kt;
   gemm_launch(g, s);
-  if (labelled && distinct)
+  if (labelled && scores == nullptr) {  // the labelled exchange format: every result with its row's group
+    if (distinct)
+      hipLaunchKernelGGL((topk_merge_kernel<int, true, true>), dim3(b), dim3(256), 0, s, cand_s_.p, (const int*)cand_i_.p, (int)ncand, k,
+                         (long)id_base, thr, (long*)ids, scores, g.col_groups);
+    else
+      hipLaunchKernelGGL((topk_merge_kernel<int, false, true>), dim3(b), dim3(256), 0, s, cand_s_.p, (const int*)cand_i_.p, (int)ncand, k,
+                         (long)id_base, thr, (long*)ids, scores, g.col_groups);
+  } else if (labelled && distinct)
     hipLaunchKernelGGL((topk_merge_kernel<int, true>), dim3(b), dim3(256), 0, s, cand_s_.p, (const int*)cand_i_.p, (int)ncand, k,
                        (long)id_base, thr, (long*)ids, scores, g.col_groups);
   else
@@ -549,6 +658,24 @@ void Bank::topk_labelled(const float* q, int b, int k, int64_t id_base, float th
   MTGV_CHECK(size_ > 0, ERR_RUNTIME, "bank is empty");
   ensure_labels();  // (first labelled call on a bank without labels: allocates and synchronises once)
   topk_one_pass(q, b, k, id_base, thr, true, masks, distinct, ids, scores, s);
+}
+
+// The labelled match of a row shard in the exchange format (topk_one_pass, labelled, scores == nullptr).  No threshold here:
+// it belongs to the merge.  An empty shard answers with pads instead of an error - a rank that raised would leave the
+// others waiting in the collective.
+void Bank::topk_packed_labelled(const float* q, int b, int k, int64_t id_base, const uint64_t* masks, bool distinct, int64_t* packed,
+                                hipStream_t s) {
+  MTGV_CHECK(b > 0 && k > 0 && k <= 65536, ERR_INVALID, "bank: b=%d k=%d (k must be in [1,65536])", b, k);
+  MTGV_CHECK(q != nullptr && packed != nullptr, ERR_INVALID, "bank: null tensor");
+  MTGV_CHECK(masks != nullptr || distinct, ERR_INVALID, "bank: a labelled match needs masks or distinct");
+  if (size_ == 0) {
+    const long slots = (long)b * k;
+    hipLaunchKernelGGL(packed_pads_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, (long*)packed, slots);
+    HIP_OK(hipGetLastError());
+    return;
+  }
+  ensure_labels();  // (first labelled call on a bank without labels: allocates and synchronises once)
+  topk_one_pass(q, b, k, id_base, -INFINITY, true, masks, distinct, packed, nullptr, s);
 }
 
 void Bank::topk(const float* q, int b, int k, int64_t id_base, float thr, int64_t* ids, float* scores, hipStream_t s) {

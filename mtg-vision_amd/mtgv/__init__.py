@@ -15,6 +15,7 @@ _LAZY = {
     "ObbDetections": ("detector", "ObbDetections"),
     "Matcher": ("matcher", "Matcher"),
     "merge_topk": ("matcher", "merge_topk"),
+    "ShardedMatcher": ("dist", "ShardedMatcher"),
     "Pipeline": ("pipeline", "Pipeline"),
     "warp_quads": ("crop", "warp_quads"),
     "DeviceTracker": ("track", "DeviceTracker"),

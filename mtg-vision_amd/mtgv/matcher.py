@@ -159,16 +159,26 @@ class Matcher:
                 )
         return ids, scores
 
-    def match_packed(self, q: torch.Tensor, k: int = 1) -> torch.Tensor:
+    def match_packed(self, q: torch.Tensor, k: int = 1, *, filter=None, distinct: bool = False) -> torch.Tensor:
         """The local top-k in the sharded match's exchange format (mtgv.dist, include/mtgv.h): q (B, D) float32 on the
         device, contiguous -> (B, k, 2) int64 = (global id or -1, float32 bit pattern of the score).  One library call,
-        no other kernel: what one all-gather then carries to every rank."""
+        no other kernel: what one all-gather then carries to every rank.
+
+        `filter` (the forms `match` takes; a (B, 3) int64 tensor on the device is used as it is) / `distinct`: the
+        labelled match of this shard (mtgv_bank_topk_packed_ex) - the high half of word 1 then carries the row's group,
+        which `merge_gathered(..., distinct=True)` needs, and an empty shard answers with pads.  The defaults make the
+        same call as before."""
         assert q.is_cuda and q.dtype == torch.float32 and q.ndim == 2 and q.shape[1] == self.dim and q.is_contiguous(), f"{tuple(q.shape)} {q.dtype}"
         b = q.shape[0]
         packed = torch.empty((b, k, 2), dtype=torch.int64, device=self.device)
+        masks = None if filter is None else self._masks(filter, b)
         if b:
             with torch.cuda.device(self.device):
-                native.check(native.lib().mtgv_bank_topk_packed(self._h, native.ptr(q), b, int(k), self.id_base, native.ptr(packed), native.stream()))
+                if masks is None and not distinct:
+                    native.check(native.lib().mtgv_bank_topk_packed(self._h, native.ptr(q), b, int(k), self.id_base, native.ptr(packed), native.stream()))
+                else:
+                    native.check(native.lib().mtgv_bank_topk_packed_ex(self._h, native.ptr(q), b, int(k), self.id_base, native.ptr(masks),
+                                                                       1 if distinct else 0, native.ptr(packed), native.stream()))
         return packed
 
     def prepass_fallbacks(self) -> int:
@@ -204,10 +214,15 @@ def merge_topk(cand_scores: torch.Tensor, cand_ids: torch.Tensor, k: int, thresh
     return ids, scores
 
 
-def merge_gathered(gathered: torch.Tensor, row0: int, b: int, k: int, threshold: Optional[float] = None) -> Tuple[torch.Tensor, torch.Tensor]:
+def merge_gathered(gathered: torch.Tensor, row0: int, b: int, k: int, threshold: Optional[float] = None, *,
+                   distinct: bool = False) -> Tuple[torch.Tensor, torch.Tensor]:
     """Merge the all-gathered per-shard candidates (R, B_total, k, 2) int64 in the exchange format of
     `Matcher.match_packed` for the queries [row0, row0 + b): global (ids (b, k) int64, scores (b, k) float32), score desc
-    then id asc.  One library kernel reads the collective's output buffer in place."""
+    then id asc.  One library kernel reads the collective's output buffer in place.
+
+    `distinct`: the candidates come from `match_packed(..., distinct=True)` on every shard; a picked candidate retires the
+    other candidates of its group (mtgv_topk_merge_gathered_ex), so the result is `Matcher.match(..., distinct=True)` over
+    the whole bank.  Filter-only exchanges merge with the default."""
     assert gathered.is_cuda and gathered.dtype == torch.int64 and gathered.ndim == 4 and gathered.shape[2] == k and gathered.shape[3] == 2
     assert gathered.is_contiguous()
     R, b_total = gathered.shape[0], gathered.shape[1]
@@ -215,6 +230,10 @@ def merge_gathered(gathered: torch.Tensor, row0: int, b: int, k: int, threshold:
     scores = torch.empty((b, k), dtype=torch.float32, device=gathered.device)
     if b:
         with torch.cuda.device(gathered.device):
-            native.check(native.lib().mtgv_topk_merge_gathered(native.ptr(gathered), R, b_total, int(k), int(row0), int(b), _thr(threshold),
-                                                               native.ptr(ids), native.ptr(scores), native.stream()))
+            if not distinct:
+                native.check(native.lib().mtgv_topk_merge_gathered(native.ptr(gathered), R, b_total, int(k), int(row0), int(b), _thr(threshold),
+                                                                   native.ptr(ids), native.ptr(scores), native.stream()))
+            else:
+                native.check(native.lib().mtgv_topk_merge_gathered_ex(native.ptr(gathered), R, b_total, int(k), int(row0), int(b), _thr(threshold),
+                                                                      1, native.ptr(ids), native.ptr(scores), native.stream()))
     return ids, scores

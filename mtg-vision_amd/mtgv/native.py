@@ -105,6 +105,8 @@ SIGNATURES = {
     "mtgv_get_gemm_precision": (C.c_int, [C.POINTER(c_i32)]),
     "mtgv_bank_topk_packed": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i64, c_vp, c_vp]),
     "mtgv_topk_merge_gathered": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp]),
+    "mtgv_bank_topk_packed_ex": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i64, c_vp, c_i32, c_vp, c_vp]),  # mtgv_version >= 108
+    "mtgv_topk_merge_gathered_ex": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_f32, c_i32, c_vp, c_vp, c_vp]),
     "mtgv_letterbox_u8": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "mtgv_letterbox_rect_u8": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "mtgv_profile_gemm": (C.c_int, [c_i32]),

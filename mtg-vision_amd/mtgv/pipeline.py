@@ -92,7 +92,8 @@ def _frames_of(item):
 
 class Pipeline:
     def __init__(self, detector: Detector, encoder: Encoder, matcher, cards_per_frame: int = 8, top_k: int = 1,
-                 match_fn: Optional[Callable] = None, quad_source: str = "box", thumbnail_quality: Optional[int] = None):
+                 match_fn: Optional[Callable] = None, quad_source: str = "box", thumbnail_quality: Optional[int] = None,
+                 match_opts: Optional[dict] = None):
         """quad_source: "box" crops the detection boxes (the synthetic bench workload, SURVEY.md section 8d config 4);
         "mask" crops the oriented quad fitted to each detection's mask, as the reference does
         (od_export.py:52-111: InstanceSeg._orient + extract_dewarped); "obb" (an OBB detector, spec.DetectorConfig(task="obb"))
@@ -102,7 +103,9 @@ class Pipeline:
         thumbnail_quality: when set, every step's crops are also encoded as 4:2:0 JPEG files at that quality on the GPU
         right after the de-warp, on the stream that made them (the thumbnails of mtgvision/server.py:222-225); the
         output gains `thumbs` (packed files, device) and `thumb_offsets` ((F * K + 1,) int64, device), file j being
-        thumbs[thumb_offsets[j]:thumb_offsets[j + 1]].  None (default): no encode, no extra launch."""
+        thumbs[thumb_offsets[j]:thumb_offsets[j + 1]].  None (default): no encode, no extra launch.
+        match_opts: keyword arguments handed to `matcher.match` (threshold, filter, distinct), like TrackedPipeline's;
+        None keeps the call as it is.  `matcher` may be a `mtgv.ShardedMatcher` (the row-sharded bank)."""
         assert quad_source in ("box", "mask", "obb"), quad_source
         task = getattr(getattr(detector, "cfg", None), "task", "seg")
         assert (quad_source == "obb") == (task == "obb"), f'quad_source "{quad_source}" with a {task} detector'
@@ -120,8 +123,13 @@ class Pipeline:
         self.K = int(cards_per_frame)
         self.top_k = int(top_k)
         # a caller-supplied match (bench.py: the sharded bank's local top-k + all-gathers + merge) may issue collectives, which
-        # run on the process group's own normal-priority stream: run_many then keeps every stream at normal priority (below)
-        self._plain_match = match_fn is None
+        # run on the process group's own normal-priority stream: run_many then keeps every stream at normal priority (below);
+        # so does a matcher that says it issues them (ShardedMatcher)
+        self._plain_match = match_fn is None and not getattr(matcher, "issues_collectives", False)
+        assert match_fn is None or not match_opts, "match_opts go to matcher.match: a match_fn takes its own"
+        opts = dict(match_opts or {})
+        if match_fn is None and opts:
+            match_fn = lambda z, k: matcher.match(z, k, **opts)  # noqa: E731
         self.match_fn = match_fn or (lambda z, k: matcher.match(z, k))
         reps = (self.K + _PAD_BOXES.shape[0] - 1) // _PAD_BOXES.shape[0]
         # a rectangular detector (cfg.input_hw): the pad boxes shrink with the frame, (in_w / imgsz, in_h / imgsz), and stay

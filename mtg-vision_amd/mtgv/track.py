@@ -186,6 +186,8 @@ class TrackedPipeline:
     def __init__(self, pipeline, streams: int, top_k: int = 3, max_tracks: int = 64, match_opts: Optional[dict] = None, **policy):
         """match_opts: keyword arguments for `Matcher.match` (`filter`, `distinct`, `threshold`): {"distinct": True} makes a
         track's top_k matches top_k different cards (the bank's rows carry groups).  None: the plain match."""
+        # (each rank has its own number of due tracks; the sharded exchange needs equal query counts on every rank)
+        assert not getattr(pipeline.matcher, "issues_collectives", False), "TrackedPipeline does not run on a sharded bank"
         self.pipeline = pipeline
         self.top_k = int(top_k)
         self.match_opts = dict(match_opts) if match_opts else None
