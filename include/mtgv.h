@@ -221,7 +221,7 @@ MTGV_API int mtgv_topk_merge_gathered_ex(const int64_t* gathered_dev, int32_t n_
                                          float score_threshold, int32_t distinct, int64_t* ids_dev, float* scores_dev, void* stream);
 
 /* ------------------------------------------------------------------------- */
-/* Detector: YOLOv8 / YOLO11 at scales n, s, m, -seg (forward + decode + NMS  */
+/* Detector: YOLOv8 / 11 / 12 at scales n, s, m, -seg (forward + decode + NMS */
 /* + mask logits) or -obb (forward + rotated decode + rotated NMS).           */
 /* Replaces CardSegmenter.__call__ -> ultralytics YOLO predict                */
 /* (mtgvision/od_export.py:141-160; model built in od_train.py:46-70).        */
@@ -235,7 +235,13 @@ typedef struct {
   float conf;        /* 0.25 */
   float iou;         /* 0.7 */
   int32_t max_det;   /* 300 */
-  int32_t arch;      /* 0 or 8: YOLOv8n; 11: YOLO11n (C3k2, C2PSA, depthwise class branch; od_train.py:20) */
+  int32_t arch;      /* 0 or 8: YOLOv8; 11: YOLO11 (C3k2, C2PSA, depthwise class branch; od_train.py:20); 12 (version 109): YOLO12 -
+                      * YOLO11's scale table, C3k2 and class branch, a backbone without SPPF and C2PSA whose nodes 6 and 8 are
+                      * A2C2f blocks (four ABlocks each at n, s, m: area attention over 4 areas at P4 and 1 at P5, heads of 32
+                      * channels, a depthwise 7x7 positional encoding, a 2-layer MLP of ratio 2), A2C2f without attention (C3k
+                      * inside) in the neck, the head at node 21 on nodes 14, 17, 20.  Recalled from ultralytics 8.3.x and
+                      * unpinned like the rest of the detector (least certain: the MLP ratio at scale m); a checkpoint that
+                      * disagrees fails in mtgv_detector_set_param on the element count (status 1).  Anything else: status 2. */
   int32_t task;      /* 0: segment head (-seg); 1: OBB head (-obb, what od_train.py:19, :101 builds by default): no prototypes,
                       * one angle logit per anchor, rotated NMS.  (Added in version 101: the struct grew by this field.) */
   int32_t in_h, in_w; /* the input rectangle (added in version 102: the struct grew by these two fields).  Both 0: imgsz x imgsz.
@@ -600,6 +606,14 @@ MTGV_API int mtgv_op_conv2d_ex(const mtgv_conv_ex* d, int32_t* path, void* strea
  * one; `wide` != 0 runs the wide kernel at 16 channels too (it must give scale n's bits).  Other widths: status 1. */
 MTGV_API int mtgv_op_stem_u8(const uint8_t* frames_dev, const float* w_dev, const float* bias_dev, float* out_dev, int32_t n, int32_t h,
                              int32_t w, int32_t cout, int32_t flip_rgb, int32_t out_sp8, int32_t wide, void* stream);
+/* YOLO12's area attention and its positional encoding alone (version 109; the detector's ABlocks run the same function), f32.
+ * qkv (n, h * w, heads * 96): per head [q 32 | k 32 | v 32], tokens are the pixels row-major.  The h * w tokens of an image
+ * are cut into `area` contiguous chunks of h * w / area tokens (not bands of whole rows) and softmax(q^T k / sqrt(32)) v runs
+ * inside each chunk; out (n, h * w, heads * 32), channel head * 32 + d.  With pe_w49_dev ([49][heads * 32] tap-major, BatchNorm
+ * folded, bias pe_bias_dev [heads * 32]) the depthwise 7x7 (zero padding 3 over the whole h x w map: it crosses the chunks) of
+ * v is added; NULL: attention only.  Status 1, and nothing launched, when h * w % area != 0, heads < 1 or area < 1. */
+MTGV_API int mtgv_op_area_attn(const float* qkv_dev, const float* pe_w49_dev, const float* pe_bias_dev, int32_t n, int32_t h, int32_t w,
+                               int32_t heads, int32_t area, float* out_dev, void* stream);
 /* The detector's prototype branch behind cv1 (Detector::proto runs the same function): ConvTranspose2d(k2, s2, bias) ->
  * cv2 (3x3, BN folded, SiLU) -> cv3 (1x1, BN folded, SiLU), c -> c -> c -> nm channels.  pr1 is an SP8 view of n images of
  * h x w pixels; protos an f32 view of (2 h, 2 w) pixels.  Weights are host pointers: wt (c, c, 2, 2) and bt (c) as

@@ -100,7 +100,8 @@ MTGV_API const char* mtgv_last_error(void) { return last_error_cstr(); }
 // 105: bank row labels (mtgv_bank_set_labels / _get_labels / mtgv_bank_topk_ex);
 // 106: progressive JPEG (mtgv_jpeg_info_ex / mtgv_jpeg_decoder_create_ex, MTGV_JPEG_PROGRESSIVE)
 // 108: labels across the sharded exchange (mtgv_bank_topk_packed_ex / mtgv_topk_merge_gathered_ex)
-MTGV_API int mtgv_version(void) { return 108; }
+// 109: mtgv_detector_cfg.arch = 12 (YOLO12), mtgv_op_area_attn
+MTGV_API int mtgv_version(void) { return 109; }
 MTGV_API int mtgv_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;

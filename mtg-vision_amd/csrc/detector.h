@@ -1,8 +1,10 @@
 // YOLOv8 / YOLO11 executor at scales n, s and m, -seg or -obb: conv stack on the implicit GEMM of gemm_launch (split-precision f16x3 or
 // f32), decode, NMS, mask logits (segment) or rotated decode, rotated NMS (OBB).
-// The two architectures differ in their backbones only (backbone_v8 in detector.hip, backbone_v11 in detector_v11.hip): the
+// The architectures differ in their backbones only (backbone_v8 in detector.hip, backbone_v11 in detector_v11.hip,
+// backbone_v12 in detector_v12.hip): the
 // CSP block, the neck from the first upsample on, the head levels, the key expectations behind the backbone and the
-// arena table are written once (detector.hip), the neck's node numbers shifted by one for YOLO11 (its node 10 is C2PSA).
+// arena table are written once (detector.hip), the neck's node numbers shifted by one for YOLO11 (its node 10 is C2PSA)
+// and by minus one for YOLO12 (it has no SPPF).
 #pragma once
 #include "common.h"
 #include "gemm_f32.h"
@@ -23,6 +25,7 @@ namespace mtgv {
 //   n    0.33, 0.25, 1024            0.50, 0.25, 1024
 //   s    0.33, 0.50, 1024            0.50, 0.50, 1024
 //   m    0.67, 0.75,  768            0.50, 1.00,  512   (YOLO11 m: every C3k2 has c3k = True)
+// YOLO12 (arch 12) has YOLO11's table and its c3k rule.
 static inline int make_div8(double v) { return (int)(ceil(v / 8.0) * 8.0); }
 struct DetScale {
   double depth, width;
@@ -34,7 +37,7 @@ static constexpr int kDetScales = 3;  // n, s, m
 static inline DetScale det_scale(int arch, int scale) {
   static const DetScale v8[kDetScales] = {{0.33, 0.25, 1024}, {0.33, 0.50, 1024}, {0.67, 0.75, 768}};
   static const DetScale v11[kDetScales] = {{0.50, 0.25, 1024}, {0.50, 0.50, 1024}, {0.50, 1.00, 512}};
-  return (arch == 11 ? v11 : v8)[scale];
+  return (arch == 11 || arch == 12 ? v11 : v8)[scale];
 }
 
 // raw head rows per anchor, four whole 128-byte lines: [0,64) box logits (4 sides x 16 bins), [64,96) mask coefficients,
@@ -137,9 +140,14 @@ class Detector {
   void expect_conv_bn(const std::string& prefix, int cout, int cin, int k);
   // CSP block (C2f / C3k2) of node idx: cv1 -> two chunks of ch = cout * e channels, n inner modules each appended to the
   // concat, cv2 over the concat.  The inner module: C2f's Bottleneck(ch -> ch -> ch), C3k2's Bottleneck(ch -> ch / 2 -> ch)
-  // or C3k(ch, ch, 2).
-  enum class Csp { C2f, Half, C3k };
-  struct CspInfo { int cout, n, ch; bool shortcut; Csp kind; };
+  // or C3k(ch, ch, 2).  A2: YOLO12's A2C2f(a2 = False) - cv1 gives ONE chunk of ch = cout / 2 channels, the inner module is
+  // C3k(ch, ch, 2), the concat is (1 + n) ch wide.
+  enum class Csp { C2f, Half, C3k, A2 };
+  struct CspInfo {
+    int cout, n, ch; bool shortcut; Csp kind;
+    int lead() const { return kind == Csp::A2 ? 1 : 2; }          // chunks cv1 writes
+    bool c3k() const { return kind == Csp::C3k || kind == Csp::A2; }
+  };
   void expect_csp(int idx, int cin, int cout, int n, bool shortcut, Csp kind, double e = 0.5);
   void expect_sppf(const std::string& prefix, int c);
   // nodes 10 + k .. 22 + k (k = 1 for YOLO11): the neck's four CSP blocks (`kind`, the P5 one `kind_p5`) and two stride-2
@@ -162,16 +170,23 @@ class Detector {
   // pre: the stride-2 Conv in front of the block (input pre_in) where cv1 is its only consumer: `in` is then that conv's output
   void csp_block(int idx, const View& in, const View& out, int n, hipStream_t s, const ConvW* pre = nullptr, const View* pre_in = nullptr);
   // YOLO11 modules
-  ConvW fold_dw(const std::string& prefix);                         // depthwise 3x3 Conv+BN -> weight [9][c], bias [c]
+  ConvW fold_dw(const std::string& prefix);                         // depthwise k x k Conv+BN -> weight [k * k][c], bias [c]
   void dwconv(const ConvW& w, const View& in, const View& out, int act, const float* add, int g_size, int g_stride, int n,
               hipStream_t s);
   void c3k(const std::string& prefix, const View& x, const View& kcat, const View& tmp, const View& out, bool shortcut, int n, hipStream_t s);
   void c2psa(int idx, const View& in, const View& out, int n, hipStream_t s);
   int chn(int c) const { return sc_.chn(c); }
   int rep(int n) const { return sc_.rep(n); }
-  int shift() const { return v11() ? 1 : 0; }                       // k: node i of the YOLOv8 neck and head is node i + k
+  // YOLO12 modules (detector_v12.hip)
+  struct A2Info { int cout, n, c, area; };                          // A2C2f(a2 = True): hidden width c = cout / 2, c / 32 heads
+  void expect_a2c2f(int idx, int cin, int cout, int n, int area);
+  View a2_view(const char* name, const View& like, int c) const;    // the shared attention buffer `name` as like's map, c wide
+  void ablock(const std::string& prefix, const View& x, const View& y, int area, int n, hipStream_t s);
+  void a2c2f(int idx, const View& in, const View& out, int n, hipStream_t s);
+  int shift() const { return v11() ? 1 : v12() ? -1 : 0; }          // k: node i of the YOLOv8 neck and head is node i + k
   void build_v8();
   void build_v11();
+  void build_v12();
   // activation arena: one entry per buffer of max_batch frames, carved in this order
   struct ArenaBuf { std::string name; int h, w, c; bool f32 = false, seg_only = false; };  // f32: View::f32; seg_only: not on an OBB handle
   std::vector<ArenaBuf> arena() const;
@@ -180,6 +195,7 @@ class Detector {
   void forward_graph(const uint8_t* frames, int n, int flip, hipStream_t s);
   View backbone_v8(int n, hipStream_t s);
   View backbone_v11(int n, hipStream_t s);
+  View backbone_v12(int n, hipStream_t s);
   void neck_and_heads(const View& top, int n, hipStream_t s);
   HeadRows head_rows() const;                                       // the arena's raw head rows (head_decode.h)
   void decode(int n, hipStream_t s);                                // decode_kernel / decode_obb_kernel: raw head rows -> pred
@@ -208,6 +224,8 @@ class Detector {
   hipStream_t fork_after(hipStream_t s, int i);
   void join_into(hipStream_t s, int i);
   bool v11() const { return cfg_.arch == 11; }
+  bool v12() const { return cfg_.arch == 12; }
+  bool dwcls() const { return v11() || v12(); }                     // Detect(legacy=False): the depthwise class branch
   View view(const std::string& k) const;
 
   mtgv_detector_cfg cfg_;
@@ -225,6 +243,7 @@ class Detector {
   // weights
   std::map<std::string, ConvW> cw_;
   std::map<int, CspInfo> csp_;
+  std::map<int, A2Info> a2_;
   ConvW cls_dw1_[3], cls_pw1_[3], cls_dw2_[3], cls_pw2_[3];
   std::string head_ = "model.22";
   // head_first_: the first 3x3 convs of the branches that read the level's features, stacked (v8: box, class and
@@ -247,5 +266,13 @@ class Detector {
   hipEvent_t ev_fork_[NSIDE] = {nullptr, nullptr, nullptr}, ev_join_[NSIDE] = {nullptr, nullptr, nullptr};
   bool side_busy_[NSIDE] = {false, false, false};  // forked in the forward in progress and not joined yet
 };
+
+// Area attention + positional encoding of YOLO12's AAttn (detector_v12.hip), f32.  qkv (n, h * w, heads * 96), per head
+// [q 32 | k 32 | v 32]; tokens are the pixels row-major, cut into `area` contiguous chunks of h * w / area; attention runs
+// inside a chunk.  att (n, h * w, heads * 32) f32 receives softmax(q^T k / sqrt(32)) v.  With pe_w49 ([49][heads * 32], bias
+// pe_bias) the depthwise 7x7 (zero padding 3 over the whole map) of the v channels is added and the sum written to channels
+// [out_co, out_co + heads * 32) of out (out_ct floats per pixel, SP8 if out_sp8, else f32; out may be att itself).
+void area_attn_launch(const float* qkv, const float* pe_w49, const float* pe_bias, int n, int h, int w, int heads, int area, float* att,
+                      float* out, int out_ct, int out_co, bool out_sp8, hipStream_t s);
 
 }  // namespace mtgv

@@ -3,10 +3,10 @@
 // family od_train.py:46-70).  BatchNorm (eps 1e-3) is folded into the conv weights at
 // finalize(); Concat is free (producers write channel slices of the consumer's buffer);
 // every Conv+SiLU is one launch of the implicit GEMM (gemm_launch, gemm_f32.hip).
-// This file also holds what YOLO11 shares with it: the CSP block (csp_block: C2f and C3k2), the neck and the head levels
+// This file also holds what YOLO11 and YOLO12 share with it: the CSP block (csp_block: C2f, C3k2 and A2C2f without attention), the neck and the head levels
 // (neck_and_heads, head_level), their key expectations (expect_csp, expect_neck, expect_head) and the arena table (arena).
 // The device kernels are in detector_kernel.h, the prototype branch behind cv1 in detector_proto.hip, the YOLO11
-// backbone and the modules only it has in detector_v11.hip.
+// backbone and the modules only it has in detector_v11.hip, YOLO12's (A2C2f with area attention) in detector_v12.hip.
 #include "detector.h"
 #include "detector_kernel.h"
 #include "nms.h"
@@ -38,7 +38,8 @@ Detector::Detector(const mtgv_detector_cfg& cfg) : cfg_(cfg) {
   MTGV_CHECK(cfg.imgsz > 0 && cfg.imgsz % 32 == 0, ERR_INVALID, "detector: imgsz=%d must be a multiple of 32", cfg.imgsz);
   MTGV_CHECK(cfg.max_batch > 0, ERR_INVALID, "detector: max_batch=%d", cfg.max_batch);
   MTGV_CHECK(cfg.max_det > 0 && cfg.max_det <= 1024, ERR_INVALID, "detector: max_det=%d", cfg.max_det);
-  MTGV_CHECK(cfg.arch == 0 || cfg.arch == 8 || cfg.arch == 11, ERR_KEY, "detector: arch=%d (8: YOLOv8n-seg, 11: YOLO11n-seg)", cfg.arch);
+  MTGV_CHECK(cfg.arch == 0 || cfg.arch == 8 || cfg.arch == 11 || cfg.arch == 12, ERR_KEY, "detector: arch=%d (8: YOLOv8, 11: YOLO11, 12: YOLO12)",
+             cfg.arch);
   MTGV_CHECK(cfg.task == MTGV_TASK_SEGMENT || cfg.task == MTGV_TASK_OBB, ERR_KEY, "detector: task=%d (0: segment, 1: OBB)", cfg.task);
   MTGV_CHECK(cfg.scale >= 0 && cfg.scale <= 4, ERR_INVALID, "detector: scale=%d (0: n, 1: s, 2: m)", cfg.scale);
   // l and x: spec.py knows their keys and the oracle runs them, but the 1e-4 contract cannot be tested at those widths yet
@@ -64,6 +65,7 @@ Detector::Detector(const mtgv_detector_cfg& cfg) : cfg_(cfg) {
   }
   head_ = "model." + std::to_string(22 + shift());
   if (v11()) build_v11();
+  else if (v12()) build_v12();
   else build_v8();
 }
 
@@ -72,15 +74,16 @@ static std::string node(int i) { return "model." + std::to_string(i); }
 void Detector::expect_csp(int idx, int cin, int cout, int n, bool shortcut, Csp kind, double e) {
   const int ch = (int)(cout * e), c_ = ch / 2;
   const std::string p = node(idx);
+  const CspInfo ci{cout, n, ch, shortcut, kind};
   auto bott = [&](const std::string& q, int c1, int cm, int c2) {
     expect_conv_bn(q + ".cv1", cm, c1, 3);
     expect_conv_bn(q + ".cv2", c2, cm, 3);
   };
-  expect_conv_bn(p + ".cv1", 2 * ch, cin, 1);
-  expect_conv_bn(p + ".cv2", cout, (2 + n) * ch, 1);
+  expect_conv_bn(p + ".cv1", ci.lead() * ch, cin, 1);
+  expect_conv_bn(p + ".cv2", cout, (ci.lead() + n) * ch, 1);
   for (int j = 0; j < n; ++j) {
     const std::string m = p + ".m." + std::to_string(j);
-    if (kind == Csp::C3k) {
+    if (ci.c3k()) {
       expect_conv_bn(m + ".cv1", c_, ch, 1);
       expect_conv_bn(m + ".cv2", c_, ch, 1);
       expect_conv_bn(m + ".cv3", ch, 2 * c_, 1);
@@ -89,7 +92,7 @@ void Detector::expect_csp(int idx, int cin, int cout, int n, bool shortcut, Csp 
       bott(m, ch, kind == Csp::Half ? c_ : ch, ch);
     }
   }
-  csp_[idx] = {cout, n, ch, shortcut, kind};
+  csp_[idx] = ci;
 }
 
 void Detector::expect_sppf(const std::string& p, int c) {
@@ -146,7 +149,7 @@ void Detector::expect_head(const int chs[3]) {
     expect_conv_bn(H + ".cv2." + ls + ".1", c2, c2, 3);
     expect(H + ".cv2." + ls + ".2.weight", {4 * reg_max_, c2, 1, 1});
     expect(H + ".cv2." + ls + ".2.bias", {4 * reg_max_});
-    if (v11()) {
+    if (dwcls()) {
       // Detect(legacy=False): Sequential(DWConv(x, x, 3), Conv(x, c3, 1)), Sequential(DWConv(c3, c3, 3), Conv(c3, c3, 1)), Conv2d
       expect_conv_bn(H + ".cv3." + ls + ".0.0", chs[l], 1, 3);
       expect_conv_bn(H + ".cv3." + ls + ".0.1", c3, chs[l], 1);
@@ -330,7 +333,8 @@ void Detector::plan_arena(const std::vector<ArenaBuf>& all) {
   HIP_OK(hipMemset(arena_.p, 0, arena_.n * sizeof(float)));
 }
 
-// The arena table of either architecture (node numbers in the comments are YOLOv8's; k = 1 shifts the neck's for YOLO11).
+// The arena table of every architecture (node numbers in the comments are YOLOv8's; k = 1 shifts the neck's for YOLO11, k = -1
+// for YOLO12).
 // The order is the carve order: it decides every buffer's address, so a buffer is added where it is first written.
 std::vector<Detector::ArenaBuf> Detector::arena() const {
   const int IH = cfg_.in_h, IW = cfg_.in_w, k = shift();
@@ -345,8 +349,8 @@ std::vector<Detector::ArenaBuf> Detector::arena() const {
   auto csp = [&](int idx, int h, int w) {
     const CspInfo& ci = csp_.at(idx);
     const std::string id = std::to_string(idx);
-    a.push_back({"cat" + id, h, w, (2 + ci.n) * ci.ch});
-    if (ci.kind == Csp::C3k) a.push_back({"kcat" + id, h, w, ci.ch});
+    a.push_back({"cat" + id, h, w, (ci.lead() + ci.n) * ci.ch});
+    if (ci.c3k()) a.push_back({"kcat" + id, h, w, ci.ch});
     a.push_back({"tmp" + id, h, w, ci.kind == Csp::C2f ? ci.ch : ci.ch / 2});
   };
   auto rows = [&] { add({{"rawhead0", h8, w8, RAW_CT, true}, {"rawhead1", h16, w16, RAW_CT, true}, {"rawhead2", h32, w32, RAW_CT, true}}); };
@@ -357,11 +361,21 @@ std::vector<Detector::ArenaBuf> Detector::arena() const {
   csp(4, h8, w8);
   add({{cat(14), h8, w8, c128 + csp_.at(4).cout},  // concat 14 = [up(12), 4]
        {"l5", h16, w16, c128}});
-  csp(6, h16, w16);
-  add({{cat(11), h16, w16, c256 + c128},  // concat 11 = [up(9), 6]
-       {"l7", h32, w32, c256}});
-  csp(8, h32, w32);
-  add({{"l8", h32, w32, c256}, {"sppcat", h32, w32, 2 * c256}});
+  if (v12()) {
+    // A2C2f 6 and 8: their concats, and one set of attention buffers for all eight ABlocks, carved for P4 (four times P5's
+    // pixels at no less than half its width) - qkv and the attention output in f32, the proj input and the MLP's hidden map
+    const A2Info &a6 = a2_.at(6), &a8 = a2_.at(8);
+    const int cw = std::max(a6.c, a8.c);
+    add({{"cat6", h16, w16, (1 + a6.n) * a6.c}, {"a2qkv", h16, w16, 3 * cw, true}, {"a2att", h16, w16, cw, true}, {"a2y", h16, w16, cw},
+         {"a2mlp", h16, w16, 2 * cw}});
+    add({{cat(11), h16, w16, c256 + c128}, {"l7", h32, w32, c256}, {"cat8", h32, w32, (1 + a8.n) * a8.c}});
+  } else {
+    csp(6, h16, w16);
+    add({{cat(11), h16, w16, c256 + c128},  // concat 11 = [up(9), 6]
+         {"l7", h32, w32, c256}});
+    csp(8, h32, w32);
+    add({{"l8", h32, w32, c256}, {"sppcat", h32, w32, 2 * c256}});
+  }
   if (v11()) {  // SPPF's own output and C2PSA (the attention core and the positional encoding read qkv and att in f32)
     const int pc = c256 / 2;  // C2PSA's hidden width: qkv is pc + 2 heads x 32 keys = 2 pc wide
     add({{"l9", h32, w32, c256}, {"psacat", h32, w32, 2 * pc}, {"qkv", h32, w32, 2 * pc, true}, {"att", h32, w32, pc, true},
@@ -380,18 +394,18 @@ std::vector<Detector::ArenaBuf> Detector::arena() const {
   // head temporaries per level (the levels' branches run concurrently): the branches head_first_ stacks side by side (160
   // channels at YOLOv8 n, 96 at YOLO11 n), and YOLO11's class branch
   const int hs[3] = {h8, h16, h32}, ws[3] = {w8, w16, w32}, chs[3] = {c64, c128, c256};
-  const int ht = hc2_ + (v11() ? 0 : hc3_) + hc4p_;
+  const int ht = hc2_ + (dwcls() ? 0 : hc3_) + hc4p_;
   for (int l = 0; l < 3; ++l) {
     const std::string ls = std::to_string(l);
     const int h = hs[l], w = ws[l];
     add({{"t1_" + ls, h, w, ht}, {"t2_" + ls, h, w, ht}});
-    if (v11()) add({{"dwa_" + ls, h, w, chs[l]}, {"dwb_" + ls, h, w, hc3_}, {"dwc_" + ls, h, w, hc3_}, {"dwd_" + ls, h, w, hc3_}});
+    if (dwcls()) add({{"dwa_" + ls, h, w, chs[l]}, {"dwb_" + ls, h, w, hc3_}, {"dwc_" + ls, h, w, hc3_}, {"dwd_" + ls, h, w, hc3_}});
   }
   // (the raw head rows are carved in front of the prototype buffers for YOLOv8 and behind them for YOLO11)
-  if (!v11()) rows();
+  if (!dwcls()) rows();
   add({{"pr1", h8, w8, npr_, false, true}, {"pr2", h4, w4, npr_, false, true}, {"pr3", h4, w4, npr_, false, true},
        {"protos", h4, w4, nm_, true, true}});
-  if (v11()) rows();
+  if (dwcls()) rows();
   add({{"pred", 1, na_, no(), true}, {"coef", 1, cfg_.max_det, nm_, true, true}});
   return a;
 }
@@ -416,8 +430,8 @@ void Detector::finalize() {
       const std::string pre = k.substr(0, k.size() - suf.size());
       if (raw_.find(pre + ".bn.weight") == raw_.end()) continue;  // dfl.conv has no BatchNorm
       const Raw& wr = kv.second;
-      if (wr.shape[1] == 1 && wr.shape[0] > 1 && wr.shape[2] == 3) {
-        cw_[pre] = fold_dw(pre);  // depthwise 3x3 (YOLO11 class branch, attention positional encoding)
+      if (wr.shape[1] == 1 && wr.shape[0] > 1 && (wr.shape[2] == 3 || wr.shape[2] == 7)) {
+        cw_[pre] = fold_dw(pre);  // depthwise 3x3 (YOLO11 class branch, attention positional encoding), 7x7 (YOLO12's)
         continue;
       }
       cw_[pre] = fold(pre, pre == "model.0" ? 4 : 0);
@@ -433,7 +447,7 @@ void Detector::finalize() {
     if (obb()) cw_[M + ".0"] = zero_pad(cw_.at(M + ".0"), hc4p_, cw_.at(M + ".0").cin);
     // the first 3x3 convs of the branches that start on the level's features as one conv (scale n: 64+64+32 outputs, box,
     // class and coefficient; YOLO11's class branch starts with a depthwise conv: 64+32)
-    if (v11()) {
+    if (dwcls()) {
       head_first_[l] = concat_out({cw_.at(B + ".0"), cw_.at(M + ".0")});
       cls_dw1_[l] = cw_.at(C + ".0.0"), cls_pw1_[l] = cw_.at(C + ".0.1");
       cls_dw2_[l] = cw_.at(C + ".1.0"), cls_pw2_[l] = cw_.at(C + ".1.1");
@@ -447,7 +461,7 @@ void Detector::finalize() {
     head_cls3_[l] = plain(C + ".2");
     // v8: the class branch's final 1x1 padded to a 32-column block (zero weights and bias past the classes), which the 3x3
     // before it can chain (gemm_sp_chain_ok wants N2 % 32 == 0)
-    if (!v11()) head_cls3_pad_[l] = plain(C + ".2", 32);
+    if (!dwcls()) head_cls3_pad_[l] = plain(C + ".2", 32);
     head_coef3_[l] = obb() ? zero_pad(plain(M + ".2"), nm_, hc4p_) : plain(M + ".2");
   }
   // DFL weights must be arange(16) (they are a fixed buffer upstream); the decode kernel hard-codes them
@@ -530,27 +544,27 @@ void Detector::bottleneck(const std::string& p, const View& x, const View& tmp, 
   conv(cw_.at(p + ".cv2"), tmp, out, 1, ACT_SILU, shortcut ? &x : nullptr, n, s);
 }
 
-// CSP block (C2f, C3k2): cv1 -> 2 chunks; n inner modules (+shortcut), each reading the chunk before it and appended to
+// CSP block (C2f, C3k2, A2C2f without attention): cv1 -> 2 chunks (A2C2f: 1); n inner modules (+shortcut), each reading the chunk before it and appended to
 // the concat; cv2 over the concat
 void Detector::csp_block(int idx, const View& in, const View& out, int n, hipStream_t s, const ConvW* pre, const View* pre_in) {
   const CspInfo& ci = csp_.at(idx);
-  const int ch = ci.ch;
+  const int ch = ci.ch, lead = ci.lead();
   const std::string id = std::to_string(idx), P = "model." + id;
   const View cat = view("cat" + id), tmp = view("tmp" + id);
   // pre: the stride-2 Conv in front of this block, whose only consumer is cv1 - the pair runs as one launch where it can
-  if (pre != nullptr) conv_pair(*pre, *pre_in, in, 2, cw_.at(P + ".cv1"), cat.slice(0, 2 * ch), ACT_SILU, n, s);
-  else conv(cw_.at(P + ".cv1"), in, cat.slice(0, 2 * ch), 1, ACT_SILU, nullptr, n, s);
+  if (pre != nullptr) conv_pair(*pre, *pre_in, in, 2, cw_.at(P + ".cv1"), cat.slice(0, lead * ch), ACT_SILU, n, s);
+  else conv(cw_.at(P + ".cv1"), in, cat.slice(0, lead * ch), 1, ACT_SILU, nullptr, n, s);
   const bool fuse = env_int("MTGV_DET_C2F_FUSE", 1) != 0;  // read per call (A/B in one process); 0: three launches
   for (int j = 0; j < ci.n; ++j) {
-    const View src = cat.slice((1 + j) * ch, ch);
-    const View dst = cat.slice((2 + j) * ch, ch);
+    const View src = cat.slice((lead - 1 + j) * ch, ch);
+    const View dst = cat.slice((lead + j) * ch, ch);
     const std::string M = P + ".m." + std::to_string(j);
     // the last bottleneck and cv2 as one launch where there is a kernel for the block (c2f_tail.h): tmp and dst stay on chip.
     // The shapes are those of C2f's Bottleneck(ch -> ch -> ch): a half-width bottleneck (cv1 has ch / 2 outputs) and C3k
     // (its cv1 and cv2 are 1x1) fail them by construction, so the inner module's kind need not be asked.
     const ConvW &w1 = cw_.at(M + ".cv1"), &w2 = cw_.at(M + ".cv2"), &w3 = cw_.at(P + ".cv2");
     const bool tail_shapes = w1.k == 3 && w1.cin == ch && w1.cout == ch && w2.k == 3 && w2.cin == ch && w2.cout == ch && w3.k == 1 &&
-                             w3.cin == (2 + ci.n) * ch && w3.cout == out.C;  // (anything else: conv() below reports it)
+                             w3.cin == (lead + ci.n) * ch && w3.cout == out.C;  // (anything else: conv() below reports it)
     if (j == ci.n - 1 && fuse && tail_shapes && !count_flops_ && fmt_ == 1 && cat.fmt == 1 && out.fmt == 1) {
       C2fTailArgs a;
       a.cat = cat.p, a.cat_ct = cat.ct, a.cat_co = cat.co, a.n_img = n, a.H = cat.H, a.W = cat.W;
@@ -562,10 +576,10 @@ void Detector::csp_block(int idx, const View& in, const View& out, int n, hipStr
         return;
       }
     }
-    if (ci.kind == Csp::C3k) c3k(M, src, view("kcat" + id), tmp, dst, ci.shortcut, n, s);
+    if (ci.c3k()) c3k(M, src, view("kcat" + id), tmp, dst, ci.shortcut, n, s);
     else bottleneck(M, src, tmp, dst, ci.shortcut, n, s);
   }
-  conv(cw_.at(P + ".cv2"), cat.slice(0, (2 + ci.n) * ch), out, 1, ACT_SILU, nullptr, n, s);
+  conv(cw_.at(P + ".cv2"), cat.slice(0, (lead + ci.n) * ch), out, 1, ACT_SILU, nullptr, n, s);
 }
 
 // The stem kernels (detector_kernel.h) on n frames of H x W: cout = 16 (scale n) is conv0_u8_kernel, 32 / 48 / 64 (s,
@@ -745,7 +759,7 @@ void Detector::upsample2x(const View& in, const View& out, int n, hipStream_t s)
 
 void Detector::forward_graph(const uint8_t* frames, int n, int flip, hipStream_t s) {
   conv0(frames, n, flip, s);
-  neck_and_heads(v11() ? backbone_v11(n, s) : backbone_v8(n, s), n, s);
+  neck_and_heads(v11() ? backbone_v11(n, s) : v12() ? backbone_v12(n, s) : backbone_v8(n, s), n, s);
 }
 
 // yolov8 nodes 1 .. 9 behind conv0; returns node 9
@@ -769,7 +783,7 @@ View Detector::backbone_v8(int n, hipStream_t s) {
 }
 
 // From the first upsample to the P5 head, on the backbone's last node `top` (9 + k, in concat 20 + k) and its nodes 4
-// and 6 (in concats 14 + k and 11 + k).  Node numbers are YOLOv8's; YOLO11's are one higher.  A concat's slices are as wide
+// and 6 (in concats 14 + k and 11 + k).  Node numbers are YOLOv8's; YOLO11's are one higher, YOLO12's one lower.  A concat's slices are as wide
 // as the views that fill them.
 void Detector::neck_and_heads(const View& top, int n, hipStream_t s) {
   const int k = shift();
@@ -822,9 +836,9 @@ void Detector::head_level(int l, int n, hipStream_t s) {
   const int c2 = hc2_, c4 = hc4p_, o4 = head_first_[l].cout - c4;
   conv_pair(head_box2_[l], t1.slice(0, c2), t2.slice(0, c2), 1, head_box3_[l], rh.slice(0, 4 * reg_max_), ACT_NONE, n, s);
   // (the class branch is enqueued between the two pairs for YOLOv8 and behind them for YOLO11)
-  if (!v11()) head_cls_v8(l, t1.slice(c2, hc3_), t2.slice(c2, hc3_), rh, n, s);
+  if (!dwcls()) head_cls_v8(l, t1.slice(c2, hc3_), t2.slice(c2, hc3_), rh, n, s);
   conv_pair(head_coef2_[l], t1.slice(o4, c4), t2.slice(o4, c4), 1, head_coef3_[l], rh.slice(RAW_COEF, nm_), ACT_NONE, n, s);
-  if (v11()) head_cls_v11(l, f, rh, n, s);
+  if (dwcls()) head_cls_v11(l, f, rh, n, s);
   obb_flops_fix(f);
 }
 

@@ -156,17 +156,18 @@ __global__ __launch_bounds__(256) void attn_kernel(const float* __restrict__ qkv
 // ---------------------------------------------------------------------------
 // weights
 // ---------------------------------------------------------------------------
-// depthwise Conv2d(c, c, 3, groups=c, bias=False) + BatchNorm2d(eps 1e-3) -> weight [9][c] (tap-major), bias [c]
+// depthwise Conv2d(c, c, k, groups=c, bias=False) + BatchNorm2d(eps 1e-3) -> weight [k * k][c] (tap-major), bias [c]; k = 3,
+// or 7 (YOLO12's positional encoding)
 ConvW Detector::fold_dw(const std::string& p) {
   const Raw& w = raw_.at(p + ".conv.weight");
-  const int c = w.shape[0];
-  std::vector<float> wf((size_t)9 * c), bf(c);
+  const int c = w.shape[0], k = w.shape[2], kk = k * k;
+  std::vector<float> wf((size_t)kk * c), bf(c);
   for (int o = 0; o < c; ++o) {
     const auto [sc, bias] = bn_affine(p, o);
     bf[o] = (float)bias;
-    for (int t = 0; t < 9; ++t) wf[(size_t)t * c + o] = (float)((double)w.data[(size_t)o * 9 + t] * sc);
+    for (int t = 0; t < kk; ++t) wf[(size_t)t * c + o] = (float)((double)w.data[(size_t)o * kk + t] * sc);
   }
-  return ConvW{upload(wf), upload(bf), c, c, 3};
+  return ConvW{upload(wf), upload(bf), c, c, k};
 }
 
 void Detector::dwconv(const ConvW& w, const View& in, const View& out, int act, const float* add, int g_size, int g_stride, int n,

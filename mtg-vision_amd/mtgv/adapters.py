@@ -356,7 +356,7 @@ class CardSegmenter:
             # (the reference's class is YOLO(path, task="segment"), od_export.py:141-146: it has no OBB counterpart to mirror)
             assert cfg.task == "seg", 'CardSegmenter takes a segment checkpoint; an OBB one runs on mtgv.Detector / Pipeline(quad_source="obb")'
             self._cfg, self._state_dict, self._max_batch = cfg, state_dict, max_batch
-            self.yolo = None if rect else Detector(cfg, state_dict, max_batch=max_batch)  # v8 / 11 -seg at the checkpoint's scale (n, s, m)
+            self.yolo = None if rect else Detector(cfg, state_dict, max_batch=max_batch)  # v8 / 11 / 12 -seg at the checkpoint's scale (n, s, m)
 
     def _handle_for(self, h: int, w: int):
         """(Detector, ratio, left, top) for an (h, w) frame: the square handle, or with rect=True the handle of the

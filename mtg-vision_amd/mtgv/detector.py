@@ -1,4 +1,4 @@
-"""Host side of the detect stage: YOLOv8 / YOLO11 (scales n, s, m: `spec.detector_scale_config`) forward + decode + NMS on the GPU - the segment family with mask
+"""Host side of the detect stage: YOLOv8 / YOLO11 / YOLO12 (scales n, s, m: `spec.detector_scale_config`) forward + decode + NMS on the GPU - the segment family with mask
 logits, the OBB family (`DetectorConfig(task="obb")`) with rotated boxes and rotated NMS.
 
 `Detector.detect(frame)` is the north-star name; the reference's boundary is
@@ -133,7 +133,7 @@ class Detector:
         c = native.DetectorCfg()
         c.nc, c.imgsz, c.max_batch = self.cfg.nc, self.cfg.imgsz, self.max_batch
         c.conf, c.iou, c.max_det = self.cfg.conf, self.cfg.iou, self.cfg.max_det
-        c.arch = 11 if self.cfg.arch == "11" else 8
+        c.arch = {"11": 11, "12": 12}.get(self.cfg.arch, 8)
         c.task = 1 if self.cfg.task == "obb" else 0
         c.scale = spec.SCALE_NAMES.index(self.cfg.scale)  # (l and x: the library refuses them, status 2)
         if self.cfg.input_hw is not None:  # (0, 0: the square imgsz x imgsz)
@@ -301,6 +301,25 @@ def probiou(a: torch.Tensor, b: torch.Tensor) -> torch.Tensor:
     out = torch.empty((a.shape[0],), dtype=torch.float32, device=a.device)
     with torch.cuda.device(a.device):
         native.check(native.lib().mtgv_op_probiou(native.ptr(a), native.ptr(b), a.shape[0], native.ptr(out), native.stream()))
+    return out
+
+
+def area_attn(qkv: torch.Tensor, h: int, w: int, heads: int, area: int, pe_w49: Optional[torch.Tensor] = None,
+              pe_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """YOLO12's area attention alone (mtgv_op_area_attn, what the detector's ABlocks run; test surface): qkv (n, h * w, heads * 96)
+    float32, per head [q 32 | k 32 | v 32] -> (n, h * w, heads * 32): softmax(q^T k / sqrt(32)) v inside each of the `area`
+    contiguous token chunks, plus - with pe_w49 ([49][heads * 32]) and pe_bias - the depthwise 7x7 of v over the h x w map."""
+    native.require_gpu()
+    assert qkv.is_cuda and qkv.dtype == torch.float32 and qkv.ndim == 3 and tuple(qkv.shape[1:]) == (h * w, heads * 96), f"{tuple(qkv.shape)}"
+    assert (pe_w49 is None) == (pe_bias is None)
+    if pe_w49 is not None:
+        assert pe_w49.is_cuda and pe_bias.is_cuda and tuple(pe_w49.shape) == (49, heads * 32) and tuple(pe_bias.shape) == (heads * 32,)
+        pe_w49, pe_bias = pe_w49.float().contiguous(), pe_bias.float().contiguous()
+    qkv = qkv.contiguous()
+    out = torch.empty((qkv.shape[0], h * w, heads * 32), dtype=torch.float32, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        native.check(native.lib().mtgv_op_area_attn(native.ptr(qkv), native.ptr(pe_w49), native.ptr(pe_bias), qkv.shape[0], h, w, heads, area,
+                                                    native.ptr(out), native.stream()))
     return out
 
 

@@ -144,14 +144,83 @@ class C2PSA(nn.Module):
         return self.cv2(torch.cat((a, self.m(b)), 1))
 
 
+class AAttn(nn.Module):
+    """YOLO12's area attention: heads of 32 channels, qkv channel h * 96 + [q 32 | k 32 | v 32]; the H * W tokens (row-major)
+    are cut into `area` contiguous chunks and attention runs inside a chunk; the depthwise 7x7 positional encoding runs on v
+    as the whole map.  [external - recalled from ultralytics 8.3.x nn/modules/block.py, unpinned]"""
+
+    def __init__(self, dim, num_heads, area=1):
+        super().__init__()
+        self.area, self.num_heads, self.head_dim = area, num_heads, dim // num_heads
+        self.qkv = Conv(dim, dim * 3, 1, act=False)
+        self.proj = Conv(dim, dim, 1, act=False)
+        self.pe = Conv(dim, dim, 7, 1, g=dim, act=False)
+
+    def forward(self, x):
+        b, c, h, w = x.shape
+        n, hd, nh = h * w, self.head_dim, self.num_heads
+        qkv = self.qkv(x).flatten(2).transpose(1, 2)  # (b, n, 3c)
+        if self.area > 1:
+            qkv = qkv.reshape(b * self.area, n // self.area, c * 3)
+        bb, nn_, _ = qkv.shape
+        q, k, v = qkv.view(bb, nn_, nh, hd * 3).permute(0, 2, 3, 1).split([hd, hd, hd], dim=2)
+        attn = ((q.transpose(-2, -1) @ k) * (hd**-0.5)).softmax(dim=-1)
+        y = (v @ attn.transpose(-2, -1)).permute(0, 3, 1, 2)  # (bb, nn, heads, hd)
+        v = v.permute(0, 3, 1, 2)
+        y = y.reshape(b, h, w, c).permute(0, 3, 1, 2)
+        v = v.reshape(b, h, w, c).permute(0, 3, 1, 2)
+        return self.proj(y + self.pe(v.contiguous()))
+
+
+class ABlock(nn.Module):
+    def __init__(self, dim, num_heads, mlp_ratio=1.2, area=1):
+        super().__init__()
+        self.attn = AAttn(dim, num_heads, area)
+        hidden = int(dim * mlp_ratio)
+        self.mlp = nn.Sequential(Conv(dim, hidden, 1), Conv(hidden, dim, 1, act=False))
+
+    def forward(self, x):
+        x = x + self.attn(x)
+        return x + self.mlp(x)
+
+
+class A2C2f(nn.Module):
+    """cv1 gives ONE chunk of c_ = c2 // 2 channels; n modules - two ABlocks (a2) or C3k(c_, c_, 2) - each appended to the
+    concat; cv2 over (1 + n) c_.  residual (scales l, x): x + gamma * out on the a2 blocks."""
+
+    def __init__(self, c1, c2, n=1, a2=True, area=1, residual=False, mlp_ratio=2.0):
+        super().__init__()
+        c_ = c2 // 2
+        assert c_ % 32 == 0, "the hidden width of A2C2f is a multiple of 32"
+        self.cv1 = Conv(c1, c_, 1)
+        self.cv2 = Conv((1 + n) * c_, c2, 1)
+        self.gamma = nn.Parameter(0.01 * torch.ones(c2)) if a2 and residual else None
+        self.m = nn.ModuleList(
+            nn.Sequential(*(ABlock(c_, c_ // 32, mlp_ratio, area) for _ in range(2))) if a2 else C3k(c_, c_, 2, True) for _ in range(n)
+        )
+
+    def forward(self, x):
+        y = [self.cv1(x)]
+        for m in self.m:
+            y.append(m(y[-1]))
+        y = self.cv2(torch.cat(y, 1))
+        return x + self.gamma.view(1, -1, 1, 1) * y if self.gamma is not None else y
+
+
 class _DFL(nn.Module):
-    def __init__(self, c1=16):
+    def __init__(self, c1=16, as_sum=False):
+        """as_sum (YOLO12's Segment head only; YOLOv8 and YOLO11 keep the conv): the same 1x1 conv written as the expectation
+        sum(softmax * weight) - the form, and so the float32 summation order, of the Segment decode the YOLO12 mirror is
+        checked against to 1e-5 (tests/yolo12_ref.py -> oracle/detector_ref.py: _head_segment; its OBB decode has the conv)"""
         super().__init__()
         self.conv = nn.Conv2d(c1, 1, 1, bias=False).requires_grad_(False)
         self.c1 = c1
+        self.as_sum = as_sum
 
     def forward(self, x):
         b, _, a = x.shape
+        if self.as_sum:
+            return (x.view(b, 4, self.c1, a).transpose(2, 1).softmax(1) * self.conv.weight.view(1, self.c1, 1, 1)).sum(1)
         return self.conv(x.view(b, 4, self.c1, a).transpose(2, 1).softmax(1)).view(b, 4, a)
 
 
@@ -190,14 +259,14 @@ class _Detect(nn.Module):
         c3 = max(ch[0], min(nc, 100))
         c4 = max(ch[0] // 4, n4)
         self.cv2 = nn.ModuleList(nn.Sequential(Conv(x, c2, 3), Conv(c2, c2, 3), nn.Conv2d(c2, 4 * rm, 1)) for x in ch)
-        if cfg.arch == "11":
+        if cfg.arch in ("11", "12"):
             self.cv3 = nn.ModuleList(
                 nn.Sequential(nn.Sequential(Conv(x, x, 3, g=x), Conv(x, c3, 1)), nn.Sequential(Conv(c3, c3, 3, g=c3), Conv(c3, c3, 1)), nn.Conv2d(c3, nc, 1))
                 for x in ch
             )
         else:
             self.cv3 = nn.ModuleList(nn.Sequential(Conv(x, c3, 3), Conv(c3, c3, 3), nn.Conv2d(c3, nc, 1)) for x in ch)
-        self.dfl = _DFL(rm)
+        self.dfl = _DFL(rm, as_sum=cfg.arch == "12" and proto is not None)
         if proto is not None:
             self.proto = proto
         self.cv4 = nn.ModuleList(nn.Sequential(Conv(x, c4, 3), Conv(c4, c4, 3), nn.Conv2d(c4, n4, 1)) for x in ch)
@@ -267,6 +336,8 @@ class DetectorModule(nn.Module):
                 m, prev = C3k2(prev, a[0], a[1], a[2], a[3]), a[0]
             elif kind == "C2PSA":
                 m, prev = C2PSA(prev, a[0], a[1]), a[0]
+            elif kind == "A2C2f":
+                m, prev = A2C2f(prev, *a), a[0]
             elif kind == "SPPF":
                 m, prev = SPPF(prev, a[0]), a[0]
             elif kind == "Upsample":

@@ -263,9 +263,11 @@ def strip_checkpoint_prefix(state_dict, prefix: str = "model.encoder."):
 # yolo{arch}{size}-{kind}).  [external - recalled from ultralytics 8.3.x cfg/models/v8/yolov8-seg.yaml and
 # cfg/models/11/yolo11-seg.yaml, unpinned like the rest of the detector]  YOLO11 m, l and x also set c3k = True on every
 # C3k2 (yolo11_seg_graph).  The GPU executor runs n, s and m (GPU_SCALES); l and x are here for keys, shapes and the oracle.
+# YOLO12 [external - recalled from ultralytics 8.3.x cfg/models/12/yolo12-seg.yaml, unpinned] has YOLO11's table and its c3k rule.
 DETECTOR_SCALES = {
     "v8": {"n": (0.33, 0.25, 1024), "s": (0.33, 0.50, 1024), "m": (0.67, 0.75, 768), "l": (1.00, 1.00, 512), "x": (1.00, 1.25, 512)},
     "11": {"n": (0.50, 0.25, 1024), "s": (0.50, 0.50, 1024), "m": (0.50, 1.00, 512), "l": (1.00, 1.00, 512), "x": (1.00, 1.50, 512)},
+    "12": {"n": (0.50, 0.25, 1024), "s": (0.50, 0.50, 1024), "m": (0.50, 1.00, 512), "l": (1.00, 1.00, 512), "x": (1.00, 1.50, 512)},
 }
 SCALE_NAMES = "nsmlx"  # index: mtgv_detector_cfg.scale
 GPU_SCALES = "nsm"
@@ -273,7 +275,8 @@ GPU_SCALES = "nsm"
 
 @dataclass(frozen=True)
 class DetectorConfig:
-    # "v8": yolov8n-seg (BASELINE.json); "11": yolo11n-seg, what the reference trains by default (od_train.py:20, :55-56)
+    # "v8": yolov8n-seg (BASELINE.json); "11": yolo11n-seg, what the reference trains by default (od_train.py:20, :55-56);
+    # "12": yolo12n-seg, od_train.py's other `--arch` (A2C2f / area attention backbone, yolo12_graph)
     arch: str = "v8"
     nc: int = 3  # od_train.py:46-50
     nm: int = 32  # mask coefficients
@@ -334,7 +337,7 @@ class DetectorConfig:
 
     @property
     def head_index(self) -> int:
-        return 23 if self.arch == "11" else 22
+        return {"11": 23, "12": 21}.get(self.arch, 22)
 
     @property
     def num_anchors(self) -> int:
@@ -381,26 +384,29 @@ def yolo11_config(**kw) -> DetectorConfig:
 
 
 def detector_scale_config(arch: str, scale: str, **kw) -> DetectorConfig:
-    """yolov8{scale} / yolo11{scale}: DETECTOR_SCALES' depth, width and max_channels, and the prototype width
-    npr = make_divisible(min(256, max_ch) * width, 8) (64 at n, 128 at s, 192 at YOLOv8 m, 256 at YOLO11 m)"""
-    arch = "11" if str(arch) in ("11", "v11") else "v8"
+    """yolov8{scale} / yolo11{scale} / yolo12{scale}: DETECTOR_SCALES' depth, width and max_channels, and the prototype width
+    npr = make_divisible(min(256, max_ch) * width, 8) (64 at n, 128 at s, 192 at YOLOv8 m, 256 at YOLO11 m and YOLO12 m)"""
+    arch = {"11": "11", "v11": "11", "12": "12", "v12": "12"}.get(str(arch), "v8")
     depth, width, max_ch = DETECTOR_SCALES[arch][scale]
     npr = int(-(-(min(256, max_ch) * width) // 8) * 8)
     return DetectorConfig(arch=arch, scale=scale, depth=depth, width=width, max_ch=max_ch, npr=npr, **kw)
 
 
 # width of model.0 (make_divisible(64 * width, 8)) -> scale
-_STEM_SCALE = {"v8": {16: "n", 32: "s", 48: "m", 64: "l", 80: "x"}, "11": {16: "n", 32: "s", 64: "ml", 96: "x"}}
+_STEM_SCALE = {"v8": {16: "n", 32: "s", 48: "m", 64: "l", 80: "x"}, "11": {16: "n", 32: "s", 64: "ml", 96: "x"},
+               "12": {16: "n", 32: "s", 64: "ml", 96: "x"}}
 
 
 def detector_config_for_state(state_dict, **kw) -> DetectorConfig:
     """The family and scale a ultralytics `state_dict` belongs to, from its key set: YOLO11 has its head at index 23
-    (`model.23.*`; C2PSA at 10), YOLOv8 at 22; a head without `.proto.` keys is an OBB head.  `nc` is read from the class
+    (`model.23.*`; C2PSA at 10), YOLOv8 at 22, YOLO12 (no SPPF, no C2PSA) at 21 with no `model.22.*` keys; a head without
+    `.proto.` keys is an OBB head.  `nc` is read from the class
     branch's last conv, the scale from the stem's width (`model.0.conv.weight`; KeyError for a width no scale has) -
-    YOLO11 m and l share theirs and differ in depth: l has a second inner module `model.2.m.1.*`."""
+    YOLO11 and YOLO12 m and l share theirs and differ in depth: l has a second inner module `model.2.m.1.*`."""
     keys = list(state_dict.keys())
-    head = 23 if any(k.startswith("model.23.") for k in keys) else 22
-    arch = "11" if head == 23 else "v8"
+    has = lambda i: any(k.startswith(f"model.{i}.") for k in keys)
+    head = 23 if has(23) else 22 if has(22) or not has(21) else 21
+    arch = {23: "11", 22: "v8", 21: "12"}[head]
     if not any(".proto." in k for k in keys):
         kw.setdefault("task", "obb")
     w = state_dict.get(f"model.{head}.cv3.0.2.weight")
@@ -451,8 +457,44 @@ def yolo11_seg_graph(cfg: DetectorConfig):
     return [(i, kind, (a[0], a[1], a[2] or k, a[3]) if kind == "C3k2" else a) for i, kind, a in g]
 
 
+# ---- YOLO12-seg graph (ultralytics cfg/models/12/yolo12-seg.yaml) ----------
+# A2C2f(cout, n, a2, area, residual, mlp_ratio); no SPPF, no C2PSA; the head is node 21.  [external - recalled from
+# ultralytics 8.3.x, unpinned.  The least certain item is the MLP ratio of scale m: 2.0 (kept here for n, s, m) gives 3 % more
+# parameters than the published yolo12m-seg count, 1.2 would give 1 % fewer.]
+def yolo12_graph(cfg: DetectorConfig):
+    c, r = cfg.ch, cfg.rep
+    k = cfg.scale in "mlx"
+    big = cfg.scale in "lx"  # l, x: residual x + gamma * out on the a2 blocks, MLP ratio 1.2
+    ratio = 1.2 if big else 2.0
+    return [
+        (0, "Conv", (c(64), 3, 2)),
+        (1, "Conv", (c(128), 3, 2)),
+        (2, "C3k2", (c(256), r(2), k, 0.25)),
+        (3, "Conv", (c(256), 3, 2)),
+        (4, "C3k2", (c(512), r(2), k, 0.25)),
+        (5, "Conv", (c(512), 3, 2)),
+        (6, "A2C2f", (c(512), r(4), True, 4, big, ratio)),
+        (7, "Conv", (c(1024), 3, 2)),
+        (8, "A2C2f", (c(1024), r(4), True, 1, big, ratio)),
+        (9, "Upsample", ()),
+        (10, "Concat", (9, 6)),
+        (11, "A2C2f", (c(512), r(2), False, -1, False, ratio)),
+        (12, "Upsample", ()),
+        (13, "Concat", (12, 4)),
+        (14, "A2C2f", (c(256), r(2), False, -1, False, ratio)),
+        (15, "Conv", (c(256), 3, 2)),
+        (16, "Concat", (15, 11)),
+        (17, "A2C2f", (c(512), r(2), False, -1, False, ratio)),
+        (18, "Conv", (c(512), 3, 2)),
+        (19, "Concat", (18, 8)),
+        (20, "C3k2", (c(1024), r(2), True, 0.5)),
+    ]
+
+
 def detector_graph(cfg: DetectorConfig):
     """(graph, indices of the P3 / P4 / P5 feature maps the Segment head reads)"""
+    if cfg.arch == "12":
+        return yolo12_graph(cfg), (14, 17, 20)
     if cfg.arch == "11":
         return yolo11_seg_graph(cfg), (16, 19, 22)
     return yolov8_seg_graph(cfg), (15, 18, 21)
@@ -484,7 +526,7 @@ def _c3k_keys(prefix: str, c1: int, c2: int, n: int = 2):
 
 
 def detector_param_shapes(cfg: DetectorConfig) -> "OrderedDict[str, tuple]":
-    """ultralytics state_dict keys of YOLOv8 / YOLO11 at cfg's scale, -seg or -obb (``num_batches_tracked`` buffers omitted).
+    """ultralytics state_dict keys of YOLOv8 / YOLO11 / YOLO12 at cfg's scale, -seg or -obb (``num_batches_tracked`` buffers omitted).
 
     Third-party layout, recalled from ultralytics 8.3.x (pyproject.toml:32 pins ~=8.3.80); it
     cannot be checked against the package in this environment.
@@ -537,6 +579,29 @@ def detector_param_shapes(cfg: DetectorConfig) -> "OrderedDict[str, tuple]":
                 out.update(_conv_bn_keys(f"{q}.ffn.0", 2 * ch, ch, 1))
                 out.update(_conv_bn_keys(f"{q}.ffn.1", ch, 2 * ch, 1))
             prev = cout
+        elif kind == "A2C2f":
+            # cv1 (1x1 c1 -> c_: one chunk), n modules each appended to the concat, cv2 over (1 + n) c_.  a2: a module is two
+            # ABlocks (area attention with c_ // 32 heads of 32 channels and a depthwise 7x7 positional encoding, then a
+            # 2-layer MLP); otherwise C3k(c_, c_, 2).  gamma: a parameter of the block itself, so it precedes the children.
+            cout, n, a2, _, residual, ratio = a
+            ch = cout // 2
+            assert ch % 32 == 0, f"A2C2f hidden width {ch} is no multiple of 32"
+            if a2 and residual:
+                out[f"{p}.gamma"] = (cout,)
+            out.update(_conv_bn_keys(f"{p}.cv1", ch, prev, 1))
+            out.update(_conv_bn_keys(f"{p}.cv2", cout, (1 + n) * ch, 1))
+            for j in range(n):
+                if not a2:
+                    out.update(_c3k_keys(f"{p}.m.{j}", ch, ch, 2))
+                    continue
+                for b in range(2):
+                    q = f"{p}.m.{j}.{b}"
+                    out.update(_conv_bn_keys(f"{q}.attn.qkv", 3 * ch, ch, 1))
+                    out.update(_conv_bn_keys(f"{q}.attn.proj", ch, ch, 1))
+                    out.update(_conv_bn_keys(f"{q}.attn.pe", ch, 1, 7))  # depthwise
+                    out.update(_conv_bn_keys(f"{q}.mlp.0", int(ch * ratio), ch, 1))
+                    out.update(_conv_bn_keys(f"{q}.mlp.1", ch, int(ch * ratio), 1))
+            prev = cout
         elif kind == "SPPF":
             (cout,) = a
             out.update(_conv_bn_keys(f"{p}.cv1", prev // 2, prev, 1))
@@ -558,7 +623,7 @@ def detector_param_shapes(cfg: DetectorConfig) -> "OrderedDict[str, tuple]":
         out[f"{p}.cv2.{l}.2.weight"] = (4 * cfg.reg_max, c2, 1, 1)
         out[f"{p}.cv2.{l}.2.bias"] = (4 * cfg.reg_max,)
     for l, cl in enumerate(ch):
-        if cfg.arch == "11":  # Detect(legacy=False): Sequential(DWConv(x, x, 3), Conv(x, c3, 1)), Sequential(DWConv(c3, c3, 3), Conv(c3, c3, 1))
+        if cfg.arch in ("11", "12"):  # Detect(legacy=False): Sequential(DWConv(x, x, 3), Conv(x, c3, 1)), Sequential(DWConv(c3, c3, 3), Conv(c3, c3, 1))
             out.update(_conv_bn_keys(f"{p}.cv3.{l}.0.0", cl, 1, 3))
             out.update(_conv_bn_keys(f"{p}.cv3.{l}.0.1", c3, cl, 1))
             out.update(_conv_bn_keys(f"{p}.cv3.{l}.1.0", c3, 1, 3))
@@ -588,8 +653,14 @@ def random_detector_state(cfg: DetectorConfig, seed: int, cls_bias: float = -2.1
 
     Conv weights are fan-in scaled so activations stay O(1) through the SiLU stack; the
     class-logit bias is shifted by `cls_bias` so that only a few hundred of the 8400
-    anchors pass conf 0.25 on random frames."""
+    anchors pass conf 0.25 on random frames.
+
+    YOLO12 only: the convs of an ABlock that have no activation get smaller gains - qkv and pe 1.0, proj and mlp.1 0.5
+    instead of 1.6.  With 1.6 every ABlock multiplies the activation scale by about 5 (eight of them in a row: std 0.19
+    into node 6, 6e4 out of node 8, attention logits of 1e10); with these every node stays at std 0.15 - 0.6.  The draws
+    are the same in number and order, so the other families' states do not change (YOLO11's C2PSA has `.attn.` keys too)."""
     rng = np.random.default_rng(seed)
+    gains = {".attn.qkv.": 1.0, ".attn.pe.": 1.0, ".attn.proj.": 0.5, ".mlp.1.": 0.5} if cfg.arch == "12" else {}
     sd: Dict[str, np.ndarray] = OrderedDict()
     for key, shape in detector_param_shapes(cfg).items():
         leaf = key.rsplit(".", 1)[-1]
@@ -598,7 +669,8 @@ def random_detector_state(cfg: DetectorConfig, seed: int, cls_bias: float = -2.1
         elif key.endswith("proto.upsample.weight"):
             a = rng.standard_normal(shape) * (1.6 / np.sqrt(shape[0]))
         elif leaf == "weight" and len(shape) == 4:
-            a = rng.standard_normal(shape) * (1.6 / np.sqrt(_fan_in(shape)))
+            gain = next((g for frag, g in gains.items() if frag in key), 1.6)
+            a = rng.standard_normal(shape) * (gain / np.sqrt(_fan_in(shape)))
         elif leaf == "weight":  # bn scale
             a = 1.0 + 0.1 * rng.standard_normal(shape)
         elif leaf == "running_var":
