@@ -36,6 +36,7 @@ extern "C" {
 #endif
 
 MTGV_API const char* mtgv_last_error(void);
+/* 110: mtgv_tracker_create_ex / MTGV_TRACKER_WIDE (256 tracks per stream, 64 cards per frame) */
 MTGV_API int mtgv_version(void);
 /* number of HIP devices visible; does not initialise a device context */
 MTGV_API int mtgv_device_count(void);
@@ -655,14 +656,16 @@ MTGV_API int mtgv_op_l2norm(const float* x_dev, float* out_dev, int64_t rows, in
  * followed by TrackerCtx's gating: a track is embedded when it is new or update_wait_sec have passed, an exponentially
  * weighted mean of its embeddings queries the bank, the last top_k matches stay on the track.  Filter state is fp64 and the
  * arithmetic is the host class's, operation for operation (no FMA contraction): ids, due sets and filter state are equal.
- * Caps the host class does not have: at most max_tracks (<= 64) live tracks per stream - a detection that finds no free slot
- * is dropped and counted - at most 16 cards per frame, and every stream at most once per update.
+ * Caps the host class does not have: at most max_tracks live tracks per stream - a detection that finds no free slot is
+ * dropped and counted - at most cards_per_frame cards per frame, and every stream at most once per update.  max_tracks <= 64
+ * and cards_per_frame <= 16 for mtgv_tracker_create; 256 and 64 for mtgv_tracker_create_ex with MTGV_TRACKER_WIDE (version
+ * 110).  Ids are int32.  mtgv_tracker_gather_u8 takes at most 65535 rows: a step of frames * K rows above that is refused there.
  * Zero in a policy field selects the reference's value (300, 5, 2, 1, 0.5 s, 0.1).  To run without an initialisation delay
  * pass initialization_delay = -1 (an id at creation); a negative update_wait_sec makes every reported track due. */
 typedef struct {
   int32_t streams;         /* S >= 1 */
-  int32_t max_tracks;      /* T, 1..64 slots per stream */
-  int32_t cards_per_frame; /* K, 1..16 */
+  int32_t max_tracks;      /* T, 1..64 slots per stream (MTGV_TRACKER_WIDE: 1..256) */
+  int32_t cards_per_frame; /* K, 1..16 (MTGV_TRACKER_WIDE: 1..64) */
   int32_t dim;             /* embedding size */
   int32_t top_k;           /* 1..8 matches kept per track */
   int32_t hit_counter_max, initialization_delay, period;
@@ -671,6 +674,12 @@ typedef struct {
 typedef struct mtgv_tracker mtgv_tracker;
 /* Anything out of range: status 1, checked before the first HIP call (needs no device). */
 MTGV_API int mtgv_tracker_create(const mtgv_tracker_cfg* cfg, mtgv_tracker** out);
+#define MTGV_TRACKER_WIDE 1
+/* flags 0: mtgv_tracker_create itself (T 1..64, K 1..16, the one-wave update kernel).
+ * MTGV_TRACKER_WIDE: T 1..256, K 1..64, the multi-wave update kernel (one workgroup of ceil(T / 64) waves per stream) at
+ * every size; the same arithmetic, the same results.  Unknown flag bits: status 1.  Checked before the first HIP call.
+ * Every other mtgv_tracker_* call works on both kinds of handle; mtgv_tracker_get_state keeps its layout with the handle's T. */
+MTGV_API int mtgv_tracker_create_ex(const mtgv_tracker_cfg* cfg, int32_t flags, mtgv_tracker** out);
 MTGV_API void mtgv_tracker_destroy(mtgv_tracker* h);
 /* forget the tracks of one stream, or of all (-1): ids start again at 1.  Asynchronous on `stream`. */
 MTGV_API int mtgv_tracker_reset(mtgv_tracker* h, int32_t stream_or_minus_1, void* stream);

@@ -89,7 +89,7 @@ struct mtgv_bank {
 
 struct mtgv_tracker {
   Tracker impl;
-  explicit mtgv_tracker(const mtgv_tracker_cfg& c) : impl(c) {}
+  mtgv_tracker(const mtgv_tracker_cfg& c, int32_t flags) : impl(c, flags) {}
 };
 
 extern "C" {
@@ -101,7 +101,8 @@ MTGV_API const char* mtgv_last_error(void) { return last_error_cstr(); }
 // 106: progressive JPEG (mtgv_jpeg_info_ex / mtgv_jpeg_decoder_create_ex, MTGV_JPEG_PROGRESSIVE)
 // 108: labels across the sharded exchange (mtgv_bank_topk_packed_ex / mtgv_topk_merge_gathered_ex)
 // 109: mtgv_detector_cfg.arch = 12 (YOLO12), mtgv_op_area_attn
-MTGV_API int mtgv_version(void) { return 109; }
+// 110: mtgv_tracker_create_ex, MTGV_TRACKER_WIDE (256 tracks per stream, 64 cards per frame)
+MTGV_API int mtgv_version(void) { return 110; }
 MTGV_API int mtgv_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -305,11 +306,12 @@ MTGV_API int mtgv_topk_merge(float* cand_scores_dev, const int64_t* cand_ids_dev
 }
 
 // ---- tracker ----
-MTGV_API int mtgv_tracker_create(const mtgv_tracker_cfg* cfg, mtgv_tracker** out) {
+MTGV_API int mtgv_tracker_create(const mtgv_tracker_cfg* cfg, mtgv_tracker** out) { return mtgv_tracker_create_ex(cfg, 0, out); }
+MTGV_API int mtgv_tracker_create_ex(const mtgv_tracker_cfg* cfg, int32_t flags, mtgv_tracker** out) {
   return guarded([&] {
-    MTGV_CHECK(cfg != nullptr && out != nullptr, ERR_INVALID, "null argument");
-    (void)tracker_resolve_cfg(*cfg);  // the range check before any HIP call
-    *out = new mtgv_tracker(*cfg);
+    MTGV_CHECK(cfg != nullptr && out != nullptr, ERR_INVALID, "tracker: null argument");
+    (void)tracker_resolve_cfg(*cfg, flags);  // the range check before any HIP call
+    *out = new mtgv_tracker(*cfg, flags);
   });
 }
 MTGV_API void mtgv_tracker_destroy(mtgv_tracker* h) { delete h; }

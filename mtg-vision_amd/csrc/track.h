@@ -1,5 +1,5 @@
 // Device-resident card tracker: mtgv/tracker.py's KalmanPointTracker + TrackerCtx gating for S independent streams,
-// one wave per stream, all state on the GPU (include/mtgv.h: mtgv_tracker_*).
+// one workgroup (one wave; up to four in the wide form) per stream, all state on the GPU (include/mtgv.h: mtgv_tracker_*).
 #pragma once
 #include "common.h"
 #include "mtgv.h"
@@ -8,18 +8,20 @@ namespace mtgv {
 
 constexpr int TRACK_MAX_TRACKS = 64;   // one lane of the wave per slot
 constexpr int TRACK_MAX_CARDS = 16;    // detections of a frame held in LDS
+constexpr int TRACK_WIDE_MAX_TRACKS = 256;  // MTGV_TRACKER_WIDE: one thread of a workgroup of up to four waves per slot
+constexpr int TRACK_WIDE_MAX_CARDS = 64;
 constexpr int TRACK_MAX_TOPK = 8;
 constexpr int TRACK_KAL = 40;          // doubles per slot: pos, vel, pp, pv, vv of the 8 corner coordinates
 constexpr int TRACK_INTS = 6;          // live, hit_counter, is_initializing, id, birth, has_z
 constexpr int TRACK_CTRS = 4;          // per stream: next_id, next_birth, overflow, (unused)
 
 // Policy with the zero fields replaced by the reference's values; throws ERR_INVALID on anything out of range.
-// No HIP call: works on a machine without a GPU.
-mtgv_tracker_cfg tracker_resolve_cfg(const mtgv_tracker_cfg& c);
+// No HIP call: works on a machine without a GPU.  flags: 0 or MTGV_TRACKER_WIDE (the caps of the wide form).
+mtgv_tracker_cfg tracker_resolve_cfg(const mtgv_tracker_cfg& c, int32_t flags = 0);
 
 class Tracker {
  public:
-  explicit Tracker(const mtgv_tracker_cfg& c);
+  explicit Tracker(const mtgv_tracker_cfg& c, int32_t flags = 0);
   ~Tracker();
   Tracker(const Tracker&) = delete;
   Tracker& operator=(const Tracker&) = delete;
@@ -34,6 +36,7 @@ class Tracker {
 
  private:
   mtgv_tracker_cfg c_;
+  bool wide_;  // the multi-wave update kernel, at every size
   int frames_ = 0;  // of the last update: commit / store run over frames_ * K rows
   // state, per (stream, slot); lane-major so that the wave's loads coalesce
   double* kal_ = nullptr;       // (S, TRACK_KAL, T)

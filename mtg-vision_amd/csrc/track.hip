@@ -1,7 +1,8 @@
 // Device-resident card tracker (track.h).  update: one wave64 workgroup per frame = stream, lane t owns track slot t with its
 // filter state in registers, the frame's detections in LDS, the greedy association as at most K rounds of a wave-wide
 // lexicographic minimum over (distance, birth, detection index).  A second, single-workgroup launch compacts the due slots in
-// ascending order.  Everything the host tracker computes in fp64 is computed here in fp64 with the same operations in the
+// ascending order.  The wide form (MTGV_TRACKER_WIDE: up to 256 slots, 64 detections) is a second update kernel with up to
+// four waves per workgroup; the one-wave kernel is what a handle of mtgv_tracker_create launches.  Everything the host tracker computes in fp64 is computed here in fp64 with the same operations in the
 // same order: this translation unit must not contract a * b + c into an FMA.
 #include "track.h"
 
@@ -216,6 +217,225 @@ __global__ __launch_bounds__(64) void track_update_kernel(State st, Params p, Fr
   }
 }
 
+// mean corner distance of detection q to a track's predicted corners: the host's np.linalg.norm(..., axis=1).mean(), the same
+// operations in the same order as the one-wave kernel's distance row
+__device__ __forceinline__ double track_distance(const double* q, const double (&pos)[8]) {
+  double sum = 0.0;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const double dx = q[2 * c] - pos[2 * c], dy = q[2 * c + 1] - pos[2 * c + 1];
+    const double r = __dsqrt_rn(dx * dx + dy * dy);
+    sum = c == 0 ? r : sum + r;
+  }
+  return sum / 4.0;
+}
+
+// The wide form (MTGV_TRACKER_WIDE): one workgroup of W = ceil(T / 64) waves per frame, thread t owns slot t, up to 64
+// detections in LDS.  A track's own arithmetic is the one-wave kernel's; only what crosses a wave differs: the round's minimum
+// is reduced per wave by shuffles and across waves through LDS, the free detections are a 64-bit mask, the free slots W ballots.
+// A lane keeps no distance row: it caches (best, index) over the free detections and rescans from LDS only when that
+// detection was taken by another track (its minimum over the free set changes only then).
+// Every __syncthreads() below is reached by every thread: the loop bounds (nd, two phases) and the early exit are values
+// that all threads read from LDS after a barrier.
+__global__ __launch_bounds__(TRACK_WIDE_MAX_TRACKS) void track_update_wide_kernel(State st, Params p, FrameArgs fr, int f0,
+                                                                                  const float* __restrict__ quads,
+                                                                                  const int32_t* __restrict__ n_det,
+                                                                                  const int32_t* __restrict__ state,
+                                                                                  int32_t* __restrict__ track_id, int32_t* __restrict__ slot_of,
+                                                                                  int32_t* __restrict__ due_flag) {
+  constexpr int KM = TRACK_WIDE_MAX_CARDS, WM = TRACK_WIDE_MAX_TRACKS / 64;
+  __shared__ double det[KM][8];
+  __shared__ int det_k[KM];
+  __shared__ int o_id[KM], o_slot[KM], o_due[KM];
+  __shared__ int s_nd;
+  __shared__ double r_dist[WM];                                   // per wave: its minimum of the round ...
+  __shared__ int r_birth[WM], r_thread[WM], r_di[WM], r_gets[WM];  // ... and whose it is
+  __shared__ unsigned long long s_free[WM];                        // per wave: ballot of its free slots
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, W = blockDim.x >> 6;
+  const int f = f0 + blockIdx.x, s = fr.stream[blockIdx.x];
+  const double now = fr.now[blockIdx.x];
+  const int T = p.T, K = p.K;
+
+  // the frame's detection list: the valid slots in ascending k (K <= 64: all of it in wave 0)
+  if (wave == 0) {
+    bool valid = lane < K;
+    if (valid && n_det != nullptr) valid = lane < min(n_det[f], K);
+    if (valid && state != nullptr) valid = state[(size_t)f * K + lane] > 0;
+    const unsigned long long vm = __ballot(valid);
+    if (lane == 0) s_nd = __popcll(vm);
+    o_id[lane] = 0, o_slot[lane] = -1, o_due[lane] = 0;
+    if (valid) {
+      const int di = __popcll(vm & ((1ull << lane) - 1ull));
+      det_k[di] = lane;
+      const float* q = quads + ((size_t)f * K + lane) * 8;
+#pragma unroll
+      for (int j = 0; j < 8; ++j) det[di][j] = (double)q[j];
+    }
+  }
+  __syncthreads();
+  const int nd = s_nd;  // workgroup-uniform, 0..64
+
+  const bool own = tid < T;
+  int32_t* I = st.ints + (size_t)s * TRACK_INTS * T;
+  double* Kal = st.kal + (size_t)s * TRACK_KAL * T;
+  int32_t* C = st.ctrs + (size_t)s * TRACK_CTRS;
+  int live = 0, hit = 0, init = 0, id = 0, birth = 0, has_z = 0;
+  double last_t = 0.0;
+  if (own) {
+    live = I[0 * T + tid], hit = I[1 * T + tid], init = I[2 * T + tid], id = I[3 * T + tid], birth = I[4 * T + tid];
+    has_z = I[5 * T + tid];
+    last_t = st.last_t[(size_t)s * T + tid];
+  }
+  double pos[8], vel[8], pp[8], pv[8], vv[8];
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    pos[j] = vel[j] = pp[j] = pv[j] = vv[j] = 0.0;
+    if (live) {
+      pos[j] = Kal[(0 + j) * T + tid], vel[j] = Kal[(8 + j) * T + tid], pp[j] = Kal[(16 + j) * T + tid];
+      pv[j] = Kal[(24 + j) * T + tid], vv[j] = Kal[(32 + j) * T + tid];
+    }
+  }
+  int next_id = C[0], next_birth = C[1], overflow = C[2];  // (written by thread 0 behind the last barrier)
+
+  // 1. drop, 2. age and predict
+  if (live && hit < 0) live = 0, id = 0;
+  if (live) {
+    hit -= 1;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) pos[j] = pos[j] + vel[j];
+  }
+
+  // 3. greedy association, closest pair first: the initialised tracks, then the initialising ones on what is left
+  int mdi = -1;  // detection this thread's track took in this frame
+  unsigned long long free_d = nd >= 64 ? ~0ull : ((1ull << nd) - 1ull);  // workgroup-uniform: changed only by values read from LDS
+  for (int phase = 0; phase < 2; ++phase) {
+    const bool cand = live && init == phase;
+    bool used = false, rescan = true;
+    double best = INFINITY;
+    int bdi = -1;
+    for (int round = 0; round < nd; ++round) {
+      if (cand && !used && rescan) {  // (divergent, no barrier inside)
+        best = INFINITY, bdi = -1;
+        for (int di = 0; di < nd; ++di) {
+          if (!((free_d >> di) & 1ull)) continue;
+          const double dist = track_distance(det[di], pos);
+          if (dist < p.thr && dist < best) best = dist, bdi = di;  // a NaN never matches; strict: the lowest index wins a tie
+        }
+        rescan = false;
+      }
+      const double mine = cand && !used ? best : INFINITY;
+      double m = mine;
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) m = fmin(m, __shfl_xor(m, off));
+      int b = mine == m ? birth : INT_MAX;  // ties between tracks: creation order, as the host's list order
+#pragma unroll
+      for (int off = 32; off > 0; off >>= 1) b = min(b, __shfl_xor(b, off));
+      const bool win = mine == m && birth == b;
+      const int wl = max(__ffsll((unsigned long long)__ballot(win)) - 1, 0);
+      const int nh = min(hit + 2 * p.period, p.hmax);
+      if (lane == wl) {  // one lane per wave (the entry is not used when m is not finite)
+        r_dist[wave] = m, r_birth[wave] = b, r_thread[wave] = tid, r_di[wave] = bdi;
+        r_gets[wave] = (init && nh > p.delay) ? 1 : 0;
+      }
+      __syncthreads();
+      double gm = INFINITY;
+      int gb = INT_MAX, gt = -1, gdi = -1, gets_id = 0;
+      for (int w = 0; w < W; ++w) {
+        const double wm = r_dist[w];
+        const int wb = r_birth[w];
+        if (wm < gm || (wm == gm && wm < INFINITY && wb < gb)) gm = wm, gb = wb, gt = r_thread[w], gdi = r_di[w], gets_id = r_gets[w];
+      }
+      __syncthreads();  // all have read the entries before the next round (or phase) rewrites them
+      if (!(gm < INFINITY)) break;  // workgroup-uniform: gm was read from LDS behind a barrier by every thread
+      free_d &= ~(1ull << gdi);
+      if (tid == gt) {
+        used = true;
+        mdi = gdi;
+        hit = nh;
+        if (gets_id) init = 0, id = next_id, has_z = 0;
+#pragma unroll
+        for (int j = 0; j < 8; ++j) {  // _KalmanTrack.kalman_update
+          const double e = det[gdi][j] - pos[j];
+          const double sv = pp[j] + 2.0 * pv[j] + vv[j] + KAL_Q + KAL_R;
+          const double k0 = 1.0 - KAL_R / sv, k1 = (pv[j] + vv[j]) / sv;
+          pos[j] = pos[j] + k0 * e;
+          vel[j] = vel[j] + k1 * e;
+          const double nvv = vv[j] + KAL_Q - k1 * k1 * sv;
+          pp[j] = k0 * KAL_R, pv[j] = k1 * KAL_R, vv[j] = nvv;
+        }
+      } else if (bdi == gdi) {
+        rescan = true;  // the cached minimum was taken
+      }
+      next_id += gets_id;
+    }
+  }
+
+  // 4. unmatched detections, ascending, take the lowest free slot of the whole workgroup
+  {
+    const unsigned long long fb = __ballot(own && !live);
+    if (lane == 0) s_free[wave] = fb;
+  }
+  __syncthreads();
+  unsigned long long freem[WM];
+#pragma unroll
+  for (int w = 0; w < WM; ++w) freem[w] = w < W ? s_free[w] : 0ull;
+  const bool new_init = p.period <= p.delay;
+  bool fresh = false;
+  for (int di = 0; di < nd; ++di) {  // workgroup-uniform: nd, free_d and freem are the same in every thread
+    if (!((free_d >> di) & 1ull)) continue;
+    int sl = -1;
+#pragma unroll
+    for (int w = 0; w < WM; ++w)
+      if (sl < 0 && freem[w] != 0ull) sl = w * 64 + __ffsll(freem[w]) - 1, freem[w] &= freem[w] - 1ull;
+    if (sl < 0) {
+      overflow += 1;
+      continue;
+    }
+    if (tid == sl) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) pos[j] = det[di][j], vel[j] = 0.0, pp[j] = KAL_POS_VAR, pv[j] = 0.0, vv[j] = KAL_VEL_VAR;
+      live = 1, hit = p.period, init = new_init ? 1 : 0, id = new_init ? 0 : next_id, birth = next_birth;
+      has_z = 0, last_t = 0.0, mdi = di, fresh = true;
+    }
+    if (!new_init) next_id += 1;
+    next_birth += 1;
+  }
+
+  // 5. report and gate
+  const bool rep = live && id > 0 && mdi >= 0 && hit >= 0;
+  const bool due = rep && (!has_z || now - last_t > p.wait);
+  if (due) last_t = now;
+  if (rep) {
+    const int k = det_k[mdi];
+    o_id[k] = id, o_slot[k] = s * T + tid, o_due[k] = due ? 1 : 0;
+  }
+
+  if (own) {
+    I[0 * T + tid] = live, I[1 * T + tid] = hit, I[2 * T + tid] = init, I[3 * T + tid] = id, I[4 * T + tid] = birth;
+    I[5 * T + tid] = has_z;
+    st.last_t[(size_t)s * T + tid] = last_t;
+    if (live) {
+#pragma unroll
+      for (int j = 0; j < 8; ++j) {
+        Kal[(0 + j) * T + tid] = pos[j], Kal[(8 + j) * T + tid] = vel[j], Kal[(16 + j) * T + tid] = pp[j];
+        Kal[(24 + j) * T + tid] = pv[j], Kal[(32 + j) * T + tid] = vv[j];
+      }
+    }
+    if (fresh) {
+      for (int t = 0; t < p.top_k; ++t) {
+        st.m_ids[((size_t)s * T + tid) * p.top_k + t] = -1;
+        st.m_scores[((size_t)s * T + tid) * p.top_k + t] = -INFINITY;
+      }
+    }
+  }
+  if (tid == 0) C[0] = next_id, C[1] = next_birth, C[2] = overflow;
+  __syncthreads();
+  if (tid < K) {
+    const size_t o = (size_t)f * K + tid;
+    track_id[o] = o_id[tid], slot_of[o] = o_slot[tid], due_flag[o] = o_due[tid];
+  }
+}
+
 // ordered compaction of the due slots: one wave walks the n = F * K flags in ascending order (no atomics, so the order of
 // due_idx does not depend on which workgroup finished first); entries behind n_due are -1
 __global__ __launch_bounds__(64) void track_compact_kernel(const int32_t* __restrict__ due_flag, int n, int32_t* __restrict__ due_idx,
@@ -324,12 +544,15 @@ void dev_alloc(P*& p, size_t count) {
 
 }  // namespace
 
-mtgv_tracker_cfg tracker_resolve_cfg(const mtgv_tracker_cfg& in) {
+mtgv_tracker_cfg tracker_resolve_cfg(const mtgv_tracker_cfg& in, int32_t flags) {
   mtgv_tracker_cfg c = in;
+  MTGV_CHECK((flags & ~MTGV_TRACKER_WIDE) == 0, ERR_INVALID, "tracker: unknown flags 0x%x", (unsigned)flags);
+  const int max_t = (flags & MTGV_TRACKER_WIDE) ? TRACK_WIDE_MAX_TRACKS : TRACK_MAX_TRACKS;
+  const int max_k = (flags & MTGV_TRACKER_WIDE) ? TRACK_WIDE_MAX_CARDS : TRACK_MAX_CARDS;
   MTGV_CHECK(c.streams >= 1 && c.streams <= 4096, ERR_INVALID, "tracker: streams %d outside 1..4096", c.streams);
-  MTGV_CHECK(c.max_tracks >= 1 && c.max_tracks <= TRACK_MAX_TRACKS, ERR_INVALID, "tracker: max_tracks %d outside 1..%d", c.max_tracks, TRACK_MAX_TRACKS);
-  MTGV_CHECK(c.cards_per_frame >= 1 && c.cards_per_frame <= TRACK_MAX_CARDS, ERR_INVALID, "tracker: cards_per_frame %d outside 1..%d",
-             c.cards_per_frame, TRACK_MAX_CARDS);
+  MTGV_CHECK(c.max_tracks >= 1 && c.max_tracks <= max_t, ERR_INVALID, "tracker: max_tracks %d outside 1..%d", c.max_tracks, max_t);
+  MTGV_CHECK(c.cards_per_frame >= 1 && c.cards_per_frame <= max_k, ERR_INVALID, "tracker: cards_per_frame %d outside 1..%d", c.cards_per_frame,
+             max_k);
   MTGV_CHECK(c.dim >= 1 && c.dim <= 65536, ERR_INVALID, "tracker: dim %d outside 1..65536", c.dim);
   MTGV_CHECK(c.top_k >= 1 && c.top_k <= TRACK_MAX_TOPK, ERR_INVALID, "tracker: top_k %d outside 1..%d", c.top_k, TRACK_MAX_TOPK);
   // zero: the reference's value (mtgvision/server.py:100-106, :41-43)
@@ -350,7 +573,7 @@ mtgv_tracker_cfg tracker_resolve_cfg(const mtgv_tracker_cfg& in) {
   return c;
 }
 
-Tracker::Tracker(const mtgv_tracker_cfg& c) : c_(tracker_resolve_cfg(c)) {
+Tracker::Tracker(const mtgv_tracker_cfg& c, int32_t flags) : c_(tracker_resolve_cfg(c, flags)), wide_((flags & MTGV_TRACKER_WIDE) != 0) {
   const size_t S = c_.streams, T = c_.max_tracks, K = c_.cards_per_frame;
   dev_alloc(kal_, S * TRACK_KAL * T);
   dev_alloc(ints_, S * TRACK_INTS * T);
@@ -400,7 +623,11 @@ void Tracker::update(const float* quads, const int32_t* n_det, const int32_t* st
     const int n = std::min(FRAMES_PER_LAUNCH, frames - f0);
     FrameArgs fr = {};
     for (int i = 0; i < n; ++i) fr.stream[i] = stream_of_frame[f0 + i], fr.now[i] = now[f0 + i];
-    hipLaunchKernelGGL(track_update_kernel, dim3(n), dim3(64), 0, s, st, p, fr, f0, quads, n_det, state, track_id, slot_of_, due_flag_);
+    if (wide_)
+      hipLaunchKernelGGL(track_update_wide_kernel, dim3(n), dim3(64 * ceil_div(c_.max_tracks, 64)), 0, s, st, p, fr, f0, quads, n_det, state, track_id,
+                         slot_of_, due_flag_);
+    else
+      hipLaunchKernelGGL(track_update_kernel, dim3(n), dim3(64), 0, s, st, p, fr, f0, quads, n_det, state, track_id, slot_of_, due_flag_);
   }
   hipLaunchKernelGGL(track_compact_kernel, dim3(1), dim3(64), 0, s, due_flag_, frames * c_.cards_per_frame, due_idx, rank_of_, n_due);
   HIP_OK(hipGetLastError());

@@ -94,6 +94,7 @@ class TrackerCfg(C.Structure):
     )
 
 
+TRACKER_WIDE = 1  # MTGV_TRACKER_WIDE: the flag of mtgv_tracker_create_ex
 JPEG_PROGRESSIVE = 1  # MTGV_JPEG_PROGRESSIVE: the flag of mtgv_jpeg_info_ex / mtgv_jpeg_decoder_create_ex
 
 # name -> (restype, argtypes); every symbol include/mtgv.h declares
@@ -201,6 +202,7 @@ SIGNATURES = {
     "mtgv_op_block_workspace_floats": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
     "mtgv_op_l2norm": (C.c_int, [c_vp, c_vp, c_i64, c_i32, c_vp]),
     "mtgv_tracker_create": (C.c_int, [C.POINTER(TrackerCfg), C.POINTER(c_vp)]),
+    "mtgv_tracker_create_ex": (C.c_int, [C.POINTER(TrackerCfg), c_i32, C.POINTER(c_vp)]),  # mtgv_version >= 110
     "mtgv_tracker_destroy": (None, [c_vp]),
     "mtgv_tracker_reset": (C.c_int, [c_vp, c_i32, c_vp]),
     "mtgv_tracker_update": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),

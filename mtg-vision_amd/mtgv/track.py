@@ -7,9 +7,11 @@ embeddings queries the bank and the last matches stay on the track.  `mtgv.track
 cameras with all state on the device (csrc/track.hip), `TrackedPipeline` puts it between the crop and the embed stage of
 `Pipeline`.
 
-Limits the host tracker does not have: at most `max_tracks` (<= 64) live tracks per stream - a detection that finds no
-free slot is dropped and counted (`state(s)["overflow"]`) - at most 16 cards per frame, and every stream at most once per
-step.  Like the host class it restates norfair's published algorithm: parity with norfair itself is unpinned.
+Limits the host tracker does not have: at most `max_tracks` (<= 256) live tracks per stream - a detection that finds no
+free slot is dropped and counted (`state(s)["overflow"]`) - at most 64 cards per frame, every stream at most once per
+step, int32 ids, and at most 65535 rows (frames * cards per frame) in a step that is gathered.  Up to 64 tracks and 16
+cards run on the one-wave update kernel; anything larger (or `wide=True` at any size) on the multi-wave one, opt-in in
+the C ABI (`mtgv_tracker_create_ex`, `MTGV_TRACKER_WIDE`), with the same results.  Like the host class it restates norfair's published algorithm: parity with norfair itself is unpinned.
 """
 
 from __future__ import annotations
@@ -56,9 +58,13 @@ class DeviceTracker:
 
     A step is update -> (read n_due) -> gather -> encode -> commit -> match -> store; every call is asynchronous on the
     current stream.  policy: distance_threshold, hit_counter_max, initialization_delay, period, update_wait_sec,
-    ewma_weight (defaults: the reference's 300, 5, 2, 1, 0.5 s, 0.1)."""
+    ewma_weight (defaults: the reference's 300, 5, 2, 1, 0.5 s, 0.1).
 
-    def __init__(self, streams: int, cards_per_frame: int, dim: int, top_k: int = 3, max_tracks: int = 64, device=None, **policy):
+    wide: None picks the wide handle (max_tracks <= 256, cards_per_frame <= 64, the multi-wave update kernel) iff
+    max_tracks > 64 or cards_per_frame > 16; True forces it at any size; False is the narrow handle, refusals included."""
+
+    def __init__(self, streams: int, cards_per_frame: int, dim: int, top_k: int = 3, max_tracks: int = 64, device=None, wide: Optional[bool] = None,
+                 **policy):
         native.require_gpu()
         self.streams, self.K, self.dim, self.top_k, self.max_tracks = int(streams), int(cards_per_frame), int(dim), int(top_k), int(max_tracks)
         self.device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
@@ -67,9 +73,10 @@ class DeviceTracker:
         cfg = native.TrackerCfg()
         cfg.streams, cfg.max_tracks, cfg.cards_per_frame, cfg.dim, cfg.top_k = self.streams, self.max_tracks, self.K, self.dim, self.top_k
         _policy_cfg(cfg, policy)
+        self.wide = (self.max_tracks > 64 or self.K > 16) if wide is None else bool(wide)
         self._h = native.c_vp(0)
         with torch.cuda.device(self.device):
-            native.check(native.lib().mtgv_tracker_create(C.byref(cfg), C.byref(self._h)))
+            native.check(native.lib().mtgv_tracker_create_ex(C.byref(cfg), native.TRACKER_WIDE if self.wide else 0, C.byref(self._h)))
         self._frames = 0
         self._due_idx = self._n_due = None
 
@@ -183,15 +190,18 @@ class TrackedPipeline:
     the current stream.  The overlapped schedule of `Pipeline.run_many` is not offered: the read-back of n_due would stall
     the stream that holds it."""
 
-    def __init__(self, pipeline, streams: int, top_k: int = 3, max_tracks: int = 64, match_opts: Optional[dict] = None, **policy):
+    def __init__(self, pipeline, streams: int, top_k: int = 3, max_tracks: int = 64, match_opts: Optional[dict] = None,
+                 wide: Optional[bool] = None, **policy):
         """match_opts: keyword arguments for `Matcher.match` (`filter`, `distinct`, `threshold`): {"distinct": True} makes a
-        track's top_k matches top_k different cards (the bank's rows carry groups).  None: the plain match."""
+        track's top_k matches top_k different cards (the bank's rows carry groups).  None: the plain match.
+        wide: as for `DeviceTracker` (None: by size, so 24 cards per frame or 128 tracks just work)."""
         # (each rank has its own number of due tracks; the sharded exchange needs equal query counts on every rank)
         assert not getattr(pipeline.matcher, "issues_collectives", False), "TrackedPipeline does not run on a sharded bank"
         self.pipeline = pipeline
         self.top_k = int(top_k)
         self.match_opts = dict(match_opts) if match_opts else None
-        self.tracker = DeviceTracker(streams, pipeline.K, pipeline.encoder.cfg.z_size, self.top_k, max_tracks, pipeline.detector.device, **policy)
+        self.tracker = DeviceTracker(streams, pipeline.K, pipeline.encoder.cfg.z_size, self.top_k, max_tracks, pipeline.detector.device, wide=wide,
+                                     **policy)
         self.last_z = None  # the embeddings committed by the last step (n_due, dim), None when nothing was due
 
     def _crop(self, frames_u8, det):

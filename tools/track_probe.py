@@ -10,6 +10,9 @@ and the tracker's launches one by one.  The frames are bench.py's: four batches 
 are whatever the random-weight detector sees in noise; the association is real work, the tracks are not real cards.
 
     python tools/track_probe.py [--steps 40 --settle-steps 160 --out FILE]
+                                [--cards K --max-tracks T --wide auto|on|off]   the tracker's size and update kernel
+                                [--synthetic]   and the launches again in a synthetic steady state: T live tracks per stream,
+                                                disjoint sets of K cards in rotation, every detection matched
 """
 from __future__ import annotations
 
@@ -38,6 +41,42 @@ def _timed(fn, n):
     return a.elapsed_time(b) / n, r
 
 
+def _synthetic(F, K, T, wide, crops, encoder, matcher):
+    """the tracker's launches with every slot in use: T // K disjoint sets of K cards (700 px apart) shown in rotation to
+    tracks that outlive the rotation, so each step matches K detections against T live tracks per stream in K rounds"""
+    from mtgv.track import DeviceTracker
+
+    n_sets = max(T // K, 1)
+    trk = DeviceTracker(F, K, 768, 3, max_tracks=T, wide=wide, period=8, hit_counter_max=15, initialization_delay=10, update_wait_sec=0.0)
+    sets = []
+    for r in range(n_sets):
+        c = np.arange(r * K, (r + 1) * K)
+        ctr = np.stack([100 + 700.0 * (c % 32), 100 + 700.0 * (c // 32)], -1)[:, None, :]
+        q = ctr + np.array([[-40, -60], [40, -60], [40, 60], [-40, 60]], np.float64)[None]
+        sets.append(torch.from_numpy(np.broadcast_to(q.astype(np.float32), (F, K, 4, 2)).copy()).cuda())
+    n_det = torch.full((F,), K, dtype=torch.int32, device="cuda")
+    streams, t = list(range(F)), [0.0]
+
+    def upd(i):
+        t[0] += 1.0
+        return trk.update(sets[i % n_sets], streams, t[0], n_det=n_det)
+
+    for i in range(3 * n_sets):  # every track has its id
+        upd(i)
+    n = 50
+    ms_upd, (tid, _, n_due_dev) = _timed(upd, n)
+    n_due = int(n_due_dev.item())
+    live = int(trk.state(0)["live"].sum())
+    ms_gather, packed = _timed(lambda i: trk.gather(crops), n)
+    z = encoder.encode(packed[:max(n_due, 1)])
+    ms_commit, q = _timed(lambda i: trk.commit(z), n)
+    ids, scores = matcher.match(q, 3)
+    ms_store, _ = _timed(lambda i: trk.store(ids, scores), n)
+    return (f"synthetic steady state, {live} live tracks per stream, {int((tid > 0).sum())} of {F * K} slots matched, n_due = {n_due} "
+            f"(mean of {n} back-to-back calls): update + compaction {ms_upd * 1e3:.1f} us, gather {ms_gather * 1e3:.1f} us, "
+            f"commit {ms_commit * 1e3:.1f} us, store {ms_store * 1e3:.1f} us")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=32)
@@ -46,6 +85,9 @@ def main():
     ap.add_argument("--steps", type=int, default=40)
     ap.add_argument("--settle-steps", type=int, default=160)
     ap.add_argument("--warmup", type=int, default=3)
+    ap.add_argument("--max-tracks", type=int, default=64)
+    ap.add_argument("--wide", choices=("auto", "on", "off"), default="auto", help="the multi-wave update kernel: by size, forced, refused")
+    ap.add_argument("--synthetic", action="store_true")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
 
@@ -57,7 +99,8 @@ def main():
     from mtgv.track import TrackedPipeline
 
     torch.cuda.set_device(0)
-    F, K = a.frames, a.cards
+    F, K, T = a.frames, a.cards, a.max_tracks
+    wide = {"auto": None, "on": True, "off": False}[a.wide]
     det_cfg = spec.DetectorConfig()
     enc_cfg = spec.encoder_config("cnvnxt2ae_tiny", (192, 128), "conv+linear")
     detector = Detector(det_cfg, spec.random_detector_state(det_cfg, 3), max_batch=F)
@@ -75,7 +118,7 @@ def main():
             pipe.run(batches[i % 4])
         torch.cuda.synchronize()
 
-    lines = [f"# track_probe: {torch.cuda.get_device_name(0)}, {F} streams x {K} cards, AE-tiny, bank {a.bank} x 768, mask quads, "
+    lines = [f"# track_probe: {torch.cuda.get_device_name(0)}, {F} streams x {K} cards, {T} slots per stream, wide={a.wide}, AE-tiny, bank {a.bank} x 768, mask quads, "
              f"{a.steps} steps after {a.settle_steps} settle + {a.warmup} warm-up steps"]
     ms1, _ = _timed(lambda i: pipe.run(batches[i % 4]), a.warmup)
     ms1, _ = _timed(lambda i: pipe.run(batches[i % 4]), a.steps)
@@ -86,7 +129,7 @@ def main():
     lines.append(f"(1) Pipeline.run (untracked, top-3)                  {ms1:7.3f} ms/step  {F * K / ms1 * 1e3:9.0f} cards/s  embeds/step {F * K}")
 
     def tracked(label, **policy):
-        tp = TrackedPipeline(pipe, streams=F, top_k=3, **policy)
+        tp = TrackedPipeline(pipe, streams=F, top_k=3, max_tracks=T, wide=wide, **policy)
         clock, due = [0.0], []
 
         def step(i):
@@ -128,6 +171,8 @@ def main():
     lines.append(f"tracker launches at n_due = {n_due} (mean of {n} back-to-back calls, host call overhead included): update + compaction (2 launches) "
                  f"{ms_upd * 1e3:.1f} us, n_due read-back {ms_read * 1e3:.1f} us, gather {ms_gather * 1e3:.1f} us, commit {ms_commit * 1e3:.1f} us, "
                  f"store {ms_store * 1e3:.1f} us; sum {(ms_upd + ms_read + ms_gather + ms_commit + ms_store) * 1e3:.1f} us; (2) - (1) = {(ms2 - ms1) * 1e3:.0f} us")
+    if a.synthetic:
+        lines.append(_synthetic(F, K, T, wide, crops, encoder, matcher))
     text = "\n".join(lines)
     print(text)
     if a.out:
