@@ -36,7 +36,8 @@ extern "C" {
 #endif
 
 MTGV_API const char* mtgv_last_error(void);
-/* 110: mtgv_tracker_create_ex / MTGV_TRACKER_WIDE (256 tracks per stream, 64 cards per frame) */
+/* 110: mtgv_tracker_create_ex / MTGV_TRACKER_WIDE (256 tracks per stream, 64 cards per frame)
+ * 111: mtgv_letterbox_ragged_u8, mtgv_warp_quads_src (crops from full-resolution source frames) */
 MTGV_API int mtgv_version(void);
 /* number of HIP devices visible; does not initialise a device context */
 MTGV_API int mtgv_device_count(void);
@@ -449,6 +450,21 @@ MTGV_API size_t mtgv_warp_workspace_bytes(int32_t nq);
 MTGV_API int mtgv_warp_quads(const uint8_t* frames_dev, int32_t nf, int32_t fh, int32_t fw, const float* quads_dev,
                              const int32_t* frame_idx_dev, int32_t nq, int32_t out_h, int32_t out_w, double expand_ratio,
                              uint8_t* out_dev, void* workspace_dev, size_t workspace_bytes, void* stream);
+/* The same from source frames of their own sizes (mtgv_version >= 111): the crops are sampled from the frames the camera
+ * delivered, not from their letterboxed copies.  src_dev: nf uint8 HWC RGB frames back to back, offsets_dev (nf) int64 byte
+ * offset of each (any alignment), hw_dev (nf, 2) int32 height, width - the ragged layout of mtgv_make_cropped - plus
+ * geo_dev (nf, 4) int32 = nh, nw, top, left and ratio_dev (nf) float64: each frame's letterbox into the detector's input
+ * (mtgv.detector.fit_geometry; only top, left and the ratio are read here).  quads_dev (nq, 4, 2) float32 are pixels of
+ * that input; quads_src_dev (nq, 4, 2) float32 receives every corner in the pixels of its own frame, in float64
+ * x = (x_det - left) / ratio clipped to [0, w], y = (y_det - top) / ratio clipped to [0, h], rounded to float32
+ * (ultralytics' scale_coords + clip_coords, mtgv.adapters: to_frame).  The homographies are solved from quads_src and each
+ * crop is sampled from frame frame_idx_dev[q] with mtgv_warp_quads' arithmetic: for frames of one size the crops equal
+ * mtgv_warp_quads(src, quads_src) bit for bit.  No byte outside a frame's own h * w * 3 is read.  A frame index outside
+ * [0, nf) or a frame with h or w <= 0 gives a crop of zeros.  The caller guarantees offsets[i] + h * w * 3 <= the buffer. */
+MTGV_API int mtgv_warp_quads_src(const uint8_t* src_dev, const int64_t* offsets_dev, const int32_t* hw_dev, const int32_t* geo_dev,
+                                 const double* ratio_dev, int32_t nf, const float* quads_dev, const int32_t* frame_idx_dev, int32_t nq,
+                                 int32_t out_h, int32_t out_w, double expand_ratio, uint8_t* out_dev, float* quads_src_dev,
+                                 void* workspace_dev, size_t workspace_bytes, void* stream);
 
 /* ------------------------------------------------------------------------- */
 /* Bank build: card image -> encoder input.                */
@@ -473,6 +489,14 @@ MTGV_API int mtgv_letterbox_u8(const uint8_t* src_dev, int32_t h, int32_t w, uin
  * is the n = 1, dst_h = dst_w case of the same kernel); a frame with (nh, nw) == (h, w) is copied exactly. */
 MTGV_API int mtgv_letterbox_rect_u8(const uint8_t* src_dev, int32_t n, int32_t h, int32_t w, uint8_t* dst_dev, int32_t dst_h, int32_t dst_w,
                                     int32_t nh, int32_t nw, int32_t top, int32_t left, int32_t pad_value, void* stream);
+/* the same for n frames of different sizes in one launch (mtgv_version >= 111): src_dev, offsets_dev (n) int64, hw_dev (n, 2)
+ * int32 as for mtgv_make_cropped, geo_dev (n, 4) int32 = nh, nw, top, left of each frame (the host computes them:
+ * mtgv.detector.fit_geometry).  Frame i goes to dst_dev[i] of (n, dst_h, dst_w, 3), pad included; byte for byte what
+ * mtgv_letterbox_rect_u8 writes frame by frame.  The arrays live on the device and are not validated by the host: whatever
+ * geo_dev holds, source positions are clamped into the frame and writes stay inside dst_dev[i]; a frame with h or w <= 0 is
+ * all pad.  The caller guarantees offsets[i] + h * w * 3 <= the buffer. */
+MTGV_API int mtgv_letterbox_ragged_u8(const uint8_t* src_dev, const int64_t* offsets_dev, const int32_t* hw_dev, const int32_t* geo_dev,
+                                      int32_t n, uint8_t* dst_dev, int32_t dst_h, int32_t dst_w, int32_t pad_value, void* stream);
 /* fills the pad of n letterboxed (size, size, 3) uint8 frames with pad_value: every pixel outside the (nh, nw) rectangle
  * at (top, left), which someone else writes (mtgv.jpeg.JpegDecoder.decode_frames decodes a frame that already fits
  * straight into it) */

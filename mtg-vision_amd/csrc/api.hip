@@ -102,7 +102,8 @@ MTGV_API const char* mtgv_last_error(void) { return last_error_cstr(); }
 // 108: labels across the sharded exchange (mtgv_bank_topk_packed_ex / mtgv_topk_merge_gathered_ex)
 // 109: mtgv_detector_cfg.arch = 12 (YOLO12), mtgv_op_area_attn
 // 110: mtgv_tracker_create_ex, MTGV_TRACKER_WIDE (256 tracks per stream, 64 cards per frame)
-MTGV_API int mtgv_version(void) { return 110; }
+// 111: mtgv_letterbox_ragged_u8, mtgv_warp_quads_src (crops from full-resolution source frames)
+MTGV_API int mtgv_version(void) { return 111; }
 MTGV_API int mtgv_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;

@@ -60,15 +60,11 @@ __global__ __launch_bounds__(256) void make_cropped_kernel(const uint8_t* __rest
 // filled with pad_value.  Thread = one output pixel.  The resample is the align_corners = False form PyTorch's
 // interpolate uses, in float32 in this order: src = scale * (dst + 0.5) - 0.5 clamped at 0, h0 * (w0 * v00 + w1 * v01) +
 // h1 * (w0 * v10 + w1 * v11), rounded to nearest even, clamped to [0, 255] (oracle/resize_ref.py: letterbox).  A frame
-// that already has the target size is copied exactly (all weights 0 or 1).  blockIdx.y: one of n same-sized frames.
-__global__ __launch_bounds__(256) void letterbox_u8_kernel(const uint8_t* __restrict__ src, int h, int w, uint8_t* __restrict__ dst, int dst_h,
-                                                          int dst_w, int nh, int nw, int top, int left, int pad_value) {
+// that already has the target size is copied exactly (all weights 0 or 1).  letterbox_pixel is output pixel (y, x) of one
+// frame, shared by the two kernels below.
+__device__ __forceinline__ void letterbox_pixel(const uint8_t* __restrict__ src, int h, int w, uint8_t* __restrict__ o, int y, int x, int nh,
+                                                int nw, int top, int left, int pad_value) {
 #pragma clang fp contract(off)
-  const int idx = blockIdx.x * 256 + threadIdx.x;
-  if (idx >= dst_h * dst_w) return;
-  const int y = idx / dst_w, x = idx - y * dst_w;
-  src += (long)blockIdx.y * h * w * 3;
-  uint8_t* o = dst + ((long)blockIdx.y * dst_h * dst_w + idx) * 3;
   const int ry = y - top, rx = x - left;
   if (ry < 0 || ry >= nh || rx < 0 || rx >= nw) {
     o[0] = o[1] = o[2] = (uint8_t)pad_value;
@@ -93,6 +89,32 @@ __global__ __launch_bounds__(256) void letterbox_u8_kernel(const uint8_t* __rest
     r = r < 0.f ? 0.f : (r > 255.f ? 255.f : r);
     o[c] = (uint8_t)r;
   }
+}
+
+// blockIdx.y: one of n same-sized frames
+__global__ __launch_bounds__(256) void letterbox_u8_kernel(const uint8_t* __restrict__ src, int h, int w, uint8_t* __restrict__ dst, int dst_h,
+                                                          int dst_w, int nh, int nw, int top, int left, int pad_value) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= dst_h * dst_w) return;
+  const int y = idx / dst_w, x = idx - y * dst_w;
+  letterbox_pixel(src + (long)blockIdx.y * h * w * 3, h, w, dst + ((long)blockIdx.y * dst_h * dst_w + idx) * 3, y, x, nh, nw, top, left,
+                  pad_value);
+}
+
+// blockIdx.y: one of n frames of their own sizes (the ragged layout of make_cropped_kernel) and their own geometry.  The
+// tables come from device memory unchecked: reads are clamped into the frame whatever geo holds, a frame without pixels is
+// all pad (nh = 0), and a thread writes only its own pixel of dst.
+__global__ __launch_bounds__(256) void letterbox_ragged_u8_kernel(const uint8_t* __restrict__ src, const long* __restrict__ offsets,
+                                                                 const int* __restrict__ hw, const int* __restrict__ geo,
+                                                                 uint8_t* __restrict__ dst, int dst_h, int dst_w, int pad_value) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= dst_h * dst_w) return;
+  const int y = idx / dst_w, x = idx - y * dst_w;
+  const int f = blockIdx.y;
+  const int h = hw[f * 2], w = hw[f * 2 + 1];
+  const int nh = (h > 0 && w > 0) ? geo[f * 4] : 0;
+  letterbox_pixel(src + offsets[f], h, w, dst + ((long)f * dst_h * dst_w + idx) * 3, y, x, nh, geo[f * 4 + 1], geo[f * 4 + 2], geo[f * 4 + 3],
+                  pad_value);
 }
 
 // pad of n letterboxed dst_h x dst_w x 3 frames whose (nh, nw) image at (top, left) is written by someone else
@@ -144,6 +166,18 @@ MTGV_API int mtgv_letterbox_u8(const uint8_t* src_dev, int32_t h, int32_t w, uin
 MTGV_API int mtgv_letterbox_rect_u8(const uint8_t* src_dev, int32_t n, int32_t h, int32_t w, uint8_t* dst_dev, int32_t dst_h, int32_t dst_w,
                                     int32_t nh, int32_t nw, int32_t top, int32_t left, int32_t pad_value, void* stream) {
   return guarded([&] { letterbox_launch(src_dev, n, h, w, dst_dev, dst_h, dst_w, nh, nw, top, left, pad_value, (hipStream_t)stream); });
+}
+MTGV_API int mtgv_letterbox_ragged_u8(const uint8_t* src_dev, const int64_t* offsets_dev, const int32_t* hw_dev, const int32_t* geo_dev,
+                                      int32_t n, uint8_t* dst_dev, int32_t dst_h, int32_t dst_w, int32_t pad_value, void* stream) {
+  return guarded([&] {
+    MTGV_CHECK(n >= 0 && n <= 65535 && dst_h > 0 && dst_w > 0 && (long)dst_h * dst_w < (1l << 30) && pad_value >= 0 && pad_value <= 255,
+               ERR_INVALID, "letterbox ragged: %d frames -> %dx%d, pad value %d", n, dst_h, dst_w, pad_value);
+    if (n == 0) return;
+    MTGV_CHECK(src_dev && offsets_dev && hw_dev && geo_dev && dst_dev, ERR_INVALID, "null argument");
+    hipLaunchKernelGGL(letterbox_ragged_u8_kernel, dim3((dst_h * dst_w + 255) / 256, n), dim3(256), 0, (hipStream_t)stream, src_dev,
+                       (const long*)offsets_dev, hw_dev, geo_dev, dst_dev, dst_h, dst_w, pad_value);
+    HIP_OK(hipGetLastError());
+  });
 }
 MTGV_API int mtgv_letterbox_pad_u8(uint8_t* frames_dev, int32_t n, int32_t size, int32_t nh, int32_t nw, int32_t top, int32_t left,
                                    int32_t pad_value, void* stream) {

@@ -18,10 +18,41 @@
 
 namespace mtgv {
 
+// What the source-frame form of the two kernels below reads per quad (mtgv_warp_quads_src); the same-size form
+// (mtgv_warp_quads) has the frame geometry per launch and carries nothing.
+template <bool SRC>
+struct SourceTables {};
+template <>
+struct SourceTables<true> {
+  const long* offsets;  // (nf) byte offset of every frame in the ragged buffer
+  const int* hw;        // (nf, 2) height, width
+  const int* geo;       // (nf, 4) nh, nw, top, left of the frame's letterbox into the detector's input
+  const double* ratio;  // (nf)
+  int nf;
+  const int* frame_idx;  // (nq)
+  float* quads_src;      // (nq, 4, 2) out
+};
+
+// SRC: the quads are pixels of the detector's input and the crops come from the source frames.  Every corner goes back
+// into its own frame first - ultralytics' scale_coords + clip_coords (mtgv/adapters.py: to_frame) in float64,
+// (x - left) / ratio clipped to [0, w], (y - top) / ratio clipped to [0, h], rounded to float32 - is written to quads_src,
+// and the system is solved from those float32 corners: what this kernel without SRC computes from quads_src.  A frame
+// index outside [0, nf): corners 0, a singular system, a crop of zeros.
+template <bool SRC>
 __global__ __launch_bounds__(64) void warp_coeffs_kernel(const float* __restrict__ quads, int nq, int out_h, int out_w,
-                                                        double expand, double* __restrict__ coef) {
+                                                        double expand, double* __restrict__ coef, const SourceTables<SRC> tab) {
   const int q = blockIdx.x * 64 + threadIdx.x;
   if (q >= nq) return;
+  bool known = true;
+  double fw = 0.0, fh = 0.0, top = 0.0, left = 0.0, ratio = 1.0;
+  if constexpr (SRC) {
+    const int f = tab.frame_idx[q];
+    known = f >= 0 && f < tab.nf;
+    if (known) {
+      fh = (double)tab.hw[f * 2], fw = (double)tab.hw[f * 2 + 1];
+      top = (double)tab.geo[f * 4 + 2], left = (double)tab.geo[f * 4 + 3], ratio = tab.ratio[f];
+    }
+  }
   const double w = (double)out_w, h = (double)out_h, e = expand;
   // dst_pts = (1 + e) * [[0,0],[w,0],[w,h],[0,h]] - 0.5 * e * [w,h]   (od_export.py:102-106), float32 like the reference
   const float dxs[4] = {0.f, (float)w, (float)w, 0.f}, dys[4] = {0.f, 0.f, (float)h, (float)h};
@@ -29,8 +60,19 @@ __global__ __launch_bounds__(64) void warp_coeffs_kernel(const float* __restrict
   for (int i = 0; i < 4; ++i) {
     u[i] = (double)(float)((1.0 + e) * (double)dxs[i] - (0.5 * e) * w);
     v[i] = (double)(float)((1.0 + e) * (double)dys[i] - (0.5 * e) * h);
-    x[i] = (double)quads[(q * 4 + i) * 2 + 0];
-    y[i] = (double)quads[(q * 4 + i) * 2 + 1];
+    if constexpr (SRC) {
+      double sx = ((double)quads[(q * 4 + i) * 2 + 0] - left) / ratio, sy = ((double)quads[(q * 4 + i) * 2 + 1] - top) / ratio;
+      sx = sx < 0.0 ? 0.0 : (sx > fw ? fw : sx);  // (comparisons, not fmin / fmax: a NaN stays one, as under np.clip)
+      sy = sy < 0.0 ? 0.0 : (sy > fh ? fh : sy);
+      const float qx = known ? (float)sx : 0.f, qy = known ? (float)sy : 0.f;
+      tab.quads_src[(q * 4 + i) * 2 + 0] = qx;
+      tab.quads_src[(q * 4 + i) * 2 + 1] = qy;
+      x[i] = (double)qx;
+      y[i] = (double)qy;
+    } else {
+      x[i] = (double)quads[(q * 4 + i) * 2 + 0];
+      y[i] = (double)quads[(q * 4 + i) * 2 + 1];
+    }
   }
   // unknowns c0..c7 of  X = (c0 u + c1 v + c2) / (c6 u + c7 v + 1),  Y = (c3 u + c4 v + c5) / (...)
   double A[8][9];
@@ -85,10 +127,15 @@ __device__ __forceinline__ int sat_short_rint(float v) {
 // leave as three dwords; PX = 1 otherwise).  Taps whose 2 x 2 window lies inside the frame are fetched as three aligned
 // dwords per row (the six bytes of two neighbouring pixels start at any byte offset) instead of six byte loads; windows
 // that touch the border take the byte path with constant border 0.  The arithmetic per pixel is the same in every path.
-template <int PX>
+//
+// SRC (mtgv_warp_quads_src): the frame's base, fh and fw are read per quad from `tab` instead of per launch.  Such a frame
+// starts at any byte (its offset is a sum of h * w * 3), so there the 12-byte window is aligned on the absolute address and
+// must also begin inside the frame; it always ends inside it (the guard bounds the second row's window by the frame's own
+// end).  A frame index outside [0, nf) or a frame without pixels is 0 x 0: every tap is border.
+template <int PX, bool SRC>
 __global__ __launch_bounds__(256) void warp_kernel(const uint8_t* __restrict__ frames, int fh, int fw,
                                                   const double* __restrict__ coef, const int* __restrict__ frame_idx, int nq,
-                                                  int out_h, int out_w, uint8_t* __restrict__ out) {
+                                                  int out_h, int out_w, uint8_t* __restrict__ out, const SourceTables<SRC> tab) {
   const long gidx = (long)blockIdx.x * 256 + threadIdx.x;
   const long idx = gidx * PX;  // first output pixel of this thread
   const long total = (long)nq * out_h * out_w;
@@ -98,7 +145,14 @@ __global__ __launch_bounds__(256) void warp_kernel(const uint8_t* __restrict__ f
   const int y = (int)(t % out_h);
   const int q = (int)(t / out_h);
   const double* c = coef + (long)q * 9;
-  const uint8_t* F = frames + (long)frame_idx[q] * fh * fw * 3;
+  const uint8_t* F;
+  if constexpr (SRC) {
+    const int f = frame_idx[q];
+    F = frames, fh = fw = 0;
+    if (f >= 0 && f < tab.nf && tab.hw[f * 2] > 0 && tab.hw[f * 2 + 1] > 0) F = frames + tab.offsets[f], fh = tab.hw[f * 2], fw = tab.hw[f * 2 + 1];
+  } else {
+    F = frames + (long)frame_idx[q] * fh * fw * 3;
+  }
   const long frame_px = (long)fh * fw;
   uint32_t pix[PX];  // b | g << 8 | r << 16 in memory order: three result bytes per pixel
 #pragma unroll
@@ -126,14 +180,17 @@ __global__ __launch_bounds__(256) void warp_kernel(const uint8_t* __restrict__ f
 
     int acc[3] = {0, 0, 0};
     const long p00 = (long)sy * fw + sx;  // pixel index of the top-left tap
-    if (sx >= 0 && sy >= 0 && sx + 1 < fw && sy + 1 < fh && p00 + fw + 4 <= frame_px) {
+    bool fast = sx >= 0 && sy >= 0 && sx + 1 < fw && sy + 1 < fh && p00 + fw + 4 <= frame_px;
+    if constexpr (SRC) fast = fast && p00 * 3 >= (long)(reinterpret_cast<uintptr_t>(F + p00 * 3) & 3);
+    if (fast) {
       // both rows: bytes [3 p, 3 p + 6) out of the aligned 12-byte window that starts at (3 p) & ~3
 #pragma unroll
       for (int row = 0; row < 2; ++row) {
         const long B = (p00 + (long)row * fw) * 3;
-        const uint32_t* wp = reinterpret_cast<const uint32_t*>(F + (B & ~3L));
+        const long Bw = SRC ? (long)reinterpret_cast<uintptr_t>(F + B) : B;  // what the window is aligned on
+        const uint32_t* wp = reinterpret_cast<const uint32_t*>(F + (B - (Bw & 3)));
         const uint32_t d0 = wp[0], d1 = wp[1], d2 = wp[2];
-        const int sh = (int)(B & 3) * 8;
+        const int sh = (int)(Bw & 3) * 8;
         const uint64_t lo = ((uint64_t)d1 << 32) | d0, hi = ((uint64_t)d2 << 32) | d1;
         const uint32_t b03 = (uint32_t)(lo >> sh), b47 = (uint32_t)(hi >> sh);  // bytes 0..3 and 4..7 from B
         const int wl = wq[row * 2], wr = wq[row * 2 + 1];
@@ -236,16 +293,45 @@ MTGV_API int mtgv_warp_quads(const uint8_t* frames_dev, int32_t nf, int32_t fh, 
                "warp: workspace too small");
     hipStream_t s = (hipStream_t)stream;
     double* coef = (double*)workspace_dev;
-    hipLaunchKernelGGL(warp_coeffs_kernel, dim3((nq + 63) / 64), dim3(64), 0, s, quads_dev, nq, out_h, out_w, expand_ratio, coef);
+    hipLaunchKernelGGL(warp_coeffs_kernel<false>, dim3((nq + 63) / 64), dim3(64), 0, s, quads_dev, nq, out_h, out_w, expand_ratio, coef,
+                       SourceTables<false>{});
     HIP_OK(hipGetLastError());
     const long total = (long)nq * out_h * out_w;
     // four pixels per thread need rows of whole groups and dword-aligned buffers (frame f starts at f * fh * fw * 3 bytes)
     if (out_w % 4 == 0 && ((uintptr_t)out_dev & 3) == 0 && ((uintptr_t)frames_dev & 3) == 0 && ((long)fh * fw * 3) % 4 == 0)
-      hipLaunchKernelGGL(warp_kernel<4>, dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, s, frames_dev, fh, fw, coef, frame_idx_dev,
-                         nq, out_h, out_w, out_dev);
+      hipLaunchKernelGGL((warp_kernel<4, false>), dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, s, frames_dev, fh, fw, coef,
+                         frame_idx_dev, nq, out_h, out_w, out_dev, SourceTables<false>{});
     else
-      hipLaunchKernelGGL(warp_kernel<1>, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, frames_dev, fh, fw, coef, frame_idx_dev,
-                         nq, out_h, out_w, out_dev);
+      hipLaunchKernelGGL((warp_kernel<1, false>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, frames_dev, fh, fw, coef,
+                         frame_idx_dev, nq, out_h, out_w, out_dev, SourceTables<false>{});
+    HIP_OK(hipGetLastError());
+  });
+}
+
+MTGV_API int mtgv_warp_quads_src(const uint8_t* src_dev, const int64_t* offsets_dev, const int32_t* hw_dev, const int32_t* geo_dev,
+                                 const double* ratio_dev, int32_t nf, const float* quads_dev, const int32_t* frame_idx_dev, int32_t nq,
+                                 int32_t out_h, int32_t out_w, double expand_ratio, uint8_t* out_dev, float* quads_src_dev,
+                                 void* workspace_dev, size_t workspace_bytes, void* stream) {
+  return guarded([&] {
+    MTGV_CHECK(src_dev && offsets_dev && hw_dev && geo_dev && ratio_dev && quads_dev && frame_idx_dev && out_dev && quads_src_dev,
+               ERR_INVALID, "null argument");
+    MTGV_CHECK(nf > 0 && out_h > 0 && out_w > 0 && nq >= 0, ERR_INVALID, "warp from sources: bad geometry");
+    if (nq == 0) return;
+    MTGV_CHECK(workspace_dev != nullptr && workspace_bytes >= (size_t)nq * 9 * sizeof(double), ERR_INVALID,
+               "warp: workspace too small");
+    hipStream_t s = (hipStream_t)stream;
+    double* coef = (double*)workspace_dev;
+    const SourceTables<true> tab{(const long*)offsets_dev, hw_dev, geo_dev, ratio_dev, nf, (const int*)frame_idx_dev, quads_src_dev};
+    hipLaunchKernelGGL(warp_coeffs_kernel<true>, dim3((nq + 63) / 64), dim3(64), 0, s, quads_dev, nq, out_h, out_w, expand_ratio, coef, tab);
+    HIP_OK(hipGetLastError());
+    const long total = (long)nq * out_h * out_w;
+    // four pixels per thread: rows of whole groups and a dword-aligned output; the frames may start at any byte
+    if (out_w % 4 == 0 && ((uintptr_t)out_dev & 3) == 0)
+      hipLaunchKernelGGL((warp_kernel<4, true>), dim3((unsigned)((total / 4 + 255) / 256)), dim3(256), 0, s, src_dev, 0, 0, coef,
+                         (const int*)frame_idx_dev, nq, out_h, out_w, out_dev, tab);
+    else
+      hipLaunchKernelGGL((warp_kernel<1, true>), dim3((unsigned)((total + 255) / 256)), dim3(256), 0, s, src_dev, 0, 0, coef,
+                         (const int*)frame_idx_dev, nq, out_h, out_w, out_dev, tab);
     HIP_OK(hipGetLastError());
   });
 }

@@ -17,7 +17,9 @@ _LAZY = {
     "merge_topk": ("matcher", "merge_topk"),
     "ShardedMatcher": ("dist", "ShardedMatcher"),
     "Pipeline": ("pipeline", "Pipeline"),
+    "SourceFrames": ("pipeline", "SourceFrames"),
     "warp_quads": ("crop", "warp_quads"),
+    "warp_quads_src": ("crop", "warp_quads_src"),
     "DeviceTracker": ("track", "DeviceTracker"),
     "TrackedPipeline": ("track", "TrackedPipeline"),
 }

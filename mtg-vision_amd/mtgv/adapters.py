@@ -302,6 +302,16 @@ class InstanceSeg:
         raise NotImplementedError("debug drawing needs cv2; out of scope for the recognition path (SURVEY.md section 2 row 6)")
 
 
+def to_frame_points(p, ratio: float, left: int, top: int, fh: int, fw: int) -> np.ndarray:
+    """ultralytics' scale_coords + clip_coords: (..., 2) points (x, y) in the pixels of the letterboxed input back to the
+    caller's (fh, fw) frame, float64.  (The batched pipelines do the same on the GPU for `SourceFrames`:
+    mtgv_warp_quads_src, csrc/warp.hip.)"""
+    p = (np.asarray(p, np.float64) - np.asarray([left, top], np.float64)) / float(ratio)
+    p[..., 0] = np.clip(p[..., 0], 0, fw)
+    p[..., 1] = np.clip(p[..., 1], 0, fh)
+    return p
+
+
 class CardSegmenter:
     """`CardSegmenter(model_path)(rgb_im) -> list[InstanceSeg]` (od_export.py:141-160).
 
@@ -386,11 +396,8 @@ class CardSegmenter:
             return detections
         fh, fw = rgb_im.shape[0], rgb_im.shape[1]
 
-        def to_frame(p):  # scale_coords + clip_coords back to the caller's frame
-            p = (np.asarray(p, np.float64) - np.asarray([left, top], np.float64)) / float(ratio)
-            p[..., 0] = np.clip(p[..., 0], 0, fw)
-            p[..., 1] = np.clip(p[..., 1], 0, fh)
-            return p
+        def to_frame(p):
+            return to_frame_points(p, ratio, left, top, fh, fw)
 
         if self.contours == "trace_host":
             masks = binarize_masks(det.mask_logits).cpu().numpy()

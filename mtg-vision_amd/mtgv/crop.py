@@ -45,6 +45,40 @@ def warp_quads(frames: torch.Tensor, quads: torch.Tensor, frame_idx: torch.Tenso
     return out
 
 
+def warp_quads_src(src, quads: torch.Tensor, frame_idx: torch.Tensor, out_size_hw=(192, 128), expand_ratio: float = 0.05,
+                   workspace: torch.Tensor = None):
+    """`warp_quads` from the frames the camera delivered: `src` is a `mtgv.pipeline.SourceFrames` (buf, offsets, hw, geo,
+    ratio: frames of their own sizes back to back and each one's letterbox into the detector's input), quads (nq, 4, 2)
+    float32 are pixels of that input.  -> (crops (nq, out_h, out_w, 3) uint8, quads_src (nq, 4, 2) float32: the corners in
+    the pixels of their own frames, `adapters.to_frame(...).astype(float32)` of each).  One library call (mtgv_warp_quads_src):
+    the mapping rides in the coefficient kernel, the sampling kernel reads every crop from its own frame."""
+    native.require_gpu()
+    buf = src.buf
+    assert buf.is_cuda and buf.dtype == torch.uint8 and buf.ndim == 1 and buf.is_contiguous(), f"{tuple(buf.shape)} {buf.dtype}"
+    nf, nq = int(src.offsets.shape[0]), quads.shape[0]
+    oh, ow = out_size_hw
+    out = torch.empty((nq, oh, ow, 3), dtype=torch.uint8, device=buf.device)
+    quads_src = torch.empty((nq, 4, 2), dtype=torch.float32, device=buf.device)
+    if nq == 0:
+        return out, quads_src
+    quads = quads.to(buf.device, torch.float32).contiguous()
+    frame_idx = frame_idx.to(buf.device, torch.int32).contiguous()
+    assert tuple(quads.shape) == (nq, 4, 2) and tuple(frame_idx.shape) == (nq,)
+    assert src.offsets.dtype == torch.int64 and src.hw.dtype == torch.int32 and src.geo.dtype == torch.int32 and src.ratio.dtype == torch.float64
+    assert tuple(src.hw.shape) == (nf, 2) and tuple(src.geo.shape) == (nf, 4) and tuple(src.ratio.shape) == (nf,)
+    L = native.lib()
+    ws = workspace
+    if ws is None or ws.device != buf.device or ws.numel() * 8 < int(L.mtgv_warp_workspace_bytes(nq)):
+        ws = warp_workspace(nq, buf.device)
+    with torch.cuda.device(buf.device):
+        native.check(
+            L.mtgv_warp_quads_src(native.ptr(buf), native.ptr(src.offsets), native.ptr(src.hw), native.ptr(src.geo), native.ptr(src.ratio), nf,
+                                  native.ptr(quads), native.ptr(frame_idx), nq, oh, ow, float(expand_ratio), native.ptr(out),
+                                  native.ptr(quads_src), native.ptr(ws), ws.numel() * 8, native.stream())
+        )
+    return out, quads_src
+
+
 def select_cards(n_det: torch.Tensor, boxes: torch.Tensor, pad_boxes: torch.Tensor, k: int, want_quads: bool = True):
     """The K cards per frame that go on to the crop stage, in one library kernel: the K best detections of the padded
     detector outputs (n_det (F,), boxes (F, max_det, 4), score-descending) or pad_boxes[k] where a frame has fewer.

@@ -7,6 +7,7 @@ device in one copy per batch and are decoded there:
     dec = JpegDecoder(max_images=32, max_bytes=4 << 20, max_pixels=32 * 640 * 480)
     frames = dec.decode_frames(list_of_jpeg_bytes)          # (n, 640, 640, 3) uint8, letterboxed, on the GPU; input_hw=(480, 640): (n, 480, 640, 3)
     buf, offsets, hw, status = dec.decode(list_of_jpeg_bytes)  # ragged RGB, the layout mtgv_make_cropped takes
+    src = dec.decode_sources(list_of_jpeg_bytes)            # both: mtgv.pipeline.SourceFrames - Pipeline.run(src) crops the cards from the camera's pixels
 
 Supported: baseline / extended sequential Huffman 8-bit (SOF0 / SOF1), greyscale or YCbCr 4:4:4 / 4:2:2 / 4:2:0,
 restart intervals.  The output equals libjpeg-turbo's default decode (Pillow's `Image.open(f).convert("RGB")`).
@@ -214,6 +215,37 @@ class JpegDecoder:
         self.last_status = status
         return out
 
+    def decode_sources(self, datas: Sequence[bytes], size: int = 640, input_hw=None, pad_value: int = 114, out: torch.Tensor = None,
+                       buf: torch.Tensor = None, check: bool = True):
+        """JPEG frames -> `mtgv.pipeline.SourceFrames`: the frames at the camera's resolution (`buf`, `offsets`, `hw`: what
+        `decode` returns) beside the detector input made from them (`frames`: what `decode_frames` returns, byte for byte).
+        One decode into the ragged layout, one letterbox launch for the whole batch whatever the frames' sizes
+        (mtgv_letterbox_ragged_u8).  Hand the result to `Pipeline.run` and the cards are cropped from the camera's pixels.
+        out: the (n, size, size, 3) / (n, in_h, in_w, 3) tensor for the frames; buf: a uint8 tensor of at least sum h * w * 3
+        bytes for the sources (JpegFrames keeps both in its ring)."""
+        from .pipeline import SourceFrames
+
+        infos = self._infos(datas)
+        n = len(datas)
+        hw = np.array([(f.h, f.w) for f in infos], np.int64).reshape(n, 2)
+        nbytes = hw[:, 0] * hw[:, 1] * 3
+        offs = np.zeros(n, np.int64)
+        if n > 1:
+            offs[1:] = np.cumsum(nbytes)[:-1]
+        total = int(nbytes.sum())
+        if buf is None:
+            buf = torch.empty(total, dtype=torch.uint8, device=self.device)
+        assert buf.dtype == torch.uint8 and buf.ndim == 1 and buf.is_contiguous() and buf.numel() >= total and buf.is_cuda, \
+            f"source buffer {tuple(buf.shape)} {buf.dtype} for {total} bytes"
+        buf = buf[:total]
+        status = self._launch(datas, buf, offs, hw[:, 1] * 3) if n else torch.zeros(0, dtype=torch.int32, device=self.device)
+        with torch.cuda.device(self.device):
+            sf = SourceFrames.from_ragged(buf, offs, hw, size, input_hw, pad_value, out)
+        if check:
+            self._raise_on_status(status)
+        self.last_status = status
+        return sf
+
     def __del__(self):
         try:
             if getattr(self, "_h", None) and self._h.value:
@@ -246,9 +278,12 @@ class JpegFrames:
     which the caller reads once the pipeline's outputs are synchronised (reading it earlier would stall the overlap)."""
 
     def __init__(self, jpeg_batches: Sequence[Sequence[bytes]], device, size: int = 640, pad_value: int = 114, depth: int = 3,
-                 decoder: JpegDecoder = None, input_hw=None, progressive: bool = False):
+                 decoder: JpegDecoder = None, input_hw=None, progressive: bool = False, keep_source: bool = False):
         """input_hw = (in_h, in_w): buffers of a rectangular detector's input (JpegDecoder.decode_frames);
-        progressive: the decoder created here also takes progressive frames (a `decoder` passed in is used as given)"""
+        progressive: the decoder created here also takes progressive frames (a `decoder` passed in is used as given);
+        keep_source: the ring also holds every batch's frames at the camera's resolution (JpegDecoder.decode_sources; the
+        buffers are sized here from the largest batch, like the decoder) and a lease has `sources()`, which Pipeline.run /
+        run_many pick up: the cards are cropped from the camera's pixels.  `tensor()` still returns the frames."""
         assert depth >= 2 and len(jpeg_batches) > 0
         self.batches = [list(b) for b in jpeg_batches]
         self.device = torch.device(device)
@@ -256,15 +291,22 @@ class JpegFrames:
         self.input_hw = None if input_hw is None else (int(input_hw[0]), int(input_hw[1]))
         oh, ow = (size, size) if self.input_hw is None else self.input_hw
         n = max(len(b) for b in self.batches)
+        self.keep_source = bool(keep_source)
+        infos = None
+        if decoder is None or self.keep_source:
+            infos = [[jpeg_info(d, progressive or getattr(decoder, "progressive", False)) for d in b] for b in self.batches]
         if decoder is None:
             nbytes = max(sum(len(d) for d in b) for b in self.batches)
-            infos = [[jpeg_info(d, progressive) for d in b] for b in self.batches]
             pix = max(sum(_padded_pixels(f) for f in b) for b in infos)
             scans = max(sum(f.scans for f in b if f.progressive) for b in infos) if progressive else None
             decoder = JpegDecoder(n, nbytes, pix, self.device, progressive=progressive, max_scans=max(scans, 1) if progressive else None)
         self.dec = decoder
         self.s_dec = torch.cuda.Stream(self.device)
         self.bufs = [torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=self.device) for _ in range(depth)]
+        self.src_bufs = None
+        if self.keep_source:
+            src_bytes = max(sum(f.h * f.w * 3 for f in b) for b in infos)
+            self.src_bufs = [torch.empty(max(src_bytes, 1), dtype=torch.uint8, device=self.device) for _ in range(depth)]
         self.decoded = [torch.cuda.Event() for _ in range(depth)]
         self.released = [None] * depth
         self._issued = 0
@@ -282,6 +324,21 @@ class JpegFrames:
             ev.record(torch.cuda.current_stream(self.src.device))
             self.src.released[self.slot] = ev
 
+    class _SourceLease(_Lease):
+        """a lease of JpegFrames(keep_source=True): `sources()` is the batch's SourceFrames (its `frames` are `tensor()`),
+        `done()` releases the frame buffer and the source buffer together"""
+
+        def __init__(self, src, slot, n, status, sf):
+            super().__init__(src, slot, n, status)
+            self._sf = sf
+
+        def sources(self):
+            cur = torch.cuda.current_stream(self.src.device)
+            cur.wait_event(self.src.decoded[self.slot])
+            for t in (self._sf.offsets, self._sf.hw, self._sf.geo, self._sf.ratio):  # allocated on the decode stream
+                t.record_stream(cur)
+            return self._sf
+
     def _issue(self, batch_index: int):
         j = self._issued % self.depth
         datas = self.batches[batch_index % len(self.batches)]
@@ -290,10 +347,14 @@ class JpegFrames:
             if self.released[j] is not None:
                 self.s_dec.wait_event(self.released[j])  # the batch that used this buffer has been de-warped
             n = len(datas)
-            self.dec.decode_frames(datas, self.size, self.pad_value, out=self.bufs[j][:n], check=False, input_hw=self.input_hw)
+            sf = None
+            if self.keep_source:
+                sf = self.dec.decode_sources(datas, self.size, self.input_hw, self.pad_value, out=self.bufs[j][:n], buf=self.src_bufs[j], check=False)
+            else:
+                self.dec.decode_frames(datas, self.size, self.pad_value, out=self.bufs[j][:n], check=False, input_hw=self.input_hw)
             status = self.dec.last_status
             self.decoded[j].record(self.s_dec)
-        return JpegFrames._Lease(self, j, n, status)
+        return JpegFrames._SourceLease(self, j, n, status, sf) if self.keep_source else JpegFrames._Lease(self, j, n, status)
 
     def leases(self, n: int):
         """n leases of batches 0, 1, ... (cyclically), decodes one to two batches ahead of their consumer (HostFrames.leases)"""

@@ -8,13 +8,15 @@ batch of frames goes through each stage once; every stage's arithmetic is in lib
 from __future__ import annotations
 
 import os
+from dataclasses import dataclass
 from typing import Callable, Optional
 
+import numpy as np
 import torch
 
-from . import native
+from . import crop, native
 from .crop import mask_quads_from_logits, obb_cards, select_cards, warp_quads, warp_workspace
-from .detector import Detector
+from .detector import Detector, fit_geometry
 from .encoder import Encoder
 from .matcher import Matcher
 
@@ -85,9 +87,86 @@ class HostFrames:
             yield ahead.pop(0)
 
 
+def _host_i64(a, shape) -> np.ndarray:
+    a = a.cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    return np.ascontiguousarray(a, np.int64).reshape(shape)
+
+
+@dataclass
+class SourceFrames:
+    """A batch of frames as the camera delivered them, beside the detector input made from them.  Handed to `Pipeline.run` /
+    `run_many` / `TrackedPipeline.run` in place of the frame tensor, detection runs on `frames` and every card is cropped
+    from its own source frame at that frame's resolution, as the reference crops from the caller's frame
+    (mtgvision/od_export.py:95-111, server.py:173) - not from the letterboxed copy.
+
+    buf (bytes,) uint8: the frames back to back, HWC RGB; offsets (n,) int64 byte offset of each; hw (n, 2) int32 height,
+    width (the ragged layout of `JpegDecoder.decode` and mtgv_make_cropped); geo (n, 4) int32 = nh, nw, top, left and ratio
+    (n,) float64: each frame's `fit_geometry` into the detector's input; frames (n, in_h, in_w, 3) uint8: that input.  All
+    on the device."""
+
+    buf: torch.Tensor
+    offsets: torch.Tensor
+    hw: torch.Tensor
+    geo: torch.Tensor
+    ratio: torch.Tensor
+    frames: torch.Tensor
+
+    @staticmethod
+    def geometry(hw, input_hw):
+        """host side: (geo (n, 4) int32 = nh, nw, top, left, ratio (n,) float64) of (n, 2) frame sizes into input_hw,
+        `fit_geometry` per frame"""
+        g = [fit_geometry(int(h), int(w), int(input_hw[0]), int(input_hw[1])) for h, w in np.asarray(hw).reshape(-1, 2)]
+        geo = np.array([t[1:] for t in g], np.int32).reshape(len(g), 4)
+        return geo, np.array([t[0] for t in g], np.float64)
+
+    @classmethod
+    def from_ragged(cls, buf: torch.Tensor, offsets, hw, size: int = 640, input_hw=None, pad_value: int = 114, out: torch.Tensor = None):
+        """frames of their own sizes in one buffer (offsets, hw: host sequences or arrays; device tensors are read back) ->
+        SourceFrames whose `frames` are all of them letterboxed into (size, size) or input_hw in one launch
+        (mtgv_letterbox_ragged_u8; `out`: the tensor to write them to)."""
+        native.require_gpu()
+        assert buf.is_cuda and buf.dtype == torch.uint8 and buf.ndim == 1 and buf.is_contiguous(), f"{tuple(buf.shape)} {buf.dtype}"
+        hw_h = _host_i64(hw, (-1, 2))
+        n = hw_h.shape[0]
+        off_h = _host_i64(offsets, (n,))
+        oh, ow = (int(size), int(size)) if input_hw is None else (int(input_hw[0]), int(input_hw[1]))
+        # the kernels trust these tables: every frame has pixels and lies inside the buffer
+        assert n == 0 or ((hw_h > 0).all() and (off_h >= 0).all() and (off_h + hw_h[:, 0] * hw_h[:, 1] * 3 <= buf.numel()).all()), \
+            f"frames (offsets {off_h.tolist()}, sizes {hw_h.tolist()}) outside a buffer of {buf.numel()} bytes"
+        geo, ratio = cls.geometry(hw_h, (oh, ow))
+        dev = buf.device
+        if out is None:
+            out = torch.empty((n, oh, ow, 3), dtype=torch.uint8, device=dev)
+        assert tuple(out.shape) == (n, oh, ow, 3) and out.dtype == torch.uint8 and out.is_contiguous() and out.device == dev
+        sf = cls(buf, torch.from_numpy(off_h).to(dev), torch.from_numpy(hw_h.astype(np.int32)).to(dev), torch.from_numpy(geo).to(dev),
+                 torch.from_numpy(ratio).to(dev), out)
+        if n and out.data_ptr() != buf.data_ptr():  # (from_frames: frames of the input's own size are the input)
+            with torch.cuda.device(dev):
+                native.check(native.lib().mtgv_letterbox_ragged_u8(native.ptr(buf), native.ptr(sf.offsets), native.ptr(sf.hw), native.ptr(sf.geo), n,
+                                                                   native.ptr(out), oh, ow, int(pad_value), native.stream()))
+        return sf
+
+    @classmethod
+    def from_frames(cls, frames: torch.Tensor, size: int = 640, input_hw=None, pad_value: int = 114):
+        """(n, h, w, 3) uint8 same-sized frames on the device: the buffer is the tensor itself (offsets i * h * w * 3, no
+        copy).  Frames that already have the detector's input size are that input, without a launch; others are letterboxed
+        as in from_ragged."""
+        assert frames.is_cuda and frames.dtype == torch.uint8 and frames.ndim == 4 and frames.shape[-1] == 3 and frames.is_contiguous(), \
+            f"{tuple(frames.shape)} {frames.dtype}"
+        n, h, w = int(frames.shape[0]), int(frames.shape[1]), int(frames.shape[2])
+        oh, ow = (int(size), int(size)) if input_hw is None else (int(input_hw[0]), int(input_hw[1]))
+        return cls.from_ragged(frames.view(-1), np.arange(n, dtype=np.int64) * (h * w * 3), [(h, w)] * n, input_hw=(oh, ow), pad_value=pad_value,
+                               out=frames if (h, w) == (oh, ow) else None)
+
+
 def _frames_of(item):
-    """(tensor, lease or None) of a batch handed to run / run_many: a device tensor, or a lease of HostFrames"""
-    return (item.tensor(), item) if hasattr(item, "tensor") and hasattr(item, "done") else (item, None)
+    """(tensor, lease or None, SourceFrames or None) of a batch handed to run / run_many: a device tensor, a SourceFrames,
+    or a lease of HostFrames / JpegFrames (one that has `sources()` - JpegFrames(keep_source=True) - brings its SourceFrames)"""
+    if isinstance(item, SourceFrames):
+        return item.frames, None, item
+    if hasattr(item, "tensor") and hasattr(item, "done"):
+        return item.tensor(), item, (item.sources() if hasattr(item, "sources") else None)
+    return item, None, None
 
 
 class Pipeline:
@@ -140,8 +219,8 @@ class Pipeline:
         self._pad = pad.repeat(reps, 1)[: self.K].to(detector.device).contiguous()
         self._warp_ws = None
 
-    def _embed_match(self, frames_u8: torch.Tensor, det, lease=None):
-        boxes, crops = self._crop(frames_u8, det, lease)
+    def _embed_match(self, frames_u8: torch.Tensor, det, lease=None, src=None):
+        boxes, crops = self._crop(frames_u8, det, lease, src)
         return self._embed(det, boxes, crops, *self._thumbnails(crops))
 
     def _thumbnails(self, crops):
@@ -150,13 +229,14 @@ class Pipeline:
             return None, None
         return self._jpeg.encode_device(crops, self.thumbnail_quality, 420)
 
-    def _crop(self, frames_u8: torch.Tensor, det, lease=None):
-        """detections -> (boxes (F, K, 4), crops (F * K, h, w, 3) uint8): the K best boxes or mask quadrilaterals, de-warped"""
+    def _crop(self, frames_u8: torch.Tensor, det, lease=None, src=None):
+        """detections -> (boxes (F, K, 4), crops (F * K, h, w, 3) uint8): the K best boxes or mask quadrilaterals, de-warped
+        from frames_u8 or, with `src` (SourceFrames), from the source frames"""
         F, K = frames_u8.shape[0], self.K
         if self.quad_source == "obb":
             quads, sel, frame_idx, state = obb_cards(det["n_det"], det["rboxes"], det["conf"], det["cls"], self._pad, K, 0, 1, 2)
             det["quads"], det["card_state"] = quads.view(F, K, 4, 2), state.view(F, K)
-            return self._warp(frames_u8, sel.view(F, K, 4), quads, frame_idx, lease)
+            return self._warp(frames_u8, sel.view(F, K, 4), quads, frame_idx, lease, src, det)
         # the K highest-confidence detections per frame (NMS output is score-descending), pad boxes where a frame has
         # fewer; every step of the glue is a library kernel (no PyTorch arithmetic on the streams of the step)
         want_mask = self.quad_source == "mask"
@@ -168,13 +248,19 @@ class Pipeline:
             ml = det["mask_logits"]
             assert ml.shape[1] == K, f"mask rows {ml.shape[1]} != cards per frame {K}"
             quads, _ = mask_quads_from_logits(ml.view(F * K, *ml.shape[-2:]), sel)
-        return self._warp(frames_u8, sel.view(F, K, 4), quads, frame_idx, lease)
+        return self._warp(frames_u8, sel.view(F, K, 4), quads, frame_idx, lease, src, det)
 
-    def _warp(self, frames_u8, boxes, quads, frame_idx, lease):
+    def _warp(self, frames_u8, boxes, quads, frame_idx, lease, src=None, det=None):
+        """the one place every quad_source's quads are de-warped.  With `src` the quads (pixels of the detector's input, like
+        the boxes) are mapped into their source frames and the crops come from there; det gains quads_src (F, K, 4, 2)."""
         F, K = frames_u8.shape[0], self.K
         if self._warp_ws is None or self._warp_ws.numel() < 9 * F * K:
             self._warp_ws = warp_workspace(F * K, frames_u8.device)  # once per pipeline (the largest batch seen so far)
-        crops = warp_quads(frames_u8, quads, frame_idx, self.encoder.cfg.image_hw, 0.05, self._warp_ws)
+        if src is None:
+            crops = warp_quads(frames_u8, quads, frame_idx, self.encoder.cfg.image_hw, 0.05, self._warp_ws)
+        else:
+            crops, quads_src = crop.warp_quads_src(src, quads, frame_idx, self.encoder.cfg.image_hw, 0.05, self._warp_ws)
+            det["quads_src"] = quads_src.view(F, K, 4, 2)
         if lease is not None:
             lease.done()  # the de-warp is the last reader of the frames
         return boxes, crops
@@ -204,6 +290,8 @@ class Pipeline:
             out["thumbs"], out["thumb_offsets"] = thumbs, thumb_offsets
         if "quads" in det:  # quad_source "obb"
             out["quads"], out["card_state"] = det["quads"], det["card_state"]
+        if "quads_src" in det:  # the batch came as SourceFrames
+            out["quads_src"] = det["quads_src"]
         return out
 
     @staticmethod
@@ -279,33 +367,33 @@ class Pipeline:
             nxt = None
             if item is not None:
                 with torch.cuda.stream(self._s_det):
-                    frames, lease = _frames_of(item)
+                    frames, lease, src = _frames_of(item)
                     det = self.detector.forward(frames, flip_rgb, mask_rows=self.K)
                     # the crop stage (card selection, mask -> quadrilateral, de-warp: latency-bound kernels of a few hundred
                     # workgroups) belongs to the detect stream: beside the other stream's GEMMs it costs next to nothing, in
                     # front of the encoder it would leave most of the GPU idle (MTGV_CROP_STAGE=enc: the round-3 split)
-                    cropped = self._crop(frames, det, lease) if crop_on_det else None
+                    cropped = self._crop(frames, det, lease, src) if crop_on_det else None
                     ev = torch.cuda.Event()
                     ev.record(self._s_det)
                     if cropped is not None:  # behind the event: this batch's embed does not wait for its thumbnails
                         cropped = (*cropped, *self._thumbnails(cropped[1]))
-                nxt = (frames, det, ev, lease, cropped)
+                nxt = (frames, det, ev, lease, cropped, src)
             if pending is not None:
-                pf, pdet, pev, please, pcrop = pending
+                pf, pdet, pev, please, pcrop, psrc = pending
                 with torch.cuda.stream(self._s_enc):
                     self._s_enc.wait_event(pev)
                     for t in list(pdet.values()) + list(pcrop or ()):
                         if t is not None:
                             t.record_stream(self._s_enc)
                     outs.append(self._embed(pdet, *pcrop, match_stream=s_match) if pcrop is not None
-                                else self._embed_match(pf, pdet, please))
+                                else self._embed_match(pf, pdet, please, psrc))
             pending = nxt
         cur.wait_stream(self._s_det)
         cur.wait_stream(self._s_enc)
         if s_match is not None:
             cur.wait_stream(s_match)
         for o in outs:
-            for t in (o["ids"], o["scores"], o["z"], o["crops"], o["boxes"], o.get("thumbs"), o.get("thumb_offsets")):
+            for t in (o["ids"], o["scores"], o["z"], o["crops"], o["boxes"], o.get("thumbs"), o.get("thumb_offsets"), o.get("quads_src")):
                 if t is not None:
                     t.record_stream(cur)
         return outs
@@ -313,7 +401,11 @@ class Pipeline:
     def run(self, frames_u8: torch.Tensor, flip_rgb: bool = True):
         """frames (F, in_h, in_w, 3) uint8 on the GPU (640 x 640 unless the detector's cfg.input_hw names a rectangle; the mask
         quads, the OBB quads and the de-warp work in the pixels of that frame) -> dict with ids (F, K, top_k) int64, scores, n_det (F,)
-        and the intermediate crops / embeddings (device tensors)."""
-        frames_u8, lease = _frames_of(frames_u8)
+        and the intermediate crops / embeddings (device tensors).
+
+        A `SourceFrames` (or a lease that has `sources()`) instead: detection runs on its `frames`, the quads go back into
+        the camera's frames and the cards are cropped from those at their own resolution; the dict gains quads_src
+        (F, K, 4, 2), the corners in camera pixels.  boxes (and an OBB detector's quads) stay pixels of the detector's input."""
+        frames_u8, lease, src = _frames_of(frames_u8)
         det = self.detector.forward(frames_u8, flip_rgb, mask_rows=self.K)
-        return self._embed_match(frames_u8, det, lease)
+        return self._embed_match(frames_u8, det, lease, src)

@@ -204,21 +204,22 @@ class TrackedPipeline:
                                      **policy)
         self.last_z = None  # the embeddings committed by the last step (n_due, dim), None when nothing was due
 
-    def _crop(self, frames_u8, det):
-        """Pipeline._crop, keeping the quads it hands to the de-warp (Pipeline returns them only for "obb")"""
+    def _crop(self, frames_u8, det, src=None):
+        """Pipeline._crop, keeping the quads it hands to the de-warp (Pipeline returns them only for "obb"); with `src`
+        (SourceFrames) the quads the de-warp mapped into the camera's frames"""
         p, seen = self.pipeline, {}
         warp = p._warp
 
-        def keep(frames, boxes, quads, frame_idx, lease):
+        def keep(frames, boxes, quads, *rest):
             seen["quads"] = quads
-            return warp(frames, boxes, quads, frame_idx, lease)
+            return warp(frames, boxes, quads, *rest)
 
         p._warp = keep  # shadows the method for this call
         try:
-            boxes, crops = p._crop(frames_u8, det, None)
+            boxes, crops = p._crop(frames_u8, det, None) if src is None else p._crop(frames_u8, det, None, src)
         finally:
             del p._warp
-        return boxes, crops, seen["quads"]
+        return boxes, crops, (seen["quads"] if src is None else det["quads_src"])
 
     def run(self, frames_u8: torch.Tensor, stream_of_frame: Sequence[int], now, flip_rgb: bool = True) -> dict:
         """frames (F, in_h, in_w, 3) uint8 on the GPU, frame f from camera stream_of_frame[f] (distinct) at now[f] seconds
@@ -226,14 +227,21 @@ class TrackedPipeline:
         (F, K, top_k): each slot's track's kept matches (-1 / -inf without a track), n_due (int), due_idx (F * K,) int32,
         n_det, boxes, crops, det, quads (F, K, 4, 2) (+ card_state, thumbs, thumb_offsets where Pipeline.run has them).
 
+        frames_u8 may be a `mtgv.pipeline.SourceFrames`: the cards are cropped from the camera's frames and the tracker is
+        updated with the quads in camera pixels, the unit of the reference's norfair thresholds (server.py:100-106); the
+        returned quads (and quads_src) are those.
+
         One synchronisation per step: the 4-byte read of n_due, which the encoder and the matcher need on the host as
         their batch size.  All crops (and thumbnails) are produced as in Pipeline.run; only the due ones are embedded."""
         p, trk = self.pipeline, self.tracker
         sof = check_streams(stream_of_frame, trk.streams)
+        src = frames_u8 if hasattr(frames_u8, "frames") and hasattr(frames_u8, "geo") else None  # a SourceFrames
+        if src is not None:
+            frames_u8 = src.frames
         F, K = frames_u8.shape[0], p.K
         assert sof.size == F, f"{sof.size} streams named for {F} frames"
         det = p.detector.forward(frames_u8, flip_rgb, mask_rows=K)
-        boxes, crops, quads = self._crop(frames_u8, det)
+        boxes, crops, quads = self._crop(frames_u8, det, src)
         thumbs, thumb_offsets = p._thumbnails(crops)
         if p.quad_source == "obb":
             track_ids, due_idx, n_due_dev = trk.update(quads, sof, now, state=det["card_state"])
@@ -255,4 +263,6 @@ class TrackedPipeline:
             out["thumbs"], out["thumb_offsets"] = thumbs, thumb_offsets
         if "card_state" in det:
             out["card_state"] = det["card_state"]
+        if src is not None:
+            out["quads_src"] = det["quads_src"]
         return out
