@@ -2,8 +2,9 @@
 // filter state in registers, the frame's detections in LDS, the greedy association as at most K rounds of a wave-wide
 // lexicographic minimum over (distance, birth, detection index).  A second, single-workgroup launch compacts the due slots in
 // ascending order.  The wide form (MTGV_TRACKER_WIDE: up to 256 slots, 64 detections) is a second update kernel with up to
-// four waves per workgroup; the one-wave kernel is what a handle of mtgv_tracker_create launches.  Everything the host tracker computes in fp64 is computed here in fp64 with the same operations in the
-// same order: this translation unit must not contract a * b + c into an FMA.
+// four waves per workgroup; the one-wave kernel is what a handle of mtgv_tracker_create launches.  What a track does on its
+// own (Slot and the slot_* pieces) is written once for both.  Everything the host tracker computes in fp64 is computed here
+// in fp64 with the same operations in the same order: this translation unit must not contract a * b + c into an FMA.
 #include "track.h"
 
 #include <math.h>
@@ -40,82 +41,193 @@ struct State {
 // _KalmanTrack's constants (mtgv/tracker.py): norfair's OptimizedKalmanFilter defaults
 constexpr double KAL_R = 4.0, KAL_Q = 0.1, KAL_POS_VAR = 10.0, KAL_VEL_VAR = 1.0;
 
-__global__ __launch_bounds__(64) void track_update_kernel(State st, Params p, FrameArgs fr, int f0, const float* __restrict__ quads,
-                                                          const int32_t* __restrict__ n_det, const int32_t* __restrict__ state,
-                                                          int32_t* __restrict__ track_id, int32_t* __restrict__ slot_of,
-                                                          int32_t* __restrict__ due_flag) {
-  __shared__ double det[TRACK_MAX_CARDS][8];
-  __shared__ int det_k[TRACK_MAX_CARDS];
-  __shared__ int o_id[TRACK_MAX_CARDS], o_slot[TRACK_MAX_CARDS], o_due[TRACK_MAX_CARDS];
-  const int lane = threadIdx.x;
-  const int f = f0 + blockIdx.x, s = fr.stream[blockIdx.x];
-  const double now = fr.now[blockIdx.x];
-  const int T = p.T, K = p.K;
+// ---- what both update kernels share: the frame's detection list and everything a track does on its own.  No piece holds a
+// barrier or reads another thread's registers; what crosses a wave stays in the kernels.
 
-  // the frame's detection list: the valid slots in ascending k
+// a frame in LDS: its detections (the valid slots in ascending k, as fp64) and what the step reports per slot k
+template <int KM>
+struct Dets {
+  alignas(16) double det[KM][8];  // (16: a corner pair per LDS access, as a __shared__ array of its own has)
+  int det_k[KM];
+  int o_id[KM], o_slot[KM], o_due[KM];
+};
+
+// called by one whole wave (K <= 64: the list fits its ballot) -> the number of detections; the caller's barrier publishes it
+template <int KM>
+__device__ __forceinline__ int stage_detections(Dets<KM>& D, int lane, int f, int K, const float* __restrict__ quads,
+                                                const int32_t* __restrict__ n_det, const int32_t* __restrict__ state) {
   bool valid = lane < K;
   if (valid && n_det != nullptr) valid = lane < min(n_det[f], K);
   if (valid && state != nullptr) valid = state[(size_t)f * K + lane] > 0;
   const unsigned long long vm = __ballot(valid);
-  const int nd = __popcll(vm);
-  if (lane < TRACK_MAX_CARDS) o_id[lane] = 0, o_slot[lane] = -1, o_due[lane] = 0;
+  if (lane < KM) D.o_id[lane] = 0, D.o_slot[lane] = -1, D.o_due[lane] = 0;
   if (valid) {
     const int di = __popcll(vm & ((1ull << lane) - 1ull));
-    det_k[di] = lane;
+    D.det_k[di] = lane;
     const float* q = quads + ((size_t)f * K + lane) * 8;
 #pragma unroll
-    for (int j = 0; j < 8; ++j) det[di][j] = (double)q[j];
+    for (int j = 0; j < 8; ++j) D.det[di][j] = (double)q[j];
   }
+  return __popcll(vm);
+}
+
+template <int KM>
+__device__ __forceinline__ void write_report(const Dets<KM>& D, int f, int K, int t, int32_t* __restrict__ track_id, int32_t* __restrict__ slot_of,
+                                             int32_t* __restrict__ due_flag) {
+  if (t < K) {
+    const size_t o = (size_t)f * K + t;
+    track_id[o] = D.o_id[t], slot_of[o] = D.o_slot[t], due_flag[o] = D.o_due[t];
+  }
+}
+
+// mean corner distance of detection q to a track's predicted corners: the host's np.linalg.norm(..., axis=1).mean()
+__device__ __forceinline__ double track_distance(const double* q, const double (&pos)[8]) {
+  double sum = 0.0;
+#pragma unroll
+  for (int c = 0; c < 4; ++c) {
+    const double dx = q[2 * c] - pos[2 * c], dy = q[2 * c + 1] - pos[2 * c + 1];
+    const double r = __dsqrt_rn(dx * dx + dy * dy);
+    sum = c == 0 ? r : sum + r;
+  }
+  return sum / 4.0;
+}
+
+// track slot t of stream s in its thread's registers
+struct Slot {
+  int live = 0, hit = 0, init = 0, id = 0, birth = 0, has_z = 0;
+  int mdi = -1;        // detection the track took in this frame
+  bool fresh = false;  // created in this frame
+  double last_t = 0.0;
+  double pos[8] = {}, vel[8] = {}, pp[8] = {}, pv[8] = {}, vv[8] = {};
+};
+
+__device__ __forceinline__ Slot slot_load(const State& st, int s, int T, int t, bool own) {
+  const int32_t* I = st.ints + (size_t)s * TRACK_INTS * T;
+  const double* Kal = st.kal + (size_t)s * TRACK_KAL * T;
+  Slot a;
+  if (own) {
+    a.live = I[0 * T + t], a.hit = I[1 * T + t], a.init = I[2 * T + t], a.id = I[3 * T + t], a.birth = I[4 * T + t];
+    a.has_z = I[5 * T + t];
+    a.last_t = st.last_t[(size_t)s * T + t];
+  }
+  if (a.live) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      a.pos[j] = Kal[(0 + j) * T + t], a.vel[j] = Kal[(8 + j) * T + t], a.pp[j] = Kal[(16 + j) * T + t];
+      a.pv[j] = Kal[(24 + j) * T + t], a.vv[j] = Kal[(32 + j) * T + t];
+    }
+  }
+  return a;
+}
+
+// the slot back to memory; a track created in this frame starts without kept matches
+__device__ __forceinline__ void slot_store(const State& st, const Slot& a, int s, int T, int t, bool own, int top_k) {
+  if (!own) return;
+  int32_t* I = st.ints + (size_t)s * TRACK_INTS * T;
+  double* Kal = st.kal + (size_t)s * TRACK_KAL * T;
+  I[0 * T + t] = a.live, I[1 * T + t] = a.hit, I[2 * T + t] = a.init, I[3 * T + t] = a.id, I[4 * T + t] = a.birth;
+  I[5 * T + t] = a.has_z;
+  st.last_t[(size_t)s * T + t] = a.last_t;
+  if (a.live) {
+#pragma unroll
+    for (int j = 0; j < 8; ++j) {
+      Kal[(0 + j) * T + t] = a.pos[j], Kal[(8 + j) * T + t] = a.vel[j], Kal[(16 + j) * T + t] = a.pp[j];
+      Kal[(24 + j) * T + t] = a.pv[j], Kal[(32 + j) * T + t] = a.vv[j];
+    }
+  }
+  if (a.fresh) {
+    for (int k = 0; k < top_k; ++k) {
+      st.m_ids[((size_t)s * T + t) * top_k + k] = -1;
+      st.m_scores[((size_t)s * T + t) * top_k + k] = -INFINITY;
+    }
+  }
+}
+
+// 1. drop, 2. age and predict
+__device__ __forceinline__ void slot_age(Slot& a) {
+  if (a.live && a.hit < 0) a.live = 0, a.id = 0;
+  if (a.live) {
+    a.hit -= 1;
+#pragma unroll
+    for (int j = 0; j < 8; ++j) a.pos[j] = a.pos[j] + a.vel[j];
+  }
+}
+
+// whether a match in this frame takes the track out of initialisation, which costs the stream an id
+__device__ __forceinline__ int slot_gets_id(const Slot& a, const Params& p) { return (a.init && min(a.hit + 2 * p.period, p.hmax) > p.delay) ? 1 : 0; }
+
+// the track takes detection di = z: hit counter, the id on leaving initialisation, _KalmanTrack.kalman_update -> slot_gets_id
+__device__ __forceinline__ int slot_take(Slot& a, const Params& p, const double* z, int di, int next_id) {
+  const int gets_id = slot_gets_id(a, p);
+  a.mdi = di;
+  a.hit = min(a.hit + 2 * p.period, p.hmax);
+  if (gets_id) a.init = 0, a.id = next_id, a.has_z = 0;
+#pragma unroll
+  for (int j = 0; j < 8; ++j) {
+    const double e = z[j] - a.pos[j];
+    const double sv = a.pp[j] + 2.0 * a.pv[j] + a.vv[j] + KAL_Q + KAL_R;
+    const double k0 = 1.0 - KAL_R / sv, k1 = (a.pv[j] + a.vv[j]) / sv;
+    a.pos[j] = a.pos[j] + k0 * e;
+    a.vel[j] = a.vel[j] + k1 * e;
+    const double nvv = a.vv[j] + KAL_Q - k1 * k1 * sv;
+    a.pp[j] = k0 * KAL_R, a.pv[j] = k1 * KAL_R, a.vv[j] = nvv;
+  }
+  return gets_id;
+}
+
+// a track that is born initialised takes its id at creation
+__device__ __forceinline__ bool spawn_initialising(const Params& p) { return p.period <= p.delay; }
+
+// a new track in this (free) slot from the unmatched detection di = z
+__device__ __forceinline__ void slot_spawn(Slot& a, const Params& p, const double* z, int di, int next_id, int next_birth) {
+  const bool new_init = spawn_initialising(p);
+#pragma unroll
+  for (int j = 0; j < 8; ++j) a.pos[j] = z[j], a.vel[j] = 0.0, a.pp[j] = KAL_POS_VAR, a.pv[j] = 0.0, a.vv[j] = KAL_VEL_VAR;
+  a.live = 1, a.hit = p.period, a.init = new_init ? 1 : 0, a.id = new_init ? 0 : next_id, a.birth = next_birth;
+  a.has_z = 0, a.last_t = 0.0, a.mdi = di, a.fresh = true;
+}
+
+// 5. report and gate
+template <int KM>
+__device__ __forceinline__ void slot_report(Slot& a, const Params& p, double now, Dets<KM>& D, int s, int T, int t) {
+  const bool rep = a.live && a.id > 0 && a.mdi >= 0 && a.hit >= 0;
+  const bool due = rep && (!a.has_z || now - a.last_t > p.wait);
+  if (due) a.last_t = now;
+  if (rep) {
+    const int k = D.det_k[a.mdi];
+    D.o_id[k] = a.id, D.o_slot[k] = s * T + t, D.o_due[k] = due ? 1 : 0;
+  }
+}
+
+__global__ __launch_bounds__(64) void track_update_kernel(State st, Params p, FrameArgs fr, int f0, const float* __restrict__ quads,
+                                                          const int32_t* __restrict__ n_det, const int32_t* __restrict__ state,
+                                                          int32_t* __restrict__ track_id, int32_t* __restrict__ slot_of,
+                                                          int32_t* __restrict__ due_flag) {
+  __shared__ Dets<TRACK_MAX_CARDS> D;
+  const int lane = threadIdx.x;
+  const int f = f0 + blockIdx.x, s = fr.stream[blockIdx.x];
+  const double now = fr.now[blockIdx.x];
+  const int T = p.T;
+
+  const int nd = stage_detections(D, lane, f, p.K, quads, n_det, state);
   __syncthreads();
 
   const bool own = lane < T;
-  int32_t* I = st.ints + (size_t)s * TRACK_INTS * T;
-  double* Kal = st.kal + (size_t)s * TRACK_KAL * T;
+  Slot a = slot_load(st, s, T, lane, own);
   int32_t* C = st.ctrs + (size_t)s * TRACK_CTRS;
-  int live = 0, hit = 0, init = 0, id = 0, birth = 0, has_z = 0;
-  double last_t = 0.0;
-  if (own) {
-    live = I[0 * T + lane], hit = I[1 * T + lane], init = I[2 * T + lane], id = I[3 * T + lane], birth = I[4 * T + lane];
-    has_z = I[5 * T + lane];
-    last_t = st.last_t[(size_t)s * T + lane];
-  }
-  double pos[8], vel[8], pp[8], pv[8], vv[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    pos[j] = vel[j] = pp[j] = pv[j] = vv[j] = 0.0;
-    if (live) {
-      pos[j] = Kal[(0 + j) * T + lane], vel[j] = Kal[(8 + j) * T + lane], pp[j] = Kal[(16 + j) * T + lane];
-      pv[j] = Kal[(24 + j) * T + lane], vv[j] = Kal[(32 + j) * T + lane];
-    }
-  }
   int next_id = C[0], next_birth = C[1], overflow = C[2];
-
-  // 1. drop, 2. age and predict
-  if (live && hit < 0) live = 0, id = 0;
-  if (live) {
-    hit -= 1;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) pos[j] = pos[j] + vel[j];
-  }
+  slot_age(a);
 
   // 3. greedy association, closest pair first: the initialised tracks, then the initialising ones on what is left
-  int mdi = -1;  // detection this lane's track took in this frame
   unsigned free_d = nd > 0 ? (0xffffffffu >> (32 - nd)) : 0u;
   for (int phase = 0; phase < 2; ++phase) {
-    const bool cand = live && init == phase;
+    const bool cand = a.live && a.init == phase;
     double d[TRACK_MAX_CARDS];
 #pragma unroll
     for (int di = 0; di < TRACK_MAX_CARDS; ++di) {
       d[di] = INFINITY;
       if (di < nd && cand && ((free_d >> di) & 1u)) {
-        double sum = 0.0;
-#pragma unroll
-        for (int c = 0; c < 4; ++c) {
-          const double dx = det[di][2 * c] - pos[2 * c], dy = det[di][2 * c + 1] - pos[2 * c + 1];
-          const double r = __dsqrt_rn(dx * dx + dy * dy);
-          sum = c == 0 ? r : sum + r;
-        }
-        const double dist = sum / 4.0;
+        const double dist = track_distance(D.det[di], a.pos);
         if (dist < p.thr) d[di] = dist;  // a NaN never matches
       }
     }
@@ -132,38 +244,24 @@ __global__ __launch_bounds__(64) void track_update_kernel(State st, Params p, Fr
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) m = fmin(m, __shfl_xor(m, off));
       if (!(m < INFINITY)) break;  // wave-uniform
-      int b = best == m ? birth : INT_MAX;  // ties between tracks: creation order, as the host's list order
+      int b = best == m ? a.birth : INT_MAX;  // ties between tracks: creation order, as the host's list order
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) b = min(b, __shfl_xor(b, off));
-      const bool win = best == m && birth == b;
+      const bool win = best == m && a.birth == b;
       const int wl = __ffsll((unsigned long long)__ballot(win)) - 1;
       const int wdi = __shfl(bdi, wl);
       free_d &= ~(1u << wdi);
       int gets_id = 0;
       if (lane == wl) {
         used = true;
-        mdi = wdi;
-        hit = min(hit + 2 * p.period, p.hmax);
-        if (init && hit > p.delay) init = 0, id = next_id, gets_id = 1, has_z = 0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {  // _KalmanTrack.kalman_update
-          const double e = det[wdi][j] - pos[j];
-          const double sv = pp[j] + 2.0 * pv[j] + vv[j] + KAL_Q + KAL_R;
-          const double k0 = 1.0 - KAL_R / sv, k1 = (pv[j] + vv[j]) / sv;
-          pos[j] = pos[j] + k0 * e;
-          vel[j] = vel[j] + k1 * e;
-          const double nvv = vv[j] + KAL_Q - k1 * k1 * sv;
-          pp[j] = k0 * KAL_R, pv[j] = k1 * KAL_R, vv[j] = nvv;
-        }
+        gets_id = slot_take(a, p, D.det[wdi], wdi, next_id);
       }
       next_id += __shfl(gets_id, wl);
     }
   }
 
   // 4. unmatched detections, ascending, take the lowest free slot
-  unsigned long long freem = __ballot(own && !live);
-  const bool new_init = p.period <= p.delay;
-  bool fresh = false;
+  unsigned long long freem = __ballot(own && !a.live);
   for (int di = 0; di < nd; ++di) {
     if (!((free_d >> di) & 1u)) continue;
     if (freem == 0ull) {
@@ -172,69 +270,23 @@ __global__ __launch_bounds__(64) void track_update_kernel(State st, Params p, Fr
     }
     const int sl = __ffsll(freem) - 1;
     freem &= freem - 1ull;
-    if (lane == sl) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) pos[j] = det[di][j], vel[j] = 0.0, pp[j] = KAL_POS_VAR, pv[j] = 0.0, vv[j] = KAL_VEL_VAR;
-      live = 1, hit = p.period, init = new_init ? 1 : 0, id = new_init ? 0 : next_id, birth = next_birth;
-      has_z = 0, last_t = 0.0, mdi = di, fresh = true;
-    }
-    if (!new_init) next_id += 1;
+    if (lane == sl) slot_spawn(a, p, D.det[di], di, next_id, next_birth);
+    if (!spawn_initialising(p)) next_id += 1;
     next_birth += 1;
   }
 
-  // 5. report and gate
-  const bool rep = live && id > 0 && mdi >= 0 && hit >= 0;
-  const bool due = rep && (!has_z || now - last_t > p.wait);
-  if (due) last_t = now;
-  if (rep) {
-    const int k = det_k[mdi];
-    o_id[k] = id, o_slot[k] = s * T + lane, o_due[k] = due ? 1 : 0;
-  }
-
-  if (own) {
-    I[0 * T + lane] = live, I[1 * T + lane] = hit, I[2 * T + lane] = init, I[3 * T + lane] = id, I[4 * T + lane] = birth;
-    I[5 * T + lane] = has_z;
-    st.last_t[(size_t)s * T + lane] = last_t;
-    if (live) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        Kal[(0 + j) * T + lane] = pos[j], Kal[(8 + j) * T + lane] = vel[j], Kal[(16 + j) * T + lane] = pp[j];
-        Kal[(24 + j) * T + lane] = pv[j], Kal[(32 + j) * T + lane] = vv[j];
-      }
-    }
-    if (fresh) {
-      for (int t = 0; t < p.top_k; ++t) {
-        st.m_ids[((size_t)s * T + lane) * p.top_k + t] = -1;
-        st.m_scores[((size_t)s * T + lane) * p.top_k + t] = -INFINITY;
-      }
-    }
-  }
+  slot_report(a, p, now, D, s, T, lane);
+  slot_store(st, a, s, T, lane, own, p.top_k);
   if (lane == 0) C[0] = next_id, C[1] = next_birth, C[2] = overflow;
   __syncthreads();
-  if (lane < K) {
-    const size_t o = (size_t)f * K + lane;
-    track_id[o] = o_id[lane], slot_of[o] = o_slot[lane], due_flag[o] = o_due[lane];
-  }
-}
-
-// mean corner distance of detection q to a track's predicted corners: the host's np.linalg.norm(..., axis=1).mean(), the same
-// operations in the same order as the one-wave kernel's distance row
-__device__ __forceinline__ double track_distance(const double* q, const double (&pos)[8]) {
-  double sum = 0.0;
-#pragma unroll
-  for (int c = 0; c < 4; ++c) {
-    const double dx = q[2 * c] - pos[2 * c], dy = q[2 * c + 1] - pos[2 * c + 1];
-    const double r = __dsqrt_rn(dx * dx + dy * dy);
-    sum = c == 0 ? r : sum + r;
-  }
-  return sum / 4.0;
+  write_report(D, f, p.K, lane, track_id, slot_of, due_flag);
 }
 
 // The wide form (MTGV_TRACKER_WIDE): one workgroup of W = ceil(T / 64) waves per frame, thread t owns slot t, up to 64
-// detections in LDS.  A track's own arithmetic is the one-wave kernel's; only what crosses a wave differs: the round's minimum
-// is reduced per wave by shuffles and across waves through LDS, the free detections are a 64-bit mask, the free slots W ballots.
-// A lane keeps no distance row: it caches (best, index) over the free detections and rescans from LDS only when that
-// detection was taken by another track (its minimum over the free set changes only then).
+// detections in LDS.  A track's own arithmetic is the one-wave kernel's, the same slot_* pieces; only what crosses a wave
+// differs: the round's minimum is reduced per wave by shuffles and across waves through LDS, the free detections are a 64-bit
+// mask, the free slots W ballots.  A lane keeps no distance row: it caches (best, index) over the free detections and rescans
+// from LDS only when that detection was taken by another track (its minimum over the free set changes only then).
 // Every __syncthreads() below is reached by every thread: the loop bounds (nd, two phases) and the early exit are values
 // that all threads read from LDS after a barrier.
 __global__ __launch_bounds__(TRACK_WIDE_MAX_TRACKS) void track_update_wide_kernel(State st, Params p, FrameArgs fr, int f0,
@@ -243,10 +295,8 @@ __global__ __launch_bounds__(TRACK_WIDE_MAX_TRACKS) void track_update_wide_kerne
                                                                                   const int32_t* __restrict__ state,
                                                                                   int32_t* __restrict__ track_id, int32_t* __restrict__ slot_of,
                                                                                   int32_t* __restrict__ due_flag) {
-  constexpr int KM = TRACK_WIDE_MAX_CARDS, WM = TRACK_WIDE_MAX_TRACKS / 64;
-  __shared__ double det[KM][8];
-  __shared__ int det_k[KM];
-  __shared__ int o_id[KM], o_slot[KM], o_due[KM];
+  constexpr int WM = TRACK_WIDE_MAX_TRACKS / 64;
+  __shared__ Dets<TRACK_WIDE_MAX_CARDS> D;
   __shared__ int s_nd;
   __shared__ double r_dist[WM];                                   // per wave: its minimum of the round ...
   __shared__ int r_birth[WM], r_thread[WM], r_di[WM], r_gets[WM];  // ... and whose it is
@@ -254,62 +304,25 @@ __global__ __launch_bounds__(TRACK_WIDE_MAX_TRACKS) void track_update_wide_kerne
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, W = blockDim.x >> 6;
   const int f = f0 + blockIdx.x, s = fr.stream[blockIdx.x];
   const double now = fr.now[blockIdx.x];
-  const int T = p.T, K = p.K;
+  const int T = p.T;
 
-  // the frame's detection list: the valid slots in ascending k (K <= 64: all of it in wave 0)
-  if (wave == 0) {
-    bool valid = lane < K;
-    if (valid && n_det != nullptr) valid = lane < min(n_det[f], K);
-    if (valid && state != nullptr) valid = state[(size_t)f * K + lane] > 0;
-    const unsigned long long vm = __ballot(valid);
-    if (lane == 0) s_nd = __popcll(vm);
-    o_id[lane] = 0, o_slot[lane] = -1, o_due[lane] = 0;
-    if (valid) {
-      const int di = __popcll(vm & ((1ull << lane) - 1ull));
-      det_k[di] = lane;
-      const float* q = quads + ((size_t)f * K + lane) * 8;
-#pragma unroll
-      for (int j = 0; j < 8; ++j) det[di][j] = (double)q[j];
-    }
+  if (wave == 0) {  // (K <= 64: the whole list in wave 0)
+    const int n = stage_detections(D, lane, f, p.K, quads, n_det, state);
+    if (lane == 0) s_nd = n;
   }
   __syncthreads();
   const int nd = s_nd;  // workgroup-uniform, 0..64
 
   const bool own = tid < T;
-  int32_t* I = st.ints + (size_t)s * TRACK_INTS * T;
-  double* Kal = st.kal + (size_t)s * TRACK_KAL * T;
+  Slot a = slot_load(st, s, T, tid, own);
   int32_t* C = st.ctrs + (size_t)s * TRACK_CTRS;
-  int live = 0, hit = 0, init = 0, id = 0, birth = 0, has_z = 0;
-  double last_t = 0.0;
-  if (own) {
-    live = I[0 * T + tid], hit = I[1 * T + tid], init = I[2 * T + tid], id = I[3 * T + tid], birth = I[4 * T + tid];
-    has_z = I[5 * T + tid];
-    last_t = st.last_t[(size_t)s * T + tid];
-  }
-  double pos[8], vel[8], pp[8], pv[8], vv[8];
-#pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    pos[j] = vel[j] = pp[j] = pv[j] = vv[j] = 0.0;
-    if (live) {
-      pos[j] = Kal[(0 + j) * T + tid], vel[j] = Kal[(8 + j) * T + tid], pp[j] = Kal[(16 + j) * T + tid];
-      pv[j] = Kal[(24 + j) * T + tid], vv[j] = Kal[(32 + j) * T + tid];
-    }
-  }
   int next_id = C[0], next_birth = C[1], overflow = C[2];  // (written by thread 0 behind the last barrier)
-
-  // 1. drop, 2. age and predict
-  if (live && hit < 0) live = 0, id = 0;
-  if (live) {
-    hit -= 1;
-#pragma unroll
-    for (int j = 0; j < 8; ++j) pos[j] = pos[j] + vel[j];
-  }
+  slot_age(a);
 
   // 3. greedy association, closest pair first: the initialised tracks, then the initialising ones on what is left
-  int mdi = -1;  // detection this thread's track took in this frame
   unsigned long long free_d = nd >= 64 ? ~0ull : ((1ull << nd) - 1ull);  // workgroup-uniform: changed only by values read from LDS
   for (int phase = 0; phase < 2; ++phase) {
-    const bool cand = live && init == phase;
+    const bool cand = a.live && a.init == phase;
     bool used = false, rescan = true;
     double best = INFINITY;
     int bdi = -1;
@@ -318,7 +331,7 @@ __global__ __launch_bounds__(TRACK_WIDE_MAX_TRACKS) void track_update_wide_kerne
         best = INFINITY, bdi = -1;
         for (int di = 0; di < nd; ++di) {
           if (!((free_d >> di) & 1ull)) continue;
-          const double dist = track_distance(det[di], pos);
+          const double dist = track_distance(D.det[di], a.pos);
           if (dist < p.thr && dist < best) best = dist, bdi = di;  // a NaN never matches; strict: the lowest index wins a tie
         }
         rescan = false;
@@ -327,15 +340,14 @@ __global__ __launch_bounds__(TRACK_WIDE_MAX_TRACKS) void track_update_wide_kerne
       double m = mine;
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) m = fmin(m, __shfl_xor(m, off));
-      int b = mine == m ? birth : INT_MAX;  // ties between tracks: creation order, as the host's list order
+      int b = mine == m ? a.birth : INT_MAX;  // ties between tracks: creation order, as the host's list order
 #pragma unroll
       for (int off = 32; off > 0; off >>= 1) b = min(b, __shfl_xor(b, off));
-      const bool win = mine == m && birth == b;
+      const bool win = mine == m && a.birth == b;
       const int wl = max(__ffsll((unsigned long long)__ballot(win)) - 1, 0);
-      const int nh = min(hit + 2 * p.period, p.hmax);
       if (lane == wl) {  // one lane per wave (the entry is not used when m is not finite)
         r_dist[wave] = m, r_birth[wave] = b, r_thread[wave] = tid, r_di[wave] = bdi;
-        r_gets[wave] = (init && nh > p.delay) ? 1 : 0;
+        r_gets[wave] = slot_gets_id(a, p);
       }
       __syncthreads();
       double gm = INFINITY;
@@ -350,19 +362,7 @@ __global__ __launch_bounds__(TRACK_WIDE_MAX_TRACKS) void track_update_wide_kerne
       free_d &= ~(1ull << gdi);
       if (tid == gt) {
         used = true;
-        mdi = gdi;
-        hit = nh;
-        if (gets_id) init = 0, id = next_id, has_z = 0;
-#pragma unroll
-        for (int j = 0; j < 8; ++j) {  // _KalmanTrack.kalman_update
-          const double e = det[gdi][j] - pos[j];
-          const double sv = pp[j] + 2.0 * pv[j] + vv[j] + KAL_Q + KAL_R;
-          const double k0 = 1.0 - KAL_R / sv, k1 = (pv[j] + vv[j]) / sv;
-          pos[j] = pos[j] + k0 * e;
-          vel[j] = vel[j] + k1 * e;
-          const double nvv = vv[j] + KAL_Q - k1 * k1 * sv;
-          pp[j] = k0 * KAL_R, pv[j] = k1 * KAL_R, vv[j] = nvv;
-        }
+        slot_take(a, p, D.det[gdi], gdi, next_id);  // (-> gets_id, which every thread has from LDS)
       } else if (bdi == gdi) {
         rescan = true;  // the cached minimum was taken
       }
@@ -372,15 +372,13 @@ __global__ __launch_bounds__(TRACK_WIDE_MAX_TRACKS) void track_update_wide_kerne
 
   // 4. unmatched detections, ascending, take the lowest free slot of the whole workgroup
   {
-    const unsigned long long fb = __ballot(own && !live);
+    const unsigned long long fb = __ballot(own && !a.live);
     if (lane == 0) s_free[wave] = fb;
   }
   __syncthreads();
   unsigned long long freem[WM];
 #pragma unroll
   for (int w = 0; w < WM; ++w) freem[w] = w < W ? s_free[w] : 0ull;
-  const bool new_init = p.period <= p.delay;
-  bool fresh = false;
   for (int di = 0; di < nd; ++di) {  // workgroup-uniform: nd, free_d and freem are the same in every thread
     if (!((free_d >> di) & 1ull)) continue;
     int sl = -1;
@@ -391,49 +389,16 @@ __global__ __launch_bounds__(TRACK_WIDE_MAX_TRACKS) void track_update_wide_kerne
       overflow += 1;
       continue;
     }
-    if (tid == sl) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) pos[j] = det[di][j], vel[j] = 0.0, pp[j] = KAL_POS_VAR, pv[j] = 0.0, vv[j] = KAL_VEL_VAR;
-      live = 1, hit = p.period, init = new_init ? 1 : 0, id = new_init ? 0 : next_id, birth = next_birth;
-      has_z = 0, last_t = 0.0, mdi = di, fresh = true;
-    }
-    if (!new_init) next_id += 1;
+    if (tid == sl) slot_spawn(a, p, D.det[di], di, next_id, next_birth);
+    if (!spawn_initialising(p)) next_id += 1;
     next_birth += 1;
   }
 
-  // 5. report and gate
-  const bool rep = live && id > 0 && mdi >= 0 && hit >= 0;
-  const bool due = rep && (!has_z || now - last_t > p.wait);
-  if (due) last_t = now;
-  if (rep) {
-    const int k = det_k[mdi];
-    o_id[k] = id, o_slot[k] = s * T + tid, o_due[k] = due ? 1 : 0;
-  }
-
-  if (own) {
-    I[0 * T + tid] = live, I[1 * T + tid] = hit, I[2 * T + tid] = init, I[3 * T + tid] = id, I[4 * T + tid] = birth;
-    I[5 * T + tid] = has_z;
-    st.last_t[(size_t)s * T + tid] = last_t;
-    if (live) {
-#pragma unroll
-      for (int j = 0; j < 8; ++j) {
-        Kal[(0 + j) * T + tid] = pos[j], Kal[(8 + j) * T + tid] = vel[j], Kal[(16 + j) * T + tid] = pp[j];
-        Kal[(24 + j) * T + tid] = pv[j], Kal[(32 + j) * T + tid] = vv[j];
-      }
-    }
-    if (fresh) {
-      for (int t = 0; t < p.top_k; ++t) {
-        st.m_ids[((size_t)s * T + tid) * p.top_k + t] = -1;
-        st.m_scores[((size_t)s * T + tid) * p.top_k + t] = -INFINITY;
-      }
-    }
-  }
+  slot_report(a, p, now, D, s, T, tid);
+  slot_store(st, a, s, T, tid, own, p.top_k);
   if (tid == 0) C[0] = next_id, C[1] = next_birth, C[2] = overflow;
   __syncthreads();
-  if (tid < K) {
-    const size_t o = (size_t)f * K + tid;
-    track_id[o] = o_id[tid], slot_of[o] = o_slot[tid], due_flag[o] = o_due[tid];
-  }
+  write_report(D, f, p.K, tid, track_id, slot_of, due_flag);
 }
 
 // ordered compaction of the due slots: one wave walks the n = F * K flags in ascending order (no atomics, so the order of

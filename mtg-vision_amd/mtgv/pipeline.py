@@ -169,6 +169,33 @@ def _frames_of(item):
     return item, None, None
 
 
+@dataclass
+class Cropped:
+    """What `Pipeline.crop` hands on.  boxes (F, K, 4); crops (F * K, h, w, 3) uint8; quads (F * K, 4, 2): what the de-warp
+    was given, pixels of the detector's input; quads_src: the same corners in camera pixels (SourceFrames only); card_state
+    (F * K,) ("obb" only); thumbs, thumb_offsets: filled by `Pipeline._thumbnails` when the pipeline encodes them."""
+
+    boxes: torch.Tensor
+    crops: torch.Tensor
+    quads: torch.Tensor
+    quads_src: Optional[torch.Tensor] = None
+    card_state: Optional[torch.Tensor] = None
+    thumbs: Optional[torch.Tensor] = None
+    thumb_offsets: Optional[torch.Tensor] = None
+
+    def extras(self, det: dict, F: int, K: int) -> dict:
+        """the optional parts as an output dict carries them; those that are no thumbnails go into its `det` as well"""
+        out = {}
+        if self.card_state is not None:
+            out["quads"], out["card_state"] = self.quads.view(F, K, 4, 2), self.card_state.view(F, K)
+        if self.quads_src is not None:
+            out["quads_src"] = self.quads_src.view(F, K, 4, 2)
+        det.update(out)
+        if self.thumbs is not None:
+            out["thumbs"], out["thumb_offsets"] = self.thumbs, self.thumb_offsets
+        return out
+
+
 class Pipeline:
     def __init__(self, detector: Detector, encoder: Encoder, matcher, cards_per_frame: int = 8, top_k: int = 1,
                  match_fn: Optional[Callable] = None, quad_source: str = "box", thumbnail_quality: Optional[int] = None,
@@ -220,23 +247,21 @@ class Pipeline:
         self._warp_ws = None
 
     def _embed_match(self, frames_u8: torch.Tensor, det, lease=None, src=None):
-        boxes, crops = self._crop(frames_u8, det, lease, src)
-        return self._embed(det, boxes, crops, *self._thumbnails(crops))
+        return self._embed(det, self._thumbnails(self.crop(frames_u8, det, lease, src)))
 
-    def _thumbnails(self, crops):
-        """(thumbs, thumb_offsets): the crops as JPEG files, encoded on the current stream; (None, None) when off"""
-        if self._jpeg is None:
-            return None, None
-        return self._jpeg.encode_device(crops, self.thumbnail_quality, 420)
+    def _thumbnails(self, cropped: Cropped) -> Cropped:
+        """fills thumbs, thumb_offsets: the crops as JPEG files, encoded on the current stream; nothing when off"""
+        if self._jpeg is not None:
+            cropped.thumbs, cropped.thumb_offsets = self._jpeg.encode_device(cropped.crops, self.thumbnail_quality, 420)
+        return cropped
 
-    def _crop(self, frames_u8: torch.Tensor, det, lease=None, src=None):
-        """detections -> (boxes (F, K, 4), crops (F * K, h, w, 3) uint8): the K best boxes or mask quadrilaterals, de-warped
-        from frames_u8 or, with `src` (SourceFrames), from the source frames"""
+    def crop(self, frames_u8: torch.Tensor, det, lease=None, src=None) -> Cropped:
+        """detections -> Cropped: the K best boxes, mask quadrilaterals or oriented boxes per frame, de-warped from frames_u8
+        or, with `src` (SourceFrames), from the source frames.  `det` is read, not written."""
         F, K = frames_u8.shape[0], self.K
         if self.quad_source == "obb":
             quads, sel, frame_idx, state = obb_cards(det["n_det"], det["rboxes"], det["conf"], det["cls"], self._pad, K, 0, 1, 2)
-            det["quads"], det["card_state"] = quads.view(F, K, 4, 2), state.view(F, K)
-            return self._warp(frames_u8, sel.view(F, K, 4), quads, frame_idx, lease, src, det)
+            return self._warp(frames_u8, sel.view(F, K, 4), quads, frame_idx, lease, src, state)
         # the K highest-confidence detections per frame (NMS output is score-descending), pad boxes where a frame has
         # fewer; every step of the glue is a library kernel (no PyTorch arithmetic on the streams of the step)
         want_mask = self.quad_source == "mask"
@@ -248,26 +273,25 @@ class Pipeline:
             ml = det["mask_logits"]
             assert ml.shape[1] == K, f"mask rows {ml.shape[1]} != cards per frame {K}"
             quads, _ = mask_quads_from_logits(ml.view(F * K, *ml.shape[-2:]), sel)
-        return self._warp(frames_u8, sel.view(F, K, 4), quads, frame_idx, lease, src, det)
+        return self._warp(frames_u8, sel.view(F, K, 4), quads, frame_idx, lease, src)
 
-    def _warp(self, frames_u8, boxes, quads, frame_idx, lease, src=None, det=None):
+    def _warp(self, frames_u8, boxes, quads, frame_idx, lease, src=None, state=None) -> Cropped:
         """the one place every quad_source's quads are de-warped.  With `src` the quads (pixels of the detector's input, like
-        the boxes) are mapped into their source frames and the crops come from there; det gains quads_src (F, K, 4, 2)."""
+        the boxes) are mapped into their source frames and the crops come from there; the record gains quads_src."""
         F, K = frames_u8.shape[0], self.K
         if self._warp_ws is None or self._warp_ws.numel() < 9 * F * K:
             self._warp_ws = warp_workspace(F * K, frames_u8.device)  # once per pipeline (the largest batch seen so far)
         if src is None:
-            crops = warp_quads(frames_u8, quads, frame_idx, self.encoder.cfg.image_hw, 0.05, self._warp_ws)
+            crops, quads_src = warp_quads(frames_u8, quads, frame_idx, self.encoder.cfg.image_hw, 0.05, self._warp_ws), None
         else:
             crops, quads_src = crop.warp_quads_src(src, quads, frame_idx, self.encoder.cfg.image_hw, 0.05, self._warp_ws)
-            det["quads_src"] = quads_src.view(F, K, 4, 2)
         if lease is not None:
             lease.done()  # the de-warp is the last reader of the frames
-        return boxes, crops
+        return Cropped(boxes, crops, quads, quads_src, state)
 
-    def _embed(self, det, boxes, crops, thumbs=None, thumb_offsets=None, match_stream=None):
-        F, K = boxes.shape[0], self.K
-        z = self.encoder.encode(crops)
+    def _embed(self, det, cropped: Cropped, match_stream=None):
+        F, K = cropped.boxes.shape[0], self.K
+        z = self.encoder.encode(cropped.crops)
         if match_stream is None:
             ids, scores = self.match_fn(z, self.top_k)
         else:  # the match on a stream of its own: the next batch's encoder does not queue behind it
@@ -281,17 +305,12 @@ class Pipeline:
             "ids": ids.view(F, K, self.top_k),
             "scores": scores.view(F, K, self.top_k),
             "n_det": det["n_det"],
-            "boxes": boxes,
-            "crops": crops,
+            "boxes": cropped.boxes,
+            "crops": cropped.crops,
             "z": z,
             "det": det,
         }
-        if thumbs is not None:
-            out["thumbs"], out["thumb_offsets"] = thumbs, thumb_offsets
-        if "quads" in det:  # quad_source "obb"
-            out["quads"], out["card_state"] = det["quads"], det["card_state"]
-        if "quads_src" in det:  # the batch came as SourceFrames
-            out["quads_src"] = det["quads_src"]
+        out.update(cropped.extras(det, F, K))
         return out
 
     @staticmethod
@@ -372,20 +391,20 @@ class Pipeline:
                     # the crop stage (card selection, mask -> quadrilateral, de-warp: latency-bound kernels of a few hundred
                     # workgroups) belongs to the detect stream: beside the other stream's GEMMs it costs next to nothing, in
                     # front of the encoder it would leave most of the GPU idle (MTGV_CROP_STAGE=enc: the round-3 split)
-                    cropped = self._crop(frames, det, lease, src) if crop_on_det else None
+                    cropped = self.crop(frames, det, lease, src) if crop_on_det else None
                     ev = torch.cuda.Event()
                     ev.record(self._s_det)
                     if cropped is not None:  # behind the event: this batch's embed does not wait for its thumbnails
-                        cropped = (*cropped, *self._thumbnails(cropped[1]))
+                        self._thumbnails(cropped)
                 nxt = (frames, det, ev, lease, cropped, src)
             if pending is not None:
                 pf, pdet, pev, please, pcrop, psrc = pending
                 with torch.cuda.stream(self._s_enc):
                     self._s_enc.wait_event(pev)
-                    for t in list(pdet.values()) + list(pcrop or ()):
+                    for t in list(pdet.values()) + list(vars(pcrop).values() if pcrop is not None else ()):
                         if t is not None:
                             t.record_stream(self._s_enc)
-                    outs.append(self._embed(pdet, *pcrop, match_stream=s_match) if pcrop is not None
+                    outs.append(self._embed(pdet, pcrop, match_stream=s_match) if pcrop is not None
                                 else self._embed_match(pf, pdet, please, psrc))
             pending = nxt
         cur.wait_stream(self._s_det)

@@ -23,6 +23,7 @@ import numpy as np
 import torch
 
 from . import native
+from .pipeline import SourceFrames
 
 _POLICY = ("distance_threshold", "hit_counter_max", "initialization_delay", "period", "update_wait_sec", "ewma_weight")
 
@@ -204,23 +205,6 @@ class TrackedPipeline:
                                      **policy)
         self.last_z = None  # the embeddings committed by the last step (n_due, dim), None when nothing was due
 
-    def _crop(self, frames_u8, det, src=None):
-        """Pipeline._crop, keeping the quads it hands to the de-warp (Pipeline returns them only for "obb"); with `src`
-        (SourceFrames) the quads the de-warp mapped into the camera's frames"""
-        p, seen = self.pipeline, {}
-        warp = p._warp
-
-        def keep(frames, boxes, quads, *rest):
-            seen["quads"] = quads
-            return warp(frames, boxes, quads, *rest)
-
-        p._warp = keep  # shadows the method for this call
-        try:
-            boxes, crops = p._crop(frames_u8, det, None) if src is None else p._crop(frames_u8, det, None, src)
-        finally:
-            del p._warp
-        return boxes, crops, (seen["quads"] if src is None else det["quads_src"])
-
     def run(self, frames_u8: torch.Tensor, stream_of_frame: Sequence[int], now, flip_rgb: bool = True) -> dict:
         """frames (F, in_h, in_w, 3) uint8 on the GPU, frame f from camera stream_of_frame[f] (distinct) at now[f] seconds
         (or one clock for all) -> dict: track_ids (F, K) int32 (0: no initialised track in the slot), ids / scores
@@ -235,34 +219,30 @@ class TrackedPipeline:
         their batch size.  All crops (and thumbnails) are produced as in Pipeline.run; only the due ones are embedded."""
         p, trk = self.pipeline, self.tracker
         sof = check_streams(stream_of_frame, trk.streams)
-        src = frames_u8 if hasattr(frames_u8, "frames") and hasattr(frames_u8, "geo") else None  # a SourceFrames
+        src = frames_u8 if isinstance(frames_u8, SourceFrames) else None
         if src is not None:
             frames_u8 = src.frames
         F, K = frames_u8.shape[0], p.K
         assert sof.size == F, f"{sof.size} streams named for {F} frames"
         det = p.detector.forward(frames_u8, flip_rgb, mask_rows=K)
-        boxes, crops, quads = self._crop(frames_u8, det, src)
-        thumbs, thumb_offsets = p._thumbnails(crops)
+        cropped = p._thumbnails(p.crop(frames_u8, det, src=src))
+        quads = cropped.quads if src is None else cropped.quads_src
         if p.quad_source == "obb":
-            track_ids, due_idx, n_due_dev = trk.update(quads, sof, now, state=det["card_state"])
+            track_ids, due_idx, n_due_dev = trk.update(quads, sof, now, state=cropped.card_state)
         else:
             track_ids, due_idx, n_due_dev = trk.update(quads, sof, now, n_det=det["n_det"])
         n_due = int(n_due_dev.item())  # the step's only synchronisation
         self.last_z = None
         if n_due > 0:
-            z = p.encoder.encode(trk.gather(crops)[:n_due])
+            z = p.encoder.encode(trk.gather(cropped.crops)[:n_due])
             q = trk.commit(z)
             hits = p.matcher.match(q, self.top_k) if self.match_opts is None else p.matcher.match(q, self.top_k, **self.match_opts)
             ids, scores = trk.store(*hits)
             self.last_z = z
         else:
             ids, scores = trk.store()
-        out = {"track_ids": track_ids, "ids": ids, "scores": scores, "n_due": n_due, "due_idx": due_idx, "n_det": det["n_det"], "boxes": boxes,
-               "crops": crops, "det": det, "quads": quads.view(F, K, 4, 2)}
-        if thumbs is not None:
-            out["thumbs"], out["thumb_offsets"] = thumbs, thumb_offsets
-        if "card_state" in det:
-            out["card_state"] = det["card_state"]
-        if src is not None:
-            out["quads_src"] = det["quads_src"]
+        out = {"track_ids": track_ids, "ids": ids, "scores": scores, "n_due": n_due, "due_idx": due_idx, "n_det": det["n_det"],
+               "boxes": cropped.boxes, "crops": cropped.crops, "det": det}
+        out.update(cropped.extras(det, F, K))
+        out["quads"] = quads.view(F, K, 4, 2)  # every quad_source's, and what the tracker saw: camera pixels with sources
         return out

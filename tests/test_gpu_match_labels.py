@@ -371,18 +371,17 @@ class _StubPipeline:
 
         self.detector, self.encoder = Det(), Enc()
 
-    def _warp(self, frames, boxes, quads, frame_idx, lease):
-        return frames
+    def crop(self, frames_u8, det, lease=None, src=None):
+        from mtgv.pipeline import Cropped
 
-    def _crop(self, frames_u8, det, lease):
         streams = self.scn.steps[self.step].streams
         crops = torch.zeros((len(streams) * self.K, 4), dtype=torch.uint8, device="cuda")
         crops[:, 0] = torch.tensor(streams, device="cuda").repeat_interleave(self.K)
         crops[:, 1] = torch.arange(self.K, device="cuda").repeat(len(streams))
-        return None, self._warp(crops, None, det["quads"].reshape(-1, 4, 2), None, lease)
+        return Cropped(None, crops, det["quads"].reshape(-1, 4, 2))
 
-    def _thumbnails(self, crops):
-        return None, None
+    def _thumbnails(self, cropped):
+        return cropped
 
 
 def test_tracked_pipeline_distinct_matches():

@@ -11,6 +11,7 @@ import pytest
 import torch
 
 import source_frames_common as sc
+import track_common as tc
 from oracle import resize_ref, warp_ref
 
 pytestmark = pytest.mark.gpu
@@ -259,6 +260,8 @@ def test_pipeline_run_source_frames(quad_source):
     ref = pipe.run(sf.frames)
     torch.cuda.synchronize()
     assert "quads_src" not in ref and "quads_src" not in ref["det"]
+    assert (set(out), set(out["det"])) == tc.output_keys(quad_source, sources=True, thumbs=True)
+    assert (set(ref), set(ref["det"])) == tc.output_keys(quad_source, thumbs=True)
     assert int(out["n_det"].min()) >= K, "the detector found fewer than K detections: the slots would be pad boxes"
     for k, v in ref["det"].items():  # the detections are those of the frames: bit for bit
         assert (out["det"][k] is None) if v is None else torch.equal(out["det"][k].contiguous().view(torch.uint8), v.contiguous().view(torch.uint8)), k
@@ -325,6 +328,7 @@ def test_tracked_pipeline_source_frames():
         sf = _source_frames(frames, IN_HW)
         now = [10.0 + 0.6 * step, 10.01 + 0.6 * step]
         out = tp.run(sf, [1, 0], now)
+        assert (set(out), set(out["det"])) == tc.output_keys("mask", tracked=True, sources=True)
         quads = _det_quads_2(pipe, out)
         want_src = sc.map_quads(quads, np.repeat(np.arange(2), K), shapes, IN_HW)
         assert np.array_equal(sc.bits(out["quads"].cpu().numpy().reshape(2 * K, 4, 2)), sc.bits(want_src))  # camera pixels

@@ -284,6 +284,8 @@ def test_tracked_pipeline_end_to_end(source):
         now = [50.0 + 0.2 * step + 0.01 * f for f in range(F)]
         out = tp.run(frames, [2, 0, 1], now)
         ref = pipe.run(frames)
+        assert (set(out), set(out["det"])) == tc.output_keys(source, tracked=True)
+        assert (set(ref), set(ref["det"])) == tc.output_keys(source)
         for k in ("crops", "boxes", "n_det"):
             assert torch.equal(out[k], ref[k]), k
         n_due, due = out["n_due"], out["due_idx"].cpu().numpy()

@@ -42,7 +42,7 @@ def _device_pass(scn, S, K, layout, wide):
 
     trk = DeviceTracker(S, K, tw.DIM, tw.TOP_K, max_tracks=scn.max_tracks, wide=wide, update_wait_sec=scn.update_wait_sec,
                         ewma_weight=scn.ewma_weight, **scn.policy)
-    assert trk.wide
+    assert trk.wide == (wide is not False)
     m, Z, dev = _matcher(), scn.z(), []
     for i, st in enumerate(scn.steps):
         quads, n_det, state, where = layout(scn, i)
@@ -125,8 +125,16 @@ def _check_association(name, run):
 
 @pytest.mark.parametrize("name", sorted(tc.SCENARIOS))
 def test_forced_wide_equals_the_host(name):
-    """T = 8 (4 in j_overflow), K = 4: every scenario of the one-wave tests through wide=True"""
+    """T = 8 (4 in j_overflow), K = 4: every scenario of the one-wave tests through wide=True; and the one-wave kernel leaves
+    the same state behind, array for array and bit for bit (the two kernels share one per-slot body, csrc/track.hip)"""
     _check_association(name, _run_forced(name))
+    scn, S, K, _, _, wide = _run_forced(name)
+    narrow = _device_pass(scn, S, K, tc.layout, False)
+    for i, (a, b) in enumerate(zip(narrow, wide)):
+        for s in range(S):
+            assert a["states"][s].keys() == b["states"][s].keys()
+            for key, v in a["states"][s].items():
+                assert np.array_equal(_bits(np.asarray(v)), _bits(np.asarray(b["states"][s][key]))), (name, i, s, key)
 
 
 @pytest.mark.parametrize("name", sorted(tw.scenarios()))
@@ -342,6 +350,8 @@ def test_tracked_pipeline_end_to_end(source):
         now = [50.0 + 0.2 * step + 0.01 * f for f in range(F)]
         out = tp.run(frames, order, now)
         ref = pipe.run(frames)
+        assert (set(out), set(out["det"])) == tc.output_keys(source, tracked=True)
+        assert (set(ref), set(ref["det"])) == tc.output_keys(source)
         for k in ("crops", "boxes", "n_det"):
             assert torch.equal(out[k], ref[k]), k
         n_due, due = out["n_due"], out["due_idx"].cpu().numpy()

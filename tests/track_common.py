@@ -197,6 +197,22 @@ def layout(scn: Scenario, i: int):
     return quads, (None if scn.mode == "state" else n_det), (None if scn.mode == "n_det" else state), where
 
 
+def output_keys(quad_source, tracked=False, sources=False, thumbs=False):
+    """(keys of the dict that Pipeline.run or - tracked - TrackedPipeline.run returns, keys of its "det"), as the code
+    returned them when the crop stage still wrote its quads into the detector's dict: the detector's own outputs, quads and
+    card_state for "obb", quads_src for SourceFrames, the thumbnails with a thumbnail quality"""
+    out = {"ids", "scores", "n_det", "boxes", "crops", "det"}
+    out |= {"track_ids", "n_due", "due_idx", "quads"} if tracked else {"z"}
+    det = {"n_det", "conf", "cls", "keep_idx"} | ({"rboxes"} if quad_source == "obb" else {"boxes", "mask_logits"})
+    if quad_source == "obb":
+        out, det = out | {"quads", "card_state"}, det | {"quads", "card_state"}
+    if sources:
+        out, det = out | {"quads_src"}, det | {"quads_src"}
+    if thumbs:
+        out |= {"thumbs", "thumb_offsets"}
+    return out, det
+
+
 def ewma32(prev, z, w):
     """TrackerCtx's `avg = w * z + (1 - w) * avg` on float32 vectors, restated with explicit float32 scalars (a Python
     float times a float32 array is a float32 product with the scalar rounded to float32); prev None: avg starts as z"""
