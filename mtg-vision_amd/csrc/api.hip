@@ -269,7 +269,7 @@ MTGV_API int mtgv_topk_merge_gathered(const int64_t* gathered_dev, int32_t n_ran
   return guarded([&] {
     MTGV_CHECK(gathered_dev && ids_dev && scores_dev, ERR_INVALID, "null argument");
     MTGV_CHECK(!(score_threshold != score_threshold), ERR_INVALID, "topk_merge_gathered: score_threshold is NaN");
-    topk_merge_gathered_launch(gathered_dev, n_ranks, b_total, k, row0, b, score_threshold, ids_dev, scores_dev, (hipStream_t)stream);
+    topk_merge_gathered_launch(gathered_dev, n_ranks, b_total, k, row0, b, score_threshold, false, ids_dev, scores_dev, (hipStream_t)stream);
   });
 }
 MTGV_API int mtgv_bank_topk_packed_ex(mtgv_bank* h, const float* q_dev, int32_t b, int32_t k, int64_t id_base, const uint64_t* masks_dev,
@@ -284,11 +284,9 @@ MTGV_API int mtgv_topk_merge_gathered_ex(const int64_t* gathered_dev, int32_t n_
   return guarded([&] {
     MTGV_CHECK(gathered_dev && ids_dev && scores_dev, ERR_INVALID, "null argument");
     MTGV_CHECK(!(score_threshold != score_threshold), ERR_INVALID, "topk_merge_gathered: score_threshold is NaN");
-    if (distinct == 0)  // groups play no part: mtgv_topk_merge_gathered itself
-      topk_merge_gathered_launch(gathered_dev, n_ranks, b_total, k, row0, b, score_threshold, ids_dev, scores_dev, (hipStream_t)stream);
-    else
-      topk_merge_gathered_distinct_launch(gathered_dev, n_ranks, b_total, k, row0, b, score_threshold, ids_dev, scores_dev,
-                                          (hipStream_t)stream);
+    // distinct == 0: groups play no part, mtgv_topk_merge_gathered itself
+    topk_merge_gathered_launch(gathered_dev, n_ranks, b_total, k, row0, b, score_threshold, distinct != 0, ids_dev, scores_dev,
+                               (hipStream_t)stream);
   });
 }
 MTGV_API int mtgv_bank_prepass_fallbacks(const mtgv_bank* h, int64_t* count) {

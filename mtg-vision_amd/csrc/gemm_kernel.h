@@ -384,33 +384,39 @@ __global__ __launch_bounds__(256, (TM * TN == 1 ? (BK == 16 ? 6 : 4) : TM * TN =
     k_loop(std::false_type{});
   }
 
-  if constexpr (EPI == 3) {
-    // ---- fused per-tile top-k with row labels (Bank::topk_labelled): the twin of EPI 1 below.  A column whose tags
-    // fail the row's (all_of, any_of, none_of) masks scores -inf like a column past N; with topk_distinct the winner's
-    // group travels with (score, id) through the butterfly and the retire step retires every column of that group
-    // (group >= 0), so a tile reports its best eligible rows of pairwise different groups.  A lane owns TN columns:
-    // their tags and groups are TN registers each, a row's masks are read once, when the row is filtered.
-    unsigned long tg[TN];
-    int gr[TN];
-    bool cok[TN];
+  if constexpr (EPI == 1 || EPI == 3) {
+    // ---- fused per-tile top-k (match path): the tile's scores never leave registers.
+    // A row's BN scores sit in the 32 lanes of one wave half x TN registers; each
+    // round picks the (score desc, id asc) maximum with a 5-step butterfly and
+    // retires it.  Candidates go to cand[m][tile_n][kk]; a merge kernel finishes.
+    // LAB (EPI 3, row labels, Bank::topk_labelled): a column whose tags fail the row's (all_of, any_of, none_of) masks
+    // scores -inf like a column past N; with topk_distinct the winner's group travels with (score, id) through the
+    // butterfly and the retire step retires every column of that group (group >= 0), so a tile reports its best eligible
+    // rows of pairwise different groups.  A lane owns TN columns: their tags and groups are TN registers each, a row's
+    // masks are read once, when the row is filtered.
+    constexpr bool LAB = EPI == 3;
+    unsigned long tg[LAB ? TN : 1];
+    int gr[LAB ? TN : 1];
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       const int n = bn0 + j * 32 + col;
-      cok[j] = n < p.N;
-      const float ws = (PREC == 1 && p.wscale != nullptr && cok[j]) ? p.wscale[n] * p.a_unmul : p.a_unmul;
-      tg[j] = (p.row_masks != nullptr && cok[j]) ? p.col_tags[n] : 0ul;
-      gr[j] = (p.topk_distinct != 0 && cok[j]) ? p.col_groups[n] : -1;
+      const bool nok = n < p.N;
+      const float ws = (PREC == 1 && p.wscale != nullptr && nok) ? p.wscale[n] * p.a_unmul : p.a_unmul;
+      if constexpr (LAB) {
+        tg[j] = (p.row_masks != nullptr && nok) ? p.col_tags[n] : 0ul;
+        gr[j] = (p.topk_distinct != 0 && nok) ? p.col_groups[n] : -1;
+      }
 #pragma unroll
       for (int i = 0; i < TM; ++i)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = cok[j] ? acc[i][j][r] * ws : -INFINITY;
+        for (int r = 0; r < 16; ++r) acc[i][j][r] = nok ? acc[i][j][r] * ws : -INFINITY;
     }
 #pragma unroll
     for (int i = 0; i < TM; ++i) {
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const int m = bm0 + wave * 32 * TM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-        {
+        if constexpr (LAB) {
           // (straight-line on purpose: bitwise & and | on the three tests and a select, no short-circuit branches)
           const bool mok = p.row_masks != nullptr && m < M_eff;
           const unsigned long m_all = mok ? p.row_masks[3 * (long)m] : 0ul;
@@ -428,13 +434,16 @@ __global__ __launch_bounds__(256, (TM * TN == 1 ? (BK == 16 ? 6 : 4) : TM * TN =
 #pragma unroll
           for (int j = 0; j < TN; ++j) {
             const float v = acc[i][j][r];
-            if (v > bs) bs = v, bi = bn0 + j * 32 + col, bg = gr[j];
+            if (v > bs) {
+              bs = v, bi = bn0 + j * 32 + col;
+              if constexpr (LAB) bg = gr[j];
+            }
           }
 #pragma unroll
           for (int mask = 16; mask > 0; mask >>= 1) {
             const float os = __shfl_xor(bs, mask);
             const int oi = __shfl_xor(bi, mask);
-            const int og = __shfl_xor(bg, mask);
+            const int og = LAB ? __shfl_xor(bg, mask) : -1;
             if (os > bs || (os == bs && oi < bi)) bs = os, bi = oi, bg = og;
           }
           if (col == 0 && m < M_eff) {
@@ -443,55 +452,11 @@ __global__ __launch_bounds__(256, (TM * TN == 1 ? (BK == 16 ? 6 : 4) : TM * TN =
             p.cand_i[o] = (bs == -INFINITY) ? -1 : bi;
           }
 #pragma unroll
-          for (int j = 0; j < TN; ++j)
-            if (bn0 + j * 32 + col == bi || (bg >= 0 && gr[j] == bg)) acc[i][j][r] = -INFINITY;
-        }
-      }
-    }
-    return;
-  }
-
-  if constexpr (EPI == 1) {
-    // ---- fused per-tile top-k (match path): the tile's scores never leave registers.
-    // A row's BN scores sit in the 32 lanes of one wave half x TN registers; each
-    // round picks the (score desc, id asc) maximum with a 5-step butterfly and
-    // retires it.  Candidates go to cand[m][tile_n][kk]; a merge kernel finishes.
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      const bool nok = (bn0 + j * 32 + col) < p.N;
-      const float ws = (PREC == 1 && p.wscale != nullptr && nok) ? p.wscale[bn0 + j * 32 + col] * p.a_unmul : p.a_unmul;
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = nok ? acc[i][j][r] * ws : -INFINITY;
-    }
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = bm0 + wave * 32 * TM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-        for (int kk = 0; kk < p.topk; ++kk) {
-          float bs = -INFINITY;
-          int bi = 0x7fffffff;
-#pragma unroll
           for (int j = 0; j < TN; ++j) {
-            const float v = acc[i][j][r];
-            if (v > bs) bs = v, bi = bn0 + j * 32 + col;
+            bool out = bn0 + j * 32 + col == bi;
+            if constexpr (LAB) out = out || (bg >= 0 && gr[j] == bg);
+            if (out) acc[i][j][r] = -INFINITY;
           }
-#pragma unroll
-          for (int mask = 16; mask > 0; mask >>= 1) {
-            const float os = __shfl_xor(bs, mask);
-            const int oi = __shfl_xor(bi, mask);
-            if (os > bs || (os == bs && oi < bi)) bs = os, bi = oi;
-          }
-          if (col == 0 && m < M_eff) {
-            const long o = ((long)m * g.tiles_n + tile_n) * p.topk + kk;
-            p.cand_s[o] = bs;
-            p.cand_i[o] = (bs == -INFINITY) ? -1 : bi;
-          }
-#pragma unroll
-          for (int j = 0; j < TN; ++j)
-            if (bn0 + j * 32 + col == bi) acc[i][j][r] = -INFINITY;
         }
       }
     }

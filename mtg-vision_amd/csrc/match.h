@@ -54,13 +54,10 @@ class Bank {
 };
 
 // merge of all-gathered per-shard candidates in the exchange format (gathered[R][b_total][k][2]: id, score bits) for
-// the queries [row0, row0 + b)
-void topk_merge_gathered_launch(const int64_t* gathered, int R, int b_total, int k, int row0, int b, float thr, int64_t* ids,
+// the queries [row0, row0 + b).  distinct: the candidates are in the labelled exchange format, and there is one result per
+// group >= 0: picking a candidate retires every other candidate of its group
+void topk_merge_gathered_launch(const int64_t* gathered, int R, int b_total, int k, int row0, int b, float thr, bool distinct, int64_t* ids,
                                 float* scores, hipStream_t s);
-// the same over candidates in the labelled exchange format, one result per group >= 0: picking a candidate retires every
-// other candidate of its group
-void topk_merge_gathered_distinct_launch(const int64_t* gathered, int R, int b_total, int k, int row0, int b, float thr, int64_t* ids,
-                                         float* scores, hipStream_t s);
 void topk_merge_launch_i64(float* cs, const int64_t* ci, int b, int ncand, int k, float thr, int64_t* ids, float* scores,
                            hipStream_t s);
 

@@ -42,61 +42,111 @@ __global__ __launch_bounds__(256) void packed_pads_kernel(long* __restrict__ pac
   if (i < slots) store_result(packed, i, -1, -INFINITY, -1);
 }
 
-// DISTINCT (labelled matches, Bank::topk_labelled): candidate ids are bank rows, so a candidate's group is groups[id];
-// after a pick every candidate of the winner's group (>= 0) is retired with it.  The candidate ranges dedupe too
-// (gemm_sp_kernel.h SP_EPI_TOPK_LABELS, gemm_kernel.h EPI 3): a merge-only dedupe would miss rows hidden inside a range.
+// ---------------------------------------------------------------------------
+// The one selection step and the one merge body of every top-k merge.  The contract, on a single bank and across
+// shards alike (same ids, same score bits): order by score descending, then id ascending; an id < 0 is a pad and never
+// takes part; the threshold is applied last - a representative below it becomes a pad and is not replaced; a picked
+// group >= 0 retires its other candidates; picks never depend on which rank a candidate came from.
+// ---------------------------------------------------------------------------
+template <typename IdT>
+__device__ __forceinline__ bool better(float v, IdT i, float bs, IdT bi) {
+  return v > bs || (v == bs && i < bi);
+}
+
+// a thread's proposal rule: candidate (v, i) at position p replaces the thread's best so far unless it is a pad (i < 0)
+// or retired (-inf)
+template <typename IdT>
+__device__ __forceinline__ void propose(float v, IdT i, int p, float& bs, IdT& bi, int& bp) {
+  if (i >= 0 && v > -INFINITY && better(v, i, bs, bi)) bs = v, bi = i, bp = p;
+}
+
+// Block selection: every thread hands in its best (score, id, position), position < 0 for none; a 256-thread LDS tree
+// leaves the block's winner in rs[0], ri[0], rp[0] (rp[0] < 0: nothing left), visible to every thread on return.
+// CONTAINS BARRIERS: call it from block-uniform control flow only, and put a barrier between the last read of the
+// winner and the next call, which overwrites it.
+template <typename IdT>
+__device__ __forceinline__ void block_pick(float bs, IdT bi, int bp, float* rs, IdT* ri, int* rp, int tid) {
+  rs[tid] = bs, ri[tid] = bi, rp[tid] = bp;
+  __syncthreads();
+  for (int st = 128; st > 0; st >>= 1) {
+    if (tid < st) {
+      const float os = rs[tid + st];
+      const IdT oi = ri[tid + st];
+      const int op = rp[tid + st];
+      if (op >= 0 && (rp[tid] < 0 || better(os, oi, rs[tid], ri[tid]))) rs[tid] = os, ri[tid] = oi, rp[tid] = op;
+    }
+    __syncthreads();
+  }
+}
+
+// The k rounds of a merge over the candidates of one query: pick, apply the threshold, emit, retire the winner - with
+// DISTINCT the winner's whole group, if it has one (>= 0).  View: n candidates with score(p), id(p), group(p) (read with
+// DISTINCT only) and retire(p); LAZY_ID views keep their ids far away, so an id is read only where its candidate leads
+// or ties.  emit(kk, ok, id, score) writes result kk; !ok: a pad.  CONTAINS BARRIERS, like block_pick.
+template <bool DISTINCT, typename View, typename Emit>
+__device__ __forceinline__ void merge_rounds(View c, int k, float thr, Emit emit) {
+  __shared__ float rs[256];
+  __shared__ long ri[256];
+  __shared__ int rp[256];
+  const int tid = threadIdx.x;
+  for (int kk = 0; kk < k; ++kk) {
+    float bs = -INFINITY;
+    long bi = 0x7fffffffffffffffL;
+    int bp = -1;
+    for (int p = tid; p < c.n; p += 256) {
+      const float v = c.score(p);
+      if (View::LAZY_ID && !(v > -INFINITY && v >= bs)) continue;
+      propose(v, c.id(p), p, bs, bi, bp);
+    }
+    block_pick(bs, bi, bp, rs, ri, rp, tid);
+    const int wp = rp[0];  // the winner is overwritten only after the barrier below
+    // score_threshold (qdrant.py:83,93): candidates below it are not results - id -1 / score -inf pads, like a bank with
+    // fewer than k rows.  It comes last: a representative below it is a pad, not replaced.
+    if (tid == 0) emit(kk, wp >= 0 && rs[0] >= thr, ri[0], rs[0]);
+    if (wp >= 0) {
+      int wg = -1;
+      if constexpr (DISTINCT) wg = c.group(wp);
+      if (wg >= 0) {
+        for (int p = tid; p < c.n; p += 256)
+          if (c.group(p) == wg) c.retire(p);  // the winner with its group
+      } else if (tid == 0) {
+        c.retire(wp);
+      }
+    }
+    __syncthreads();
+  }
+}
+
+// Candidates in HBM, ids are bank rows: a candidate's group is groups[id] (a pad has none).
+template <typename IdT>
+struct HbmCandidates {
+  static constexpr bool LAZY_ID = false;
+  float* __restrict__ s;
+  const IdT* __restrict__ ids;
+  const int* __restrict__ groups;
+  int n;
+  __device__ __forceinline__ float score(int p) const { return s[p]; }
+  __device__ __forceinline__ long id(int p) const { return (long)ids[p]; }
+  __device__ __forceinline__ int group(int p) const { return ids[p] >= 0 ? groups[ids[p]] : -1; }
+  __device__ __forceinline__ void retire(int p) const { s[p] = -INFINITY; }
+};
+
+// DISTINCT (labelled matches, Bank::topk_labelled): after a pick every candidate of the winner's group (>= 0) is retired
+// with it.  The candidate ranges dedupe too (gemm_sp_kernel.h SP_EPI_TOPK_LABELS, gemm_kernel.h EPI 3): a merge-only
+// dedupe would miss rows hidden inside a range.
 // PACK_GROUP: out_ids is the labelled exchange format (out_scores is not read).
 template <typename IdT, bool DISTINCT = false, bool PACK_GROUP = false>
 __global__ __launch_bounds__(256) void topk_merge_kernel(float* __restrict__ cs, const IdT* __restrict__ ci, int ncand, int k,
                                                         long id_base, float thr, long* __restrict__ out_ids,
                                                         float* __restrict__ out_scores, const int* __restrict__ groups = nullptr) {
-  __shared__ float rs[256];
-  __shared__ long ri[256];
-  __shared__ int rp[256];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  float* s = cs + (long)b * ncand;
-  const IdT* id = ci + (long)b * ncand;
-  for (int kk = 0; kk < k; ++kk) {
-    float bs = -INFINITY;
-    long bi = 0x7fffffffffffffffL;
-    int bp = -1;
-    for (int p = tid; p < ncand; p += 256) {
-      const float v = s[p];
-      const long i = (long)id[p];
-      if (i >= 0 && v > -INFINITY && (v > bs || (v == bs && i < bi))) bs = v, bi = i, bp = p;
-    }
-    rs[tid] = bs, ri[tid] = bi, rp[tid] = bp;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-      if (tid < st) {
-        const float os = rs[tid + st];
-        const long oi = ri[tid + st];
-        const int op = rp[tid + st];
-        if (op >= 0 && (rp[tid] < 0 || os > rs[tid] || (os == rs[tid] && oi < ri[tid]))) rs[tid] = os, ri[tid] = oi, rp[tid] = op;
-      }
-      __syncthreads();
-    }
-    if (tid == 0) {
-      // score_threshold (qdrant.py:83,93): candidates below it are not results - id -1 / score -inf pads, like a
-      // bank with fewer than k rows
-      const bool ok = rp[0] >= 0 && rs[0] >= thr;
-      if constexpr (PACK_GROUP)
-        store_result(out_ids, (long)b * k + kk, ok ? ri[0] + id_base : -1, ok ? rs[0] : -INFINITY, ok ? groups[ri[0]] : -1);
-      else
-        store_result(out_ids, out_scores, (long)b * k + kk, ok ? ri[0] + id_base : -1, ok ? rs[0] : -INFINITY);
-      if (rp[0] >= 0) s[rp[0]] = -INFINITY;  // retire
-    }
-    __syncthreads();
-    if constexpr (DISTINCT) {
-      const int wg = rp[0] >= 0 ? groups[id[rp[0]]] : -1;  // rp[0] is rewritten only after the barrier below
-      if (wg >= 0)
-        for (int p = tid; p < ncand; p += 256) {
-          const long i = (long)id[p];
-          if (i >= 0 && groups[i] == wg) s[p] = -INFINITY;
-        }
-      __syncthreads();
-    }
-  }
+  const int b = blockIdx.x;
+  const HbmCandidates<IdT> c{cs + (long)b * ncand, ci + (long)b * ncand, groups, ncand};
+  merge_rounds<DISTINCT>(c, k, thr, [&](int kk, bool ok, long id, float score) {
+    if constexpr (PACK_GROUP)
+      store_result(out_ids, (long)b * k + kk, ok ? id + id_base : -1, ok ? score : -INFINITY, ok ? groups[id] : -1);
+    else
+      store_result(out_ids, out_scores, (long)b * k + kk, ok ? id + id_base : -1, ok ? score : -INFINITY);
+  });
 }
 
 // ---------------------------------------------------------------------------
@@ -130,6 +180,12 @@ __global__ __launch_bounds__(256) void f32_to_f16_rows_kernel(const float* __res
 #pragma unroll
   for (int e = 0; e < 4; ++e) o[e] = (_Float16)a[e], o[4 + e] = (_Float16)b[e];
   *reinterpret_cast<sp_h8*>(out + i * 8) = o;
+}
+
+static void f32_to_f16_rows_launch(const float* in, const float* wscale, _Float16* out, long rows, int K, hipStream_t s) {
+  const long n8 = rows * (K / 8);
+  hipLaunchKernelGGL(f32_to_f16_rows_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, in, wscale, out, rows, K);
+  HIP_OK(hipGetLastError());
 }
 
 // exact score of (query, bank row): float64 sum of the f32 products, 64 lanes over k, fixed reduction order
@@ -209,18 +265,9 @@ __global__ __launch_bounds__(256) void rerank_kernel(const float* __restrict__ q
       const int i = ci[p];
       bool taken = false;
       for (int t = 0; t < rr; ++t) taken |= sel_p[t] == p;
-      if (!taken && i >= 0 && v > -INFINITY && (v > bs || (v == bs && i < bi))) bs = v, bi = i, bp = p;
+      if (!taken) propose(v, i, p, bs, bi, bp);
     }
-    rs[tid] = bs, ri[tid] = bi, rp[tid] = bp;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-      if (tid < st) {
-        const float os = rs[tid + st];
-        const int oi = ri[tid + st], op = rp[tid + st];
-        if (op >= 0 && (rp[tid] < 0 || os > rs[tid] || (os == rs[tid] && oi < ri[tid]))) rs[tid] = os, ri[tid] = oi, rp[tid] = op;
-      }
-      __syncthreads();
-    }
+    block_pick(bs, bi, bp, rs, ri, rp, tid);
     if (tid == 0) {
       sel_p[rr] = rp[0];
       if (rr == PRE_R - 1) s_aR = rp[0] >= 0 ? rs[0] : -INFINITY;  // bounds the reported candidates that were not selected
@@ -298,143 +345,72 @@ __global__ __launch_bounds__(256) void rerank_kernel(const float* __restrict__ q
     }
 }
 
-// Merge of the all-gathered per-shard candidates (mtgv/dist.py step 4): gathered[R][b_total][k][2] in the exchange
-// format above; block b merges the R * k candidates of query row0 + b (score desc, id asc; ids are global already).
+// Candidates of one query in the all-gathered exchange buffer (gathered[R][b_total][k][2], either exchange format):
+// LDS holds the score and, for distinct merges, the group (the high half of word 1) per candidate - 32 KiB at the
+// 4096-candidate cap, so with the reduction scratch the block stays inside the 64 KiB a launch gets without an opt-in;
+// ids stay in the gathered buffer (LAZY_ID).  A pad (id < 0) is staged as -inf whatever its score word says: it never
+// takes part.
+struct GatheredCandidates {
+  static constexpr bool LAZY_ID = true;
+  const long* __restrict__ query;  // candidate (rank 0, kk 0) of this query
+  long rank_stride;                // words from one rank's candidates to the next rank's
+  int k, n;
+  float* cs;
+  int* cg;
+  __device__ __forceinline__ const long* cand(int p) const {
+    const int r = p / k;
+    return query + r * rank_stride + (p - r * k) * 2;
+  }
+  template <bool DISTINCT>
+  __device__ __forceinline__ void stage(int tid) const {
+    for (int p = tid; p < n; p += 256) {
+      const long* e = cand(p);
+      const long w = e[1];
+      cs[p] = e[0] >= 0 ? __uint_as_float((unsigned)w) : -INFINITY;
+      if constexpr (DISTINCT) cg[p] = (int)(w >> 32);
+    }
+    __syncthreads();
+  }
+  __device__ __forceinline__ float score(int p) const { return cs[p]; }
+  __device__ __forceinline__ long id(int p) const { return cand(p)[0]; }
+  __device__ __forceinline__ int group(int p) const { return cg[p]; }
+  __device__ __forceinline__ void retire(int p) const { cs[p] = -INFINITY; }
+};
+
+// Merge of the all-gathered per-shard candidates (mtgv/dist.py step 4): block b merges the R * k candidates of query
+// row0 + b (ids are global already).  Plain: either exchange format, the high half of word 1 is ignored.  DISTINCT: the
+// labelled exchange format (Bank::topk_packed_labelled); after a pick every other candidate of the winner's group (>= 0)
+// is retired with it - two shards may each report a row of one card, and only the better one represents it.
+template <bool DISTINCT>
 __global__ __launch_bounds__(256) void topk_merge_gathered_kernel(const long* __restrict__ gathered, int R, int b_total, int k, int row0,
                                                                  float thr, long* __restrict__ out_ids, float* __restrict__ out_scores) {
   extern __shared__ __attribute__((aligned(16))) char gm_sm[];
-  const int ncand = R * k;
-  long* ci = reinterpret_cast<long*>(gm_sm);
-  float* cs = reinterpret_cast<float*>(gm_sm + (size_t)ncand * sizeof(long));
-  __shared__ float rs[256];
-  __shared__ long ri[256];
-  __shared__ int rp[256];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  for (int p = tid; p < ncand; p += 256) {
-    const int r = p / k, kk = p - r * k;
-    const long* e = gathered + (((long)r * b_total + row0 + b) * k + kk) * 2;
-    ci[p] = e[0];
-    cs[p] = __uint_as_float((unsigned)e[1]);
-  }
-  __syncthreads();
-  for (int kk = 0; kk < k; ++kk) {
-    float bs = -INFINITY;
-    long bi = 0x7fffffffffffffffL;
-    int bp = -1;
-    for (int p = tid; p < ncand; p += 256) {
-      const float v = cs[p];
-      const long i = ci[p];
-      if (i >= 0 && v > -INFINITY && (v > bs || (v == bs && i < bi))) bs = v, bi = i, bp = p;
-    }
-    rs[tid] = bs, ri[tid] = bi, rp[tid] = bp;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-      if (tid < st) {
-        const float os = rs[tid + st];
-        const long oi = ri[tid + st];
-        const int op = rp[tid + st];
-        if (op >= 0 && (rp[tid] < 0 || os > rs[tid] || (os == rs[tid] && oi < ri[tid]))) rs[tid] = os, ri[tid] = oi, rp[tid] = op;
-      }
-      __syncthreads();
-    }
-    if (tid == 0) {
-      const bool ok = rp[0] >= 0 && rs[0] >= thr;
-      out_scores[(long)b * k + kk] = ok ? rs[0] : -INFINITY;
-      out_ids[(long)b * k + kk] = ok ? ri[0] : -1;
-      if (rp[0] >= 0) cs[rp[0]] = -INFINITY;  // retire
-    }
-    __syncthreads();
-  }
+  const int b = blockIdx.x, ncand = R * k;
+  const GatheredCandidates c{gathered + (long)(row0 + b) * k * 2, (long)b_total * k * 2, k, ncand, reinterpret_cast<float*>(gm_sm),
+                             reinterpret_cast<int*>(gm_sm + (size_t)ncand * sizeof(float))};
+  c.stage<DISTINCT>(threadIdx.x);
+  merge_rounds<DISTINCT>(c, k, thr, [&](int kk, bool ok, long id, float score) {
+    store_result(out_ids, out_scores, (long)b * k + kk, ok ? id : -1, ok ? score : -INFINITY);
+  });
 }
 
-void topk_merge_gathered_launch(const int64_t* gathered, int R, int b_total, int k, int row0, int b, float thr, int64_t* ids,
+void topk_merge_gathered_launch(const int64_t* gathered, int R, int b_total, int k, int row0, int b, float thr, bool distinct, int64_t* ids,
                                 float* scores, hipStream_t s) {
   MTGV_CHECK(R > 0 && k > 0 && b > 0 && row0 >= 0 && row0 + b <= b_total, ERR_INVALID, "topk_merge_gathered: R=%d k=%d rows [%d, %d) of %d", R,
              k, row0, row0 + b, b_total);
   MTGV_CHECK((long)R * k <= 4096, ERR_INVALID, "topk_merge_gathered: %d x %d candidates per query (at most 4096)", R, k);
-  const size_t lds = (size_t)R * k * (sizeof(long) + sizeof(float));
-  hipLaunchKernelGGL(topk_merge_gathered_kernel, dim3(b), dim3(256), lds, s, (const long*)gathered, R, b_total, k, row0, thr, (long*)ids,
-                     scores);
+  const size_t lds = (size_t)R * k * (sizeof(float) + (distinct ? sizeof(int) : 0));
+  hipLaunchKernelGGL(distinct ? topk_merge_gathered_kernel<true> : topk_merge_gathered_kernel<false>, dim3(b), dim3(256), lds, s,
+                     (const long*)gathered, R, b_total, k, row0, thr, (long*)ids, scores);
   HIP_OK(hipGetLastError());
 }
 
-// The same merge for distinct matches over candidates in the labelled exchange format (Bank::topk_packed_labelled): a
-// candidate's group is the high half of its word 1, and after a pick every other candidate of the winner's group (>= 0)
-// is retired with it - two shards may each report a row of one card, and only the better one represents it.  LDS holds
-// (score, group) per candidate: 32 KiB at the 4096-candidate cap, so with the reduction scratch the block stays inside
-// the 64 KiB a launch gets without an opt-in; ids stay in the gathered buffer and are read where a candidate leads or
-// ties.  Picks are decided by (score desc, id asc) alone, never by which rank a candidate came from.
-__global__ __launch_bounds__(256) void topk_merge_gathered_distinct_kernel(const long* __restrict__ gathered, int R, int b_total, int k,
-                                                                          int row0, float thr, long* __restrict__ out_ids,
-                                                                          float* __restrict__ out_scores) {
-  extern __shared__ __attribute__((aligned(16))) char gd_sm[];
-  const int ncand = R * k;
-  float* cs = reinterpret_cast<float*>(gd_sm);
-  int* cg = reinterpret_cast<int*>(gd_sm + (size_t)ncand * sizeof(float));
-  __shared__ float rs[256];
-  __shared__ long ri[256];
-  __shared__ int rp[256];
-  const int b = blockIdx.x, tid = threadIdx.x;
-  auto cand = [&](int p) {
-    const int r = p / k;
-    return gathered + (((long)r * b_total + row0 + b) * k + (p - r * k)) * 2;
-  };
-  for (int p = tid; p < ncand; p += 256) {
-    const long* e = cand(p);
-    const long w = e[1];
-    cs[p] = e[0] >= 0 ? __uint_as_float((unsigned)w) : -INFINITY;  // a pad never takes part
-    cg[p] = (int)(w >> 32);
-  }
-  __syncthreads();
-  for (int kk = 0; kk < k; ++kk) {
-    float bs = -INFINITY;
-    long bi = 0x7fffffffffffffffL;
-    int bp = -1;
-    for (int p = tid; p < ncand; p += 256) {
-      const float v = cs[p];
-      if (v > -INFINITY && v >= bs) {
-        const long i = cand(p)[0];
-        if (v > bs || i < bi) bs = v, bi = i, bp = p;
-      }
-    }
-    rs[tid] = bs, ri[tid] = bi, rp[tid] = bp;
-    __syncthreads();
-    for (int st = 128; st > 0; st >>= 1) {
-      if (tid < st) {
-        const float os = rs[tid + st];
-        const long oi = ri[tid + st];
-        const int op = rp[tid + st];
-        if (op >= 0 && (rp[tid] < 0 || os > rs[tid] || (os == rs[tid] && oi < ri[tid]))) rs[tid] = os, ri[tid] = oi, rp[tid] = op;
-      }
-      __syncthreads();
-    }
-    if (tid == 0) {
-      const bool ok = rp[0] >= 0 && rs[0] >= thr;  // the threshold comes last: a representative below it is a pad, not replaced
-      out_scores[(long)b * k + kk] = ok ? rs[0] : -INFINITY;
-      out_ids[(long)b * k + kk] = ok ? ri[0] : -1;
-    }
-    const int wp = rp[0];  // rp[0] is rewritten only after the barrier below
-    if (wp >= 0) {
-      const int wg = cg[wp];
-      if (wg >= 0) {
-        for (int p = tid; p < ncand; p += 256)
-          if (cg[p] == wg) cs[p] = -INFINITY;  // the winner with its group
-      } else if (tid == 0) {
-        cs[wp] = -INFINITY;  // retire
-      }
-    }
-    __syncthreads();
-  }
-}
-
-void topk_merge_gathered_distinct_launch(const int64_t* gathered, int R, int b_total, int k, int row0, int b, float thr, int64_t* ids,
-                                         float* scores, hipStream_t s) {
-  MTGV_CHECK(R > 0 && k > 0 && b > 0 && row0 >= 0 && row0 + b <= b_total, ERR_INVALID, "topk_merge_gathered: R=%d k=%d rows [%d, %d) of %d", R,
-             k, row0, row0 + b, b_total);
-  MTGV_CHECK((long)R * k <= 4096, ERR_INVALID, "topk_merge_gathered: %d x %d candidates per query (at most 4096)", R, k);
-  const size_t lds = (size_t)R * k * (sizeof(float) + sizeof(int));
-  hipLaunchKernelGGL(topk_merge_gathered_distinct_kernel, dim3(b), dim3(256), lds, s, (const long*)gathered, R, b_total, k, row0, thr,
-                     (long*)ids, scores);
+// the merge of a bank's own candidates (ids are bank rows; groups: the bank's, read with distinct or pack_group only)
+static void local_merge_launch(bool distinct, bool pack_group, float* cs, const int* ci, int b, int ncand, int k, int64_t id_base, float thr,
+                               int64_t* ids, float* scores, const int* groups, hipStream_t s) {
+  const auto kernel = pack_group ? (distinct ? topk_merge_kernel<int, true, true> : topk_merge_kernel<int, false, true>)
+                                 : (distinct ? topk_merge_kernel<int, true> : topk_merge_kernel<int>);
+  hipLaunchKernelGGL(kernel, dim3(b), dim3(256), 0, s, cs, ci, ncand, k, (long)id_base, thr, (long*)ids, scores, groups);
   HIP_OK(hipGetLastError());
 }
 
@@ -473,10 +449,7 @@ void Bank::refresh_hi(int64_t row0, int64_t rows, hipStream_t s) {
   hi_.ensure((size_t)cap_ * dim_ / 2 + 8);
   const float* wsc = nullptr;
   if (!operand_sp8(vecs_.p + (size_t)row0 * dim_, dim_, nullptr, &wsc)) return;
-  const long n8 = (long)rows * (dim_ / 8);
-  hipLaunchKernelGGL(f32_to_f16_rows_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, vecs_.p + (size_t)row0 * dim_, wsc,
-                     reinterpret_cast<_Float16*>(hi_.p) + (size_t)row0 * dim_, (long)rows, dim_);
-  HIP_OK(hipGetLastError());
+  f32_to_f16_rows_launch(vecs_.p + (size_t)row0 * dim_, wsc, reinterpret_cast<_Float16*>(hi_.p) + (size_t)row0 * dim_, (long)rows, dim_, s);
 }
 
 int64_t Bank::prepass_fallbacks() const {
@@ -500,10 +473,7 @@ void Bank::topk_prepass(const float* q, int b, int k, int64_t id_base, float thr
   cand_s_.ensure((size_t)b * ncand);
   cand_i_.ensure((size_t)b * ncand);
   l2norm_rows_launch(q, qn_.p, b, dim_, s);
-  const long n8 = (long)b * (dim_ / 8);
-  hipLaunchKernelGGL(f32_to_f16_rows_kernel, dim3((unsigned)((n8 + 255) / 256)), dim3(256), 0, s, qn_.p, (const float*)nullptr,
-                     reinterpret_cast<_Float16*>(qhi_.p), (long)b, dim_);
-  HIP_OK(hipGetLastError());
+  f32_to_f16_rows_launch(qn_.p, nullptr, reinterpret_cast<_Float16*>(qhi_.p), (long)b, dim_, s);
   const float* wsc = nullptr;
   MTGV_CHECK(operand_sp8(vecs_.p, dim_, nullptr, &wsc), ERR_RUNTIME, "bank: row scales missing");
   int sl = 0;
@@ -633,28 +603,22 @@ void Bank::topk_one_pass(const float* q, int b, int k, int64_t id_base, float th
   g.cand_i = reinterpret_cast<int*>(cand_i_.p);
   g.topk = kt;
   gemm_launch(g, s);
-  if (labelled && scores == nullptr) {  // the labelled exchange format: every result with its row's group
-    if (distinct)
-      hipLaunchKernelGGL((topk_merge_kernel<int, true, true>), dim3(b), dim3(256), 0, s, cand_s_.p, (const int*)cand_i_.p, (int)ncand, k,
-                         (long)id_base, thr, (long*)ids, scores, g.col_groups);
-    else
-      hipLaunchKernelGGL((topk_merge_kernel<int, false, true>), dim3(b), dim3(256), 0, s, cand_s_.p, (const int*)cand_i_.p, (int)ncand, k,
-                         (long)id_base, thr, (long*)ids, scores, g.col_groups);
-  } else if (labelled && distinct)
-    hipLaunchKernelGGL((topk_merge_kernel<int, true>), dim3(b), dim3(256), 0, s, cand_s_.p, (const int*)cand_i_.p, (int)ncand, k,
-                       (long)id_base, thr, (long*)ids, scores, g.col_groups);
-  else
-    hipLaunchKernelGGL((topk_merge_kernel<int>), dim3(b), dim3(256), 0, s, cand_s_.p, (const int*)cand_i_.p, (int)ncand, k,
-                       (long)id_base, thr, (long*)ids, scores, (const int*)nullptr);
-  HIP_OK(hipGetLastError());
+  // labelled with scores == nullptr: the labelled exchange format, every result with its row's group
+  local_merge_launch(labelled && distinct, labelled && scores == nullptr, cand_s_.p, (const int*)cand_i_.p, b, (int)ncand, k, id_base, thr,
+                     ids, scores, g.col_groups, s);
+}
+
+// what every Bank::topk* entry checks first; labels_ok: a labelled entry got masks or distinct
+static void check_topk_args(int b, int k, bool tensors_ok, bool labels_ok = true) {
+  MTGV_CHECK(b > 0 && k > 0 && k <= 65536, ERR_INVALID, "bank: b=%d k=%d (k must be in [1,65536])", b, k);
+  MTGV_CHECK(tensors_ok, ERR_INVALID, "bank: null tensor");
+  MTGV_CHECK(labels_ok, ERR_INVALID, "bank: a labelled match needs masks or distinct");
 }
 
 // Labelled match: always the one-pass kernel with the labelled epilogue (the fp16 pre-pass's bound does not cover labels).
 void Bank::topk_labelled(const float* q, int b, int k, int64_t id_base, float thr, const uint64_t* masks, bool distinct, int64_t* ids,
                          float* scores, hipStream_t s) {
-  MTGV_CHECK(b > 0 && k > 0 && k <= 65536, ERR_INVALID, "bank: b=%d k=%d (k must be in [1,65536])", b, k);
-  MTGV_CHECK(q != nullptr && ids != nullptr && scores != nullptr, ERR_INVALID, "bank: null tensor");
-  MTGV_CHECK(masks != nullptr || distinct, ERR_INVALID, "bank: a labelled match needs masks or distinct");
+  check_topk_args(b, k, q != nullptr && ids != nullptr && scores != nullptr, masks != nullptr || distinct);
   MTGV_CHECK(size_ > 0, ERR_RUNTIME, "bank is empty");
   ensure_labels();  // (first labelled call on a bank without labels: allocates and synchronises once)
   topk_one_pass(q, b, k, id_base, thr, true, masks, distinct, ids, scores, s);
@@ -665,9 +629,7 @@ void Bank::topk_labelled(const float* q, int b, int k, int64_t id_base, float th
 // others waiting in the collective.
 void Bank::topk_packed_labelled(const float* q, int b, int k, int64_t id_base, const uint64_t* masks, bool distinct, int64_t* packed,
                                 hipStream_t s) {
-  MTGV_CHECK(b > 0 && k > 0 && k <= 65536, ERR_INVALID, "bank: b=%d k=%d (k must be in [1,65536])", b, k);
-  MTGV_CHECK(q != nullptr && packed != nullptr, ERR_INVALID, "bank: null tensor");
-  MTGV_CHECK(masks != nullptr || distinct, ERR_INVALID, "bank: a labelled match needs masks or distinct");
+  check_topk_args(b, k, q != nullptr && packed != nullptr, masks != nullptr || distinct);
   if (size_ == 0) {
     const long slots = (long)b * k;
     hipLaunchKernelGGL(packed_pads_kernel, dim3((unsigned)((slots + 255) / 256)), dim3(256), 0, s, (long*)packed, slots);
@@ -679,8 +641,7 @@ void Bank::topk_packed_labelled(const float* q, int b, int k, int64_t id_base, c
 }
 
 void Bank::topk(const float* q, int b, int k, int64_t id_base, float thr, int64_t* ids, float* scores, hipStream_t s) {
-  MTGV_CHECK(b > 0 && k > 0 && k <= 65536, ERR_INVALID, "bank: b=%d k=%d (k must be in [1,65536])", b, k);
-  MTGV_CHECK(q != nullptr && ids != nullptr, ERR_INVALID, "bank: null tensor");  // scores == nullptr: exchange format in ids (store_result)
+  check_topk_args(b, k, q != nullptr && ids != nullptr);  // scores == nullptr: exchange format in ids (store_result)
   MTGV_CHECK(size_ > 0, ERR_RUNTIME, "bank is empty");
   if (prepass_ok(b, k)) {
     topk_prepass(q, b, k, id_base, thr, ids, scores, s);

@@ -82,19 +82,17 @@ def sharded_topk(q_local: torch.Tensor, k: int, local_topk: Callable, merge: Cal
         return local_topk(q_local, k, filter=masks_local, distinct=distinct) if labelled else local_topk(q_local, k)
     world, rank = dist.get_world_size(group), dist.get_rank(group)
     b_local = q_local.shape[0]
-    if labelled:
-        assert local_topk_packed is not None and merge_gathered is not None, "the labelled exchange needs local_topk_packed and merge_gathered"
-        q_all = _all_gather_cat(q_local, group).view(world * b_local, -1)
-        masks_all = None
-        if masks_local is not None:
-            assert masks_local.dtype == torch.int64 and tuple(masks_local.shape) == (b_local, 3), f"masks_local: {tuple(masks_local.shape)} {masks_local.dtype}"
-            masks_all = _all_gather_cat(masks_local, group).view(world * b_local, 3)
-        packed = local_topk_packed(q_all, k, filter=masks_all, distinct=distinct)
-        return merge_gathered(_all_gather_cat(packed, group), rank * b_local, b_local, k, distinct=distinct)
+    assert not labelled or (local_topk_packed is not None and merge_gathered is not None), "the labelled exchange needs local_topk_packed and merge_gathered"
     if local_topk_packed is not None and merge_gathered is not None:
         q_all = _all_gather_cat(q_local, group).view(world * b_local, -1)  # a view of the collective's output
-        packed = local_topk_packed(q_all, k)
-        return merge_gathered(_all_gather_cat(packed, group), rank * b_local, b_local, k)
+        local_kw, merge_kw = {}, {}  # the label keywords are passed only when labelled: the unlabelled calls stay as they were
+        if labelled:
+            local_kw, merge_kw = {"filter": None, "distinct": distinct}, {"distinct": distinct}
+            if masks_local is not None:
+                assert masks_local.dtype == torch.int64 and tuple(masks_local.shape) == (b_local, 3), f"masks_local: {tuple(masks_local.shape)} {masks_local.dtype}"
+                local_kw["filter"] = _all_gather_cat(masks_local, group).view(world * b_local, 3)
+        packed = local_topk_packed(q_all, k, **local_kw)
+        return merge_gathered(_all_gather_cat(packed, group), rank * b_local, b_local, k, **merge_kw)
     q_all = _all_gather_cat(q_local, group).reshape(world * b_local, -1)
     ids, scores = local_topk(q_all, k)
     # one message: [..., 0] = id, [..., 1] = the score's float32 bit pattern

@@ -184,6 +184,51 @@ def test_candidate_cap():
             merge_gathered(torch.zeros((3, 1, 1366, 2), dtype=torch.int64, device="cuda"), 0, 1, 1366, distinct=distinct)
 
 
+def _tied_candidates(k, R=3, b=2):
+    """(R, b, k, 2) packed candidates: distinct ids, scores on a grid of eight values (exact ties are common), every group
+    -1, about 5 % pads - two of them placed by hand per query, one of which keeps a finite score word (2.0, above every real
+    score) that no merge may look at"""
+    rng = np.random.default_rng(11)
+    ids = rng.permutation(10 * R * b * k)[: R * b * k].reshape(R, b, k).astype(np.int64)
+    sc = rng.integers(0, 8, (R, b, k)).astype(np.float32) / 8
+    ids[rng.random((R, b, k)) < 0.05] = -1
+    ids[0, :, 1] = ids[R - 1, :, k - 1] = -1
+    packed = D.pack(ids, sc, -1)
+    loud = ids < 0
+    loud[R - 1] = False  # the last rank's pads stay the canonical pad word
+    packed[..., 1].view(np.uint64)[loud] = np.uint64((0xFFFFFFFF << 32) | int(np.float32(2.0).view(np.uint32)))
+    assert loud.any() and (ids[R - 1] < 0).any()
+    return packed
+
+
+@pytest.mark.parametrize("k", [5, 100])
+def test_every_merge_form_gives_one_answer(k):
+    """One candidate set, one answer (ids and score bits) through every form of the merge - merge_topk on the flattened
+    candidates (64-bit ids in HBM), the plain gathered merge and the distinct gathered merge with every group -1 - with and
+    without a threshold that cuts inside the list, and that answer is dist_labels_common.merge's.  R * k = 15 candidates
+    are fewer than one per thread; 300 make the strided scan take a second, partial pass."""
+    from mtgv.matcher import merge_gathered, merge_topk
+
+    R, b = 3, 2
+    packed = _tied_candidates(k, R, b)
+    want = D.merge(packed, 0, b, k, False)
+    assert len(np.unique(want[1][0])) < k, "no exact tie among the results: choose another seed"
+    thr = float(want[1][0, k // 2])
+    g = torch.from_numpy(packed).cuda()
+    flat = g.permute(1, 0, 2, 3).reshape(b, R * k, 2)
+    flat_i, flat_s = flat[..., 0].contiguous(), flat[..., 1].to(torch.int32).contiguous().view(torch.float32)
+    for t in (None, thr):
+        want_i, want_s = D.merge(packed, 0, b, k, False, t)
+        dis_i, dis_s = D.merge(packed, 0, b, k, True, t)
+        assert (dis_i == want_i).all() and (dis_s.view(np.int32) == want_s.view(np.int32)).all()
+        if t is not None:
+            assert (want_i[0] >= 0).any() and (want_i[0] < 0).any(), "the threshold must cut inside the list"
+        want_t = (torch.from_numpy(want_i).cuda(), torch.from_numpy(want_s).cuda())
+        _same(merge_topk(flat_s, flat_i, k, t), want_t, f"merge_topk k={k} thr={t}")
+        _same(merge_gathered(g, 0, b, k, t, distinct=False), want_t, f"plain gathered k={k} thr={t}")
+        _same(merge_gathered(g, 0, b, k, t, distinct=True), want_t, f"distinct gathered k={k} thr={t}")
+
+
 def test_empty_shard_and_missing_labels():
     from mtgv import native
     from mtgv.matcher import Matcher, merge_gathered
