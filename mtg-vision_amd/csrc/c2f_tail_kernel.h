@@ -72,11 +72,7 @@ struct C2fTailDev {
 
 // Blocks go round the eight XCDs: each XCD gets a contiguous run of tiles, so the halo lines that rows of tiles share
 // are read into one L2 (gemm_sp_kernel's tile order).
-__device__ __forceinline__ int c2f_tile_of_block() {
-  const int nwg = gridDim.x, b = blockIdx.x;
-  const int q = nwg >> 3, rr = nwg & 7, x = b & 7;
-  return (x < rr ? x * (q + 1) : rr * (q + 1) + (x - rr) * q) + (b >> 3);
-}
+__device__ __forceinline__ int c2f_tile_of_block() { return xcd_block_order<int>(blockIdx.x, gridDim.x); }
 
 // A lane's quad of activated outputs (columns 8 gq + 4 h + 0..3 of its pixel: the MFMA accumulator layout) split as the
 // SP8_OUT epilogue splits it (sp8_split4), written as the lane's 8 bytes of the chunk's hi piece and of its lo piece.

@@ -20,6 +20,15 @@ namespace mtgv {
 
 typedef float f32x4 __attribute__((ext_vector_type(4)));
 
+// XCD-aware block order.  The hardware deals blocks to the eight XCDs round robin (block b runs on XCD b % 8); this maps
+// b to a work index such that the blocks of one XCD walk a contiguous run of the nwg work items, so what neighbouring
+// items share (halo rows, an A row-panel) is fetched into one L2 and not into all eight.  T: the caller's index type.
+template <typename T>
+__device__ __forceinline__ T xcd_block_order(T b, T nwg) {
+  const T q = nwg >> 3, r = nwg & 7, x = b & 7;
+  return (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
+}
+
 // ---- exact unsigned division by a runtime constant (n * d < 2^40) ----
 struct FastDiv {
   uint64_t mul;  // ceil(2^40 / d)

@@ -144,7 +144,7 @@ __global__ __launch_bounds__(C* SPLIT) void dwconv7_ln_image_kernel(const float*
   for (int i = 0; i < PG; ++i) v[i] = *reinterpret_cast<const sp_f4*>(img + (g * PG + i) * C + q4 * 4);
   __syncthreads();  // every output is in its new owner's registers: the same LDS now holds the partial sums
 #pragma unroll
-  for (int i = 0; i < PG; ++i) part[(g * PG + i) * PITCH + q4] = (v[i][0] + v[i][1]) + (v[i][2] + v[i][3]);
+  for (int i = 0; i < PG; ++i) part[(g * PG + i) * PITCH + q4] = quad_sum(v[i]);
   __syncthreads();
   const int rp = wave * PPW + lane;  // lane < PPW of every wave reduces one pixel
   const bool reducer = lane < PPW && rp < PT;
@@ -167,10 +167,7 @@ __global__ __launch_bounds__(C* SPLIT) void dwconv7_ln_image_kernel(const float*
   if (reducer) smean[rp] = quad_chain() / (float)C;
   __syncthreads();
 #pragma unroll
-  for (int i = 0; i < PG; ++i) {
-    const sp_f4 d = v[i] - smean[g * PG + i];
-    part[(g * PG + i) * PITCH + q4] = (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
-  }
+  for (int i = 0; i < PG; ++i) part[(g * PG + i) * PITCH + q4] = quad_sumsq(v[i] - smean[g * PG + i]);
   __syncthreads();
   if (reducer) srstd[rp] = 1.0f / sqrtf(quad_chain() / (float)C + eps);
   __syncthreads();

@@ -93,12 +93,7 @@ __global__ __launch_bounds__(256, (TM * TN == 1 ? (BK == 16 ? 6 : 4) : TM * TN =
 
   // XCD-aware tile order: blocks that share an XCD (equal blockIdx % 8) walk a
   // contiguous run of tiles, n fastest, so an A row-panel is fetched once per L2.
-  int L;
-  {
-    const int nwg = gridDim.x, b = blockIdx.x;
-    const int q = nwg >> 3, r = nwg & 7, x = b & 7;
-    L = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
-  }
+  const int L = xcd_block_order<int>(blockIdx.x, gridDim.x);
   const int tile_n = L % g.tiles_n, tile_m = L / g.tiles_n;
   const int bm0 = tile_m * BM, bn0 = tile_n * BN;
   if (bm0 >= M_eff) return;  // whole tile beyond this batch's rows (uniform per block)

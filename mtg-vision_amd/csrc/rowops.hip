@@ -32,7 +32,7 @@ __global__ __launch_bounds__(256) void ln_rows_kernel(const float* __restrict__ 
     f32x4 t = {0.f, 0.f, 0.f, 0.f};
     if (rok && c4 < c4n) t = *reinterpret_cast<const f32x4*>(x + c4 * 4);
     v[i] = t;
-    sum += (t[0] + t[1]) + (t[2] + t[3]);
+    sum += quad_sum(t);
   }
 #pragma unroll
   for (int m = G >> 1; m > 0; m >>= 1) sum += __shfl_xor(sum, m);
@@ -41,10 +41,7 @@ __global__ __launch_bounds__(256) void ln_rows_kernel(const float* __restrict__ 
 #pragma unroll
   for (int i = 0; i < NV; ++i) {
     const int c4 = sub + i * G;
-    if (c4 < c4n) {
-      const f32x4 d = v[i] - mean;
-      sq += (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]);
-    }
+    if (c4 < c4n) sq += quad_sumsq(v[i] - mean);
   }
 #pragma unroll
   for (int m = G >> 1; m > 0; m >>= 1) sq += __shfl_xor(sq, m);
@@ -148,16 +145,9 @@ template <int TW>
 __global__ __launch_bounds__(256) void dwconv7_kernel(const float* __restrict__ in, const float* __restrict__ w49,
                                                      const float* __restrict__ bias, float* __restrict__ out, int N, int H, int W,
                                                      int C, int nstrips, long total) {
-  // XCD-aware block order: blocks that share an XCD (equal blockIdx % 8) walk a contiguous run of
-  // rows, so the 6 halo rows an output row shares with its neighbours are re-read from that XCD's L2
+  // XCD-aware block order: the 6 halo rows an output row shares with its neighbours are re-read from one XCD's L2
   // instead of being fetched again by every XCD (measured 3.3x the algorithmic reads without this).
-  long blk;
-  {
-    const long nwg = gridDim.x, b = blockIdx.x;
-    const long q = nwg >> 3, r = nwg & 7, x = b & 7;
-    blk = (x < r ? x * (q + 1) : r * (q + 1) + (x - r) * q) + (b >> 3);
-  }
-  const long idx = blk * 256 + threadIdx.x;
+  const long idx = xcd_block_order<long>(blockIdx.x, gridDim.x) * 256 + threadIdx.x;
   if (idx >= total) return;
   const int c4n = C >> 2;
   const int c4 = (int)(idx % c4n);

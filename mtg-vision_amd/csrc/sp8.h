@@ -88,4 +88,9 @@ __device__ __forceinline__ sp_h8 sp8_piece_from_quad(const sp_f4 x, int c4) {
   return __builtin_bit_cast(sp_h8, out);
 }
 
+// LayerNorm over channel quads (ln_rows_kernel, the dwconv7_ln row-group and whole-image kernels): every kernel that
+// must give the others' bits sums a quad, and a quad's squared deviations, in this association.
+__device__ __forceinline__ float quad_sum(const sp_f4 a) { return (a[0] + a[1]) + (a[2] + a[3]); }
+__device__ __forceinline__ float quad_sumsq(const sp_f4 d) { return (d[0] * d[0] + d[1] * d[1]) + (d[2] * d[2] + d[3] * d[3]); }
+
 }  // namespace mtgv
