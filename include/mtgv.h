@@ -655,6 +655,27 @@ typedef struct {
   int32_t fold;
 } mtgv_proto_tail;
 MTGV_API int mtgv_op_proto_tail(const mtgv_proto_tail* d, int32_t* folded, void* stream);
+/* The fused tail of a C2f block alone (version 112; Detector::csp_block runs the same launch, c2f_tail_kernel.h): the block's
+ * last bottleneck and its closing 1x1 conv as one launch on SP8 activations,
+ *   t = SiLU(w1 (*) y_last + b1), y_new = [y_last +] SiLU(w2 (*) t + b2), out = SiLU(w3 . [cat slices | y_new] + b3),
+ * both 3x3 convs stride 1 with zero padding 1 (t is zero outside the frame).  cat is an SP8 view of n images of h x w pixels,
+ * cat_ct floats per pixel: the 1 + nb slices of ch channels from channel cat_co on are read, y_last is the last of them; y_new
+ * is never stored, so cat needs no room for it.  Weights and biases are device f32: w1 and w2 [ch][3][3][ch], w3
+ * [cout][(2 + nb) ch].  out is an SP8 view, channels [out_co, out_co + cout) of out_ct floats per pixel.  There is a kernel
+ * for ch = 16 with nb = 1 (w a multiple of 32) and ch = 32 with nb = 1 or 2 (w a multiple of 16), cout = 2 ch, h a multiple
+ * of 8, h and w at least 80, channel counts and offsets in multiples of 8, 16-byte aligned pointers, every bias present,
+ * f16x3 operand mode.  Anything else is status 1 with nothing launched: the call never falls back to the three conv
+ * launches.  Synchronises the stream before it returns. */
+typedef struct {
+  const void* cat;
+  int32_t cat_ct, cat_co;
+  int32_t n, h, w, ch, nb, shortcut;
+  const float *w1, *b1, *w2, *b2, *w3, *b3;
+  int32_t cout;
+  void* out;
+  int32_t out_ct, out_co;
+} mtgv_c2f_tail;
+MTGV_API int mtgv_op_c2f_tail(const mtgv_c2f_tail* d, void* stream);
 /* The weights of that fold, on the host: we [4 (phase 2 a + b)][cout][2][2][c] and bias9 [9 (3 row class + column class;
  * 0 first, 1 inner, 2 last)][cout] from wt (c, mid, 2, 2), bt (mid), w2 [cout][3][3][mid], b2 [cout].  Sums in double,
  * rounded to float once.  Needs no device. */

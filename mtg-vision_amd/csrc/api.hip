@@ -7,6 +7,7 @@
 #include <algorithm>
 #include <mutex>
 
+#include "c2f_tail.h"
 #include "encoder.h"
 #include "match.h"
 #include "rowops.h"
@@ -103,7 +104,8 @@ MTGV_API const char* mtgv_last_error(void) { return last_error_cstr(); }
 // 109: mtgv_detector_cfg.arch = 12 (YOLO12), mtgv_op_area_attn
 // 110: mtgv_tracker_create_ex, MTGV_TRACKER_WIDE (256 tracks per stream, 64 cards per frame)
 // 111: mtgv_letterbox_ragged_u8, mtgv_warp_quads_src (crops from full-resolution source frames)
-MTGV_API int mtgv_version(void) { return 111; }
+// 112: mtgv_op_c2f_tail (the fused C2f tail as a single op)
+MTGV_API int mtgv_version(void) { return 112; }
 MTGV_API int mtgv_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -449,6 +451,26 @@ MTGV_API int mtgv_op_conv2d_ex(const mtgv_conv_ex* d, int32_t* path, void* strea
       }
     }
     gemm_launch(g, s);
+  });
+}
+MTGV_API int mtgv_op_c2f_tail(const mtgv_c2f_tail* d, void* stream) {
+  return guarded([&] {
+    MTGV_CHECK(d && d->cat && d->out && d->w1 && d->w2 && d->w3, ERR_INVALID, "c2f_tail: null argument");
+    MTGV_CHECK(d->n > 0 && d->h > 0 && d->w > 0 && d->ch > 0 && d->nb > 0 && d->cout > 0, ERR_INVALID, "c2f_tail: bad geometry");
+    hipStream_t s = (hipStream_t)stream;
+    const int k3 = (2 + d->nb) * d->ch;
+    ScopedWeights reg1(d->w1, d->ch, 9 * d->ch, s), reg2(d->w2, d->ch, 9 * d->ch, s), reg3(d->w3, d->cout, k3, s);
+    C2fTailArgs a;
+    a.cat = (const float*)d->cat, a.cat_ct = d->cat_ct, a.cat_co = d->cat_co, a.n_img = d->n, a.H = d->h, a.W = d->w;
+    a.ch = d->ch, a.nb = d->nb, a.shortcut = d->shortcut != 0;
+    a.w1 = d->w1, a.b1 = d->b1, a.w2 = d->w2, a.b2 = d->b2, a.w3 = d->w3, a.b3 = d->b3, a.cout = d->cout;
+    a.out = (float*)d->out, a.out_ct = d->out_ct, a.out_co = d->out_co;
+    // the fused launch or an error: the three launches it replaces are mtgv_op_conv2d_ex's to run
+    MTGV_CHECK(c2f_tail_ok(a), ERR_INVALID,
+               "c2f_tail: no fused kernel for ch=%d nb=%d cout=%d on %d x %d (cat %d/%d, out %d/%d, f16x3 mode, biases, alignment)", d->ch,
+               d->nb, d->cout, d->h, d->w, d->cat_ct, d->cat_co, d->out_ct, d->out_co);
+    c2f_tail_launch(a, s);
+    HIP_OK(hipStreamSynchronize(s));
   });
 }
 MTGV_API int mtgv_op_layernorm(const float* x_dev, const float* w_dev, const float* b_dev, float* out_dev, int64_t rows,

@@ -85,6 +85,17 @@ class ProtoTail(C.Structure):
     )
 
 
+class C2fTail(C.Structure):
+    """mtgv_c2f_tail: a C2f block's last bottleneck and closing 1x1 conv as the one fused launch (test surface)"""
+
+    _fields_ = (
+        [("cat", c_vp)]
+        + [(k, c_i32) for k in ("cat_ct", "cat_co", "n", "h", "w", "ch", "nb", "shortcut")]
+        + [(k, c_vp) for k in ("w1", "b1", "w2", "b2", "w3", "b3")]
+        + [("cout", c_i32), ("out", c_vp), ("out_ct", c_i32), ("out_co", c_i32)]
+    )
+
+
 class TrackerCfg(C.Structure):
     """mtgv_tracker_cfg (mtgv_version >= 104); zero in a policy field selects the reference's value"""
 
@@ -200,6 +211,7 @@ SIGNATURES = {
     "mtgv_op_stem_u8": (C.c_int, [c_vp, c_vp, c_vp, c_vp] + [c_i32] * 7 + [c_vp]),
     "mtgv_op_area_attn": (C.c_int, [c_vp, c_vp, c_vp] + [c_i32] * 5 + [c_vp, c_vp]),  # mtgv_version >= 109
     "mtgv_op_proto_tail": (C.c_int, [C.POINTER(ProtoTail), C.POINTER(c_i32), c_vp]),
+    "mtgv_op_c2f_tail": (C.c_int, [C.POINTER(C2fTail), c_vp]),  # mtgv_version >= 112
     "mtgv_op_proto_fold_compose": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mtgv_op_layernorm": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_f32, c_vp]),
     "mtgv_op_dwconv7": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
