@@ -10,9 +10,11 @@ namespace mtgv {
 namespace {
 // tile geometry of the instance that takes slices of ch channels
 struct TailGeom { int th, tw, win_bytes, lds; };
+template <class G>
+constexpr TailGeom geom_of() { return {G::TH, G::TW, G::WIN_PX * G::RB, G::LDS}; }
 bool tail_geom(int ch, TailGeom* t) {
-  if (ch == C2fTail16::CH) *t = {C2fTail16::TH, C2fTail16::TW, C2fTail16::WIN_PX * C2fTail16::RB, C2fTail16::LDS};
-  else if (ch == C2fTail32::CH) *t = {C2fTail32::TH, C2fTail32::TW, C2fTail32::WIN_PX * C2fTail32::RB, C2fTail32::LDS};
+  if (ch == C2fTail16::CH) *t = geom_of<C2fTail16>();
+  else if (ch == C2fTail32::CH) *t = geom_of<C2fTail32>();
   else return false;
   return true;
 }
