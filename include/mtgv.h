@@ -686,6 +686,19 @@ MTGV_API int mtgv_op_layernorm(const float* x_dev, const float* w_dev, const flo
 /* depthwise 7x7 pad 3; weight (49, c) tap-major */
 MTGV_API int mtgv_op_dwconv7(const float* x_dev, const float* w49_dev, const float* bias_dev, float* out_dev, int32_t n,
                              int32_t h, int32_t w, int32_t c, void* stream);
+/* The fused depthwise 7x7 (pad 3, + bias) and LayerNorm over C alone (version 113; the launch that opens every block
+ * of mtgv_op_block): NHWC x (n,h,w,c) f32, weight (49, c) tap-major, out (n,h,w,c) as f32 rows (out_fmt 0) or SP8 rows
+ * (out_fmt 1, c % 8 == 0).  Runs the fused launch and synchronises the stream; where no fused kernel takes the shape
+ * (c % 4 != 0, c > 1024, c / 4 below the strip width: 8 at w >= 8, 4 at w >= 4, else 2) or the format, status 1 and nothing launched -
+ * never mtgv_op_dwconv7 + mtgv_op_layernorm.  form receives {kind, TW, TH, WL} of the kernel that ran: kind 0 row groups
+ * (dwconv7_ln_rows_kernel<TW, TH, SP8, WL>), 1 row streaming (strip TW, TH rows a step), 2 whole image (TW = w, TH = the band
+ * height); WL = 0 for kinds 1 and 2. */
+MTGV_API int mtgv_op_dwconv7_ln(const float* x_dev, const float* w49_dev, const float* bias_dev, const float* ln_w_dev,
+                                const float* ln_b_dev, float* out_dev, int32_t n, int32_t h, int32_t w, int32_t c, float eps,
+                                int32_t out_fmt, int32_t form[4], void* stream);
+/* The form that call (and the encoder) would run at this shape, by the launcher's own rule; MTGV_DW_ROWS and
+ * MTGV_DW_IMAGE are read per call.  Status 1 for a shape the fused launch refuses.  Needs no device. */
+MTGV_API int mtgv_op_dwconv7_ln_form(int32_t n, int32_t h, int32_t w, int32_t c, int32_t form[4]);
 /* one ConvNeXt-V2 block on NHWC x (n,h,w,c): convnextv2.py:212-224.  params in reference layout
  * except dw weight (49,c).  ws_dev: workspace of mtgv_op_block_workspace_floats() floats. */
 MTGV_API int mtgv_op_block(const float* x_dev, float* out_dev, int32_t n, int32_t h, int32_t w, int32_t c, int32_t act,

@@ -105,7 +105,8 @@ MTGV_API const char* mtgv_last_error(void) { return last_error_cstr(); }
 // 110: mtgv_tracker_create_ex, MTGV_TRACKER_WIDE (256 tracks per stream, 64 cards per frame)
 // 111: mtgv_letterbox_ragged_u8, mtgv_warp_quads_src (crops from full-resolution source frames)
 // 112: mtgv_op_c2f_tail (the fused C2f tail as a single op)
-MTGV_API int mtgv_version(void) { return 112; }
+// 113: mtgv_op_dwconv7_ln, mtgv_op_dwconv7_ln_form (the fused depthwise 7x7 + LayerNorm as a single op, and its kernel form)
+MTGV_API int mtgv_version(void) { return 113; }
 MTGV_API int mtgv_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -485,6 +486,26 @@ MTGV_API int mtgv_op_dwconv7(const float* x_dev, const float* w49_dev, const flo
   return guarded([&] {
     MTGV_CHECK(x_dev && w49_dev && bias_dev && out_dev, ERR_INVALID, "null argument");
     dwconv7_launch(x_dev, w49_dev, bias_dev, out_dev, n, h, w, c, (hipStream_t)stream);
+  });
+}
+MTGV_API int mtgv_op_dwconv7_ln_form(int32_t n, int32_t h, int32_t w, int32_t c, int32_t form[4]) {
+  return guarded([&] {
+    MTGV_CHECK(form != nullptr, ERR_INVALID, "dwconv7_ln: null form");
+    MTGV_CHECK(n > 0 && h > 0 && w > 0 && c > 0, ERR_INVALID, "dwconv7_ln: bad geometry");
+    dwconv7_ln_form(n, h, w, c, form);
+  });
+}
+MTGV_API int mtgv_op_dwconv7_ln(const float* x_dev, const float* w49_dev, const float* bias_dev, const float* ln_w_dev,
+                                const float* ln_b_dev, float* out_dev, int32_t n, int32_t h, int32_t w, int32_t c, float eps,
+                                int32_t out_fmt, int32_t form[4], void* stream) {
+  return guarded([&] {
+    MTGV_CHECK(x_dev && w49_dev && bias_dev && ln_w_dev && ln_b_dev && out_dev && form, ERR_INVALID, "dwconv7_ln: null argument");
+    MTGV_CHECK(n > 0 && h > 0 && w > 0 && c > 0 && (out_fmt == 0 || out_fmt == 1), ERR_INVALID, "dwconv7_ln: bad geometry or format");
+    // the fused launch or an error: the unfused pair is mtgv_op_dwconv7 and mtgv_op_layernorm's to run
+    int32_t f[4];  // the plan the launch ran, from the launch itself
+    dwconv7_ln_launch(x_dev, w49_dev, bias_dev, ln_w_dev, ln_b_dev, out_dev, n, h, w, c, eps, (hipStream_t)stream, out_fmt, f);
+    HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+    memcpy(form, f, sizeof(f));  // (a refused call leaves it as it was)
   });
 }
 MTGV_API int64_t mtgv_op_block_workspace_floats(int32_t n, int32_t h, int32_t w, int32_t c) {

@@ -155,9 +155,16 @@ static void dwconv7_ln_rows_launch(const float* in, const float* w49, const floa
   HIP_OK(hipGetLastError());
 }
 
-template <bool SP8>
-static void dwconv7_ln_launch_fmt(const float* in, const float* w49, const float* bias, const float* ln_w, const float* ln_b,
-                                  float* out, int N, int H, int W, int C, float eps, hipStream_t s) {
+// The kernel form of a launch: kind, and the TW / TH / WL of the instantiation (the streaming form's strip and row step; the
+// whole-image form's full width and band height H / SPLIT; WL = 0 for both)
+enum DwLnKind : int { DWLN_ROWS = 0, DWLN_STREAM = 1, DWLN_IMAGE = 2 };
+struct DwLnPlan {
+  int kind, tw, th, wl;
+};
+
+// The one selection rule: which form runs a shape dwconv7_ln_supported admits (host only; the launch below, the block and
+// mtgv_op_dwconv7_ln_form all read it)
+static inline DwLnPlan dwconv7_ln_plan(int N, int H, int W, int C) {
   // Row-group forms (tools/micro/dwconv_rows_probe.hip, profiles/r03_dwconv_rows_probe.txt; all bit-identical to the
   // single-row form): 4-pixel strips x 3 rows with the tap table in LDS while table + partial sums fit the default
   // 64 KB window (C <= 192: 121.5 vs 144-155 us at 256 x 48 x 32 x 96, 60.9 vs 66.7 at 24 x 16 x 192), else 3 rows of the
@@ -176,30 +183,55 @@ static void dwconv7_ln_launch_fmt(const float* in, const float* w49, const float
   // MTGV_DW_IMAGE=0: never, =1: at any batch size (tests).
   const int image_mode = env_int("MTGV_DW_IMAGE", -1);  // read per call, like MTGV_DW_ROWS
   if (rows_on && image_mode != 0 && (N >= 128 || image_mode == 1)) {
-    if (C == 384 && H == 12 && W == 8) return dwconv7_ln_image_launch<384, 12, 8, 2, SP8>(in, w49, bias, ln_w, ln_b, out, N, eps, s);
-    if (C == 768 && H == 6 && W == 4) return dwconv7_ln_image_launch<768, 6, 4, 1, SP8>(in, w49, bias, ln_w, ln_b, out, N, eps, s);
+    if (C == 384 && H == 12 && W == 8) return {DWLN_IMAGE, 8, 6, 0};  // <384, 12, 8, SPLIT 2>
+    if (C == 768 && H == 6 && W == 4) return {DWLN_IMAGE, 4, 6, 0};   // <768, 6, 4, SPLIT 1>
   }
   if (rows_on && N >= 128) {
-    if (C == 96 && W == 32) return dwconv7_ln_stream_launch<96, 8, 4, 3, SP8>(in, w49, bias, ln_w, ln_b, out, N, H, 1, eps, s);
-    if (C == 192 && W == 16) return dwconv7_ln_stream_launch<192, 4, 4, 3, SP8>(in, w49, bias, ln_w, ln_b, out, N, H, 1, eps, s);
+    if (C == 96 && W == 32) return {DWLN_STREAM, 4, 3, 0};   // <96, G 8, 4, 3>
+    if (C == 192 && W == 16) return {DWLN_STREAM, 4, 3, 0};  // <192, G 4, 4, 3>
   }
   if (rows_on && W >= 4) {
-    if (dwconv7_ln_rows_lds_bytes(4, 3, true, C) <= 65536) dwconv7_ln_rows_launch<4, 3, SP8, true>(in, w49, bias, ln_w, ln_b, out, N, H, W, C, eps, s);
-    else if (W >= 8) dwconv7_ln_rows_launch<8, 3, SP8, false>(in, w49, bias, ln_w, ln_b, out, N, H, W, C, eps, s);
-    else dwconv7_ln_rows_launch<4, 3, SP8, false>(in, w49, bias, ln_w, ln_b, out, N, H, W, C, eps, s);
-    return;
+    if (dwconv7_ln_rows_lds_bytes(4, 3, true, C) <= 65536) return {DWLN_ROWS, 4, 3, 1};
+    return {DWLN_ROWS, W >= 8 ? 8 : 4, 3, 0};
   }
   // single-row form: the widest strip the width allows (dwconv7_ln_supported: C / 4 lanes of a strip cover its pixels)
-  if (W >= 8) dwconv7_ln_rows_launch<8, 1, SP8, false>(in, w49, bias, ln_w, ln_b, out, N, H, W, C, eps, s);
-  else if (W >= 4) dwconv7_ln_rows_launch<4, 1, SP8, false>(in, w49, bias, ln_w, ln_b, out, N, H, W, C, eps, s);
-  else dwconv7_ln_rows_launch<2, 1, SP8, false>(in, w49, bias, ln_w, ln_b, out, N, H, W, C, eps, s);
+  return {DWLN_ROWS, W >= 8 ? 8 : (W >= 4 ? 4 : 2), 1, 0};
 }
 
-// picks the kernel form for the shape and launches it; out_fmt 0: f32 rows, 1: SP8 rows
+// launches the instantiation the plan names
+template <bool SP8>
+static void dwconv7_ln_launch_fmt(const DwLnPlan& p, const float* in, const float* w49, const float* bias, const float* ln_w,
+                                  const float* ln_b, float* out, int N, int H, int W, int C, float eps, hipStream_t s) {
+  if (p.kind == DWLN_IMAGE) {
+    if (C == 384) return dwconv7_ln_image_launch<384, 12, 8, 2, SP8>(in, w49, bias, ln_w, ln_b, out, N, eps, s);
+    return dwconv7_ln_image_launch<768, 6, 4, 1, SP8>(in, w49, bias, ln_w, ln_b, out, N, eps, s);
+  }
+  if (p.kind == DWLN_STREAM) {
+    if (C == 96) return dwconv7_ln_stream_launch<96, 8, 4, 3, SP8>(in, w49, bias, ln_w, ln_b, out, N, H, 1, eps, s);
+    return dwconv7_ln_stream_launch<192, 4, 4, 3, SP8>(in, w49, bias, ln_w, ln_b, out, N, H, 1, eps, s);
+  }
+  switch (p.tw * 100 + p.th * 10 + p.wl) {
+    case 431: return dwconv7_ln_rows_launch<4, 3, SP8, true>(in, w49, bias, ln_w, ln_b, out, N, H, W, C, eps, s);
+    case 830: return dwconv7_ln_rows_launch<8, 3, SP8, false>(in, w49, bias, ln_w, ln_b, out, N, H, W, C, eps, s);
+    case 430: return dwconv7_ln_rows_launch<4, 3, SP8, false>(in, w49, bias, ln_w, ln_b, out, N, H, W, C, eps, s);
+    case 810: return dwconv7_ln_rows_launch<8, 1, SP8, false>(in, w49, bias, ln_w, ln_b, out, N, H, W, C, eps, s);
+    case 410: return dwconv7_ln_rows_launch<4, 1, SP8, false>(in, w49, bias, ln_w, ln_b, out, N, H, W, C, eps, s);
+    case 210: return dwconv7_ln_rows_launch<2, 1, SP8, false>(in, w49, bias, ln_w, ln_b, out, N, H, W, C, eps, s);
+  }
+  MTGV_CHECK(false, ERR_RUNTIME, "dwconv7_ln: no row-group kernel <%d, %d, %d>", p.tw, p.th, p.wl);
+}
+
+// launches the form p names; out_fmt 0: f32 rows, 1: SP8 rows
+static void dwconv7_ln_dispatch_plan(const DwLnPlan& p, const float* in, const float* w49, const float* bias, const float* ln_w,
+                                     const float* ln_b, float* out, int N, int H, int W, int C, float eps, hipStream_t s, int out_fmt) {
+  out_fmt == 1 ? dwconv7_ln_launch_fmt<true>(p, in, w49, bias, ln_w, ln_b, out, N, H, W, C, eps, s)
+               : dwconv7_ln_launch_fmt<false>(p, in, w49, bias, ln_w, ln_b, out, N, H, W, C, eps, s);
+}
+
+// picks the kernel form for the shape and launches it
 static void dwconv7_ln_dispatch(const float* in, const float* w49, const float* bias, const float* ln_w, const float* ln_b,
                                 float* out, int N, int H, int W, int C, float eps, hipStream_t s, int out_fmt) {
-  out_fmt == 1 ? dwconv7_ln_launch_fmt<true>(in, w49, bias, ln_w, ln_b, out, N, H, W, C, eps, s)
-               : dwconv7_ln_launch_fmt<false>(in, w49, bias, ln_w, ln_b, out, N, H, W, C, eps, s);
+  dwconv7_ln_dispatch_plan(dwconv7_ln_plan(N, H, W, C), in, w49, bias, ln_w, ln_b, out, N, H, W, C, eps, s, out_fmt);
 }
 
 }  // namespace mtgv

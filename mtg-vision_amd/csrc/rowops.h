@@ -17,7 +17,11 @@ void dwconv7_launch(const float* in, const float* w49, const float* bias, float*
 // depthwise 7x7 + bias followed by LayerNorm over C, fused (no un-normalised intermediate in HBM)
 bool dwconv7_ln_supported(int W, int C);
 void dwconv7_ln_launch(const float* in, const float* w49, const float* bias, const float* ln_w, const float* ln_b, float* out,
-                       int N, int H, int W, int C, float eps, hipStream_t s, int out_fmt = 0);
+                       int N, int H, int W, int C, float eps, hipStream_t s, int out_fmt = 0, int32_t* form = nullptr);
+// the kernel form, {kind 0 row groups / 1 streaming / 2 whole image, TW, TH, WL}: dwconv7_ln_plan's answer
+// (dwconv7_ln_kernel.h; MTGV_DW_ROWS and MTGV_DW_IMAGE read per call).  The launch fills `form` with the plan it launched;
+// dwconv7_ln_form asks the same rule without launching.  Host only.
+void dwconv7_ln_form(int N, int H, int W, int C, int32_t form[4]);
 
 // (N,C,H,W) f32 -> (N,H,W,Cp) f32, y = x*scale + shift, channels C..Cp-1 zero.  (x*2-1: convnextv2ae.py:257-258)
 void nchw_to_nhwc_launch(const float* in, float* out, int N, int C, int H, int W, int Cp, float scale, float shift,

@@ -213,11 +213,19 @@ bool dwconv7_ln_supported(int W, int C) {
 }
 
 void dwconv7_ln_launch(const float* in, const float* w49, const float* bias, const float* ln_w, const float* ln_b, float* out,
-                       int N, int H, int W, int C, float eps, hipStream_t s, int out_fmt) {
+                       int N, int H, int W, int C, float eps, hipStream_t s, int out_fmt, int32_t* form) {
   MTGV_CHECK(dwconv7_ln_supported(W, C), ERR_INVALID, "dwconv7_ln: unsupported W=%d C=%d", W, C);
   MTGV_CHECK(out_fmt == 0 || C % 8 == 0, ERR_INVALID, "dwconv7_ln: SP8 output needs C=%d %% 8 == 0", C);
   if (N <= 0) return;
-  dwconv7_ln_dispatch(in, w49, bias, ln_w, ln_b, out, N, H, W, C, eps, s, out_fmt);
+  const DwLnPlan p = dwconv7_ln_plan(N, H, W, C);
+  dwconv7_ln_dispatch_plan(p, in, w49, bias, ln_w, ln_b, out, N, H, W, C, eps, s, out_fmt);
+  if (form != nullptr) form[0] = p.kind, form[1] = p.tw, form[2] = p.th, form[3] = p.wl;  // the plan that was launched
+}
+
+void dwconv7_ln_form(int N, int H, int W, int C, int32_t form[4]) {
+  MTGV_CHECK(dwconv7_ln_supported(W, C), ERR_INVALID, "dwconv7_ln: unsupported W=%d C=%d", W, C);
+  const DwLnPlan p = dwconv7_ln_plan(N, H, W, C);
+  form[0] = p.kind, form[1] = p.tw, form[2] = p.th, form[3] = p.wl;
 }
 
 // ---------------------------------------------------------------------------

@@ -215,6 +215,8 @@ SIGNATURES = {
     "mtgv_op_proto_fold_compose": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
     "mtgv_op_layernorm": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_i32, c_f32, c_vp]),
     "mtgv_op_dwconv7": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_vp]),
+    "mtgv_op_dwconv7_ln": (C.c_int, [c_vp] * 6 + [c_i32] * 4 + [c_f32, c_i32, C.POINTER(c_i32), c_vp]),  # mtgv_version >= 113
+    "mtgv_op_dwconv7_ln_form": (C.c_int, [c_i32] * 4 + [C.POINTER(c_i32)]),
     "mtgv_op_block": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32] + [c_vp] * 10 + [c_vp, c_vp]),
     "mtgv_op_block_workspace_floats": (c_i64, [c_i32, c_i32, c_i32, c_i32]),
     "mtgv_op_l2norm": (C.c_int, [c_vp, c_vp, c_i64, c_i32, c_vp]),

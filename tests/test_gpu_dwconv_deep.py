@@ -1,4 +1,6 @@
-"""Whole-image form of dwconv7_ln (deep stages: 12 x 8 x 384, 6 x 4 x 768) against the single-row kernel, bit for bit."""
+"""Whole-image form of dwconv7_ln (deep stages: 12 x 8 x 384, 6 x 4 x 768) against the single-row form (the row-group
+kernel at one output row per thread, MTGV_DW_ROWS=0), bit for bit.  The forms share their arithmetic, so this says nothing
+about a mistake they all make: the absolute reference is tests/test_gpu_dwconv_ln_direct.py."""
 import os
 
 import numpy as np
@@ -34,7 +36,7 @@ class _Env:
                 os.environ[k] = v
 
 
-# forms by the launcher's switches: the single-row kernel, whatever the launcher picks by itself (whole image from 128
+# forms by the launcher's switches: the single-row form, whatever the launcher picks by itself (whole image from 128
 # images at the two deep shapes, else row groups), the whole-image form at any batch size where its rule admits the shape
 FORMS = {
     "single_row": dict(MTGV_DW_ROWS="0", MTGV_DW_IMAGE=None),
@@ -59,7 +61,7 @@ SHAPES = [
 @pytest.mark.parametrize("n,h,w,c,zeros", SHAPES)
 def test_dwconv_ln_image_form_is_bit_identical(n, h, w, c, zeros, prec):
     """dwconv7_ln's output (the block's normalised tensor in the workspace, raw 32-bit words: SP8 in the f16x3 GEMM
-    mode, f32 in the f32 mode) and the block's output are the same bits from the single-row kernel, the launcher's own
+    mode, f32 in the f32 mode) and the block's output are the same bits from the single-row form, the launcher's own
     choice, the whole-image form forced at any batch size, and the launcher with that form switched off."""
     from mtgv import native as nv
 
@@ -92,7 +94,7 @@ def test_dwconv_ln_image_form_is_bit_identical(n, h, w, c, zeros, prec):
     assert torch.isfinite(ref_out).all()
     for name in ("default", "image", "no_image"):
         t2, out = res[name]
-        assert torch.equal(t2, ref_t2), f"{name}: normalised tensor differs from the single-row kernel's"
+        assert torch.equal(t2, ref_t2), f"{name}: normalised tensor differs from the single-row form's"
         assert torch.equal(out.view(torch.int32), ref_out.view(torch.int32)), f"{name}: block output differs"
 
 

@@ -156,7 +156,9 @@ def test_dwconv_ln_forms_are_bit_identical(n, h, w, c):
     """the single-row form of dwconv7_ln (MTGV_DW_ROWS=0: the row-group kernel with one output row per thread, at strip
     widths 2, 4 and 8 - the last three shapes reach each with a ragged last strip) and the default forms - row groups
     (three output rows per thread, ragged last rows and strips included) and, from 128 images at 32 x 96 / 16 x 192
-    rows, the row-streaming kernel (LDS-DMA row ring; ragged heights included) - give the same bits (whole block)"""
+    rows, the row-streaming kernel (LDS-DMA row ring; ragged heights included) - give the same bits (whole block).
+    Both sides are dwconv7_ln_rows_kernel or share its arithmetic: a mistake common to all forms passes here, and is
+    test_gpu_dwconv_ln_direct.py's to find"""
     import os
 
     nv = _lib()
