@@ -639,6 +639,37 @@ MTGV_API int mtgv_op_stem_u8(const uint8_t* frames_dev, const float* w_dev, cons
  * v is added; NULL: attention only.  Status 1, and nothing launched, when h * w % area != 0, heads < 1 or area < 1. */
 MTGV_API int mtgv_op_area_attn(const float* qkv_dev, const float* pe_w49_dev, const float* pe_bias_dev, int32_t n, int32_t h, int32_t w,
                                int32_t heads, int32_t area, float* out_dev, void* stream);
+/* YOLO11's C2PSA attention core and its positional encoding alone (version 114; Detector::c2psa runs the same two launches), f32.
+ * qkv (n, h * w, heads * 128): per head [q 32 | k 32 | v 64], tokens are the pixels row-major; out (n, h * w, heads * 64), channel
+ * head * 64 + d, receives softmax(q^T k / sqrt(32)) v per image and head.  With pe_w9_dev ([9][heads * 64] tap-major, BatchNorm
+ * folded, bias pe_bias_dev [heads * 64]) the depthwise 3x3 (zero padding 1) of v over the h x w map is added: the attention
+ * goes to a scratch buffer of the library's and the 3x3 runs as the detector launches it - input channel offset 64, g_size 64,
+ * g_stride 128, the attention as addend.  NULL for both: attention only.  Status 1, and nothing launched, for null or
+ * misaligned (16 bytes) tensors, sizes below 1, n or heads above 65535.  Synchronises the stream before it returns. */
+MTGV_API int mtgv_op_psa_attn(const float* qkv_dev, const float* pe_w9_dev, const float* pe_bias_dev, int32_t n, int32_t h, int32_t w,
+                              int32_t heads, float* out_dev, void* stream);
+/* The detector's depthwise 3x3 alone (version 114; C2PSA's positional encoding and the Detect(legacy=False) class branch run
+ * the same launch): stride 1, zero padding 1, BatchNorm folded into w9 [9][c] tap-major and bias [c], then act (0 none, 3 SiLU),
+ * then the optional f32 addend (rows of add_ld floats, channel c at add[pixel * add_ld + c]).  x and out are NHWC views as in
+ * mtgv_conv_ex (pixel 0, floats per pixel, first channel; fmt 0 f32, 1 SP8).  Output channel k reads input channel
+ * x_co + (k / g_size) * g_stride + k % g_size; g_size 0: x_co + k.  Status 1, and nothing launched, for: null x, w9, bias or
+ * out; a size below 1; c % 8 != 0; g_size neither 0 nor a multiple of 8; another act or format; a pointer that is not 16-byte
+ * aligned; x_ct, x_co, g_stride (where there is more than one group), out_ct or out_co no multiple of 4 floats (8 on an SP8
+ * side), add_ld no multiple of 4 or below c; channels that leave their pixel (x_co + the last channel read > x_ct,
+ * out_co + c > out_ct).  Synchronises the stream before it returns. */
+typedef struct {
+  const void* x;       /* input: n images of h x w pixels, x_ct floats per pixel */
+  int32_t n, h, w, x_ct, x_co, x_fmt;
+  int32_t c, g_size, g_stride;
+  const float* w9;
+  const float* bias;
+  int32_t act;
+  const float* add;    /* NULL, or the addend */
+  int32_t add_ld;
+  void* out;           /* channels [out_co, out_co + c) of out_ct floats per pixel */
+  int32_t out_ct, out_co, out_fmt;
+} mtgv_dwconv3;
+MTGV_API int mtgv_op_dwconv3(const mtgv_dwconv3* d, void* stream);
 /* The detector's prototype branch behind cv1 (Detector::proto runs the same function): ConvTranspose2d(k2, s2, bias) ->
  * cv2 (3x3, BN folded, SiLU) -> cv3 (1x1, BN folded, SiLU), c -> c -> c -> nm channels.  pr1 is an SP8 view of n images of
  * h x w pixels; protos an f32 view of (2 h, 2 w) pixels.  Weights are host pointers: wt (c, c, 2, 2) and bt (c) as

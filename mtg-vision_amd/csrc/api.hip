@@ -106,7 +106,8 @@ MTGV_API const char* mtgv_last_error(void) { return last_error_cstr(); }
 // 111: mtgv_letterbox_ragged_u8, mtgv_warp_quads_src (crops from full-resolution source frames)
 // 112: mtgv_op_c2f_tail (the fused C2f tail as a single op)
 // 113: mtgv_op_dwconv7_ln, mtgv_op_dwconv7_ln_form (the fused depthwise 7x7 + LayerNorm as a single op, and its kernel form)
-MTGV_API int mtgv_version(void) { return 113; }
+// 114: mtgv_op_psa_attn, mtgv_op_dwconv3 (YOLO11's C2PSA attention and the depthwise 3x3 as single ops)
+MTGV_API int mtgv_version(void) { return 114; }
 MTGV_API int mtgv_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;

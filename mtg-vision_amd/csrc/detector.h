@@ -275,4 +275,30 @@ class Detector {
 void area_attn_launch(const float* qkv, const float* pe_w49, const float* pe_bias, int n, int h, int w, int heads, int area, float* att,
                       float* out, int out_ct, int out_co, bool out_sp8, hipStream_t s);
 
+// C2PSA's attention core (detector_v11.hip: attn_kernel<32, 64, 16>), f32.  qkv (n, N, heads * 128), per head
+// [q 32 | k 32 | v 64]; att (n, N, heads * 64) receives softmax(q^T k / sqrt(32)) v per image and head.  Refused with
+// ERR_INVALID before any launch: null or misaligned tensors, non-positive sizes, n or heads above 65535 (grid dimensions).
+// psa_attn_check is that refusal alone.
+void psa_attn_check(const float* qkv, int n, int N, int heads, const float* att);
+void psa_attn_launch(const float* qkv, int n, int N, int heads, float* att, hipStream_t s);
+
+// Depthwise 3x3, stride 1, zero padding 1, + bias (+ SiLU) (+ f32 addend) on n images of H x W pixels (detector_v11.hip:
+// dwconv3_kernel<IN_SP8, OUT_SP8>).  Views as in mtgv_conv_ex: pixel 0, floats per pixel, first channel; fmt 0 f32, 1 SP8.
+// Output channel c reads input channel in_co + (c / g_size) g_stride + c % g_size (g_size 0: in_co + c); w9 [9][C] tap-major
+// and bias [C] f32; act ACT_NONE or ACT_SILU; add nullptr or f32 rows of add_ld floats, added behind the activation.
+// dwconv3_check is the launch's refusal alone (ERR_INVALID; the conditions are at its definition).
+struct Dwconv3Args {
+  const float* in;
+  int in_ct, in_co, in_fmt, g_size, g_stride;
+  const float *w9, *bias;
+  int act;
+  const float* add;
+  int add_ld;
+  float* out;
+  int out_ct, out_co, out_fmt;
+  int n, H, W, C;
+};
+void dwconv3_check(const Dwconv3Args& a);
+void dwconv3_launch(const Dwconv3Args& a, hipStream_t s);
+
 }  // namespace mtgv

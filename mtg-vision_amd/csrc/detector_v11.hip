@@ -170,6 +170,69 @@ ConvW Detector::fold_dw(const std::string& p) {
   return ConvW{upload(wf), upload(bf), c, c, k};
 }
 
+static bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
+
+// What dwconv3_kernel can run, from its accesses.  A thread moves 8 channels as two 16-byte vectors: bias + c, w9 + tap C + c
+// (C % 8 == 0), in + pixel in_ct + cin, add + pixel add_ld + c and out + pixel out_ct + out_co + c, c a multiple of 8.
+// So every pointer is 16-byte aligned and in_ct, in_co, g_stride, add_ld, out_ct and out_co are multiples of 4 floats - of
+// 8 on an SP8 side, whose 8-channel chunk (8 hi halves, then 8 lo halves) is one 32-byte unit of the format.  The 8 channels
+// stay inside one group when g_size % 8 == 0, and inside their pixel when the last group ends within in_ct.
+void dwconv3_check(const Dwconv3Args& a) {
+  MTGV_CHECK(a.in != nullptr && a.w9 != nullptr && a.bias != nullptr && a.out != nullptr, ERR_INVALID, "dwconv3: null tensor");
+  MTGV_CHECK(a.n > 0 && a.H > 0 && a.W > 0 && a.C > 0, ERR_INVALID, "dwconv3: n=%d h=%d w=%d c=%d", a.n, a.H, a.W, a.C);
+  MTGV_CHECK(a.C % 8 == 0, ERR_INVALID, "dwconv3: c=%d is no multiple of 8", a.C);
+  MTGV_CHECK((a.in_fmt == 0 || a.in_fmt == 1) && (a.out_fmt == 0 || a.out_fmt == 1), ERR_INVALID, "dwconv3: formats %d -> %d", a.in_fmt,
+             a.out_fmt);
+  MTGV_CHECK(a.act == ACT_NONE || a.act == ACT_SILU, ERR_INVALID, "dwconv3: activation %d (none or SiLU)", a.act);
+  MTGV_CHECK(a.g_size == 0 || (a.g_size > 0 && a.g_size % 8 == 0 && a.g_stride >= 0), ERR_INVALID,
+             "dwconv3: g_size=%d (0 or a multiple of 8) g_stride=%d", a.g_size, a.g_stride);
+  const int gs = a.g_size > 0 ? a.g_size : a.C;
+  const int qi = a.in_fmt == 1 ? 8 : 4, qo = a.out_fmt == 1 ? 8 : 4;
+  const long last = (long)((a.C - 8) / gs) * a.g_stride + (a.C - 8) % gs + 8;  // one past the last input channel read, from in_co
+  MTGV_CHECK(aligned16(a.in) && a.in_ct > 0 && a.in_ct % qi == 0 && a.in_co >= 0 && a.in_co % qi == 0 && (gs >= a.C || a.g_stride % qi == 0) &&
+                 a.in_co + last <= a.in_ct,
+             ERR_INVALID, "dwconv3: input view %d/%d fmt %d with g_size=%d g_stride=%d (16-byte alignment, channels inside the pixel)", a.in_ct,
+             a.in_co, a.in_fmt, a.g_size, a.g_stride);
+  MTGV_CHECK(aligned16(a.w9) && aligned16(a.bias), ERR_INVALID, "dwconv3: weights not 16-byte aligned");
+  MTGV_CHECK(a.add == nullptr || (aligned16(a.add) && a.add_ld >= a.C && a.add_ld % 4 == 0), ERR_INVALID,
+             "dwconv3: addend with add_ld=%d (16-byte alignment, at least c)", a.add_ld);
+  MTGV_CHECK(aligned16(a.out) && a.out_ct % qo == 0 && a.out_co >= 0 && a.out_co % qo == 0 && a.out_co + a.C <= a.out_ct, ERR_INVALID,
+             "dwconv3: output view %d/%d fmt %d (16-byte alignment, channels inside the pixel)", a.out_ct, a.out_co, a.out_fmt);
+  MTGV_CHECK(((long)a.n * a.H * a.W * (a.C / 8) + 255) / 256 <= 0x7fffffffL, ERR_INVALID, "dwconv3: %d x %d x %d x %d is too large", a.n, a.H,
+             a.W, a.C);
+}
+
+void dwconv3_launch(const Dwconv3Args& a, hipStream_t s) {
+  dwconv3_check(a);
+  const int gs = a.g_size > 0 ? a.g_size : a.C;
+  const long total = (long)a.n * a.H * a.W * (a.C / 8);
+  const unsigned grid = (unsigned)((total + 255) / 256);
+#define DW_GO(I_, O_)                                                                                                                  \
+  hipLaunchKernelGGL((dwconv3_kernel<I_, O_>), dim3(grid), dim3(256), 0, s, a.in, a.in_ct, a.in_co, gs, a.g_stride, a.w9, a.bias, a.add, \
+                     a.add_ld, a.out, a.out_ct, a.out_co, a.H, a.W, a.C, a.act, total)
+  if (a.in_fmt == 1 && a.out_fmt == 1) DW_GO(true, true);
+  else if (a.in_fmt == 1) DW_GO(true, false);
+  else if (a.out_fmt == 1) DW_GO(false, true);
+  else DW_GO(false, false);
+#undef DW_GO
+  HIP_OK(hipGetLastError());
+}
+
+void psa_attn_check(const float* qkv, int n, int N, int heads, const float* att) {
+  MTGV_CHECK(qkv != nullptr && att != nullptr, ERR_INVALID, "psa_attn: null tensor");
+  MTGV_CHECK(n > 0 && N > 0 && heads > 0, ERR_INVALID, "psa_attn: n=%d tokens=%d heads=%d", n, N, heads);
+  MTGV_CHECK(n <= 65535 && heads <= 65535, ERR_INVALID, "psa_attn: n=%d heads=%d are grid dimensions (at most 65535)", n, heads);
+  // rows of heads * 128 and heads * 64 floats, read and written as 16-byte vectors
+  MTGV_CHECK(aligned16(qkv) && aligned16(att), ERR_INVALID, "psa_attn: tensors not 16-byte aligned");
+}
+
+void psa_attn_launch(const float* qkv, int n, int N, int heads, float* att, hipStream_t s) {
+  psa_attn_check(qkv, n, N, heads, att);
+  constexpr int KD = 32, HD = 64;
+  hipLaunchKernelGGL((attn_kernel<KD, HD, 16>), dim3((N + 255) / 256, heads, n), dim3(256), 0, s, qkv, att, N, heads, 1.0f / sqrtf((float)KD));
+  HIP_OK(hipGetLastError());
+}
+
 void Detector::dwconv(const ConvW& w, const View& in, const View& out, int act, const float* add, int g_size, int g_stride, int n,
                       hipStream_t s) {
   MTGV_CHECK(out.C == w.cout && w.cout % 8 == 0, ERR_RUNTIME, "detector: depthwise conv channel mismatch");
@@ -177,18 +240,8 @@ void Detector::dwconv(const ConvW& w, const View& in, const View& out, int act, 
     flops_ += 2.0 * 9.0 * n * out.H * out.W * w.cout;
     return;
   }
-  const int gs = g_size > 0 ? g_size : w.cout;
-  const long total = (long)n * out.H * out.W * (w.cout / 8);
-  const unsigned grid = (unsigned)((total + 255) / 256);
-#define DW_GO(I_, O_)                                                                                                             \
-  hipLaunchKernelGGL((dwconv3_kernel<I_, O_>), dim3(grid), dim3(256), 0, s, in.p, in.ct, in.co, gs, g_stride, w.w, w.b, add, w.cout, \
-                     out.p, out.ct, out.co, out.H, out.W, w.cout, act, total)
-  if (in.fmt == 1 && out.fmt == 1) DW_GO(true, true);
-  else if (in.fmt == 1) DW_GO(true, false);
-  else if (out.fmt == 1) DW_GO(false, true);
-  else DW_GO(false, false);
-#undef DW_GO
-  HIP_OK(hipGetLastError());
+  dwconv3_launch({in.p, in.ct, in.co, in.fmt, g_size, g_stride, w.w, w.b, act, add, w.cout, out.p, out.ct, out.co, out.fmt, n, out.H, out.W, w.cout},
+                 s);
 }
 
 // ---------------------------------------------------------------------------
@@ -260,9 +313,7 @@ void Detector::c2psa(int idx, const View& in, const View& out, int n, hipStream_
   if (count_flops_) {
     flops_ += 2.0 * n * NH * (double)N * N * (KD + HD);
   } else {
-    hipLaunchKernelGGL((attn_kernel<KD, HD, 16>), dim3((N + 255) / 256, NH, n), dim3(256), 0, s, qkv.p, att.p, N, NH,
-                       1.0f / sqrtf((float)KD));
-    HIP_OK(hipGetLastError());
+    psa_attn_launch(qkv.p, n, N, NH, att.p, s);
   }
   // y = attn_out + pe(v): depthwise 3x3 over the v rows of qkv (head h: channels h*(2 KD + HD) + 2 KD ...)
   View vin = qkv;
@@ -307,3 +358,51 @@ void Detector::head_cls_v11(int l, const View& f, const View& rh, int n, hipStre
 }
 
 }  // namespace mtgv
+
+// ---------------------------------------------------------------------------
+// C ABI
+// ---------------------------------------------------------------------------
+using namespace mtgv;
+extern "C" {
+// The positional encoding is not added in place.  dwconv3_kernel declares `add` and `out` __restrict__: with add == out the
+// compiler may assume the two never overlap, and although a thread reads only the eight addend values it then replaces,
+// that is an argument about the code it happens to generate, not about the kernel's source.  The detector keeps the two
+// apart as well ("att" and "atty"), so the attention output goes to a scratch buffer this entry point owns (test surface:
+// one per process, grown on demand, on the device of the first call) and the 3x3 reads it as the addend - the launch
+// c2psa makes.
+MTGV_API int mtgv_op_psa_attn(const float* qkv_dev, const float* pe_w9_dev, const float* pe_bias_dev, int32_t n, int32_t h, int32_t w,
+                              int32_t heads, float* out_dev, void* stream) {
+  return guarded([&] {
+    MTGV_CHECK(qkv_dev != nullptr && out_dev != nullptr, ERR_INVALID, "psa_attn: null argument");
+    MTGV_CHECK(n > 0 && h > 0 && w > 0 && heads > 0 && (long)h * w <= (1 << 24), ERR_INVALID, "psa_attn: n=%d h=%d w=%d heads=%d", n, h, w, heads);
+    MTGV_CHECK((pe_w9_dev == nullptr) == (pe_bias_dev == nullptr) && aligned16(pe_w9_dev) && aligned16(pe_bias_dev), ERR_INVALID,
+               "psa_attn: positional encoding needs weights and bias, both 16-byte aligned");
+    hipStream_t s = (hipStream_t)stream;
+    const int N = h * w;
+    psa_attn_check(qkv_dev, n, N, heads, out_dev);
+    if (pe_w9_dev == nullptr) {
+      psa_attn_launch(qkv_dev, n, N, heads, out_dev, s);
+    } else {
+      constexpr int KD = 32, HD = 64;  // Detector::c2psa's arguments
+      Dwconv3Args pe{qkv_dev, heads * (2 * KD + HD), 2 * KD, 0, HD, 2 * KD + HD, pe_w9_dev, pe_bias_dev, ACT_NONE, nullptr, heads * HD,
+                     out_dev, heads * HD, 0, 0, n, h, w, heads * HD};
+      dwconv3_check(pe);  // all but the addend: nothing is launched unless both launches can run
+      static DevBuf att;
+      att.ensure((size_t)n * N * heads * HD);
+      pe.add = att.p;
+      psa_attn_launch(qkv_dev, n, N, heads, att.p, s);
+      dwconv3_launch(pe, s);
+    }
+    HIP_OK(hipStreamSynchronize(s));
+  });
+}
+MTGV_API int mtgv_op_dwconv3(const mtgv_dwconv3* d, void* stream) {
+  return guarded([&] {
+    MTGV_CHECK(d != nullptr, ERR_INVALID, "dwconv3: null descriptor");
+    dwconv3_launch({(const float*)d->x, d->x_ct, d->x_co, d->x_fmt, d->g_size, d->g_stride, d->w9, d->bias, d->act, d->add, d->add_ld,
+                    (float*)d->out, d->out_ct, d->out_co, d->out_fmt, d->n, d->h, d->w, d->c},
+                   (hipStream_t)stream);
+    HIP_OK(hipStreamSynchronize((hipStream_t)stream));
+  });
+}
+}

@@ -323,6 +323,54 @@ def area_attn(qkv: torch.Tensor, h: int, w: int, heads: int, area: int, pe_w49: 
     return out
 
 
+def psa_attn(qkv: torch.Tensor, h: int, w: int, heads: int, pe_w9: Optional[torch.Tensor] = None,
+             pe_bias: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """YOLO11's C2PSA attention core alone (mtgv_op_psa_attn, the launches Detector::c2psa makes; test surface): qkv
+    (n, h * w, heads * 128) float32, per head [q 32 | k 32 | v 64] -> (n, h * w, heads * 64): softmax(q^T k / sqrt(32)) v per image
+    and head, plus - with pe_w9 ([9][heads * 64]) and pe_bias - the depthwise 3x3 of v over the h x w map."""
+    native.require_gpu()
+    assert qkv.is_cuda and qkv.dtype == torch.float32 and qkv.ndim == 3 and tuple(qkv.shape[1:]) == (h * w, heads * 128), f"{tuple(qkv.shape)}"
+    assert (pe_w9 is None) == (pe_bias is None)
+    if pe_w9 is not None:
+        assert pe_w9.is_cuda and pe_bias.is_cuda and tuple(pe_w9.shape) == (9, heads * 64) and tuple(pe_bias.shape) == (heads * 64,)
+        pe_w9, pe_bias = pe_w9.float().contiguous(), pe_bias.float().contiguous()
+    qkv = qkv.contiguous()
+    out = torch.empty((qkv.shape[0], h * w, heads * 64), dtype=torch.float32, device=qkv.device)
+    with torch.cuda.device(qkv.device):
+        native.check(native.lib().mtgv_op_psa_attn(native.ptr(qkv), native.ptr(pe_w9), native.ptr(pe_bias), qkv.shape[0], h, w, heads,
+                                                   native.ptr(out), native.stream()))
+    return out
+
+
+def dwconv3(x: torch.Tensor, w9: torch.Tensor, bias: torch.Tensor, *, x_co: int = 0, x_fmt: int = 0, g_size: int = 0, g_stride: int = 0,
+            act: int = 0, add: Optional[torch.Tensor] = None, out: Optional[torch.Tensor] = None, out_co: int = 0, out_fmt: int = 0) -> torch.Tensor:
+    """The detector's depthwise 3x3 alone (mtgv_op_dwconv3, the launch of C2PSA's positional encoding and of the
+    Detect(legacy=False) class branch; test surface): x (n, h, w, x_ct) float32-typed (fmt 1: SP8 bytes), w9 [9][c] tap-major,
+    bias [c]; output channel k reads input channel x_co + (k // g_size) * g_stride + k % g_size (g_size 0: x_co + k); act 0
+    none or 3 SiLU; add (n, h, w, add_ld) float32 is added behind the activation.  Writes channels [out_co, out_co + c) of
+    out (n, h, w, out_ct) - a new (n, h, w, c) tensor if none is given - and returns it."""
+    native.require_gpu()
+    assert x.is_cuda and x.dtype == torch.float32 and x.ndim == 4 and w9.ndim == 2 and w9.shape[0] == 9
+    n, h, w, x_ct = x.shape
+    c = w9.shape[1]
+    if out is None:
+        out = torch.empty((n, h, w, c), dtype=torch.float32, device=x.device)
+    assert out.is_cuda and out.dtype == torch.float32 and tuple(out.shape[:3]) == (n, h, w) and tuple(bias.shape) == (c,)
+    assert add is None or (add.is_cuda and add.dtype == torch.float32 and tuple(add.shape[:3]) == (n, h, w))
+    d = native.Dwconv3()
+    d.x, d.n, d.h, d.w, d.x_ct, d.x_co, d.x_fmt = x.data_ptr(), n, h, w, x_ct, x_co, x_fmt
+    d.c, d.g_size, d.g_stride = c, g_size, g_stride
+    keep = (w9.float().contiguous(), bias.float().contiguous())
+    d.w9, d.bias, d.act = keep[0].data_ptr(), keep[1].data_ptr(), act
+    if add is not None:
+        d.add, d.add_ld = add.data_ptr(), add.shape[3]
+    d.out, d.out_ct, d.out_co, d.out_fmt = out.data_ptr(), out.shape[3], out_co, out_fmt
+    assert x.is_contiguous() and out.is_contiguous() and (add is None or add.is_contiguous())
+    with torch.cuda.device(x.device):
+        native.check(native.lib().mtgv_op_dwconv3(C.byref(d), native.stream()))
+    return out
+
+
 def binarize_masks(mask_logits: torch.Tensor, scale: int = 4) -> torch.Tensor:
     """(n, mh, mw) cropped logits -> (n, mh * scale, mw * scale) uint8 {0,1}: bilinear x`scale` (align_corners=False), > 0.
     (160 x 160 -> 640 x 640 for a square handle, in_h / 4 x in_w / 4 -> in_h x in_w for a rectangular one.)"""

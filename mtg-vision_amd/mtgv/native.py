@@ -96,6 +96,17 @@ class C2fTail(C.Structure):
     )
 
 
+class Dwconv3(C.Structure):
+    """mtgv_dwconv3: the detector's depthwise 3x3 as one launch (test surface)"""
+
+    _fields_ = (
+        [("x", c_vp)]
+        + [(k, c_i32) for k in ("n", "h", "w", "x_ct", "x_co", "x_fmt", "c", "g_size", "g_stride")]
+        + [("w9", c_vp), ("bias", c_vp), ("act", c_i32), ("add", c_vp), ("add_ld", c_i32), ("out", c_vp)]
+        + [(k, c_i32) for k in ("out_ct", "out_co", "out_fmt")]
+    )
+
+
 class TrackerCfg(C.Structure):
     """mtgv_tracker_cfg (mtgv_version >= 104); zero in a policy field selects the reference's value"""
 
@@ -210,6 +221,8 @@ SIGNATURES = {
     "mtgv_op_conv2d_ex": (C.c_int, [C.POINTER(ConvEx), C.POINTER(c_i32), c_vp]),
     "mtgv_op_stem_u8": (C.c_int, [c_vp, c_vp, c_vp, c_vp] + [c_i32] * 7 + [c_vp]),
     "mtgv_op_area_attn": (C.c_int, [c_vp, c_vp, c_vp] + [c_i32] * 5 + [c_vp, c_vp]),  # mtgv_version >= 109
+    "mtgv_op_psa_attn": (C.c_int, [c_vp, c_vp, c_vp] + [c_i32] * 4 + [c_vp, c_vp]),  # mtgv_version >= 114
+    "mtgv_op_dwconv3": (C.c_int, [C.POINTER(Dwconv3), c_vp]),
     "mtgv_op_proto_tail": (C.c_int, [C.POINTER(ProtoTail), C.POINTER(c_i32), c_vp]),
     "mtgv_op_c2f_tail": (C.c_int, [C.POINTER(C2fTail), c_vp]),  # mtgv_version >= 112
     "mtgv_op_proto_fold_compose": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp]),
