@@ -37,7 +37,9 @@ extern "C" {
 
 MTGV_API const char* mtgv_last_error(void);
 /* 110: mtgv_tracker_create_ex / MTGV_TRACKER_WIDE (256 tracks per stream, 64 cards per frame)
- * 111: mtgv_letterbox_ragged_u8, mtgv_warp_quads_src (crops from full-resolution source frames) */
+ * 111: mtgv_letterbox_ragged_u8, mtgv_warp_quads_src (crops from full-resolution source frames)
+ * 115: the embed budget of the tracker (mtgv_tracker_create_budget, mtgv_tracker_update_budget, mtgv_tracker_gather_u8_pad,
+ *      mtgv_op_track_select) */
 MTGV_API int mtgv_version(void);
 /* number of HIP devices visible; does not initialise a device context */
 MTGV_API int mtgv_device_count(void);
@@ -180,8 +182,10 @@ MTGV_API int mtgv_bank_topk_ex(mtgv_bank* h, const float* q_dev, int32_t b, int3
 /* Batches of >= 128 queries (dim % 64 == 0, k <= 4, F16X3 mode) are matched in two passes: approximate fp16 scores over a
  * hi-only copy of the bank, then an exact re-rank of the best candidates with a bound that proves no other row can enter
  * the top k; a query whose bound fails is scanned exactly, so the answer is always the exact top k.  count: how many
- * queries took that scan so far (banks with many near-duplicate rows); synchronises the device.  MTGV_MATCH_PREPASS=0
- * keeps to the one-pass exact kernel. */
+ * queries took that scan so far (banks with many near-duplicate rows); synchronises the device.  An all-zero query (every
+ * score exactly 0, so no bound could hold) is answered directly with that scan's result - the k first rows at score 0 - and
+ * is not counted (version 115; before, each took the scan of the whole bank and counted).  MTGV_MATCH_PREPASS=0 keeps to the
+ * one-pass exact kernel. */
 MTGV_API int mtgv_bank_prepass_fallbacks(const mtgv_bank* h, int64_t* count);
 /* merge ncand (score,id) candidates per query into the top k (multi-GPU shard merge); same threshold rule */
 MTGV_API int mtgv_topk_merge(float* cand_scores_dev, const int64_t* cand_ids_dev, int32_t b, int32_t ncand, int32_t k,
@@ -769,6 +773,22 @@ MTGV_API int mtgv_tracker_create(const mtgv_tracker_cfg* cfg, mtgv_tracker** out
  * every size; the same arithmetic, the same results.  Unknown flag bits: status 1.  Checked before the first HIP call.
  * Every other mtgv_tracker_* call works on both kinds of handle; mtgv_tracker_get_state keeps its layout with the handle's T. */
 MTGV_API int mtgv_tracker_create_ex(const mtgv_tracker_cfg* cfg, int32_t flags, mtgv_tracker** out);
+/* A handle with an embed budget (version 115): flags as for mtgv_tracker_create_ex (0 or MTGV_TRACKER_WIDE), embed_budget
+ * E in 1..65535, anything else status 1 before the first HIP call.  The layout of mtgv_tracker_cfg is unchanged.
+ * A slot whose track is due (reported, and without an embedding or with more than update_wait_sec since its last one) is a
+ * candidate; its key is the time it has waited, now - last_update in fp64 as the gate computes it, +inf for a track that was
+ * never embedded.  mtgv_tracker_update takes the min(E, candidates) candidates with the largest key - ties go to the smaller
+ * flat index f K + k - and reports them as due_idx (ascending) / n_due; only they get last_update = now.  (So a track
+ * that was deferred before its first embed reads last_update = 0, the value of a new slot, in mtgv_tracker_get_state until
+ * it is taken, where the host's TrackedData carries the clock of its first report; the gate never reads it without an
+ * embedding, and the key of such a track is +inf.)  The others stay
+ * due: their key grows with every step, so under a lasting overload a candidate is taken after at most
+ * ceil(candidates / E) steps.  With E >= candidates the step is that of a handle without a budget, bit for bit.
+ * n_due <= E always, so the embed and match stages can run on exactly E rows with no count read back: gather with
+ * mtgv_tracker_gather_u8_pad, and mtgv_tracker_commit on this handle writes zeros into the rows [n_due, rows) of q (and
+ * launches over all `rows` rows, at most 65535).  mtgv_tracker_store ignores rows that no slot ranks.
+ * An update of more than 8192 flat slots (frames * K) on this handle: status 1, checked before any HIP call. */
+MTGV_API int mtgv_tracker_create_budget(const mtgv_tracker_cfg* cfg, int32_t flags, int32_t embed_budget, mtgv_tracker** out);
 MTGV_API void mtgv_tracker_destroy(mtgv_tracker* h);
 /* forget the tracks of one stream, or of all (-1): ids start again at 1.  Asynchronous on `stream`. */
 MTGV_API int mtgv_tracker_reset(mtgv_tracker* h, int32_t stream_or_minus_1, void* stream);
@@ -782,13 +802,24 @@ MTGV_API int mtgv_tracker_reset(mtgv_tracker* h, int32_t stream_or_minus_1, void
 MTGV_API int mtgv_tracker_update(mtgv_tracker* h, const float* quads_dev, const int32_t* n_det_dev, const int32_t* state_dev, int32_t frames,
                                  const int32_t* stream_of_frame_host, const double* now_host, int32_t* track_id_dev, int32_t* due_idx_dev,
                                  int32_t* n_due_dev, void* stream);
+/* mtgv_tracker_update on a handle with an embed budget (status 1 on any other), which also writes n_deferred_dev (1): the
+ * candidates of the step that the budget left for later, candidates - n_due.  (mtgv_tracker_update itself works on such a
+ * handle too and drops that count.) */
+MTGV_API int mtgv_tracker_update_budget(mtgv_tracker* h, const float* quads_dev, const int32_t* n_det_dev, const int32_t* state_dev,
+                                        int32_t frames, const int32_t* stream_of_frame_host, const double* now_host, int32_t* track_id_dev,
+                                        int32_t* due_idx_dev, int32_t* n_due_dev, int32_t* n_deferred_dev, void* stream);
 /* dst row r = src row due_idx[r] for r < min(n_due, max_rows), rows of row_bytes bytes; indices outside [0, src_rows) are
  * skipped.  n_due is read on the device: launched over max_rows rows, nothing written when it is 0. */
 MTGV_API int mtgv_tracker_gather_u8(const uint8_t* src_dev, int64_t src_rows, int64_t row_bytes, const int32_t* due_idx_dev,
                                     const int32_t* n_due_dev, int32_t max_rows, uint8_t* dst_dev, void* stream);
+/* mtgv_tracker_gather_u8 that also fills the rows [n_due, max_rows) of dst with zeros: every one of the max_rows rows is
+ * written (a row whose index is outside [0, src_rows) excepted, as above), so dst can be embedded whole. */
+MTGV_API int mtgv_tracker_gather_u8_pad(const uint8_t* src_dev, int64_t src_rows, int64_t row_bytes, const int32_t* due_idx_dev,
+                                        const int32_t* n_due_dev, int32_t max_rows, uint8_t* dst_dev, void* stream);
 /* z (rows, dim): the embeddings of the due slots in due_idx order.  avg = w z + (1 - w) avg in f32 (the first time avg = z,
  * then the same formula); q (rows, dim) receives the averaged vectors, the queries of the match.  n_due is read on the
- * device and min(n_due, rows) rows are processed: rows is what the buffers hold (n_due, or frames * K without the count). */
+ * device and min(n_due, rows) rows are processed: rows is what the buffers hold (n_due, or frames * K without the count).
+ * On a handle of mtgv_tracker_create_budget only: rows [n_due, rows) of q are zeroed and rows is at most 65535 (status 1). */
 MTGV_API int mtgv_tracker_commit(mtgv_tracker* h, const float* z_dev, float* q_dev, int32_t rows, void* stream);
 /* ids / scores (rows, top_k): the matches of q, rows as in commit.  They are kept on the due tracks; then every slot of the step with a track id
  * emits its track's kept matches into out_ids (frames, K, top_k) / out_scores - a track that was not due its older ones - and
@@ -800,6 +831,14 @@ MTGV_API int mtgv_tracker_store(mtgv_tracker* h, const int64_t* ids_dev, const f
  * last_update (T); avg_z (T, dim); match_ids / match_scores (T, top_k); counters (4): next_id, next_birth, overflow, 0. */
 MTGV_API int mtgv_tracker_get_state(mtgv_tracker* h, int32_t stream_index, double* kal_host, int32_t* ints_host, double* last_update_host,
                                     float* avg_z_host, int64_t* match_ids_host, float* match_scores_host, int32_t* counters_host, void* stream);
+/* The selection kernel of a budget handle alone (version 115): one launch of one workgroup.  waited (n) fp64, slot i's key,
+ * NaN for a slot that is no candidate; n in 1..8192, budget in 1..65535, else status 1.  Writes due_idx (n): the
+ * min(budget, candidates) candidates with the largest key, ties to the smaller index, in ascending index, -1 behind them;
+ * rank_of (n): a selected slot's position in due_idx, -1 otherwise; n_due (1); n_deferred (1) = candidates - n_due.  The
+ * budget-th largest key is found exactly (a radix select over the keys as order-preserving 64-bit integers); mtgv/tracker.py's
+ * select_due states the rule on the host. */
+MTGV_API int mtgv_op_track_select(const double* waited_dev, int32_t n, int32_t budget, int32_t* due_idx_dev, int32_t* rank_of_dev,
+                                  int32_t* n_due_dev, int32_t* n_deferred_dev, void* stream);
 
 #ifdef __cplusplus
 }

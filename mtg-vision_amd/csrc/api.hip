@@ -90,7 +90,7 @@ struct mtgv_bank {
 
 struct mtgv_tracker {
   Tracker impl;
-  mtgv_tracker(const mtgv_tracker_cfg& c, int32_t flags) : impl(c, flags) {}
+  mtgv_tracker(const mtgv_tracker_cfg& c, int32_t flags, int embed_budget = 0) : impl(c, flags, embed_budget) {}
 };
 
 extern "C" {
@@ -107,7 +107,8 @@ MTGV_API const char* mtgv_last_error(void) { return last_error_cstr(); }
 // 112: mtgv_op_c2f_tail (the fused C2f tail as a single op)
 // 113: mtgv_op_dwconv7_ln, mtgv_op_dwconv7_ln_form (the fused depthwise 7x7 + LayerNorm as a single op, and its kernel form)
 // 114: mtgv_op_psa_attn, mtgv_op_dwconv3 (YOLO11's C2PSA attention and the depthwise 3x3 as single ops)
-MTGV_API int mtgv_version(void) { return 114; }
+// 115: the embed budget (mtgv_tracker_create_budget, mtgv_tracker_update_budget, mtgv_tracker_gather_u8_pad, mtgv_op_track_select)
+MTGV_API int mtgv_version(void) { return 115; }
 MTGV_API int mtgv_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -317,6 +318,14 @@ MTGV_API int mtgv_tracker_create_ex(const mtgv_tracker_cfg* cfg, int32_t flags, 
     *out = new mtgv_tracker(*cfg, flags);
   });
 }
+MTGV_API int mtgv_tracker_create_budget(const mtgv_tracker_cfg* cfg, int32_t flags, int32_t embed_budget, mtgv_tracker** out) {
+  return guarded([&] {
+    MTGV_CHECK(cfg != nullptr && out != nullptr, ERR_INVALID, "tracker: null argument");
+    (void)tracker_resolve_cfg(*cfg, flags);  // the range checks before any HIP call
+    (void)tracker_check_budget(embed_budget);
+    *out = new mtgv_tracker(*cfg, flags, embed_budget);
+  });
+}
 MTGV_API void mtgv_tracker_destroy(mtgv_tracker* h) { delete h; }
 MTGV_API int mtgv_tracker_reset(mtgv_tracker* h, int32_t stream_or_minus_1, void* stream) {
   return guarded([&] {
@@ -329,13 +338,30 @@ MTGV_API int mtgv_tracker_update(mtgv_tracker* h, const float* quads_dev, const 
                                  int32_t* n_due_dev, void* stream) {
   return guarded([&] {
     MTGV_CHECK(h != nullptr, ERR_INVALID, "null handle");
-    h->impl.update(quads_dev, n_det_dev, state_dev, frames, stream_of_frame_host, now_host, track_id_dev, due_idx_dev, n_due_dev,
+    h->impl.update(quads_dev, n_det_dev, state_dev, frames, stream_of_frame_host, now_host, track_id_dev, due_idx_dev, n_due_dev, nullptr,
+                   (hipStream_t)stream);
+  });
+}
+MTGV_API int mtgv_tracker_update_budget(mtgv_tracker* h, const float* quads_dev, const int32_t* n_det_dev, const int32_t* state_dev, int32_t frames,
+                                        const int32_t* stream_of_frame_host, const double* now_host, int32_t* track_id_dev, int32_t* due_idx_dev,
+                                        int32_t* n_due_dev, int32_t* n_deferred_dev, void* stream) {
+  return guarded([&] {
+    MTGV_CHECK(h != nullptr && n_deferred_dev != nullptr, ERR_INVALID, "null handle or n_deferred");
+    h->impl.update(quads_dev, n_det_dev, state_dev, frames, stream_of_frame_host, now_host, track_id_dev, due_idx_dev, n_due_dev, n_deferred_dev,
                    (hipStream_t)stream);
   });
 }
 MTGV_API int mtgv_tracker_gather_u8(const uint8_t* src_dev, int64_t src_rows, int64_t row_bytes, const int32_t* due_idx_dev,
                                     const int32_t* n_due_dev, int32_t max_rows, uint8_t* dst_dev, void* stream) {
-  return guarded([&] { tracker_gather_u8_launch(src_dev, src_rows, row_bytes, due_idx_dev, n_due_dev, max_rows, dst_dev, (hipStream_t)stream); });
+  return guarded([&] { tracker_gather_u8_launch(src_dev, src_rows, row_bytes, due_idx_dev, n_due_dev, max_rows, dst_dev, false, (hipStream_t)stream); });
+}
+MTGV_API int mtgv_tracker_gather_u8_pad(const uint8_t* src_dev, int64_t src_rows, int64_t row_bytes, const int32_t* due_idx_dev,
+                                        const int32_t* n_due_dev, int32_t max_rows, uint8_t* dst_dev, void* stream) {
+  return guarded([&] { tracker_gather_u8_launch(src_dev, src_rows, row_bytes, due_idx_dev, n_due_dev, max_rows, dst_dev, true, (hipStream_t)stream); });
+}
+MTGV_API int mtgv_op_track_select(const double* waited_dev, int32_t n, int32_t budget, int32_t* due_idx_dev, int32_t* rank_of_dev, int32_t* n_due_dev,
+                                  int32_t* n_deferred_dev, void* stream) {
+  return guarded([&] { tracker_select_launch(waited_dev, n, budget, due_idx_dev, rank_of_dev, n_due_dev, n_deferred_dev, (hipStream_t)stream); });
 }
 MTGV_API int mtgv_tracker_commit(mtgv_tracker* h, const float* z_dev, float* q_dev, int32_t rows, void* stream) {
   return guarded([&] {

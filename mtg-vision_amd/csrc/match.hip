@@ -244,6 +244,21 @@ __global__ __launch_bounds__(256) void rerank_kernel(const float* __restrict__ q
   const float* cs = cand_s + (long)b * ncand;
   const int* ci = cand_i + (long)b * ncand;
   const float* q = qn + (long)b * K;
+  // A query without a direction (all zeros: a row that a budgeted tracker step pads its queries with) scores exactly 0 on
+  // every row, so its exact answer is known: the k first rows.  Without this the bound below can prove nothing - every
+  // approximate score ties at 0 - and the block would score the whole bank exactly and count as a fallback.
+  {
+    bool nonzero = false;
+    for (int c = tid; c < K; c += 256) nonzero |= q[c] != 0.f;
+    if (!__syncthreads_or(nonzero)) {  // (the whole block)
+      if (tid == 0)
+        for (int kk = 0; kk < k; ++kk) {
+          const bool ok = kk < nrows && 0.f >= thr;
+          store_result(out_ids, out_scores, (long)b * k + kk, ok ? kk + id_base : -1, ok ? 0.f : -INFINITY);
+        }
+      return;
+    }
+  }
   // bound of everything a wave range did not report: its last reported score (-inf when the range ran out of columns)
   float cut = -INFINITY;
   for (int w = tid; w < slots; w += 256) cut = fmaxf(cut, cs[w * PRE_KP + PRE_KP - 1]);

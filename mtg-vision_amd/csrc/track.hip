@@ -1,7 +1,8 @@
 // Device-resident card tracker (track.h).  update: one wave64 workgroup per frame = stream, lane t owns track slot t with its
 // filter state in registers, the frame's detections in LDS, the greedy association as at most K rounds of a wave-wide
 // lexicographic minimum over (distance, birth, detection index).  A second, single-workgroup launch compacts the due slots in
-// ascending order.  The wide form (MTGV_TRACKER_WIDE: up to 256 slots, 64 detections) is a second update kernel with up to
+// ascending order; on a handle with an embed budget that launch is track_select_kernel, which takes at most `budget` of them,
+// the longest-waiting first.  The wide form (MTGV_TRACKER_WIDE: up to 256 slots, 64 detections) is a second update kernel with up to
 // four waves per workgroup; the one-wave kernel is what a handle of mtgv_tracker_create launches.  What a track does on its
 // own (Slot and the slot_* pieces) is written once for both.  Everything the host tracker computes in fp64 is computed here
 // in fp64 with the same operations in the same order: this translation unit must not contract a * b + c into an FMA.
@@ -188,21 +189,38 @@ __device__ __forceinline__ void slot_spawn(Slot& a, const Params& p, const doubl
 }
 
 // 5. report and gate
-template <int KM>
-__device__ __forceinline__ void slot_report(Slot& a, const Params& p, double now, Dets<KM>& D, int s, int T, int t) {
+// On a budget handle (BUDGET; defer: its (frames * K, 2) candidate records) a due track is a candidate only: its key, the time
+// it has waited (+inf without an embedding), and the frame's clock go into the record of its flat slot f K + k, and
+// track_select_kernel stamps the tracks it takes.  On any other handle the update stamps a due track itself.
+template <bool BUDGET, int KM>
+__device__ __forceinline__ void slot_report(Slot& a, const Params& p, double now, Dets<KM>& D, int f, int s, int T, int t, double* defer) {
   const bool rep = a.live && a.id > 0 && a.mdi >= 0 && a.hit >= 0;
   const bool due = rep && (!a.has_z || now - a.last_t > p.wait);
-  if (due) a.last_t = now;
+  if constexpr (BUDGET) {
+    if (due) {
+      double* rec = defer + 2 * ((size_t)f * p.K + D.det_k[a.mdi]);
+      rec[0] = a.has_z ? now - a.last_t : INFINITY, rec[1] = now;
+    }
+  } else {
+    if (due) a.last_t = now;
+  }
   if (rep) {
     const int k = D.det_k[a.mdi];
     D.o_id[k] = a.id, D.o_slot[k] = s * T + t, D.o_due[k] = due ? 1 : 0;
   }
 }
 
+// Defer: nothing, or the one double* of a budget handle (its candidate records), whose kernel differs in slot_report alone.
+// A trailing parameter pack, so that the kernel of every other handle keeps the argument list it had (the one-wave kernel
+// then compiles to the same instruction stream as without the pack).
+__device__ __forceinline__ double* defer_of() { return nullptr; }
+__device__ __forceinline__ double* defer_of(double* d) { return d; }
+
+template <class... Defer>
 __global__ __launch_bounds__(64) void track_update_kernel(State st, Params p, FrameArgs fr, int f0, const float* __restrict__ quads,
                                                           const int32_t* __restrict__ n_det, const int32_t* __restrict__ state,
                                                           int32_t* __restrict__ track_id, int32_t* __restrict__ slot_of,
-                                                          int32_t* __restrict__ due_flag) {
+                                                          int32_t* __restrict__ due_flag, Defer... defer) {
   __shared__ Dets<TRACK_MAX_CARDS> D;
   const int lane = threadIdx.x;
   const int f = f0 + blockIdx.x, s = fr.stream[blockIdx.x];
@@ -275,7 +293,7 @@ __global__ __launch_bounds__(64) void track_update_kernel(State st, Params p, Fr
     next_birth += 1;
   }
 
-  slot_report(a, p, now, D, s, T, lane);
+  slot_report<sizeof...(Defer) != 0>(a, p, now, D, f, s, T, lane, defer_of(defer...));
   slot_store(st, a, s, T, lane, own, p.top_k);
   if (lane == 0) C[0] = next_id, C[1] = next_birth, C[2] = overflow;
   __syncthreads();
@@ -289,12 +307,13 @@ __global__ __launch_bounds__(64) void track_update_kernel(State st, Params p, Fr
 // from LDS only when that detection was taken by another track (its minimum over the free set changes only then).
 // Every __syncthreads() below is reached by every thread: the loop bounds (nd, two phases) and the early exit are values
 // that all threads read from LDS after a barrier.
+template <class... Defer>
 __global__ __launch_bounds__(TRACK_WIDE_MAX_TRACKS) void track_update_wide_kernel(State st, Params p, FrameArgs fr, int f0,
                                                                                   const float* __restrict__ quads,
                                                                                   const int32_t* __restrict__ n_det,
                                                                                   const int32_t* __restrict__ state,
                                                                                   int32_t* __restrict__ track_id, int32_t* __restrict__ slot_of,
-                                                                                  int32_t* __restrict__ due_flag) {
+                                                                                  int32_t* __restrict__ due_flag, Defer... defer) {
   constexpr int WM = TRACK_WIDE_MAX_TRACKS / 64;
   __shared__ Dets<TRACK_WIDE_MAX_CARDS> D;
   __shared__ int s_nd;
@@ -394,7 +413,7 @@ __global__ __launch_bounds__(TRACK_WIDE_MAX_TRACKS) void track_update_wide_kerne
     next_birth += 1;
   }
 
-  slot_report(a, p, now, D, s, T, tid);
+  slot_report<sizeof...(Defer) != 0>(a, p, now, D, f, s, T, tid, defer_of(defer...));
   slot_store(st, a, s, T, tid, own, p.top_k);
   if (tid == 0) C[0] = next_id, C[1] = next_birth, C[2] = overflow;
   __syncthreads();
@@ -422,13 +441,161 @@ __global__ __launch_bounds__(64) void track_compact_kernel(const int32_t* __rest
   if (lane == 0) *n_due = base;
 }
 
-// row r < n_due: avg = w z + (1 - w) avg in f32 (avg = z the first time, then the same formula), q[r] = avg
+// ---- the embed budget: track_select_kernel in the place of track_compact_kernel (mtgv/tracker.py: select_due is the rule).
+// Of the step's candidates (due_flag, or a key that is no NaN) it takes the min(budget, candidates) with the largest key, ties
+// to the smaller flat index, and writes them as the compaction does: due_idx ascending with -1 behind, rank_of, n_due, and
+// n_deferred = candidates - n_due.  One workgroup of 256 threads; thread t owns the `per` consecutive slots from t * per.
+// The keys are staged once in LDS as order-preserving 64-bit integers (0: no candidate; no candidate's key maps to 0).
+// When the budget binds, the budget-th largest key is found exactly by a radix select from the top byte down, eight passes
+// of an LDS histogram of one byte over the keys that share the bytes found so far.  The histogram's atomics only count;
+// the position of an output row comes from two ordered prefix counts over the threads (ties, then everything selected).
+// Every loop bound (`per`, eight passes, four waves) is fixed before its loop, and every barrier is reached by every thread:
+// the one branch around barriers, `binds`, is a value that all threads read from LDS behind a barrier.
+constexpr int SELECT_THREADS = 256;
+constexpr int SELECT_MAX_SLOTS = 8192;  // 64 KiB of staged keys (MI355X: 160 KiB of LDS per CU, one workgroup may ask for all)
+constexpr int SELECT_WAVES = SELECT_THREADS / 64;
+
+struct SelectShared {
+  int hist[256];
+  int wave_sum[SELECT_WAVES];
+  int digit, rest;
+};
+
+__device__ __forceinline__ unsigned long long select_key(double waited) {  // a < b <=> key(a) < key(b); -0.0 counts as +0.0
+  const unsigned long long u = (unsigned long long)__double_as_longlong(waited + 0.0);
+  return (u >> 63) ? ~u : (u | 0x8000000000000000ull);
+}
+
+// exclusive prefix sum of v over the workgroup's threads in thread order -> (prefix, total); two barriers, called by all
+__device__ __forceinline__ int select_scan(int v, int* wave_sum, int& total) {
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+  int inc = v;
+#pragma unroll
+  for (int off = 1; off < 64; off <<= 1) {
+    const int o = __shfl_up(inc, off);
+    if (lane >= off) inc += o;
+  }
+  __syncthreads();  // the last call's readers are done with wave_sum
+  if (lane == 63) wave_sum[wave] = inc;
+  __syncthreads();
+  int before = 0, all = 0;
+#pragma unroll
+  for (int w = 0; w < SELECT_WAVES; ++w) {
+    const int ws = wave_sum[w];
+    before += w < wave ? ws : 0, all += ws;
+  }
+  total = all;
+  return before + inc - v;
+}
+
+// waited: the key of slot i at waited[i * stride] (a budget handle's records: stride 2, the frame's clock behind the key).
+// due_flag nullptr: a NaN key marks a slot that is no candidate.  last_t given: the taken tracks (slot_of) are stamped.
+__global__ __launch_bounds__(SELECT_THREADS) void track_select_kernel(const double* __restrict__ waited, int stride,
+                                                                      const int32_t* __restrict__ due_flag, int n, int budget,
+                                                                      const int32_t* __restrict__ slot_of, double* __restrict__ last_t,
+                                                                      int32_t* __restrict__ due_idx, int32_t* __restrict__ rank_of,
+                                                                      int32_t* __restrict__ n_due, int32_t* __restrict__ n_deferred) {
+  extern __shared__ unsigned long long s_key[];  // n keys, then SelectShared
+  SelectShared& sh = *reinterpret_cast<SelectShared*>(s_key + n);
+  const int tid = threadIdx.x;
+  const int per = (n + SELECT_THREADS - 1) / SELECT_THREADS;
+  const int lo = min(tid * per, n), hi = min(lo + per, n);
+
+  int mine = 0;
+  for (int i = lo; i < hi; ++i) {
+    bool cand = due_flag != nullptr ? due_flag[i] != 0 : true;
+    unsigned long long key = 0ull;
+    if (cand) {
+      const double w = waited[(size_t)i * stride];
+      cand = w == w;
+      if (cand) key = select_key(w);
+    }
+    s_key[i] = key;
+    mine += cand ? 1 : 0;
+  }
+  int cands;
+  (void)select_scan(mine, sh.wave_sum, cands);  // (its barriers publish s_key too)
+  const bool binds = cands > budget;            // workgroup-uniform: a sum read from LDS behind a barrier
+
+  // the threshold: the budget-th largest key, and how many of the keys equal to it are taken
+  unsigned long long thr = 0ull;  // not binding: every candidate's key is above 0
+  int take_eq = 0;
+  if (binds) {
+    int rest = budget;  // the rank of the wanted key among those that share the prefix
+    for (int pass = 7; pass >= 0; --pass) {
+      const unsigned long long above = pass == 7 ? 0ull : (~0ull << (8 * pass + 8));
+      sh.hist[tid] = 0;
+      __syncthreads();
+      for (int i = lo; i < hi; ++i) {
+        const unsigned long long key = s_key[i];
+        if (key != 0ull && (key & above) == thr) atomicAdd(&sh.hist[(int)((key >> (8 * pass)) & 0xffull)], 1);
+      }
+      __syncthreads();
+      // thread d: how many keys of the prefix have a byte above d; byte d holds the wanted key iff gt < rest <= gt + h
+      const int h = sh.hist[tid];
+      int total;
+      const int lt = select_scan(h, sh.wave_sum, total);
+      const int gt = total - lt - h;
+      if (gt < rest && rest <= gt + h) sh.digit = tid, sh.rest = rest - gt;  // exactly one thread: rest is in 1..total
+      __syncthreads();
+      thr |= (unsigned long long)sh.digit << (8 * pass);
+      rest = sh.rest;
+      // (the next pass's barrier behind the clearing of hist orders these reads before the next writes of digit / rest)
+    }
+    take_eq = rest;
+  }
+
+  // ties in ascending flat index: an ordered prefix count of the keys equal to the threshold
+  int eq = 0;
+  for (int i = lo; i < hi; ++i) eq += (binds && s_key[i] == thr) ? 1 : 0;
+  int eq_total;
+  int eq_rank = select_scan(eq, sh.wave_sum, eq_total);
+  int sel = 0;
+  for (int i = lo; i < hi; ++i) {
+    const unsigned long long key = s_key[i];
+    bool take = key > thr;
+    if (binds && key == thr) take = eq_rank < take_eq, eq_rank += 1;
+    sel += take ? 1 : 0;
+  }
+  int n_sel;
+  int r = select_scan(sel, sh.wave_sum, n_sel);
+  eq_rank -= eq;  // back to the thread's first
+  for (int i = lo; i < hi; ++i) {
+    const unsigned long long key = s_key[i];
+    bool take = key > thr;
+    if (binds && key == thr) take = eq_rank < take_eq, eq_rank += 1;
+    rank_of[i] = take ? r : -1;
+    if (take) {
+      due_idx[r] = i;
+      if (last_t != nullptr && slot_of[i] >= 0) last_t[slot_of[i]] = waited[(size_t)i * stride + 1];
+      r += 1;
+    }
+  }
+  for (int i = n_sel + tid; i < n; i += SELECT_THREADS) due_idx[i] = -1;
+  if (tid == 0) *n_due = n_sel, *n_deferred = cands - n_sel;
+}
+
+void select_launch(const double* waited, int stride, const int32_t* due_flag, int n, int budget, const int32_t* slot_of, double* last_t,
+                   int32_t* due_idx, int32_t* rank_of, int32_t* n_due, int32_t* n_deferred, hipStream_t s) {
+  const size_t lds = (size_t)n * sizeof(unsigned long long) + sizeof(SelectShared);
+  lds_opt_in<track_select_kernel>(lds, (int)(SELECT_MAX_SLOTS * sizeof(unsigned long long) + sizeof(SelectShared)));
+  hipLaunchKernelGGL(track_select_kernel, dim3(1), dim3(SELECT_THREADS), lds, s, waited, stride, due_flag, n, budget, slot_of, last_t, due_idx,
+                     rank_of, n_due, n_deferred);
+  HIP_OK(hipGetLastError());
+}
+
+// row r < n_due: avg = w z + (1 - w) avg in f32 (avg = z the first time, then the same formula), q[r] = avg;
+// pad (a budget handle): q rows behind n_due are zeroed, so that the match never reads what nobody wrote
 __global__ __launch_bounds__(128) void track_commit_kernel(const float* __restrict__ z, float* __restrict__ q, const int32_t* __restrict__ due_idx,
                                                            const int32_t* __restrict__ n_due, const int32_t* __restrict__ slot_of,
                                                            int32_t* __restrict__ ints, float* __restrict__ avg_z, int T, int dim, float w,
-                                                           float omw) {
-  const int r = blockIdx.x;  // (the grid is min(rows of z, F * K) blocks)
-  if (r >= *n_due) return;
+                                                           float omw, int pad) {
+  const int r = blockIdx.x;  // (the grid is min(rows of z, F * K) blocks; with pad every row of z)
+  if (r >= *n_due) {  // (the whole block)
+    if (pad)
+      for (int c = threadIdx.x; c < dim; c += 128) q[(size_t)r * dim + c] = 0.f;
+    return;
+  }
   const int slot = slot_of[due_idx[r]];
   if (slot < 0) return;  // (cannot happen: a due slot has a track)
   int32_t* has = ints + (size_t)(slot / T) * TRACK_INTS * T + 5 * T + slot % T;
@@ -483,16 +650,25 @@ __global__ __launch_bounds__(256) void track_reset_kernel(State st, float* __res
   }
 }
 
-// dst row r = src row due_idx[r], r < min(n_due, max_rows); 16 bytes per thread where the rows allow it
+// dst row r = src row due_idx[r], r < min(n_due, max_rows); 16 bytes per thread where the rows allow it; pad: the rows
+// behind n_due are zeroed
 __global__ __launch_bounds__(256) void track_gather_u8_kernel(const uint8_t* __restrict__ src, long src_rows, long row_bytes,
                                                               const int32_t* __restrict__ due_idx, const int32_t* __restrict__ n_due,
-                                                              uint8_t* __restrict__ dst, int vec) {
+                                                              uint8_t* __restrict__ dst, int vec, int pad) {
   const int r = blockIdx.x;
-  if (r >= *n_due) return;
+  uint8_t* b = dst + (long)r * row_bytes;
+  if (r >= *n_due) {
+    if (pad && vec) {
+      uint4* b4 = (uint4*)b;
+      for (long c = (long)blockIdx.y * 256 + threadIdx.x; c < row_bytes / 16; c += (long)gridDim.y * 256) b4[c] = make_uint4(0u, 0u, 0u, 0u);
+    } else if (pad) {
+      for (long c = (long)blockIdx.y * 256 + threadIdx.x; c < row_bytes; c += (long)gridDim.y * 256) b[c] = 0;
+    }
+    return;
+  }
   const long i = due_idx[r];
   if (i < 0 || i >= src_rows) return;
   const uint8_t* a = src + i * row_bytes;
-  uint8_t* b = dst + (long)r * row_bytes;
   if (vec) {
     const uint4* a4 = (const uint4*)a;
     uint4* b4 = (uint4*)b;
@@ -538,8 +714,18 @@ mtgv_tracker_cfg tracker_resolve_cfg(const mtgv_tracker_cfg& in, int32_t flags) 
   return c;
 }
 
-Tracker::Tracker(const mtgv_tracker_cfg& c, int32_t flags) : c_(tracker_resolve_cfg(c, flags)), wide_((flags & MTGV_TRACKER_WIDE) != 0) {
+int tracker_check_budget(int embed_budget) {
+  MTGV_CHECK(embed_budget >= 1 && embed_budget <= 65535, ERR_INVALID, "tracker: embed_budget %d outside 1..65535", embed_budget);
+  return embed_budget;
+}
+
+Tracker::Tracker(const mtgv_tracker_cfg& c, int32_t flags, int embed_budget)
+    : c_(tracker_resolve_cfg(c, flags)), wide_((flags & MTGV_TRACKER_WIDE) != 0), budget_(embed_budget == 0 ? 0 : tracker_check_budget(embed_budget)) {
   const size_t S = c_.streams, T = c_.max_tracks, K = c_.cards_per_frame;
+  if (budget_ > 0) {  // the candidate records of a step: never more slots than the selection takes
+    dev_alloc(defer_, 2 * std::min<size_t>(S * K, SELECT_MAX_SLOTS));
+    dev_alloc(n_deferred_, 1);
+  }
   dev_alloc(kal_, S * TRACK_KAL * T);
   dev_alloc(ints_, S * TRACK_INTS * T);
   dev_alloc(last_t_, S * T);
@@ -556,7 +742,7 @@ Tracker::Tracker(const mtgv_tracker_cfg& c, int32_t flags) : c_(tracker_resolve_
 
 Tracker::~Tracker() {
   for (void* p : {(void*)kal_, (void*)ints_, (void*)last_t_, (void*)avg_z_, (void*)m_ids_, (void*)m_scores_, (void*)ctrs_, (void*)slot_of_,
-                  (void*)due_flag_, (void*)rank_of_})
+                  (void*)due_flag_, (void*)rank_of_, (void*)defer_, (void*)n_deferred_})
     if (p != nullptr) (void)hipFree(p);
 }
 
@@ -570,10 +756,13 @@ void Tracker::reset(int stream_or_all, hipStream_t s) {
 }
 
 void Tracker::update(const float* quads, const int32_t* n_det, const int32_t* state, int frames, const int32_t* stream_of_frame, const double* now,
-                     int32_t* track_id, int32_t* due_idx, int32_t* n_due, hipStream_t s) {
+                     int32_t* track_id, int32_t* due_idx, int32_t* n_due, int32_t* n_deferred, hipStream_t s) {
   MTGV_CHECK(quads && stream_of_frame && now && track_id && due_idx && n_due, ERR_INVALID, "tracker: null argument");
   MTGV_CHECK(n_det != nullptr || state != nullptr, ERR_INVALID, "tracker: one of n_det and state must be given");
   MTGV_CHECK(frames >= 1 && frames <= c_.streams, ERR_INVALID, "tracker: %d frames for %d streams", frames, c_.streams);
+  MTGV_CHECK(budget_ > 0 || n_deferred == nullptr, ERR_INVALID, "tracker: n_deferred on a handle without an embed budget");
+  MTGV_CHECK(budget_ == 0 || (long)frames * c_.cards_per_frame <= SELECT_MAX_SLOTS, ERR_INVALID,
+             "tracker: a step of %d x %d slots on a budget handle (at most %d)", frames, c_.cards_per_frame, SELECT_MAX_SLOTS);
   std::set<int32_t> seen;
   for (int f = 0; f < frames; ++f) {
     MTGV_CHECK(stream_of_frame[f] >= 0 && stream_of_frame[f] < c_.streams, ERR_INVALID, "tracker: frame %d names stream %d outside [0, %d)", f,
@@ -588,13 +777,23 @@ void Tracker::update(const float* quads, const int32_t* n_det, const int32_t* st
     const int n = std::min(FRAMES_PER_LAUNCH, frames - f0);
     FrameArgs fr = {};
     for (int i = 0; i < n; ++i) fr.stream[i] = stream_of_frame[f0 + i], fr.now[i] = now[f0 + i];
-    if (wide_)
-      hipLaunchKernelGGL(track_update_wide_kernel, dim3(n), dim3(64 * ceil_div(c_.max_tracks, 64)), 0, s, st, p, fr, f0, quads, n_det, state, track_id,
-                         slot_of_, due_flag_);
+    const dim3 wide_block(64 * ceil_div(c_.max_tracks, 64));
+    if (wide_ && budget_ > 0)
+      hipLaunchKernelGGL(track_update_wide_kernel<double*>, dim3(n), wide_block, 0, s, st, p, fr, f0, quads, n_det, state, track_id, slot_of_, due_flag_,
+                         defer_);
+    else if (wide_)
+      hipLaunchKernelGGL(track_update_wide_kernel<>, dim3(n), wide_block, 0, s, st, p, fr, f0, quads, n_det, state, track_id, slot_of_, due_flag_);
+    else if (budget_ > 0)
+      hipLaunchKernelGGL(track_update_kernel<double*>, dim3(n), dim3(64), 0, s, st, p, fr, f0, quads, n_det, state, track_id, slot_of_, due_flag_,
+                         defer_);
     else
-      hipLaunchKernelGGL(track_update_kernel, dim3(n), dim3(64), 0, s, st, p, fr, f0, quads, n_det, state, track_id, slot_of_, due_flag_);
+      hipLaunchKernelGGL(track_update_kernel<>, dim3(n), dim3(64), 0, s, st, p, fr, f0, quads, n_det, state, track_id, slot_of_, due_flag_);
   }
-  hipLaunchKernelGGL(track_compact_kernel, dim3(1), dim3(64), 0, s, due_flag_, frames * c_.cards_per_frame, due_idx, rank_of_, n_due);
+  if (budget_ > 0)
+    select_launch(defer_, 2, due_flag_, frames * c_.cards_per_frame, budget_, slot_of_, last_t_, due_idx, rank_of_, n_due,
+                  n_deferred != nullptr ? n_deferred : n_deferred_, s);
+  else
+    hipLaunchKernelGGL(track_compact_kernel, dim3(1), dim3(64), 0, s, due_flag_, frames * c_.cards_per_frame, due_idx, rank_of_, n_due);
   HIP_OK(hipGetLastError());
   frames_ = frames, due_idx_ = due_idx, n_due_ = n_due;
 }
@@ -603,8 +802,10 @@ void Tracker::commit(const float* z, float* q, int rows, hipStream_t s) {
   MTGV_CHECK(z && q && rows >= 1, ERR_INVALID, "tracker: null argument or no rows");
   MTGV_CHECK(frames_ > 0, ERR_INVALID, "tracker: commit without an update");
   const double w = c_.ewma_weight;
-  hipLaunchKernelGGL(track_commit_kernel, dim3(std::min(rows, frames_ * c_.cards_per_frame)), dim3(128), 0, s, z, q, due_idx_, n_due_, slot_of_, ints_, avg_z_,
-                     c_.max_tracks, c_.dim, (float)w, (float)(1.0 - w));
+  const int pad = budget_ > 0 ? 1 : 0;  // a budget handle's q is matched whole: every row is written, one block each
+  MTGV_CHECK(!pad || rows <= 65535, ERR_INVALID, "tracker: commit of %d rows on a budget handle (at most 65535)", rows);
+  hipLaunchKernelGGL(track_commit_kernel, dim3(pad ? rows : std::min(rows, frames_ * c_.cards_per_frame)), dim3(128), 0, s, z, q, due_idx_, n_due_,
+                     slot_of_, ints_, avg_z_, c_.max_tracks, c_.dim, (float)w, (float)(1.0 - w), pad);
   HIP_OK(hipGetLastError());
 }
 
@@ -635,15 +836,23 @@ void Tracker::get_state(int stream, double* kal, int32_t* ints, double* last_t, 
   get(ctrs, ctrs_ + i * TRACK_CTRS, TRACK_CTRS * sizeof(int32_t));
 }
 
+void tracker_select_launch(const double* waited, int n, int budget, int32_t* due_idx, int32_t* rank_of, int32_t* n_due, int32_t* n_deferred,
+                           hipStream_t s) {
+  MTGV_CHECK(waited && due_idx && rank_of && n_due && n_deferred, ERR_INVALID, "track_select: null argument");
+  MTGV_CHECK(n >= 1 && n <= SELECT_MAX_SLOTS, ERR_INVALID, "track_select: n %d outside 1..%d", n, SELECT_MAX_SLOTS);
+  (void)tracker_check_budget(budget);
+  select_launch(waited, 1, nullptr, n, budget, nullptr, nullptr, due_idx, rank_of, n_due, n_deferred, s);
+}
+
 void tracker_gather_u8_launch(const uint8_t* src, int64_t src_rows, int64_t row_bytes, const int32_t* due_idx, const int32_t* n_due, int max_rows,
-                              uint8_t* dst, hipStream_t s) {
+                              uint8_t* dst, bool pad, hipStream_t s) {
   MTGV_CHECK(src && due_idx && n_due && dst, ERR_INVALID, "tracker_gather: null argument");
   MTGV_CHECK(src_rows >= 0 && row_bytes > 0 && max_rows >= 0 && max_rows <= 65535, ERR_INVALID, "tracker_gather: bad shape");
   if (max_rows == 0) return;
   const int vec = row_bytes % 16 == 0 && (uintptr_t)src % 16 == 0 && (uintptr_t)dst % 16 == 0;
   const long units = vec ? row_bytes / 16 : row_bytes;
   const int gy = (int)std::min<long>(std::max<long>(1, units / 1024), 32);
-  hipLaunchKernelGGL(track_gather_u8_kernel, dim3(max_rows, gy), dim3(256), 0, s, src, (long)src_rows, (long)row_bytes, due_idx, n_due, dst, vec);
+  hipLaunchKernelGGL(track_gather_u8_kernel, dim3(max_rows, gy), dim3(256), 0, s, src, (long)src_rows, (long)row_bytes, due_idx, n_due, dst, vec, pad ? 1 : 0);
   HIP_OK(hipGetLastError());
 }
 

@@ -182,7 +182,8 @@ class Matcher:
         return packed
 
     def prepass_fallbacks(self) -> int:
-        """Queries of two-pass matches (>= 128 queries per call) that had to be scanned exactly so far (include/mtgv.h)."""
+        """Queries of two-pass matches (>= 128 queries per call) that had to be scanned exactly so far (include/mtgv.h).
+        An all-zero query is not among them: its answer (the k first rows at score 0) needs no scan and is given directly."""
         v = native.c_i64(0)
         native.check(native.lib().mtgv_bank_prepass_fallbacks(self._h, C.byref(v)))
         return int(v.value)

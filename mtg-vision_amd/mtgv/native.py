@@ -235,13 +235,17 @@ SIGNATURES = {
     "mtgv_op_l2norm": (C.c_int, [c_vp, c_vp, c_i64, c_i32, c_vp]),
     "mtgv_tracker_create": (C.c_int, [C.POINTER(TrackerCfg), C.POINTER(c_vp)]),
     "mtgv_tracker_create_ex": (C.c_int, [C.POINTER(TrackerCfg), c_i32, C.POINTER(c_vp)]),  # mtgv_version >= 110
+    "mtgv_tracker_create_budget": (C.c_int, [C.POINTER(TrackerCfg), c_i32, c_i32, C.POINTER(c_vp)]),  # mtgv_version >= 115
     "mtgv_tracker_destroy": (None, [c_vp]),
     "mtgv_tracker_reset": (C.c_int, [c_vp, c_i32, c_vp]),
     "mtgv_tracker_update": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mtgv_tracker_update_budget": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),  # >= 115
     "mtgv_tracker_gather_u8": (C.c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp]),
+    "mtgv_tracker_gather_u8_pad": (C.c_int, [c_vp, c_i64, c_i64, c_vp, c_vp, c_i32, c_vp, c_vp]),  # >= 115
     "mtgv_tracker_commit": (C.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp]),
     "mtgv_tracker_store": (C.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "mtgv_tracker_get_state": (C.c_int, [c_vp, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "mtgv_op_track_select": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp]),  # mtgv_version >= 115
 }
 
 _lib = None

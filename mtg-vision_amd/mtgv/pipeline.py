@@ -7,6 +7,7 @@ batch of frames goes through each stage once; every stage's arithmetic is in lib
 
 from __future__ import annotations
 
+import contextlib
 import os
 from dataclasses import dataclass
 from typing import Callable, Optional
@@ -338,6 +339,14 @@ class Pipeline:
         section 5 - and tests/test_gpu_overlap.py guards the combination.)"""
         if not self.overlap_enabled():
             return [self.run(frames, flip_rgb) for frames in batches]
+        crop_on_det, s_match, cur = self._overlap_streams()
+        with self._det_fork_off():
+            return self._run_overlapped(batches, flip_rgb, crop_on_det, s_match, cur)
+
+    def _overlap_streams(self):
+        """the streams of the overlapped schedules (run_many here and TrackedPipeline.run_many), created on first use:
+        self._s_det, self._s_enc and the match stream, each waiting for the current stream
+        -> (crop_on_det, s_match or None, the current stream)"""
         dev = self.detector.device
         if not hasattr(self, "_s_det"):
             # The embed + match stream runs at high priority: it is the longer chain (6 of a step's 8 ms), so its kernels get the
@@ -366,6 +375,10 @@ class Pipeline:
         cur = torch.cuda.current_stream(dev)
         self._s_det.wait_stream(cur)
         self._s_enc.wait_stream(cur)
+        return crop_on_det, s_match, cur
+
+    @contextlib.contextmanager
+    def _det_fork_off(self):
         # The detector's own fork-join is for the one-stream schedule (its late layers alone on 256 CUs); here the embed stream
         # fills those gaps, and the branch streams would only add normal-priority streams to the few hardware queues:
         # 8.05 vs 8.3 ms per step with it off, whatever the handle creation order (MTGV_OVERLAP_DET_FORK=1: left on)
@@ -373,7 +386,7 @@ class Pipeline:
         if fork_off:
             self.detector.set_fork(0)
         try:
-            return self._run_overlapped(batches, flip_rgb, crop_on_det, s_match, cur)
+            yield
         finally:
             if fork_off:
                 self.detector.set_fork(-1)

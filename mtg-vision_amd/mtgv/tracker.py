@@ -256,6 +256,23 @@ class KalmanPointTracker:
         return sorted(out)
 
 
+def select_due(waited, budget: int) -> np.ndarray:
+    """The embed budget's selection rule, the specification of csrc/track.hip's track_select_kernel.
+
+    waited: one float64 per flat slot i = f * K + k of a step, NaN for a slot that is no candidate.  A slot is a candidate
+    when its track is due (reported, and without an embedding or with more than update_wait_sec since its last one); its
+    key is the time it has waited, `now - last_update_time` as the gate computes it, +inf for a track that was never
+    embedded.  -> the min(budget, candidates) candidates with the largest key, ties to the smaller index, as int64 indices
+    in ascending order (the order of due_idx).  With budget >= candidates that is every candidate.  The tracks that are
+    left out stay due and their keys grow with every step: under a lasting overload of C candidates a track is taken
+    after at most ceil(C / budget) steps."""
+    w = np.asarray(waited, dtype=np.float64).reshape(-1)
+    assert int(budget) >= 1, f"budget {budget}"
+    cand = np.flatnonzero(~np.isnan(w))
+    order = cand[np.lexsort((cand, -w[cand]))]  # key descending, then index ascending
+    return np.sort(order[: int(budget)]).astype(np.int64)
+
+
 class TrackerCtx:
     def __init__(self, update_wait_sec: float = 0.5, ewma_weight: float = 0.1, *, segmenter, encoder, vecs, data=None,
                  clock: Callable[[], float] = time.time, thumbnails: bool = True, jpeg_encoder=None):

@@ -13,6 +13,10 @@ are whatever the random-weight detector sees in noise; the association is real w
                                 [--cards K --max-tracks T --wide auto|on|off]   the tracker's size and update kernel
                                 [--synthetic]   and the launches again in a synthetic steady state: T live tracks per stream,
                                                 disjoint sets of K cards in rotation, every detection matched
+                                [--embed-budget E [E ...]]   (3) again with an embed budget: at most E embeds per step, the
+                                                encoder and the matcher on exactly E rows, no read-back (line (4)); and
+                                                update + selection beside update + compaction
+                                [--overlap]     each budget also through TrackedPipeline.run_many with MTGV_OVERLAP=on (line (5))
 """
 from __future__ import annotations
 
@@ -77,6 +81,51 @@ def _synthetic(F, K, T, wide, crops, encoder, matcher):
             f"commit {ms_commit * 1e3:.1f} us, store {ms_store * 1e3:.1f} us")
 
 
+def _budget(a, pipe, streams, batches, T, wide, E, quads, n_det):
+    """(3)'s steady state with an embed budget E: one stream (4) and, with --overlap, run_many's three streams (5); then
+    update + selection on (2)'s detections with every detection due"""
+    from mtgv.track import DeviceTracker, TrackedPipeline
+
+    F, K = a.frames, a.cards
+    out_lines = []
+    for label, overlap in [("(4) TrackedPipeline.run", False)] + ([("(5) TrackedPipeline.run_many", True)] if a.overlap else []):
+        os.environ["MTGV_OVERLAP"] = "on" if overlap else "off"
+        tp = TrackedPipeline(pipe, streams=F, top_k=3, max_tracks=T, wide=wide, embed_budget=E)
+        clock, outs = [0.0], []
+
+        def chunk(n):
+            steps = []
+            for i in range(n):
+                clock[0] += 1.0 / 30.0
+                steps.append((batches[i % 4], streams, clock[0]))
+            return steps
+
+        def run(n):
+            outs.extend(tp.run_many(chunk(n)) if overlap else [tp.run(*st) for st in chunk(n)])
+
+        _timed(lambda i: run(4), max(a.warmup, 20) // 4 + 1)
+        del outs[:]
+        ms, _ = _timed(lambda i: run(a.steps), 1)
+        ms /= a.steps
+        due = np.array([int(o["n_due"].item()) for o in outs])
+        deferred = np.array([int(o["n_deferred"].item()) for o in outs])
+        out_lines.append(f"{label}, embed_budget {E:3d}, {'three streams' if overlap else 'one stream   '} {ms:7.3f} ms/step  {F * K / ms * 1e3:9.0f} cards/s  "
+                         f"embeds/step {due.mean():6.1f} of {E} rows (max {due.max()}), deferred/step {deferred.mean():5.1f} (max {deferred.max()})")
+    os.environ["MTGV_OVERLAP"] = "off"
+    trk = DeviceTracker(F, K, 768, 3, max_tracks=T, wide=wide, embed_budget=E, update_wait_sec=0.0, initialization_delay=0)
+    t = [2e3]
+
+    def upd(i):
+        t[0] += 1.0
+        return trk.update(quads, streams, t[0], n_det=n_det)
+
+    _timed(upd, 5)
+    ms_upd, (_, _, n_due_dev) = _timed(upd, 50)
+    out_lines.append(f"    update + selection (2 launches) at {int(n_due_dev.item())} selected, {int(trk.n_deferred.item())} deferred: {ms_upd * 1e3:.1f} us "
+                     f"(mean of 50 back-to-back calls, host call overhead included)")
+    return out_lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--frames", type=int, default=32)
@@ -88,6 +137,8 @@ def main():
     ap.add_argument("--max-tracks", type=int, default=64)
     ap.add_argument("--wide", choices=("auto", "on", "off"), default="auto", help="the multi-wave update kernel: by size, forced, refused")
     ap.add_argument("--synthetic", action="store_true")
+    ap.add_argument("--embed-budget", type=int, nargs="*", default=[], help="embed budgets E to time in the gated steady state")
+    ap.add_argument("--overlap", action="store_true", help="also time TrackedPipeline.run_many with MTGV_OVERLAP=on for every budget")
     ap.add_argument("--out", default=None)
     a = ap.parse_args()
 
@@ -171,6 +222,8 @@ def main():
     lines.append(f"tracker launches at n_due = {n_due} (mean of {n} back-to-back calls, host call overhead included): update + compaction (2 launches) "
                  f"{ms_upd * 1e3:.1f} us, n_due read-back {ms_read * 1e3:.1f} us, gather {ms_gather * 1e3:.1f} us, commit {ms_commit * 1e3:.1f} us, "
                  f"store {ms_store * 1e3:.1f} us; sum {(ms_upd + ms_read + ms_gather + ms_commit + ms_store) * 1e3:.1f} us; (2) - (1) = {(ms2 - ms1) * 1e3:.0f} us")
+    for E in a.embed_budget:
+        lines.extend(_budget(a, pipe, streams, batches, T, wide, E, quads, n_det))
     if a.synthetic:
         lines.append(_synthetic(F, K, T, wide, crops, encoder, matcher))
     text = "\n".join(lines)
