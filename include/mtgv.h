@@ -39,7 +39,8 @@ MTGV_API const char* mtgv_last_error(void);
 /* 110: mtgv_tracker_create_ex / MTGV_TRACKER_WIDE (256 tracks per stream, 64 cards per frame)
  * 111: mtgv_letterbox_ragged_u8, mtgv_warp_quads_src (crops from full-resolution source frames)
  * 115: the embed budget of the tracker (mtgv_tracker_create_budget, mtgv_tracker_update_budget, mtgv_tracker_gather_u8_pad,
- *      mtgv_op_track_select) */
+ *      mtgv_op_track_select)
+ * 116: mtgv_op_mask_logits (the detector's mask stage as a single op) */
 MTGV_API int mtgv_version(void);
 /* number of HIP devices visible; does not initialise a device context */
 MTGV_API int mtgv_device_count(void);
@@ -629,6 +630,16 @@ typedef struct {
 /* path, unless NULL, receives {tile configuration, A mode, epilogue id, ring depth} of the launch that ran (the
  * values of gemm_sp_cfg.h); configuration -1 (the rest 0): the convert-on-load kernel. */
 MTGV_API int mtgv_op_conv2d_ex(const mtgv_conv_ex* d, int32_t* path, void* stream);
+/* The detector's mask stage alone (version 116; Detector::head_tail runs the same function): out[z][m][px] =
+ * <coef[z][m], protos[z][px]> where pixel px = (py, px) of the mh x mw map lies inside box m scaled by crop_scale (x1 <= px < x2,
+ * y1 <= py < y2, the products box * crop_scale rounded to f32), 0 outside, and 0 in every row m >= min(n_det[z], mask_rows).
+ * coef (n, max_det, nm), protos NHWC (n, mh * mw, nm), n_det (n) int32, boxes (n, max_det, 4) xyxy, out (n, mask_rows, mh * mw),
+ * all on the device, f32; nm a multiple of 4, 0 < mask_rows <= max_det.  form 0: the kernel the detector would choose for
+ * these sizes; 1: the per-pixel kernel (one pass over the prototypes); 2: the batched GEMM behind a clearing memset.  Status 1,
+ * and nothing launched, where the form cannot run: form 1 with nm != 32 or mask_rows > 16. */
+MTGV_API int mtgv_op_mask_logits(const float* coef_dev, const float* protos_dev, const int32_t* n_det_dev, const float* boxes_dev,
+                                 int32_t n, int32_t max_det, int32_t nm, int32_t mh, int32_t mw, float crop_scale, int32_t mask_rows,
+                                 int32_t form, float* out_dev, void* stream);
 /* The detector's stem alone (version 103): Conv(3 -> cout, k3, s2, p1) + SiLU straight from uint8 frames (n, h, w, 3), h even,
  * w a multiple of 8, frames 8-byte and out 128-byte aligned; w_dev [cout][3][3][4] with BatchNorm folded and a zero 4th
  * input channel, out (n, h / 2, w / 2, cout) in SP8 (out_sp8) or f32.  cout 16 runs scale n's kernel, 32 / 48 / 64 the wide

@@ -108,7 +108,8 @@ MTGV_API const char* mtgv_last_error(void) { return last_error_cstr(); }
 // 113: mtgv_op_dwconv7_ln, mtgv_op_dwconv7_ln_form (the fused depthwise 7x7 + LayerNorm as a single op, and its kernel form)
 // 114: mtgv_op_psa_attn, mtgv_op_dwconv3 (YOLO11's C2PSA attention and the depthwise 3x3 as single ops)
 // 115: the embed budget (mtgv_tracker_create_budget, mtgv_tracker_update_budget, mtgv_tracker_gather_u8_pad, mtgv_op_track_select)
-MTGV_API int mtgv_version(void) { return 115; }
+// 116: mtgv_op_mask_logits (the detector's mask stage as a single op)
+MTGV_API int mtgv_version(void) { return 116; }
 MTGV_API int mtgv_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;

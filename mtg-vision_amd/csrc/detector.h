@@ -111,6 +111,24 @@ ProtoTailW proto_tail_weights(const float* wt, const float* bt, int c, int mid, 
 bool proto_tail_launch(const ProtoTailW& w, const View& pr1, const View& pr2, const View& pr3, const View& protos, int n, bool fold,
                        hipStream_t s);
 
+// The mask stage (process_mask / crop_mask): out[z][m][px] = <coef[z][m], protos[z][px]> inside box m * crop_scale, 0 outside
+// and in rows m >= min(n_det[z], mask_rows).  coef [n][max_det][nm], protos NHWC [n][mh * mw][nm], boxes [n][max_det][4],
+// out [n][mask_rows][mh * mw].  MASK_FORM_AUTO takes the per-pixel kernel where it can run, else the batched GEMM.
+enum { MASK_FORM_AUTO = 0, MASK_FORM_PIXELS = 1, MASK_FORM_GEMM = 2 };
+struct MaskLogitsArgs {
+  const float* coef;
+  const float* protos;
+  const int* n_det;
+  const float* boxes;
+  int n, max_det, nm, mh, mw;
+  float crop_scale;
+  int mask_rows;
+  float* out;
+};
+// mask_logits_kernel (detector_kernel.h) holds 16 rows of 32 coefficients
+inline bool mask_logits_pixels_ok(int nm, int mask_rows) { return nm == 32 && mask_rows <= 16; }
+void mask_logits_launch(const MaskLogitsArgs& a, int form, hipStream_t s);
+
 class Detector {
  public:
   explicit Detector(const mtgv_detector_cfg& cfg);

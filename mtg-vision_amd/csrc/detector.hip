@@ -667,31 +667,44 @@ void Detector::head_tail(int n, int* n_det, float* boxes, float* conf, int* cls,
   }
   join_into(s, 0);  // the prototype branch ran beside the heads, decode and NMS (one workgroup per frame: 32 of 256 CUs)
   if (mask_logits != nullptr) {
-    // masks = coeffs @ protos^T per image, cropped to the box (process_mask / crop_mask)
     const View pr = view("protos");
-    const int npx = pr.H * pr.W;
     // the prototypes are a quarter of the input in both directions: one crop scale (pr.W / in_w, = pr.H / in_h)
     const float crop_scale = (float)pr.W / (float)cfg_.in_w;
-    if (nm_ == 32 && mask_rows <= 16 && !count_flops_) {  // a handful of masks per frame: one pass over the prototypes
-      hipLaunchKernelGGL(mask_logits_kernel, dim3((unsigned)((npx + 255) / 256), (unsigned)n), dim3(256), 0, s, coef, pr.p, n_det, boxes,
-                         mask_logits, npx, pr.W, mask_rows, cfg_.max_det, crop_scale);
-      HIP_OK(hipGetLastError());
-      return;
-    }
-    // the batched GEMM writes only the rows of kept detections: the rest is cleared first
-    HIP_OK(hipMemsetAsync(mask_logits, 0, (size_t)n * mask_rows * npx * sizeof(float), s));
-    GemmArgs g = linear_args(coef, nm_, pr.p, nullptr, mask_logits, npx, mask_rows, npx, nm_, ACT_NONE);
-    g.batch = n;
-    g.strideA = (long)cfg_.max_det * nm_;
-    g.strideW = (long)npx * nm_;
-    g.strideO = (long)mask_rows * npx;
-    g.m_count = n_det;
-    g.crop_boxes = boxes;
-    g.crop_rows = cfg_.max_det;
-    g.crop_scale = crop_scale;
-    g.crop_w = pr.W;
-    gemm_launch(g, s);
+    // (the FLOP count is of GEMM launches: it takes the batched GEMM at every size)
+    mask_logits_launch({coef, pr.p, n_det, boxes, n, cfg_.max_det, nm_, pr.H, pr.W, crop_scale, mask_rows, mask_logits},
+                       count_flops_ ? MASK_FORM_GEMM : MASK_FORM_AUTO, s);
   }
+}
+
+// masks = coeffs @ protos^T per image, cropped to the box (process_mask / crop_mask)
+void mask_logits_launch(const MaskLogitsArgs& a, int form, hipStream_t s) {
+  MTGV_CHECK(form == MASK_FORM_AUTO || form == MASK_FORM_PIXELS || form == MASK_FORM_GEMM, ERR_INVALID, "mask_logits: form=%d", form);
+  MTGV_CHECK(a.coef && a.protos && a.n_det && a.boxes && a.out, ERR_INVALID, "mask_logits: null tensor");
+  MTGV_CHECK(a.n > 0 && a.n <= 65535 && a.nm > 0 && a.mh > 0 && a.mw > 0 && a.mask_rows > 0 && a.mask_rows <= a.max_det, ERR_INVALID,
+             "mask_logits: n=%d nm=%d map %d x %d mask_rows=%d max_det=%d", a.n, a.nm, a.mh, a.mw, a.mask_rows, a.max_det);
+  const bool pixels_ok = mask_logits_pixels_ok(a.nm, a.mask_rows);
+  MTGV_CHECK(form != MASK_FORM_PIXELS || pixels_ok, ERR_INVALID, "mask_logits: the per-pixel kernel needs nm == 32 and mask_rows <= 16 (nm=%d, mask_rows=%d)",
+             a.nm, a.mask_rows);
+  const int npx = a.mh * a.mw;
+  if (form == MASK_FORM_PIXELS || (form == MASK_FORM_AUTO && pixels_ok)) {  // a handful of masks per frame: one pass over the prototypes
+    hipLaunchKernelGGL(mask_logits_kernel, dim3((unsigned)((npx + 255) / 256), (unsigned)a.n), dim3(256), 0, s, a.coef, a.protos, a.n_det,
+                       a.boxes, a.out, npx, a.mw, a.mask_rows, a.max_det, a.crop_scale);
+    HIP_OK(hipGetLastError());
+    return;
+  }
+  // the batched GEMM writes only the rows of kept detections: the rest is cleared first
+  HIP_OK(hipMemsetAsync(a.out, 0, (size_t)a.n * a.mask_rows * npx * sizeof(float), s));
+  GemmArgs g = linear_args(a.coef, a.nm, a.protos, nullptr, a.out, npx, a.mask_rows, npx, a.nm, ACT_NONE);
+  g.batch = a.n;
+  g.strideA = (long)a.max_det * a.nm;
+  g.strideW = (long)npx * a.nm;
+  g.strideO = (long)a.mask_rows * npx;
+  g.m_count = a.n_det;
+  g.crop_boxes = a.boxes;
+  g.crop_rows = a.max_det;
+  g.crop_scale = a.crop_scale;
+  g.crop_w = a.mw;
+  gemm_launch(g, s);
 }
 
 void Detector::forward(const uint8_t* frames, int n, int flip, int* n_det, float* boxes, float* conf, int* cls, int* keep_idx,
@@ -933,6 +946,14 @@ MTGV_API int mtgv_mask_binarize(const float* logits_dev, int32_t n, int32_t mh, 
                          out_dev, mh, mw, scale, npx);
     }
     HIP_OK(hipGetLastError());
+  });
+}
+MTGV_API int mtgv_op_mask_logits(const float* coef_dev, const float* protos_dev, const int32_t* n_det_dev, const float* boxes_dev,
+                                 int32_t n, int32_t max_det, int32_t nm, int32_t mh, int32_t mw, float crop_scale, int32_t mask_rows,
+                                 int32_t form, float* out_dev, void* stream) {
+  return guarded([&] {
+    mask_logits_launch({coef_dev, protos_dev, n_det_dev, boxes_dev, n, max_det, nm, mh, mw, crop_scale, mask_rows, out_dev}, form,
+                       (hipStream_t)stream);
   });
 }
 static HeadRows op_head_rows(const mtgv_head_rows* r) {

@@ -219,6 +219,7 @@ SIGNATURES = {
     "mtgv_op_linear_ex": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp]),
     "mtgv_op_conv2d": (C.c_int, [c_vp, c_vp, c_vp, c_vp] + [c_i32] * 10 + [c_vp]),
     "mtgv_op_conv2d_ex": (C.c_int, [C.POINTER(ConvEx), C.POINTER(c_i32), c_vp]),
+    "mtgv_op_mask_logits": (C.c_int, [c_vp] * 4 + [c_i32] * 5 + [c_f32, c_i32, c_i32, c_vp, c_vp]),  # mtgv_version >= 116
     "mtgv_op_stem_u8": (C.c_int, [c_vp, c_vp, c_vp, c_vp] + [c_i32] * 7 + [c_vp]),
     "mtgv_op_area_attn": (C.c_int, [c_vp, c_vp, c_vp] + [c_i32] * 5 + [c_vp, c_vp]),  # mtgv_version >= 109
     "mtgv_op_psa_attn": (C.c_int, [c_vp, c_vp, c_vp] + [c_i32] * 4 + [c_vp, c_vp]),  # mtgv_version >= 114

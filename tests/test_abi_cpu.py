@@ -41,7 +41,8 @@ def test_ctypes_table_matches_header(libpath):
 
     assert sorted(native.SIGNATURES) == _declared()
     L = native.lib()
-    assert L.mtgv_version() >= 100
+    assert L.mtgv_version() >= 116  # the newest entry of the table: mtgv_op_mask_logits
+    assert "mtgv_op_mask_logits" in native.SIGNATURES and len(native.SIGNATURES["mtgv_op_mask_logits"][1]) == 14
     assert L.mtgv_device_count() >= 0
 
 
