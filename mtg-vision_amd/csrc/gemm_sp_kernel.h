@@ -52,6 +52,22 @@
 //
 // The code names the A modes SP_A_* and the EPI values SP_EPI_*, and takes its LDS layout from the functions the host
 // sizes a launch with: gemm_sp_cfg.h.
+//
+// Where things are.  This file: SpDev, the helpers every part shares (sp_sw: row swizzle; sp_slots: the hi / lo fragment
+// slots of a k16 step; sp_pixel: m -> (img, oh, ow); sp_mfma3: the three products of a k16 step; sp_block_put / sp_block_get:
+// one accumulator column block through a wave's staging rows; sp_activate), and the kernel, whose body reads set-up, main
+// loop, pick the epilogue:
+//   gemm_sp_epi_chain.h   sp_epi_chain<PHASE>: the chained 1x1 and its phase form (EPI 32 / 96)
+//   gemm_sp_epi_topk.h    sp_epi_topk<LABELS>: the fused top-k, plain and labelled (EPI 16 / 17), one function
+// Still written in the kernel body, on purpose (the record of what each costs elsewhere: profiles/gemm_sp_phases.txt):
+//   - the DMA piece set-up with the `issue` / `issue_piece` lambdas, `wait_stage`, the register A loader and the window
+//     loader: they share the piece arrays and the ring, and the waits count the instructions they issue;
+//   - the four main-loop forms (window, fp16 rows, scheduled f32 rows, generic).  The generic loop takes sp_mfma3; the
+//     scheduled f32 loop spells its products itself, interleaved with its sched_group_barriers; the window loop keeps
+//     its accumulator-major order;
+//   - `load_colvecs`, a lambda called once (see its comment);
+//   - the staged store epilogue with its `load_res`, `flush` and `slab` lambdas, the two-round barriers of eight-wave
+//     blocks around it and the `stamps` tail: moved into a function it compiles to other code in every instance.
 #pragma once
 #include <type_traits>
 
@@ -135,6 +151,76 @@ inline int sp_epi_of(const SpDev& g) {
 typedef const __attribute__((address_space(1))) void* sp_gptr;
 typedef __attribute__((address_space(3))) void* sp_lptr;
 
+// ---- what the main loops and the epilogues share, each written once ----
+// Swizzle of a stage row: its 16-byte slot s sits at s ^ sp_sw<KS>(row).
+template <int KS>
+__device__ __forceinline__ int sp_sw(int row) {
+  return KS == 2 ? (row >> 1) & 7 : (row >> 2) & 3;
+}
+// Byte offsets, inside a stage row with swizzle sw, of the hi and lo fragments that half-wave h feeds k16 step ks.
+struct SpSlots {
+  unsigned hi, lo;
+};
+__device__ __forceinline__ SpSlots sp_slots(int ks, int h, unsigned sw) {
+  return {(unsigned)(((ks * 4 + h * 2 + 0) ^ sw) << 4), (unsigned)(((ks * 4 + h * 2 + 1) ^ sw) << 4)};
+}
+// Conv geometry: output row m -> (img, oh, ow).
+__device__ __forceinline__ void sp_pixel(const SpDev& g, uint32_t m, uint32_t& img, uint32_t& oh, uint32_t& ow) {
+  img = fdiv(m, g.d_ohw);
+  const uint32_t rem = m - img * (uint32_t)(g.OH * g.OW);
+  oh = fdiv(rem, g.d_ow);
+  ow = rem - oh * (uint32_t)g.OW;
+}
+// One k16 step of the split product: the small cross terms first, the hi*hi product last (per accumulator); each product
+// sweeps all accumulators before the next, so the three MFMAs of an accumulator are issued TM * TN instructions apart and
+// none waits on the one just before it.  (The scheduled f32 loop spells its own: its interleaving is its point.)
+template <int TM, int TN>
+__device__ __forceinline__ void sp_mfma3(spf16 (&acc)[TM][TN], const sp_h8 (&bh)[TN], const sp_h8 (&bl)[TN], const sp_h8 (&ah)[TM], const sp_h8 (&al)[TM]) {
+#pragma unroll
+  for (int j = 0; j < TN; ++j)
+#pragma unroll
+    for (int i = 0; i < TM; ++i) acc[i][j] = sp_mfma(bl[j], ah[i], acc[i][j]);
+#pragma unroll
+  for (int j = 0; j < TN; ++j)
+#pragma unroll
+    for (int i = 0; i < TM; ++i) acc[i][j] = sp_mfma(bh[j], al[i], acc[i][j]);
+#pragma unroll
+  for (int j = 0; j < TN; ++j)
+#pragma unroll
+    for (int i = 0; i < TM; ++i) acc[i][j] = sp_mfma(bh[j], ah[i], acc[i][j]);
+}
+// One accumulator column block through a wave's staging rows of SROW bytes.  Put: register group gq of lane (r, h) holds
+// columns 8 gq + 4 h + 0..3 of row r and goes to slot 8 j + 2 gq + h, swizzled by the row.  Get: 8 lanes per 128-byte
+// row segment - lane (lrow, slot) reads columns 32 j + 4 slot + 0..3 of row 8 it + lrow.  Same wave on both sides: LDS
+// operations of one wave execute in order, no barrier.
+template <int SROW>
+__device__ __forceinline__ void sp_block_put(char* stg, const spf16& a, int j, int r, int h) {
+#pragma unroll
+  for (int gq = 0; gq < 4; ++gq)
+    *reinterpret_cast<sp_f4*>(stg + r * SROW + (((j * 8 + gq * 2 + h) ^ (r & 7)) << 4)) = sp_f4{a[4 * gq], a[4 * gq + 1], a[4 * gq + 2], a[4 * gq + 3]};
+}
+template <int SROW>
+__device__ __forceinline__ sp_f4 sp_block_get(const char* stg, int j, int it, int lrow, int slot) {
+  return *reinterpret_cast<const sp_f4*>(stg + (it * 8 + lrow) * SROW + j * 128 + ((slot ^ lrow) << 4));
+}
+
+// The launch's activation: ACT fixes it at compile time, SP_ACT_ARGS reads it from the arguments.
+template <int ACT>
+__device__ __forceinline__ float sp_activate(float x, int act) {
+  if constexpr (ACT == ACT_NONE) return x;
+  else if constexpr (ACT == ACT_GELU) return act_gelu(x);
+  else if constexpr (ACT == ACT_MISH) return act_mish(x);
+  else if constexpr (ACT == ACT_SILU) return act_silu(x);
+  else return apply_act(x, act);
+}
+
+}  // namespace mtgv
+
+#include "gemm_sp_epi_chain.h"  // after the helpers above: the epilogues use them
+#include "gemm_sp_epi_topk.h"
+
+namespace mtgv {
+
 template <int WM, int WN, int TM, int TN, int KS, int NST, int AMODE, int ACT, int EPI>
 __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_kernel(const SpDev g) {
 #pragma clang fp contract(off)
@@ -199,8 +285,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
     const bool isA = p < PA;
     const int pp = isA ? p : p - PA;
     const int row = pp * RPP + lane / SPR;
-    const int sw = KS == 2 ? (row >> 1) & 7 : (row >> 2) & 3;
-    const int slot = (lane % SPR) ^ sw;
+    const int slot = (lane % SPR) ^ sp_sw<KS>(row);
     cslot[u] = slot, cih0[u] = 0, ciw0[u] = 0, csrc[u] = nullptr;
     {
       const int mm = m0 + row < g.M ? m0 + row : g.M - 1, nn = n0 + row < g.N ? n0 + row : g.N - 1;
@@ -210,10 +295,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
       int m = m0 + row;
       m = m < g.M ? m : g.M - 1;
       if constexpr (AMODE == SP_A_CONV) {
-        const uint32_t img = fdiv((uint32_t)m, g.d_ohw);
-        const uint32_t rem = (uint32_t)m - img * (uint32_t)(g.OH * g.OW);
-        const uint32_t oh = fdiv(rem, g.d_ow);
-        const uint32_t ow = rem - oh * (uint32_t)g.OW;
+        uint32_t img, oh, ow;
+        sp_pixel(g, (uint32_t)m, img, oh, ow);
         cih0[u] = (int)oh * g.stride - g.pad;
         ciw0[u] = (int)ow * g.stride - g.pad_w;
         csrc[u] = g.A + (((long)img * g.H + cih0[u]) * g.Wd + ciw0[u]) * g.a_rowb + g.a_offb + slot * 16;
@@ -314,8 +397,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
       m = m < g.M ? m : g.M - 1;
       a_ptr[v] = g.A + (long)m * g.a_rowb + g.a_offb + ch * 32;
       s_ptr[v] = g.a_scale != nullptr ? g.a_scale + (long)fdiv((uint32_t)m, g.d_hw) * g.K + ch * 8 : nullptr;
-      const int sw = KS == 2 ? (row >> 1) & 7 : (row >> 2) & 3;
-      a_lds[v] = (unsigned)(row * RB + (((2 * ch) ^ sw) << 4));  // hi piece; the lo piece sits at ^16
+      a_lds[v] = (unsigned)(row * RB + (((2 * ch) ^ sp_sw<KS>(row)) << 4));  // hi piece; the lo piece sits at ^16
       a_ch[v] = ch;
     }
   }
@@ -362,7 +444,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
       for (int pw = wave; pw < win_px / RPP; pw += NW) {
         const int w = pw * RPP + lane / SPR;
         const long gp = (long)m0 - g.Wd - 1 + w;
-        const int slot = (lane % SPR) ^ (KS == 2 ? (w >> 1) & 7 : (w >> 2) & 3);
+        const int slot = (lane % SPR) ^ sp_sw<KS>(w);
         const char* sp = (gp >= 0 && gp < (long)g.M) ? g.A + gp * g.a_rowb + g.a_offb + cc * RB + slot * 16 : g.zero;
         __builtin_amdgcn_global_load_lds((sp_gptr)sp, (sp_lptr)(smem + pw * 1024), 16, 0, 0);
       }
@@ -390,10 +472,9 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
     if constexpr (AWIN) {
       int m = m0 + wm * TM * 32 + i * 32 + r;
       m = m < g.M ? m : g.M - 1;
-      const uint32_t img = fdiv((uint32_t)m, g.d_ohw);
-      const uint32_t rem = (uint32_t)m - img * (uint32_t)(g.OH * g.OW);
-      wy[i] = (int)fdiv(rem, g.d_ow);
-      wx[i] = (int)(rem - (uint32_t)wy[i] * (uint32_t)g.OW);
+      uint32_t img, oh, ow;
+      sp_pixel(g, (uint32_t)m, img, oh, ow);
+      wy[i] = (int)oh, wx[i] = (int)ow;
     }
   }
 
@@ -405,7 +486,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
 #pragma unroll
       for (int q = 0; q < 16; ++q) acc[i][j][q] = 0.f;
 
-  const int swr = KS == 2 ? (r >> 1) & 7 : (r >> 2) & 3;
+  const int swr = sp_sw<KS>(r);
   unsigned a_off[TM], b_off[TN];
 #pragma unroll
   for (int i = 0; i < TM; ++i) a_off[i] = (unsigned)((wm * TM * 32 + i * 32 + r) * RB);
@@ -514,27 +595,29 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
           for (int i = 0; i < TM; ++i) {
             const int w = wm * TM * 32 + i * 32 + r + shift;
             w_off[i] = (unsigned)w * (unsigned)RB;
-            w_sw[i] = KS == 2 ? (unsigned)(w >> 1) & 7u : (unsigned)(w >> 2) & 3u;
+            w_sw[i] = (unsigned)sp_sw<KS>(w);
             w_ok[i] = (unsigned)(wy[i] + dy) < (unsigned)g.H && (unsigned)(wx[i] + dx) < (unsigned)g.Wd;
           }
 #pragma unroll
           for (int ks = 0; ks < KS; ++ks) {
-            const unsigned shi = (unsigned)(((ks * 4 + h * 2 + 0) ^ swr) << 4);
-            const unsigned slo = (unsigned)(((ks * 4 + h * 2 + 1) ^ swr) << 4);
+            const SpSlots so = sp_slots(ks, h, swr);
             sp_h8 ah[TM], al[TM], bh[TN], bl[TN];
             const sp_h8 z8 = {0, 0, 0, 0, 0, 0, 0, 0};
 #pragma unroll
             for (int i = 0; i < TM; ++i) {
-              const sp_h8 vh = *reinterpret_cast<const sp_h8*>(win + w_off[i] + (((ks * 4 + h * 2 + 0) ^ w_sw[i]) << 4));
-              const sp_h8 vl = *reinterpret_cast<const sp_h8*>(win + w_off[i] + (((ks * 4 + h * 2 + 1) ^ w_sw[i]) << 4));
+              const SpSlots sw = sp_slots(ks, h, w_sw[i]);
+              const sp_h8 vh = *reinterpret_cast<const sp_h8*>(win + w_off[i] + sw.hi);
+              const sp_h8 vl = *reinterpret_cast<const sp_h8*>(win + w_off[i] + sw.lo);
               ah[i] = w_ok[i] ? vh : z8;  // zero padding: the tap's pixel lies outside the image
               al[i] = w_ok[i] ? vl : z8;
             }
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
-              bh[j] = *reinterpret_cast<const sp_h8*>(sb + b_off[j] + shi);
-              bl[j] = *reinterpret_cast<const sp_h8*>(sb + b_off[j] + slo);
+              bh[j] = *reinterpret_cast<const sp_h8*>(sb + b_off[j] + so.hi);
+              bl[j] = *reinterpret_cast<const sp_h8*>(sb + b_off[j] + so.lo);
             }
+            // (the three products accumulator by accumulator, not sp_mfma3's product-major sweep: with that the eight-wave
+            // tile's window instances spill 4 - 16 bytes more per lane - profiles/gemm_sp_phases.txt)
 #pragma unroll
             for (int j = 0; j < TN; ++j)
 #pragma unroll
@@ -590,12 +673,11 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
           sp_h8 bh[2][TN], bl[2][TN];
   #pragma unroll
           for (int ks = 0; ks < 2; ++ks) {
-            const unsigned shi = (unsigned)(((ks * 4 + h * 2 + 0) ^ swr) << 4);
-            const unsigned slo = (unsigned)(((ks * 4 + h * 2 + 1) ^ swr) << 4);
+            const SpSlots so = sp_slots(ks, h, swr);
   #pragma unroll
             for (int i = 0; i < TM; ++i) {
-              xa[ks][i][0] = *reinterpret_cast<const sp_f4*>(sb + a_off[i] + shi);
-              xa[ks][i][1] = *reinterpret_cast<const sp_f4*>(sb + a_off[i] + slo);
+              xa[ks][i][0] = *reinterpret_cast<const sp_f4*>(sb + a_off[i] + so.hi);
+              xa[ks][i][1] = *reinterpret_cast<const sp_f4*>(sb + a_off[i] + so.lo);
               if constexpr (AMODE == SP_A_F32_MUL) {
                 xs[ks][i][0] = *reinterpret_cast<const sp_f4*>(sb + sc_off[i] + ks * 64);
                 xs[ks][i][1] = *reinterpret_cast<const sp_f4*>(sb + sc_off[i] + ks * 64 + 16);
@@ -603,8 +685,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
             }
   #pragma unroll
             for (int j = 0; j < TN; ++j) {
-              bh[ks][j] = *reinterpret_cast<const sp_h8*>(sb + b_off[j] + shi);
-              bl[ks][j] = *reinterpret_cast<const sp_h8*>(sb + b_off[j] + slo);
+              bh[ks][j] = *reinterpret_cast<const sp_h8*>(sb + b_off[j] + so.hi);
+              bl[ks][j] = *reinterpret_cast<const sp_h8*>(sb + b_off[j] + so.lo);
             }
           }
           if constexpr (AMODE == SP_A_F32_MUL) {
@@ -650,43 +732,29 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
         const char* const sb = ring + buf * STG;
   #pragma unroll
         for (int ks = 0; ks < KS; ++ks) {
-          const unsigned shi = (unsigned)(((ks * 4 + h * 2 + 0) ^ swr) << 4);
-          const unsigned slo = (unsigned)(((ks * 4 + h * 2 + 1) ^ swr) << 4);
+          const SpSlots so = sp_slots(ks, h, swr);
           sp_h8 ah[TM], al[TM], bh[TN], bl[TN];
   #pragma unroll
           for (int i = 0; i < TM; ++i) {
             if constexpr (AF32) {  // 8 consecutive k of row r as f32: (scale,) split, and the fragments are ready
-              sp_f4 x0 = *reinterpret_cast<const sp_f4*>(sb + a_off[i] + shi);
-              sp_f4 x1 = *reinterpret_cast<const sp_f4*>(sb + a_off[i] + slo);
+              sp_f4 x0 = *reinterpret_cast<const sp_f4*>(sb + a_off[i] + so.hi);
+              sp_f4 x1 = *reinterpret_cast<const sp_f4*>(sb + a_off[i] + so.lo);
               if constexpr (AMODE == SP_A_F32_MUL) {
                 x0 = x0 * *reinterpret_cast<const sp_f4*>(sb + sc_off[i] + ks * 64);
                 x1 = x1 * *reinterpret_cast<const sp_f4*>(sb + sc_off[i] + ks * 64 + 16);
               }
               sp8_split8_mix(x0, x1, ah[i], al[i]);  // (same values as sp8_split8, 8 vector instructions fewer per 8 elements)
             } else {
-              ah[i] = *reinterpret_cast<const sp_h8*>(sb + a_off[i] + shi);
-              al[i] = *reinterpret_cast<const sp_h8*>(sb + a_off[i] + slo);
+              ah[i] = *reinterpret_cast<const sp_h8*>(sb + a_off[i] + so.hi);
+              al[i] = *reinterpret_cast<const sp_h8*>(sb + a_off[i] + so.lo);
             }
           }
   #pragma unroll
           for (int j = 0; j < TN; ++j) {
-            bh[j] = *reinterpret_cast<const sp_h8*>(sb + b_off[j] + shi);
-            bl[j] = *reinterpret_cast<const sp_h8*>(sb + b_off[j] + slo);
+            bh[j] = *reinterpret_cast<const sp_h8*>(sb + b_off[j] + so.hi);
+            bl[j] = *reinterpret_cast<const sp_h8*>(sb + b_off[j] + so.lo);
           }
-          // small cross terms first, the hi*hi product last (per accumulator); the three products of an accumulator are
-          // issued TM * TN instructions apart, so no MFMA waits on the one just before it
-  #pragma unroll
-          for (int j = 0; j < TN; ++j)
-  #pragma unroll
-            for (int i = 0; i < TM; ++i) acc[i][j] = sp_mfma(bl[j], ah[i], acc[i][j]);
-  #pragma unroll
-          for (int j = 0; j < TN; ++j)
-  #pragma unroll
-            for (int i = 0; i < TM; ++i) acc[i][j] = sp_mfma(bh[j], al[i], acc[i][j]);
-  #pragma unroll
-          for (int j = 0; j < TN; ++j)
-  #pragma unroll
-            for (int i = 0; i < TM; ++i) acc[i][j] = sp_mfma(bh[j], ah[i], acc[i][j]);
+          sp_mfma3<TM, TN>(acc, bh, bl, ah, al);
         }
       }
       if (AMODE == SP_A_REG && t + 1 < nk) storeA(buf ^ 1);
@@ -696,286 +764,23 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
   }
 
   // ---- epilogue ----
-  auto activate = [&](float x) -> float {
-    if constexpr (ACT == ACT_NONE) return x;
-    else if constexpr (ACT == ACT_GELU) return act_gelu(x);
-    else if constexpr (ACT == ACT_MISH) return act_mish(x);
-    else if constexpr (ACT == ACT_SILU) return act_silu(x);
-    else return apply_act(x, g.act);
-  };
-  __builtin_amdgcn_s_barrier();  // every wave is done with the ring: it becomes the store staging area
+  __builtin_amdgcn_s_barrier();  // every wave is done with the ring: it becomes the epilogue's staging area
   const long st2 = g.stamps != nullptr ? (long)__builtin_amdgcn_s_memtime() : 0;
 
   if constexpr (sp_epi_chains(EPI)) {
-    static_assert(!sp_epi_chains(EPI) || (sp_tile_chains(T) && !HI16), "chained 1x1: one wave holds whole rows");
-    constexpr bool PHASE = EPI == SP_EPI_CHAIN_PHASE;
-    static_assert(!PHASE || AMODE == SP_A_CONV, "the phase form reads the conv geometry");
-    // LDS after the main loop: [NW x 4 KB: one column block of each wave's accumulators][NW x TN x 4 KB: each wave's A2
-    // stages, row-major 128-byte rows with the main loop's swizzle][TN stages x N2 rows x 128 B: W2]
-    constexpr int CB = kSpSlab;
-    char* const stg1 = smem + wave * CB;
-    char* const a2 = smem + sp_chain_a2(T) + wave * (TN * CB);
-    char* const w2 = smem + sp_chain_w2(T);
-    const int n2g = g.N2 >> 3;  // 8-row DMA pieces per stage
-    for (int p = wave; p < TN * n2g; p += NW) {
-      const int s = p / n2g, rg = p - s * n2g;
-      const int row = rg * 8 + (lane >> 3);
-      const int slot_s = (lane & 7) ^ ((row >> 1) & 7);
-      const char* const sp = g.W2 + (long)row * ((long)g.N * 4) + s * 128 + slot_s * 16;
-      __builtin_amdgcn_global_load_lds((sp_gptr)sp, (sp_lptr)(w2 + s * (g.N2 * 128) + rg * 1024), 16, 0, 0);
-    }
-    const int slot = lane & 7, lrow = lane >> 3;
-    const int mw0 = m0 + wm * 32;
-    // PHASE: where each of this lane's four rows goes in Out2, and its border class
-    long orow2[4];
-    int bcls[4];
-    if constexpr (PHASE) {
-#pragma unroll
-      for (int it = 0; it < 4; ++it) {
-        int m = mw0 + it * 8 + lrow;
-        m = m < g.M ? m : g.M - 1;
-        const uint32_t img = fdiv((uint32_t)m, g.d_ohw);
-        const uint32_t rem = (uint32_t)m - img * (uint32_t)(g.OH * g.OW);
-        const uint32_t oh = fdiv(rem, g.d_ow);
-        const uint32_t ow = rem - oh * (uint32_t)g.OW;
-        const int y = (int)oh * g.os + g.oy, x = (int)ow * g.os + g.ox;
-        orow2[it] = ((long)img * g.OH2 + y) * g.OW2 + x;
-        bcls[it] = (y == 0 ? 0 : (y == g.OH2 - 1 ? 2 : 1)) * 3 + (x == 0 ? 0 : (x == g.OW2 - 1 ? 2 : 1));
-      }
-    }
-    if (wave_active) {
-#pragma unroll
-      for (int j = 0; j < TN; ++j) {
-        const int n = n0 + j * 32 + slot * 4;
-        const sp_f4 w1 = *reinterpret_cast<const sp_f4*>(g.wscale + n);
-        const sp_f4 b1 = g.bias != nullptr ? *reinterpret_cast<const sp_f4*>(g.bias + n) : sp_f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-        for (int gq = 0; gq < 4; ++gq)
-          *reinterpret_cast<sp_f4*>(stg1 + r * 128 + (((gq * 2 + h) ^ (r & 7)) << 4)) =
-              sp_f4{acc[0][j][4 * gq], acc[0][j][4 * gq + 1], acc[0][j][4 * gq + 2], acc[0][j][4 * gq + 3]};
-#pragma unroll
-        for (int it = 0; it < 4; ++it) {
-          const int row = it * 8 + lrow;
-          const sp_f4 raw = *reinterpret_cast<const sp_f4*>(stg1 + row * 128 + ((slot ^ lrow) << 4));
-          sp_f4 br = b1;  // PHASE: the row's own bias (the launch has no bias vector)
-          if constexpr (PHASE) br = *reinterpret_cast<const sp_f4*>(g.bias_tab + bcls[it] * g.N + n);
-          sp_f4 v;
-#pragma unroll
-          for (int e = 0; e < 4; ++e) v[e] = activate(__builtin_fmaf(raw[e], w1[e] * g.a_unmul, br[e]));
-          // this lane's 16-byte piece of the row's SP8 form (even quads: the chunk's hi halves, odd quads: its lo halves)
-          *reinterpret_cast<sp_f4*>(a2 + j * CB + row * 128 + ((slot ^ ((row >> 1) & 7)) << 4)) =
-              __builtin_bit_cast(sp_f4, sp8_piece_from_quad(v, slot));
-        }
-      }
-    }
-    asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
-    __builtin_amdgcn_s_barrier();  // W2 has landed for every wave (each waited for its own pieces)
-    if (!wave_active) return;
-    const int tn2 = g.N2 >> 5;
-    spf16 acc2[TN];
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int q = 0; q < 16; ++q) acc2[j][q] = 0.f;
-#pragma unroll
-    for (int s = 0; s < TN; ++s) {
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) {
-        const unsigned shi = (unsigned)(((ks * 4 + h * 2 + 0) ^ swr) << 4);
-        const unsigned slo = (unsigned)(((ks * 4 + h * 2 + 1) ^ swr) << 4);
-        const sp_h8 ah = *reinterpret_cast<const sp_h8*>(a2 + s * CB + r * 128 + shi);
-        const sp_h8 al = *reinterpret_cast<const sp_h8*>(a2 + s * CB + r * 128 + slo);
-        sp_h8 bh[TN], bl[TN];
-#pragma unroll
-        for (int j = 0; j < TN; ++j) {
-          const int rowb = j < tn2 ? j * 32 + r : r;  // (column blocks beyond N2 are computed on block 0's rows and dropped)
-          bh[j] = *reinterpret_cast<const sp_h8*>(w2 + s * (g.N2 * 128) + rowb * 128 + shi);
-          bl[j] = *reinterpret_cast<const sp_h8*>(w2 + s * (g.N2 * 128) + rowb * 128 + slo);
-        }
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc2[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bl[j], ah, acc2[j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc2[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[j], al, acc2[j], 0, 0, 0);
-#pragma unroll
-        for (int j = 0; j < TN; ++j) acc2[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(bh[j], ah, acc2[j], 0, 0, 0);
-      }
-    }
-#pragma unroll
-    for (int j = 0; j < TN; ++j) {
-      if (j >= tn2) break;
-      const int n = j * 32 + slot * 4;
-      const sp_f4 w1 = *reinterpret_cast<const sp_f4*>(g.wscale2 + n);
-      const sp_f4 b1 = g.bias2 != nullptr ? *reinterpret_cast<const sp_f4*>(g.bias2 + n) : sp_f4{0.f, 0.f, 0.f, 0.f};
-#pragma unroll
-      for (int gq = 0; gq < 4; ++gq)
-        *reinterpret_cast<sp_f4*>(stg1 + r * 128 + (((gq * 2 + h) ^ (r & 7)) << 4)) =
-            sp_f4{acc2[j][4 * gq], acc2[j][4 * gq + 1], acc2[j][4 * gq + 2], acc2[j][4 * gq + 3]};
-#pragma unroll
-      for (int it = 0; it < 4; ++it) {
-        const int m = mw0 + it * 8 + lrow;
-        const sp_f4 raw = *reinterpret_cast<const sp_f4*>(stg1 + (it * 8 + lrow) * 128 + ((slot ^ lrow) << 4));
-        sp_f4 v;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const float t = __builtin_fmaf(raw[e], w1[e], b1[e]);
-          v[e] = g.act2 == ACT_SILU ? act_silu(t) : (g.act2 == ACT_NONE ? t : apply_act(t, g.act2));
-        }
-        sp_f4 piece = v;
-        if (g.out_fmt2 == 1) piece = __builtin_bit_cast(sp_f4, sp8_piece_from_quad(v, slot));  // every lane takes part
-        if constexpr (PHASE) {
-          if (m < g.M) *reinterpret_cast<sp_f4*>(g.Out2 + orow2[it] * g.ldo2 + g.o_off2 + n) = piece;
-        } else {
-          if (m < g.M) *reinterpret_cast<sp_f4*>(g.Out2 + (long)m * g.ldo2 + g.o_off2 + n) = piece;
-        }
-      }
-    }
+    static_assert(!sp_epi_chains(EPI) || !HI16, "chained 1x1: SP8 stages");
+    static_assert(EPI != SP_EPI_CHAIN_PHASE || AMODE == SP_A_CONV, "the phase form reads the conv geometry");
+    sp_epi_chain<EPI == SP_EPI_CHAIN_PHASE, ACT, WM, TN>(g, acc, smem, mw0, n0, wave, lane, wave_active);
     return;
   }
   if (!wave_active) return;
-
-  if constexpr (EPI == SP_EPI_TOPK) {
-    // ---- fused top-k (match path): the scores never leave registers.  A lane holds 16 TN columns of its row, its
-    // partner lane ^ 32 the other 16 TN; each round picks the (score desc, column asc) maximum of the wave's 32 TN
-    // columns and retires it.  Candidates: cand[m][(tile_n * WN + wn) * topk + kk]; topk_merge_kernel finishes.
-    const int ncol0 = n0 + wn * TN * 32;
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int gq = 0; gq < 4; ++gq) {
-        const int n = ncol0 + j * 32 + gq * 8 + 4 * h;
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const bool nok = n + e < g.N;
-          const float ws = (g.wscale != nullptr && nok) ? g.wscale[n + e] * g.a_unmul : g.a_unmul;
-#pragma unroll
-          for (int i = 0; i < TM; ++i) acc[i][j][4 * gq + e] = nok ? acc[i][j][4 * gq + e] * ws : -INFINITY;
-        }
-      }
-    const long slots = (long)g.tiles_n * WN;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int m = m0 + wm * TM * 32 + i * 32 + r;
-      for (int kk = 0; kk < g.topk; ++kk) {
-        float bs = -INFINITY;
-        int bi = 0x7fffffff;
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-          for (int q = 0; q < 16; ++q) {  // ascending column order inside the lane: the first maximum has the lowest column
-            const float v = acc[i][j][q];
-            const int n = ncol0 + j * 32 + (q >> 2) * 8 + 4 * h + (q & 3);
-            if (v > bs || (v == bs && n < bi)) bs = v, bi = n;
-          }
-        const float os = __shfl_xor(bs, 32);
-        const int oi = __shfl_xor(bi, 32);
-        if (os > bs || (os == bs && oi < bi)) bs = os, bi = oi;
-        if (h == 0 && m < g.M) {
-          const long o = ((long)m * slots + (long)tile_n * WN + wn) * g.topk + kk;
-          g.cand_s[o] = bs;
-          g.cand_i[o] = (bs == -INFINITY) ? -1 : bi;
-        }
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-          for (int q = 0; q < 16; ++q)
-            if (ncol0 + j * 32 + (q >> 2) * 8 + 4 * h + (q & 3) == bi) acc[i][j][q] = -INFINITY;
-      }
-    }
+  if constexpr (EPI == SP_EPI_TOPK || EPI == SP_EPI_TOPK_LABELS) {
+    sp_epi_topk<EPI == SP_EPI_TOPK_LABELS>(g, acc, mw0, nw0, (long)tile_n * WN + wn, (long)g.tiles_n * WN, r, h);
     return;
   }
 
-  if constexpr (EPI == SP_EPI_TOPK_LABELS) {
-    // ---- fused top-k with row labels (Bank::topk_labelled): the twin of the epilogue above.  A column whose tags fail
-    // the row's (all_of, any_of, none_of) masks scores -inf like a column past N; with g.distinct the winner's group
-    // travels with (score, column) through the lane exchange and the retire step retires every column of that group
-    // (group >= 0), so a wave range reports its best eligible rows of pairwise different groups.  A lane keeps the groups
-    // of its 16 TN columns in registers (the operand registers are dead); tags are read once per tile and dropped.
-    const int ncolh = n0 + wn * TN * 32 + 4 * h;  // the lane's first column; its columns are ncolh + 32 j + 8 gq + e
-    unsigned long m_all[TM], m_any[TM], m_none[TM];
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int m = m0 + wm * TM * 32 + i * 32 + r;
-      const bool mok = g.row_masks != nullptr && m < g.M;
-      m_all[i] = mok ? g.row_masks[3 * (long)m] : 0ul;
-      m_any[i] = mok ? g.row_masks[3 * (long)m + 1] : 0ul;
-      m_none[i] = mok ? g.row_masks[3 * (long)m + 2] : 0ul;
-    }
-    typedef unsigned long sp_u2 __attribute__((ext_vector_type(2)));
-    typedef int sp_i4 __attribute__((ext_vector_type(4)));
-    int grp[TN][16];
-#pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int gq = 0; gq < 4; ++gq) {
-        const int n = ncolh + j * 32 + gq * 8;
-        unsigned long tg[4] = {0ul, 0ul, 0ul, 0ul};
-        sp_i4 gr = {-1, -1, -1, -1};
-        if (n + 3 < g.N) {  // a whole quad of columns: 16-byte loads (n % 4 == 0; gemm_sp_topk_labels_launch checks the bases)
-          if (g.row_masks != nullptr) {
-            const sp_u2 t0 = *reinterpret_cast<const sp_u2*>(g.col_tags + n), t1 = *reinterpret_cast<const sp_u2*>(g.col_tags + n + 2);
-            tg[0] = t0[0], tg[1] = t0[1], tg[2] = t1[0], tg[3] = t1[1];
-          }
-          if (g.distinct != 0) gr = *reinterpret_cast<const sp_i4*>(g.col_groups + n);
-        } else {
-#pragma unroll
-          for (int e = 0; e < 4; ++e) {
-            if (g.row_masks != nullptr && n + e < g.N) tg[e] = g.col_tags[n + e];
-            if (g.distinct != 0 && n + e < g.N) gr[e] = g.col_groups[n + e];
-          }
-        }
-#pragma unroll
-        for (int e = 0; e < 4; ++e) {
-          const bool nok = n + e < g.N;
-          const float ws = (g.wscale != nullptr && nok) ? g.wscale[n + e] * g.a_unmul : g.a_unmul;
-          grp[j][4 * gq + e] = gr[e];
-#pragma unroll
-          for (int i = 0; i < TM; ++i) {
-            // (short-circuit form on purpose: written with & and | the step becomes one straight line, the compiler takes all
-            // 48 columns' loads and tests at once and the kernel needs 256 VGPRs and 344 bytes of scratch per lane; in this
-            // form it is 236 VGPRs without scratch.  tests/test_gpu_match_labels.py::test_filter runs it at b = 130.)
-            const bool el = (tg[e] & m_all[i]) == m_all[i] && (m_any[i] == 0ul || (tg[e] & m_any[i]) != 0ul) && (tg[e] & m_none[i]) == 0ul;
-            acc[i][j][4 * gq + e] = (nok && el) ? acc[i][j][4 * gq + e] * ws : -INFINITY;
-          }
-        }
-      }
-    const long slots = (long)g.tiles_n * WN;
-#pragma unroll
-    for (int i = 0; i < TM; ++i) {
-      const int m = m0 + wm * TM * 32 + i * 32 + r;
-      for (int kk = 0; kk < g.topk; ++kk) {
-        // the lane's columns are named by their compile-time offset from ncolh (no register per column index); ascending
-        // column order inside the lane, so the first strict maximum has the lowest column
-        float bs = -INFINITY;
-        int br = -1, bg = -1;
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-          for (int q = 0; q < 16; ++q) {
-            const float v = acc[i][j][q];
-            if (v > bs) bs = v, br = j * 32 + (q >> 2) * 8 + (q & 3), bg = grp[j][q];
-          }
-        int bi = br >= 0 ? ncolh + br : 0x7fffffff;
-        const float os = __shfl_xor(bs, 32);
-        const int oi = __shfl_xor(bi, 32);
-        const int og = __shfl_xor(bg, 32);
-        if (os > bs || (os == bs && oi < bi)) bs = os, bi = oi, bg = og;
-        if (h == 0 && m < g.M) {
-          const long o = ((long)m * slots + (long)tile_n * WN + wn) * g.topk + kk;
-          g.cand_s[o] = bs;
-          g.cand_i[o] = (bs == -INFINITY) ? -1 : bi;
-        }
-        // (the partner's winner is 4 columns off every offset of this lane: rr matches none of them)
-        const int rr = bi - ncolh;
-#pragma unroll
-        for (int j = 0; j < TN; ++j)
-#pragma unroll
-          for (int q = 0; q < 16; ++q)
-            if (j * 32 + (q >> 2) * 8 + (q & 3) == rr || (bg >= 0 && grp[j][q] == bg)) acc[i][j][q] = -INFINITY;
-      }
-    }
-    return;
-  }
-
+  // ---- staged store (in the kernel body on purpose: as a function of its own it costs the dense instances 1 - 7 % more
+  // instructions and the eight-wave tile scratch - profiles/gemm_sp_phases.txt) ----
   // The accumulators of one 32-row slab go to LDS untouched (register group gq of column block j holds columns
   // 32 j + 8 gq + 4 h + 0..3 of row lane & 31) and are read back row-wise, 8 lanes per 128-byte row segment: a lane
   // keeps the same 4 columns of every column block for the whole tile, so its column scale, bias and GRN sums of
@@ -1080,7 +885,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
         sp_f4 v;
 #pragma unroll
         for (int e = 0; e < 4; ++e)  // wsc is a power of two: the fused form rounds exactly like multiply-then-add
-          v[e] = activate(__builtin_fmaf(raw[e], wsc[j][e], bsv[j][e]));
+          v[e] = sp_activate<ACT>(__builtin_fmaf(raw[e], wsc[j][e], bsv[j][e]), g.act);
         if (grn) {
           if (single) {
             if (ok) {
@@ -1104,10 +909,8 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
         if (ok) {
           const long drow = i * 32 + it * 8;  // compile-time constant: drow * ld is scalar arithmetic
           if (remap) {
-            const uint32_t img = fdiv((uint32_t)m, g.d_ohw);
-            const uint32_t rem = (uint32_t)m - img * (uint32_t)(g.OH * g.OW);
-            const uint32_t oh = fdiv(rem, g.d_ow);
-            const uint32_t ow = rem - oh * (uint32_t)g.OW;
+            uint32_t img, oh, ow;
+            sp_pixel(g, (uint32_t)m, img, oh, ow);
             uint32_t oy = (uint32_t)g.oy, ox = (uint32_t)g.ox, cn = (uint32_t)(ncol0 + j * 32);
             if (g.nq > 0) {  // whole ConvTranspose in one launch: this lane's column group names the output phase
               const uint32_t q = fdiv(cn, g.d_nq);
@@ -1156,13 +959,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
 #pragma unroll
   for (int i = 0; i < TM; ++i) {
 #pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int gq = 0; gq < 4; ++gq) {
-        const int sl = j * 8 + gq * 2 + h;
-        *reinterpret_cast<sp_f4*>(stg + r * SROW + ((sl ^ (r & 7)) << 4)) =
-            sp_f4{acc[i][j][4 * gq], acc[i][j][4 * gq + 1], acc[i][j][4 * gq + 2], acc[i][j][4 * gq + 3]};
-      }
+    for (int j = 0; j < TN; ++j) sp_block_put<SROW>(stg, acc[i][j], j, r, h);
     // the slab is complete in LDS (same wave wrote it; LDS operations of one wave execute in order)
     const int ms0 = mw0 + i * 32;
     bool fast = !GEN && cols_full && ms0 + 32 <= g.M;  // the generic form keeps to the masked body (code size)
