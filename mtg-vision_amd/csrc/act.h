@@ -88,4 +88,15 @@ __device__ __forceinline__ float apply_act(float x, int act) {
   }
 }
 
+// A GEMM epilogue's activation: ACT >= 0 fixes it at compile time, any other value (the kernels pass -1) reads it from
+// the launch's arguments.
+template <int ACT>
+__device__ __forceinline__ float act_fixed(float x, int act) {
+  if constexpr (ACT == ACT_NONE) return x;
+  else if constexpr (ACT == ACT_GELU) return act_gelu(x);
+  else if constexpr (ACT == ACT_MISH) return act_mish(x);
+  else if constexpr (ACT == ACT_SILU) return act_silu(x);
+  else return apply_act(x, act);
+}
+
 }  // namespace mtgv

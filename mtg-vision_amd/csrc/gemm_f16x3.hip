@@ -5,8 +5,8 @@
 
 namespace mtgv {
 
-bool gemm_dispatch_f16x3(const GemmDev& g, const GemmPlan& pl, bool conv, bool apro, int grid, hipStream_t s) {
-  return gemm_dispatch<1>(g, pl, conv, apro, grid, s);
+void gemm_dispatch_f16x3(const GemmDev& g, const GemmPlan& pl, bool conv, bool apro, int grid, hipStream_t s) {
+  gemm_dispatch<1>(g, pl, conv, apro, grid, s);
 }
 
 }  // namespace mtgv

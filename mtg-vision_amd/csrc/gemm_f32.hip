@@ -49,10 +49,10 @@ GemmArgs conv_args(const ConvIn& in, const float* W, const float* bias, int cout
   return a;
 }
 
-bool gemm_dispatch_f32(const GemmDev& g, const GemmPlan& pl, bool conv, bool apro, int grid, hipStream_t s) {
-  return gemm_dispatch<0>(g, pl, conv, apro, grid, s);
+void gemm_dispatch_f32(const GemmDev& g, const GemmPlan& pl, bool conv, bool apro, int grid, hipStream_t s) {
+  gemm_dispatch<0>(g, pl, conv, apro, grid, s);
 }
-bool gemm_dispatch_f16x3(const GemmDev& g, const GemmPlan& pl, bool conv, bool apro, int grid, hipStream_t s);  // gemm_f16x3.hip
+void gemm_dispatch_f16x3(const GemmDev& g, const GemmPlan& pl, bool conv, bool apro, int grid, hipStream_t s);  // gemm_f16x3.hip
 
 // ---------------------------------------------------------------------------
 // host side
@@ -68,7 +68,7 @@ struct GemmProf {
   double flops = 0;
   double bytes = 0;  // compulsory HBM bytes: every operand element read once, every output written once
   long launches = 0;
-  struct Rec { int M, N, K, KH, stride, batch, act, apro, grn, topk, tm, tn, bk, sp; double bytes, fill, xflops; };
+  struct Rec { int M, N, K, KH, stride, batch, act, apro, grn, topk, tn, bk, sp; double bytes, fill, xflops; };
   std::vector<Rec> recs;
 } g_prof;
 }  // namespace
@@ -86,7 +86,7 @@ void gemm_profile_enable(bool on) {
 void gemm_profile_dump(const char* path) {
   FILE* f = fopen(path, "w");
   MTGV_CHECK(f != nullptr, ERR_RUNTIME, "cannot open %s", path);
-  fprintf(f, "idx,M,N,K,KH,stride,batch,act,apro,grn,topk,tm,tn,bk,ms,tflops,bytes,sp,fill,xflops\n");
+  fprintf(f, "idx,M,N,K,KH,stride,batch,act,apro,grn,topk,tm,tn,bk,ms,tflops,bytes,sp,fill,xflops\n");  // tm: always 1 (BM = 128)
   for (size_t i = 0; i + 1 < g_prof.used && i / 2 < g_prof.recs.size(); i += 2) {
     HIP_OK(hipEventSynchronize(g_prof.ev[i + 1]));
     float t = 0.f;
@@ -94,7 +94,7 @@ void gemm_profile_dump(const char* path) {
     const auto& r = g_prof.recs[i / 2];
     const double fl = 2.0 * r.M * r.N * r.K * r.batch + r.xflops;  // xflops: further layers run inside the launch
     fprintf(f, "%zu,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%d,%.4f,%.2f,%.0f,%d,%.0f,%.0f\n", i / 2, r.M, r.N, r.K, r.KH, r.stride, r.batch, r.act,
-            r.apro, r.grn, r.topk, r.tm, r.tn, r.bk, t, fl / (t * 1e-3) / 1e12, r.bytes, r.sp, r.fill, r.xflops);
+            r.apro, r.grn, r.topk, 1, r.tn, r.bk, t, fl / (t * 1e-3) / 1e12, r.bytes, r.sp, r.fill, r.xflops);
   }
   fclose(f);
   gemm_sp_stamps_dump((std::string(path) + ".stamps").c_str());
@@ -141,7 +141,7 @@ static void prof_begin(const GemmArgs& a, const GemmPlan& pl, hipStream_t s, int
     if (bytes_override >= 0.0) by = bytes_override;
     g_prof.bytes += by;
     g_prof.recs.push_back({a.M, a.N, a.K, a.KH, a.stride, a.batch, a.act, a.a_scale != nullptr, a.grn_part != nullptr, a.topk,
-                           pl.tm, pl.tn, pl.bk, sp, by, fill, xfl});
+                           pl.tn, pl.bk, sp, by, fill, xfl});
   }
   g_prof.launches += 1;
 }
@@ -168,8 +168,8 @@ void gemm_set_precision(int prec) {
   g_prec = prec;
 }
 
-static GemmPlan tile(int tm, int tn, int bk, int M, int N) {
-  GemmPlan pl{tm, tn, bk, 0, 0};
+static GemmPlan tile(GemmTile t, int M, int N) {
+  GemmPlan pl{t.tn, t.bk, 0, 0};
   pl.tiles_m = ceil_div(M, pl.bm());
   pl.tiles_n = ceil_div(N, pl.bn());
   return pl;
@@ -180,8 +180,11 @@ static GemmPlan tile(int tm, int tn, int bk, int M, int N) {
 static GemmPlan gemm_plan(int M, int N, int K, bool heavy_epilogue, bool scaled_a) {
   if (const char* e = getenv("MTGV_GEMM_TILE")) {  // read at every launch (tests switch it within one process)
     int tm = 0, tn = 0, bk = 0;
-    if (sscanf(e, "%d,%d,%d", &tm, &tn, &bk) == 3 && (tm == 1 || tm == 2) && tn >= 1 && tn <= 5 && (bk == 16 || bk == 32))
-      return tile(tm, tn, bk, M, N);
+    if (sscanf(e, "%d,%d,%d", &tm, &tn, &bk) == 3) {  // (a malformed value is ignored)
+      // refused here, before the profiler records the launch or anything is enqueued
+      MTGV_CHECK(tm == 1 && gemm_tile_built(tn, bk), ERR_INVALID, "gemm: no kernel for tile tm=%d tn=%d bk=%d", tm, tn, bk);
+      return tile({tn, bk}, M, N);
+    }
   }
   // Cost model fitted to tile sweeps on MI355X (tools/gemm_sweep.py, profiles/r01_gemm_sweep.txt):
   // narrow tiles with BK = 16 win - more resident blocks per CU overlap one block's tile load and
@@ -208,13 +211,13 @@ static GemmPlan gemm_plan(int M, int N, int K, bool heavy_epilogue, bool scaled_
     const double cost = rounds * 128.0 * 32.0 * tn * ((double)K + ov) / eff[tn];
     if (best < 0 || cost < best) best = cost, best_tn = tn;
   }
-  return tile(1, best_tn, (best_tn == 1 && K >= 256) ? 32 : 16, M, N);  // sweep: BK 32 pays only for the narrowest tile on long K
+  return tile({best_tn, (best_tn == 1 && K >= 256) ? 32 : 16}, M, N);  // sweep: BK 32 pays only for the narrowest tile on long K
 }
 
 // the convert-on-load kernel's tile for a launch: the top-k epilogue has one instance (gemm_dispatch), every other
 // launch gets the cost model's choice
 static GemmPlan plan_for(const GemmArgs& a) {
-  if (a.topk > 0) return tile(1, 2, 16, a.M, a.N);
+  if (a.topk > 0) return tile(kGemmTopkTile, a.M, a.N);
   return gemm_plan(a.M, a.N, a.K, a.act != ACT_NONE, a.a_scale != nullptr);
 }
 
@@ -252,7 +255,7 @@ size_t gemm_grn_part_floats_max(int M, int N, int hw) {
 
 static bool ln_fusable(const GemmArgs& a, const GemmPlan& pl) {
   // the instance that carries the epilogue: conv gather, 128 x 96 x 16 tile; one tile per row, whole tiles, plain f32 rows out
-  if (!(pl.tm == 1 && pl.tn == 3 && pl.bk == 16 && is_conv(a) && a.N == pl.bn() && a.M % pl.bm() == 0)) return false;
+  if (!(pl.tn == kGemmLnTile.tn && pl.bk == kGemmLnTile.bk && is_conv(a) && a.N == pl.bn() && a.M % pl.bm() == 0)) return false;
   if (a.batch != 1 || a.act != ACT_NONE || a.res != nullptr || a.a_scale != nullptr || a.grn_part != nullptr || a.topk > 0 ||
       a.crop_boxes != nullptr || a.m_count != nullptr || is_remap(a) || a.out_fmt != 0 || a.a_fmt != 0)
     return false;
@@ -330,14 +333,10 @@ void gemm_launch(const GemmArgs& args, hipStream_t s) {
     MTGV_CHECK(a.cand_s != nullptr && a.cand_i != nullptr && a.topk <= 128, ERR_INVALID, "gemm: bad top-k arguments");
   }
   prof_begin(a, pl, s, 0, (double)grid * a.batch * (pl.bm() + pl.bn()) * a.K * 4.0);
-  const bool found = gemm_precision() == GEMM_PREC_F16X3 ? gemm_dispatch_f16x3(g, pl, conv, apro, grid, s)
-                                                         : gemm_dispatch_f32(g, pl, conv, apro, grid, s);
-  if (found) {
-    HIP_OK(hipGetLastError());
-    prof_end(s);
-    return;
-  }
-  MTGV_CHECK(false, ERR_INVALID, "gemm: no kernel for tile tm=%d tn=%d bk=%d", pl.tm, pl.tn, pl.bk);
+  if (gemm_precision() == GEMM_PREC_F16X3) gemm_dispatch_f16x3(g, pl, conv, apro, grid, s);
+  else gemm_dispatch_f32(g, pl, conv, apro, grid, s);
+  HIP_OK(hipGetLastError());
+  prof_end(s);
 }
 
 // ---------------------------------------------------------------------------

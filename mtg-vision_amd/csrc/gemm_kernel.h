@@ -4,9 +4,9 @@
 //   gemm_f16x3.hip  PREC 1: every f32 operand split on the fly into fp16 hi + lo, three
 //                           v_mfma_f32_32x32x16_f16 per product (hi*hi + hi*lo + lo*hi, f32 accumulate)
 //
-// Tile: 256 threads = 4 waves stacked along M.  Block tile BM = 128*TM rows by
-// BN = 32*TN columns; wave w owns rows [w*32*TM, (w+1)*32*TM) x all BN columns
-// as TM x TN accumulators of 32x32.  K is consumed in BK-wide steps staged
+// Tile: 256 threads = 4 waves stacked along M.  Block tile BM = 128 rows by
+// BN = 32*TN columns; wave w owns rows [w*32, (w+1)*32) x all BN columns
+// as TN accumulators of 32x32.  K is consumed in BK-wide steps staged
 // through LDS, with the next step's global loads in flight while the current one feeds the MFMAs.
 #pragma once
 #include "gemm_f32.h"
@@ -30,11 +30,27 @@ struct GemmDev {
   int off32_ok;  // every operand of the launch spans less than 4 GiB: 32-bit byte offsets are enough
 };
 
+// The tiles the kernel is built for, BM = 128 rows x BN = 32*tn columns, K staged bk at a time.  This is the one list:
+// gemm_dispatch instantiates one set of kernels per entry (launch_tile) and gemm_plan refuses any other tile.
+struct GemmTile {
+  int tn, bk;
+};
+constexpr GemmTile kGemmTiles[] = {{1, 16}, {2, 16}, {3, 16}, {4, 16}, {5, 16}, {1, 32}};
+constexpr GemmTile kGemmTopkTile = {2, 16};  // the top-k epilogues' instance (EPI 1 / 3)
+constexpr GemmTile kGemmLnTile = {3, 16};    // the LayerNorm epilogue's instance (EPI 2): the stem's 128 x 96 x 16
+constexpr bool gemm_tile_built(int tn, int bk) {
+  for (const GemmTile& t : kGemmTiles)
+    if (t.tn == tn && t.bk == bk) return true;
+  return false;
+}
+static_assert(gemm_tile_built(kGemmTopkTile.tn, kGemmTopkTile.bk) && gemm_tile_built(kGemmLnTile.tn, kGemmLnTile.bk),
+              "the epilogue instances sit on built tiles");
+
 // tile of one launch (chosen by gemm_launch, gemm_f32.hip)
 struct GemmPlan {
-  int tm, tn, bk;  // BM = 128*tm, BN = 32*tn
+  int tn, bk;  // BM = 128, BN = 32*tn
   int tiles_m, tiles_n;
-  int bm() const { return 128 * tm; }
+  int bm() const { return 128; }
   int bn() const { return 32 * tn; }
 };
 
@@ -51,18 +67,54 @@ __device__ __forceinline__ void split_f16(const f32x4 x, f16x4& hi, f16x4& lo) {
   lo = __builtin_convertvector(x - __builtin_convertvector(hi, f32x4), f16x4);
 }
 
-// LDS bytes of one launch.  PREC 0: f32 rows padded by 16 B (conflict-free ds_read_b128) + the APRO multiplier
-// tile.  PREC 1: two fp16 planes (hi, lo) per operand; 16-half rows are contiguous, 32-half rows padded by 16 B.
-template <int TM, int TN, int BK, bool APRO, int PREC>
-constexpr size_t gemm_lds_bytes(int nseg_max) {
-  if (PREC == 1) return (size_t)2 * 2 * (128 * TM + 32 * TN) * (BK == 16 ? 16 : BK + 8) * sizeof(_Float16);
-  return (size_t)2 * (128 * TM + 32 * TN) * (BK + 4) * sizeof(float) + (APRO ? (size_t)2 * nseg_max * BK * sizeof(float) : 0);
+// C layout of a 32x32 accumulator: register r of a lane holds column lane & 31 of row gemm_c_row(r) + 4 * (lane >> 5)
+__device__ __forceinline__ constexpr int gemm_c_row(int r) { return (r & 3) + 8 * (r >> 2); }
+
+// accumulator -> the value the activation sees.  PREC 1 undoes the weight row's scale and a_mul on the way (ws is a power
+// of two times a_unmul: the fused form rounds like multiply-then-add)
+template <int PREC>
+__device__ __forceinline__ float gemm_scale_bias(float acc, float ws, float bv) {
+#pragma clang fp contract(off)
+  return PREC == 1 ? __builtin_fmaf(acc, ws, bv) : acc + bv;
 }
 
-template <int TM, int TN, int BK, bool CONV, bool APRO, int EPI, int ACT, int PREC>
-__global__ __launch_bounds__(256, (TM * TN == 1 ? (BK == 16 ? 6 : 4) : TM * TN == 2 ? (BK == 16 ? 5 : 4) : TM * TN == 3 ? (BK == 16 ? 4 : 3) : TM * TN == 4 ? (BK == 16 ? 3 : 2) : 2)) void gemm_f32_kernel(const GemmDev g) {
+// column n's entries of the launch's per-column vectors; ok = false for a column past N (nothing is read)
+__device__ __forceinline__ float gemm_col_bias(const float* bias, int n, bool ok = true) { return (bias != nullptr && ok) ? bias[n] : 0.f; }
+template <int PREC>
+__device__ __forceinline__ float gemm_col_unscale(const float* wscale, float a_unmul, int n, bool ok = true) {
+#pragma clang fp contract(off)
+  return (PREC == 1 && wscale != nullptr && ok) ? wscale[n] * a_unmul : a_unmul;
+}
+
+// conv output row m -> (image, output y, output x); ohw = OH * OW.  The A gather and the output row remap both use it.
+struct GemmPixel {
+  uint32_t img, oh, ow;
+};
+__device__ __forceinline__ GemmPixel gemm_pixel(uint32_t m, FastDiv d_ohw, FastDiv d_ow, int ohw, int ow_) {
+  const uint32_t img = fdiv(m, d_ohw);
+  const uint32_t rem = m - img * (uint32_t)ohw;
+  const uint32_t oh = fdiv(rem, d_ow);
+  return {img, oh, rem - oh * (uint32_t)ow_};
+}
+
+}  // namespace mtgv
+
+#include "gemm_epi.h"  // after the helpers above: the epilogue uses them
+
+namespace mtgv {
+
+// LDS bytes of one launch.  PREC 0: f32 rows padded by 16 B (conflict-free ds_read_b128) + the APRO multiplier
+// tile.  PREC 1: two fp16 planes (hi, lo) per operand; 16-half rows are contiguous, 32-half rows padded by 16 B.
+template <int TN, int BK, bool APRO, int PREC>
+constexpr size_t gemm_lds_bytes(int nseg_max) {
+  if (PREC == 1) return (size_t)2 * 2 * (128 + 32 * TN) * (BK == 16 ? 16 : BK + 8) * sizeof(_Float16);
+  return (size_t)2 * (128 + 32 * TN) * (BK + 4) * sizeof(float) + (APRO ? (size_t)2 * nseg_max * BK * sizeof(float) : 0);
+}
+
+template <int TN, int BK, bool CONV, bool APRO, int EPI, int ACT, int PREC>
+__global__ __launch_bounds__(256, (TN == 1 ? (BK == 16 ? 6 : 4) : TN == 2 ? (BK == 16 ? 5 : 4) : TN == 3 ? (BK == 16 ? 4 : 3) : TN == 4 ? (BK == 16 ? 3 : 2) : 2)) void gemm_f32_kernel(const GemmDev g) {
 #pragma clang fp contract(off)  // loader scaling and epilogue arithmetic identical in every instantiation (act.h)
-  constexpr int BM = 128 * TM, BN = 32 * TN, LS = BK + 4;
+  constexpr int BM = 128, BN = 32 * TN, LS = BK + 4;
   constexpr int LSH = BK == 16 ? 16 : BK + 8;  // PREC 1: halves per staged row
   constexpr int KQ = BK / 4;      // float4 per staged row
   constexpr int RPP = 256 / KQ;   // rows staged per pass
@@ -109,13 +161,10 @@ __global__ __launch_bounds__(256, (TM * TN == 1 ? (BK == 16 ? 6 : 4) : TM * TN =
     a_ok[i] = m < M_eff;
     const uint32_t mm = a_ok[i] ? (uint32_t)m : 0u;
     if (CONV) {
-      const uint32_t img = fdiv(mm, g.d_ohw);
-      const uint32_t rem = mm - img * (uint32_t)(p.OH * p.OW);
-      const uint32_t oh = fdiv(rem, g.d_ow);
-      const uint32_t ow = rem - oh * (uint32_t)p.OW;
-      a_row[i] = (long)img * p.H * p.Wd;
-      a_ih0[i] = (int)oh * p.stride - p.pad;
-      a_iw0[i] = (int)ow * (p.stride_w > 0 ? p.stride_w : p.stride) - p.pad;
+      const GemmPixel px = gemm_pixel(mm, g.d_ohw, g.d_ow, p.OH * p.OW, p.OW);
+      a_row[i] = (long)px.img * p.H * p.Wd;
+      a_ih0[i] = (int)px.oh * p.stride - p.pad;
+      a_iw0[i] = (int)px.ow * (p.stride_w > 0 ? p.stride_w : p.stride) - p.pad;
     } else {
       a_row[i] = (long)mm * p.c_total + p.c_off;
       a_ih0[i] = a_iw0[i] = 0;
@@ -167,6 +216,20 @@ __global__ __launch_bounds__(256, (TM * TN == 1 ? (BK == 16 ? 6 : 4) : TM * TN =
   }
 #pragma unroll
   for (int i = 0; i < BP; ++i) b_off[i] = (unsigned)((b_row[i] + lk) * (long)sizeof(float));
+  // APRO, PREC 0: this thread's float4s of the K step's multiplier tile (the fast path needs no k < K test)
+  auto load_mults = [&](int kt, auto fast_c) {
+    if constexpr (APRO && PREC == 0) {
+#pragma unroll
+      for (int u = 0; u < SPT; ++u) {
+        const int e = tid + u * 256;  // (segment, float4 column) of the multiplier tile
+        const int seg = e / KQ, kq = (e % KQ) * 4;
+        f32x4 v = {0.f, 0.f, 0.f, 0.f};
+        if (seg < nseg_t && (decltype(fast_c)::value || kt * BK + kq < p.K))
+          v = *reinterpret_cast<const f32x4*>(p.a_scale + (long)(img_first_t + seg) * p.K + kt * BK + kq);
+        rsl[u] = v;
+      }
+    }
+  };
   auto load_tile = [&](int kt, auto fast_c) {
     if constexpr (decltype(fast_c)::value) {
       const char* const Ak = reinterpret_cast<const char*>(Ap) + (size_t)kt * BK * sizeof(float);
@@ -180,16 +243,7 @@ __global__ __launch_bounds__(256, (TM * TN == 1 ? (BK == 16 ? 6 : 4) : TM * TN =
       }
 #pragma unroll
       for (int i = 0; i < BP; ++i) rb[i] = *reinterpret_cast<const f32x4*>(Wk + b_off[i]);  // rows past BN: row 0, never stored
-      if (APRO && PREC == 0) {
-#pragma unroll
-        for (int u = 0; u < SPT; ++u) {
-          const int e = tid + u * 256;
-          const int seg = e / KQ, kq = (e % KQ) * 4;
-          f32x4 v = {0.f, 0.f, 0.f, 0.f};
-          if (seg < nseg_t) v = *reinterpret_cast<const f32x4*>(p.a_scale + (long)(img_first_t + seg) * p.K + kt * BK + kq);
-          rsl[u] = v;
-        }
-      }
+      load_mults(kt, fast_c);
       return;
     }
     const int k = kt * BK + lk;
@@ -225,17 +279,7 @@ __global__ __launch_bounds__(256, (TM * TN == 1 ? (BK == 16 ? 6 : 4) : TM * TN =
       if (b_ok[i] && kok) v = *reinterpret_cast<const f32x4*>(Wld + b_row[i] + k);
       rb[i] = v;
     }
-    if (APRO && PREC == 0) {
-#pragma unroll
-      for (int u = 0; u < SPT; ++u) {
-        const int e = tid + u * 256;  // (segment, float4 column) of the multiplier tile
-        const int seg = e / KQ, kq = (e % KQ) * 4;
-        f32x4 v = {0.f, 0.f, 0.f, 0.f};
-        if (seg < nseg_t && kt * BK + kq < p.K)
-          v = *reinterpret_cast<const f32x4*>(p.a_scale + (long)(img_first_t + seg) * p.K + kt * BK + kq);
-        rsl[u] = v;
-      }
-    }
+    load_mults(kt, fast_c);
   };
   auto store_tile = [&](int buf) {
     if constexpr (PREC == 1) {
@@ -280,29 +324,23 @@ __global__ __launch_bounds__(256, (TM * TN == 1 ? (BK == 16 ? 6 : 4) : TM * TN =
     }
   };
 
-  f32x16 acc[TM][TN];
+  f32x16 acc[TN];
 #pragma unroll
-  for (int i = 0; i < TM; ++i)
+  for (int j = 0; j < TN; ++j)
 #pragma unroll
-    for (int j = 0; j < TN; ++j)
-#pragma unroll
-      for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
 
+  const int wrow0 = bm0 + wave * 32;  // this wave's first row of the problem
   const int col = lane & 31, half = lane >> 5;
-  const int arow = wave * 32 * TM + col;
+  const int arow = wave * 32 + col;
   const int kh4 = 4 * half;
 
   // a wave whose rows all lie beyond M (ragged last tile, tiny-M problems) skips its MFMAs
-  const bool wave_active = bm0 + wave * 32 * TM < M_eff;
-  int seg_lane[TM];
-#pragma unroll
-  for (int i = 0; i < TM; ++i) {
-    int sg = 0;
-    if (APRO) {
-      const int m = bm0 + arow + i * 32;
-      sg = (int)fdiv((uint32_t)(m < M_eff ? m : M_eff - 1), g.d_hw) - img_first_t;
-    }
-    seg_lane[i] = sg;
+  const bool wave_active = wrow0 < M_eff;
+  int seg_lane = 0;
+  if (APRO) {
+    const int m = bm0 + arow;
+    seg_lane = (int)fdiv((uint32_t)(m < M_eff ? m : M_eff - 1), g.d_hw) - img_first_t;
   }
   const int nk = (p.K + BK - 1) / BK;
   auto k_loop = [&](auto fast_c) {
@@ -324,22 +362,16 @@ __global__ __launch_bounds__(256, (TM * TN == 1 ? (BK == 16 ? 6 : 4) : TM * TN =
           for (int ks = 0; ks < BK / 16; ++ks) {
             // lane half h holds k = ks*16 + 8h + j in element j of both operands' fragments
             const int ko = ks * 16 + 8 * half;
-            f16x8 ah[TM], al[TM];
-#pragma unroll
-            for (int i = 0; i < TM; ++i) {
-              ah[i] = *reinterpret_cast<const f16x8*>(&Ahi[(arow + i * 32) * LSH + ko]);
-              al[i] = *reinterpret_cast<const f16x8*>(&Alo[(arow + i * 32) * LSH + ko]);
-            }
+            const f16x8 ah = *reinterpret_cast<const f16x8*>(&Ahi[arow * LSH + ko]);
+            const f16x8 al = *reinterpret_cast<const f16x8*>(&Alo[arow * LSH + ko]);
 #pragma unroll
             for (int j = 0; j < TN; ++j) {
               const f16x8 bh = *reinterpret_cast<const f16x8*>(&Bhi[(j * 32 + col) * LSH + ko]);
               const f16x8 bl = *reinterpret_cast<const f16x8*>(&Blo[(j * 32 + col) * LSH + ko]);
-#pragma unroll
-              for (int i = 0; i < TM; ++i) {  // small cross terms first, the hi*hi product last
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al[i], bh, acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bl, acc[i][j], 0, 0, 0);
-                acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah[i], bh, acc[i][j], 0, 0, 0);
-              }
+              // small cross terms first, the hi*hi product last
+              acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[j], 0, 0, 0);
+              acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[j], 0, 0, 0);
+              acc[j] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[j], 0, 0, 0);
             }
           }
         }
@@ -348,21 +380,15 @@ __global__ __launch_bounds__(256, (TM * TN == 1 ? (BK == 16 ? 6 : 4) : TM * TN =
       for (int kk = 0; kk < BK / 8; ++kk) {
         // lane half h holds k = kk*8 + 4h + j in element j; A and B use the same
         // k assignment, so MFMA j multiplies matching k pairs {j, 4+j}.
-        f32x4 a[TM], b[TN];
-#pragma unroll
-        for (int i = 0; i < TM; ++i) {
-          a[i] = *reinterpret_cast<const f32x4*>(&Ab[(arow + i * 32) * LS + kk * 8 + kh4]);
-          if (APRO) a[i] = a[i] * *reinterpret_cast<const f32x4*>(&Ss[(cur * g.nseg_max + seg_lane[i]) * BK + kk * 8 + kh4]);
-        }
+        f32x4 a = *reinterpret_cast<const f32x4*>(&Ab[arow * LS + kk * 8 + kh4]);
+        if (APRO) a = a * *reinterpret_cast<const f32x4*>(&Ss[(cur * g.nseg_max + seg_lane) * BK + kk * 8 + kh4]);
+        f32x4 b[TN];
 #pragma unroll
         for (int j = 0; j < TN; ++j) b[j] = *reinterpret_cast<const f32x4*>(&Bb[(j * 32 + col) * LS + kk * 8 + kh4]);
 #pragma unroll
         for (int e = 0; e < 4; ++e)
 #pragma unroll
-          for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int j = 0; j < TN; ++j)
-              acc[i][j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[i][e], b[j][e], acc[i][j], 0, 0, 0);
+          for (int j = 0; j < TN; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[e], b[j][e], acc[j], 0, 0, 0);
       }
       }
       if (kt + 1 < nk) store_tile(cur ^ 1);
@@ -396,90 +422,78 @@ __global__ __launch_bounds__(256, (TM * TN == 1 ? (BK == 16 ? 6 : 4) : TM * TN =
     for (int j = 0; j < TN; ++j) {
       const int n = bn0 + j * 32 + col;
       const bool nok = n < p.N;
-      const float ws = (PREC == 1 && p.wscale != nullptr && nok) ? p.wscale[n] * p.a_unmul : p.a_unmul;
+      const float ws = gemm_col_unscale<PREC>(p.wscale, p.a_unmul, n, nok);
       if constexpr (LAB) {
         tg[j] = (p.row_masks != nullptr && nok) ? p.col_tags[n] : 0ul;
         gr[j] = (p.topk_distinct != 0 && nok) ? p.col_groups[n] : -1;
       }
 #pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) acc[i][j][r] = nok ? acc[i][j][r] * ws : -INFINITY;
+      for (int r = 0; r < 16; ++r) acc[j][r] = nok ? acc[j][r] * ws : -INFINITY;
     }
 #pragma unroll
-    for (int i = 0; i < TM; ++i) {
+    for (int r = 0; r < 16; ++r) {
+      const int m = wrow0 + gemm_c_row(r) + 4 * half;
+      if constexpr (LAB) {
+        // (straight-line on purpose: bitwise & and | on the three tests and a select, no short-circuit branches)
+        const bool mok = p.row_masks != nullptr && m < M_eff;
+        const unsigned long m_all = mok ? p.row_masks[3 * (long)m] : 0ul;
+        const unsigned long m_any = mok ? p.row_masks[3 * (long)m + 1] : 0ul;
+        const unsigned long m_none = mok ? p.row_masks[3 * (long)m + 2] : 0ul;
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const int m = bm0 + wave * 32 * TM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-        if constexpr (LAB) {
-          // (straight-line on purpose: bitwise & and | on the three tests and a select, no short-circuit branches)
-          const bool mok = p.row_masks != nullptr && m < M_eff;
-          const unsigned long m_all = mok ? p.row_masks[3 * (long)m] : 0ul;
-          const unsigned long m_any = mok ? p.row_masks[3 * (long)m + 1] : 0ul;
-          const unsigned long m_none = mok ? p.row_masks[3 * (long)m + 2] : 0ul;
+        for (int j = 0; j < TN; ++j) {
+          const bool el = ((tg[j] & m_all) == m_all) & ((m_any == 0ul) | ((tg[j] & m_any) != 0ul)) & ((tg[j] & m_none) == 0ul);
+          acc[j][r] = el ? acc[j][r] : -INFINITY;
+        }
+      }
+      for (int kk = 0; kk < p.topk; ++kk) {
+        float bs = -INFINITY;
+        int bi = 0x7fffffff, bg = -1;
 #pragma unroll
-          for (int j = 0; j < TN; ++j) {
-            const bool el = ((tg[j] & m_all) == m_all) & ((m_any == 0ul) | ((tg[j] & m_any) != 0ul)) & ((tg[j] & m_none) == 0ul);
-            acc[i][j][r] = el ? acc[i][j][r] : -INFINITY;
+        for (int j = 0; j < TN; ++j) {
+          const float v = acc[j][r];
+          if (v > bs) {
+            bs = v, bi = bn0 + j * 32 + col;
+            if constexpr (LAB) bg = gr[j];
           }
         }
-        for (int kk = 0; kk < p.topk; ++kk) {
-          float bs = -INFINITY;
-          int bi = 0x7fffffff, bg = -1;
 #pragma unroll
-          for (int j = 0; j < TN; ++j) {
-            const float v = acc[i][j][r];
-            if (v > bs) {
-              bs = v, bi = bn0 + j * 32 + col;
-              if constexpr (LAB) bg = gr[j];
-            }
-          }
+        for (int mask = 16; mask > 0; mask >>= 1) {
+          const float os = __shfl_xor(bs, mask);
+          const int oi = __shfl_xor(bi, mask);
+          const int og = LAB ? __shfl_xor(bg, mask) : -1;
+          if (os > bs || (os == bs && oi < bi)) bs = os, bi = oi, bg = og;
+        }
+        if (col == 0 && m < M_eff) {
+          const long o = ((long)m * g.tiles_n + tile_n) * p.topk + kk;
+          p.cand_s[o] = bs;
+          p.cand_i[o] = (bs == -INFINITY) ? -1 : bi;
+        }
 #pragma unroll
-          for (int mask = 16; mask > 0; mask >>= 1) {
-            const float os = __shfl_xor(bs, mask);
-            const int oi = __shfl_xor(bi, mask);
-            const int og = LAB ? __shfl_xor(bg, mask) : -1;
-            if (os > bs || (os == bs && oi < bi)) bs = os, bi = oi, bg = og;
-          }
-          if (col == 0 && m < M_eff) {
-            const long o = ((long)m * g.tiles_n + tile_n) * p.topk + kk;
-            p.cand_s[o] = bs;
-            p.cand_i[o] = (bs == -INFINITY) ? -1 : bi;
-          }
-#pragma unroll
-          for (int j = 0; j < TN; ++j) {
-            bool out = bn0 + j * 32 + col == bi;
-            if constexpr (LAB) out = out || (bg >= 0 && gr[j] == bg);
-            if (out) acc[i][j][r] = -INFINITY;
-          }
+        for (int j = 0; j < TN; ++j) {
+          bool out = bn0 + j * 32 + col == bi;
+          if constexpr (LAB) out = out || (bg >= 0 && gr[j] == bg);
+          if (out) acc[j][r] = -INFINITY;
         }
       }
     }
     return;
   }
 
-  // ---- epilogue: bias, activation, residual, store (C layout: col = lane&31,
-  // row = (r&3) + 8*(r>>2) + 4*(lane>>5)).  ACT >= 0 fixes the activation at compile time. ----
-  auto activate = [&](float x) -> float {
-    if constexpr (ACT == ACT_NONE) return x;
-    else if constexpr (ACT == ACT_GELU) return act_gelu(x);
-    else if constexpr (ACT == ACT_MISH) return act_mish(x);
-    else if constexpr (ACT == ACT_SILU) return act_silu(x);
-    else return apply_act(x, p.act);
-  };
+  // ---- epilogue: bias, activation, residual, store (C layout: col = lane&31, row = gemm_c_row(r) + 4*(lane>>5)).
+  // ACT >= 0 fixes the activation at compile time.  Every branch leaves the activated values in acc for the GRN sums. ----
   const int wave_u = __builtin_amdgcn_readfirstlane(wave);
   const bool interior = (bm0 + BM <= M_eff) && (bn0 + BN <= p.N) && !g.remap && p.crop_boxes == nullptr;
   if (interior) {
     // Whole tile inside the problem, rows map 1:1: no per-element predicates, and every address is
     // (wave-uniform base) + (32-bit lane offset), so stores/loads need no per-element address VALU.
-    const long row0 = (long)bm0 + (long)wave_u * 32 * TM;
+    const long row0 = (long)bm0 + (long)wave_u * 32;
     float* const obase = Op + row0 * p.ldo + p.o_off + bn0;
     const unsigned loff = (unsigned)(4 * half) * (unsigned)p.ldo + (unsigned)col;
     float bv[TN], wsv[TN];
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
-      bv[j] = p.bias != nullptr ? p.bias[bn0 + j * 32 + col] : 0.f;
-      wsv[j] = (PREC == 1 && p.wscale != nullptr) ? p.wscale[bn0 + j * 32 + col] * p.a_unmul : p.a_unmul;
+      bv[j] = gemm_col_bias(p.bias, bn0 + j * 32 + col);
+      wsv[j] = gemm_col_unscale<PREC>(p.wscale, p.a_unmul, bn0 + j * 32 + col);
     }
     if (p.res != nullptr) {
       const float* const rbase = p.res + row0 * p.ldr + bn0;
@@ -488,120 +502,76 @@ __global__ __launch_bounds__(256, (TM * TN == 1 ? (BK == 16 ? 6 : 4) : TM * TN =
       // Issue them in two batches of 8 rows ahead of the math and the stores, so the latencies overlap
       // instead of being paid once per output row.
 #pragma unroll
-      for (int i = 0; i < TM; ++i)
+      for (int hb = 0; hb < 2; ++hb) {
+        float rv[8][TN];
 #pragma unroll
-        for (int hb = 0; hb < 2; ++hb) {
-          float rv[8][TN];
+        for (int q = 0; q < 8; ++q) {
+          const long rr = gemm_c_row(hb * 8 + q);
 #pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            const int r = hb * 8 + q;
-            const long rr = i * 32 + (r & 3) + 8 * (r >> 2);
+          for (int j = 0; j < TN; ++j) rv[q][j] = (rbase + rr * p.ldr + j * 32)[roff];
+        }
 #pragma unroll
-            for (int j = 0; j < TN; ++j) rv[q][j] = (rbase + rr * p.ldr + j * 32)[roff];
-          }
+        for (int q = 0; q < 8; ++q) {
+          const int r = hb * 8 + q;
+          const long rr = gemm_c_row(r);
 #pragma unroll
-          for (int q = 0; q < 8; ++q) {
-            const int r = hb * 8 + q;
-            const long rr = i * 32 + (r & 3) + 8 * (r >> 2);
-#pragma unroll
-            for (int j = 0; j < TN; ++j) {
-              const float v = activate(PREC == 1 ? __builtin_fmaf(acc[i][j][r], wsv[j], bv[j]) : acc[i][j][r] + bv[j]);
-              (obase + rr * p.ldo + j * 32)[loff] = v + rv[q][j];
-              acc[i][j][r] = v;
-            }
+          for (int j = 0; j < TN; ++j) {
+            const float v = act_fixed<ACT>(gemm_scale_bias<PREC>(acc[j][r], wsv[j], bv[j]), p.act);
+            (obase + rr * p.ldo + j * 32)[loff] = v + rv[q][j];
+            acc[j][r] = v;
           }
         }
+      }
     } else if constexpr (EPI == 2) {
-      // LayerNorm over the row (the tile holds all N = BN columns of its rows: gemm_ln_fusable): a row's values sit in
-      // the 32 lanes of one half-wave x TN column blocks; sums over the blocks in j order, then a butterfly over the
-      // lanes (the same two-pass form as ln_rows_kernel: mean, then the squared deviations).
-      float lw[TN], lb[TN];
-#pragma unroll
-      for (int j = 0; j < TN; ++j) lw[j] = p.ln_w[j * 32 + col], lb[j] = p.ln_b[j * 32 + col];
-      const float inv_n = 1.0f / (float)BN;
-#pragma unroll
-      for (int i = 0; i < TM; ++i)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const long rr = i * 32 + (r & 3) + 8 * (r >> 2);
-          float v[TN];
-          float sum = 0.f;
-#pragma unroll
-          for (int j = 0; j < TN; ++j) {
-            v[j] = PREC == 1 ? __builtin_fmaf(acc[i][j][r], wsv[j], bv[j]) : acc[i][j][r] + bv[j];
-            sum += v[j];
-          }
-#pragma unroll
-          for (int m = 16; m > 0; m >>= 1) sum += __shfl_xor(sum, m);
-          const float mean = sum * inv_n;
-          float sq = 0.f;
-#pragma unroll
-          for (int j = 0; j < TN; ++j) {
-            v[j] -= mean;
-            sq += v[j] * v[j];
-          }
-#pragma unroll
-          for (int m = 16; m > 0; m >>= 1) sq += __shfl_xor(sq, m);
-          const float rstd = 1.0f / sqrtf(sq * inv_n + p.ln_eps);
-#pragma unroll
-          for (int j = 0; j < TN; ++j) (obase + rr * p.ldo + j * 32)[loff] = v[j] * rstd * lw[j] + lb[j];
-        }
+      gemm_epi_ln<TN, PREC>(acc, bv, wsv, p.ln_w, p.ln_b, p.ln_eps, obase, p.ldo, loff, col);
     } else {
 #pragma unroll
-      for (int i = 0; i < TM; ++i)
+      for (int r = 0; r < 16; ++r) {
+        const long rr = gemm_c_row(r);
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const long rr = i * 32 + (r & 3) + 8 * (r >> 2);
-#pragma unroll
-          for (int j = 0; j < TN; ++j) {
-            const float v = activate(PREC == 1 ? __builtin_fmaf(acc[i][j][r], wsv[j], bv[j]) : acc[i][j][r] + bv[j]);
-            (obase + rr * p.ldo + j * 32)[loff] = v;
-            acc[i][j][r] = v;
-          }
+        for (int j = 0; j < TN; ++j) {
+          const float v = act_fixed<ACT>(gemm_scale_bias<PREC>(acc[j][r], wsv[j], bv[j]), p.act);
+          (obase + rr * p.ldo + j * 32)[loff] = v;
+          acc[j][r] = v;
         }
+      }
     }
   } else {
 #pragma unroll
     for (int j = 0; j < TN; ++j) {
       const int n = bn0 + j * 32 + col;
       const bool nok = n < p.N;
-      const float bv = (p.bias != nullptr && nok) ? p.bias[n] : 0.f;
-      const float ws = (PREC == 1 && p.wscale != nullptr && nok) ? p.wscale[n] * p.a_unmul : p.a_unmul;
+      const float bv = gemm_col_bias(p.bias, n, nok);
+      const float ws = gemm_col_unscale<PREC>(p.wscale, p.a_unmul, n, nok);
 #pragma unroll
-      for (int i = 0; i < TM; ++i) {
-#pragma unroll
-        for (int r = 0; r < 16; ++r) {
-          const int m = bm0 + wave * 32 * TM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-          float v = 0.f;
-          if (m < M_eff && nok) {
-            v = activate(PREC == 1 ? __builtin_fmaf(acc[i][j][r], ws, bv) : acc[i][j][r] + bv);
-            if (p.crop_boxes != nullptr) {
-              const float* bx = p.crop_boxes + ((long)z * p.crop_rows + m) * 4;
-              const uint32_t py = fdiv((uint32_t)n, g.d_cw);
-              const float fx = (float)((uint32_t)n - py * (uint32_t)p.crop_w), fy = (float)py;
-              const bool inside = fx >= __fmul_rn(bx[0], p.crop_scale) && fx < __fmul_rn(bx[2], p.crop_scale) &&
-                                  fy >= __fmul_rn(bx[1], p.crop_scale) && fy < __fmul_rn(bx[3], p.crop_scale);
-              if (!inside) v = 0.f;
-            }
-            float o = v;
-            if (p.res != nullptr) o += p.res[(long)m * p.ldr + n];
-            long orow = m;
-            if (g.remap) {
-              const uint32_t img = fdiv((uint32_t)m, g.d_ohw);
-              const uint32_t rem = (uint32_t)m - img * (uint32_t)(p.OH * p.OW);
-              const uint32_t oh = fdiv(rem, g.d_ow);
-              const uint32_t ow = rem - oh * (uint32_t)p.OW;
-              orow = ((long)img * p.OH2 + oh * p.os + p.oy) * p.OW2 + ow * p.os + p.ox;
-            }
-            Op[orow * p.ldo + p.o_off + n] = o;
+      for (int r = 0; r < 16; ++r) {
+        const int m = wrow0 + gemm_c_row(r) + 4 * half;
+        float v = 0.f;
+        if (m < M_eff && nok) {
+          v = act_fixed<ACT>(gemm_scale_bias<PREC>(acc[j][r], ws, bv), p.act);
+          if (p.crop_boxes != nullptr) {
+            const float* bx = p.crop_boxes + ((long)z * p.crop_rows + m) * 4;
+            const uint32_t py = fdiv((uint32_t)n, g.d_cw);
+            const float fx = (float)((uint32_t)n - py * (uint32_t)p.crop_w), fy = (float)py;
+            const bool inside = fx >= __fmul_rn(bx[0], p.crop_scale) && fx < __fmul_rn(bx[2], p.crop_scale) &&
+                                fy >= __fmul_rn(bx[1], p.crop_scale) && fy < __fmul_rn(bx[3], p.crop_scale);
+            if (!inside) v = 0.f;
           }
-          acc[i][j][r] = v;
+          float o = v;
+          if (p.res != nullptr) o += p.res[(long)m * p.ldr + n];
+          long orow = m;
+          if (g.remap) {
+            const GemmPixel px = gemm_pixel((uint32_t)m, g.d_ohw, g.d_ow, p.OH * p.OW, p.OW);
+            orow = ((long)px.img * p.OH2 + px.oh * p.os + p.oy) * p.OW2 + px.ow * p.os + p.ox;
+          }
+          Op[orow * p.ldo + p.o_off + n] = o;
         }
+        acc[j][r] = v;
       }
     }
   }
 
-  // ---- GRN partial sums of squares, segmented by image, fixed summation order ----
+  // GRN partial sums of squares over acc (red = smem: the K loop ended on a barrier, LDS is free)
   if (p.grn_part != nullptr) {
     float* red = smem;  // [4][BN]; the K loop ended on a barrier, LDS is free
     const int m_end = (bm0 + BM < M_eff) ? bm0 + BM : M_eff;
@@ -615,18 +585,14 @@ __global__ __launch_bounds__(256, (TM * TN == 1 ? (BK == 16 ? 6 : 4) : TM * TN =
         float sum = 0.f;
         if (one_image) {
 #pragma unroll
-          for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) sum += acc[i][j][r] * acc[i][j][r];
+          for (int r = 0; r < 16; ++r) sum += acc[j][r] * acc[j][r];
         } else {
 #pragma unroll
-          for (int i = 0; i < TM; ++i)
-#pragma unroll
-            for (int r = 0; r < 16; ++r) {
-              const int m = bm0 + wave * 32 * TM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * half;
-              const float v = acc[i][j][r];
-              sum += (m >= lo && m < hi) ? v * v : 0.f;
-            }
+          for (int r = 0; r < 16; ++r) {
+            const int m = wrow0 + gemm_c_row(r) + 4 * half;
+            const float v = acc[j][r];
+            sum += (m >= lo && m < hi) ? v * v : 0.f;
+          }
         }
         sum += __shfl_xor(sum, 32);
         if (half == 0) red[wave * BN + j * 32 + col] = sum;
@@ -643,59 +609,68 @@ __global__ __launch_bounds__(256, (TM * TN == 1 ? (BK == 16 ? 6 : 4) : TM * TN =
   }
 }
 
-template <int TM, int TN, int BK, bool CONV, bool APRO, int EPI, int ACT, int PREC>
+template <int TN, int BK, bool CONV, bool APRO, int EPI, int ACT, int PREC>
 static void launch_one(const GemmDev& g, int grid, hipStream_t s) {
-  const size_t lds = gemm_lds_bytes<TM, TN, BK, APRO, PREC>(g.nseg_max);
-  lds_opt_in<gemm_f32_kernel<TM, TN, BK, CONV, APRO, EPI, ACT, PREC>>(lds, 96 * 1024);
-  hipLaunchKernelGGL((gemm_f32_kernel<TM, TN, BK, CONV, APRO, EPI, ACT, PREC>), dim3(grid, g.a.batch), dim3(256), lds, s, g);
+  const size_t lds = gemm_lds_bytes<TN, BK, APRO, PREC>(g.nseg_max);
+  lds_opt_in<gemm_f32_kernel<TN, BK, CONV, APRO, EPI, ACT, PREC>>(lds, 96 * 1024);
+  hipLaunchKernelGGL((gemm_f32_kernel<TN, BK, CONV, APRO, EPI, ACT, PREC>), dim3(grid, g.a.batch), dim3(256), lds, s, g);
 }
 
 // activation fixed at compile time for the combinations the path uses; anything else takes the
 // runtime-switch instance (ACT = -1)
-template <int TM, int TN, int BK, int PREC>
+template <int TN, int BK, int PREC>
 static void launch_variant(const GemmDev& g, bool conv, bool apro, int grid, hipStream_t s) {
   const int act = g.a.act;
   if (apro) {
-    launch_one<TM, TN, BK, false, true, 0, ACT_NONE, PREC>(g, grid, s);
+    launch_one<TN, BK, false, true, 0, ACT_NONE, PREC>(g, grid, s);
   } else if (conv) {
-    if (act == ACT_SILU) launch_one<TM, TN, BK, true, false, 0, ACT_SILU, PREC>(g, grid, s);
-    else if (act == ACT_NONE) launch_one<TM, TN, BK, true, false, 0, ACT_NONE, PREC>(g, grid, s);
-    else launch_one<TM, TN, BK, true, false, 0, -1, PREC>(g, grid, s);
+    if (act == ACT_SILU) launch_one<TN, BK, true, false, 0, ACT_SILU, PREC>(g, grid, s);
+    else if (act == ACT_NONE) launch_one<TN, BK, true, false, 0, ACT_NONE, PREC>(g, grid, s);
+    else launch_one<TN, BK, true, false, 0, -1, PREC>(g, grid, s);
   } else {
-    if (act == ACT_NONE) launch_one<TM, TN, BK, false, false, 0, ACT_NONE, PREC>(g, grid, s);
-    else if (act == ACT_MISH) launch_one<TM, TN, BK, false, false, 0, ACT_MISH, PREC>(g, grid, s);
-    else if (act == ACT_GELU) launch_one<TM, TN, BK, false, false, 0, ACT_GELU, PREC>(g, grid, s);
-    else if (act == ACT_SILU) launch_one<TM, TN, BK, false, false, 0, ACT_SILU, PREC>(g, grid, s);
-    else launch_one<TM, TN, BK, false, false, 0, -1, PREC>(g, grid, s);
+    if (act == ACT_NONE) launch_one<TN, BK, false, false, 0, ACT_NONE, PREC>(g, grid, s);
+    else if (act == ACT_MISH) launch_one<TN, BK, false, false, 0, ACT_MISH, PREC>(g, grid, s);
+    else if (act == ACT_GELU) launch_one<TN, BK, false, false, 0, ACT_GELU, PREC>(g, grid, s);
+    else if (act == ACT_SILU) launch_one<TN, BK, false, false, 0, ACT_SILU, PREC>(g, grid, s);
+    else launch_one<TN, BK, false, false, 0, -1, PREC>(g, grid, s);
   }
 }
 
-// Picks the instantiation for a plan.  top-k launches (match path: scores + per-tile top-k) use one tile
-// shape, 128 queries x 64 bank rows, BK 16.  Returns false when no kernel exists for the tile.
-template <int PREC>
-static bool gemm_dispatch(const GemmDev& g, const GemmPlan& pl, bool conv, bool apro, int grid, hipStream_t s) {
-  if (g.a.topk > 0) {
-    if (topk_labelled(g.a)) launch_one<1, 2, 16, false, false, 3, ACT_NONE, PREC>(g, grid, s);  // row labels: filter / distinct
-    else launch_one<1, 2, 16, false, false, 1, ACT_NONE, PREC>(g, grid, s);
-    return true;
+// one case per entry of kGemmTiles: the instances are the list
+template <int PREC, size_t I = 0>
+static bool launch_tile(const GemmDev& g, const GemmPlan& pl, bool conv, bool apro, int grid, hipStream_t s) {
+  if constexpr (I < sizeof(kGemmTiles) / sizeof(kGemmTiles[0])) {
+    constexpr GemmTile T = kGemmTiles[I];
+    if (pl.tn == T.tn && pl.bk == T.bk) {
+      launch_variant<T.tn, T.bk, PREC>(g, conv, apro, grid, s);
+      return true;
+    }
+    return launch_tile<PREC, I + 1>(g, pl, conv, apro, grid, s);
   }
-  if (g.a.ln_w != nullptr) {  // fused LayerNorm epilogue: the stem's tile only (gemm_ln_fusable)
-    if (!(pl.tm == 1 && pl.tn == 3 && pl.bk == 16 && conv && !apro && g.a.act == ACT_NONE)) return false;
-    launch_one<1, 3, 16, true, false, 2, ACT_NONE, PREC>(g, grid, s);
-    return true;
-  }
-#define MTGV_CASE(TM_, TN_, BK_)                                \
-  if (pl.tm == TM_ && pl.tn == TN_ && pl.bk == BK_) {           \
-    launch_variant<TM_, TN_, BK_, PREC>(g, conv, apro, grid, s); \
-    return true;                                                \
-  }
-  MTGV_CASE(1, 1, 16) MTGV_CASE(1, 2, 16) MTGV_CASE(1, 3, 16) MTGV_CASE(1, 4, 16) MTGV_CASE(1, 5, 16) MTGV_CASE(1, 1, 32)
-#ifdef MTGV_ALL_TILES  // sweep-only shapes (tools/gemm_sweep.py); never chosen by gemm_plan
-  MTGV_CASE(1, 2, 32) MTGV_CASE(1, 3, 32) MTGV_CASE(1, 4, 32) MTGV_CASE(2, 2, 16) MTGV_CASE(2, 2, 32) MTGV_CASE(2, 1, 16)
-  MTGV_CASE(2, 3, 16) MTGV_CASE(2, 4, 16) MTGV_CASE(2, 3, 32)
-#endif
-#undef MTGV_CASE
   return false;
 }
 
+// Picks the instantiation for a plan (a planned tile is a built one: gemm_plan).  top-k launches (match path: scores +
+// per-tile top-k) use one tile shape, 128 queries x 64 bank rows, BK 16.
+template <int PREC>
+static void gemm_dispatch(const GemmDev& g, const GemmPlan& pl, bool conv, bool apro, int grid, hipStream_t s) {
+  if (g.a.topk > 0) {
+    constexpr GemmTile T = kGemmTopkTile;
+    MTGV_CHECK(pl.tn == T.tn && pl.bk == T.bk, ERR_INVALID, "gemm: top-k planned on tile tn=%d bk=%d", pl.tn, pl.bk);
+    if (topk_labelled(g.a)) launch_one<T.tn, T.bk, false, false, 3, ACT_NONE, PREC>(g, grid, s);  // row labels: filter / distinct
+    else launch_one<T.tn, T.bk, false, false, 1, ACT_NONE, PREC>(g, grid, s);
+    return;
+  }
+  if (g.a.ln_w != nullptr) {  // fused LayerNorm epilogue: the stem's tile only (gemm_ln_fusable)
+    constexpr GemmTile T = kGemmLnTile;
+    MTGV_CHECK(pl.tn == T.tn && pl.bk == T.bk && conv && !apro && g.a.act == ACT_NONE, ERR_INVALID,
+               "gemm: no LayerNorm epilogue for this launch (tn=%d bk=%d)", pl.tn, pl.bk);
+    launch_one<T.tn, T.bk, true, false, 2, ACT_NONE, PREC>(g, grid, s);
+    return;
+  }
+  const bool found = launch_tile<PREC>(g, pl, conv, apro, grid, s);
+  MTGV_CHECK(found, ERR_INVALID, "gemm: no kernel for tile tm=1 tn=%d bk=%d", pl.tn, pl.bk);
+}
+
 }  // namespace mtgv
+

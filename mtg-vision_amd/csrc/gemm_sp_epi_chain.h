@@ -1,5 +1,5 @@
 // Split GEMM epilogue: the chained 1x1 (SP_EPI_CHAIN) and its phase form (SP_EPI_CHAIN_PHASE).
-// Included by gemm_sp_kernel.h, which defines SpDev, spf16 and the helpers used here (sp_activate, sp_sw, sp_slots,
+// Included by gemm_sp_kernel.h, which defines SpDev, spf16 and the helpers used here (sp_sw, sp_slots,
 // sp_pixel, sp_mfma3, sp_block_put / sp_block_get).
 //
 // A following 1x1 conv / Linear whose input is this launch's whole output row runs here: the activated values of the
@@ -69,7 +69,7 @@ __device__ __forceinline__ void sp_epi_chain(const SpDev& g, spf16 (&acc)[1][TN]
         if constexpr (PHASE) br = *reinterpret_cast<const sp_f4*>(g.bias_tab + bcls[it] * g.N + n);
         sp_f4 v;
 #pragma unroll
-        for (int e = 0; e < 4; ++e) v[e] = sp_activate<ACT>(__builtin_fmaf(raw[e], w1[e] * g.a_unmul, br[e]), g.act);
+        for (int e = 0; e < 4; ++e) v[e] = act_fixed<ACT>(__builtin_fmaf(raw[e], w1[e] * g.a_unmul, br[e]), g.act);
         // this lane's 16-byte piece of the row's SP8 form (even quads: the chunk's hi halves, odd quads: its lo halves)
         *reinterpret_cast<sp_f4*>(a2 + j * CB + row * 128 + ((slot ^ sp_sw<2>(row)) << 4)) = __builtin_bit_cast(sp_f4, sp8_piece_from_quad(v, slot));
       }

@@ -55,7 +55,7 @@
 //
 // Where things are.  This file: SpDev, the helpers every part shares (sp_sw: row swizzle; sp_slots: the hi / lo fragment
 // slots of a k16 step; sp_pixel: m -> (img, oh, ow); sp_mfma3: the three products of a k16 step; sp_block_put / sp_block_get:
-// one accumulator column block through a wave's staging rows; sp_activate), and the kernel, whose body reads set-up, main
+// one accumulator column block through a wave's staging rows), and the kernel, whose body reads set-up, main
 // loop, pick the epilogue:
 //   gemm_sp_epi_chain.h   sp_epi_chain<PHASE>: the chained 1x1 and its phase form (EPI 32 / 96)
 //   gemm_sp_epi_topk.h    sp_epi_topk<LABELS>: the fused top-k, plain and labelled (EPI 16 / 17), one function
@@ -202,16 +202,6 @@ __device__ __forceinline__ void sp_block_put(char* stg, const spf16& a, int j, i
 template <int SROW>
 __device__ __forceinline__ sp_f4 sp_block_get(const char* stg, int j, int it, int lrow, int slot) {
   return *reinterpret_cast<const sp_f4*>(stg + (it * 8 + lrow) * SROW + j * 128 + ((slot ^ lrow) << 4));
-}
-
-// The launch's activation: ACT fixes it at compile time, SP_ACT_ARGS reads it from the arguments.
-template <int ACT>
-__device__ __forceinline__ float sp_activate(float x, int act) {
-  if constexpr (ACT == ACT_NONE) return x;
-  else if constexpr (ACT == ACT_GELU) return act_gelu(x);
-  else if constexpr (ACT == ACT_MISH) return act_mish(x);
-  else if constexpr (ACT == ACT_SILU) return act_silu(x);
-  else return apply_act(x, act);
 }
 
 }  // namespace mtgv
@@ -885,7 +875,7 @@ __global__ __launch_bounds__(64 * WM * WN, (WM * WN == 8 ? 4 : 2)) void gemm_sp_
         sp_f4 v;
 #pragma unroll
         for (int e = 0; e < 4; ++e)  // wsc is a power of two: the fused form rounds exactly like multiply-then-add
-          v[e] = sp_activate<ACT>(__builtin_fmaf(raw[e], wsc[j][e], bsv[j][e]), g.act);
+          v[e] = act_fixed<ACT>(__builtin_fmaf(raw[e], wsc[j][e], bsv[j][e]), g.act);  // SP_ACT_ARGS: g.act
         if (grn) {
           if (single) {
             if (ok) {

@@ -152,10 +152,6 @@ __global__ __launch_bounds__(256, 2) void mlp_fused_kernel(const MlpDev g) {
   };
   const unsigned swr = (unsigned)(r >> 1) & 7u;
   const unsigned frag = (unsigned)r * 128u;
-  auto activate = [&](float x) -> float {
-    if constexpr (ACT == ACT_GELU) return act_gelu(x);
-    else return act_mish(x);
-  };
   // this wave's pieces of every slot but the N youngest have landed
   auto wait_but = [&](int slots_in_flight) {
     if (slots_in_flight >= 4) asm volatile("s_waitcnt vmcnt(%0) lgkmcnt(0)" ::"n"(4 * PPW) : "memory");
@@ -217,7 +213,7 @@ __global__ __launch_bounds__(256, 2) void mlp_fused_kernel(const MlpDev g) {
       float ssq = 0.f;
 #pragma unroll
       for (int q = 0; q < 16; ++q) {
-        const float a = activate(__builtin_fmaf(acc[q], ws, bs));
+        const float a = act_fixed<ACT>(__builtin_fmaf(acc[q], ws, bs), ACT);
         ssq = __builtin_fmaf(a, a, ssq);
       }
       ssq += __shfl_xor(ssq, 32);

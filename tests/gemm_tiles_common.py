@@ -28,8 +28,8 @@ import numpy as np
 import torch
 import torch.nn.functional as F
 
-TILES = [(1, 1, 16), (1, 2, 16), (1, 3, 16), (1, 4, 16), (1, 5, 16), (1, 1, 32)]  # gemm_dispatch's MTGV_CASE list
-UNBUILT = [(1, 2, 32), (2, 2, 16)]  # accepted by MTGV_GEMM_TILE, instantiated only with MTGV_ALL_TILES
+TILES = [(1, 1, 16), (1, 2, 16), (1, 3, 16), (1, 4, 16), (1, 5, 16), (1, 1, 32)]  # gemm_kernel.h: kGemmTiles, as (1, tn, bk)
+UNBUILT = [(1, 2, 32), (2, 2, 16)]  # well-formed for MTGV_GEMM_TILE but not in kGemmTiles (tm is always 1): refused when the launch is planned
 BM = 128
 TOL = 3e-5
 GRN_RTOL = 1e-5

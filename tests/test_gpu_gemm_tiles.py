@@ -226,6 +226,44 @@ def test_tile_that_is_not_built_is_an_error(tile, mode):
     assert (out.dev.cpu().numpy().view(np.uint32) == CANARY).all(), "the refused launch wrote to its output"
 
 
+@pytest.mark.parametrize("mode", MODES)
+def test_refused_tile_leaves_no_row_in_the_profile(tmp_path, mode):
+    """the tile is refused before the launch profiler records anything: a refused launch followed by a real one leaves
+    the real one's row alone in the table, so a row's shape and tile always belong to the time beside them"""
+    from mtgv import native as nv
+
+    L = nv.lib()
+    nv.set_gemm_precision(mode)
+    case = gc.DENSE_BY_NAME[gc.UNBUILT_CASE]
+    T = {k: dev(v) for k, v in gc.dense_draw(case.name).items()}
+    out = Out(case.M, case.N)
+    csv = str(tmp_path / "gemm.csv")
+
+    def launch():
+        return L.mtgv_op_linear(nv.ptr(T["a"]), nv.ptr(T["w"]), nv.ptr(T["b"]), None, out.ptr, case.M, case.N, case.K, case.act, nv.stream())
+
+    nv.check(L.mtgv_profile_gemm(1))
+    try:
+        with forced_tile((1, 2, 32)):
+            rc = launch()
+        assert rc == 1 and b"no kernel for tile" in L.mtgv_last_error(), (rc, L.mtgv_last_error())
+        with forced_tile((1, 2, 16)):
+            nv.check(launch())
+        torch.cuda.synchronize()
+        nv.check(L.mtgv_profile_gemm_dump(csv.encode()))
+        ms, flops, launches = C.c_double(0), C.c_double(0), C.c_int64(0)
+        nv.check(L.mtgv_profile_gemm_read(C.byref(ms), C.byref(flops), C.byref(launches)))
+    finally:
+        nv.check(L.mtgv_profile_gemm(0))
+    rows = [ln.split(",") for ln in open(csv).read().split()[1:]]
+    assert len(rows) == 1, rows
+    r = rows[0]
+    assert (int(r[COL_TM]), int(r[COL_TN]), int(r[COL_BK])) == (1, 2, 16) and r[COL_SP] == "0", r
+    assert (int(r[COL_M]), int(r[COL_N]), int(r[COL_K])) == (case.M, case.N, case.K), r
+    assert launches.value == 1, launches.value
+    assert np.isfinite(out.read()[0]).all()
+
+
 # ---- conv ----
 def run_conv(tmp_path, case, tile, T):
     from mtgv import native as nv
