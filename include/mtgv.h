@@ -40,7 +40,8 @@ MTGV_API const char* mtgv_last_error(void);
  * 111: mtgv_letterbox_ragged_u8, mtgv_warp_quads_src (crops from full-resolution source frames)
  * 115: the embed budget of the tracker (mtgv_tracker_create_budget, mtgv_tracker_update_budget, mtgv_tracker_gather_u8_pad,
  *      mtgv_op_track_select)
- * 116: mtgv_op_mask_logits (the detector's mask stage as a single op) */
+ * 116: mtgv_op_mask_logits (the detector's mask stage as a single op)
+ * 117: mtgv_letterbox_tiles_u8, mtgv_tiles_merge (detection on overlapping windows of large source frames) */
 MTGV_API int mtgv_version(void);
 /* number of HIP devices visible; does not initialise a device context */
 MTGV_API int mtgv_device_count(void);
@@ -502,6 +503,40 @@ MTGV_API int mtgv_letterbox_rect_u8(const uint8_t* src_dev, int32_t n, int32_t h
  * all pad.  The caller guarantees offsets[i] + h * w * 3 <= the buffer. */
 MTGV_API int mtgv_letterbox_ragged_u8(const uint8_t* src_dev, const int64_t* offsets_dev, const int32_t* hw_dev, const int32_t* geo_dev,
                                       int32_t n, uint8_t* dst_dev, int32_t dst_h, int32_t dst_w, int32_t pad_value, void* stream);
+/* Tiled detection, the cut (mtgv_version >= 117): nt windows of the nf ragged frames, each letterboxed into its own
+ * detector input, in one launch.  tiles_dev (nt, 5) int32 = frame, y0, x0, wh, ww (frame pixels), geo_dev (nt, 4) int32 =
+ * nh, nw, top, left of each window's fit into (dst_h, dst_w) (mtgv.detector.fit_geometry(wh, ww, dst_h, dst_w)).  Output
+ * pixel (y, x) of dst_dev[t] is what mtgv_letterbox_ragged_u8 writes for a contiguous copy of the window - the same float32
+ * resample, the window's rows read w * 3 bytes apart in place; a window of the input's size is copied exactly.  The tables
+ * are not validated by the host: a window is clamped into its frame, a frame index outside [0, nf) or an empty window is
+ * all pad, writes stay inside dst_dev[t] and no byte outside a frame's own h * w * 3 is read.  nt <= 65535. */
+MTGV_API int mtgv_letterbox_tiles_u8(const uint8_t* src_dev, const int64_t* offsets_dev, const int32_t* hw_dev, int32_t nf,
+                                     const int32_t* tiles_dev, const int32_t* geo_dev, int32_t nt, uint8_t* dst_dev, int32_t dst_h, int32_t dst_w,
+                                     int32_t pad_value, void* stream);
+/* Tiled detection, the merge (mtgv_version >= 117): per-tile detector outputs -> the k cards of every frame in camera pixels
+ * ("Tiled detection"; mtgv/tiles.py: merge_tiles_host is the rule in numpy, matched bit for bit).
+ * n_det_dev (nt), boxes_dev (nt, max_det, 4) xyxy in the pixels of each tile's detector input, score-descending, conf_dev
+ * (nt, max_det): mtgv_detector_forward's outputs with the tiles as frames.  quads_dev (nt * kt, 4, 2): the quads of the first
+ * kt detections per tile (mtgv_mask_quads_logits), or NULL: the boxes' corners (TL, TR, BR, BL).  tiles_dev, geo_dev as for
+ * mtgv_letterbox_tiles_u8, ratio_dev (nt) float64; tile_start_dev (frames + 1) int32: frame f owns tiles
+ * [tile_start[f], tile_start[f + 1]); hw_dev (frames, 2) int32; pad_frac_dev (k, 4) float32.
+ *   candidates  detection j < min(n_det[t], kt) of tile t
+ *   mapping     float64 x = (x_det - left) / ratio + x0 clipped to [x0, x0 + ww], y likewise, rounded to float32
+ *   cut rule    a window side that is no side of the frame is an inner side; dropped if bx0 < x0 + edge, bx1 > x0 + ww - edge
+ *               (or the same in y) at an inner side, in float32
+ *   order       conf descending, tile ascending, j ascending
+ *   greedy      dropped if inter > ios_thr * min(area_a, area_b) against an earlier kept one (float32, strict)
+ *   slots       the first k kept fill slots 0 .. n_sel - 1; slot >= n_sel is pad_frac[slot] * (w, h, w, h), conf 0, src_slot -1
+ * Writes sel_boxes_src_dev (frames * k, 4), quads_src_dev (frames * k, 4, 2), frame_idx_dev, sel_conf_dev, src_slot_dev
+ * (frames * k; t * kt + j) and n_sel_dev (frames).  Caps, checked from the arguments before anything touches a device
+ * (status 1 with the numbers): k <= 64, kt <= max_det, frames <= 65535, max_tiles_per_frame * kt <= 1024.  The kernel
+ * trusts tile_start no further than max_tiles_per_frame: a frame whose range is longer, negative or outside [0, nt] gets
+ * n_sel = 0 and pads. */
+MTGV_API int mtgv_tiles_merge(const int32_t* n_det_dev, const float* boxes_dev, const float* conf_dev, const float* quads_dev, int32_t nt,
+                              int32_t max_det, int32_t kt, const int32_t* tiles_dev, const int32_t* geo_dev, const double* ratio_dev,
+                              const int32_t* tile_start_dev, const int32_t* hw_dev, int32_t frames, int32_t max_tiles_per_frame,
+                              const float* pad_frac_dev, int32_t k, float edge, float ios_thr, float* sel_boxes_src_dev, float* quads_src_dev,
+                              int32_t* frame_idx_dev, float* sel_conf_dev, int32_t* src_slot_dev, int32_t* n_sel_dev, void* stream);
 /* fills the pad of n letterboxed (size, size, 3) uint8 frames with pad_value: every pixel outside the (nh, nw) rectangle
  * at (top, left), which someone else writes (mtgv.jpeg.JpegDecoder.decode_frames decodes a frame that already fits
  * straight into it) */

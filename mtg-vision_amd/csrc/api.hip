@@ -109,7 +109,8 @@ MTGV_API const char* mtgv_last_error(void) { return last_error_cstr(); }
 // 114: mtgv_op_psa_attn, mtgv_op_dwconv3 (YOLO11's C2PSA attention and the depthwise 3x3 as single ops)
 // 115: the embed budget (mtgv_tracker_create_budget, mtgv_tracker_update_budget, mtgv_tracker_gather_u8_pad, mtgv_op_track_select)
 // 116: mtgv_op_mask_logits (the detector's mask stage as a single op)
-MTGV_API int mtgv_version(void) { return 116; }
+// 117: mtgv_letterbox_tiles_u8, mtgv_tiles_merge (tiled detection: the cut and the merge)
+MTGV_API int mtgv_version(void) { return 117; }
 MTGV_API int mtgv_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;

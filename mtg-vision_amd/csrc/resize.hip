@@ -61,9 +61,10 @@ __global__ __launch_bounds__(256) void make_cropped_kernel(const uint8_t* __rest
 // interpolate uses, in float32 in this order: src = scale * (dst + 0.5) - 0.5 clamped at 0, h0 * (w0 * v00 + w1 * v01) +
 // h1 * (w0 * v10 + w1 * v11), rounded to nearest even, clamped to [0, 255] (oracle/resize_ref.py: letterbox).  A frame
 // that already has the target size is copied exactly (all weights 0 or 1).  letterbox_pixel is output pixel (y, x) of one
-// frame, shared by the two kernels below.
-__device__ __forceinline__ void letterbox_pixel(const uint8_t* __restrict__ src, int h, int w, uint8_t* __restrict__ o, int y, int x, int nh,
-                                                int nw, int top, int left, int pad_value) {
+// frame, shared by the kernels below.  `pitch`: pixels between the starts of two rows of src - w for a whole frame, the
+// frame's width for a window of it (letterbox_tiles_u8_kernel).
+__device__ __forceinline__ void letterbox_pixel(const uint8_t* __restrict__ src, int h, int w, int pitch, uint8_t* __restrict__ o, int y, int x,
+                                                int nh, int nw, int top, int left, int pad_value) {
 #pragma clang fp contract(off)
   const int ry = y - top, rx = x - left;
   if (ry < 0 || ry >= nh || rx < 0 || rx >= nw) {
@@ -80,8 +81,8 @@ __device__ __forceinline__ void letterbox_pixel(const uint8_t* __restrict__ src,
   const int y1 = y0 + (y0 < h - 1 ? 1 : 0), x1 = x0 + (x0 < w - 1 ? 1 : 0);
   const float ly1 = sy - (float)y0, lx1 = sx - (float)x0;
   const float ly0 = 1.0f - ly1, lx0 = 1.0f - lx1;
-  const uint8_t *p00 = src + ((long)y0 * w + x0) * 3, *p01 = src + ((long)y0 * w + x1) * 3, *p10 = src + ((long)y1 * w + x0) * 3,
-                *p11 = src + ((long)y1 * w + x1) * 3;
+  const uint8_t *p00 = src + ((long)y0 * pitch + x0) * 3, *p01 = src + ((long)y0 * pitch + x1) * 3, *p10 = src + ((long)y1 * pitch + x0) * 3,
+                *p11 = src + ((long)y1 * pitch + x1) * 3;
 #pragma unroll
   for (int c = 0; c < 3; ++c) {
     const float v = ly0 * (lx0 * (float)p00[c] + lx1 * (float)p01[c]) + ly1 * (lx0 * (float)p10[c] + lx1 * (float)p11[c]);
@@ -97,7 +98,7 @@ __global__ __launch_bounds__(256) void letterbox_u8_kernel(const uint8_t* __rest
   const int idx = blockIdx.x * 256 + threadIdx.x;
   if (idx >= dst_h * dst_w) return;
   const int y = idx / dst_w, x = idx - y * dst_w;
-  letterbox_pixel(src + (long)blockIdx.y * h * w * 3, h, w, dst + ((long)blockIdx.y * dst_h * dst_w + idx) * 3, y, x, nh, nw, top, left,
+  letterbox_pixel(src + (long)blockIdx.y * h * w * 3, h, w, w, dst + ((long)blockIdx.y * dst_h * dst_w + idx) * 3, y, x, nh, nw, top, left,
                   pad_value);
 }
 
@@ -113,8 +114,37 @@ __global__ __launch_bounds__(256) void letterbox_ragged_u8_kernel(const uint8_t*
   const int f = blockIdx.y;
   const int h = hw[f * 2], w = hw[f * 2 + 1];
   const int nh = (h > 0 && w > 0) ? geo[f * 4] : 0;
-  letterbox_pixel(src + offsets[f], h, w, dst + ((long)f * dst_h * dst_w + idx) * 3, y, x, nh, geo[f * 4 + 1], geo[f * 4 + 2], geo[f * 4 + 3],
+  letterbox_pixel(src + offsets[f], h, w, w, dst + ((long)f * dst_h * dst_w + idx) * 3, y, x, nh, geo[f * 4 + 1], geo[f * 4 + 2], geo[f * 4 + 3],
                   pad_value);
+}
+
+// blockIdx.y: one of nt windows (tiles (nt, 5) = frame, y0, x0, wh, ww) of the nf ragged frames, each letterboxed into its
+// own dst[t] with its own geometry (geo (nt, 4) = nh, nw, top, left of the window's fit): letterbox_pixel on the window, whose
+// rows lie the frame's width apart.  The tables come from device memory unchecked: the window is clamped into its frame
+// (so no byte outside the frame's h * w * 3 is read), a frame index outside [0, nf), a frame without pixels or an empty
+// window is all pad, and a thread writes only its own pixel of dst[t].
+__global__ __launch_bounds__(256) void letterbox_tiles_u8_kernel(const uint8_t* __restrict__ src, const long* __restrict__ offsets,
+                                                                const int* __restrict__ hw, int nf, const int* __restrict__ tiles,
+                                                                const int* __restrict__ geo, uint8_t* __restrict__ dst, int dst_h, int dst_w,
+                                                                int pad_value) {
+  const int idx = blockIdx.x * 256 + threadIdx.x;
+  if (idx >= dst_h * dst_w) return;
+  const int y = idx / dst_w, x = idx - y * dst_w;
+  const int t = blockIdx.y;
+  const int f = tiles[t * 5];
+  int y0 = tiles[t * 5 + 1], x0 = tiles[t * 5 + 2], wh = tiles[t * 5 + 3], ww = tiles[t * 5 + 4];
+  int h = 0, w = 0;
+  if (f >= 0 && f < nf) h = hw[f * 2], w = hw[f * 2 + 1];
+  const uint8_t* win = src;
+  int nh = 0;
+  if (h > 0 && w > 0) {
+    y0 = y0 < 0 ? 0 : (y0 > h ? h : y0);
+    x0 = x0 < 0 ? 0 : (x0 > w ? w : x0);
+    wh = wh > h - y0 ? h - y0 : wh;
+    ww = ww > w - x0 ? w - x0 : ww;
+    if (wh > 0 && ww > 0) win = src + offsets[f] + ((long)y0 * w + x0) * 3, nh = geo[t * 4];
+  }
+  letterbox_pixel(win, wh, ww, w, dst + ((long)t * dst_h * dst_w + idx) * 3, y, x, nh, geo[t * 4 + 1], geo[t * 4 + 2], geo[t * 4 + 3], pad_value);
 }
 
 // pad of n letterboxed dst_h x dst_w x 3 frames whose (nh, nw) image at (top, left) is written by someone else
@@ -176,6 +206,19 @@ MTGV_API int mtgv_letterbox_ragged_u8(const uint8_t* src_dev, const int64_t* off
     MTGV_CHECK(src_dev && offsets_dev && hw_dev && geo_dev && dst_dev, ERR_INVALID, "null argument");
     hipLaunchKernelGGL(letterbox_ragged_u8_kernel, dim3((dst_h * dst_w + 255) / 256, n), dim3(256), 0, (hipStream_t)stream, src_dev,
                        (const long*)offsets_dev, hw_dev, geo_dev, dst_dev, dst_h, dst_w, pad_value);
+    HIP_OK(hipGetLastError());
+  });
+}
+MTGV_API int mtgv_letterbox_tiles_u8(const uint8_t* src_dev, const int64_t* offsets_dev, const int32_t* hw_dev, int32_t nf,
+                                     const int32_t* tiles_dev, const int32_t* geo_dev, int32_t nt, uint8_t* dst_dev, int32_t dst_h, int32_t dst_w,
+                                     int32_t pad_value, void* stream) {
+  return guarded([&] {
+    MTGV_CHECK(nf >= 0 && nt >= 0 && nt <= 65535 && dst_h > 0 && dst_w > 0 && (long)dst_h * dst_w < (1l << 30) && pad_value >= 0 && pad_value <= 255,
+               ERR_INVALID, "letterbox tiles: %d tiles of %d frames -> %dx%d, pad value %d", nt, nf, dst_h, dst_w, pad_value);
+    if (nt == 0) return;
+    MTGV_CHECK(src_dev && offsets_dev && hw_dev && tiles_dev && geo_dev && dst_dev, ERR_INVALID, "null argument");
+    hipLaunchKernelGGL(letterbox_tiles_u8_kernel, dim3((dst_h * dst_w + 255) / 256, nt), dim3(256), 0, (hipStream_t)stream, src_dev,
+                       (const long*)offsets_dev, hw_dev, nf, tiles_dev, geo_dev, dst_dev, dst_h, dst_w, pad_value);
     HIP_OK(hipGetLastError());
   });
 }

@@ -18,6 +18,7 @@ _LAZY = {
     "ShardedMatcher": ("dist", "ShardedMatcher"),
     "Pipeline": ("pipeline", "Pipeline"),
     "SourceFrames": ("pipeline", "SourceFrames"),
+    "TiledFrames": ("tiles", "TiledFrames"),
     "warp_quads": ("crop", "warp_quads"),
     "warp_quads_src": ("crop", "warp_quads_src"),
     "DeviceTracker": ("track", "DeviceTracker"),

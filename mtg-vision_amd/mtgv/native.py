@@ -133,6 +133,12 @@ SIGNATURES = {
     "mtgv_letterbox_u8": (C.c_int, [c_vp, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "mtgv_letterbox_rect_u8": (C.c_int, [c_vp, c_i32, c_i32, c_i32, c_vp, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_i32, c_vp]),
     "mtgv_letterbox_ragged_u8": (C.c_int, [c_vp, c_vp, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp]),  # mtgv_version >= 111
+    "mtgv_letterbox_tiles_u8": (C.c_int, [c_vp, c_vp, c_vp, c_i32, c_vp, c_vp, c_i32, c_vp, c_i32, c_i32, c_i32, c_vp]),  # mtgv_version >= 117
+    "mtgv_tiles_merge": (
+        C.c_int,
+        [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_f32, c_f32]
+        + [c_vp] * 6 + [c_vp],
+    ),
     "mtgv_profile_gemm": (C.c_int, [c_i32]),
     "mtgv_profile_gemm_read": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(c_i64)]),
     "mtgv_profile_gemm_bytes": (C.c_int, [C.POINTER(C.c_double)]),

@@ -20,6 +20,7 @@ from .crop import mask_quads_from_logits, obb_cards, select_cards, warp_quads, w
 from .detector import Detector, fit_geometry
 from .encoder import Encoder
 from .matcher import Matcher
+from .tiles import TiledFrames, merge_tiles
 
 # fixed quads (pixels of the 640x640 frame; scaled with a rectangular detector's input, Pipeline.__init__) used when a frame has fewer than K detections, so that
 # cards/sec is well defined on synthetic frames
@@ -170,11 +171,21 @@ def _frames_of(item):
     return item, None, None
 
 
+def _no_tiles(batches, who: str):
+    """the batches of a run_many, refusing a TiledFrames when its turn comes"""
+    for b in batches:
+        if isinstance(b[0] if isinstance(b, tuple) else b, TiledFrames):
+            raise NotImplementedError(f"{who} does not take TiledFrames: the overlapped schedule for a tile batch is not built; call run per batch")
+        yield b
+
+
 @dataclass
 class Cropped:
     """What `Pipeline.crop` hands on.  boxes (F, K, 4); crops (F * K, h, w, 3) uint8; quads (F * K, 4, 2): what the de-warp
     was given, pixels of the detector's input; quads_src: the same corners in camera pixels (SourceFrames only); card_state
-    (F * K,) ("obb" only); thumbs, thumb_offsets: filled by `Pipeline._thumbnails` when the pipeline encodes them."""
+    (F * K,) ("obb" only); thumbs, thumb_offsets: filled by `Pipeline._thumbnails` when the pipeline encodes them.
+    TiledFrames only: boxes, quads and quads_src are all camera pixels, n_sel (F,) is the frames' card count (the step's
+    n_det) and tile_slot (F * K,) each card's tile * cards_per_tile + detection, -1 for a pad."""
 
     boxes: torch.Tensor
     crops: torch.Tensor
@@ -183,6 +194,8 @@ class Cropped:
     card_state: Optional[torch.Tensor] = None
     thumbs: Optional[torch.Tensor] = None
     thumb_offsets: Optional[torch.Tensor] = None
+    n_sel: Optional[torch.Tensor] = None
+    tile_slot: Optional[torch.Tensor] = None
 
     def extras(self, det: dict, F: int, K: int) -> dict:
         """the optional parts as an output dict carries them; those that are no thumbnails go into its `det` as well"""
@@ -192,6 +205,8 @@ class Cropped:
         if self.quads_src is not None:
             out["quads_src"] = self.quads_src.view(F, K, 4, 2)
         det.update(out)
+        if self.tile_slot is not None:  # (behind det.update: det keeps the per-tile n_det)
+            out["n_det"], out["tile_slot"] = self.n_sel, self.tile_slot.view(F, K)
         if self.thumbs is not None:
             out["thumbs"], out["thumb_offsets"] = self.thumbs, self.thumb_offsets
         return out
@@ -200,7 +215,7 @@ class Cropped:
 class Pipeline:
     def __init__(self, detector: Detector, encoder: Encoder, matcher, cards_per_frame: int = 8, top_k: int = 1,
                  match_fn: Optional[Callable] = None, quad_source: str = "box", thumbnail_quality: Optional[int] = None,
-                 match_opts: Optional[dict] = None):
+                 match_opts: Optional[dict] = None, cards_per_tile: Optional[int] = None, tile_merge: Optional[dict] = None):
         """quad_source: "box" crops the detection boxes (the synthetic bench workload, SURVEY.md section 8d config 4);
         "mask" crops the oriented quad fitted to each detection's mask, as the reference does
         (od_export.py:52-111: InstanceSeg._orient + extract_dewarped); "obb" (an OBB detector, spec.DetectorConfig(task="obb"))
@@ -212,7 +227,9 @@ class Pipeline:
         output gains `thumbs` (packed files, device) and `thumb_offsets` ((F * K + 1,) int64, device), file j being
         thumbs[thumb_offsets[j]:thumb_offsets[j + 1]].  None (default): no encode, no extra launch.
         match_opts: keyword arguments handed to `matcher.match` (threshold, filter, distinct), like TrackedPipeline's;
-        None keeps the call as it is.  `matcher` may be a `mtgv.ShardedMatcher` (the row-sharded bank)."""
+        None keeps the call as it is.  `matcher` may be a `mtgv.ShardedMatcher` (the row-sharded bank).
+        cards_per_tile, tile_merge: read only by `run(TiledFrames)` - the detections kept per tile (None: cards_per_frame) and
+        the merge rule's `edge` (pixels) and `ios` (mtgv.tiles.merge_tiles_host; None: edge 2.0, ios 0.5)."""
         assert quad_source in ("box", "mask", "obb"), quad_source
         task = getattr(getattr(detector, "cfg", None), "task", "seg")
         assert (quad_source == "obb") == (task == "obb"), f'quad_source "{quad_source}" with a {task} detector'
@@ -246,6 +263,13 @@ class Pipeline:
         pad = _PAD_BOXES * torch.tensor([sx, sy, sx, sy])
         self._pad = pad.repeat(reps, 1)[: self.K].to(detector.device).contiguous()
         self._warp_ws = None
+        self.Kt = self.K if cards_per_tile is None else int(cards_per_tile)
+        self.tile_merge = {"edge": 2.0, "ios": 0.5, **(tile_merge or {})}
+        assert set(self.tile_merge) == {"edge", "ios"}, f"tile_merge keys {sorted(self.tile_merge)}: expected edge, ios"
+        # the tiled path's pads: fractions of each frame's own size, and the per-tile pad of select_cards
+        self._pad_frac = (_PAD_BOXES / 640.0).repeat(reps, 1)[: self.K].to(detector.device).contiguous()
+        treps = (self.Kt + _PAD_BOXES.shape[0] - 1) // _PAD_BOXES.shape[0]
+        self._pad_tile = pad.repeat(treps, 1)[: self.Kt].to(detector.device).contiguous()
 
     def _embed_match(self, frames_u8: torch.Tensor, det, lease=None, src=None):
         return self._embed(det, self._thumbnails(self.crop(frames_u8, det, lease, src)))
@@ -337,6 +361,7 @@ class Pipeline:
         the library, kernels sharing a CU with the split-precision GEMM of the other stream sporadically lost a
         packed result in one 16-lane group; the library is built without those instructions - build.py, DESIGN.md
         section 5 - and tests/test_gpu_overlap.py guards the combination.)"""
+        batches = _no_tiles(batches, "Pipeline.run_many")
         if not self.overlap_enabled():
             return [self.run(frames, flip_rgb) for frames in batches]
         crop_on_det, s_match, cur = self._overlap_streams()
@@ -438,6 +463,35 @@ class Pipeline:
         A `SourceFrames` (or a lease that has `sources()`) instead: detection runs on its `frames`, the quads go back into
         the camera's frames and the cards are cropped from those at their own resolution; the dict gains quads_src
         (F, K, 4, 2), the corners in camera pixels.  boxes (and an OBB detector's quads) stay pixels of the detector's input."""
+        if isinstance(frames_u8, TiledFrames):
+            det, cropped = self.detect_crop_tiled(frames_u8, flip_rgb)
+            return self._embed(det, self._thumbnails(cropped))
         frames_u8, lease, src = _frames_of(frames_u8)
         det = self.detector.forward(frames_u8, flip_rgb, mask_rows=self.K)
         return self._embed_match(frames_u8, det, lease, src)
+
+    def detect_crop_tiled(self, tf: TiledFrames, flip_rgb: bool = True):
+        """The detect and crop stages of a `TiledFrames` batch -> (det, Cropped).  The detector runs on the tiles as if they
+        were frames, in chunks of its max_batch (`det`: its outputs per tile, concatenated); the K best cards of every frame
+        come out of mtgv_tiles_merge in camera pixels (mtgv.tiles.merge_tiles_host is the rule) and are de-warped from the
+        source frames.  Output per frame: boxes (F, K, 4) and quads_src (F, K, 4, 2) in camera pixels, n_det = the merge's n_sel,
+        tile_slot (F, K) = tile * cards_per_tile + detection of every card (-1: a pad)."""
+        if self.quad_source == "obb":
+            raise NotImplementedError('quad_source "obb" does not take TiledFrames: merging rotated boxes needs a rotated overlap rule')
+        F, K, Kt = tf.n_frames, self.K, self.Kt
+        nt, mb = int(tf.frames.shape[0]), self.detector.max_batch
+        assert F > 0 and nt > 0, "a TiledFrames batch without frames"
+        want_mask = self.quad_source == "mask"
+        parts = [self.detector.forward(tf.frames[i : i + mb], flip_rgb, mask_rows=Kt if want_mask else 0) for i in range(0, nt, mb)]
+        det = parts[0] if len(parts) == 1 else {k: (None if v is None else torch.cat([p[k] for p in parts])) for k, v in parts[0].items()}
+        quads = None  # "box": the merge takes the boxes' corners itself
+        if want_mask:
+            sel, _, _ = select_cards(det["n_det"], det["boxes"], self._pad_tile, Kt, want_quads=False)
+            ml = det["mask_logits"]
+            quads, _ = mask_quads_from_logits(ml.view(nt * Kt, *ml.shape[-2:]), sel)
+        m = merge_tiles(tf, det["n_det"], det["boxes"], det["conf"], quads, Kt, self._pad_frac, K, self.tile_merge["edge"], self.tile_merge["ios"])
+        if self._warp_ws is None or self._warp_ws.numel() < 9 * F * K:
+            self._warp_ws = warp_workspace(F * K, tf.buf.device)
+        # the quads are camera pixels already: an identity geometry makes mtgv_warp_quads_src read them as they are
+        crops, quads_src = crop.warp_quads_src(tf.sources(), m["quads_src"], m["frame_idx"], self.encoder.cfg.image_hw, 0.05, self._warp_ws)
+        return det, Cropped(m["sel_boxes_src"].view(F, K, 4), crops, quads_src, quads_src, n_sel=m["n_sel"], tile_slot=m["src_slot"])

@@ -28,7 +28,8 @@ import numpy as np
 import torch
 
 from . import native
-from .pipeline import SourceFrames
+from .pipeline import SourceFrames, _no_tiles
+from .tiles import TiledFrames
 
 _POLICY = ("distance_threshold", "hit_counter_max", "initialization_delay", "period", "update_wait_sec", "ewma_weight")
 
@@ -268,7 +269,7 @@ class TrackedPipeline:
         if p.quad_source == "obb":
             track_ids, due_idx, n_due_dev = trk.update(quads, sof, now, state=cropped.card_state)
         else:
-            track_ids, due_idx, n_due_dev = trk.update(quads, sof, now, n_det=det["n_det"])
+            track_ids, due_idx, n_due_dev = trk.update(quads, sof, now, n_det=det["n_det"] if cropped.n_sel is None else cropped.n_sel)
         n_due = int(n_due_dev.item())  # the step's only synchronisation
         self.last_z = None
         if n_due > 0:
@@ -297,6 +298,10 @@ class TrackedPipeline:
 
     def _detect_crop(self, frames_u8, sof, flip_rgb):
         """-> (det, Cropped without thumbnails, SourceFrames or None, the number of frames)"""
+        if isinstance(frames_u8, TiledFrames):  # its cards are camera pixels, like a SourceFrames': the tracker sees quads_src
+            assert sof.size == frames_u8.n_frames, f"{sof.size} streams named for {frames_u8.n_frames} frames"
+            det, cropped = self.pipeline.detect_crop_tiled(frames_u8, flip_rgb)
+            return det, cropped, frames_u8, frames_u8.n_frames
         det, frames_u8, src = self._detect(frames_u8, sof, flip_rgb)
         return det, self.pipeline.crop(frames_u8, det, src=src), src, frames_u8.shape[0]
 
@@ -307,7 +312,7 @@ class TrackedPipeline:
         if p.quad_source == "obb":
             track_ids, due_idx, n_due = trk.update(quads, sof, now, state=cropped.card_state)
         else:
-            track_ids, due_idx, n_due = trk.update(quads, sof, now, n_det=det["n_det"])
+            track_ids, due_idx, n_due = trk.update(quads, sof, now, n_det=det["n_det"] if cropped.n_sel is None else cropped.n_sel)
         z = p.encoder.encode(trk.gather(cropped.crops, pad=True))
         return track_ids, due_idx, n_due, trk.n_deferred, z, trk.commit(z)
 
@@ -341,7 +346,7 @@ class TrackedPipeline:
         MTGV_CROP_STAGE=enc moves the crop stage (and the thumbnails) in front of the update on the embed stream, as it
         does in `Pipeline.run_many`; then only the detector overlaps."""
         assert self.embed_budget is not None, "TrackedPipeline.run_many needs an embed_budget: without one every step reads n_due back"
-        steps = list(steps)
+        steps = list(_no_tiles(steps, "TrackedPipeline.run_many"))
         p = self.pipeline
         if not p.overlap_enabled():
             return [self.run(frames, sof, now, flip_rgb) for frames, sof, now in steps]
