@@ -189,6 +189,17 @@ MTGV_API int mtgv_bank_topk_ex(mtgv_bank* h, const float* q_dev, int32_t b, int3
  * is not counted (version 115; before, each took the scan of the whole bank and counted).  MTGV_MATCH_PREPASS=0 keeps to the
  * one-pass exact kernel. */
 MTGV_API int mtgv_bank_prepass_fallbacks(const mtgv_bank* h, int64_t* count);
+/* TEST SURFACE (version 118): the first pass of the two-pass match on its own - the queries' normalisation, their fp16
+ * copy and the fp16 x fp16 launch that mtgv_bank_topk runs before the re-rank, same functions and arguments - with the
+ * candidates in caller buffers.  cand_scores_dev / cand_cols_dev: [b][slots][per_range] float32 / int32 on the device;
+ * range w covers the bank rows [w * range_cols, (w + 1) * range_cols) and reports its per_range best approximate scores
+ * (score desc, row asc) with their rows; a range with fewer rows pads with (-inf, -1).  mtgv_bank_prepass_layout gives
+ * slots, range_cols and per_range for the bank's current size (pure arithmetic, any bank).  Where mtgv_bank_topk would
+ * not run the first pass whatever k is - F32 mode, b < 128, dim % 64 != 0, fewer than 4096 rows, no fp16 copy -
+ * mtgv_bank_prepass_candidates returns status 1 with a message and writes nothing.  MTGV_MATCH_PREPASS plays no part. */
+MTGV_API int mtgv_bank_prepass_layout(const mtgv_bank* h, int32_t* slots, int32_t* range_cols, int32_t* per_range);
+MTGV_API int mtgv_bank_prepass_candidates(mtgv_bank* h, const float* q_dev, int32_t b, float* cand_scores_dev, int32_t* cand_cols_dev,
+                                          int32_t* slots, int32_t* range_cols, void* stream);
 /* merge ncand (score,id) candidates per query into the top k (multi-GPU shard merge); same threshold rule */
 MTGV_API int mtgv_topk_merge(float* cand_scores_dev, const int64_t* cand_ids_dev, int32_t b, int32_t ncand, int32_t k,
                              float score_threshold, int64_t* ids_dev, float* scores_dev, void* stream);

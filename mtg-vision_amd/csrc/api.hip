@@ -110,7 +110,8 @@ MTGV_API const char* mtgv_last_error(void) { return last_error_cstr(); }
 // 115: the embed budget (mtgv_tracker_create_budget, mtgv_tracker_update_budget, mtgv_tracker_gather_u8_pad, mtgv_op_track_select)
 // 116: mtgv_op_mask_logits (the detector's mask stage as a single op)
 // 117: mtgv_letterbox_tiles_u8, mtgv_tiles_merge (tiled detection: the cut and the merge)
-MTGV_API int mtgv_version(void) { return 117; }
+// 118: mtgv_bank_prepass_layout, mtgv_bank_prepass_candidates (test surface: the two-pass match's first pass on its own)
+MTGV_API int mtgv_version(void) { return 118; }
 MTGV_API int mtgv_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;
@@ -300,6 +301,24 @@ MTGV_API int mtgv_bank_prepass_fallbacks(const mtgv_bank* h, int64_t* count) {
   return guarded([&] {
     MTGV_CHECK(h != nullptr && count != nullptr, ERR_INVALID, "null argument");
     *count = h->impl.prepass_fallbacks();
+  });
+}
+MTGV_API int mtgv_bank_prepass_layout(const mtgv_bank* h, int32_t* slots, int32_t* range_cols, int32_t* per_range) {
+  return guarded([&] {
+    MTGV_CHECK(h != nullptr && slots != nullptr && range_cols != nullptr && per_range != nullptr, ERR_INVALID, "null argument");
+    int sl = 0, rc = 0, kp = 0;
+    h->impl.prepass_layout(&sl, &rc, &kp);
+    *slots = sl, *range_cols = rc, *per_range = kp;
+  });
+}
+MTGV_API int mtgv_bank_prepass_candidates(mtgv_bank* h, const float* q_dev, int32_t b, float* cand_scores_dev, int32_t* cand_cols_dev,
+                                          int32_t* slots, int32_t* range_cols, void* stream) {
+  return guarded([&] {
+    MTGV_CHECK(h != nullptr, ERR_INVALID, "null handle");
+    int sl = 0, rc = 0;
+    h->impl.prepass_candidates(q_dev, b, cand_scores_dev, cand_cols_dev, &sl, &rc, (hipStream_t)stream);
+    if (slots != nullptr) *slots = sl;
+    if (range_cols != nullptr) *range_cols = rc;
   });
 }
 MTGV_API int mtgv_topk_merge(float* cand_scores_dev, const int64_t* cand_ids_dev, int32_t b, int32_t ncand, int32_t k,

@@ -36,6 +36,12 @@ class Bank {
   // queries of two-pass matches so far whose answer the first pass could not prove and that were scanned exactly
   // (synchronises the device)
   int64_t prepass_fallbacks() const;
+  // Test surface of the two-pass match's first pass: the candidates it hands the re-rank, cand_s / cand_i as
+  // [b][slots][per_range] in the caller's device buffers; range w covers columns [w * range_cols, (w + 1) * range_cols).
+  // prepass_layout sizes the buffers for the bank's current size; prepass_candidates throws (ERR_INVALID) before writing
+  // anything when topk would not run the first pass on this bank and batch.
+  void prepass_layout(int* slots, int* range_cols, int* per_range) const;
+  void prepass_candidates(const float* q, int b, float* cand_s, int* cand_i, int* slots, int* range_cols, hipStream_t s);
 
  private:
   // two-pass match (match.hip): approximate fp16 scores over a hi-only copy of the bank, exact re-rank of the candidates

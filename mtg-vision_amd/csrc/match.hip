@@ -479,6 +479,33 @@ bool Bank::prepass_ok(int b, int k) const {
   return on && gemm_sp_active() && b >= 128 && k <= 4 && dim_ % 64 == 0 && size_ >= 4096 && hi_.p != nullptr;
 }
 
+void Bank::prepass_layout(int* slots, int* range_cols, int* per_range) const {
+  *slots = gemm_sp_topk_hi16_slots((int)size_);
+  *range_cols = gemm_sp_topk_hi16_range_cols();
+  *per_range = PRE_KP;
+}
+
+// TEST SURFACE: what topk_prepass runs before the re-rank - the same launches with the same arguments - with the candidates
+// in the caller's buffers instead of the bank's (not recorded by the launch profiler: topk_prepass's record stands for the
+// match).  Refuses, before anything is written, a bank or batch that topk would not give to the first pass.
+void Bank::prepass_candidates(const float* q, int b, float* cand_s, int* cand_i, int* slots, int* range_cols, hipStream_t s) {
+  MTGV_CHECK(b > 0 && q != nullptr && cand_s != nullptr && cand_i != nullptr, ERR_INVALID, "bank: prepass_candidates b=%d or a null tensor", b);
+  MTGV_CHECK(gemm_sp_active() && b >= 128 && dim_ % 64 == 0 && size_ >= 4096 && hi_.p != nullptr, ERR_INVALID,
+             "bank: no fp16 first pass here (f16x3 mode %d, b=%d >= 128, dim=%d %% 64 == 0, size=%lld >= 4096, fp16 copy %d)",
+             gemm_sp_active() ? 1 : 0, b, dim_, (long long)size_, hi_.p != nullptr ? 1 : 0);
+  const int N = (int)size_;
+  qn_.ensure((size_t)b * dim_);
+  qhi_.ensure((size_t)b * dim_ / 2 + 8);
+  l2norm_rows_launch(q, qn_.p, b, dim_, s);
+  f32_to_f16_rows_launch(qn_.p, nullptr, reinterpret_cast<_Float16*>(qhi_.p), (long)b, dim_, s);
+  const float* wsc = nullptr;
+  MTGV_CHECK(operand_sp8(vecs_.p, dim_, nullptr, &wsc), ERR_RUNTIME, "bank: row scales missing");
+  int sl = 0;
+  gemm_sp_topk_hi16_launch(qhi_.p, hi_.p, wsc, b, N, dim_, PRE_KP, cand_s, cand_i, &sl, s);
+  if (slots != nullptr) *slots = sl;
+  if (range_cols != nullptr) *range_cols = gemm_sp_topk_hi16_range_cols();
+}
+
 void Bank::topk_prepass(const float* q, int b, int k, int64_t id_base, float thr, int64_t* ids, float* scores, hipStream_t s) {
   const int N = (int)size_;
   const int slots = gemm_sp_topk_hi16_slots(N);

@@ -188,6 +188,27 @@ class Matcher:
         native.check(native.lib().mtgv_bank_prepass_fallbacks(self._h, C.byref(v)))
         return int(v.value)
 
+    def prepass_candidates(self, q: torch.Tensor, out: Optional[Tuple[torch.Tensor, torch.Tensor]] = None):
+        """TEST SURFACE, not part of the match API: the first pass of the two-pass match on its own
+        (mtgv_bank_prepass_candidates).  q (B, D) float32 on the device -> (scores float32 (B, slots, per_range), rows int32
+        of the same shape, range_cols): per 96-row range of the bank its best approximate (fp16 x fp16) scores, pads
+        (-inf, -1).  `out`: flat buffers to write into instead of fresh ones (at least B * slots * per_range elements);
+        a refused call (AssertionError: the bank or batch never takes the first pass) leaves them untouched."""
+        assert q.is_cuda and q.dtype == torch.float32 and q.ndim == 2 and q.shape[1] == self.dim and q.is_contiguous(), f"{tuple(q.shape)} {q.dtype}"
+        b = q.shape[0]
+        slots, cols, kp = native.c_i32(0), native.c_i32(0), native.c_i32(0)
+        native.check(native.lib().mtgv_bank_prepass_layout(self._h, C.byref(slots), C.byref(cols), C.byref(kp)))
+        n = b * slots.value * kp.value
+        if out is None:
+            out = (torch.empty(n, dtype=torch.float32, device=self.device), torch.empty(n, dtype=torch.int32, device=self.device))
+        cs, ci = out
+        assert cs.dtype == torch.float32 and ci.dtype == torch.int32 and cs.numel() >= n and ci.numel() >= n
+        with torch.cuda.device(self.device):
+            native.check(native.lib().mtgv_bank_prepass_candidates(self._h, native.ptr(q), b, native.ptr(cs), native.ptr(ci), C.byref(slots),
+                                                                   C.byref(cols), native.stream()))
+        shape = (b, slots.value, kp.value)
+        return cs[:n].view(shape), ci[:n].view(shape), cols.value
+
     def __del__(self):
         try:
             if getattr(self, "_h", None) and self._h.value:

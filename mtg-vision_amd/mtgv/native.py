@@ -164,6 +164,8 @@ SIGNATURES = {
     "mtgv_bank_get_labels": (C.c_int, [c_vp, c_i64, c_i64, c_vp, c_vp]),
     "mtgv_bank_topk_ex": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i64, c_f32, c_vp, c_i32, c_vp, c_vp, c_vp]),
     "mtgv_bank_prepass_fallbacks": (C.c_int, [c_vp, C.POINTER(c_i64)]),
+    "mtgv_bank_prepass_layout": (C.c_int, [c_vp, C.POINTER(c_i32), C.POINTER(c_i32), C.POINTER(c_i32)]),  # mtgv_version >= 118
+    "mtgv_bank_prepass_candidates": (C.c_int, [c_vp, c_vp, c_i32, c_vp, c_vp, C.POINTER(c_i32), C.POINTER(c_i32), c_vp]),
     "mtgv_topk_merge": (C.c_int, [c_vp, c_vp, c_i32, c_i32, c_i32, c_f32, c_vp, c_vp, c_vp]),
     "mtgv_detector_create": (C.c_int, [C.POINTER(DetectorCfg), C.POINTER(c_vp)]),
     "mtgv_detector_destroy": (None, [c_vp]),

@@ -41,8 +41,9 @@ def test_ctypes_table_matches_header(libpath):
 
     assert sorted(native.SIGNATURES) == _declared()
     L = native.lib()
-    assert L.mtgv_version() >= 116  # the newest entry of the table: mtgv_op_mask_logits
+    assert L.mtgv_version() >= 118  # the newest entries of the table: mtgv_bank_prepass_layout / _candidates
     assert "mtgv_op_mask_logits" in native.SIGNATURES and len(native.SIGNATURES["mtgv_op_mask_logits"][1]) == 14
+    assert len(native.SIGNATURES["mtgv_bank_prepass_candidates"][1]) == 8 and len(native.SIGNATURES["mtgv_bank_prepass_layout"][1]) == 4
     assert L.mtgv_device_count() >= 0
 
 
