@@ -41,7 +41,8 @@ MTGV_API const char* mtgv_last_error(void);
  * 115: the embed budget of the tracker (mtgv_tracker_create_budget, mtgv_tracker_update_budget, mtgv_tracker_gather_u8_pad,
  *      mtgv_op_track_select)
  * 116: mtgv_op_mask_logits (the detector's mask stage as a single op)
- * 117: mtgv_letterbox_tiles_u8, mtgv_tiles_merge (detection on overlapping windows of large source frames) */
+ * 117: mtgv_letterbox_tiles_u8, mtgv_tiles_merge (detection on overlapping windows of large source frames)
+ * 119: mtgv_tiles_merge_obb, mtgv_op_quad_inter (the same for OBB detectors: oriented quads merged across windows) */
 MTGV_API int mtgv_version(void);
 /* number of HIP devices visible; does not initialise a device context */
 MTGV_API int mtgv_device_count(void);
@@ -548,6 +549,36 @@ MTGV_API int mtgv_tiles_merge(const int32_t* n_det_dev, const float* boxes_dev, 
                               const int32_t* tile_start_dev, const int32_t* hw_dev, int32_t frames, int32_t max_tiles_per_frame,
                               const float* pad_frac_dev, int32_t k, float edge, float ios_thr, float* sel_boxes_src_dev, float* quads_src_dev,
                               int32_t* frame_idx_dev, float* sel_conf_dev, int32_t* src_slot_dev, int32_t* n_sel_dev, void* stream);
+/* Tiled detection, the rotated merge (mtgv_version >= 119): the same for an OBB detector's oriented quads (DESIGN.md section 4,
+ * "Tiled detection"; mtgv/tiles.py: merge_tiles_obb_host and quad_inter_host are the rule in numpy, matched bit for bit).
+ * n_det_dev (nt), conf_dev, cls_dev (nt, max_det): mtgv_detector_forward's outputs with the tiles as frames; quads_dev
+ * (nt * kt, 4, 2), state_dev (nt * kt): mtgv_obb_cards' outputs for them with k = kt.  The tables as for mtgv_tiles_merge.
+ *   candidates  slot j < kt of tile t iff state[t * kt + j] is 1 or 2 and the tile has a j-th detection of class card_cls
+ *               among its first min(max(n_det[t], 0), max_det); its confidence is that detection's
+ *   mapping     every corner as in mtgv_tiles_merge; bounds = min / max of the mapped corners (float32 comparisons)
+ *   cut rule    mtgv_tiles_merge's, on those bounds
+ *   order       conf descending, tile ascending, j ascending
+ *   greedy      b is dropped by an earlier kept a if inter > ios_thr * min(area_a, area_b) (float32, strict): area = half the
+ *               absolute shoelace sum, inter = the area of intersection of the two convex quads, both with coordinates
+ *               relative to a's corner 0; inter = 0 where the bounds do not overlap; a quad of zero area neither drops nor is
+ *               dropped.  inter sums cross(p', q') over the parts of a's edges inside b (closed; an edge along an edge of b
+ *               counts iff both run the same way) and of b's edges inside a (open), halved and clamped at 0
+ *   orientation a kept a of state 1 takes the first candidate of the order that it dropped and that has state 2 as donor:
+ *               u = (TL + TR) - (BR + BL), d = ua.x * ub.x + ua.y * ub.y; d != 0: state 2, oriented_by = the donor's slot;
+ *               d < 0: a's corners are rolled by two
+ *   slots       as for mtgv_tiles_merge; sel_boxes_src = the quad's bounds; a pad has state 0, oriented_by -1
+ * Writes mtgv_tiles_merge's outputs plus state_out_dev and oriented_by_dev (frames * k) int32.  The same caps and the same
+ * distrust of tile_start; a state outside {1, 2} is no candidate. */
+MTGV_API int mtgv_tiles_merge_obb(const int32_t* n_det_dev, const float* conf_dev, const int32_t* cls_dev, const float* quads_dev,
+                                  const int32_t* state_dev, int32_t nt, int32_t max_det, int32_t kt, const int32_t* tiles_dev,
+                                  const int32_t* geo_dev, const double* ratio_dev, const int32_t* tile_start_dev, const int32_t* hw_dev,
+                                  int32_t frames, int32_t max_tiles_per_frame, const float* pad_frac_dev, int32_t k, float edge, float ios_thr,
+                                  int32_t card_cls, float* sel_boxes_src_dev, float* quads_src_dev, int32_t* frame_idx_dev, float* sel_conf_dev,
+                                  int32_t* src_slot_dev, int32_t* n_sel_dev, int32_t* state_out_dev, int32_t* oriented_by_dev, void* stream);
+/* test surface (mtgv_version >= 119): the pair function of mtgv_tiles_merge_obb on m pairs of quads a_dev, b_dev (m, 4, 2)
+ * -> inter_dev, area_a_dev, area_b_dev (m) float32; the same device functions (mtgv/tiles.py: quad_inter_host) */
+MTGV_API int mtgv_op_quad_inter(const float* a_dev, const float* b_dev, int64_t m, float* inter_dev, float* area_a_dev, float* area_b_dev,
+                                void* stream);
 /* fills the pad of n letterboxed (size, size, 3) uint8 frames with pad_value: every pixel outside the (nh, nw) rectangle
  * at (top, left), which someone else writes (mtgv.jpeg.JpegDecoder.decode_frames decodes a frame that already fits
  * straight into it) */

@@ -111,7 +111,8 @@ MTGV_API const char* mtgv_last_error(void) { return last_error_cstr(); }
 // 116: mtgv_op_mask_logits (the detector's mask stage as a single op)
 // 117: mtgv_letterbox_tiles_u8, mtgv_tiles_merge (tiled detection: the cut and the merge)
 // 118: mtgv_bank_prepass_layout, mtgv_bank_prepass_candidates (test surface: the two-pass match's first pass on its own)
-MTGV_API int mtgv_version(void) { return 118; }
+// 119: mtgv_tiles_merge_obb, mtgv_op_quad_inter (tiled detection for OBB detectors: the rotated merge and its pair function)
+MTGV_API int mtgv_version(void) { return 119; }
 MTGV_API int mtgv_device_count(void) {
   int n = 0;
   if (hipGetDeviceCount(&n) != hipSuccess) return 0;

@@ -13,17 +13,16 @@
 //      inter > ios_thr * min(area) (float32, no division, strict).  One ballot per wave and kept box; at most K rounds.
 //   5. slot k < n_sel is the k-th kept candidate, the others are pad boxes.  No atomic decides a position.
 //
-// Every loop bound is known before its loop and every barrier is reached by all 1024 threads.
+// Every loop bound is known before its loop and every barrier is reached by all 1024 threads.  The mapping, the cut rule, the
+// key, the sort and the greedy pass are tiles_merge.h's, shared with the rotated merge (tiles_obb.hip).
 // No FMA contraction anywhere in this file: merge_tiles_host evaluates the same single operations.
 #include "common.h"
 #include "mtgv.h"
+#include "tiles_merge.h"
 
 #pragma clang fp contract(off)
 
 namespace mtgv {
-
-static constexpr int TILES_THREADS = 1024;  // = the cap on candidates per frame
-static constexpr int TILES_MAX_K = 64;
 
 struct TilesMergeArgs {
   const int* n_det;     // (nt)
@@ -46,30 +45,16 @@ struct TilesMergeArgs {
   int* n_sel;        // (frames)
 };
 
-// one coordinate of the detector's input -> camera pixels: float64, clipped to the window (comparisons, not fmin / fmax: a
-// NaN stays one, as under np.where), rounded to float32
-__device__ __forceinline__ float tile_to_src(float v, double pad, double ratio, double origin, double extent) {
-  double s = ((double)v - pad) / ratio + origin;
-  const double hi = origin + extent;
-  s = s < origin ? origin : (s > hi ? hi : s);
-  return (float)s;
-}
-
-__device__ __forceinline__ float min_f(float a, float b) { return a < b ? a : b; }
-__device__ __forceinline__ float max_f(float a, float b) { return a > b ? a : b; }
-
 __global__ __launch_bounds__(TILES_THREADS) void tiles_merge_kernel(const TilesMergeArgs a) {
   __shared__ __attribute__((aligned(16))) unsigned long long keys[TILES_THREADS];  // 8 KiB
   __shared__ __attribute__((aligned(16))) float box[TILES_THREADS * 4];            // 16 KiB, by candidate index c
-  __shared__ unsigned long long s_alive[2][TILES_THREADS / 64];                   // the waves' ballots, double-buffered
+  __shared__ unsigned long long s_alive[2][TILES_WAVES];                          // the waves' ballots, double-buffered
   __shared__ int s_keep[TILES_MAX_K];
-  const int f = blockIdx.x, tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+  const int f = blockIdx.x, tid = threadIdx.x;
   const int K = a.k, Kt = a.kt;
   const int fh = a.hw[f * 2], fw = a.hw[f * 2 + 1];
-
-  // the frame's tiles; tile_start is trusted no further than max_tiles: a longer, negative or outlying range has no candidates
-  int ts = a.tile_start[f], te = a.tile_start[f + 1];
-  if (ts < 0 || te < ts || te > a.nt || te - ts > a.max_tiles) te = ts = 0;
+  int ts, te;
+  tiles_range(a.tile_start, f, a.nt, a.max_tiles, ts, te);
   const int ncand = (te - ts) * Kt;  // <= 1024: the launcher checked max_tiles * kt
 
   // 1. - 3. this thread's candidate
@@ -85,74 +70,30 @@ __global__ __launch_bounds__(TILES_THREADS) void tiles_merge_kernel(const TilesM
       const float bx0 = tile_to_src(b[0], left, r, (double)x0, (double)ww), by0 = tile_to_src(b[1], top, r, (double)y0, (double)wh);
       const float bx1 = tile_to_src(b[2], left, r, (double)x0, (double)ww), by1 = tile_to_src(b[3], top, r, (double)y0, (double)wh);
       box[tid * 4 + 0] = bx0, box[tid * 4 + 1] = by0, box[tid * 4 + 2] = bx1, box[tid * 4 + 3] = by1;
-      const float e = a.edge;
-      const bool cut = (x0 > 0 && bx0 < (float)x0 + e) || (x0 + ww < fw && bx1 > (float)(x0 + ww) - e) ||
-                       (y0 > 0 && by0 < (float)y0 + e) || (y0 + wh < fh && by1 > (float)(y0 + wh) - e);
-      if (!cut) {
-        const unsigned u = __float_as_uint(a.conf[(long)t * a.max_det + j]);
-        const unsigned ord = (u & 0x80000000u) ? ~u : (u | 0x80000000u);  // order-preserving; a finite conf >= 0 gives ord >= 2^31
-        key = ((unsigned long long)ord << 32) | (unsigned)(~(unsigned)tid);
-      }
+      if (!tiles_cut(bx0, by0, bx1, by1, x0, y0, ww, wh, fw, fh, a.edge)) key = tiles_key(a.conf[(long)t * a.max_det + j], tid);
     }
   }
-  keys[tid] = key;
-  int n2 = 1;
-  while (n2 < ncand) n2 <<= 1;  // block-uniform, <= 1024
-  __syncthreads();
-
-  // 3. bitonic sort of keys[0, n2), descending: the absent ones (0) end up behind the survivors
-  for (int k = 2; k <= n2; k <<= 1) {
-    for (int j = k >> 1; j > 0; j >>= 1) {
-      const int l = tid ^ j;
-      if (tid < n2 && l > tid) {
-        const unsigned long long x = keys[tid], y = keys[l];
-        const bool desc = (tid & k) == 0;
-        if (desc ? (x < y) : (x > y)) keys[tid] = y, keys[l] = x;
-      }
-      __syncthreads();
-    }
-  }
+  const int n2 = tiles_sort(keys, key, ncand);
 
   // 4. greedy suppression: thread i owns the i-th candidate of the order
   const unsigned long long mykey = keys[tid];
-  bool alive = tid < n2 && mykey != 0ull;
-  const int c = (int)(~(unsigned)(mykey & 0xffffffffull)) & (TILES_THREADS - 1);
+  const bool alive = tid < n2 && mykey != 0ull;
+  const int c = tiles_cand(mykey);
   float mx0 = 0.f, my0 = 0.f, mx1 = 0.f, my1 = 0.f, marea = 0.f;
   if (alive) {
     mx0 = box[c * 4], my0 = box[c * 4 + 1], mx1 = box[c * 4 + 2], my1 = box[c * 4 + 3];
     marea = (mx1 - mx0) * (my1 - my0);
   }
-  const int rounds = K < ncand ? K : ncand;  // a round keeps one box or ends the pass
-  int nk = 0;
-  bool open = true;  // block-uniform
-  for (int it = 0; it < rounds; ++it) {
-    const unsigned long long m = __ballot(alive);
-    if (lane == 0) s_alive[it & 1][wave] = m;
-    __syncthreads();  // (the other buffer was last read one round ago, in front of this barrier's predecessor)
-    int p = -1;
-    if (open) {
-#pragma unroll
-      for (int w = TILES_THREADS / 64 - 1; w >= 0; --w) {
-        const unsigned long long mw = s_alive[it & 1][w];
-        if (mw != 0ull) p = (w << 6) + __builtin_ctzll(mw);
-      }
-    }
-    if (p < 0) {
-      open = false;  // nobody is alive: the remaining rounds only keep the barriers in step
-    } else {
-      const int pc = (int)(~(unsigned)(keys[p] & 0xffffffffull)) & (TILES_THREADS - 1);
-      const float ax0 = box[pc * 4], ay0 = box[pc * 4 + 1], ax1 = box[pc * 4 + 2], ay1 = box[pc * 4 + 3];
-      if (tid == p) s_keep[nk] = p, alive = false;
-      nk += 1;
-      if (alive && tid > p) {
+  const int nk = tiles_greedy(
+      keys, s_alive, s_keep, alive, K < ncand ? K : ncand,  // a round keeps one box or ends the pass
+      [&](int pc) {
+        const float ax0 = box[pc * 4], ay0 = box[pc * 4 + 1], ax1 = box[pc * 4 + 2], ay1 = box[pc * 4 + 3];
         const float aarea = (ax1 - ax0) * (ay1 - ay0);
         const float iw = max_f(0.f, min_f(ax1, mx1) - max_f(ax0, mx0)), ih = max_f(0.f, min_f(ay1, my1) - max_f(ay0, my0));
         const float inter = iw * ih;
-        if (inter > a.ios_thr * min_f(aarea, marea)) alive = false;
-      }
-    }
-  }
-  __syncthreads();  // s_keep is complete
+        return inter > a.ios_thr * min_f(aarea, marea);
+      },
+      [](int, bool) {});
 
   // 5. the frame's K slots
   if (tid == 0) a.n_sel[f] = nk;
@@ -161,7 +102,7 @@ __global__ __launch_bounds__(TILES_THREADS) void tiles_merge_kernel(const TilesM
     float q[8], x0, y0, x1, y1, cf = 0.f;
     int slot = -1;
     if (tid < nk) {
-      const int cc = (int)(~(unsigned)(keys[s_keep[tid]] & 0xffffffffull)) & (TILES_THREADS - 1);
+      const int cc = tiles_cand(keys[s_keep[tid]]);
       const int tl = cc / Kt, j = cc - tl * Kt, t = ts + tl;
       x0 = box[cc * 4], y0 = box[cc * 4 + 1], x1 = box[cc * 4 + 2], y1 = box[cc * 4 + 3];
       cf = a.conf[(long)t * a.max_det + j];

@@ -139,6 +139,12 @@ SIGNATURES = {
         [c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_f32, c_f32]
         + [c_vp] * 6 + [c_vp],
     ),
+    "mtgv_tiles_merge_obb": (  # mtgv_version >= 119
+        C.c_int,
+        [c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_i32, c_vp, c_vp, c_vp, c_vp, c_vp, c_i32, c_i32, c_vp, c_i32, c_f32, c_f32, c_i32]
+        + [c_vp] * 8 + [c_vp],
+    ),
+    "mtgv_op_quad_inter": (C.c_int, [c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp]),  # mtgv_version >= 119
     "mtgv_profile_gemm": (C.c_int, [c_i32]),
     "mtgv_profile_gemm_read": (C.c_int, [C.POINTER(C.c_double), C.POINTER(C.c_double), C.POINTER(c_i64)]),
     "mtgv_profile_gemm_bytes": (C.c_int, [C.POINTER(C.c_double)]),

@@ -20,7 +20,7 @@ from .crop import mask_quads_from_logits, obb_cards, select_cards, warp_quads, w
 from .detector import Detector, fit_geometry
 from .encoder import Encoder
 from .matcher import Matcher
-from .tiles import TiledFrames, merge_tiles
+from .tiles import TiledFrames, merge_tiles, merge_tiles_obb
 
 # fixed quads (pixels of the 640x640 frame; scaled with a rectangular detector's input, Pipeline.__init__) used when a frame has fewer than K detections, so that
 # cards/sec is well defined on synthetic frames
@@ -229,7 +229,9 @@ class Pipeline:
         match_opts: keyword arguments handed to `matcher.match` (threshold, filter, distinct), like TrackedPipeline's;
         None keeps the call as it is.  `matcher` may be a `mtgv.ShardedMatcher` (the row-sharded bank).
         cards_per_tile, tile_merge: read only by `run(TiledFrames)` - the detections kept per tile (None: cards_per_frame) and
-        the merge rule's `edge` (pixels) and `ios` (mtgv.tiles.merge_tiles_host; None: edge 2.0, ios 0.5)."""
+        the merge rule's `edge` (pixels) and `ios` (mtgv.tiles.merge_tiles_host; None: edge 2.0, ios 0.5).  An "obb" pipeline
+        takes TiledFrames only with tile_merge={"rule": "rotated"} (mtgv.tiles.merge_tiles_obb_host: the overlap of two
+        oriented quads is the area of their intersection, and orientation is carried over from a dropped duplicate)."""
         assert quad_source in ("box", "mask", "obb"), quad_source
         task = getattr(getattr(detector, "cfg", None), "task", "seg")
         assert (quad_source == "obb") == (task == "obb"), f'quad_source "{quad_source}" with a {task} detector'
@@ -265,7 +267,10 @@ class Pipeline:
         self._warp_ws = None
         self.Kt = self.K if cards_per_tile is None else int(cards_per_tile)
         self.tile_merge = {"edge": 2.0, "ios": 0.5, **(tile_merge or {})}
-        assert set(self.tile_merge) == {"edge", "ios"}, f"tile_merge keys {sorted(self.tile_merge)}: expected edge, ios"
+        assert set(self.tile_merge) - {"rule"} == {"edge", "ios"}, f"tile_merge keys {sorted(self.tile_merge)}: expected edge, ios and optionally rule"
+        if "rule" in self.tile_merge:
+            assert self.tile_merge["rule"] == "rotated", f'tile_merge rule "{self.tile_merge["rule"]}": the only rule to choose is "rotated"'
+            assert quad_source == "obb", f'tile_merge rule "rotated" with quad_source "{quad_source}": it merges the quads of an "obb" pipeline'
         # the tiled path's pads: fractions of each frame's own size, and the per-tile pad of select_cards
         self._pad_frac = (_PAD_BOXES / 640.0).repeat(reps, 1)[: self.K].to(detector.device).contiguous()
         treps = (self.Kt + _PAD_BOXES.shape[0] - 1) // _PAD_BOXES.shape[0]
@@ -475,23 +480,38 @@ class Pipeline:
         were frames, in chunks of its max_batch (`det`: its outputs per tile, concatenated); the K best cards of every frame
         come out of mtgv_tiles_merge in camera pixels (mtgv.tiles.merge_tiles_host is the rule) and are de-warped from the
         source frames.  Output per frame: boxes (F, K, 4) and quads_src (F, K, 4, 2) in camera pixels, n_det = the merge's n_sel,
-        tile_slot (F, K) = tile * cards_per_tile + detection of every card (-1: a pad)."""
-        if self.quad_source == "obb":
-            raise NotImplementedError('quad_source "obb" does not take TiledFrames: merging rotated boxes needs a rotated overlap rule')
+        tile_slot (F, K) = tile * cards_per_tile + detection of every card (-1: a pad).  An "obb" pipeline with the rotated rule
+        runs crop.obb_cards per tile and mtgv_tiles_merge_obb instead (mtgv.tiles.merge_tiles_obb_host): its cards also carry
+        quads (= quads_src) and card_state, and tile_slot counts a tile's card slots."""
+        obb = self.quad_source == "obb"
+        if obb and self.tile_merge.get("rule") != "rotated":
+            raise NotImplementedError('quad_source "obb" takes TiledFrames only with the rotated overlap rule: Pipeline(..., tile_merge={"rule": "rotated"})')
         F, K, Kt = tf.n_frames, self.K, self.Kt
         nt, mb = int(tf.frames.shape[0]), self.detector.max_batch
         assert F > 0 and nt > 0, "a TiledFrames batch without frames"
         want_mask = self.quad_source == "mask"
         parts = [self.detector.forward(tf.frames[i : i + mb], flip_rgb, mask_rows=Kt if want_mask else 0) for i in range(0, nt, mb)]
         det = parts[0] if len(parts) == 1 else {k: (None if v is None else torch.cat([p[k] for p in parts])) for k, v in parts[0].items()}
+        if obb:
+            # the card slots of every tile, oriented where the tile saw a marker; the rotated rule merges them and carries
+            # the orientation of a dropped duplicate over to the one it keeps
+            quads, _, _, state = obb_cards(det["n_det"], det["rboxes"], det["conf"], det["cls"], self._pad_tile, Kt, 0, 1, 2)
+            m = merge_tiles_obb(tf, det["n_det"], det["conf"], det["cls"], quads, state, Kt, self._pad_frac, K, self.tile_merge["edge"],
+                                self.tile_merge["ios"], 0)
+            return det, self._warp_tiled(tf, m, m["state"])
         quads = None  # "box": the merge takes the boxes' corners itself
         if want_mask:
             sel, _, _ = select_cards(det["n_det"], det["boxes"], self._pad_tile, Kt, want_quads=False)
             ml = det["mask_logits"]
             quads, _ = mask_quads_from_logits(ml.view(nt * Kt, *ml.shape[-2:]), sel)
         m = merge_tiles(tf, det["n_det"], det["boxes"], det["conf"], quads, Kt, self._pad_frac, K, self.tile_merge["edge"], self.tile_merge["ios"])
+        return det, self._warp_tiled(tf, m)
+
+    def _warp_tiled(self, tf: TiledFrames, m: dict, state=None) -> Cropped:
+        """a merge's cards -> Cropped, de-warped from the source frames"""
+        F, K = tf.n_frames, self.K
         if self._warp_ws is None or self._warp_ws.numel() < 9 * F * K:
             self._warp_ws = warp_workspace(F * K, tf.buf.device)
         # the quads are camera pixels already: an identity geometry makes mtgv_warp_quads_src read them as they are
         crops, quads_src = crop.warp_quads_src(tf.sources(), m["quads_src"], m["frame_idx"], self.encoder.cfg.image_hw, 0.05, self._warp_ws)
-        return det, Cropped(m["sel_boxes_src"].view(F, K, 4), crops, quads_src, quads_src, n_sel=m["n_sel"], tile_slot=m["src_slot"])
+        return Cropped(m["sel_boxes_src"].view(F, K, 4), crops, quads_src, quads_src, card_state=state, n_sel=m["n_sel"], tile_slot=m["src_slot"])

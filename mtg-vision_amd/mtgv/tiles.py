@@ -5,7 +5,10 @@ near, native resolution (`tile_grid`, `TiledFrames`, csrc/resize.hip: mtgv_lette
 windows as if they were frames, and one kernel (csrc/tiles.hip: mtgv_tiles_merge) maps the detections back into camera
 pixels, drops the cards a window cut, removes the duplicates of the overlap and hands the K best per frame to the crop
 stage.  `Pipeline.run(TiledFrames)` is the caller.  The rule is this library's; `merge_tiles_host` states it in numpy - the
-specification the kernel is tested against, bit for bit; nothing on the GPU path calls it.
+specification the kernel is tested against, bit for bit; nothing on the GPU path calls it.  An OBB detector's oriented
+quads are merged by the rotated rule (csrc/tiles_obb.hip: mtgv_tiles_merge_obb; `merge_tiles_obb_host`, `quad_inter_host`):
+the overlap is the exact area of intersection of two convex quads, and a kept card takes its orientation from an oriented
+duplicate.  `Pipeline(..., quad_source="obb", tile_merge={"rule": "rotated"})` turns it on.
 """
 
 from __future__ import annotations
@@ -212,6 +215,55 @@ def merge_tiles(tf: TiledFrames, n_det: torch.Tensor, boxes: torch.Tensor, conf:
     return out
 
 
+MERGE_OBB_OUTPUTS = ("sel_boxes_src", "quads_src", "frame_idx", "sel_conf", "src_slot", "n_sel", "state", "oriented_by")
+
+
+def merge_tiles_obb(tf: TiledFrames, n_det: torch.Tensor, conf: torch.Tensor, cls: torch.Tensor, quads: torch.Tensor, state: torch.Tensor, kt: int,
+                    pad_frac: torch.Tensor, k: int, edge: float = 2.0, ios: float = 0.5, card_cls: int = 0,
+                    max_tiles_per_frame: Optional[int] = None) -> dict:
+    """mtgv_tiles_merge_obb: the per-tile outputs of an OBB detector (n_det (NT,), conf, cls (NT, max_det)) and of
+    crop.obb_cards on them with k = kt (quads (NT * kt, 4, 2), state (NT * kt,)) -> the k cards of every frame in camera
+    pixels: `merge_tiles`' dict plus state and oriented_by (F * k,) int32.  `merge_tiles_obb_host` is the rule."""
+    native.require_gpu()
+    F, nt, md = tf.n_frames, int(tf.tiles.shape[0]), int(conf.shape[1])
+    dev = conf.device
+    assert n_det.dtype == torch.int32 and conf.dtype == torch.float32 and cls.dtype == torch.int32 and pad_frac.dtype == torch.float32
+    assert tuple(n_det.shape) == (nt,) and tuple(conf.shape) == (nt, md) and tuple(cls.shape) == (nt, md) and tuple(pad_frac.shape) == (k, 4)
+    assert quads.dtype == torch.float32 and quads.numel() == nt * kt * 8, "quads: (NT * kt, 4, 2) float32"
+    assert state.dtype == torch.int32 and state.numel() == nt * kt, "state: (NT * kt,) int32"
+    out = {
+        "sel_boxes_src": torch.empty((F * k, 4), dtype=torch.float32, device=dev),
+        "quads_src": torch.empty((F * k, 4, 2), dtype=torch.float32, device=dev),
+        "frame_idx": torch.empty((F * k,), dtype=torch.int32, device=dev),
+        "sel_conf": torch.empty((F * k,), dtype=torch.float32, device=dev),
+        "src_slot": torch.empty((F * k,), dtype=torch.int32, device=dev),
+        "n_sel": torch.empty((F,), dtype=torch.int32, device=dev),
+        "state": torch.empty((F * k,), dtype=torch.int32, device=dev),
+        "oriented_by": torch.empty((F * k,), dtype=torch.int32, device=dev),
+    }
+    mt = tf.max_tiles_per_frame if max_tiles_per_frame is None else int(max_tiles_per_frame)
+    with torch.cuda.device(dev):
+        native.check(native.lib().mtgv_tiles_merge_obb(
+            native.ptr(n_det), native.ptr(conf.contiguous()), native.ptr(cls.contiguous()), native.ptr(quads.contiguous()), native.ptr(state.contiguous()),
+            nt, md, int(kt), native.ptr(tf.tiles), native.ptr(tf.geo), native.ptr(tf.ratio), native.ptr(tf.tile_start), native.ptr(tf.hw), F, mt,
+            native.ptr(pad_frac), int(k), float(edge), float(ios), int(card_cls), *(native.ptr(out[n]) for n in MERGE_OBB_OUTPUTS), native.stream()))
+    return out
+
+
+def quad_inter(a: torch.Tensor, b: torch.Tensor):
+    """mtgv_op_quad_inter: the rotated merge's pair function on m pairs of quads (m, 4, 2) float32 on the device ->
+    (inter, area_a, area_b), (m,) float32 each (`quad_inter_host` is the rule)"""
+    native.require_gpu()
+    assert a.is_cuda and a.dtype == torch.float32 and b.dtype == torch.float32 and a.shape == b.shape and tuple(a.shape[1:]) == (4, 2), \
+        f"{tuple(a.shape)} {tuple(b.shape)}"
+    m = int(a.shape[0])
+    inter, area_a, area_b = (torch.empty((m,), dtype=torch.float32, device=a.device) for _ in range(3))
+    with torch.cuda.device(a.device):
+        native.check(native.lib().mtgv_op_quad_inter(native.ptr(a.contiguous()), native.ptr(b.contiguous()), m, native.ptr(inter), native.ptr(area_a),
+                                                     native.ptr(area_b), native.stream()))
+    return inter, area_a, area_b
+
+
 def _to_src(v, pad, ratio, origin, extent):
     """float32 coordinates of a tile's detector input -> camera pixels: float64 (v - pad) / ratio + origin, clipped to
     [origin, origin + extent] by comparisons (a NaN stays one), rounded to float32"""
@@ -318,4 +370,196 @@ def merge_tiles_host(n_det, boxes, conf, quads, tiles, geo, ratio, tile_start, h
         for s in range(n_sel, k):
             pb = pad_frac[s] * np.array([w, h, w, h], np.float32)
             out["sel_boxes_src"][f * k + s], out["quads_src"][f * k + s] = pb, corners(pb)
+    return out
+
+
+# ---------------------------------------------------------------------------
+# the rotated rule: oriented quads of an OBB detector (csrc/tiles_obb.hip: mtgv_tiles_merge_obb)
+# ---------------------------------------------------------------------------
+_F0, _F1, _HALF = np.float32(0), np.float32(1), np.float32(0.5)
+
+
+def _min4(v):
+    """min of (n, 4) float32 by comparisons, (v0 ? v1) ? (v2 ? v3): a NaN behaves as under np.where"""
+    a, b = np.where(v[:, 0] < v[:, 1], v[:, 0], v[:, 1]), np.where(v[:, 2] < v[:, 3], v[:, 2], v[:, 3])
+    return np.where(a < b, a, b)
+
+
+def _max4(v):
+    a, b = np.where(v[:, 0] > v[:, 1], v[:, 0], v[:, 1]), np.where(v[:, 2] > v[:, 3], v[:, 2], v[:, 3])
+    return np.where(a > b, a, b)
+
+
+def quad_bounds(q) -> np.ndarray:
+    """(n, 4, 2) float32 quads -> (n, 4) bounds x0, y0, x1, y1"""
+    q = np.asarray(q, np.float32).reshape(-1, 4, 2)
+    return np.stack([_min4(q[:, :, 0]), _min4(q[:, :, 1]), _max4(q[:, :, 0]), _max4(q[:, :, 1])], 1)
+
+
+def _shoelace(x, y):
+    """the doubled signed area: s = 0, then s = s + (x_i * y_i+1 - x_i+1 * y_i) for i = 0 .. 3"""
+    s = np.zeros(x.shape[0], np.float32)
+    for i in range(4):
+        j = (i + 1) & 3
+        s = s + (x[:, i] * y[:, j] - x[:, j] * y[:, i])
+    return s
+
+
+def _edge_sum(px, py, qx, qy, sq, same, closed: bool):
+    """sum over P's four edges of cross(p', q'), p' -> q' being the part of the edge inside Q's four half-planes (sq: the sign
+    of Q's winding).  closed: a point on a boundary line is inside, and an edge that lies along an edge of Q counts iff the
+    two run the same way (same: the product of the two windings' signs); open: neither."""
+    n = px.shape[0]
+    ex = [qx[:, (k + 1) & 3] - qx[:, k] for k in range(4)]
+    ey = [qy[:, (k + 1) & 3] - qy[:, k] for k in range(4)]
+    d = [[sq * (ex[k] * (py[:, i] - qy[:, k]) - ey[k] * (px[:, i] - qx[:, k])) for i in range(4)] for k in range(4)]
+    tot = np.zeros(n, np.float32)
+    for e in range(4):
+        e1 = (e + 1) & 3
+        dx, dy = px[:, e1] - px[:, e], py[:, e1] - py[:, e]
+        t0, t1, ok = np.zeros(n, np.float32), np.ones(n, np.float32), np.ones(n, bool)
+        for k in range(4):
+            dp, dq = d[k][e], d[k][e1]
+            line = ~((ex[k] == _F0) & (ey[k] == _F0))  # a zero-length edge of Q bounds nothing
+            along = (dp == _F0) & (dq == _F0)
+            if closed:
+                inp, inq = dp >= _F0, dq >= _F0
+                along_out = along & ~(same * (dx * ex[k] + dy * ey[k]) > _F0)
+            else:
+                inp, inq = dp > _F0, dq > _F0
+                along_out = along
+            rest = line & ~along
+            ok &= ~(line & along_out) & ~(rest & ~inp & ~inq)
+            cross = rest & (inp != inq)
+            t = dp / (dp - dq)
+            t1 = np.where(cross & inp & (t < t1), t, t1)
+            t0 = np.where(cross & ~inp & (t > t0), t, t0)
+        x0, y0 = px[:, e] + t0 * dx, py[:, e] + t0 * dy
+        x1, y1 = px[:, e] + t1 * dx, py[:, e] + t1 * dy
+        tot = np.where(ok & (t0 < t1), tot + (x0 * y1 - x1 * y0), tot)
+    return tot
+
+
+def quad_inter_host(a, b):
+    """The pair function of the rotated merge on m pairs of quads (m, 4, 2) -> (inter, area_a, area_b), float32 (m,): what
+    mtgv_op_quad_inter computes, bit for bit.  Single rounded float32 operations in the order written.
+
+    All coordinates are first taken relative to a's corner 0 (one subtraction each).  area = |s| / 2 of the shoelace sum s.
+    inter = 0 where the bounds of the two quads (`quad_bounds` of the absolute corners) do not overlap - min(x1) - max(x0) > 0
+    and the same in y - or either s is 0.  Otherwise the boundary of the intersection of two convex quads is made of the
+    parts of a's edges inside b and the parts of b's edges inside a: with both windings made positive by their signs,
+    inter = max(0, (sign_a * sum_a + sign_b * sum_b) / 2), every sum being `_edge_sum`: an edge p -> q is cut to the
+    parameter interval [t0, t1] that lies inside the other quad's four half-planes (d = the signed distance numerators of p
+    and q, t = dp / (dp - dq) where they differ in side) and adds cross(p', q') of what is left.  a's edges are tested closed and
+    b's open, so a shared piece of boundary counts once; an edge of a that runs along an edge of b counts only where the two
+    run the same way (identical quads: the area; quads that touch from outside: 0)."""
+    a, b = np.asarray(a, np.float32).reshape(-1, 4, 2), np.asarray(b, np.float32).reshape(-1, 4, 2)
+    with np.errstate(all="ignore"):
+        ba, bb = quad_bounds(a), quad_bounds(b)
+        iw = np.where(ba[:, 2] < bb[:, 2], ba[:, 2], bb[:, 2]) - np.where(ba[:, 0] > bb[:, 0], ba[:, 0], bb[:, 0])
+        ih = np.where(ba[:, 3] < bb[:, 3], ba[:, 3], bb[:, 3]) - np.where(ba[:, 1] > bb[:, 1], ba[:, 1], bb[:, 1])
+        o = a[:, :1]
+        ra, rb = a - o, b - o
+        ax, ay, bx, by = ra[:, :, 0], ra[:, :, 1], rb[:, :, 0], rb[:, :, 1]
+        sa, sb = _shoelace(ax, ay), _shoelace(bx, by)
+        area_a, area_b = np.abs(sa) * _HALF, np.abs(sb) * _HALF
+        sga, sgb = np.where(sa > _F0, _F1, -_F1), np.where(sb > _F0, _F1, -_F1)
+        same = sga * sgb
+        s = (sga * _edge_sum(ax, ay, bx, by, sgb, same, True) + sgb * _edge_sum(bx, by, ax, ay, sga, same, False)) * _HALF
+        full = (iw > _F0) & (ih > _F0) & ~(sa == _F0) & ~(sb == _F0)
+        inter = np.where(full & (s > _F0), s, _F0)
+    return inter.astype(np.float32), area_a.astype(np.float32), area_b.astype(np.float32)
+
+
+def merge_tiles_obb_host(n_det, conf, cls, quads, state, tiles, geo, ratio, tile_start, hw, pad_frac, kt: int, k: int, edge: float = 2.0,
+                         ios: float = 0.5, card_cls: int = 0, max_tiles_per_frame: Optional[int] = None) -> dict:
+    """The rotated merge rule on the host (numpy arrays in and out): what mtgv_tiles_merge_obb computes, bit for bit.  The
+    inputs are what the untiled OBB path produces with the tiles as frames: n_det (NT,), conf, cls (NT, max_det) of
+    Detector.forward, quads (NT * kt, 4, 2) and state (NT * kt,) of crop.obb_cards(..., k=kt).
+
+    1. candidates: slot j < kt of tile t iff state[t * kt + j] is 1 or 2 and the tile has a j-th detection of class card_cls
+       among its first min(max(n_det[t], 0), max_det) (obb_cards' own scan); its confidence is that detection's.
+    2. mapping: every corner through `_to_src`; bounds = min / max of the mapped corners by float32 comparisons.
+    3. cut rule: rule 3 of `merge_tiles_host` on those bounds.
+    4. order: conf descending, tile ascending, j ascending (the same 64-bit key).
+    5. greedy: a later candidate b is dropped by a kept a if inter > ios * min(area_a, area_b) (`quad_inter_host`: float32,
+       strict, no division in the comparison); a quad of zero area neither drops nor is dropped.
+    6. orientation: a kept a of state 1 that dropped candidates of state 2 takes the first of them in the order as its donor:
+       with u = (TL + TR) - (BR + BL) of each and d = ua.x * ub.x + ua.y * ub.y, d != 0 makes a's state 2 and oriented_by the
+       donor's slot, d < 0 also rolls a's corners by two (TL, TR, BR, BL <- BR, BL, TL, TR).
+    7. the first k kept fill slots 0 .. n_sel - 1 (sel_boxes_src: the quad's bounds); slot >= n_sel is pad_frac[slot] *
+       (w, h, w, h) with its corners as quad, conf 0, state 0, src_slot -1, oriented_by -1.
+    Caps and distrust are `merge_tiles_host`'s."""
+    n_det, conf, cls = np.asarray(n_det, np.int32), np.asarray(conf, np.float32), np.asarray(cls, np.int32)
+    tiles, geo, ratio = np.asarray(tiles, np.int32).reshape(-1, 5), np.asarray(geo, np.int32).reshape(-1, 4), np.asarray(ratio, np.float64)
+    tile_start, hw, pad_frac = np.asarray(tile_start, np.int64), np.asarray(hw, np.int32).reshape(-1, 2), np.asarray(pad_frac, np.float32)
+    NT, F, kt, k, md = tiles.shape[0], hw.shape[0], int(kt), int(k), conf.shape[1]
+    quads, state = np.asarray(quads, np.float32).reshape(NT * kt, 4, 2), np.asarray(state, np.int32).reshape(NT * kt)
+    mt = int(np.diff(tile_start).max()) if max_tiles_per_frame is None and F else int(max_tiles_per_frame or 0)
+    assert 1 <= k <= MAX_CARDS and 1 <= kt <= md and mt * kt <= MAX_CANDIDATES, f"k={k} kt={kt} tiles per frame {mt}"
+    e32, thr = np.float32(edge), np.float32(ios)
+    out = {"sel_boxes_src": np.zeros((F * k, 4), np.float32), "quads_src": np.zeros((F * k, 4, 2), np.float32),
+           "frame_idx": np.repeat(np.arange(F, dtype=np.int32), k), "sel_conf": np.zeros((F * k,), np.float32),
+           "src_slot": np.full((F * k,), -1, np.int32), "n_sel": np.zeros((F,), np.int32), "state": np.zeros((F * k,), np.int32),
+           "oriented_by": np.full((F * k,), -1, np.int32)}
+    for f in range(F):
+        h, w = int(hw[f, 0]), int(hw[f, 1])
+        ts, te = int(tile_start[f]), int(tile_start[f + 1])
+        if ts < 0 or te < ts or te > NT or te - ts > mt:
+            ts = te = 0
+        cq, cc, cslot, cflat = [], [], [], []
+        for tl, t in enumerate(range(ts, te)):
+            _, y0, x0, wh, ww = (int(v) for v in tiles[t])
+            nd = min(max(int(n_det[t]), 0), md)
+            cards = np.flatnonzero(cls[t, :nd] == card_cls)
+            st = state[t * kt : (t + 1) * kt]
+            j = np.arange(kt)[((st == 1) | (st == 2)) & (np.arange(kt) < len(cards))]
+            if j.size == 0:
+                continue
+            q = quads[t * kt + j]
+            m = np.stack([_to_src(q[:, :, 0], geo[t, 3], ratio[t], x0, ww), _to_src(q[:, :, 1], geo[t, 2], ratio[t], y0, wh)], 2)
+            bd = quad_bounds(m)
+            cut = np.zeros((len(j),), bool)
+            if x0 > 0:
+                cut |= bd[:, 0] < np.float32(x0) + e32
+            if x0 + ww < w:
+                cut |= bd[:, 2] > np.float32(x0 + ww) - e32
+            if y0 > 0:
+                cut |= bd[:, 1] < np.float32(y0) + e32
+            if y0 + wh < h:
+                cut |= bd[:, 3] > np.float32(y0 + wh) - e32
+            j = j[~cut]
+            cq.append(m[~cut]), cc.append(conf[t, cards[j]]), cslot.append(t * kt + j), cflat.append(tl * kt + j)
+        n_sel = 0
+        if cq and sum(len(x) for x in cq):
+            cq, cc, cslot, cflat = np.concatenate(cq), np.concatenate(cc), np.concatenate(cslot), np.concatenate(cflat)
+            order = np.argsort(_order_key(cc, cflat))[::-1]  # the keys are unique
+            cq, cc, cslot = cq[order], cc[order], cslot[order]
+            cst = state[cslot]
+            alive = np.ones((len(cq),), bool)
+            while n_sel < k and alive.any():
+                p = int(np.argmax(alive))
+                alive[p] = False
+                inter, area_a, area_b = quad_inter_host(np.broadcast_to(cq[p], cq.shape), cq)
+                drop = alive & ~(area_a == _F0) & ~(area_b == _F0) & (inter > thr * np.where(area_a < area_b, area_a, area_b))
+                alive &= ~drop
+                o = f * k + n_sel
+                qa, sta, by = cq[p], int(cst[p]), -1
+                donors = np.flatnonzero(drop & (cst == 2))
+                if sta == 1 and donors.size:
+                    qb = cq[donors[0]]
+                    ua, ub = (qa[0] + qa[1]) - (qa[2] + qa[3]), (qb[0] + qb[1]) - (qb[2] + qb[3])
+                    d = ua[0] * ub[0] + ua[1] * ub[1]
+                    if d != _F0:
+                        sta, by = 2, int(cslot[donors[0]])
+                    if d < _F0:
+                        qa = qa[[2, 3, 0, 1]]
+                out["sel_boxes_src"][o], out["quads_src"][o], out["sel_conf"][o], out["src_slot"][o] = quad_bounds(cq[p])[0], qa, cc[p], cslot[p]
+                out["state"][o], out["oriented_by"][o] = sta, by
+                n_sel += 1
+        out["n_sel"][f] = n_sel
+        for s in range(n_sel, k):
+            pb = pad_frac[s] * np.array([w, h, w, h], np.float32)
+            out["sel_boxes_src"][f * k + s] = pb
+            out["quads_src"][f * k + s] = np.array([[pb[0], pb[1]], [pb[2], pb[1]], [pb[2], pb[3]], [pb[0], pb[3]]], np.float32)
     return out

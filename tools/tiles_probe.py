@@ -10,8 +10,12 @@ frame, Kt = 16 per tile, mask quads:
     the de-warp               mtgv_warp_quads_src with the identity geometry
     Pipeline.run(TiledFrames) the whole step, and Pipeline.run(SourceFrames) on the same four frames untiled for context
 
+The OBB leg (a YOLO11n-obb detector, tile_merge={"rule": "rotated"}) measures the same four frames: the per-tile mtgv_obb_cards
+launch, mtgv_tiles_merge_obb next to mtgv_tiles_merge on the same candidates (the card quads' bounds as boxes), the whole
+step and the untiled step.
+
 Every time is the median [p10, p90] of --runs calls after --warmup, HIP events around the calls (Python's launch overhead
-is inside).  --untiled-only measures the last line alone: the path that exists without this module.
+is inside).  --untiled-only measures the untiled lines alone: the paths that exist without this module.
 
     python tools/tiles_probe.py [--runs 50 --warmup 5 --out profiles/tiles_probe.txt]
 """
@@ -51,6 +55,59 @@ def median_ms(fn, runs, warmup):
 
 def fmt(t):
     return f"{t[0]:8.3f} [{t[1]:.3f}, {t[2]:.3f}]"
+
+
+def obb_leg(frames, a, out):
+    from mtgv import spec
+    from mtgv.detector import Detector
+    from mtgv.encoder import Encoder
+    from mtgv.matcher import Matcher
+    from mtgv.pipeline import Pipeline, SourceFrames
+
+    det_cfg = spec.yolo11_config(task="obb")
+    enc_cfg = spec.encoder_config("cnvnxt2ae_nano", (192, 128), "conv+linear")
+    m = Matcher(768, capacity=20000)
+    m.add(np.random.default_rng(2).standard_normal((20000, 768)).astype(np.float32))
+    pipe = Pipeline(Detector(det_cfg, spec.random_detector_state(det_cfg, 3, cls_bias=-0.9), max_batch=MAX_BATCH),
+                    Encoder(enc_cfg, spec.random_encoder_state(enc_cfg, 1), max_batch=F * K), m, K, 1, quad_source="obb",
+                    **({} if a.untiled_only else {"cards_per_tile": KT, "tile_merge": {"rule": "rotated"}}))
+    out.append(f"OBB leg: YOLO11n-obb, random weights (class bias -0.9), {K} cards per frame")
+    sf = SourceFrames.from_frames(frames, size=S)
+    t_u = median_ms(lambda: pipe.run(sf), a.runs, a.warmup)
+    out.append(f"Pipeline.run(SourceFrames), the four frames untiled:      {fmt(t_u)}")
+    if a.untiled_only:
+        return
+    from mtgv.crop import obb_cards
+    from mtgv.tiles import TiledFrames, merge_tiles, merge_tiles_obb
+
+    tf = TiledFrames.from_frames(frames, window_hw=(S, S), overlap=OVERLAP, with_full=True, size=S)
+    nt = int(tf.tiles.shape[0])
+    det = pipe.detector
+    parts = [det.forward(tf.frames[i : i + det.max_batch]) for i in range(0, nt, det.max_batch)]
+    d = parts[0] if len(parts) == 1 else {k: torch.cat([p[k] for p in parts]) for k in parts[0]}
+    t_fwd = median_ms(lambda: [det.forward(tf.frames[i : i + det.max_batch]) for i in range(0, nt, det.max_batch)], a.runs, a.warmup)
+    cards = lambda: obb_cards(d["n_det"], d["rboxes"], d["conf"], d["cls"], pipe._pad_tile, KT, 0, 1, 2)  # noqa: E731
+    q, sel, _, state = cards()
+    t_c = median_ms(cards, a.runs, a.warmup)
+    rot = lambda: merge_tiles_obb(tf, d["n_det"], d["conf"], d["cls"], q, state, KT, pipe._pad_frac, K, 2.0, 0.5, 0)  # noqa: E731
+    mo = rot()
+    t_r = median_ms(rot, a.runs, a.warmup)
+    # the axis-aligned merge on the same candidates: every tile's card slots as its detections (bounds as boxes, quads as quads)
+    n_card = (state.view(nt, KT) > 0).sum(1).to(torch.int32)
+    boxes, conf = sel.view(nt, KT, 4).contiguous(), torch.linspace(0.9, 0.3, KT, device="cuda").repeat(nt, 1).contiguous()
+    flat = lambda: merge_tiles(tf, n_card, boxes, conf, q, KT, pipe._pad_frac, K, 2.0, 0.5)  # noqa: E731
+    fo = flat()
+    t_f = median_ms(flat, a.runs, a.warmup)
+    t_run = median_ms(lambda: pipe.run(tf), a.runs, a.warmup)
+    out.append(f"card slots per tile {n_card.cpu().tolist()}")
+    out.append(f"n_sel per frame: rotated {mo['n_sel'].cpu().tolist()} (oriented by a duplicate: {int((mo['oriented_by'] >= 0).sum())}), "
+               f"axis-aligned on the bounds {fo['n_sel'].cpu().tolist()}")
+    out.append(f"the detector forward on the {nt} tiles:                    {fmt(t_fwd)}")
+    out.append(f"per-tile mtgv_obb_cards ({nt * KT} slots):                    {fmt(t_c)}")
+    out.append(f"mtgv_tiles_merge_obb, one workgroup per frame:            {fmt(t_r)}")
+    out.append(f"mtgv_tiles_merge on the same candidates:                  {fmt(t_f)}")
+    out.append(f"Pipeline.run(TiledFrames):                                {fmt(t_run)}")
+    out.append(f"rotated over axis-aligned merge: {t_r[0] / t_f[0]:.2f}")
 
 
 def main():
@@ -126,6 +183,7 @@ def main():
         out.append(f"Pipeline.run(TiledFrames):                                {fmt(t_run)}")
         out.append(f"TiledFrames.from_frames + Pipeline.run (tables, cut):     {fmt(t_all)}")
         out.append(f"cut + merge over the forward on the same tiles: {(t_cut[0] + t_m[0]) / t_fwd[0]:.3f}")
+    obb_leg(frames, a, out)
     text = "\n".join(out)
     print(text)
     if a.out:
